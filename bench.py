@@ -16,7 +16,14 @@ packed genomes already resident in HBM.  With N ranks the SAME matrix is filled 
 (static pair shard + one RCCL gather + device-side assembly on rank 0), so scaling is
 "strong".  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints that line (plus, with --dump-outputs DIR, the last
+step's matrix as .npy files: see dump_outputs).  Everything else it can measure or check -- the sampled oracle
+check, `roofline`, `cpu_baseline`, the wall time of one matrix with upload and D2H, the start-up cost of N ranks --
+runs only with --full:
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+Extra objects on a --full line:
   roofline      the dominant kernels (the K4 alignment launches of one fill, timed with HIP
                 events on the stream they run on, inside the library).  The recurrence is bound
                 by VALU issue: every instruction class of the DP cell (v_max_f64 included) retires
@@ -37,8 +44,8 @@ Extra objects on that line:
                 + kernels + D2H of the condensed vector (never `value`); `value_wall` = pairs / that.
   stage_ms      N = 1: plan / align / reduce of one fill (HIP events inside the library).  N > 1: per-rank
                 stages as max over ranks, the exchange (gather or reduce) and the root-only assembly as rank 0
-                sees them, `shards` (pairs / cells min-max over ranks), `config.dist_mode`.
-Exit status 1 (and "valid": false) when the sampled oracle check is not bit-exact.
+                sees them, `shards` (pairs / cells min-max over ranks), `config.dist_mode`.  (On every line.)
+Exit status 1 (and "valid": false) when the sampled oracle check (--full) is not bit-exact.
 """
 
 import argparse
@@ -59,12 +66,19 @@ def parse():
     ap.add_argument("--genomes", type=int, default=5000)
     ap.add_argument("--phams", type=int, default=5000)
     ap.add_argument("--metric", default="peq", choices=["gcs", "jc", "pocp", "af", "aai", "peq"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="lower bound of CPU-baseline work; 0 disables")
-    ap.add_argument("--verify-pairs", type=int, default=20000, help="check this many random pairs against the oracle")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: lower bound of CPU-baseline work; 0 disables")
+    ap.add_argument("--verify-pairs", type=int, default=20000, help="--full: check this many random pairs against the oracle")
     ap.add_argument("--route", default="rank", choices=["rank", "process"],
                     help="N > 1: 'rank' = one process per GPU, one RCCL gather (the measured contract); 'process' = this process drives "
                          "all N GPUs through pc_multi_* (peer copies)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: oracle check, roofline, CPU baseline, wall time with upload / D2H, "
+                         "N > 1 start-up cost")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's matrix under DIR as .npy (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(a):
@@ -219,6 +233,26 @@ def verify_sample(packed, metric, n_verify, fetch):
             "parity": parity_note(metric)}
 
 
+DUMP_MAX_PAIRS = 3_500_000        # two float64 files of 28 MB: within the 64 MB a dump may take
+
+
+def dump_outputs(directory, n_pairs, fetch):
+    """--dump-outputs DIR: the condensed distance vector (scipy order) of the last timed step, as DIR/distances.npy (float64), and
+    DIR/pair_index.npy (float64): the condensed index of every value.  The whole vector up to DUMP_MAX_PAIRS pairs; above that a
+    fixed, seeded sample of that many pairs in index order -- the same pairs for the same arguments, so that two builds can be
+    compared value for value.  ``fetch(condensed indices) -> values`` reads them from wherever the matrix is."""
+    import numpy as np
+    if n_pairs <= DUMP_MAX_PAIRS:
+        idx = np.arange(n_pairs, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240).choice(n_pairs, DUMP_MAX_PAIRS, replace=False))
+    values = np.asarray(fetch(idx), dtype=np.float64)
+    assert values.shape == idx.shape
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "distances.npy"), values)
+    np.save(os.path.join(directory, "pair_index.npy"), idx.astype(np.float64))
+
+
 def child_probe(a, rank, world):
     """PC_BENCH_CHILD_PROBE=1 (tests/test_distributed_cpu.py): what a rank does BEFORE its first GPU call -- join the group the
     parent's launcher set up -- and nothing after: rank 0 prints a line that says how many ranks met.  Runs where there is no GPU."""
@@ -293,16 +327,19 @@ def main_one_process(a):
         "create_s": t_create, "upload_s": upload_s,
     }
     line["value_wall_incl_init"] = n_pairs / (t_create + upload_s + elapsed / a.steps)
-    if needs_residues:
+    if a.dump_outputs:
+        import numpy as np
+        dump_outputs(a.dump_outputs, n_pairs, lambda cond: np.asarray(out)[cond])
+    if a.full and needs_residues:
         line["roofline"], line["kernel_source_hash"] = aligned_roofline(
             a, world, tot("n_alignments"), tot("n_cells"), tot("n_residue_bytes"), tot("n_distinct_alignments"), tot("n_distinct_cells"),
             ms_align_max, [ms_align_min, ms_align_max])
-    else:
+    elif a.full:
         nb = packed.n_genomes * packed.words_per_row * 8 + 16 * packed.n_genomes + 8 * n_pairs
         t = mean(lambda s: s["ms_total"]) / 1e3
         line["roofline"] = {"bound": "hbm", "achieved": nb / t / 1e9 if t > 0 else 0.0, "peak": 8000.0 * world, "unit": "GB/s",
                             "frac": nb / t / 1e9 / (8000.0 * world) if t > 0 else 0.0, "traffic": None, "algorithmic_bytes_per_fill": nb}
-    if a.verify_pairs > 0 and n_pairs > 0:
+    if a.full and a.verify_pairs > 0 and n_pairs > 0:
         import numpy as np
         line["verified"] = verify_sample(packed, a.metric, a.verify_pairs, lambda cond: np.asarray(out)[cond])
     line["valid"] = bool(line.get("verified", {}).get("bit_exact", True))
@@ -478,6 +515,7 @@ def main():
         agg_sum = agg.clone(); dist.all_reduce(agg_sum, op=dist.ReduceOp.SUM)
         agg_max = agg.clone(); dist.all_reduce(agg_max, op=dist.ReduceOp.MAX)
         agg_min = agg.clone(); dist.all_reduce(agg_min, op=dist.ReduceOp.MIN)
+    if multi and a.full:
         # the fixed cost of being N ranks (every rank takes part: max over ranks): process start -> group ready, and one upload
         t = torch.tensor([init_s], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -541,9 +579,11 @@ def main():
                                   + ("" if backend == "nccl" or world == 1 else f" [REHEARSAL: backend {backend}, ranks share GPUs]")
                                   + (" [REHEARSAL: ONE rank, exchange forced (PC_BENCH_FORCE_DIST)]" if multi and world == 1 else "")},
     }
-    if a.metric in ("aai", "peq"):
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, n_pairs, lambda cond: out[torch.as_tensor(cond, device=out.device)].cpu().numpy())
+    if a.full and a.metric in ("aai", "peq"):
         line["roofline"], line["kernel_source_hash"] = aligned_roofline(a, world, n_aln, n_cells, n_rbytes, n_daln, n_dcells, ms_align, align_span)
-    else:
+    elif a.full:
         nb = packed.n_genomes * packed.words_per_row * 8 + 16 * packed.n_genomes + 8 * n_pairs
         t = ms_dev / 1e3
         line["roofline"] = {"bound": "hbm", "achieved": nb / t / 1e9 if t > 0 else 0.0, "peak": 8000.0, "unit": "GB/s",
@@ -561,6 +601,7 @@ def main():
     else:
         line["stage_ms"] = stage_multi
         line["shards"] = shard_span
+    if multi and a.full:
         # the fixed cost of being N ranks, and the rate a user of one matrix sees with it: process start -> group ready (max over
         # ranks), + one upload, + one fill with its exchange (the timed step)
         line["init_s"] = init_s
@@ -569,10 +610,10 @@ def main():
         line["init_note"] = ("init_s: process start -> torch imported, process group initialised, first barrier passed (max over ranks); "
                              "value_wall_incl_init = pairs / (init_s + upload_s + one step): what ONE matrix costs a job that has to start its ranks first")
 
-    if a.verify_pairs > 0 and n_pairs > 0:
+    if a.full and a.verify_pairs > 0 and n_pairs > 0:
         line["verified"] = verify_sample(packed, a.metric, a.verify_pairs,
                                          lambda cond: out[torch.as_tensor(cond, device=out.device)].cpu().numpy())
-    if world == 1:
+    if a.full and world == 1:
         # SURVEY 8(d)'s wall time of one matrix: upload + kernels + D2H of the condensed vector (host clock, second of two)
         for _ in range(2):
             torch.cuda.synchronize()
@@ -587,7 +628,7 @@ def main():
         # SURVEY 8(d)'s figure for one matrix, host clock: upload + kernels + D2H of the condensed vector
         line["value_wall"] = line["pairs_per_s_incl_upload_d2h"]
         assert host.shape[0] == n_pairs
-    if world == 1 and a.cpu_seconds > 0:
+    if a.full and world == 1 and a.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(packed, a.metric, a.cpu_seconds)
     valid = bool(line.get("verified", {}).get("bit_exact", True))
     line["valid"] = valid

@@ -244,3 +244,26 @@ def test_bench_parent_source_makes_no_gpu_call():
     first_import = min(n.lineno for n in ast.walk(main) if isinstance(n, (ast.Import, ast.ImportFrom)))
     spawn_call = min(n.lineno for n in ast.walk(main) if isinstance(n, ast.Call) and getattr(n.func, "id", "") == "spawn_ranks")
     assert spawn_call < first_import                             # main() hands over before it imports anything
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole condensed vector up to DUMP_MAX_PAIRS, above that a seeded sample (the same pairs from
+    run to run, in index order); float64 files, within 64 MB at the cap."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert 2 * (8 * bench.DUMP_MAX_PAIRS + 128) <= 64_000_000
+    matrix = np.random.default_rng(1).random(5000)
+    bench.dump_outputs(str(tmp_path / "whole"), matrix.size, lambda idx: matrix[idx])
+    assert np.array_equal(np.load(tmp_path / "whole" / "distances.npy"), matrix)
+    assert np.array_equal(np.load(tmp_path / "whole" / "pair_index.npy"), np.arange(matrix.size))
+    monkeypatch.setattr(bench, "DUMP_MAX_PAIRS", 700)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), matrix.size, lambda idx: matrix[idx])
+    index = np.load(tmp_path / "a" / "pair_index.npy")
+    values = np.load(tmp_path / "a" / "distances.npy")
+    assert index.dtype == values.dtype == np.float64 and index.size == values.size == 700
+    assert (np.diff(index) > 0).all() and np.array_equal(values, matrix[index.astype(np.int64)])
+    assert np.array_equal(index, np.load(tmp_path / "b" / "pair_index.npy"))
+    assert np.array_equal(values, np.load(tmp_path / "b" / "distances.npy"))

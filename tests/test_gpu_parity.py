@@ -910,7 +910,7 @@ def test_bench_json_contract(native_built):
     import sys
     from conftest import REPO
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--genomes", "300", "--steps", "1", "--warmup", "1",
-                           "--cpu-seconds", "1", "--verify-pairs", "2000"], capture_output=True, text=True, timeout=600)
+                           "--cpu-seconds", "1", "--verify-pairs", "2000", "--full"], capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -924,6 +924,34 @@ def test_bench_json_contract(native_built):
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(d["cpu_baseline"]) and d["cpu_baseline"]["kind"] == "port"
     assert d["verified"]["bit_exact"] is True and d["value"] > 0
     assert d["value_resident"] == d["value"] and 0 < d["value_wall"] <= d["value"] and "SURVEY 8(d)" in d["value_definition"]
+
+
+def test_bench_plain_line_and_dumped_outputs(native_built, tmp_path):
+    """A plain bench.py run (no --full) prints the headline keys only, times exactly --steps fills, and --dump-outputs writes the
+    last step's whole condensed matrix, which equals the oracle's."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import REPO
+    from oracle import oracle as O
+    from phamclust_amd.synth import synth_packed
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--genomes", "300", "--steps", "2", "--warmup", "1",
+                           "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "genome-pairs/sec" and d["unit"] == "genome-pairs/s" and d["higher_is_better"] is True and d["dtype"] == "int32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["valid"] is True
+    assert abs(d["value"] - 300 * 299 // 2 / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    for key in ("cpu_baseline", "verified", "roofline", "value_wall"):
+        assert key not in d, key
+    got = np.load(tmp_path / "distances.npy")
+    index = np.load(tmp_path / "pair_index.npy")
+    assert got.dtype == np.float64 and index.dtype == np.float64
+    assert np.array_equal(index, np.arange(300 * 299 // 2))
+    assert np.array_equal(got, O.fill(synth_packed(300, 5000), "peq", as_distance=True))
 
 
 def test_bench_two_ranks_rehearsal(native_built):
@@ -943,7 +971,7 @@ def test_bench_two_ranks_rehearsal(native_built):
     env = dict(os.environ, PC_BENCH_BACKEND="gloo")
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--genomes", "301", "--steps", "2",
-                           "--warmup", "1", "--verify-pairs", "3000"], capture_output=True, text=True, timeout=900, env=env)
+                           "--warmup", "1", "--verify-pairs", "3000", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1035,7 +1063,7 @@ def test_bench_two_ranks_rehearsal_alignment_slices(native_built, mode):
     env = dict(os.environ, PC_BENCH_BACKEND="gloo", PHAMCLUST_DIST_MODE=mode)
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--genomes", "301", "--steps", "2",
-                           "--warmup", "1", "--verify-pairs", "3000"], capture_output=True, text=True, timeout=900, env=env)
+                           "--warmup", "1", "--verify-pairs", "3000", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     d = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and "alignments sliced" in d["config"]["parallelism"]
@@ -1065,7 +1093,7 @@ def test_bench_two_gpus_rccl(native_built, mode):
     env.pop("PC_BENCH_BACKEND", None)
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--genomes", "1000", "--steps", "2",
-                           "--warmup", "1", "--verify-pairs", "5000"], capture_output=True, text=True, timeout=900, env=env)
+                           "--warmup", "1", "--verify-pairs", "5000", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     d = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["verified"]["bit_exact"] is True and d["config"]["dist_mode"] == mode
@@ -1137,7 +1165,7 @@ def test_bench_distributed_flow_with_one_rank_over_rccl(native_built, mode):
     for k in ("PC_BENCH_BACKEND", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--genomes", "301", "--steps", "2", "--warmup", "1",
-                           "--verify-pairs", "3000", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, env=env)
+                           "--verify-pairs", "3000", "--cpu-seconds", "0", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     d = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["verified"]["bit_exact"] is True and d["config"]["dist_mode"] == mode
@@ -1741,8 +1769,8 @@ def test_bench_gpus_2_by_itself_spawns_two_ranks(native_built):
     parent relays rank 0's line.  This box has one GPU, so the ranks share it over the gloo rehearsal transport (RCCL refuses two
     ranks on one device); on a node with >= 2 GPUs the same command runs over RCCL.  Replaces the reference's joblib fan-out
     (matrix.py:471-472,488-491)."""
-    d = _bench_line(["--gpus", "2", "--genomes", "301", "--steps", "2", "--warmup", "1", "--verify-pairs", "3000", "--cpu-seconds", "0"],
-                    {"PC_BENCH_BACKEND": "gloo"})
+    d = _bench_line(["--gpus", "2", "--genomes", "301", "--steps", "2", "--warmup", "1", "--verify-pairs", "3000", "--cpu-seconds", "0",
+                     "--full"], {"PC_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["route"] == "rank" and d["devices_visible"] >= 1
     assert d["verified"]["bit_exact"] is True and d["valid"] is True
     assert d["launched_by"]["parent_modules_touching_gpu"] == [] and d["launched_by"]["child_exit_status"] == 0
@@ -1755,7 +1783,7 @@ def test_bench_route_process_drives_the_devices_from_one_process(native_built, m
     peer-copy exchange can be put next to the RCCL gather.  Here: two contexts on the one GPU; the line says so, and says how
     every shard travelled (pc_multi_peer_access)."""
     d = _bench_line(["--gpus", "2", "--route", "process", "--genomes", "301", "--steps", "2", "--warmup", "1", "--verify-pairs", "3000",
-                     "--cpu-seconds", "0", "--metric", metric], {"PC_BENCH_DEVICE_IDS": "0,0"})
+                     "--cpu-seconds", "0", "--metric", metric, "--full"], {"PC_BENCH_DEVICE_IDS": "0,0"})
     assert d["route"] == "process" and d["n_gpus"] == 2 and d["device_ids"] == [0, 0]
     assert d["verified"]["bit_exact"] is True and "REHEARSAL" in d["config"]["parallelism"]
     peers = d["peer_access"]

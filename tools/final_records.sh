@@ -25,8 +25,8 @@ elif [ "$PART" = b ]; then
   t 400 python3 -u tools/pipeline_time.py 10000 peq > $OUT/pipeline_10000.txt 2>&1; tail -3 $OUT/pipeline_10000.txt | cut -c1-300
   t 300 python3 -u tools/launch_cost.py -n 5000 --ranks 1,2,4 --out $OUT/launch_cost.txt 2>&1 | tail -3 | cut -c1-200
   # bench.py by itself with N > 1: two ranks sharing this GPU over the gloo rehearsal transport, and one process driving two contexts
-  PC_BENCH_BACKEND=gloo t 300 python3 bench.py --gpus 2 --genomes 2000 --cpu-seconds 0 > $OUT/bench_rehearsal_2ranks_spawned.json 2> $OUT/bench_rehearsal_2ranks_spawned.err; cut -c1-300 $OUT/bench_rehearsal_2ranks_spawned.json
-  PC_BENCH_DEVICE_IDS=0,0 t 300 python3 bench.py --gpus 2 --route process --genomes 2000 --cpu-seconds 0 > $OUT/bench_rehearsal_2devices_one_process.json 2> $OUT/bench_rehearsal_2devices_one_process.err; cut -c1-300 $OUT/bench_rehearsal_2devices_one_process.json
+  PC_BENCH_BACKEND=gloo t 300 python3 bench.py --gpus 2 --genomes 2000 --cpu-seconds 0 --full > $OUT/bench_rehearsal_2ranks_spawned.json 2> $OUT/bench_rehearsal_2ranks_spawned.err; cut -c1-300 $OUT/bench_rehearsal_2ranks_spawned.json
+  PC_BENCH_DEVICE_IDS=0,0 t 300 python3 bench.py --gpus 2 --route process --genomes 2000 --cpu-seconds 0 --full > $OUT/bench_rehearsal_2devices_one_process.json 2> $OUT/bench_rehearsal_2devices_one_process.err; cut -c1-300 $OUT/bench_rehearsal_2devices_one_process.json
   t 500 python3 -u tools/big_fill.py 2>&1 | grep --line-buffered -v amdgpu | tee $OUT/big_fill.txt | cut -c1-400
 else
   t 1000 python3 -u -m pytest tests -q -m gpu --durations=12 > $OUT/gpu_suite.txt 2>&1; echo "pytest rc $?"; tail -16 $OUT/gpu_suite.txt

@@ -8,8 +8,8 @@ TAG=${1:-r02}
 OUT=gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
-QUICK="--cpu-seconds 0 --verify-pairs 0"
-echo "== bench (default)"; python3 bench.py > $OUT/${TAG}_bench_peq5000.json 2> $OUT/${TAG}_bench_peq5000.err || echo "bench failed"
+QUICK="--full --cpu-seconds 0 --verify-pairs 0"
+echo "== bench (default)"; python3 bench.py --full > $OUT/${TAG}_bench_peq5000.json 2> $OUT/${TAG}_bench_peq5000.err || echo "bench failed"
 echo "== kernel trace, peq N=5000"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_peq -o t -- python3 bench.py --steps 3 --warmup 1 $QUICK > $OUT/${TAG}_trace_peq.log 2>&1 || echo "trace failed"
 echo "== PMC FETCH_SIZE"
