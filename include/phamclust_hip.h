@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 151   /* 0.5.0: pc_multi_peer_access */
+#define PC_VERSION 152   /* 0.5.1: pc_task_shape, pc_ppos_width */
 
 typedef enum {
     PC_OK = 0,
@@ -256,6 +256,16 @@ int pc_get_tie_rule(const pc_ctx* ctx);
 
 /* Test hook: columns per lane of the systolic variant the chooser picks for a column gene of lb residues; 0 = general kernel. */
 int pc_variant_width(int lb);
+
+/* Test hook: how the systolic kernel runs a column gene of lb residues (no byte outside the alphabet) on the variant of
+ * `width` columns per lane (0: the chooser's): out[0] rows per workgroup task, out[1] waves per workgroup, out[2] row
+ * streams per wave (segments; 1 when strip-mined), out[3] strip-mined passes of 64 x width columns (0: in registers).
+ * An alignment stream of a full task carries out[0] / (out[1] * out[2]) alignments back to back. */
+int pc_task_shape(int lb, int width, int32_t* out);
+
+/* Test hook: columns per lane of the systolic variant a percent-positives (aai_ppos) launch runs on when the longest
+ * column gene of its class has max_lb residues; 0 = the general kernel. */
+int pc_ppos_width(int max_lb);
 
 /* Test / tuning hook: HIP-event milliseconds of the alignment kernels of the last pc_align_pairs call. */
 float pc_last_align_ms(const pc_ctx* ctx);

@@ -1862,6 +1862,26 @@ extern "C" int pc_variant_width(int lb) {
     return v < 0 ? 0 : pc_nw_variant_w(v);
 }
 
+extern "C" int pc_task_shape(int lb, int width, int32_t* out) {
+    if (lb <= 0 || lb > 65535 || !out) { pc_set_error("pc_task_shape: bad argument"); return PC_ERR_ARG; }
+    int v = -1;
+    if (width == 0) v = pc_nw_choose_variant(lb);
+    else for (int k = 0; k < pc_nw_num_variants(); ++k) if (pc_nw_variant_w(k) == width) v = k;
+    if (v < 0) { pc_set_error("pc_task_shape: no systolic variant for w = %d, %d columns", width, lb); return PC_ERR_ARG; }
+    const int W = pc_nw_variant_w(v), G = (lb + W - 1) / W;
+    const bool strip = G > 64;
+    out[0] = pc_nw_task_rows(lb, v, 0);
+    out[1] = strip ? out[0] : pc_nw_class_waves(v, lb, 0);                   // strip-mined: one row per wave
+    out[2] = strip ? 1 : std::min(64 / G, 16);                              // (as pc_align_pairs cuts buckets)
+    out[3] = strip ? pc_nw_strip_passes(lb, v) : 0;
+    return PC_OK;
+}
+extern "C" int pc_ppos_width(int max_lb) {
+    int v = pc_nw_choose_variant(max_lb);                     // as run_align_classes' launch_variant picks it
+    if (v >= 0 && !pc_nw_ppos_systolic(v, max_lb)) v = pc_nw_ppos_variant(max_lb);
+    return v < 0 ? 0 : pc_nw_variant_w(v);
+}
+
 extern "C" float pc_last_align_ms(const pc_ctx* c) { return c ? c->last_align_ms : -1.f; }
 extern "C" int pc_last_set_kernel(const pc_ctx* c) { return c ? c->last_set_kernel : -1; }
 

@@ -50,7 +50,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_shard_pairs", "pc_shard_stride", "pc_fill", "pc_fill_borrow", "pc_fill_dev", "pc_fill_shard_dev", "pc_assemble_dev",
            "pc_align_pairs", "pc_last_align_ms", "pc_round6_probe", "pc_set_tie_rule", "pc_get_tie_rule", "pc_shard_table", "pc_target_costs",
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
-           "pc_variant_width", "pc_last_set_kernel", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
+           "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_last_set_kernel", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
@@ -93,6 +93,8 @@ def load():
     L.pc_set_plan_budget.argtypes = [vp, ctypes.c_int64]
     L.pc_chunk_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_uint64, _i32p, ctypes.c_int]
     L.pc_variant_width.argtypes = [ctypes.c_int]
+    L.pc_task_shape.argtypes = [ctypes.c_int, ctypes.c_int, _i32p]
+    L.pc_ppos_width.argtypes = [ctypes.c_int]
     L.pc_set_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.pc_set_shard_balanced.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.pc_shard_pairs.argtypes = [vp]
@@ -412,6 +414,21 @@ class Context:
     def variant_width(lb):
         """Columns per lane of the systolic variant chosen for a column gene of ``lb`` residues (0: general kernel)."""
         return int(load().pc_variant_width(int(lb)))
+
+    @staticmethod
+    def task_shape(lb, width=0):
+        """How a column gene of ``lb`` residues runs on the variant of ``width`` columns per lane (0: the chooser's):
+        dict of rows per task, waves per workgroup, row streams per wave and strip-mined passes (0: in registers)."""
+        out = np.zeros(4, dtype=np.int32)
+        if load().pc_task_shape(int(lb), int(width), _ptr(out, _i32p)) != 0:
+            raise HipLibraryError(load().pc_last_error().decode())
+        return dict(zip(("rows", "waves", "streams", "passes"), out.tolist()))
+
+    @staticmethod
+    def ppos_width(max_lb):
+        """Columns per lane of the variant a percent-positives launch runs on when its longest column gene has ``max_lb``
+        residues (0: general kernel)."""
+        return int(load().pc_ppos_width(int(max_lb)))
 
     def last_align_ms(self):
         return float(self._lib.pc_last_align_ms(self._h))

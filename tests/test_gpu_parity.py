@@ -499,7 +499,9 @@ def test_strip_mined_long_column_genes(gpu_ctx, native_built):
             gpu_ctx.upload(pk)
             # PC_PIPE (read per launch): "0" one row per wave (the wide variants forced too); unset: the launcher's choice -- these few
             # tasks run pipelined, the passes of each alignment dealt over eight waves; 4, 3 (passes not a multiple of the waves), 1
-            want_fill = {metric: O.fill(pk, metric) for metric in ("peq",)}      # (peq = round(af x aai): the same alignments and reduce as aai; one oracle pass over 20,000 x 20,000 cells less)
+            # aai and peq under rule 0; peq only under rule 3 (peq = round(af x aai): the same alignments and reduce as aai; one oracle
+            # pass over 20,000 x 20,000 cells less)
+            want_fill = {metric: O.fill(pk, metric) for metric in (("aai", "peq") if rule == 0 else ("peq",))}
             for pipe in ("0", None, "4", "3", "1"):
                 if pipe is None: os.environ.pop("PC_PIPE", None)
                 else: os.environ["PC_PIPE"] = pipe
@@ -1641,8 +1643,10 @@ print("ok")
 def test_real_collection_shape_full_matrix(gpu_ctx, native_built):
     """The second workload (phamclust_amd.synth.synth_real: power-law clusters, ~6 N phams most of them with 1-3 holders, > 60 %
     byte-identical proteins inside a cluster, paralog runs up to 8, 5-8 k-residue proteins, 2-column "M" genomes) at N = 1,000:
-    the WHOLE matrix of every metric against the oracle, whichever kernels the selector and the planner pick for it, plus every
-    set-metric family forced (metrics.py:26-253; the selector's thresholds were all tuned on synth(N, 5000))."""
+    the whole matrix of every set metric against the oracle, whichever kernel the selector picks for it, plus every set-metric
+    family forced (metrics.py:26-157; the selector's thresholds were all tuned on synth(N, 5000)); aai and peq on 30,000
+    random pairs each against the oracle, and the whole peq matrix against its definition from the af and aai fills
+    (metrics.py:178-253).  The whole aai and peq matrices against the oracle: test_real_collection_whole_alignment_matrices."""
     from phamclust_amd.synth import synth_real
     O = _oracle()
     pk = synth_real(1000)
@@ -1675,6 +1679,20 @@ def test_real_collection_shape_full_matrix(gpu_ctx, native_built):
                 assert np.array_equal(gpu_ctx.fill(metric), O.fill(pk, metric)), (kernel, metric)
     finally:
         os.environ.pop("PC_SET_KERNEL", None)
+
+
+def test_real_collection_whole_alignment_matrices(gpu_ctx, native_built):
+    """The whole aai and peq matrices of synth_real(300) -- genes beyond 4,096 residues (strip-mined), byte-identical proteins
+    (aliased alignments), paralog runs -- against the oracle's: an alignment error on a few rare pairs, such as those of the
+    strip-mined long genes, shows here, where a sample of pairs could miss it."""
+    from phamclust_amd.synth import synth_real
+    O = _oracle()
+    pk = synth_real(300)
+    lens = np.diff(pk.seq_off)
+    assert (lens > 4096).any() and (pk.tlen == pk.ngen).any()
+    gpu_ctx.upload(pk)
+    for metric in ("aai", "peq"):
+        assert np.array_equal(gpu_ctx.fill(metric), O.fill(pk, metric)), metric
 
 
 def test_launch_policy_switches_change_no_value(native_built):

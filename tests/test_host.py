@@ -295,6 +295,23 @@ def test_abi_exports_match_header(native_built):
     assert "n_chunks" in hip.PcStats().as_dict()
 
 
+def test_task_shape_and_percent_positives_route(native_built):
+    """The host-side launch arithmetic that tests/test_gpu_limits.py builds its cases on (no GPU call): strip passes of a
+    65,535-residue column gene per wide variant, a full task of a 100-residue column on W = 2 / 3 (one row stream per wave,
+    52 alignments each), and where percent-positives leaves the strip-mined profile cell (13-bit fields: 8,191 columns)."""
+    from phamclust_amd import hip
+    C = hip.Context
+    assert [C.task_shape(65535, w)["passes"] for w in (32, 48, 64)] == [32, 22, 16]
+    assert C.task_shape(4096, 32)["passes"] == 2 and C.task_shape(4097, 32)["passes"] == 3 and C.task_shape(4096, 64)["passes"] == 0
+    for w in (2, 3):
+        assert C.task_shape(100, w) == {"rows": 208, "waves": 4, "streams": 1, "passes": 0}
+    assert C.task_shape(100, 4)["streams"] == 2
+    assert [C.ppos_width(n) for n in (1536, 1537, 7681, 8191, 8192, 9000)] == [24, 24, 24, 24, 0, 0]
+    for lb, w in ((100, 1), (65536, 0), (0, 0)):
+        with pytest.raises(hip.HipLibraryError):
+            C.task_shape(lb, w)
+
+
 def test_borrowed_array_guards_every_numpy_route():
     """a lent result must refuse ufuncs, reductions and numpy functions too once its loan has ended, not only
     indexing and conversion (host logic: the view class itself, over ordinary memory)."""
