@@ -271,7 +271,7 @@ int pc_ppos_width(int max_lb);
 float pc_last_align_ms(const pc_ctx* ctx);
 
 /* Which kernel family the selector gave the last gcs / jc / pocp / af fill of this context: 0 popcount tiles, 1 sparse tiles
- * 32 x 32, 2 sparse tiles 64 x 64, 3 shared-pham walker, 4 the column kernel (gcs / jc: target-block masks kept in LDS over a run
+ * 32 x 32, 2 sparse tiles 64 x 64, 3 shared-pham walker, 4 the column kernel (gcs / jc / pocp / af: target-block masks kept in LDS over a run
  * of source tiles); -1 before the first such fill.  (The selector reads the collection:
  * genomes, bitmap words, phams an average pair shares -- metrics.py:26-157 have one code path, this has four.) */
 int pc_last_set_kernel(const pc_ctx* ctx);
@@ -305,7 +305,7 @@ int pc_round6_probe(pc_ctx* ctx, const double* in, double* out, int64_t n);
  *     PC_POPC_TILE=32|64        force the word-split 32 x 32 / the 64 x 64 popcount tile kernel
  *     PC_SET_KERNEL=popc|sparse|sparse64|sparsecol|walker    force a kernel family for gcs / jc / pocp / af where it exists for the metric
  *     PC_S64_CHUNKS=n           at least n mask chunks in the 64 x 64 sparse tile kernel
- *     PC_COL_SEG=n              source tiles per unit of the column kernel (gcs / jc; default: by the matrix, at most 8)
+ *     PC_COL_SEG=1..64          source tiles per unit of the column kernel (gcs / jc / pocp / af; default: by the matrix, at most 8)
  *     PC_PIPE=0|n               strip-mined launches: never pipelined (one row per wave) / always, the passes of a row over n <= 8 waves (default: by the launch's size)
  *   only in libphamclust_hip_hooks.so (compiled with -DPC_TEST_HOOKS; pc_test_hooks() == 1)
  *     PC_FAKE_OOM_ABOVE=n       device allocations above n bytes made while a fill is planning fail (fault injection)

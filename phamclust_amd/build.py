@@ -21,14 +21,18 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # tools/build_variant.py adds -ffinite-math-only to these units for the builds that use __builtin_fmax on the cell's 64-bit words
 # (PC_MAX_BUILTIN / PC_CELL_ORDER: experiment switches of pc_nw_systolic.h); the product build uses asm maxima and needs no flag.
 NW_FLAGS = []
-HIP_UNITS = [("pc_api.hip", "pc_api.o", []), ("pc_pairs.hip", "pc_pairs.o", []), ("pc_plan.hip", "pc_plan.o", []),
+# The host side of the C-ABI is five units (pc_ctx, pc_upload, pc_align, pc_fill, pc_multi; internal header pc_host.h): they hold
+# no device code, so the library's .hip_fatbin comes from the kernel units alone.
+HIP_UNITS = [("pc_ctx.hip", "pc_ctx.o", []), ("pc_upload.hip", "pc_upload.o", []), ("pc_align.hip", "pc_align.o", []),
+             ("pc_fill.hip", "pc_fill.o", []), ("pc_multi.hip", "pc_multi.o", []),
+             ("pc_pairs.hip", "pc_pairs.o", []), ("pc_plan.hip", "pc_plan.o", []),
              ("pc_nw.hip", "pc_nw.o", NW_FLAGS),
              ("pc_nw_rules.hip", "pc_nw_r23.o", NW_FLAGS + ["-DPC_RULE_A=2", "-DPC_RULE_B=3"]),
              ("pc_nw_rules.hip", "pc_nw_r45.o", NW_FLAGS + ["-DPC_RULE_A=4", "-DPC_RULE_B=5"]),
              ("pc_nw_rules.hip", "pc_nw_r67.o", NW_FLAGS + ["-DPC_RULE_A=6", "-DPC_RULE_B=7"])]
-# the same library once more with pc_api.hip compiled under -DPC_TEST_HOOKS (fault injection: PC_FAKE_OOM_ABOVE); every other
-# object is shared.  Loaded only by the test that needs it (PHAMCLUST_NATIVE_VARIANT=hooks).
-HOOKS_UNIT = ("pc_api.hip", "pc_api_hooks.o", ["-DPC_TEST_HOOKS"])
+# the same library once more with pc_ctx.hip compiled under -DPC_TEST_HOOKS (fault injection: PC_FAKE_OOM_ABOVE) in place of
+# pc_ctx.o; every other object is shared.  Loaded only by the test that needs it (PHAMCLUST_NATIVE_VARIANT=hooks).
+HOOKS_UNIT = ("pc_ctx.hip", "pc_ctx_hooks.o", ["-DPC_TEST_HOOKS"])
 HIP_SOURCES = sorted({u[0] for u in HIP_UNITS})
 HIP_LIB = os.path.join(CSRC, "libphamclust_hip.so")
 HIP_HOOKS_LIB = os.path.join(CSRC, "libphamclust_hip_hooks.so")
@@ -50,7 +54,7 @@ def _stale(target, sources):
 
 def build_hip(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "pc_common.h"), os.path.join(CSRC, "pc_nw_systolic.h"),
+    headers = [os.path.join(CSRC, "pc_common.h"), os.path.join(CSRC, "pc_nw_systolic.h"), os.path.join(CSRC, "pc_host.h"),
                os.path.join(CSRC, "..", "..", "include", "phamclust_hip.h")]
     objs, jobs = [], []
     for src, obj_name, extra in HIP_UNITS + [HOOKS_UNIT]:
@@ -66,7 +70,8 @@ def build_hip(force=False, verbose=False):
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])
     hooks_obj = objs.pop()
-    for lib, lib_objs in ((HIP_LIB, objs), (HIP_HOOKS_LIB, [hooks_obj] + objs[1:])):
+    release_obj = os.path.join(CSRC, next(o for s, o, _ in HIP_UNITS if s == HOOKS_UNIT[0]))      # pc_ctx.o, which the hooks object replaces
+    for lib, lib_objs in ((HIP_LIB, objs), (HIP_HOOKS_LIB, [hooks_obj if o == release_obj else o for o in objs])):
         if force or _stale(lib, lib_objs):
             cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + lib_objs + ["-ldl"]
             if verbose:

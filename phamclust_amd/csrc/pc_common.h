@@ -117,7 +117,7 @@ int pc_launch_pair_entries(const int32_t* pham, const int32_t* len, const int32_
 int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, const int32_t* len, const int32_t* cnt, const int32_t* dense, int W2,
                        int32_t* sp_pham, uint2* sp_len, uint2* sp_cnt, uint32_t* sp_rank, uint32_t* sp_end, hipStream_t st);
 int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st); // pocp / af, large matrices
-// k_sparse_col (gcs / jc / pocp, large matrices): masks over a block of target genomes kept in LDS across a run of source tiles
+// k_sparse_col (gcs / jc / pocp / af, large matrices): masks over a block of target genomes kept in LDS across a run of source tiles
 size_t pc_sparse_col_lds(int mode, int P64);      // 0: the masks do not fit
 int pc_sparse_col_vals_cap(int P64);             // pocp / af: entries (of phams with two holders) a block of 64 targets may hold
 int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st);

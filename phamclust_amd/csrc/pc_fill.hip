@@ -1,0 +1,204 @@
+// pc_fill.hip -- the fill entry points of libphamclust_hip.so (pc_fill, pc_fill_borrow, pc_fill_dev, pc_fill_shard_dev,
+// pc_assemble_dev) and the set-metric kernel selector.
+#include "pc_host.h"
+
+#ifndef PC_COL_MIN_N
+#define PC_COL_MIN_N 2200        // genomes from which k_sparse_col takes over from the popcount tiles (r05 sweep: profiles/r05/experiments/sparse_col.txt)
+#endif
+enum { K_POPC, K_SPARSE32, K_SPARSE64, K_WALKER, K_SPARSE_COL };   // the set metrics' kernel families (pc_last_set_kernel)
+
+// Which kernel fills a set metric (measured crossovers, `profiles/r03/experiments/p_sparse64_record.txt`, `r03_z_pocp_kernel_by_density.txt`;
+// PC_SET_KERNEL = popc | sparse | sparse64 | sparsecol | walker forces one where it exists, applied last, for A/B runs and for the
+// tests that keep every one of them honest):
+//   gcs, jc          popcount tiles; a collection of many phams (long bitmap rows, few of them shared): the 64 x 64 sparse tile
+//                    kernel in its counting mode
+//   pocp             popcount tiles + paralog excess; from ~2,500 genomes the 64 x 64 sparse tile kernel where pairs share few
+//                    enough of the phams
+//   af               the 64 x 64 sparse tile kernel (the 32 x 32 one where that kernel's preconditions fail), the column kernel from ~1,400 genomes
+// The popcount tiles cost ~ pairs x bitmap words W, the sparse tiles ~ pairs x (a constant + the phams a pair shares).  Measured on
+// synth(5000, P), P = 300 ... 40,000, in ms: pocp 0.15 + 0.002 W against 0.207 + 0.0085 shared (sparse wins where W > 28 + 4.3 shared:
+// the synthetic collection's 79 words and 2.85 shared phams yes, 300 phams -- 5 words, 34 shared -- three times no); gcs / jc
+// 0.05 + 0.0014 W against 0.155 + 0.0004 W + ~0.005 shared (W > 113 + 5.4 shared: from ~7,500 phams; at 40,000: 0.43 against 0.90).
+// `shared` of an average pair = sum over phams of n_p (n_p - 1) / (N (N - 1)), counted at upload.
+// The 64 x 64 kernel takes "sum == 0" for "no shared pham" and sums in 32 bits: it needs every entry value >= 1 (a
+// genome with an empty translation fails that for af) and genome totals below 2^31; else af falls back to the
+// 32 x 32 kernel / the shared-pham walker (crossover ~3,500 genomes), pocp to the popcount tiles.
+static int pick_set_kernel(const pc_ctx* c, int metric) {
+    const PcDev& d = c->dev;
+    int kernel = K_POPC;
+    const char* set_force = getenv("PC_SET_KERNEL");                   // (read per fill: the tests switch it between launches)
+    const int64_t area = (int64_t)d.N * c->shard.nown;
+    const double shared = std::max(c->avg_shared, 0.0);
+    const bool counts = metric == PC_GCS || metric == PC_JC;
+    const bool s64_ok = counts ? c->max_nph < (1 << 30) : metric == PC_POCP ? c->max_ngen < (1 << 16) /* two gene counts per register */ : (c->min_gene_len >= 1 && c->max_tlen < (int64_t)1 << 31);
+    if (counts) kernel = (((double)d.Wb > 113.0 + 5.4 * shared && area >= (int64_t)3000 * 3000) ||
+                          ((double)d.Wb > 60.0 + 5.4 * shared && area >= (int64_t)6000 * 6000)) ? K_SPARSE64 : K_POPC;   // (the sparse tiles gain on the popcount tiles as N grows: 5,056 phams, r04 with four workgroups per CU: N = 5,000 0.162 against 0.157 ms, 6,000 0.218 / 0.219, 7,000 0.258 / 0.282, 20,000 1.56 / 2.03)
+    else if (metric == PC_POCP) kernel = (s64_ok && (double)d.Wb > 28.0 + 4.3 * shared && area >= (int64_t)2500 * 2500) ? K_SPARSE64 : K_POPC;
+    else if (s64_ok) kernel = K_SPARSE64;                                  // (af; r05, ms, 32 x 32 / 64 x 64 tiles: N = 200 0.060 / 0.058, 800 0.095 / 0.061, 1,300 0.082 / 0.069 -- since r04's dense broadcast path the larger tile wins at every size)
+    else kernel = area > (int64_t)3500 * 3500 ? K_WALKER : K_SPARSE32;
+    // r05: the column kernel for all four (k_sparse_col: the masks over a block of targets stay in LDS for a run of source tiles, no
+    // barrier per tile) -- while its masks fit 78 KB of LDS (pocp / af: beside a table of the block's entry values).  Against the popcount tiles
+    // (profiles/r05/experiments/sparse_col.txt; ms, popcount / column): 5,056 phams (79 words, 2.85 shared) N = 2,000 0.035 / 0.034,
+    // 3,000 0.070 / 0.046, 8,000 0.35 / 0.20, 20,000 2.03 / 0.99; 2,500 phams (40 words) N = 5,000 0.098 / 0.110; 1,200: 0.067 / 0.146
+    const int sp_mode = counts ? (metric == PC_GCS ? PCW_SPARSE_GCS : PCW_SPARSE_JC) : metric == PC_POCP ? PCW_POCP : PCW_AF;
+    bool col_ok = s64_ok && pc_sparse_col_lds(sp_mode, d.sp_W * 64) > 0;
+    if (col_ok && !counts) {                                           // ... pocp / af: every block's entries fit its LDS value table, as 16-bit values
+        const int cap = pc_sparse_col_vals_cap(d.sp_W * 64);
+        col_ok = metric == PC_POCP || c->max_ent_len < 65536;         // (pocp: s64_ok already holds the gene counts below 65,536)
+        for (size_t k0 = 0; k0 < c->h_owned.size() && col_ok; k0 += 64) {
+            uint32_t n = 0;
+            for (size_t k = k0; k < std::min(k0 + 64, c->h_owned.size()); ++k) n += c->h_sp_n[(size_t)c->h_owned[k]];
+            col_ok = n <= (uint32_t)cap;
+        }
+    }
+    // (ms, popcount tiles / 64 x 64 sparse tiles / column -- pocp: N = 2,000 0.066 / 0.082 / 0.078, 3,000 0.137 / 0.118 / 0.083, 5,000 0.304 / 0.217 / 0.156,
+    // 20,000 3.89 / 2.23 / 1.45; af: 2,000 - / 0.089 / 0.078, 3,000 - / 0.121 / 0.081, 5,000 - / 0.258 / 0.150, 20,000 - / 2.41 / 1.42)
+    const int64_t col_min_n = metric == PC_AF ? 1400 : PC_COL_MIN_N;        // (af, 64 x 64 tiles / column: N = 1,000 0.062 / 0.072, 1,300 0.069 / 0.073, 1,500 0.087 / 0.074, 1,800 0.088 / 0.077)
+    if (col_ok && (double)d.Wb > 40.0 + 8.0 * shared && area >= col_min_n * col_min_n) kernel = K_SPARSE_COL;
+    if (set_force) {
+        if (!strcmp(set_force, "sparsecol") && col_ok) kernel = K_SPARSE_COL;
+        if (!strcmp(set_force, "popc") && metric != PC_AF) kernel = K_POPC;
+        else if (!strcmp(set_force, "sparse") && !counts) kernel = K_SPARSE32;
+        else if (!strcmp(set_force, "sparse64") && s64_ok) kernel = K_SPARSE64;
+        else if (!strcmp(set_force, "walker") && !counts) kernel = K_WALKER;
+    }
+    return kernel;
+}
+
+// gcs / jc / pocp on the popcount tiles.  Their epilogue table: gcs / jc over (shared, nph_s + nph_t), at most (max_nph+1) x
+// (2 max_nph+1) doubles; pocp over (conserved, ngen_s + ngen_t), (2 max_ngen+1)^2; skipped when huge.  It depends on (metric,
+// as_distance, that maximum) only, so it is rebuilt only when one of them changes.
+static int launch_popc(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st) {
+    const int top = metric == PC_POCP ? c->max_ngen : c->max_nph;
+    const int sh_dim = metric == PC_POCP ? 2 * top + 1 : top + 1, tot_dim = 2 * top + 1;
+    double* lut = nullptr; bool build_lut = false; int64_t lut_key_now = -1;
+    if ((int64_t)sh_dim * tot_dim <= (4 << 20)) {
+        if (const int rc = c->b_lut.ensure((size_t)sh_dim * tot_dim * 8)) return abi_rc(rc);
+        lut = c->b_lut.as<double>();
+        lut_key_now = ((int64_t)metric << 40) | ((int64_t)as_distance << 32) | (int64_t)top;
+        build_lut = lut_key_now != c->lut_key || lut != c->lut_ptr;
+    }
+    const int rc = pc_launch_set_popc(c->dev, c->shard, metric, as_distance, out, condensed, lut, build_lut, sh_dim, tot_dim, st);
+    if (rc != PC_OK) { c->lut_key = -1; c->lut_ptr = nullptr; return rc; }           // (whatever the table holds now, it is not trusted)
+    if (lut) { c->lut_key = lut_key_now; c->lut_ptr = lut; }                          // remembered only once its build was launched
+    return PC_OK;
+}
+
+static int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("fill: upload first"); return PC_ERR_STATE; }
+    if (metric < PC_GCS || metric > PC_AAI_PPOS) { pc_set_error("fill: metric %d", metric); return PC_ERR_ARG; }
+    const int ppos = metric == PC_AAI_PPOS;
+    if (ppos) metric = PC_AAI;
+    if (!out) { pc_set_error("fill: out is NULL"); return PC_ERR_ARG; }
+    PC_ON_DEVICE(c);
+    static const char* const fill_names[] = {"pc:fill:gcs", "pc:fill:jc", "pc:fill:pocp", "pc:fill:af", "pc:fill:aai", "pc:fill:peq"};
+    PcRange range(fill_names[metric]);
+    int rc = PC_OK;
+    // st == NULL is HIP's legacy default stream, used as such: a caller whose producers / consumers run on it (PyTorch's
+    // default stream has handle 0) is ordered with these launches; the library's own streams are non-blocking
+    if ((rc = wait_last_work(c, st, true))) return rc;
+    const PcDev& d = c->dev;
+    const int64_t Lp = c->shard_pairs;
+    pc_stats local; memset(&local, 0, sizeof(local));
+    local.n_pairs = Lp;
+    as_distance = as_distance ? 1 : 0;
+    PC_HIP(hipEventRecord(c->ev[0], st));
+
+    if (metric < PC_AAI) {
+        const int kernel = pick_set_kernel(c, metric);
+        const int mode = metric == PC_GCS ? PCW_SPARSE_GCS : metric == PC_JC ? PCW_SPARSE_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
+        c->last_set_kernel = kernel;
+        if (kernel == K_SPARSE_COL) rc = pc_launch_sparse_col(mode, d, c->shard, out, as_distance, condensed, st);
+        else if (kernel == K_SPARSE64) rc = pc_launch_sparse64(mode, d, c->shard, out, as_distance, condensed, st);
+        else if (kernel == K_POPC) rc = launch_popc(c, metric, as_distance, out, condensed, st);
+        else if (kernel == K_SPARSE32) rc = pc_launch_sparse(mode, d, c->shard, out, as_distance, condensed, st);
+        else {                                                             // K_WALKER
+            PcWalkArgs a; memset(&a, 0, sizeof(a));
+            a.out = out; a.as_distance = as_distance; a.condensed = condensed;
+            rc = pc_launch_walk(mode, d, c->shard, a, st);
+        }
+        if (rc != PC_OK) return rc;
+        PC_HIP(hipEventRecord(c->ev[3], st));
+        local.n_chunks = 1;
+    } else {
+        rc = fill_aligned(c, metric, ppos, as_distance, out, condensed, st, local, stats != nullptr);
+        if (rc != PC_OK) { (void)mark_work(c, st); return rc == PC_ERR_NOMEM_INTERNAL ? PC_ERR_HIP : rc; }
+    }
+    if ((rc = mark_work(c, st))) return rc;
+    if (stats) {
+        PC_HIP(hipEventSynchronize(c->ev[3]));
+        c->busy = false;
+        PC_HIP(hipEventElapsedTime(&local.ms_total, c->ev[0], c->ev[3]));
+        if (metric >= PC_AAI) {
+            if (local.n_chunks == 1) {
+                PC_HIP(hipEventElapsedTime(&local.ms_plan, c->ev[0], c->ev[1]));
+                PC_HIP(hipEventElapsedTime(&local.ms_align, c->ev[1], c->ev[2]));
+                PC_HIP(hipEventElapsedTime(&local.ms_reduce, c->ev[2], c->ev[3]));
+            }
+        } else {
+            local.ms_reduce = local.ms_total;
+        }
+        *stats = local;
+    }
+    return PC_OK;
+}
+
+extern "C" int pc_fill_dev(pc_ctx* c, int metric, int as_distance, void* out_dev, void* stream, pc_stats* stats) {
+    if (c && c->uploaded && c->world != 1) { pc_set_error("pc_fill_dev: context is sharded (%d/%d); use pc_fill_shard_dev", c->rank, c->world); return PC_ERR_STATE; }
+    return fill_impl(c, metric, as_distance, (double*)out_dev, 1, (hipStream_t)stream, stats);
+}
+
+extern "C" int pc_fill(pc_ctx* c, int metric, int as_distance, double* out_condensed, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill: upload first"); return PC_ERR_STATE; }
+    if (!out_condensed) { pc_set_error("pc_fill: out is NULL"); return PC_ERR_ARG; }
+    PC_ON_DEVICE(c);
+    int rc = PC_OK;
+    const int64_t np = (int64_t)c->dev.N * (c->dev.N - 1) / 2;
+    if ((rc = c->b_out.ensure(std::max<int64_t>(np, 1) * 8))) return abi_rc(rc);
+    if ((rc = pc_fill_dev(c, metric, as_distance, c->b_out.p, c->stream, stats))) return rc;
+    if (np) PC_HIP(hipMemcpyAsync(out_condensed, c->b_out.p, np * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    c->busy = false;
+    return PC_OK;
+}
+
+// Whole matrix into page-locked host memory that the CONTEXT owns: the D2H copy of an N = 20,000 matrix (1.6 GB) runs at
+// PCIe speed (~30 ms) instead of through pageable staging (~165 ms), and the 1.6 GB are pinned once, not per call.
+// *out_host stays valid until the next fill / upload on this context or its destruction.
+extern "C" int pc_fill_borrow(pc_ctx* c, int metric, int as_distance, const double** out_host, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_borrow: upload first"); return PC_ERR_STATE; }
+    if (!out_host) { pc_set_error("pc_fill_borrow: out_host is NULL"); return PC_ERR_ARG; }
+    *out_host = nullptr;
+    PC_ON_DEVICE(c);
+    int rc = PC_OK;
+    const int64_t np = (int64_t)c->dev.N * (c->dev.N - 1) / 2;
+    const size_t bytes = (size_t)std::max<int64_t>(np, 1) * 8;
+    if ((rc = c->b_out.ensure(bytes))) return abi_rc(rc);
+    if ((rc = c->h_out.ensure(bytes))) return rc;
+    if ((rc = pc_fill_dev(c, metric, as_distance, c->b_out.p, c->stream, stats))) return rc;
+    if (np) PC_HIP(hipMemcpyAsync(c->h_out.p, c->b_out.p, (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    c->busy = false;
+    *out_host = c->h_out.as<double>();
+    return PC_OK;
+}
+
+extern "C" int pc_fill_shard_dev(pc_ctx* c, int metric, int as_distance, void* shard_dev, void* stream, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_shard_dev: upload first"); return PC_ERR_STATE; }
+    PC_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->shard_stride > c->shard_pairs)
+        PC_HIP(hipMemsetAsync((double*)shard_dev + c->shard_pairs, 0, (c->shard_stride - c->shard_pairs) * 8, st));
+    return fill_impl(c, metric, as_distance, (double*)shard_dev, 0, st, stats);
+}
+
+extern "C" int pc_assemble_dev(pc_ctx* c, const void* gathered_dev, int world, void* out_condensed_dev, void* stream) {
+    if (!c || !c->uploaded) { pc_set_error("pc_assemble_dev: upload first"); return PC_ERR_STATE; }
+    if (world != c->world) { pc_set_error("pc_assemble_dev: world %d != shard world %d", world, c->world); return PC_ERR_ARG; }
+    PC_ON_DEVICE(c);
+    if (c->balanced)
+        return pc_launch_assemble_table((const double*)gathered_dev, c->shard_stride, c->dev.N, c->b_t_rank.as<int32_t>(), c->b_t_lbase.as<int64_t>(),
+                                        (double*)out_condensed_dev, (hipStream_t)stream);
+    return pc_launch_assemble((const double*)gathered_dev, world, c->shard_stride, c->dev.N, (double*)out_condensed_dev,
+                              (hipStream_t)stream);
+}

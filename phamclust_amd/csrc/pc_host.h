@@ -1,0 +1,206 @@
+// pc_host.h -- internal header of the host units of libphamclust_hip.so (pc_ctx, pc_upload, pc_align, pc_fill, pc_multi.hip):
+// the context, its buffers and the helpers they share.  Not installed, not part of the C-ABI.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "pc_common.h"
+#include "../../include/phamclust_hip.h"
+
+// roctx range around a stage of a fill (the marker library is looked up in pc_ctx.hip)
+struct PcRange {
+    bool on;
+    explicit PcRange(const char* name);
+    ~PcRange();
+    PcRange(const PcRange&) = delete; PcRange& operator=(const PcRange&) = delete;
+};
+
+// internal status: a device allocation failed.  A chunked fill answers it with smaller chunks; at the C-ABI it is PC_ERR_HIP.
+constexpr int PC_ERR_NOMEM_INTERNAL = -100;
+// marks the planning stage of a fill: the test-hooks build refuses device allocations above PC_FAKE_OOM_ABOVE inside it (pc_ctx.hip)
+struct PlanningScope { PlanningScope(); ~PlanningScope(); };
+// Grow-only device buffer that owns its memory: freed when it goes out of scope, on whichever device is current then (the
+// context's destruction runs under its device guard).  Move-only, so that a std::vector of them can grow.
+struct DevBuf {
+    void* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~DevBuf() { release(); }
+    int ensure(size_t bytes);
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return (T*)p; }
+};
+// Grow-only page-locked host buffer: ensure(bytes) frees the old buffer first, then allocates bytes + bytes / 8.
+struct PinnedBuf {
+    void* p = nullptr; size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t bytes);
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// fn(begin, end) over [0, n) on up to 16 host threads (upload-time indexing of ~10^8 residues)
+template <class F> void parallel_chunks(int64_t n, F fn, int64_t grain = 4096) {
+    int nt = (int)std::min<int64_t>(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u), (n + grain - 1) / grain);
+    if (nt <= 1) { fn((int64_t)0, n); return; }
+    std::vector<std::thread> th;
+    const int64_t per = (n + nt - 1) / nt;
+    for (int t = 0; t < nt; ++t) th.emplace_back([=] { fn(std::min(n, t * per), std::min(n, (t + 1) * per)); });
+    for (auto& x : th) x.join();
+}
+
+static inline int abi_rc(int rc) { return rc == PC_ERR_NOMEM_INTERNAL ? PC_ERR_HIP : rc; }
+
+static int upload_raw(DevBuf& b, const void* p, size_t bytes) {
+    int rc = abi_rc(b.ensure(std::max<size_t>(bytes, 16)));
+    if (rc != PC_OK) return rc;
+    if (bytes) PC_HIP(hipMemcpy(b.p, p, bytes, hipMemcpyHostToDevice));
+    return PC_OK;
+}
+
+template <class T> int upload_vec(DevBuf& b, const std::vector<T>& v) {
+    int rc = abi_rc(b.ensure(std::max<size_t>(v.size() * sizeof(T), 16)));
+    if (rc != PC_OK) return rc;
+    if (!v.empty()) PC_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PC_OK;
+}
+
+struct pc_ctx {
+    int device = 0;
+    int n_cu = 256;                         // compute units of THIS context's device (grid sizing of the persistent tile kernels)
+    hipStream_t stream = nullptr;
+    bool uploaded = false;                  // part 1 of the upload is on the device (set metrics can run)
+    bool residues_ready = false;            // ... and part 2 (aai / peq, pc_align_pairs can run)
+    int64_t n_residue_bytes_in = 0;         // residue bytes of the packed genomes part 1 saw (part 2 must be given the same)
+    PcDev dev{};
+    std::vector<int32_t> h_gene_len;
+    std::vector<uint32_t> h_sp_n;                      // [N] a genome's entries of phams with at least two holders (k_sparse_col's pocp / af modes: values per block of targets)
+    int max_ent_len = 0;                               // largest summed length of a (genome, pham) entry (k_sparse_col's af mode keeps them as 16-bit values)
+    std::vector<uint8_t> h_gene_odd;                   // gene holds a byte outside the 24-letter alphabet
+    int max_gene_len = 0, min_gene_len = 0, max_nph = 0, max_ngen = 0;
+    int64_t max_tlen = 0;                    // largest summed translation length of a genome
+    double avg_shared = 0.0;                 // phams an average genome pair shares (pocp's kernel choice)
+    // kernel-variant classes over column genes
+    int ncls_all = 0;                       // BASE classes: variant * 4 + lanes-per-segment bucket (twice: "any byte" columns), last = general kernel
+    int nlc = 0;                            // launch classes = ncls_all * PC_WAVE_MODES (base class x workgroup shape of the task, pc_common.h)
+    std::vector<int32_t> cls_max_lb;        // [nlc] longest column sequence that can land in the launch class (LDS size of its launch)
+    PcTaskPlan task_plan{};
+    // shard
+    int rank = 0, world = 1;
+    int64_t shard_pairs = 0, shard_stride = 0;
+    PcShard shard{};
+    bool balanced = false;                  // cost-balanced deal in force (pc_set_shard_balanced): assembly goes through the tables
+    std::vector<uint64_t> target_cost;      // DP cells per target genome, computed once per upload
+    std::vector<int32_t> h_t_rank;          // the deal in force, host copy: owner rank of each target genome ...
+    std::vector<int64_t> h_t_lbase;         // ... and where its pairs start inside that rank's shard
+    std::vector<int32_t> h_owned;           // this rank's targets, ascending, and
+    std::vector<int64_t> h_lbase;           // [nown+1] the shard-local index of pair (0, owned[k]) (host copies of shard.owned / lbase)
+    // persistent device arrays
+    DevBuf b_raw, b_seq_tmp;                // part 2's staging: the raw residue bytes and their offsets, as uploaded (encoded into b_codes on the device)
+    DevBuf b_sets;                          // part 1 of the upload, one allocation: bitmap | rank table | gene lengths | entry offsets | nph | ngen | tlen | 4 entry arrays
+    PinnedBuf h_stage;                      // its page-locked host image
+    PinnedBuf h_raw;                        // page-locked staging of the raw residues (part 2; <= 512 MB)
+    DevBuf b_gene_off, b_codes;
+    DevBuf b_gene_q, b_q_gene, b_q_class, b_q_nseg, b_rem_class, b_cls_begin, b_task_rows, b_owned, b_lbase, b_t_rank, b_t_lbase, b_cost;
+    // work buffers (grow-only)
+    DevBuf b_na, b_off, b_key0, b_key1, b_val0, b_val1, b_sort_tmp, b_flags, b_excl, b_alias, b_start_q, b_end_q, b_ntask_q, b_task_off_q, b_scan_tmp;
+    DevBuf b_tasks, b_tasks_sorted, b_bucket_row, b_bucket_dest, b_res, b_totals, b_plan, b_scratch, b_out, b_lut, b_slice_begin, b_aln_t;
+    PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
+    // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
+    struct PlanState {
+        bool valid = false; int ppos = 0; int condensed = 1; int64_t A = 0, n_distinct = 0; uint32_t ntasks = 0;
+        int k0 = 0, k1 = 0;                 // the owned targets [k0, k1) the plan covers (a chunk of the shard, or all of it)
+        bool whole = false;                 // ... all of an unsharded context: what the alignment-sliced route needs
+        std::vector<uint32_t> tb;           // [ncls+1] task range per launch class in b_tasks_sorted
+        pc_stats st;                        // counts of the plan (alignments, cells, tasks, distinct ...)
+    } plan;
+    PinnedBuf h_out;                        // result buffer lent out by pc_fill_borrow
+    float last_align_ms = 0.f;              // kernel time of the last pc_align_pairs call
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    static constexpr int kAux = 15;         // + the caller's stream = up to 16 concurrent alignment launches (8 by default)
+    hipStream_t aux[kAux] = {};             // alignment launches of different classes overlap on these
+    hipEvent_t aux_ev[kAux + 1] = {};
+    int n_streams = 8;                      // streams actually used (tuning knob: env PC_ALIGN_STREAMS at ctx creation)
+    // Streams for the few launches whose TASKS run for tens of milliseconds (strip-mined passes over long genes).  Their own, so
+    // that no other launch queues up behind them -- the runtime lays streams over a handful of hardware queues, and a queue runs
+    // its launches one after the other: behind a 30-ms strip launch sat a dozen launches of a millisecond each -- and of HIGH
+    // priority: those streams get hardware queues of their own, and their waves go first where they compete (they are the
+    // fill's critical path).  PC_LONG_PRIORITY=0: ordinary priority.
+    static constexpr int kLong = 4;
+    hipStream_t lng[kLong] = {};
+    hipEvent_t lng_ev[kLong] = {};
+    int tie_rule = 0;                       // row of the aligner's tie-rule table (pc_set_tie_rule)
+    int64_t lut_key = -1; const double* lut_ptr = nullptr;   // what the gcs / jc epilogue table in b_lut was built for
+    hipEvent_t ev_last = nullptr;           // recorded at the end of every entry point that leaves work on a caller's stream
+    bool busy = false;                      // ev_last was recorded and not waited for yet
+    hipStream_t last_stream = nullptr;      // ... on this stream
+    int last_set_kernel = -1;               // kernel family the last gcs / jc / pocp / af fill ran on (pc_last_set_kernel)
+    int64_t plan_budget = 0;                // bytes of plan buffers one chunk of an aai / peq fill may use; 0: automatic (pc_set_plan_budget)
+};
+
+// Every entry point runs on the context's device and leaves the calling thread's current device as it found it
+// (PyTorch and other libraries in the process keep their own idea of "current device").
+struct PcDeviceGuard {
+    int prev = -1, dev = -1; bool ok = true;
+    explicit PcDeviceGuard(int device) : dev(device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) {
+            hipError_t e = hipSetDevice(dev);
+            if (e != hipSuccess) { pc_set_error("hipSetDevice(%d): %s", dev, hipGetErrorString(e)); ok = false; }
+        }
+    }
+    ~PcDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
+    PcDeviceGuard(const PcDeviceGuard&) = delete;
+    PcDeviceGuard& operator=(const PcDeviceGuard&) = delete;
+};
+#define PC_ON_DEVICE(c) PcDeviceGuard pc_guard_((c)->device); if (!pc_guard_.ok) return PC_ERR_HIP
+
+// A fill (or plan, slice, reduce) without stats returns while its kernels still run on the CALLER's stream and still use
+// the context's work buffers and shard tables.  Every such entry point ends in mark_work(): ONE event, recorded after its
+// last launch.  Anything that rewrites those buffers (upload, re-shard, the test hooks, work on another stream) first
+// waits for it.
+static int wait_last_work(pc_ctx* c, hipStream_t next_stream, bool same_stream_is_ordered) {
+    if (!c->busy) return PC_OK;
+    if (same_stream_is_ordered && next_stream == c->last_stream) return PC_OK;
+    PC_HIP(hipEventSynchronize(c->ev_last));
+    c->busy = false;
+    return PC_OK;
+}
+static int mark_work(pc_ctx* c, hipStream_t st) {
+    PC_HIP(hipEventRecord(c->ev_last, st));
+    c->busy = true; c->last_stream = st;
+    return PC_OK;
+}
+
+// Base class of a column gene: variant * 4 + bucket of lanes per segment (<=8, <=16, <=32, <=64); the same again,
+// nvar * 4 higher, for column genes that hold a byte outside the 24-letter alphabet ("any byte" classes: they must run
+// the residue-compare cell, see pc_common.h); then one class per wide variant for column genes longer than its 64 x W columns
+// (strip-mined passes, k_nw_strip); last class: the general kernel.
+#define PC_STRIP_CLASSES 3                                 // W = 32, 48, 64: the last three variants
+static int pc_num_classes() { return pc_nw_num_variants() * 8 + PC_STRIP_CLASSES + 1; }
+static int pc_class_of(int lb, int variant, bool any_byte) {
+    const int nvar = pc_nw_num_variants();
+    if (variant < 0) return nvar * 8 + PC_STRIP_CLASSES;
+    const int W = pc_nw_variant_w(variant);
+    if (lb > 64 * W) return nvar * 8 + std::max(0, variant - (nvar - PC_STRIP_CLASSES));       // strip-mined (the chooser only picks a wide variant for these)
+    const int Gs = (lb + W - 1) / W;
+    const int Gb = pc_nw_g_bucket(Gs);
+    return variant * 4 + (Gb == 8 ? 0 : Gb == 16 ? 1 : Gb == 32 ? 2 : 3) + (any_byte && !pc_nw_variant_takes_any_byte(variant) ? nvar * 4 : 0);
+}
+static int pc_class_variant(int cls) {
+    const int nvar = pc_nw_num_variants();
+    if (cls >= nvar * 8 + PC_STRIP_CLASSES) return -1;
+    if (cls >= nvar * 8) return nvar - PC_STRIP_CLASSES + (cls - nvar * 8);
+    return (cls % (nvar * 4)) / 4;
+}
+static int pc_class_compare_only(int cls) { const int nvar = pc_nw_num_variants(); return cls >= nvar * 4 && cls < nvar * 8; }
+// a launch whose longest column gene exceeds its variant's 64 x W columns runs strip-mined and needs the scratch slab
+static bool pc_launch_is_strip(int variant, int max_lb, int mode, int ppos) { return pc_nw_launch_is_strip(variant, max_lb, mode, ppos) != 0; }
+
+// aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
+int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);

@@ -223,7 +223,7 @@ static size_t systolic_lds_bytes(int W, int G, int nw, bool inc16, bool any_buck
                                              : (size_t)((pc_prof_rows(inc16) + rpl - 1) / rpl);
     return (size_t)(144 + nw * pc_wave_lds_dwords(nseg_max)) * 4 + lines * pc_prof_row_dwords(W, inc16) * 256;
 }
-// Lanes-per-segment bucket of a launch class (pc_api.hip's classes use the same bounds): every column gene of a launch
+// Lanes-per-segment bucket of a launch class (pc_host.h's classes use the same bounds): every column gene of a launch
 // lies in one bucket, so launch, task sizes and LDS agree on the waves per workgroup without passing it around
 int pc_nw_g_bucket(int G) { return G <= 8 ? 8 : (G <= 16 ? 16 : (G <= 32 ? 32 : 64)); }
 // Which cell a launch class runs (measured per class with the launches serialised, profiles/r02/experiments/l_class_times.txt):

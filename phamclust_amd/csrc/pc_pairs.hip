@@ -994,7 +994,7 @@ int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out,
 // pocp's paralog excess from an LDS list against the source row in the HBM bitmap -- 2.14 -- or against a per-wave bit set -- 1.69.)
 // Values are 16 bits: gene counts and summed lengths of an entry below 65,536, and a block's entries within what two workgroups per
 // CU leave beside masks, offsets and accumulators (~7,000 at 5,056 phams) -- the host checks both and sends the rest to k_sparse_tile64.
-// Needs 8 B x phams-with-two-holders of LDS beside the accumulators: up to 7,680 such phams; beyond, or for small matrices, the
+// Needs 8 B x phams-with-two-holders of LDS beside the accumulators: up to 7,872 such phams (pocp / af: 6,272); beyond, or for small matrices, the
 // kernels above run.  No MFMA: this is a sparse join, ~3 shared phams per pair.
 // ---------------------------------------------------------------------------------
 #define S7_SEG 8                                                  // source tiles per unit, at most (small matrices: fewer, see the launcher)
@@ -1220,7 +1220,7 @@ __global__ __launch_bounds__(64 * S7_WAVES, 8) void k_sparse_col(PcDev d, PcShar
     }
 }
 
-// LDS the column kernel takes for a collection with P64 mask entries; 0: it cannot run (masks beyond 7,680 phams)
+// LDS the column kernel takes for a collection with P64 mask entries; 0: it cannot run (masks beyond 7,872 phams; pocp / af: 6,272)
 // pocp / af: what two workgroups per CU leave for the targets' values, 16 bits each (+ one entry of padding); < 1,024: the mode is off
 int pc_sparse_col_vals_cap(int P64) {
     const long long room = 80 * 1024 - 256 - ((long long)P64 * 8 + (long long)S6_T * S6_LD * 4 + (long long)P64 * 2);

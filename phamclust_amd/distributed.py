@@ -298,7 +298,7 @@ def fill_condensed(ctx, metric, as_distance=True):
 
 
 def balanced_deal(costs, world, pair_floor=2000):
-    """Host mirror of pc_set_shard_balanced (csrc/pc_api.hip): target t costs ``costs[t] + t * pair_floor`` (its DP
+    """Host mirror of pc_set_shard_balanced (csrc/pc_upload.hip): target t costs ``costs[t] + t * pair_floor`` (its DP
     cells plus a floor per pair); targets go, heaviest first (ties: lower index), to the rank with the least work so
     far (ties: lowest rank).  Returns (t_rank[N], t_lbase[N], stride): pair (s, t) lives at
     gathered[t_rank[t] * stride + t_lbase[t] + s]."""

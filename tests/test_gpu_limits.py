@@ -21,7 +21,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-L = 65535                                                      # pc_upload's gene-length limit (pc_api.hip, upload_sets)
+L = 65535                                                      # pc_upload's gene-length limit (pc_upload.hip, upload_sets)
 AA = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
 
 
