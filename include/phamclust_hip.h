@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 152   /* 0.5.1: pc_task_shape, pc_ppos_width */
+#define PC_VERSION 153   /* 0.5.2: pc_last_plan_tasks, pc_bucket_launch_classes */
 
 typedef enum {
     PC_OK = 0,
@@ -262,6 +262,21 @@ int pc_variant_width(int lb);
  * streams per wave (segments; 1 when strip-mined), out[3] strip-mined passes of 64 x width columns (0: in registers).
  * An alignment stream of a full task carries out[0] / (out[1] * out[2]) alignments back to back. */
 int pc_task_shape(int lb, int width, int32_t* out);
+
+/* Test hook: how the HOST functions (variant chooser, task size, remainder chooser, task mode -- what the upload's planner
+ * tables and pc_align_pairs are made from) cut a bucket of `rows` distinct row sequences against a column gene of lb residues
+ * (any_byte != 0: it holds a byte outside the 24-letter alphabet): out[0] rows per task, out[1] rows that stay with the main
+ * variant (they form out[1] / out[0] full tasks), out[2] launch class of a full main task (stated also when there is none),
+ * out[3] launch class of the last, short main task of out[1] % out[0] rows or -1, out[4] launch class of the remainder task
+ * of rows - out[1] rows or -1.  A launch class is base class * 3 + mode (0 the class's own workgroup, 1 two waves, 2 one
+ * wave); base class = variant index * 4 + lanes-per-segment bucket, the same again 4 * variants higher for "any byte"
+ * columns, then one per strip-mined variant (W = 32, 48, 64), then the general kernel.  Reads no device table, launches nothing. */
+int pc_bucket_launch_classes(int lb, int rows, int any_byte, int32_t* out);
+
+/* Test hook: tasks per launch class of the context's last aai / peq / aai_ppos fill (any pc_fill* route), summed over its
+ * chunks, as the DEVICE planner cut them; after pc_plan_dev the whole plan's counts, after pc_align_slice_dev that slice's.
+ * Writes min(cap, n) entries and returns n, the number of launch classes; PC_ERR_STATE before the first such fill. */
+int pc_last_plan_tasks(const pc_ctx* ctx, int32_t* per_launch_class, int cap);
 
 /* Test hook: columns per lane of the systolic variant a percent-positives (aai_ppos) launch runs on when the longest
  * column gene of its class has max_lb residues; 0 = the general kernel. */

@@ -367,9 +367,10 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
     PcRange range("pc:align");
     pc_ctx::PlanState& P = c->plan;
     if (!P.valid) { pc_set_error("align: no plan (pc_plan_dev first)"); return PC_ERR_STATE; }
+    const int ncls = c->nlc;
+    c->aligned_tasks.assign(ncls, 0);
     if (P.A <= 0 || P.ntasks == 0) return PC_OK;
     int rc = PC_OK;
-    const int ncls = c->nlc;
     const PcTask* task_list = c->b_tasks_sorted.as<PcTask>();
     std::vector<uint32_t> tb = P.tb;
     if (slice_world > 1) {
@@ -384,6 +385,7 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
         PC_HIP(hipMemsetAsync(res, 0, (size_t)std::max<int64_t>(P.n_distinct, 1) * 8, st));
         task_list = c->b_tasks.as<PcTask>(); tb = sb;
     }
+    for (int i = 0; i < ncls; ++i) c->aligned_tasks[i] = tb[i + 1] - tb[i];
     return run_align_classes(c, task_list, tb.data(), c->cls_max_lb.data(), res, st, stats, P.ppos);
 }
 
@@ -400,8 +402,16 @@ static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res
     return pc_launch_walk(metric == PC_AAI ? PCW_AAI : PCW_PEQ, c->dev, sub, a, st);
 }
 
-static void add_plan_stats(pc_stats& acc, const pc_stats& ps) {
+// a finished chunk: its plan's counts, and its tasks per launch class for pc_last_plan_tasks
+static void add_plan_stats(pc_ctx* c, pc_stats& acc) {
+    const pc_stats& ps = c->plan.st;
     acc.n_tasks += ps.n_tasks; acc.n_distinct_alignments += ps.n_distinct_alignments; acc.n_distinct_cells += ps.n_distinct_cells;
+    for (size_t i = 0; i < c->aligned_tasks.size() && i < c->last_plan_tasks.size(); ++i) c->last_plan_tasks[i] += c->aligned_tasks[i];
+}
+static void set_last_plan_tasks(pc_ctx* c, const std::vector<uint32_t>& per_class) {
+    c->last_plan_tasks.assign(per_class.begin(), per_class.end());
+    c->last_plan_tasks.resize(c->nlc, 0);
+    c->last_plan_tasks_valid = true;
 }
 
 // aai / peq: COUNT once, then plan -> align -> reduce -- in one piece when the plan fits the budget, else chunk by chunk
@@ -409,6 +419,8 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
     int rc = PC_OK;
     if (!c->residues_ready) { pc_set_error("fill: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
     uint64_t tot[3] = {0, 0, 0};
+    c->last_plan_tasks_valid = false;
+    c->last_plan_tasks.assign(c->nlc, 0);
     if ((rc = stage_count(c, condensed, st, tot))) return rc;
     local.n_alignments = (int64_t)tot[0]; local.n_cells = (int64_t)tot[1]; local.n_residue_bytes = (int64_t)tot[2];
     const int nown = c->shard.nown;
@@ -429,8 +441,9 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
             rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st);
         }
         if (rc == PC_OK) {
-            add_plan_stats(local, c->plan.st);
+            add_plan_stats(c, local);
             local.n_chunks = 1;
+            c->last_plan_tasks_valid = true;
             PC_HIP(hipEventRecord(c->ev[3], st));
             return PC_OK;
         }
@@ -463,7 +476,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
         }
         if (rc != PC_OK) return rc;
         PC_HIP(hipEventRecord(c->ev[3], st));
-        add_plan_stats(local, c->plan.st);
+        add_plan_stats(c, local);
         if (timed) {
             float x = 0.f;
             PC_HIP(hipEventSynchronize(c->ev[3]));
@@ -475,6 +488,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
     }
     c->plan.valid = false;                                                // the last chunk's plan is not "the plan of the fill"
     local.n_chunks = nchunks;
+    c->last_plan_tasks_valid = true;
     local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;
     return PC_OK;
 }
@@ -504,6 +518,11 @@ extern "C" int pc_plan_dev(pc_ctx* c, int metric, void* stream, pc_stats* stats)
     (void)mark_work(c, st);
     if (rc != PC_OK) return abi_rc(rc);
     c->plan.st.n_cells = (int64_t)tot[1]; c->plan.st.n_residue_bytes = (int64_t)tot[2];
+    {   // pc_last_plan_tasks: the whole plan's tasks per launch class, until a slice of it is aligned
+        std::vector<uint32_t> per_class(c->nlc, 0);
+        for (int i = 0; i < c->nlc; ++i) per_class[i] = c->plan.tb[i + 1] - c->plan.tb[i];
+        set_last_plan_tasks(c, per_class);
+    }
     PC_HIP(hipEventRecord(c->ev[1], st));
     if ((rc = mark_work(c, st))) return rc;
     if (stats) {
@@ -529,6 +548,7 @@ extern "C" int pc_align_slice_dev(pc_ctx* c, int slice_rank, int slice_world, vo
     pc_stats local = c->plan.st;
     PC_HIP(hipEventRecord(c->ev[1], st));
     rc = stage_align(c, slice_rank, slice_world, (uint2*)res_dev, st, &local);
+    if (rc == PC_OK) set_last_plan_tasks(c, c->aligned_tasks);           // this slice's own counts
     PC_HIP(hipEventRecord(c->ev[2], st));
     int rc2 = mark_work(c, st);
     if (rc != PC_OK) return abi_rc(rc);
@@ -606,20 +626,14 @@ extern "C" int pc_align_pairs(pc_ctx* c, const int32_t* a_gene, const int32_t* b
             const int64_t k = order[i];
             int64_t j = i;
             while (j < n && cls[order[j]] == cls[k] && b_gene[order[j]] == b_gene[k]) ++j;
-            const int lb = c->h_gene_len[b_gene[k]], v = pc_class_variant(cls[k]);
+            const int lb = c->h_gene_len[b_gene[k]];
             const bool odd = c->h_gene_odd[b_gene[k]] != 0;
-            const int per = pc_nw_task_rows(lb, v, pc_class_compare_only(cls[k]));
-            int64_t jmain = j; int rem_cls = -1;
-            if (forced == -2 && v >= 0) {
-                const int W = pc_nw_variant_w(v), G = (lb + W - 1) / W, nseg = std::min(G > 64 ? 1 : 64 / G, 16);
-                const int r = nseg > 1 ? (int)((j - i) % nseg) : 0;
-                const int vr = r ? pc_nw_choose_remainder(lb, r, v) : -1;
-                if (vr >= 0) { jmain = j - r; rem_cls = pc_class_of(lb, vr, odd); }
-            }
+            const PcBucketCut cut = pc_bucket_cut(lb, j - i, cls[k], odd, forced == -2);
+            const int per = cut.per, rem_cls = cut.rem_base;
+            const int64_t jmain = i + cut.n_main;
             auto put = [&](int64_t r0, int64_t r1, int base) {
                 PcTask t; t.gene = b_gene[k]; t.begin = (int32_t)r0; t.end = (int32_t)r1;
-                const int mode = forced == -2 ? pc_nw_task_mode(lb, (int)(r1 - r0), pc_class_variant(base)) : PC_MODE_CLASS;
-                t.pad = base * PC_WAVE_MODES + mode;
+                t.pad = pc_task_launch_class(lb, (int)(r1 - r0), base, forced == -2);
                 cls_maxlb[t.pad] = std::max(cls_maxlb[t.pad], lb);
                 tasks.push_back(t);
             };

@@ -164,6 +164,27 @@ extern "C" int pc_task_shape(int lb, int width, int32_t* out) {
     out[3] = strip ? pc_nw_strip_passes(lb, v) : 0;
     return PC_OK;
 }
+// The host cut of one bucket, from the functions the upload's tables and pc_align_pairs are made from (pc_bucket_cut): nothing
+// here reads a device table or calls into pc_plan.hip, so a test can hold the device planner's counts against it.
+extern "C" int pc_bucket_launch_classes(int lb, int rows, int any_byte, int32_t* out) {
+    if (lb <= 0 || lb > 65535 || rows <= 0 || !out) { pc_set_error("pc_bucket_launch_classes: bad argument"); return PC_ERR_ARG; }
+    const int base = pc_class_of(lb, pc_nw_choose_variant(lb), any_byte != 0);
+    const PcBucketCut cut = pc_bucket_cut(lb, rows, base, any_byte != 0, true);
+    const int last = (int)(cut.n_main % cut.per);
+    out[0] = cut.per;
+    out[1] = (int32_t)cut.n_main;
+    out[2] = pc_task_launch_class(lb, cut.per, base, true);
+    out[3] = last ? pc_task_launch_class(lb, last, base, true) : -1;
+    out[4] = cut.rem_base >= 0 ? pc_task_launch_class(lb, (int)(rows - cut.n_main), cut.rem_base, true) : -1;
+    return PC_OK;
+}
+extern "C" int pc_last_plan_tasks(const pc_ctx* c, int32_t* per_launch_class, int cap) {
+    if (!c || cap < 0 || (cap > 0 && !per_launch_class)) { pc_set_error("pc_last_plan_tasks: bad argument"); return PC_ERR_ARG; }
+    if (!c->last_plan_tasks_valid) { pc_set_error("pc_last_plan_tasks: no aai / peq fill on this context yet"); return PC_ERR_STATE; }
+    const int n = (int)c->last_plan_tasks.size();
+    for (int i = 0; i < n && i < cap; ++i) per_launch_class[i] = (int32_t)std::min<int64_t>(c->last_plan_tasks[i], INT32_MAX);
+    return n;
+}
 extern "C" int pc_ppos_width(int max_lb) {
     int v = pc_nw_choose_variant(max_lb);                     // as run_align_classes' launch_variant picks it
     if (v >= 0 && !pc_nw_ppos_systolic(v, max_lb)) v = pc_nw_ppos_variant(max_lb);

@@ -119,6 +119,12 @@ struct pc_ctx {
         std::vector<uint32_t> tb;           // [ncls+1] task range per launch class in b_tasks_sorted
         pc_stats st;                        // counts of the plan (alignments, cells, tasks, distinct ...)
     } plan;
+    // tasks per launch class: what the last stage_align launched (all of a plan's tasks, or one slice of them) ...
+    std::vector<uint32_t> aligned_tasks;    // [nlc]
+    // ... and what pc_last_plan_tasks reports: the sum over the chunks of the last aai / peq fill; after pc_plan_dev the whole
+    // plan's counts, after pc_align_slice_dev that slice's
+    std::vector<int64_t> last_plan_tasks;   // [nlc]
+    bool last_plan_tasks_valid = false;
     PinnedBuf h_out;                        // result buffer lent out by pc_fill_borrow
     float last_align_ms = 0.f;              // kernel time of the last pc_align_pairs call
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -199,6 +205,26 @@ static int pc_class_variant(int cls) {
     return (cls % (nvar * 4)) / 4;
 }
 static int pc_class_compare_only(int cls) { const int nvar = pc_nw_num_variants(); return cls >= nvar * 4 && cls < nvar * 8; }
+// How a bucket of `rows` distinct rows against a column gene of lb residues is cut into tasks -- the host statement of the cut
+// that pc_plan.hip makes on the device from the upload's tables (q_class, q_nseg, task_rows, rem_class): pc_align_pairs cuts its
+// buckets with it and pc_bucket_launch_classes reports it.  base: the column gene's base class (pc_class_of of its variant);
+// move_remainder: the left-over rows of a wave round may go to the remainder chooser's variant (the automatic variant only).
+struct PcBucketCut { int per; int64_t n_main; int rem_base; };     // rows per main task, rows of the main tasks, base class of the remainder task (-1: none)
+static PcBucketCut pc_bucket_cut(int lb, int64_t rows, int base, bool any_byte, bool move_remainder) {
+    const int v = pc_class_variant(base);
+    PcBucketCut cut{pc_nw_task_rows(lb, v, pc_class_compare_only(base)), rows, -1};
+    if (move_remainder && v >= 0) {
+        const int W = pc_nw_variant_w(v), G = (lb + W - 1) / W, nseg = std::min(G > 64 ? 1 : 64 / G, 16);
+        const int r = nseg > 1 ? (int)(rows % nseg) : 0;
+        const int vr = r ? pc_nw_choose_remainder(lb, r, v) : -1;
+        if (vr >= 0) { cut.n_main = rows - r; cut.rem_base = pc_class_of(lb, vr, any_byte); }
+    }
+    return cut;
+}
+// launch class of a task of `rows` rows of that bucket on base class `base`; modes: 0 = every task in its class's own workgroup shape (a forced variant)
+static int pc_task_launch_class(int lb, int rows, int base, bool modes) {
+    return base * PC_WAVE_MODES + (modes ? pc_nw_task_mode(lb, rows, pc_class_variant(base)) : (int)PC_MODE_CLASS);
+}
 // a launch whose longest column gene exceeds its variant's 64 x W columns runs strip-mined and needs the scratch slab
 static bool pc_launch_is_strip(int variant, int max_lb, int mode, int ppos) { return pc_nw_launch_is_strip(variant, max_lb, mode, ppos) != 0; }
 

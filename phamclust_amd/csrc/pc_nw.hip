@@ -355,7 +355,11 @@ int pc_nw_fuse_key(int variant, int max_lb, int ppos, int compare_only, int wave
     const int W = sh.W, G = std::min(64, (max_lb + W - 1) / W);
     const int gb = wave_mode == PC_MODE_CLASS ? 0 : (pc_nw_g_bucket(G) == 8 ? 1 : pc_nw_g_bucket(G) == 16 ? 2 : pc_nw_g_bucket(G) == 32 ? 3 : 4);
     const int key = (((tier * 2 + (sh.inc16 ? 1 : 0)) * 16 + sh.nw) * 8 + gb);
-    return off ? key * 64 + variant * 0 + 1000000 + (variant * 4096 + max_lb % 4096) : key;   // PC_FUSE=0: every class its own launch (A/B)
+    // PC_FUSE=0 (A/B): every launch class its own launch, so a key per (variant, cell, mode, lanes-per-segment bucket) -- what tells the
+    // launch classes apart.  (The key was once mixed from the shared key and max_lb % 4096: two classes of different workgroup size
+    // could collide and were refused as one group.)
+    const int bucket = pc_nw_g_bucket(G) == 8 ? 0 : pc_nw_g_bucket(G) == 16 ? 1 : pc_nw_g_bucket(G) == 32 ? 2 : 3;
+    return off ? 1000000 + ((variant * 2 + (compare_only ? 1 : 0)) * PC_WAVE_MODES + wave_mode) * 4 + bucket : key;
 }
 
 template <int TIER, bool INC16>

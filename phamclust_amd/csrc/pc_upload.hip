@@ -452,7 +452,7 @@ static int upload_residues(pc_ctx* c, const pc_packed* g) {
     {   // "any byte" classes a remainder may be sent to: their longest column gene (serial, rare)
         for (int u = 0; u < U; ++u) {
             const int len = gene_len[u_gene[u]];
-            if (!godd[u_gene[u]] || u_cls[u] == len_cls[len] || u_cls[u] == ncls_all - 1) continue;
+            if (!godd[u_gene[u]] || u_cls[u] == ncls_all - 1) continue;       // (also where the MAIN variant takes any byte: a narrower remainder variant may not)
             for (int r = 1; r < 16; ++r) {
                 const uint8_t cr = len_rem[(size_t)len * 16 + r];
                 if (cr == 255) continue;
@@ -468,9 +468,11 @@ static int upload_residues(pc_ctx* c, const pc_packed* g) {
             q_gene[q] = u_gene[u];
             q_class[q] = (uint8_t)u_cls[u];
             if (u_cls[u] == ncls_all - 1) { task_rows[q] = pc_nw_task_rows(len, -1, 0); q_nseg[q] = 1; }   // general kernel (rem_class stays 255: no remainder move)
-            else if (!godd[u_gene[u]] || u_cls[u] == len_cls[len]) { task_rows[q] = len_rows[len]; q_nseg[q] = len_nseg[len]; memcpy(&rem_class[(size_t)q * 16], &len_rem[(size_t)len * 16], 16); }
-            else {                                                   // "any byte" class: its own task size, remainders to the "any byte" class of their variant
-                task_rows[q] = pc_nw_task_rows(len, len_var[len], 1); q_nseg[q] = len_nseg[len];
+            else if (!godd[u_gene[u]]) { task_rows[q] = len_rows[len]; q_nseg[q] = len_nseg[len]; memcpy(&rem_class[(size_t)q * 16], &len_rem[(size_t)len * 16], 16); }
+            else {                                                   // "any byte" column: its class's own task size, remainders to the "any byte" class of their variant
+                // (also when the main variant takes any byte itself and so keeps its class, W = 32 at 641 ... 672 residues: the remainder
+                // chooser sends its left-over rows to W = 11, which does not -- as pc_bucket_cut states it for pc_align_pairs)
+                task_rows[q] = u_cls[u] == len_cls[len] ? len_rows[len] : pc_nw_task_rows(len, len_var[len], 1); q_nseg[q] = len_nseg[len];
                 for (int r = 1; r < 16; ++r) {
                     const uint8_t cr = len_rem[(size_t)len * 16 + r];
                     if (cr == 255) continue;

@@ -50,7 +50,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_shard_pairs", "pc_shard_stride", "pc_fill", "pc_fill_borrow", "pc_fill_dev", "pc_fill_shard_dev", "pc_assemble_dev",
            "pc_align_pairs", "pc_last_align_ms", "pc_round6_probe", "pc_set_tie_rule", "pc_get_tie_rule", "pc_shard_table", "pc_target_costs",
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
-           "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_last_set_kernel", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
+           "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
@@ -95,6 +95,8 @@ def load():
     L.pc_variant_width.argtypes = [ctypes.c_int]
     L.pc_task_shape.argtypes = [ctypes.c_int, ctypes.c_int, _i32p]
     L.pc_ppos_width.argtypes = [ctypes.c_int]
+    L.pc_bucket_launch_classes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p]
+    L.pc_last_plan_tasks.argtypes = [vp, _i32p, ctypes.c_int]
     L.pc_set_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.pc_set_shard_balanced.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.pc_shard_pairs.argtypes = [vp]
@@ -429,6 +431,38 @@ class Context:
         """Columns per lane of the variant a percent-positives launch runs on when its longest column gene has ``max_lb``
         residues (0: general kernel)."""
         return int(load().pc_ppos_width(int(max_lb)))
+
+    WAVE_MODES = 3                      # launch class = base class * WAVE_MODES + mode (0 class's own workgroup, 1 two waves, 2 one wave)
+
+    @staticmethod
+    def bucket_launch_classes(lb, rows, any_byte=False):
+        """The HOST cut of a bucket of ``rows`` distinct rows against a column gene of ``lb`` residues (``any_byte``: it
+        holds a byte outside the alphabet): dict of rows per task, rows kept by the main variant, and the launch classes
+        of a full main task, of the last short main task (-1: none) and of the remainder task (-1: none)."""
+        out = np.zeros(5, dtype=np.int32)
+        if load().pc_bucket_launch_classes(int(lb), int(rows), int(bool(any_byte)), _ptr(out, _i32p)) != 0:
+            raise HipLibraryError(load().pc_last_error().decode())
+        return dict(zip(("per", "n_main", "full", "last", "rem"), out.tolist()))
+
+    @staticmethod
+    def bucket_tasks(lb, rows, any_byte=False):
+        """{launch class: tasks} of that bucket, from :meth:`bucket_launch_classes`."""
+        cut = Context.bucket_launch_classes(lb, rows, any_byte)
+        tasks = {}
+        for cls, n in ((cut["full"], cut["n_main"] // cut["per"]), (cut["last"], 1), (cut["rem"], 1)):
+            if cls >= 0 and n > 0:
+                tasks[cls] = tasks.get(cls, 0) + n
+        return tasks
+
+    def last_plan_tasks(self):
+        """Tasks per launch class (int32 array) of this context's last aai / peq / aai_ppos fill as the device planner
+        cut them, summed over its chunks; after plan_dev the whole plan's, after align_slice_dev that slice's."""
+        n = self._lib.pc_last_plan_tasks(self._h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(n, dtype=np.int32)
+        self._check(min(0, self._lib.pc_last_plan_tasks(self._h, _ptr(out, _i32p), n)))
+        return out
 
     def last_align_ms(self):
         return float(self._lib.pc_last_align_ms(self._h))

@@ -621,6 +621,7 @@ def test_redundant_sequences_are_aligned_once(gpu_ctx, native_built):
     from phamclust_amd.genome import Genome
     from phamclust_amd.pack import pack_genomes
     from phamclust_amd.synth import synth_genomes
+    import planner_cases
     O = _oracle()
     base = synth_genomes(24, 300, seed=11)
     genomes = list(base)
@@ -639,6 +640,8 @@ def test_redundant_sequences_are_aligned_once(gpu_ctx, native_built):
         got, st = gpu_ctx.upload(packed).fill(metric, as_distance=True, want_stats=True)
         assert np.array_equal(got, O.fill(packed, metric, as_distance=True))
         assert 0 < st["n_distinct_alignments"] < 0.7 * st["n_alignments"] and st["n_distinct_cells"] < st["n_cells"]
+        recount = planner_cases.count(packed)               # the same counters from the packed arrays alone (anchor rule, distinct byte pairs)
+        assert all(st[name] == recount[name] for name in ("n_alignments", "n_distinct_alignments", "n_cells", "n_distinct_cells")), st
     clones = []                                             # 40 copies of one genome: one distinct alignment per gene
     for i in range(40):
         g = Genome(f"same_{i:02d}")
@@ -650,6 +653,8 @@ def test_redundant_sequences_are_aligned_once(gpu_ctx, native_built):
     got, st = gpu_ctx.upload(packed).fill("peq", as_distance=False, want_stats=True)
     assert np.array_equal(got, O.fill(packed, "peq", as_distance=False)) and (got == 1.0).all()
     assert st["n_alignments"] >= 780 * st["n_distinct_alignments"] > 0
+    recount = planner_cases.count(packed)
+    assert st["n_alignments"] == recount["n_alignments"] and st["n_distinct_alignments"] == recount["n_distinct_alignments"]
     got, st = gpu_ctx.upload(pack_genomes(base)).fill("peq", want_stats=True)      # the synthetic set itself: next to nothing aliased
     assert 0.99 * st["n_alignments"] < st["n_distinct_alignments"] <= st["n_alignments"] and st["n_distinct_cells"] <= st["n_cells"]
 
@@ -1262,6 +1267,10 @@ def test_chunked_fill_is_the_unchunked_matrix(gpu_ctx, native_built):
         gpu_ctx.set_plan_budget(56)
         got_aai, st = gpu_ctx.fill("aai", want_stats=True)
         assert st["n_chunks"] >= 100 and np.array_equal(got_aai, want_aai)
+        import planner_cases
+        recount = planner_cases.count(small)                # exactly where pc_chunk_plan cuts, and the counters of all chunks together
+        assert st["n_chunks"] == len(gpu_ctx.chunk_plan(recount["per_target"], 1)) - 1
+        assert st["n_alignments"] == recount["n_alignments"] and st["n_cells"] == recount["n_cells"]
         # the alignment-sliced route keeps ONE whole plan: a chunk's plan is not accepted in its place
         with pytest.raises(Exception):
             gpu_ctx.align_slice_dev(0, 1, a.data_ptr(), torch.cuda.current_stream().cuda_stream)

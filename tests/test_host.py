@@ -310,6 +310,87 @@ def test_task_shape_and_percent_positives_route(native_built):
     for lb, w in ((100, 1), (65536, 0), (0, 0)):
         with pytest.raises(hip.HipLibraryError):
             C.task_shape(lb, w)
+    # the bucket hook agrees with the shape hook: same task size, and a bucket of exactly one wave round / one task is one task
+    for lb in (1, 100, 650, 1536, 1537, 4096, 4097, 65535):
+        shape, cut = C.task_shape(lb), C.bucket_launch_classes(lb, C.task_shape(lb)["rows"])
+        assert cut["per"] == cut["n_main"] == shape["rows"] and cut["last"] == cut["rem"] == -1 and cut["full"] % 3 == (2 if shape["rows"] <= shape["streams"] else 0)
+        assert C.bucket_tasks(lb, shape["streams"]) == {cut["full"] - cut["full"] % 3 + 2: 1}
+    assert hip.load().pc_last_plan_tasks(None, None, 0) == hip.load().pc_bucket_launch_classes(100, 1, 0, None) == -1       # PC_ERR_ARG
+
+
+def test_bucket_launch_classes_hook(native_built):
+    """pc_bucket_launch_classes, the host cut of one bucket (no GPU call): task size, rows kept by the main variant and the
+    launch classes of a full, a last and a remainder task, at shapes worked out by hand from pc_nw.hip; pc_last_plan_tasks
+    refuses a NULL context."""
+    from phamclust_amd import hip
+    C = hip.Context
+    # 100 residues: W = 13 (variant index 11), 8 lanes per segment (bucket <= 8), 8 segments per wave -> base class 11 * 4 + 0
+    cut = C.bucket_launch_classes(100, 208 + 8, False)
+    assert cut["per"] == 208 and cut["n_main"] == 216 and cut["full"] == 44 * 3 and cut["last"] == 44 * 3 + 2 and cut["rem"] == -1
+    assert C.bucket_tasks(100, 208 + 8) == {44 * 3: 1, 44 * 3 + 2: 1}
+    assert C.bucket_launch_classes(100, 16, False)["last"] == 44 * 3 + 1        # 2 x 8 rows: two waves
+    assert C.bucket_launch_classes(100, 16, True)["last"] == (24 * 4 + 44) * 3 + 1      # the "any byte" classes lie 24 x 4 higher
+    # a moved remainder: 9 = 8 + 1 rows; the single left-over row goes to the cheapest step with one segment, W = 2 on 50 lanes
+    # (variant 0, bucket <= 64), in a one-wave workgroup
+    cut = C.bucket_launch_classes(100, 9, False)
+    assert cut["n_main"] == 8 and cut["last"] == 44 * 3 + 2 and cut["rem"] == (0 * 4 + 3) * 3 + 2
+    assert C.bucket_launch_classes(100, 9, True)["rem"] == (24 * 4 + 3) * 3 + 2
+    # 650 residues: W = 32 takes any byte itself and keeps its class; its remainder variant (W = 11) does not
+    clean, odd = C.bucket_launch_classes(650, 4, False), C.bucket_launch_classes(650, 4, True)
+    assert clean["full"] == odd["full"] and clean["rem"] == (9 * 4 + 3) * 3 + 2 and odd["rem"] == clean["rem"] + 24 * 4 * 3
+    # strip-mined: one row per wave, four rows per task; classes follow the 2 x 24 x 4 systolic ones
+    assert C.bucket_tasks(4097, 9) == {192 * 3: 2, 192 * 3 + 2: 1} and C.bucket_tasks(8193, 2, True) == {193 * 3 + 1: 1}
+    for lb, rows in ((0, 1), (65536, 1), (10, 0)):
+        with pytest.raises(hip.HipLibraryError):
+            C.bucket_launch_classes(lb, rows)
+    assert hip.load().pc_last_plan_tasks(None, None, 0) == -1
+
+
+# launch classes no collection reaches in a default process (each with its reason); tests/test_gpu_planner.py's collection
+# must reach every other one
+UNREACHED_BY_DESIGN = {
+    195 * 3: "general kernel: needs PC_STRIP=0 or percent-positives beyond 8,191 columns (test_launch_policy_switches_change_no_value, tests/test_gpu_limits.py)",
+    194 * 3: "strip-mined W = 64: the chooser's cost model never prefers 4,096-column passes for a gene of up to 65,535 residues; forced in tests/test_gpu_limits.py",
+    194 * 3 + 1: "strip-mined W = 64, two waves: as above",
+    194 * 3 + 2: "strip-mined W = 64, one wave: as above",
+}
+
+
+def test_planner_collection_reaches_every_launch_class(native_built):
+    """The collection tests/test_gpu_planner.py drives through the fills covers the device planner's choices: the launch
+    classes the host cut predicts for its buckets EQUAL the reachable set -- every class pc_bucket_launch_classes returns for
+    a column of 1 ... 4,096 residues with 1 ... 2 x 208 + 16 rows, clean or not, plus the strip-mined classes in the modes
+    pc_task_shape gives them and the general kernel -- except the classes listed above.  Fails, naming the class, when a
+    variant, a tier or a mode is added without a case that reaches it, or when a case that alone reached one is dropped."""
+    import planner_cases as pc
+    from phamclust_amd import hip
+    C = hip.Context
+    lib, out = hip.load(), np.zeros(5, dtype=np.int32)
+    ptr = out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    reachable = set()
+    for lb in range(1, pc.MAX_LB + 1):
+        for any_byte in (0, 1):
+            for rows in range(1, pc.MAX_ROWS + 1):
+                assert lib.pc_bucket_launch_classes(lb, rows, any_byte, ptr) == 0
+                per, n_main, full, last, rem = out.tolist()
+                reachable.update(c for c in (full if n_main >= per else -1, last, rem) if c >= 0)
+    n_systolic = 24 * 8 * 3
+    assert max(reachable) < n_systolic
+    for k, w in enumerate((32, 48, 64)):                                     # a gene beyond the variant's 64 x W columns: one row per wave
+        rows = C.task_shape(64 * w + 1, w)["rows"]
+        assert C.task_shape(64 * w + 1, w)["passes"] == 2 and rows >= 3
+        reachable.update(n_systolic + 3 * k + mode for mode in range(3))    # (<= 1 row: one wave, <= 2: two waves, else the class's workgroup)
+    reachable.add(n_systolic + 9)                                           # the general kernel has no small-task modes
+    cases = pc.design(C)
+    reached = pc.classes_of(C, cases)
+    assert len(UNREACHED_BY_DESIGN) == 4 and set(UNREACHED_BY_DESIGN) <= reachable
+    missing = reachable - set(reached) - set(UNREACHED_BY_DESIGN)
+    assert not missing, "no case of the collection reaches: " + "; ".join(f"{c} ({pc.class_name(C, c)})" for c in sorted(missing))
+    assert set(reached) == reachable - set(UNREACHED_BY_DESIGN), sorted(set(reached) - reachable)
+    # the check has teeth: without the cases of 650 residues' neighbours (the W = 32 island at 641 ... 672) classes go missing
+    fewer = pc.classes_of(C, [case for case in cases if not 641 <= case[0] <= 672])
+    assert reachable - set(fewer) - set(UNREACHED_BY_DESIGN)
+    assert all(1 <= lb <= 65535 and 1 <= rows <= pc.MAX_ROWS for lb, rows, _ in cases)
 
 
 def test_borrowed_array_guards_every_numpy_route():
