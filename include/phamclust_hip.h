@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 153   /* 0.5.2: pc_last_plan_tasks, pc_bucket_launch_classes */
+#define PC_VERSION 154   /* 0.5.3: pc_set_kernel_choice, pc_set_launch_shape, pc_set_max_block_entries, pc_last_set_launch */
 
 typedef enum {
     PC_OK = 0,
@@ -290,6 +290,54 @@ float pc_last_align_ms(const pc_ctx* ctx);
  * of source tiles); -1 before the first such fill.  (The selector reads the collection:
  * genomes, bitmap words, phams an average pair shares -- metrics.py:26-157 have one code path, this has four.) */
 int pc_last_set_kernel(const pc_ctx* ctx);
+
+/*
+ * Test hooks: the set-metric selector and the launch shapes as host arithmetic (no GPU call, no context, no environment read).
+ * The fills call the same two functions: pick the family from pc_set_inputs, then size the launch with pc_set_launch_shape.
+ */
+typedef enum { PC_SET_POPC = 0, PC_SET_SPARSE32 = 1, PC_SET_SPARSE64 = 2, PC_SET_WALKER = 3, PC_SET_SPARSE_COL = 4 } pc_set_family;
+typedef struct pc_set_inputs {      /* what the selector reads; counted at upload, nown / max_block_entries per shard */
+    int64_t n, nown;                /* genomes; target genomes this rank owns (n when unsharded)                          */
+    int32_t words;                  /* bitmap words per row                                                                 */
+    int32_t two_holder;             /* phams at least two genomes hold (the mask entries of the sparse kernels)            */
+    double avg_shared;              /* phams an average pair shares: sum over phams of holders (holders - 1) / (n (n - 1)) */
+    int32_t max_nph, max_ngen;      /* most phams, most genes of a genome                                                   */
+    int32_t min_gene_len;           /* shortest translation (0: an empty one)                                               */
+    int32_t max_ent_len;            /* largest summed translation length of one (genome, pham) entry                      */
+    int64_t max_tlen;               /* largest summed translation length of a genome                                        */
+    int64_t max_block_entries;      /* most entries of two-holder phams in one block of 64 consecutive owned targets         */
+    int32_t metric;                 /* PC_GCS ... PC_AF                                                                      */
+    int32_t forced;                 /* -1, or the pc_set_family that PC_SET_KERNEL names                                    */
+} pc_set_inputs;
+typedef struct pc_set_shape {
+    int32_t family;                 /* pc_set_family                                                                        */
+    int32_t tile;                   /* tile edge in genomes: 32 or 64                                                       */
+    int32_t super_edge;             /* super-tile edge of the XCD-aware deal in tiles (1, 2, 4, 8, 16); 0: column kernel    */
+    int32_t grid;                   /* workgroups                                                                           */
+    int32_t units;                  /* tile slots (column kernel: target blocks x runs) dealt to them                       */
+    int32_t units_per_wg;           /* most units one workgroup takes (1, or several on the 64 x 64 sparse tiles)           */
+    int32_t chunks, chunk;          /* mask chunks and mask entries per chunk (sparse families; else 0)                     */
+    int32_t batches;                /* 64 x 64 sparse tiles: 2 = one chunk holds all masks, 1 = the chunked instance        */
+    int32_t dense;                  /* ... and 1 when the instance stages broadcast entries through LDS (af, two-batch)     */
+    int32_t seg, runs;              /* column kernel: source tiles per unit, runs of them per target block                 */
+    int32_t lds;                    /* dynamic LDS bytes of the launch                                                      */
+    int32_t table;                  /* popcount tiles: 1 epilogue table, 0 division in place                                */
+    int32_t vals_cap;               /* column kernel, pocp / af: entries a block's LDS value table holds (0: cannot run)    */
+    int32_t reserved;
+} pc_set_shape;
+/* pc_set_inputs.max_block_entries as the fills count it: entries_per_genome[g] = genome g's entries of two-holder phams, owned = the
+ * rank's targets, ascending; blocks of 64 consecutive owned targets, the last one ragged. */
+int64_t pc_set_max_block_entries(const uint32_t* entries_per_genome, const int32_t* owned, int64_t nown);
+/* The selector: the family (pc_set_family) a fill with these inputs runs on; PC_ERR_ARG for a metric that is no set metric. */
+int pc_set_kernel_choice(const pc_set_inputs* in);
+/* The launch shape of `family` for (metric, n, nown, words, two_holder) on a device of n_cu compute units (<= 0: 256).
+ * table_top: most phams (gcs / jc) or genes (pocp) of a genome, for the popcount tiles' epilogue table.  knobs: NULL or the
+ * values of PC_POPC_TILE, PC_S64_CHUNKS, PC_COL_SEG (0: unset), which the launchers read from the environment. */
+int pc_set_launch_shape(int family, int metric, int64_t n, int64_t nown, int words, int two_holder, int n_cu, int table_top,
+                        const int32_t* knobs, pc_set_shape* out);
+/* The selector inputs and the launch shape (knobs applied) of the context's last gcs / jc / pocp / af fill; either pointer may
+ * be NULL.  PC_ERR_STATE before the first such fill. */
+int pc_last_set_launch(const pc_ctx* ctx, pc_set_inputs* in, pc_set_shape* shape);
 
 /* Test hook: the device implementation of Python's round(x, 6) (the rounding every metric
  * returns through, e.g. metrics.py:50-53) applied to n host doubles in [0, 2^20). */

@@ -108,19 +108,31 @@ void pc_set_error(const char* fmt, ...);
         if (_e != hipSuccess) { pc_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); return PC_ERR_HIP; } \
     } while (0)
 
-// launchers (defined next to their kernels)
+// The set metrics' kernel families (pc_set_family of the C-ABI; pc_last_set_kernel) and their launch shapes.  pc_set_shape_of is the one
+// statement of every launcher's arithmetic (pc_pairs.hip): tile and super-tile edge, grid, units per workgroup, mask chunks, instance,
+// seg / runs, LDS, epilogue table.  It reads nothing but its arguments; the launchers pass it the knobs they read from the environment.
+enum { K_POPC, K_SPARSE32, K_SPARSE64, K_WALKER, K_SPARSE_COL };
+struct pc_set_shape;
+struct PcSetKnobs { int popc_tile, s64_chunks, col_seg; };        // PC_POPC_TILE, PC_S64_CHUNKS, PC_COL_SEG; 0: unset
+PcSetKnobs pc_set_knobs_env();                                    // (read per launch: the tests switch them between fills)
+// metric: PC_GCS ... PC_AF; sp_W: 64-id words of the phams with two holders; table_top: max_nph (gcs / jc) or max_ngen (pocp)
+void pc_set_shape_of(int family, int metric, int N, int nown, int Wb, int sp_W, int n_cu, int table_top, const PcSetKnobs& knobs, pc_set_shape* out);
+// dimensions of the popcount tiles' epilogue table; false: too large (4 Mi entries), the division runs in place
+bool pc_set_table_dims(int metric, int top, int* sh_dim, int* tot_dim);
+
+// launchers (defined next to their kernels); shape_out: NULL or where the shape they launched with is left
 int pc_launch_set_popc(const PcDev& d, const PcShard& sh, int metric, int as_distance, double* out, int condensed,
-                       double* lut, bool build_lut, int sh_dim, int tot_dim, hipStream_t st);
-int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st);
-int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st);   // pocp / af
+                       double* lut, bool build_lut, int top, hipStream_t st, pc_set_shape* shape_out = nullptr);
+int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st, pc_set_shape* shape_out = nullptr);
+int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);   // pocp / af
 int pc_launch_pair_entries(const int32_t* pham, const int32_t* len, const int32_t* cnt, uint2* pair_len, uint2* pair_cnt, int64_t n, hipStream_t st);
 int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, const int32_t* len, const int32_t* cnt, const int32_t* dense, int W2,
                        int32_t* sp_pham, uint2* sp_len, uint2* sp_cnt, uint32_t* sp_rank, uint32_t* sp_end, hipStream_t st);
-int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st); // pocp / af, large matrices
+int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr); // pocp / af, large matrices
 // k_sparse_col (gcs / jc / pocp / af, large matrices): masks over a block of target genomes kept in LDS across a run of source tiles
 size_t pc_sparse_col_lds(int mode, int P64);      // 0: the masks do not fit
 int pc_sparse_col_vals_cap(int P64);             // pocp / af: entries (of phams with two holders) a block of 64 targets may hold
-int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st);
+int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);
 int pc_scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* tmp, int64_t tmp_elems, hipStream_t st);
 int64_t pc_scan_tmp_elems(int64_t n);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to

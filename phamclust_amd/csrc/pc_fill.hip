@@ -5,7 +5,6 @@
 #ifndef PC_COL_MIN_N
 #define PC_COL_MIN_N 2200        // genomes from which k_sparse_col takes over from the popcount tiles (r05 sweep: profiles/r05/experiments/sparse_col.txt)
 #endif
-enum { K_POPC, K_SPARSE32, K_SPARSE64, K_WALKER, K_SPARSE_COL };   // the set metrics' kernel families (pc_last_set_kernel)
 
 // Which kernel fills a set metric (measured crossovers, `profiles/r03/experiments/p_sparse64_record.txt`, `r03_z_pocp_kernel_by_density.txt`;
 // PC_SET_KERNEL = popc | sparse | sparse64 | sparsecol | walker forces one where it exists, applied last, for A/B runs and for the
@@ -23,17 +22,19 @@ enum { K_POPC, K_SPARSE32, K_SPARSE64, K_WALKER, K_SPARSE_COL };   // the set me
 // The 64 x 64 kernel takes "sum == 0" for "no shared pham" and sums in 32 bits: it needs every entry value >= 1 (a
 // genome with an empty translation fails that for af) and genome totals below 2^31; else af falls back to the
 // 32 x 32 kernel / the shared-pham walker (crossover ~3,500 genomes), pocp to the popcount tiles.
-static int pick_set_kernel(const pc_ctx* c, int metric) {
-    const PcDev& d = c->dev;
+// The choice itself is pc_set_choice: a function of pc_set_inputs alone (pc_set_kernel_choice of the C-ABI); pick_set_kernel gathers
+// the inputs from the context and the environment.
+static int pc_set_choice(const pc_set_inputs& in) {
     int kernel = K_POPC;
-    const char* set_force = getenv("PC_SET_KERNEL");                   // (read per fill: the tests switch it between launches)
-    const int64_t area = (int64_t)d.N * c->shard.nown;
-    const double shared = std::max(c->avg_shared, 0.0);
+    const int metric = in.metric, Wb = in.words;
+    const int P64 = std::max(1, (in.two_holder + 63) / 64) * 64;       // mask entries: the phams with two holders, in 64-id words
+    const int64_t area = in.n * in.nown;
+    const double shared = std::max(in.avg_shared, 0.0);
     const bool counts = metric == PC_GCS || metric == PC_JC;
-    const bool s64_ok = counts ? c->max_nph < (1 << 30) : metric == PC_POCP ? c->max_ngen < (1 << 16) /* two gene counts per register */ : (c->min_gene_len >= 1 && c->max_tlen < (int64_t)1 << 31);
-    if (counts) kernel = (((double)d.Wb > 113.0 + 5.4 * shared && area >= (int64_t)3000 * 3000) ||
-                          ((double)d.Wb > 60.0 + 5.4 * shared && area >= (int64_t)6000 * 6000)) ? K_SPARSE64 : K_POPC;   // (the sparse tiles gain on the popcount tiles as N grows: 5,056 phams, r04 with four workgroups per CU: N = 5,000 0.162 against 0.157 ms, 6,000 0.218 / 0.219, 7,000 0.258 / 0.282, 20,000 1.56 / 2.03)
-    else if (metric == PC_POCP) kernel = (s64_ok && (double)d.Wb > 28.0 + 4.3 * shared && area >= (int64_t)2500 * 2500) ? K_SPARSE64 : K_POPC;
+    const bool s64_ok = counts ? in.max_nph < (1 << 30) : metric == PC_POCP ? in.max_ngen < (1 << 16) /* two gene counts per register */ : (in.min_gene_len >= 1 && in.max_tlen < (int64_t)1 << 31);
+    if (counts) kernel = (((double)Wb > 113.0 + 5.4 * shared && area >= (int64_t)3000 * 3000) ||
+                          ((double)Wb > 60.0 + 5.4 * shared && area >= (int64_t)6000 * 6000)) ? K_SPARSE64 : K_POPC;   // (the sparse tiles gain on the popcount tiles as N grows: 5,056 phams, r04 with four workgroups per CU: N = 5,000 0.162 against 0.157 ms, 6,000 0.218 / 0.219, 7,000 0.258 / 0.282, 20,000 1.56 / 2.03)
+    else if (metric == PC_POCP) kernel = (s64_ok && (double)Wb > 28.0 + 4.3 * shared && area >= (int64_t)2500 * 2500) ? K_SPARSE64 : K_POPC;
     else if (s64_ok) kernel = K_SPARSE64;                                  // (af; r05, ms, 32 x 32 / 64 x 64 tiles: N = 200 0.060 / 0.058, 800 0.095 / 0.061, 1,300 0.082 / 0.069 -- since r04's dense broadcast path the larger tile wins at every size)
     else kernel = area > (int64_t)3500 * 3500 ? K_WALKER : K_SPARSE32;
     // r05: the column kernel for all four (k_sparse_col: the masks over a block of targets stay in LDS for a run of source tiles, no
@@ -41,28 +42,69 @@ static int pick_set_kernel(const pc_ctx* c, int metric) {
     // (profiles/r05/experiments/sparse_col.txt; ms, popcount / column): 5,056 phams (79 words, 2.85 shared) N = 2,000 0.035 / 0.034,
     // 3,000 0.070 / 0.046, 8,000 0.35 / 0.20, 20,000 2.03 / 0.99; 2,500 phams (40 words) N = 5,000 0.098 / 0.110; 1,200: 0.067 / 0.146
     const int sp_mode = counts ? (metric == PC_GCS ? PCW_SPARSE_GCS : PCW_SPARSE_JC) : metric == PC_POCP ? PCW_POCP : PCW_AF;
-    bool col_ok = s64_ok && pc_sparse_col_lds(sp_mode, d.sp_W * 64) > 0;
-    if (col_ok && !counts) {                                           // ... pocp / af: every block's entries fit its LDS value table, as 16-bit values
-        const int cap = pc_sparse_col_vals_cap(d.sp_W * 64);
-        col_ok = metric == PC_POCP || c->max_ent_len < 65536;         // (pocp: s64_ok already holds the gene counts below 65,536)
-        for (size_t k0 = 0; k0 < c->h_owned.size() && col_ok; k0 += 64) {
-            uint32_t n = 0;
-            for (size_t k = k0; k < std::min(k0 + 64, c->h_owned.size()); ++k) n += c->h_sp_n[(size_t)c->h_owned[k]];
-            col_ok = n <= (uint32_t)cap;
-        }
-    }
+    bool col_ok = s64_ok && pc_sparse_col_lds(sp_mode, P64) > 0;
+    if (col_ok && !counts)                                             // ... pocp / af: every block's entries fit its LDS value table, as 16-bit values
+        col_ok = (metric == PC_POCP || in.max_ent_len < 65536) &&      // (pocp: s64_ok already holds the gene counts below 65,536)
+                 in.max_block_entries <= (int64_t)pc_sparse_col_vals_cap(P64);
     // (ms, popcount tiles / 64 x 64 sparse tiles / column -- pocp: N = 2,000 0.066 / 0.082 / 0.078, 3,000 0.137 / 0.118 / 0.083, 5,000 0.304 / 0.217 / 0.156,
     // 20,000 3.89 / 2.23 / 1.45; af: 2,000 - / 0.089 / 0.078, 3,000 - / 0.121 / 0.081, 5,000 - / 0.258 / 0.150, 20,000 - / 2.41 / 1.42)
     const int64_t col_min_n = metric == PC_AF ? 1400 : PC_COL_MIN_N;        // (af, 64 x 64 tiles / column: N = 1,000 0.062 / 0.072, 1,300 0.069 / 0.073, 1,500 0.087 / 0.074, 1,800 0.088 / 0.077)
-    if (col_ok && (double)d.Wb > 40.0 + 8.0 * shared && area >= col_min_n * col_min_n) kernel = K_SPARSE_COL;
-    if (set_force) {
-        if (!strcmp(set_force, "sparsecol") && col_ok) kernel = K_SPARSE_COL;
-        if (!strcmp(set_force, "popc") && metric != PC_AF) kernel = K_POPC;
-        else if (!strcmp(set_force, "sparse") && !counts) kernel = K_SPARSE32;
-        else if (!strcmp(set_force, "sparse64") && s64_ok) kernel = K_SPARSE64;
-        else if (!strcmp(set_force, "walker") && !counts) kernel = K_WALKER;
-    }
+    if (col_ok && (double)Wb > 40.0 + 8.0 * shared && area >= col_min_n * col_min_n) kernel = K_SPARSE_COL;
+    if (in.forced == K_SPARSE_COL && col_ok) kernel = K_SPARSE_COL;         // a forced family is taken where it exists for the metric and its guards hold
+    else if (in.forced == K_POPC && metric != PC_AF) kernel = K_POPC;
+    else if (in.forced == K_SPARSE32 && !counts) kernel = K_SPARSE32;
+    else if (in.forced == K_SPARSE64 && s64_ok) kernel = K_SPARSE64;
+    else if (in.forced == K_WALKER && !counts) kernel = K_WALKER;
     return kernel;
+}
+// pc_set_inputs.max_block_entries: the targets a rank owns, ascending, in blocks of 64 as k_sparse_col takes them -- the last block of a
+// shard is ragged and counts like any other
+extern "C" int64_t pc_set_max_block_entries(const uint32_t* entries_per_genome, const int32_t* owned, int64_t nown) {
+    if (nown < 0 || (nown > 0 && (!entries_per_genome || !owned))) { pc_set_error("pc_set_max_block_entries: bad argument"); return PC_ERR_ARG; }
+    int64_t most = 0;
+    for (int64_t k0 = 0; k0 < nown; k0 += 64) {
+        int64_t n = 0;
+        for (int64_t k = k0; k < std::min(k0 + 64, nown); ++k) n += entries_per_genome[(size_t)owned[k]];
+        most = std::max(most, n);
+    }
+    return most;
+}
+extern "C" int pc_set_kernel_choice(const pc_set_inputs* in) {
+    if (!in || in->metric < PC_GCS || in->metric > PC_AF || in->n < 0 || in->nown < 0 || in->nown > in->n || in->words < 1 || in->two_holder < 0) {
+        pc_set_error("pc_set_kernel_choice: bad argument"); return PC_ERR_ARG;
+    }
+    return pc_set_choice(*in);
+}
+extern "C" int pc_set_launch_shape(int family, int metric, int64_t n, int64_t nown, int words, int two_holder, int n_cu, int table_top,
+                                   const int32_t* knobs, pc_set_shape* out) {
+    if (!out || family < K_POPC || family > K_SPARSE_COL || metric < PC_GCS || metric > PC_AF || n < 0 || n > INT32_MAX || nown < 0 || nown > n ||
+        words < 1 || two_holder < 0 || table_top < 0 || (metric == PC_AF && family == K_POPC) || (metric <= PC_JC && (family == K_SPARSE32 || family == K_WALKER))) {
+        pc_set_error("pc_set_launch_shape: bad argument"); return PC_ERR_ARG;
+    }
+    const PcSetKnobs k = knobs ? PcSetKnobs{knobs[0], knobs[1], knobs[2]} : PcSetKnobs{0, 0, 0};
+    pc_set_shape_of(family, metric, (int)n, (int)nown, words, std::max(1, (two_holder + 63) / 64), n_cu, table_top, k, out);
+    return PC_OK;
+}
+extern "C" int pc_last_set_launch(const pc_ctx* c, pc_set_inputs* in, pc_set_shape* shape) {
+    if (!c) { pc_set_error("pc_last_set_launch: NULL context"); return PC_ERR_ARG; }
+    if (c->last_set_kernel < 0) { pc_set_error("pc_last_set_launch: no gcs / jc / pocp / af fill on this context yet"); return PC_ERR_STATE; }
+    if (in) *in = c->last_set_inputs;
+    if (shape) *shape = c->last_set_shape;
+    return PC_OK;
+}
+
+static int pick_set_kernel(pc_ctx* c, int metric) {
+    pc_set_inputs in; memset(&in, 0, sizeof(in));
+    in.n = c->dev.N; in.nown = c->shard.nown; in.words = c->dev.Wb; in.two_holder = c->two_holder;
+    in.avg_shared = c->avg_shared; in.max_nph = c->max_nph; in.max_ngen = c->max_ngen; in.min_gene_len = c->min_gene_len;
+    in.max_ent_len = c->max_ent_len; in.max_tlen = c->max_tlen; in.metric = metric; in.forced = -1;
+    in.max_block_entries = pc_set_max_block_entries(c->h_sp_n.data(), c->h_owned.data(), (int64_t)c->h_owned.size());     // THIS rank's targets (k_sparse_col's value table)
+    if (const char* set_force = getenv("PC_SET_KERNEL")) {             // (read per fill: the tests switch it between launches)
+        static const char* const names[] = {"popc", "sparse", "sparse64", "walker", "sparsecol"};
+        for (int k = 0; k < 5; ++k) if (!strcmp(set_force, names[k])) in.forced = k;
+    }
+    c->last_set_inputs = in;
+    return pc_set_choice(in);
 }
 
 // gcs / jc / pocp on the popcount tiles.  Their epilogue table: gcs / jc over (shared, nph_s + nph_t), at most (max_nph+1) x
@@ -70,15 +112,15 @@ static int pick_set_kernel(const pc_ctx* c, int metric) {
 // as_distance, that maximum) only, so it is rebuilt only when one of them changes.
 static int launch_popc(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st) {
     const int top = metric == PC_POCP ? c->max_ngen : c->max_nph;
-    const int sh_dim = metric == PC_POCP ? 2 * top + 1 : top + 1, tot_dim = 2 * top + 1;
+    int sh_dim, tot_dim;
     double* lut = nullptr; bool build_lut = false; int64_t lut_key_now = -1;
-    if ((int64_t)sh_dim * tot_dim <= (4 << 20)) {
+    if (pc_set_table_dims(metric, top, &sh_dim, &tot_dim)) {
         if (const int rc = c->b_lut.ensure((size_t)sh_dim * tot_dim * 8)) return abi_rc(rc);
         lut = c->b_lut.as<double>();
         lut_key_now = ((int64_t)metric << 40) | ((int64_t)as_distance << 32) | (int64_t)top;
         build_lut = lut_key_now != c->lut_key || lut != c->lut_ptr;
     }
-    const int rc = pc_launch_set_popc(c->dev, c->shard, metric, as_distance, out, condensed, lut, build_lut, sh_dim, tot_dim, st);
+    const int rc = pc_launch_set_popc(c->dev, c->shard, metric, as_distance, out, condensed, lut, build_lut, top, st, &c->last_set_shape);
     if (rc != PC_OK) { c->lut_key = -1; c->lut_ptr = nullptr; return rc; }           // (whatever the table holds now, it is not trusted)
     if (lut) { c->lut_key = lut_key_now; c->lut_ptr = lut; }                          // remembered only once its build was launched
     return PC_OK;
@@ -108,14 +150,15 @@ static int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int co
         const int kernel = pick_set_kernel(c, metric);
         const int mode = metric == PC_GCS ? PCW_SPARSE_GCS : metric == PC_JC ? PCW_SPARSE_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
         c->last_set_kernel = kernel;
-        if (kernel == K_SPARSE_COL) rc = pc_launch_sparse_col(mode, d, c->shard, out, as_distance, condensed, st);
-        else if (kernel == K_SPARSE64) rc = pc_launch_sparse64(mode, d, c->shard, out, as_distance, condensed, st);
+        pc_set_shape* const shp = &c->last_set_shape;                      // (pc_last_set_launch)
+        if (kernel == K_SPARSE_COL) rc = pc_launch_sparse_col(mode, d, c->shard, out, as_distance, condensed, st, shp);
+        else if (kernel == K_SPARSE64) rc = pc_launch_sparse64(mode, d, c->shard, out, as_distance, condensed, st, shp);
         else if (kernel == K_POPC) rc = launch_popc(c, metric, as_distance, out, condensed, st);
-        else if (kernel == K_SPARSE32) rc = pc_launch_sparse(mode, d, c->shard, out, as_distance, condensed, st);
+        else if (kernel == K_SPARSE32) rc = pc_launch_sparse(mode, d, c->shard, out, as_distance, condensed, st, shp);
         else {                                                             // K_WALKER
             PcWalkArgs a; memset(&a, 0, sizeof(a));
             a.out = out; a.as_distance = as_distance; a.condensed = condensed;
-            rc = pc_launch_walk(mode, d, c->shard, a, st);
+            rc = pc_launch_walk(mode, d, c->shard, a, st, shp);
         }
         if (rc != PC_OK) return rc;
         PC_HIP(hipEventRecord(c->ev[3], st));

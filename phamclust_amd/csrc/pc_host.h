@@ -85,6 +85,7 @@ struct pc_ctx {
     int max_gene_len = 0, min_gene_len = 0, max_nph = 0, max_ngen = 0;
     int64_t max_tlen = 0;                    // largest summed translation length of a genome
     double avg_shared = 0.0;                 // phams an average genome pair shares (pocp's kernel choice)
+    int two_holder = 0;                      // phams at least two genomes hold (dev.sp_W = their 64-id words)
     // kernel-variant classes over column genes
     int ncls_all = 0;                       // BASE classes: variant * 4 + lanes-per-segment bucket (twice: "any byte" columns), last = general kernel
     int nlc = 0;                            // launch classes = ncls_all * PC_WAVE_MODES (base class x workgroup shape of the task, pc_common.h)
@@ -146,6 +147,8 @@ struct pc_ctx {
     bool busy = false;                      // ev_last was recorded and not waited for yet
     hipStream_t last_stream = nullptr;      // ... on this stream
     int last_set_kernel = -1;               // kernel family the last gcs / jc / pocp / af fill ran on (pc_last_set_kernel)
+    pc_set_inputs last_set_inputs{};        // ... what the selector read for it and the shape its launcher took (pc_last_set_launch)
+    pc_set_shape last_set_shape{};
     int64_t plan_budget = 0;                // bytes of plan buffers one chunk of an aai / peq fill may use; 0: automatic (pc_set_plan_budget)
 };
 

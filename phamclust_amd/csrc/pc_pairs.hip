@@ -488,26 +488,26 @@ __global__ __launch_bounds__(256) void k_set_popc_ksplit(PcDev d, PcShard sh, in
         else hipLaunchKernelGGL(KERNEL<PC_POCP>, GRID, dim3(256), 0, st, d, sh, as_distance, out, condensed, (const double*)lut, sh_dim);                     \
     } while (0)
 
+static int pc_metric_of_mode(int mode) { return mode == PCW_SPARSE_GCS ? PC_GCS : mode == PCW_SPARSE_JC ? PC_JC : mode == PCW_POCP ? PC_POCP : PC_AF; }
+
 int pc_launch_set_popc(const PcDev& d, const PcShard& sh, int metric, int as_distance, double* out, int condensed,
-                       double* lut, bool build_lut, int sh_dim, int tot_dim, hipStream_t st) {
+                       double* lut, bool build_lut, int top, hipStream_t st, pc_set_shape* shape_out) {
+    pc_set_shape shp;
+    pc_set_shape_of(K_POPC, metric, d.N, sh.nown, d.Wb, d.sp_W, d.n_cu, top, pc_set_knobs_env(), &shp);
+    if (!lut) shp.table = 0;                                                               // (the caller could not hold one)
+    if (shape_out) *shape_out = shp;
     if (sh.nown <= 0 || d.N <= 1) return PC_OK;
+    int sh_dim = 0, tot_dim = 0;
+    (void)pc_set_table_dims(metric, top, &sh_dim, &tot_dim);
     if (lut && build_lut) {
         const int n = sh_dim * tot_dim;
         if (metric == PC_GCS) hipLaunchKernelGGL(k_set_lut<PC_GCS>, dim3((n + 255) / 256), dim3(256), 0, st, lut, sh_dim, tot_dim, as_distance);
         else if (metric == PC_JC) hipLaunchKernelGGL(k_set_lut<PC_JC>, dim3((n + 255) / 256), dim3(256), 0, st, lut, sh_dim, tot_dim, as_distance);
         else hipLaunchKernelGGL(k_set_lut<PC_POCP>, dim3((n + 255) / 256), dim3(256), 0, st, lut, sh_dim, tot_dim, as_distance);
     }
-    const int64_t tiles64 = (int64_t)((d.N + 63) / 64) * ((sh.nown + 63) / 64);
-    const char* force_env = getenv("PC_POPC_TILE");                                         // tuning / test knob: 32 / 64 (read per launch)
-    const int force = force_env ? atoi(force_env) : 0;
-    const bool small = force ? force == 32 : tiles64 / 2 < PC_SMALL_GRID_TILES;             // about half of the tiles are live
-    if (small) {
-        dim3 grid(pc_tile_grid((d.N + 31) / 32, (sh.nown + 31) / 32));
-        PC_SET_DISPATCH(k_set_popc_ksplit, grid);
-    } else {
-        dim3 grid(pc_tile_grid((d.N + 63) / 64, (sh.nown + 63) / 64));
-        PC_SET_DISPATCH(k_set_popc, grid);
-    }
+    dim3 grid((unsigned)shp.grid);
+    if (shp.tile == 32) PC_SET_DISPATCH(k_set_popc_ksplit, grid);
+    else PC_SET_DISPATCH(k_set_popc, grid);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("k_set_popc launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
     return PC_OK;
@@ -632,13 +632,14 @@ __global__ __launch_bounds__(256) void k_sparse_tile(PcDev d, PcShard sh, double
     }
 }
 
-int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st) {
+int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out) {
+    pc_set_shape shp;
+    pc_set_shape_of(K_SPARSE32, pc_metric_of_mode(mode), d.N, sh.nown, d.Wb, d.sp_W, d.n_cu, 0, pc_set_knobs_env(), &shp);
+    if (shape_out) *shape_out = shp;
     if (sh.nown <= 0 || d.N <= 1) return PC_OK;
-    // colmask chunk: all phams at once while that leaves three workgroups per CU (48 KB each), else 8,192 at a time
-    const int P64 = d.Wb * 64;
-    const int CH = P64 <= 10240 ? P64 : 8192;
-    const size_t lds = (size_t)CH * 4 + (size_t)SP_T * SP_T * 8;
-    dim3 grid(pc_tile_grid((d.N + SP_T - 1) / SP_T, (sh.nown + SP_T - 1) / SP_T)), block(256);
+    const int CH = shp.chunk;
+    const size_t lds = (size_t)shp.lds;
+    dim3 grid((unsigned)shp.grid), block(256);
     if (mode == PCW_POCP) hipLaunchKernelGGL(k_sparse_tile<PCW_POCP>, grid, block, lds, st, d, sh, out, as_distance, condensed, CH);
     else hipLaunchKernelGGL(k_sparse_tile<PCW_AF>, grid, block, lds, st, d, sh, out, as_distance, condensed, CH);
     hipError_t e = hipGetLastError();
@@ -931,32 +932,18 @@ int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, cons
     return PC_OK;
 }
 
-int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st) {
+int pc_launch_sparse64(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out) {
+    pc_set_shape shp;
+    pc_set_shape_of(K_SPARSE64, pc_metric_of_mode(mode), d.N, sh.nown, d.Wb, d.sp_W, d.n_cu, 0, pc_set_knobs_env(), &shp);
+    if (shape_out) *shape_out = shp;
     if (sh.nown <= 0 || d.N <= 1) return PC_OK;
-    // mask chunk: all phams at once while two workgroups still fit a CU (8 B per pham + 17 KB of accumulators: 7,680 phams), else the
-    // fewest equal chunks of at most that many
-    const int P64 = d.sp_W * 64;                                                    // phams with at least two holders
-    // ... except that 2,048 ... 7,680 phams are split in two from ~4,000 genomes: the one-batch instances need 59 (gcs / jc), 78 (af) and --
-    // held there by the launch bound, 4 dwords of scratch -- 80 (pocp) registers, and with 20 KB of masks three workgroups fit a CU instead
-    // of two (N = 20,000, 5,056 phams: jc 2.06 -> 1.79 ms, af 2.89 -> 2.60, pocp 2.61 -> 2.42; below: af at N = 3,000 0.150 ms whole, 0.165 split)
-    const int chunk_cap = pc_s6_dense(mode, 2) ? 6912 : 7680;                       // (6 KB of broadcast staging beside the accumulators)
-    int n_chunks = (P64 + chunk_cap - 1) / chunk_cap;
-    if (n_chunks == 1 && P64 >= 2048 && (int64_t)d.N * sh.nown >= (int64_t)4000 * 4000) n_chunks = 2;
-    if (const char* force = getenv("PC_S64_CHUNKS")) {                              // test knob (read per launch): at least this many chunks, so that
-        const int want_chunks = atoi(force);                                        // small collections reach the one-batch instances and the forced split
-        if (want_chunks > n_chunks && want_chunks <= P64 / 64) n_chunks = want_chunks;
-    }
-    const int CH = (P64 / 64 + n_chunks - 1) / n_chunks * 64;                       // equal chunks (synth(20000,20000): 5 x 4,096: jc 2.67 ms, 3 x 6,720: 2.5)
-    const size_t lds = (size_t)CH * 8 + (size_t)S6_T * S6_LD * 4 + (pc_s6_dense(mode, CH < P64 ? 1 : 2) ? (size_t)S6_WAVES * S6_STAGE_DWORDS * 4 : 0);
-    const unsigned n_units = pc_tile_grid((d.N + S6_T - 1) / S6_T, (sh.nown + S6_T - 1) / S6_T, S6_SUPER);
-    const unsigned resident = (unsigned)(2 * (d.n_cu > 0 ? d.n_cu : 256) + 7) / 8u * 8u;      // (the context's own device: pc_ctx_create asked it)
-    // three units per workgroup (see the kernel); small matrices: one unit each, up to four times the workgroups that fit the chip
-    // at once (N = 2,000: 0.158 ms with two units per workgroup, 0.129 with one)
-    const unsigned want = std::max(std::min(n_units, 4u * resident), ((n_units + 2u) / 3u + 7u) / 8u * 8u);
-    dim3 grid(std::min(n_units, want)), block(64 * S6_WAVES);
+    const int CH = shp.chunk;
+    const size_t lds = (size_t)shp.lds;
+    const unsigned n_units = (unsigned)shp.units;
+    dim3 grid((unsigned)shp.grid), block(64 * S6_WAVES);
     // (up to 78 KB of dynamic LDS: HIP on this hardware needs no opt-in above 64 KB -- the K4 launches take up to 160 KB the same way)
 #define S6_LAUNCH(M, B) hipLaunchKernelGGL((k_sparse_tile64<M, B>), grid, block, lds, st, d, sh, out, as_distance, condensed, CH, n_units)
-    const bool chunked = CH < P64;
+    const bool chunked = shp.batches == 1;
     if (mode == S6_GCS) { if (chunked) S6_LAUNCH(S6_GCS, 1); else S6_LAUNCH(S6_GCS, 2); }
     else if (mode == S6_JC) { if (chunked) S6_LAUNCH(S6_JC, 1); else S6_LAUNCH(S6_JC, 2); }
     else if (mode == PCW_POCP) { if (chunked) S6_LAUNCH(PCW_POCP, 1); else S6_LAUNCH(PCW_POCP, 2); }
@@ -1231,20 +1218,101 @@ size_t pc_sparse_col_lds(int mode, int P64) {
     const size_t bytes = (size_t)P64 * 8 + (size_t)S6_T * S6_LD * 4;
     return bytes <= 78 * 1024 ? bytes : 0;                                          // two workgroups per CU
 }
-int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st) {
+// The launch shapes of the five families, as host arithmetic (pc_set_launch_shape of the C-ABI; every launcher takes its numbers from here).
+PcSetKnobs pc_set_knobs_env() {
+    PcSetKnobs k{0, 0, 0};
+    if (const char* v = getenv("PC_POPC_TILE")) k.popc_tile = atoi(v);                  // tuning / test knob: 32 / 64
+    if (const char* v = getenv("PC_S64_CHUNKS")) k.s64_chunks = atoi(v);                // test knob: at least this many chunks, so that small collections reach the one-batch instances and the forced split
+    if (const char* v = getenv("PC_COL_SEG")) k.col_seg = atoi(v);
+    return k;
+}
+bool pc_set_table_dims(int metric, int top, int* sh_dim, int* tot_dim) {
+    *sh_dim = metric == PC_POCP ? 2 * top + 1 : top + 1; *tot_dim = 2 * top + 1;
+    return (int64_t)*sh_dim * *tot_dim <= (4 << 20);
+}
+void pc_set_shape_of(int family, int metric, int N, int nown, int Wb, int sp_W, int n_cu, int table_top, const PcSetKnobs& knobs, pc_set_shape* out) {
+    *out = pc_set_shape{};
+    out->family = family;
+    if (nown <= 0 || N <= 1) return;                                                    // (nothing is launched)
+    const int mode = metric == PC_GCS ? S6_GCS : metric == PC_JC ? S6_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
+    const int cu = n_cu > 0 ? n_cu : 256;
+    const int P64 = sp_W * 64;                                                          // phams with at least two holders
+    out->units_per_wg = 1;
+    if (family == K_POPC) {
+        const int64_t tiles64 = (int64_t)((N + 63) / 64) * ((nown + 63) / 64);
+        const bool small = knobs.popc_tile ? knobs.popc_tile == 32 : tiles64 / 2 < PC_SMALL_GRID_TILES;     // about half of the tiles are live
+        out->tile = small ? 32 : 64;
+        const int ntx = (N + out->tile - 1) / out->tile, nty = (nown + out->tile - 1) / out->tile;
+        out->super_edge = (int)pc_super_edge((unsigned)ntx, (unsigned)nty);
+        out->grid = out->units = (int)pc_tile_grid(ntx, nty);
+        int sh_dim, tot_dim;
+        out->table = pc_set_table_dims(metric, table_top, &sh_dim, &tot_dim) ? 1 : 0;
+    } else if (family == K_SPARSE32 || family == K_WALKER) {
+        out->tile = TS;
+        const int ntx = (N + TS - 1) / TS, nty = (nown + TS - 1) / TS;
+        out->super_edge = (int)pc_super_edge((unsigned)ntx, (unsigned)nty);
+        out->grid = out->units = (int)pc_tile_grid(ntx, nty);
+        if (family == K_SPARSE32) {
+            // colmask chunk: all phams at once while that leaves three workgroups per CU (48 KB each), else 8,192 at a time
+            const int V64 = Wb * 64;
+            out->chunk = V64 <= 10240 ? V64 : 8192;
+            out->chunks = (V64 + out->chunk - 1) / out->chunk;
+            out->lds = (int)((size_t)out->chunk * 4 + (size_t)SP_T * SP_T * 8);
+        }
+    } else if (family == K_SPARSE64) {
+        // mask chunk: all phams at once while two workgroups still fit a CU (8 B per pham + 17 KB of accumulators: 7,680 phams), else the
+        // fewest equal chunks of at most that many
+        // ... except that 2,048 ... 7,680 phams are split in two from ~4,000 genomes: the one-batch instances need 59 (gcs / jc), 78 (af) and --
+        // held there by the launch bound, 4 dwords of scratch -- 80 (pocp) registers, and with 20 KB of masks three workgroups fit a CU instead
+        // of two (N = 20,000, 5,056 phams: jc 2.06 -> 1.79 ms, af 2.89 -> 2.60, pocp 2.61 -> 2.42; below: af at N = 3,000 0.150 ms whole, 0.165 split)
+        const int chunk_cap = pc_s6_dense(mode, 2) ? 6912 : 7680;                       // (6 KB of broadcast staging beside the accumulators)
+        int n_chunks = (P64 + chunk_cap - 1) / chunk_cap;
+        if (n_chunks == 1 && P64 >= 2048 && (int64_t)N * nown >= (int64_t)4000 * 4000) n_chunks = 2;
+        if (knobs.s64_chunks > n_chunks && knobs.s64_chunks <= P64 / 64) n_chunks = knobs.s64_chunks;
+        const int CH = (P64 / 64 + n_chunks - 1) / n_chunks * 64;                       // equal chunks (synth(20000,20000): 5 x 4,096: jc 2.67 ms, 3 x 6,720: 2.5)
+        out->tile = S6_T;
+        out->chunk = CH; out->chunks = (P64 + CH - 1) / CH;
+        out->batches = CH < P64 ? 1 : 2;
+        out->dense = pc_s6_dense(mode, out->batches) ? 1 : 0;
+        out->lds = (int)((size_t)CH * 8 + (size_t)S6_T * S6_LD * 4 + (out->dense ? (size_t)S6_WAVES * S6_STAGE_DWORDS * 4 : 0));
+        const int ntx = (N + S6_T - 1) / S6_T, nty = (nown + S6_T - 1) / S6_T;
+        out->super_edge = (int)pc_super_edge((unsigned)ntx, (unsigned)nty, S6_SUPER);
+        const unsigned n_units = pc_tile_grid(ntx, nty, S6_SUPER);
+        const unsigned resident = (unsigned)(2 * cu + 7) / 8u * 8u;                     // (the context's own device: pc_ctx_create asked it)
+        // three units per workgroup (see the kernel); small matrices: one unit each, up to four times the workgroups that fit the chip
+        // at once (N = 2,000: 0.158 ms with two units per workgroup, 0.129 with one)
+        const unsigned want = std::max(std::min(n_units, 4u * resident), ((n_units + 2u) / 3u + 7u) / 8u * 8u);
+        const unsigned grid = std::min(n_units, want);
+        out->units = (int)n_units; out->grid = (int)grid;
+        out->units_per_wg = (int)((n_units + grid - 1) / grid);
+    } else {                                                                            // K_SPARSE_COL
+        out->tile = S6_T;
+        out->vals_cap = metric == PC_POCP || metric == PC_AF ? pc_sparse_col_vals_cap(P64) : 0;
+        out->lds = (int)pc_sparse_col_lds(mode, P64);                                   // 0: the masks do not fit, the launcher refuses
+        out->chunk = P64; out->chunks = 1;
+        const int nty = (nown + S6_T - 1) / S6_T, ntx = (N + S6_T - 1) / S6_T;
+        // source tiles per unit: as many as leave ~2 units per workgroup slot of the chip (2 slots per CU), at most S7_SEG.  Measured, jc, ms
+        // (profiles/r05/experiments/sparse_col.txt): N = 2,000 / 3,000 / 5,000 / 20,000 with 1 tile per unit 0.034 / 0.046 / 0.105 / 1.27,
+        // 2: 0.047 / 0.049 / 0.092 / 1.10, 4: 0.058 / 0.060 / 0.093 / 1.02, 8: 0.081 / 0.083 / 0.100 / 0.99, 16: 0.126 / 0.127 / 0.166 / 1.005
+        const int64_t live_tiles = (int64_t)nty * ntx / 2 + nty;
+        int seg = (int)std::max<int64_t>(1, std::min<int64_t>(S7_SEG, live_tiles / (4 * (int64_t)cu)));
+        if (knobs.col_seg >= 1 && knobs.col_seg <= 64) seg = knobs.col_seg;
+        out->seg = seg; out->runs = (ntx + seg - 1) / seg;
+        out->grid = out->units = (int)(((unsigned)nty + 7u) / 8u * 8u * ((unsigned)out->runs + 2u));     // (runs 0, 1: every block's diagonal run and the one below; then the runs, highest first)
+    }
+}
+
+int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out) {
+    pc_set_shape shp;
+    pc_set_shape_of(K_SPARSE_COL, pc_metric_of_mode(mode), d.N, sh.nown, d.Wb, d.sp_W, d.n_cu, 0, pc_set_knobs_env(), &shp);
+    if (shape_out) *shape_out = shp;
     if (sh.nown <= 0 || d.N <= 1) return PC_OK;
     const int P64 = d.sp_W * 64;
-    const size_t lds = pc_sparse_col_lds(mode, P64);
+    const size_t lds = (size_t)shp.lds;
     if (!lds || (mode != S6_GCS && mode != S6_JC && mode != PCW_POCP && mode != PCW_AF)) { pc_set_error("k_sparse_col: mode %d, %d mask entries", mode, P64); return PC_ERR_LIMIT; }
-    const int nty = (sh.nown + S6_T - 1) / S6_T, ntx = (d.N + S6_T - 1) / S6_T;
-    // source tiles per unit: as many as leave ~2 units per workgroup slot of the chip (2 slots per CU), at most S7_SEG.  Measured, jc, ms
-    // (profiles/r05/experiments/sparse_col.txt): N = 2,000 / 3,000 / 5,000 / 20,000 with 1 tile per unit 0.034 / 0.046 / 0.105 / 1.27,
-    // 2: 0.047 / 0.049 / 0.092 / 1.10, 4: 0.058 / 0.060 / 0.093 / 1.02, 8: 0.081 / 0.083 / 0.100 / 0.99, 16: 0.126 / 0.127 / 0.166 / 1.005
-    const int64_t live_tiles = (int64_t)nty * ntx / 2 + nty;
-    int seg = (int)std::max<int64_t>(1, std::min<int64_t>(S7_SEG, live_tiles / (4 * (int64_t)(d.n_cu > 0 ? d.n_cu : 256))));
-    if (const char* force = getenv("PC_COL_SEG")) { const int v = atoi(force); if (v >= 1 && v <= 64) seg = v; }
-    const unsigned runs = (unsigned)((ntx + seg - 1) / seg);
-    dim3 grid(((unsigned)nty + 7u) / 8u * 8u * (runs + 2u)), block(64 * S7_WAVES);     // (runs 0, 1: every block's diagonal run and the one below; then the runs, highest first)
+    const int nty = (sh.nown + S6_T - 1) / S6_T, seg = shp.seg;
+    const unsigned runs = (unsigned)shp.runs;
+    dim3 grid((unsigned)shp.grid), block(64 * S7_WAVES);
     if (mode == S6_GCS) hipLaunchKernelGGL((k_sparse_col<S6_GCS>), grid, block, lds, st, d, sh, out, as_distance, condensed, P64, nty, seg, (int)runs);
     else if (mode == PCW_POCP) hipLaunchKernelGGL((k_sparse_col<PCW_POCP>), grid, block, lds, st, d, sh, out, as_distance, condensed, P64, nty, seg, (int)runs);
     else if (mode == PCW_AF) hipLaunchKernelGGL((k_sparse_col<PCW_AF>), grid, block, lds, st, d, sh, out, as_distance, condensed, P64, nty, seg, (int)runs);
@@ -1419,9 +1487,12 @@ __global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcWalkArgs a)
     }
 }
 
-int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st) {
+int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st, pc_set_shape* shape_out) {
+    pc_set_shape shp;
+    pc_set_shape_of(K_WALKER, mode == PCW_POCP ? PC_POCP : PC_AF, d.N, sh.nown, d.Wb, d.sp_W, d.n_cu, 0, PcSetKnobs{0, 0, 0}, &shp);
+    if (shape_out) *shape_out = shp;
     if (sh.nown <= 0 || d.N <= 1) return PC_OK;
-    dim3 grid(pc_tile_grid((d.N + TS - 1) / TS, (sh.nown + TS - 1) / TS)), block(256);
+    dim3 grid((unsigned)shp.grid), block(256);
     switch (mode) {
     case PCW_POCP: hipLaunchKernelGGL(k_walk<PCW_POCP>, grid, block, 0, st, d, sh, a); break;
     case PCW_AF: hipLaunchKernelGGL(k_walk<PCW_AF>, grid, block, 0, st, d, sh, a); break;

@@ -263,6 +263,7 @@ static int upload_sets(pc_ctx* c, const pc_packed* g) {
     d.ent_pair_len = (const uint2*)(ds + o_pair_len); d.ent_pair_cnt = (const uint2*)(ds + o_pair_cnt);
     d.sp_end = (const uint32_t*)(ds + o_sp_end); d.sp_pham = (const int32_t*)(ds + o_sp_pham); d.sp_len = (const uint2*)(ds + o_sp_len);
     d.sp_cnt = (const uint2*)(ds + o_sp_cnt); d.sp_rank = (const uint32_t*)(ds + o_sp_rank); d.sp_W = W2;
+    c->two_holder = P2;
     c->h_gene_len.swap(gene_len);
     c->max_gene_len = maxlen; c->min_gene_len = minlen;
     c->max_nph = 0;

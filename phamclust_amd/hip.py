@@ -46,11 +46,32 @@ class PcStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PcSetInputs(ctypes.Structure):
+    """What the set-metric selector reads (pc_set_inputs of the header)."""
+    _fields_ = [("n", ctypes.c_int64), ("nown", ctypes.c_int64), ("words", ctypes.c_int32), ("two_holder", ctypes.c_int32),
+                ("avg_shared", ctypes.c_double), ("max_nph", ctypes.c_int32), ("max_ngen", ctypes.c_int32),
+                ("min_gene_len", ctypes.c_int32), ("max_ent_len", ctypes.c_int32), ("max_tlen", ctypes.c_int64),
+                ("max_block_entries", ctypes.c_int64), ("metric", ctypes.c_int32), ("forced", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PcSetShape(ctypes.Structure):
+    """Launch shape of a set-metric kernel family (pc_set_shape of the header)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("family", "tile", "super_edge", "grid", "units", "units_per_wg", "chunks", "chunk",
+                                                    "batches", "dense", "seg", "runs", "lds", "table", "vals_cap", "reserved")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_ctx_destroy", "pc_upload", "pc_set_shard", "pc_set_shard_balanced",
            "pc_shard_pairs", "pc_shard_stride", "pc_fill", "pc_fill_borrow", "pc_fill_dev", "pc_fill_shard_dev", "pc_assemble_dev",
            "pc_align_pairs", "pc_last_align_ms", "pc_round6_probe", "pc_set_tie_rule", "pc_get_tie_rule", "pc_shard_table", "pc_target_costs",
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
-           "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
+           "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
+           "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
@@ -118,6 +139,12 @@ def load():
     L.pc_shard_table.argtypes = [vp, _i32p, _i64p]
     L.pc_target_costs.argtypes = [vp, _u64p]
     L.pc_last_set_kernel.argtypes = [vp]
+    L.pc_set_kernel_choice.argtypes = [ctypes.POINTER(PcSetInputs)]
+    L.pc_set_launch_shape.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, _i32p, ctypes.POINTER(PcSetShape)]
+    L.pc_set_max_block_entries.argtypes = [ctypes.POINTER(ctypes.c_uint32), _i32p, ctypes.c_int64]
+    L.pc_set_max_block_entries.restype = ctypes.c_int64
+    L.pc_last_set_launch.argtypes = [vp, ctypes.POINTER(PcSetInputs), ctypes.POINTER(PcSetShape)]
     L.pc_multi_create.argtypes = [ctypes.POINTER(vp), _i32p, ctypes.c_int]
     L.pc_multi_destroy.argtypes = [vp]
     L.pc_multi_destroy.restype = None
@@ -472,6 +499,53 @@ class Context:
     def last_set_kernel(self):
         """Kernel family the selector gave the last gcs / jc / pocp / af fill (the names PC_SET_KERNEL takes)."""
         return self.SET_KERNELS[int(self._lib.pc_last_set_kernel(self._h))]
+
+    SET_FAMILIES = {name: k for k, name in SET_KERNELS.items() if name}
+    SET_METRICS = ("gcs", "jc", "pocp", "af")
+
+    @staticmethod
+    def set_kernel_choice(metric, forced=None, **inputs):
+        """The selector as host arithmetic (no GPU, no context): the family a fill of ``metric`` runs on for the given
+        ``pc_set_inputs`` fields (n, nown, words, two_holder, avg_shared, max_nph, max_ngen, min_gene_len, max_ent_len,
+        max_tlen, max_block_entries); ``forced``: a PC_SET_KERNEL name or None."""
+        a = PcSetInputs(metric=Context.SET_METRICS.index(metric), forced=-1 if forced is None else Context.SET_FAMILIES[forced], **inputs)
+        k = load().pc_set_kernel_choice(ctypes.byref(a))
+        if k < 0:
+            raise HipLibraryError(load().pc_last_error().decode())
+        return Context.SET_KERNELS[k]
+
+    @staticmethod
+    def set_launch_shape(family, metric, n, nown, words, two_holder, n_cu=256, table_top=0, popc_tile=0, s64_chunks=0, col_seg=0):
+        """Launch shape (dict, see ``pc_set_shape``) of ``family`` for that fill; the last three are the values of the
+        PC_POPC_TILE / PC_S64_CHUNKS / PC_COL_SEG knobs (0: unset).  Host arithmetic, no GPU."""
+        out, knobs = PcSetShape(), np.array([popc_tile, s64_chunks, col_seg], dtype=np.int32)
+        if load().pc_set_launch_shape(Context.SET_FAMILIES[family], Context.SET_METRICS.index(metric), int(n), int(nown), int(words),
+                                      int(two_holder), int(n_cu), int(table_top), _ptr(knobs, _i32p), ctypes.byref(out)) != 0:
+            raise HipLibraryError(load().pc_last_error().decode())
+        d = out.as_dict()
+        d["family"] = family
+        return d
+
+    @staticmethod
+    def set_max_block_entries(entries_per_genome, owned):
+        """``max_block_entries`` of the selector's inputs as the fills count it (host arithmetic, no GPU): the most entries in
+        a block of 64 consecutive owned targets, the ragged last block included."""
+        per = np.ascontiguousarray(entries_per_genome, dtype=np.uint32)
+        owned = np.ascontiguousarray(owned, dtype=np.int32)
+        n = load().pc_set_max_block_entries(_ptr(per, ctypes.POINTER(ctypes.c_uint32)), _ptr(owned, _i32p), owned.shape[0])
+        if n < 0:
+            raise HipLibraryError(load().pc_last_error().decode())
+        return int(n)
+
+    def last_set_launch(self):
+        """(selector inputs, launch shape) of this context's last gcs / jc / pocp / af fill, as two dicts; names instead of
+        ids for metric, forced and family."""
+        a, shape = PcSetInputs(), PcSetShape()
+        self._check(self._lib.pc_last_set_launch(self._h, ctypes.byref(a), ctypes.byref(shape)))
+        a, shape = a.as_dict(), shape.as_dict()
+        a["metric"], a["forced"] = self.SET_METRICS[a["metric"]], self.SET_KERNELS[a["forced"]]
+        shape["family"] = self.SET_KERNELS[shape["family"]]
+        return a, shape
 
     @staticmethod
     def chunk_plan(counts, max_per_chunk):

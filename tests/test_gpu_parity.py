@@ -1484,11 +1484,15 @@ def test_every_pocp_af_kernel_agrees(gpu_ctx, native_built):
         gpu_ctx.upload(lonely, residues=False)
         for m in ("pocp", "af", "gcs", "jc"):
             assert np.array_equal(gpu_ctx.fill(m), O.fill(lonely, m)), m
+            assert gpu_ctx.last_set_kernel() == "sparse64", m
         # an empty translation makes "sum == 0" ambiguous: the 64 x 64 kernel must step aside, whatever was asked for
         odd = _set_kernel_case(rng, 40, 300, empty_translation_in=2)
         gpu_ctx.upload(odd, residues=False)
         for m in ("pocp", "af"):
             assert np.array_equal(gpu_ctx.fill(m), O.fill(odd, m)), m
+            assert gpu_ctx.last_set_kernel() == ("sparse64" if m == "pocp" else "sparse"), m      # (af: 40 x 40 pairs, far below the walker's 3,500^2)
+        os.environ.pop("PC_SET_KERNEL", None)
+        assert np.array_equal(gpu_ctx.fill("af", False), O.fill(odd, "af", False)) and gpu_ctx.last_set_kernel() == "sparse"
     finally:
         os.environ.pop("PC_SET_KERNEL", None)
         gpu_ctx.set_shard(0, 1)
@@ -1500,34 +1504,7 @@ def _dense_phams(packed):
     return int((bits.sum(axis=0) >= 2).sum())
 
 
-def _two_holder_case(rng, n_genomes, per_genome, wide=None, extra_holders=0):
-    """Every pham of the pool is held by exactly two genomes (then `extra_holders` random ones get a third ... holder), so the dense
-    pham count is the pool size n_genomes * per_genome / 2 -- whatever the vocabulary; `wide` = (genome, entries) gets a long row."""
-    from phamclust_amd.genome import Genome
-    from phamclust_amd.pack import pack_genomes
-    pool = n_genomes * per_genome // 2
-    slots = np.repeat(np.arange(pool), 2)
-    rng.shuffle(slots)
-    held = [set() for _ in range(n_genomes)]
-    for k, p in enumerate(slots):                           # deal the shuffled (pham, pham) list round: a genome rarely gets both copies
-        g = k % n_genomes
-        if int(p) in held[g]:
-            g = (g + 1) % n_genomes
-        held[g].add(int(p))
-    for p in rng.choice(pool, size=extra_holders, replace=False):
-        for g in rng.choice(n_genomes, size=int(rng.integers(3, 40)), replace=False):
-            held[int(g)].add(int(p))                        # phams with many holders: masks with many bits (broadcast adds)
-    if wide is not None:
-        held[wide[0]] |= set(int(x) for x in rng.choice(pool, size=wide[1], replace=False))
-    genomes = []
-    for k in range(n_genomes):
-        g = Genome(f"g{k:04d}")
-        for p in sorted(held[k]):
-            for _ in range(int(rng.integers(2, 5)) if p % 7 == 0 else 1):      # paralogs: pocp's second direction
-                g.add(f"p{p:05d}", "M" * int(rng.integers(1, 40)))
-        g.add(f"own{k:04d}", "MK")                          # a pham nobody else holds: dropped from the dense numbering
-        genomes.append(g)
-    return pack_genomes(genomes)
+from set_kernel_cases import two_holder_case as _two_holder_case      # noqa: E402  (shared with tests/test_gpu_set_kernels.py)
 
 
 def test_sparse64_chunked_instances_and_forced_split(gpu_ctx, native_built):

@@ -393,6 +393,302 @@ def test_planner_collection_reaches_every_launch_class(native_built):
     assert all(1 <= lb <= 65535 and 1 <= rows <= pc.MAX_ROWS for lb, rows, _ in cases)
 
 
+# ---- the set-metric selector and its launch shapes (host arithmetic of pc_fill.hip / pc_pairs.hip) -----------------------
+def _choice_base(**over):
+    """synth(N, 5000)'s profile: 79 bitmap words, 5,000 phams with two holders (5,056 mask entries), 2.85 phams shared per pair;
+    blocks of 6,500 entries against the value table's 7,231 at that mask count."""
+    base = dict(n=3000, nown=3000, words=79, two_holder=5000, avg_shared=2.85, max_nph=140, max_ngen=160, min_gene_len=1,
+                max_ent_len=3000, max_tlen=40000, max_block_entries=6500)
+    base.update(over)
+    return base
+
+
+def test_set_kernel_choice_pins(native_built):
+    """pc_set_kernel_choice, the selector as a function of its inputs (no GPU, no context), on both sides of every threshold and
+    guard of pick_set_kernel -- worked out by hand from pc_fill.hip, not read off the function."""
+    from phamclust_amd import hip
+    C = hip.Context
+
+    def pick(metric, forced=None, **over):
+        side = over.pop("side", None)
+        if side is not None:
+            over.update(n=side, nown=side)
+        return C.set_kernel_choice(metric, forced=forced, **_choice_base(**over))
+    # the column kernel's area: 2,200^2 (gcs / jc / pocp), 1,400^2 (af); area is N x OWNED targets
+    for m in ("gcs", "jc", "pocp"):
+        assert pick(m, side=2199) == "popc" and pick(m, side=2200) == "sparsecol", m
+        assert pick(m, n=2200, nown=2199) == "popc" and pick(m, n=4840, nown=1000) == "sparsecol" and pick(m, n=4839, nown=1000) == "popc", m
+    assert pick("af", side=1399) == "sparse64" and pick("af", side=1400) == "sparsecol" and pick("af", n=1400, nown=1399) == "sparse64"
+    # ... and its words: more than 40 + 8 x shared (2.5 shared: 60 exactly)
+    for m in C.SET_METRICS:
+        assert pick(m, words=60, avg_shared=2.5) != "sparsecol" and pick(m, words=61, avg_shared=2.5) == "sparsecol", m
+        assert pick(m, words=61, avg_shared=2.625) != "sparsecol", m
+    # ... and its masks: 7,872 phams with two holders (123 words of 64; 8 B each beside 16,640 B of accumulators in 78 KB); pocp / af
+    # 6,272 (beside a value table of at least 1,024 entries: at 6,272 it holds 1,151)
+    for m in ("gcs", "jc"):
+        assert pick(m, two_holder=7872) == "sparsecol" and pick(m, two_holder=7873) == "popc", m
+        assert pick(m, two_holder=7873, forced="sparsecol") == "popc", m
+    for m in ("pocp", "af"):
+        assert pick(m, two_holder=6272, max_block_entries=1151) == "sparsecol", m
+        assert pick(m, two_holder=6272, max_block_entries=1152) == "sparse64", m              # (pocp: 3,000^2 >= 2,500^2 and 79 > 28 + 4.3 x 2.85)
+        assert pick(m, two_holder=6273, max_block_entries=100) == "sparse64", m
+    # the value table's cap at 5,056 mask entries: (81,664 - 5,056 x 10 - 16,640) / 2 - 1 = 7,231
+    for m in ("pocp", "af"):
+        assert pick(m, max_block_entries=7231) == "sparsecol" and pick(m, max_block_entries=7232) == "sparse64", m
+        assert pick(m, max_block_entries=7232, forced="sparsecol") == "sparse64", m
+    assert pick("pocp", max_block_entries=7232, side=2200) == "popc"                              # (below 2,500^2)
+    assert pick("jc", max_block_entries=1 << 40) == "sparsecol"                                 # gcs / jc keep no values
+    # 16-bit values: af's entry lengths, pocp's gene counts (two per register in sparse64 as well)
+    assert pick("af", max_ent_len=65535) == "sparsecol" and pick("af", max_ent_len=65536) == "sparse64"
+    assert pick("pocp", max_ent_len=65536) == "sparsecol" and pick("jc", max_ent_len=65536) == "sparsecol"
+    assert pick("pocp", max_ngen=65535) == "sparsecol" and pick("pocp", max_ngen=65536) == "popc"
+    assert pick("pocp", max_ngen=65535, two_holder=7873) == "sparse64" and pick("pocp", max_ngen=65536, two_holder=7873) == "popc"
+    assert pick("pocp", max_ngen=65536, forced="sparse64") == "popc" and pick("pocp", max_ngen=65536, forced="sparsecol") == "popc"
+    assert pick("af", max_ngen=65536) == "sparsecol" and pick("jc", max_ngen=65536) == "sparsecol"
+    # af: "sum == 0" must mean "nothing shared" (no empty translation) and totals must fit 31 bits -- else 32 x 32 tiles up to 3,500^2, then the walker
+    assert pick("af", min_gene_len=0, side=3500) == "sparse" and pick("af", min_gene_len=0, side=3501) == "walker"
+    assert pick("af", min_gene_len=0, n=12250, nown=1000) == "sparse" and pick("af", min_gene_len=0, n=12251, nown=1000) == "walker"
+    assert pick("af", max_tlen=(1 << 31) - 1) == "sparsecol" and pick("af", max_tlen=1 << 31) == "sparse"
+    for forced in ("sparse64", "sparsecol"):
+        assert pick("af", min_gene_len=0, forced=forced) == "sparse"
+    assert pick("pocp", min_gene_len=0) == "sparsecol" and pick("gcs", min_gene_len=0) == "sparsecol"
+    assert pick("jc", max_nph=(1 << 30) - 1) == "sparsecol" and pick("jc", max_nph=1 << 30) == "popc"
+    # gcs / jc on sparse64 (masks beyond the column kernel): words > 113 + 5.4 x shared from 3,000^2, > 60 + 5.4 x shared from 6,000^2
+    many = dict(two_holder=7873, avg_shared=0.0)
+    for m in ("gcs", "jc"):
+        assert pick(m, words=113, **many) == "popc" and pick(m, words=114, **many) == "sparse64" and pick(m, words=114, side=2999, **many) == "popc", m
+        assert pick(m, words=126, two_holder=7873, avg_shared=2.5) == "popc" and pick(m, words=127, two_holder=7873, avg_shared=2.5) == "sparse64", m   # 113 + 13.5
+        assert pick(m, words=61, side=6000, **many) == "sparse64" and pick(m, words=60, side=6000, **many) == "popc" and pick(m, words=61, side=5999, **many) == "popc", m
+    # pocp on sparse64: words > 28 + 4.3 x shared from 2,500^2
+    assert pick("pocp", words=28, side=2500, **many) == "popc" and pick("pocp", words=29, side=2500, **many) == "sparse64"
+    assert pick("pocp", words=29, side=2499, **many) == "popc" and pick("pocp", words=37, side=2500, two_holder=7873, avg_shared=2.0) == "sparse64"      # 28 + 8.6
+    assert pick("pocp", words=36, side=2500, two_holder=7873, avg_shared=2.0) == "popc"
+    # af: sparse64 at every size below the column kernel's
+    assert pick("af", side=2) == "sparse64" and pick("af", side=1399, words=5, avg_shared=34.0) == "sparse64" and pick("af", side=20000, words=5, avg_shared=34.0) == "sparse64"
+    # a forced family is taken where it exists for the metric
+    for m in C.SET_METRICS:
+        counts = m in ("gcs", "jc")
+        assert pick(m, forced="popc") == ("sparsecol" if m == "af" else "popc"), m
+        assert pick(m, forced="sparse") == ("sparsecol" if counts else "sparse"), m
+        assert pick(m, forced="walker") == ("sparsecol" if counts else "walker"), m
+        assert pick(m, forced="sparse64") == "sparse64" and pick(m, forced="sparsecol", side=100) == "sparsecol", m
+    lib = hip.load()
+    assert lib.pc_set_kernel_choice(None) == -1 and lib.pc_last_set_launch(None, None, None) == -1                    # PC_ERR_ARG
+    with pytest.raises(hip.HipLibraryError):
+        C.set_kernel_choice("jc", **_choice_base(nown=3001))
+
+
+def test_set_block_entries_counts_the_ragged_block(native_built):
+    """max_block_entries of the selector's inputs: blocks of 64 consecutive OWNED targets, and the last block of a shard -- fewer
+    than 64 targets -- counts: here it alone exceeds the value table, so the rank leaves the column kernel where the unsharded fill,
+    whose blocks are cut elsewhere, stays."""
+    import set_kernel_cases as S
+    from phamclust_amd import hip
+    C = hip.Context
+    per = np.full(200, 100, dtype=np.int64)
+    per[190:] = 2000                                                     # ten heavy genomes at the end
+    owned = np.arange(100, 200)                                          # a rank's targets: blocks [100, 164) and the ragged [164, 200)
+    assert C.set_max_block_entries(per, owned) == 26 * 100 + 10 * 2000 == 22600
+    assert C.set_max_block_entries(per, owned[:64]) == 6400 and C.set_max_block_entries(per, owned[:65]) == 6400
+    assert C.set_max_block_entries(per, np.arange(200)) == 8 * 2000 == 16000          # unsharded: [192, 200) is the last block
+    assert C.set_max_block_entries(per, np.arange(0)) == 0
+    assert C.set_max_block_entries(per, np.array([199, 0])) == 2100       # (owned[] is what it is given: no sorting, no dedup)
+    stats = {"sp_n": per}
+    assert int(S.block_entries(stats, owned).max()) == 22600 and S.block_entries(stats, owned).tolist() == [6400, 22600]
+    assert int(S.block_entries(stats).max()) == 16000 and S.block_entries(stats).shape == (4,)
+    # the numpy recount and the library agree on every shard of a designed collection
+    packed, st = S.collection("few400_empty")
+    costs = S.target_costs(packed)
+    for world in (1, 3, 8):
+        for balanced in S.DEALS:
+            for rank in range(world):
+                own = S.owned_targets(packed, rank, world, balanced, costs)
+                assert C.set_max_block_entries(st["sp_n"], own) == S.selector_inputs(st, own)["max_block_entries"]
+    # ragged block decides: cap 7,231 at 5,056 mask entries
+    base = _choice_base(n=3000, nown=100)
+    light, heavy = np.full(3000, 100), np.full(3000, 100)
+    heavy[2990:] = 400                                                   # [2964, 3000) of a rank owning [2900, 3000): 26 x 100 + 10 x 400 = 6,600 ... no overflow
+    assert C.set_max_block_entries(heavy, np.arange(2900, 3000)) == 6600
+    heavy[2990:] = 500                                                   # 2,600 + 5,000 = 7,600 > 7,231
+    n_ragged = C.set_max_block_entries(heavy, np.arange(2900, 3000))
+    assert n_ragged == 7600 and C.set_max_block_entries(light, np.arange(2900, 3000)) == 6400
+    base.update(n=30000, nown=100)                                       # (area 3,000,000 >= 1,400^2)
+    assert C.set_kernel_choice("af", **dict(base, max_block_entries=6400)) == "sparsecol"
+    assert C.set_kernel_choice("af", **dict(base, max_block_entries=n_ragged)) == "sparse64"
+
+
+def test_set_launch_shape_pins(native_built):
+    """pc_set_launch_shape on both sides of every threshold inside the five launchers, by hand from pc_pairs.hip (256 compute units)."""
+    from phamclust_amd import hip
+    C = hip.Context
+
+    def shape(family, metric, n, nown=None, words=79, two_holder=5000, **kw):
+        return C.set_launch_shape(family, metric, n, n if nown is None else nown, words, two_holder, **kw)
+
+    def edge(tiles_x, tiles_y, top=8):
+        e = top
+        while e > 1 and -(-tiles_x // e) * -(-tiles_y // e) < 128:
+            e //= 2
+        return e
+    # popcount tiles: 64 x 64 from 1,536 live tiles (half of the 64-tiles); N = 3,520 / 3,521: 55^2 / 2 = 1,512, 56^2 / 2 = 1,568
+    assert shape("popc", "jc", 3520)["tile"] == 32 and shape("popc", "jc", 3521)["tile"] == 64
+    assert shape("popc", "pocp", 5312, 2368)["tile"] == 32 and shape("popc", "pocp", 4096, 3072)["tile"] == 64          # 83 x 37 = 3,071; 64 x 48 = 3,072
+    assert shape("popc", "gcs", 3521, popc_tile=32)["tile"] == 32 and shape("popc", "gcs", 100, popc_tile=64)["tile"] == 64
+    s = shape("popc", "jc", 3521)                                    # 56 x 56 tiles: edge 8 -> 49 super-tiles, 4 -> 196; 14 rows x 2 x 8 XCDs x 16
+    assert (s["super_edge"], s["grid"], s["units"], s["units_per_wg"], s["lds"], s["chunks"]) == (4, 3584, 3584, 1, 0, 0)
+    # super-tile edge: halved while fewer than 128 super-tiles -- 32-tiles: 22 / 23, 44 / 45, 88 / 89 tiles a side
+    for n, e in ((704, 1), (705, 2), (1408, 2), (1409, 4), (2816, 4), (2817, 8)):
+        for family, metric in (("popc", "jc"), ("sparse", "af"), ("walker", "pocp")):
+            assert shape(family, metric, n, popc_tile=32)["super_edge"] == e, (family, n)
+    assert shape("popc", "jc", 20000)["super_edge"] == 8 and shape("sparse64", "jc", 20000)["super_edge"] == 16
+    for n, e in ((11264, 8), (11265, 16), (5632, 4), (5633, 8)):      # 64-tiles, top edge 16: 176 / 177 and 88 / 89 tiles a side
+        assert shape("sparse64", "af", n)["super_edge"] == e, n
+    assert shape("popc", "jc", 6400, 2134)["super_edge"] == 4 == edge(100, 34) and shape("popc", "jc", 6400, 2134)["grid"] == 9 * 4 * 8 * 16   # a trapezoid
+    assert shape("walker", "af", 3600)["grid"] == shape("sparse", "af", 3600, words=19, two_holder=1200)["grid"] == 15 * 2 * 8 * 64     # 113 tiles: edge 8
+    # 64 x 64 sparse tiles: one unit per workgroup up to 2,048 units (4 x the 512 resident workgroups), then about three
+    s = shape("sparse64", "af", 4096, 2048, words=19, two_holder=1200)          # 64 x 32 tiles, edge 4: 8 rows x 2 x 8 x 16
+    assert (s["super_edge"], s["units"], s["grid"], s["units_per_wg"]) == (4, 2048, 2048, 1)
+    s = shape("sparse64", "af", 4096, 2049, words=19, two_holder=1200)          # 33 tile rows: 9 x 2 x 8 x 16
+    assert (s["units"], s["grid"], s["units_per_wg"]) == (2304, 2048, 2)
+    s = shape("sparse64", "af", 6000, words=19, two_holder=1200)
+    assert (s["super_edge"], s["units"], s["grid"], s["units_per_wg"]) == (8, 12288, 4096, 3)
+    assert shape("sparse64", "af", 6000, words=19, two_holder=1200, n_cu=64)["grid"] == 4096 and shape("sparse64", "af", 2560, n_cu=64)["grid"] == 640   # (4 x 128 resident < a third of 1,920 units)
+    # ... mask chunks: one up to 7,680 entries (af's two-batch instance stages broadcasts: 6,912), two from 4,000 x 4,000 with 2,048 entries
+    s = shape("sparse64", "jc", 100, two_holder=7680)
+    assert (s["chunks"], s["chunk"], s["batches"], s["dense"], s["lds"]) == (1, 7680, 2, 0, 7680 * 8 + 16640)
+    s = shape("sparse64", "jc", 100, two_holder=7681)
+    assert (s["chunks"], s["chunk"], s["batches"], s["dense"], s["lds"]) == (2, 3904, 1, 0, 3904 * 8 + 16640)
+    s = shape("sparse64", "af", 100, two_holder=6912)
+    assert (s["chunks"], s["chunk"], s["batches"], s["dense"], s["lds"]) == (1, 6912, 2, 1, 6912 * 8 + 16640 + 6144)
+    s = shape("sparse64", "af", 100, two_holder=6913)
+    assert (s["chunks"], s["chunk"], s["batches"], s["dense"], s["lds"]) == (2, 3520, 1, 0, 3520 * 8 + 16640)
+    assert shape("sparse64", "pocp", 100, two_holder=6913)["chunks"] == 1 and shape("sparse64", "pocp", 100, two_holder=7681)["chunks"] == 2
+    for m in C.SET_METRICS:
+        assert shape("sparse64", m, 4000, 3999)["chunks"] == 1 and shape("sparse64", m, 4000)["chunks"] == 2 and shape("sparse64", m, 4000)["chunk"] == 2560, m
+        assert shape("sparse64", m, 4000, two_holder=1984)["chunks"] == 1 and shape("sparse64", m, 4000, two_holder=1985)["chunks"] == 2, m   # 31 / 32 words
+        assert shape("sparse64", m, 4000)["batches"] == 1 and shape("sparse64", m, 4000)["dense"] == 0 and shape("sparse64", m, 4000, 3999)["dense"] == (m == "af"), m
+    assert shape("sparse64", "jc", 100, s64_chunks=3)["chunks"] == 3 and shape("sparse64", "jc", 100, s64_chunks=3)["chunk"] == 27 * 64
+    assert shape("sparse64", "jc", 100, two_holder=128, s64_chunks=3)["chunks"] == 1                       # (more chunks than words: ignored)
+    # 32 x 32 sparse tiles: every pham of the VOCABULARY in one chunk up to 10,240, else 8,192 at a time
+    s = shape("sparse", "af", 100, words=160)
+    assert (s["chunks"], s["chunk"], s["lds"]) == (1, 10240, 10240 * 4 + 8192)
+    s = shape("sparse", "pocp", 100, words=161)
+    assert (s["chunks"], s["chunk"], s["lds"]) == (2, 8192, 8192 * 4 + 8192)
+    # column kernel: seg = live tiles / (4 x 256), 1 ... 8; live = blocks x tiles / 2 + blocks
+    s = shape("sparsecol", "jc", 4032)                               # 63: 1,984 + 63 = 2,047
+    assert (s["seg"], s["runs"], s["grid"], s["lds"], s["vals_cap"], s["super_edge"]) == (1, 63, 64 * 65, 5056 * 8 + 16640, 0, 0)
+    s = shape("sparsecol", "af", 4033)                               # 64: 2,048 + 64
+    assert (s["seg"], s["runs"], s["grid"], s["lds"], s["vals_cap"]) == (2, 32, 64 * 34, 80 * 1024 - 256, 7231)
+    s = shape("sparsecol", "pocp", 20000)
+    assert (s["seg"], s["runs"], s["grid"]) == (8, 40, 320 * 42)
+    assert shape("sparsecol", "jc", 7200, 2400)["seg"] == 2 and shape("sparsecol", "jc", 7200, 900)["seg"] == 1        # 38 x 113 / 2 + 38 = 2,185; 15 x 113 / 2 + 15 = 862
+    assert shape("sparsecol", "jc", 20000, col_seg=1)["runs"] == 313 and shape("sparsecol", "jc", 20000, col_seg=64)["runs"] == 5
+    assert shape("sparsecol", "jc", 20000, col_seg=65)["seg"] == 8 and shape("sparsecol", "jc", 4033, n_cu=64)["seg"] == 8
+    assert shape("sparsecol", "jc", 100, two_holder=7872)["lds"] == 7872 * 8 + 16640 and shape("sparsecol", "jc", 100, two_holder=7873)["lds"] == 0
+    assert shape("sparsecol", "af", 100, two_holder=6272)["vals_cap"] == 1151 and shape("sparsecol", "pocp", 100, two_holder=6273)["vals_cap"] == 0
+    assert shape("sparsecol", "pocp", 100, two_holder=6273)["lds"] == 0
+    # epilogue table of the popcount tiles: (top + 1)(2 top + 1) entries for gcs / jc, (2 top + 1)^2 for pocp, up to 4 Mi
+    assert 1448 * 2895 <= 4 << 20 < 1449 * 2897 and 2047 ** 2 <= 4 << 20 < 2049 ** 2
+    for m in ("gcs", "jc"):
+        assert shape("popc", m, 100, table_top=1447)["table"] == 1 and shape("popc", m, 100, table_top=1448)["table"] == 0, m
+    assert shape("popc", "pocp", 100, table_top=1023)["table"] == 1 and shape("popc", "pocp", 100, table_top=1024)["table"] == 0
+    # nothing to launch; arguments that name no launch
+    assert shape("sparse64", "af", 1)["grid"] == 0 and shape("popc", "jc", 100, 0)["grid"] == 0
+    for family, metric in (("popc", "af"), ("sparse", "jc"), ("walker", "gcs")):
+        with pytest.raises(hip.HipLibraryError):
+            shape(family, metric, 100)
+    assert ctypes.sizeof(hip.PcSetInputs) == 72 and ctypes.sizeof(hip.PcSetShape) == 64
+
+
+# Coverage classes a default process can reach (tests/set_kernel_cases.py: reachable_classes) that no unforced fill of the GPU
+# tests reaches, each with its reason.  Keys are `class_of` tuples: (family, metric group, tile edge, super-tile edge, several
+# units per workgroup, mask chunks > 1, (batches, dense), epilogue table, sharded).
+SET_CLASSES_UNREACHED = {}          # (none left: few20000 / many20000 shard three ways at super-tile edge 16)
+
+
+def test_set_kernel_cases_reach_every_class(native_built):
+    """The unforced fills of tests/test_gpu_set_kernels.py (CASES: every collection unsharded, and by every rank of its worlds
+    under both deals) together with the existing synth(20000, 5000) and synth_real(1000) fills reach every coverage class a
+    default process can reach -- the sweep of the library's two host functions over N, nown <= 20,000, the generators' word /
+    pham / shared ranges, an empty translation and an overflowing block (reachable_classes) -- except the classes listed above.
+    Families and shapes come from the numpy recount of each packed collection, never from a context.  Numeric edges that no
+    generator produces (65,536 genes, 1,448 phams in one genome ...) are the pins' and the GPU module's own cases."""
+    import set_kernel_cases as S
+    from phamclust_amd import hip
+    C = hip.Context
+    reachable = S.reachable_classes(C)
+    cases = {**S.CASES, **S.EXISTING_CASES}
+    by_case = S.classes_by_case(C, cases)
+    assert set(S.EXPECTED_WHOLE) == set(S.CASES) == set(S.COLLECTIONS) - set(S.EXISTING_CASES)
+    reached = S.union_classes(by_case)
+    listing = "\n".join(f"{S.class_name(c)}  <-  {reached.get(c, SET_CLASSES_UNREACHED.get(c, 'NOTHING'))}" for c in sorted(set(reachable) | set(reached), key=str))
+    assert len(SET_CLASSES_UNREACHED) == 0 and set(SET_CLASSES_UNREACHED) <= set(reachable) and not set(SET_CLASSES_UNREACHED) & set(reached), listing
+    missing = set(reachable) - set(reached) - set(SET_CLASSES_UNREACHED)
+    assert not missing, "no case reaches: " + "; ".join(S.class_name(c) for c in sorted(missing, key=str)) + "\n" + listing
+    # what the issue names: the trapezoid classes of the 64-tile kernels beyond super-tile edge 1, several units, seg > 1 on a shard
+    sharded = [c for c in reached if c[-1]]
+    assert {c[3] for c in sharded if c[0] == "popc" and c[2] == 64} >= {4, 8}
+    assert {c[3] for c in sharded if c[0] == "sparse64"} >= {1, 2, 4, 8} and any(c[4] for c in sharded if c[0] == "sparse64")
+    assert any(c[4] for c in sharded if c[0] == "sparsecol") and any(not c[4] for c in sharded if c[0] == "sparsecol")
+    assert {c[0] for c in reached} == set(S.FAMILIES)
+    # the check has teeth: without col7200 no shard runs the column kernel with seg > 1; without the uniform draws pocp never
+    # runs sparse64's two-batch instance
+    fewer = S.union_classes(by_case, without=("col7200",))
+    assert set(reachable) - set(fewer) - set(SET_CLASSES_UNREACHED) and not any(c[4] and c[-1] for c in fewer if c[0] == "sparsecol")
+    fewer = S.union_classes(by_case, without=("uniform",))
+    assert any(c[:2] == ("sparse64", "pocp") and c[6] == (2, 0) for c in set(reachable) - set(fewer))
+
+
+def set_edges_fixture():
+    """{(metric, as_distance): condensed vector} of tests/golden/set_edges/ (written by the LIVE reference), after checking that the
+    committed generator still rebuilds the input the reference was given."""
+    import json
+    import set_kernel_cases as S
+    from conftest import GOLDEN, read_adjacency_condensed
+    manifest = json.load(open(os.path.join(GOLDEN, "set_edges", "manifest.json")))
+    genomes = S.edge_genomes()
+    assert [g.name for g in genomes] == list(S.EDGE_NAMES) == sorted(S.EDGE_NAMES)
+    assert S.edge_digest(genomes) == manifest["input_sha256"], "the generator no longer reproduces the fixture's input"
+    assert sum(len(g) for g in genomes) == manifest["genes"] == 136022 and manifest["pairs"] == 36
+    want = {}
+    for metric in S.SET_METRICS:
+        names, dist, diag = read_lower_triangle(os.path.join(GOLDEN, "set_edges", manifest["files"][metric]["distance_lower_triangle"]))
+        assert names == list(S.EDGE_NAMES) and not diag.any()
+        want[(metric, True)] = dist
+        want[(metric, False)], _ = read_adjacency_condensed(os.path.join(GOLDEN, "set_edges", manifest["files"][metric]["similarity_adjacency"]), names)
+    return want
+
+
+def test_set_edges_fixture_holds_both_oracles(native_built):
+    """The numeric-edge collection (65,535 / 65,536 copies of a pham, 1,447 / 1,448 phams, 1,023 / 1,024 genes, entries of
+    65,535 / 65,536 residues, empty translations): the C oracle and the Python restatement of metrics.py:26-157 equal what the
+    live reference wrote for all 36 pairs, distance and similarity -- and so does every sub-collection the GPU tests upload."""
+    import set_kernel_cases as S
+    from oracle import oracle as O
+    want = set_edges_fixture()
+    genomes = S.edge_genomes()
+    packed = S.edge_packed("all")
+    stats = S.recount(packed)
+    assert (stats["max_ngen"], stats["max_nph"], stats["max_ent_len"], stats["min_gene_len"]) == (65536, 1448, 65536, 0)
+    py = {"gcs": O.py_gcs, "jc": O.py_jc, "pocp": O.py_pocp, "af": O.py_af}
+    for (metric, dist), w in want.items():
+        assert np.isfinite(w).all() and np.array_equal(O.fill(packed, metric, dist), w), (metric, dist)
+        restated = np.array([py[metric](genomes[a], genomes[b], as_distance=dist) for a in range(9) for b in range(a + 1, 9)])
+        assert np.array_equal(restated, w), (metric, dist)
+    assert len({float(x) for x in want[("pocp", True)]}) > 20                      # (a collection whose pairs have values to get wrong)
+    for subset, keep in S.EDGE_SUBSETS.items():
+        sub = S.edge_packed(subset)
+        assert sub.names == list(keep)
+        for (metric, dist), w in want.items():
+            assert np.array_equal(O.fill(sub, metric, dist), S.sub_condensed(w, list(S.EDGE_NAMES), keep)), (subset, metric, dist)
+    # which side of each guard the sub-collections sit on
+    side = {name: S.recount(S.edge_packed(name)) for name in S.EDGE_SUBSETS}
+    assert (side["lo"]["max_ngen"], side["lo"]["max_nph"], side["lo"]["max_ent_len"], side["lo"]["min_gene_len"]) == (65535, 1447, 65535, 1)
+    assert (side["hi"]["max_ngen"], side["hi"]["max_nph"], side["hi"]["max_ent_len"], side["hi"]["min_gene_len"]) == (65536, 1448, 65536, 1)
+    assert side["genes1023"]["max_ngen"] == 1023 and side["genes1024"]["max_ngen"] == 1024 and side["phams1447"]["max_nph"] == 1447
+    assert side["phams1448"]["max_nph"] == 1448 and side["empty"]["min_gene_len"] == 0
+
+
 def test_borrowed_array_guards_every_numpy_route():
     """a lent result must refuse ufuncs, reductions and numpy functions too once its loan has ended, not only
     indexing and conversion (host logic: the view class itself, over ordinary memory)."""
