@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 154   /* 0.5.3: pc_set_kernel_choice, pc_set_launch_shape, pc_set_max_block_entries, pc_last_set_launch */
+#define PC_VERSION 155   /* 0.5.4: pc_fill_rows, pc_fill_rows_dev */
 
 typedef enum {
     PC_OK = 0,
@@ -169,6 +169,28 @@ int pc_fill_dev(pc_ctx* ctx, int metric, int as_distance, void* out_dev, void* s
 /* This rank's shard only, shard-local order, into device memory f64[pc_shard_stride()]
  * (tail beyond pc_shard_pairs() is zero-filled).  Followed by the caller's RCCL gather. */
 int pc_fill_shard_dev(pc_ctx* ctx, int metric, int as_distance, void* shard_dev, void* stream, pc_stats* stats);
+
+/*
+ * Rows fill: new genomes against a filled matrix.  The reference has the container half of this -- SymMatrix.append_node grows
+ * a matrix by one node, matrix.py:169-213 -- and nothing that produces the values to feed it; its only fill is the whole
+ * triangle (matrix.py:479-491).  `rows` holds n_rows distinct genome indices, strictly ascending (the "query" genomes); the
+ * call fills the pairs {q, g}, q in rows, g != q, each in the whole fill's orientation -- min(q, g) is the reference's
+ * `source`, max(q, g) its `target` -- and with the whole fill's values bit for bit, a pair of two queries computed once.
+ * out: row-major f64[n_rows][N]: out[k * N + g] is the value of {rows[k], g}, out[k * N + rows[k]] the diagonal,
+ * 1.0 - as_distance (matrix.py:467-468).  The six metrics and PC_AAI_PPOS.  gcs / jc / pocp / af always run on the rows
+ * walker: no selector, and pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill.  aai / peq are cut
+ * into successive ranges of rows under the rule of pc_set_plan_budget (the chunking rule over the rows' alignment counts; the
+ * 8 bytes per slot of the per-pair count / offset arrays count against the budget, so only one range's slot arrays are ever
+ * resident), same values whatever the cut.  stats: n_pairs = n_rows (N - 1) - n_rows (n_rows - 1) / 2 distinct pairs;
+ * n_alignments, n_cells, n_residue_bytes over those pairs, each once; n_chunks and the times as for a whole fill;
+ * pc_last_plan_tasks covers a rows fill too.
+ * n_rows == 0: PC_OK, nothing done; n_rows == N is allowed.  PC_ERR_ARG: rows not strictly ascending or out of range, NULL out,
+ * bad metric.  PC_ERR_STATE: before upload, on a sharded context (world != 1), aai / peq before pc_upload_residues.
+ * PC_ERR_DATA: an empty translation under aai / peq.  pc_fill_rows delivers into host memory; pc_fill_rows_dev leaves the
+ * result in HBM (out_dev: device f64[n_rows * N]; stream as for pc_fill_dev).
+ */
+int pc_fill_rows(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, double* out_host, pc_stats* stats);
+int pc_fill_rows_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, void* out_dev, void* stream, pc_stats* stats);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

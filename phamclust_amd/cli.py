@@ -45,6 +45,9 @@ _OPTIONS = (
     (None, "-d", "--debug", dict(action="store_true", help="log at DEBUG level")),
     (None, "-n", "--no-sub", dict(action="store_true", help="skip the sub-clustering pass")),
     (None, "-r", "--remove-tmp", dict(action="store_true", help="delete the cache directory at the end (re-runs then recompute the matrix)")),
+    (None, "-x", "--extend", dict(type=pathlib.Path, default=None, help="distance matrix an earlier run wrote over a SUBSET of these genomes (its cache's "
+                                                                       "02_distmats/<metric>_distance_matrix.tsv, or a squareform file): only the rows "
+                                                                       "of the genomes it lacks are filled, on one GPU")),
     (None, "-t", "--threads", dict(type=int, default=CPUS, help="accepted for compatibility; the six metrics run on the GPU (see --gpus)")),
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),

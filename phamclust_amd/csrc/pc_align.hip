@@ -269,19 +269,29 @@ static int count_per_target(pc_ctx* c, int condensed, hipStream_t st, std::vecto
     return PC_OK;
 }
 
-// PLAN of the owned targets [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
+// Which walk a stage launches, over which slots: the owned targets [k0, k1) of the context's shard (k_walk; slot arrays indexed
+// by the shard-local pair index), or -- rows != NULL -- the query rows [k0, k1) of a rows fill (k_walk_rows; slot arrays
+// [k1 - k0][N], filled for that range alone).
+static int walk_domain(pc_ctx* c, int mode, const PcRows* rows, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
+    if (rows) return pc_launch_walk_rows(mode, c->dev, *rows, k0, k1, a, st);
+    PcShard sub = c->shard;
+    sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
+    return pc_launch_walk(mode, c->dev, sub, a, st);
+}
+
+// PLAN of the owned targets (or query rows) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
 // sorted by launch class.  Leaves its results in the context's work buffers and c->plan; two small read-backs.
-static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A) {
+static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A, const PcRows* rows = nullptr) {
     int rc = PC_OK;
     PcRange range("pc:plan");
     PlanningScope planning;
     const PcDev& d = c->dev;
     pc_ctx::PlanState& P = c->plan;
     P.valid = false; P.ppos = ppos; P.condensed = condensed; P.A = (int64_t)A; P.n_distinct = 0; P.ntasks = 0; P.tb.assign(c->nlc + 1, 0);
-    P.k0 = k0; P.k1 = k1; P.whole = c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
+    P.k0 = k0; P.k1 = k1; P.whole = !rows && c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
     memset(&P.st, 0, sizeof(P.st));
     pc_stats& local = P.st;
-    const int64_t base = c->h_lbase[k0], Lc = c->h_lbase[k1] - base;
+    const int64_t base = rows ? 0 : c->h_lbase[k0], Lc = rows ? (int64_t)(k1 - k0) * d.N : c->h_lbase[k1] - base;
     local.n_pairs = Lc;
     local.n_alignments = (int64_t)A;
     if (A > (uint64_t)PC_PLAN_MAX_ALIGNMENTS) {
@@ -296,8 +306,6 @@ static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0
     // alignment slot of a pair = exclusive scan of the chunk's counts (slots start at 0 in every chunk)
     if (Lc > 0 && (rc = pc_scan_exclusive_u32(c->b_na.as<uint32_t>() + base, c->b_off.as<uint32_t>() + base, Lc, c->b_scan_tmp.as<uint32_t>(),
                                               (int64_t)(c->b_scan_tmp.cap / 4), st))) return rc;
-    PcShard sub = c->shard;
-    sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
     PcWalkArgs a; memset(&a, 0, sizeof(a));
     a.as_distance = 0; a.condensed = condensed;
     a.off = c->b_off.as<uint32_t>();
@@ -315,7 +323,7 @@ static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0
         const int64_t tmp_elems = (int64_t)(c->b_scan_tmp.cap / 4);
         // 2 ENUM: one sort key per alignment slot; 3 sort; 4 distinct alignments, aliases, buckets (pc_plan.hip)
         a.key = c->b_key0.as<unsigned long long>(); a.val = c->b_val0.as<uint32_t>();
-        if ((rc = pc_launch_walk(PCW_ENUM, d, sub, a, st))) return rc;
+        if ((rc = walk_domain(c, PCW_ENUM, rows, k0, k1, a, st))) return rc;
         if ((rc = pc_sort_pairs(c->b_sort_tmp.p, c->b_sort_tmp.cap, c->b_key0.as<unsigned long long>(), c->b_key1.as<unsigned long long>(),
                                 c->b_val0.as<uint32_t>(), c->b_val1.as<uint32_t>(), An, key_bits, st))) return rc;
         if ((rc = pc_launch_mark_heads(c->b_key1.as<unsigned long long>(), c->b_flags.as<uint32_t>(), An, st))) return rc;
@@ -390,16 +398,14 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
 }
 
 // REDUCE: best match per anchor gene through the aliases, fp64 epilogue (metrics.py:204-232, 247-253), over the plan's targets
-static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st) {
+static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcRows* rows = nullptr) {
     PcRange range("pc:reduce");
     pc_ctx::PlanState& P = c->plan;
     if (!P.valid) { pc_set_error("reduce: no plan (pc_plan_dev first)"); return PC_ERR_STATE; }
-    PcShard sub = c->shard;
-    sub.nown = P.k1 - P.k0; sub.owned = c->shard.owned + P.k0; sub.lbase = c->shard.lbase + P.k0; sub.ident = c->shard.ident && P.k0 == 0;
     PcWalkArgs a; memset(&a, 0, sizeof(a));
     a.off = c->b_off.as<uint32_t>(); a.alias = c->b_alias.as<uint32_t>(); a.res = res; a.out = out;
     a.as_distance = as_distance ? 1 : 0; a.condensed = P.condensed;
-    return pc_launch_walk(metric == PC_AAI ? PCW_AAI : PCW_PEQ, c->dev, sub, a, st);
+    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, rows, P.k0, P.k1, a, st);
 }
 
 // a finished chunk: its plan's counts, and its tasks per launch class for pc_last_plan_tasks
@@ -487,6 +493,94 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
         ++nchunks; k = k1;
     }
     c->plan.valid = false;                                                // the last chunk's plan is not "the plan of the fill"
+    local.n_chunks = nchunks;
+    c->last_plan_tasks_valid = true;
+    local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;
+    return PC_OK;
+}
+
+// aai / peq of a rows fill (pc_fill_rows*): COUNT over every query row (totals, alignments per row), then plan -> align -> reduce over
+// successive ranges of the rows.  The ranges follow pc_chunk_plan over the rows' costs under the budget a whole fill has
+// (pc_set_plan_budget / PC_PLAN_BYTES, 2^31-2 alignments per plan, a failed allocation halves the range); a row costs its
+// alignments plus its N slots of na / off (8 bytes each, stated in alignments), so a request of many rows never holds more
+// than a chunk's worth of slot arrays.  `out` is the whole f64[n_rows][N]; the reduce of a range writes its rows and the mirror
+// cells of pairs of two queries.  Values do not depend on the cut: every pair's alignments stay in one range.
+int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
+    int rc = PC_OK;
+    const PcDev& d = c->dev;
+    const int M = rows.nrows;
+    if (!c->residues_ready) { pc_set_error("fill: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    if (d.G > 0 && c->min_gene_len == 0) {
+        pc_set_error("fill: an empty translation cannot be aligned (aai/peq); the reference fails on it too"); return PC_ERR_DATA;
+    }
+    c->last_plan_tasks_valid = false;
+    c->last_plan_tasks.assign(c->nlc, 0);
+    c->plan.valid = false;
+    // COUNT over all rows: totals and aln_row (no slot array yet)
+    std::vector<uint64_t> cost(M);
+    {
+        PcRange range("pc:count");
+        if ((rc = c->b_totals.ensure(64)) || (rc = c->b_aln_t.ensure((size_t)M * 8))) return rc;
+        PC_HIP(hipMemsetAsync(c->b_totals.p, 0, 64, st));
+        PC_HIP(hipMemsetAsync(c->b_aln_t.p, 0, (size_t)M * 8, st));
+        PcWalkArgs a; memset(&a, 0, sizeof(a));
+        a.totals = c->b_totals.as<unsigned long long>(); a.aln_t = c->b_aln_t.as<unsigned long long>();
+        if ((rc = pc_launch_walk_rows(PCW_COUNT, d, rows, 0, M, a, st))) return rc;
+        uint64_t* h_tot = (uint64_t*)(c->h_plan.as<uint32_t>() + 1000);
+        PC_HIP(hipMemcpyAsync(h_tot, c->b_totals.p, 24, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipMemcpyAsync(cost.data(), c->b_aln_t.p, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipStreamSynchronize(st));
+        local.n_alignments = (int64_t)h_tot[0]; local.n_cells = (int64_t)h_tot[1]; local.n_residue_bytes = (int64_t)h_tot[2];
+    }
+    const uint64_t A = (uint64_t)local.n_alignments;
+    // a row's cost in alignments: its own + the 8 bytes per slot of its N entries of na / off
+    const uint64_t slot_cost = ((uint64_t)d.N * 8 + PC_PLAN_BYTES_PER_ALIGNMENT - 1) / PC_PLAN_BYTES_PER_ALIGNMENT;
+    for (uint64_t& x : cost) x += slot_cost;
+    uint64_t max_aln = (uint64_t)PC_PLAN_MAX_ALIGNMENTS;
+    if (c->plan_budget > 0 || (A + slot_cost * (uint64_t)M) * PC_PLAN_BYTES_PER_ALIGNMENT > ((uint64_t)1 << 30))
+        max_aln = std::min<uint64_t>(max_aln, (uint64_t)std::max<int64_t>(plan_budget_bytes(c) / PC_PLAN_BYTES_PER_ALIGNMENT, 1));
+    float ms_plan = 0.f, ms_align = 0.f, ms_reduce = 0.f;
+    int k = 0, nchunks = 0;
+    while (k < M) {
+        int32_t cut[2] = {0, 0};
+        if ((rc = pc_chunk_plan(cost.data() + k, M - k, max_aln, cut, 2)) < 0) return rc;
+        const int k1 = k + cut[1];
+        const int64_t Lc = (int64_t)(k1 - k) * d.N;
+        uint64_t run = 0;
+        for (int i = k; i < k1; ++i) run += cost[i] - slot_cost;
+        if (timed) PC_HIP(hipEventRecord(c->ev[4], st));
+        // the range's own COUNT: alignments per slot (its totals go to scratch words nobody reads)
+        rc = c->b_na.ensure((Lc + 1) * 4);
+        if (rc == PC_OK) rc = c->b_off.ensure((Lc + 1) * 4);
+        if (rc == PC_OK) {
+            PC_HIP(hipMemsetAsync(c->b_na.p, 0, (Lc + 1) * 4, st));
+            PcWalkArgs a; memset(&a, 0, sizeof(a));
+            a.na = c->b_na.as<uint32_t>(); a.totals = c->b_totals.as<unsigned long long>() + 5;
+            rc = pc_launch_walk_rows(PCW_COUNT, d, rows, k, k1, a, st);
+        }
+        if (rc == PC_OK) rc = stage_plan(c, ppos, 0, st, k, k1, run, &rows);
+        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
+        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, &rows); }
+        if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller range, not an error
+            PC_HIP(hipStreamSynchronize(st));
+            release_plan_buffers(c);
+            c->b_scratch.release(); c->b_na.release(); c->b_off.release();
+            max_aln = std::max<uint64_t>(std::min(max_aln, run + slot_cost * (uint64_t)(k1 - k)) / 2, 1);
+            continue;
+        }
+        if (rc != PC_OK) return rc;
+        PC_HIP(hipEventRecord(c->ev[3], st));
+        add_plan_stats(c, local);
+        if (timed) {
+            float x = 0.f;
+            PC_HIP(hipEventSynchronize(c->ev[3]));
+            PC_HIP(hipEventElapsedTime(&x, c->ev[4], c->ev[1])); ms_plan += x;
+            PC_HIP(hipEventElapsedTime(&x, c->ev[1], c->ev[2])); ms_align += x;
+            PC_HIP(hipEventElapsedTime(&x, c->ev[2], c->ev[3])); ms_reduce += x;
+        }
+        ++nchunks; k = k1;
+    }
+    c->plan.valid = false;                                                // a rows plan serves no later stage
     local.n_chunks = nchunks;
     c->last_plan_tasks_valid = true;
     local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;

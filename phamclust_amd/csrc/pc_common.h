@@ -57,6 +57,13 @@ struct PcShard {
     const int64_t* lbase;             // [nown+1] shard-local index of pair (0, owned[k]); pair (s,t) -> lbase[k] + s
 };
 
+// Pair domain of a rows fill: the query genomes, strictly ascending, against every other genome (k_walk_rows).
+struct PcRows {
+    int32_t nrows;
+    const int32_t* rows;              // [nrows] query genome q
+    const int32_t* row_of;            // [N] position of genome g in rows, or -1
+};
+
 // One wave task of the alignment kernels: column gene + a range of its bucket.
 struct PcTask { int32_t gene, begin, end, pad; };   // pad: launch class of the task (planning only)
 
@@ -77,7 +84,8 @@ struct PcTaskPlan {
 };
 
 // walker modes (pc_pairs.hip)
-enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5 };
+enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5,
+       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows only (whole fills count gcs / jc on the tile kernels)
 enum { PCW_SPARSE_GCS = 10, PCW_SPARSE_JC = 11 };   // k_sparse_tile64 only: shared-pham counts, one direction
 
 struct PcWalkArgs {
@@ -85,9 +93,10 @@ struct PcWalkArgs {
     uint32_t* na;                     // [Lp] alignments per pair
     unsigned long long* totals;       // [0] alignments [1] cells [2] residue bytes (as the reference would run them)
     unsigned long long* cost_t;       // [N] or NULL: DP cells per target genome (input of the cost-balanced deal)
-    unsigned long long* aln_t;        // [N] or NULL: alignments per target genome (where a fill that exceeds its memory budget is cut)
+    unsigned long long* aln_t;        // [N] or NULL: alignments per target genome (where a fill that exceeds its memory budget is cut);
+                                      //   k_walk_rows: [nrows], alignments per query row (aln_row)
     // ENUM: alignment slot k of a pair = off[pair] + its position in the reference's loop order
-    const uint32_t* off;              // [Lp] exclusive scan of na
+    const uint32_t* off;              // [Lp] exclusive scan of na   (k_walk_rows: na / off are [rows of the range][N], slot (k - kb) * N + g)
     unsigned long long* key;          // [A] (column sequence rank << ubits) | row sequence rank
     uint32_t* val;                    // [A] k
     // AAI / PEQ
@@ -124,6 +133,8 @@ bool pc_set_table_dims(int metric, int top, int* sh_dim, int* tot_dim);
 int pc_launch_set_popc(const PcDev& d, const PcShard& sh, int metric, int as_distance, double* out, int condensed,
                        double* lut, bool build_lut, int top, hipStream_t st, pc_set_shape* shape_out = nullptr);
 int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st, pc_set_shape* shape_out = nullptr);
+// the walker over the query rows [kb, ke) of a rows fill; a.out is the whole f64[nrows][N], a.condensed is not read
+int pc_launch_walk_rows(int mode, const PcDev& d, const PcRows& rw, int kb, int ke, const PcWalkArgs& a, hipStream_t st);
 int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);   // pocp / af
 int pc_launch_pair_entries(const int32_t* pham, const int32_t* len, const int32_t* cnt, uint2* pair_len, uint2* pair_cnt, int64_t n, hipStream_t st);
 int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, const int32_t* len, const int32_t* cnt, const int32_t* dense, int W2,

@@ -1,5 +1,5 @@
 // pc_fill.hip -- the fill entry points of libphamclust_hip.so (pc_fill, pc_fill_borrow, pc_fill_dev, pc_fill_shard_dev,
-// pc_assemble_dev) and the set-metric kernel selector.
+// pc_assemble_dev, pc_fill_rows, pc_fill_rows_dev) and the set-metric kernel selector.
 #include "pc_host.h"
 
 #ifndef PC_COL_MIN_N
@@ -233,6 +233,76 @@ extern "C" int pc_fill_shard_dev(pc_ctx* c, int metric, int as_distance, void* s
     if (c->shard_stride > c->shard_pairs)
         PC_HIP(hipMemsetAsync((double*)shard_dev + c->shard_pairs, 0, (c->shard_stride - c->shard_pairs) * 8, st));
     return fill_impl(c, metric, as_distance, (double*)shard_dev, 0, st, stats);
+}
+
+// ---- rows fill: the query genomes rows[0..n_rows) against every other genome, f64[n_rows][N].  The set metrics always run on
+// the rows walker (no selector: pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill); aai / peq run
+// COUNT -> plan -> align -> reduce over ranges of the rows (fill_rows_aligned).
+extern "C" int pc_fill_rows_dev(pc_ctx* c, int metric, int as_distance, const int32_t* rows, int n_rows, void* out_dev, void* stream, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_rows: upload first"); return PC_ERR_STATE; }
+    if (c->world != 1) { pc_set_error("pc_fill_rows: context is sharded (%d/%d); a rows fill is a one-GPU call on an unsharded context", c->rank, c->world); return PC_ERR_STATE; }
+    if (metric < PC_GCS || metric > PC_AAI_PPOS) { pc_set_error("pc_fill_rows: metric %d", metric); return PC_ERR_ARG; }
+    const int ppos = metric == PC_AAI_PPOS;
+    if (ppos) metric = PC_AAI;
+    if (n_rows < 0) { pc_set_error("pc_fill_rows: n_rows %d", n_rows); return PC_ERR_ARG; }
+    pc_stats local; memset(&local, 0, sizeof(local));
+    if (n_rows == 0) { if (stats) *stats = local; return PC_OK; }
+    if (!rows || !out_dev) { pc_set_error("pc_fill_rows: %s is NULL", rows ? "out" : "rows"); return PC_ERR_ARG; }
+    const PcDev& d = c->dev;
+    const int N = d.N;
+    for (int k = 0; k < n_rows; ++k)
+        if (rows[k] < 0 || rows[k] >= N || (k > 0 && rows[k] <= rows[k - 1])) {
+            pc_set_error("pc_fill_rows: rows must be strictly ascending genome indices below %d (rows[%d] = %d)", N, k, rows[k]); return PC_ERR_ARG;
+        }
+    if (metric >= PC_AAI && !c->residues_ready) { pc_set_error("pc_fill_rows: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    PC_ON_DEVICE(c);
+    static const char* const fill_names[] = {"pc:fill_rows:gcs", "pc:fill_rows:jc", "pc:fill_rows:pocp", "pc:fill_rows:af", "pc:fill_rows:aai", "pc:fill_rows:peq"};
+    PcRange range(fill_names[metric]);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = PC_OK;
+    if ((rc = wait_last_work(c, st, false))) return rc;                    // (the domain tables below are rewritten by a blocking copy: nothing may still read them)
+    std::vector<int32_t> h_rows(rows, rows + n_rows), h_row_of((size_t)N, -1);
+    for (int k = 0; k < n_rows; ++k) h_row_of[rows[k]] = k;
+    if ((rc = upload_vec(c->b_rows, h_rows)) || (rc = upload_vec(c->b_row_of, h_row_of))) return rc;
+    const PcRows rw{n_rows, c->b_rows.as<int32_t>(), c->b_row_of.as<int32_t>()};
+    local.n_pairs = (int64_t)n_rows * (N - 1) - (int64_t)n_rows * (n_rows - 1) / 2;
+    as_distance = as_distance ? 1 : 0;
+    PC_HIP(hipEventRecord(c->ev[0], st));
+    if (metric < PC_AAI) {
+        PcWalkArgs a; memset(&a, 0, sizeof(a));
+        a.out = (double*)out_dev; a.as_distance = as_distance;
+        const int mode = metric == PC_GCS ? PCW_GCS : metric == PC_JC ? PCW_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
+        if ((rc = pc_launch_walk_rows(mode, d, rw, 0, n_rows, a, st))) return rc;
+        PC_HIP(hipEventRecord(c->ev[3], st));
+        local.n_chunks = 1;
+    } else {
+        rc = fill_rows_aligned(c, rw, metric, ppos, as_distance, (double*)out_dev, st, local, stats != nullptr);
+        if (rc != PC_OK) { (void)mark_work(c, st); return abi_rc(rc); }
+    }
+    if ((rc = mark_work(c, st))) return rc;
+    if (stats) {
+        PC_HIP(hipEventSynchronize(c->ev[3]));
+        c->busy = false;
+        PC_HIP(hipEventElapsedTime(&local.ms_total, c->ev[0], c->ev[3]));
+        if (metric < PC_AAI) local.ms_reduce = local.ms_total;
+        *stats = local;
+    }
+    return PC_OK;
+}
+
+extern "C" int pc_fill_rows(pc_ctx* c, int metric, int as_distance, const int32_t* rows, int n_rows, double* out_host, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_rows: upload first"); return PC_ERR_STATE; }
+    if (n_rows > 0 && !out_host) { pc_set_error("pc_fill_rows: out is NULL"); return PC_ERR_ARG; }
+    PC_ON_DEVICE(c);
+    int rc = PC_OK;
+    const int64_t cells = (int64_t)std::max(n_rows, 0) * c->dev.N;
+    if ((rc = wait_last_work(c, c->stream, false))) return rc;             // (b_out may still be read by a fill left on another stream)
+    if ((rc = c->b_out.ensure(std::max<int64_t>(cells, 1) * 8))) return abi_rc(rc);
+    if ((rc = pc_fill_rows_dev(c, metric, as_distance, rows, n_rows, c->b_out.p, c->stream, stats))) return rc;
+    if (n_rows > 0 && cells) PC_HIP(hipMemcpyAsync(out_host, c->b_out.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    c->busy = false;
+    return PC_OK;
 }
 
 extern "C" int pc_assemble_dev(pc_ctx* c, const void* gathered_dev, int world, void* out_condensed_dev, void* stream) {

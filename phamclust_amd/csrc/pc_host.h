@@ -111,6 +111,7 @@ struct pc_ctx {
     // work buffers (grow-only)
     DevBuf b_na, b_off, b_key0, b_key1, b_val0, b_val1, b_sort_tmp, b_flags, b_excl, b_alias, b_start_q, b_end_q, b_ntask_q, b_task_off_q, b_scan_tmp;
     DevBuf b_tasks, b_tasks_sorted, b_bucket_row, b_bucket_dest, b_res, b_totals, b_plan, b_scratch, b_out, b_lut, b_slice_begin, b_aln_t;
+    DevBuf b_rows, b_row_of;                // the domain of the last rows fill (PcRows: the query genomes, and every genome's position among them)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -233,3 +234,5 @@ static bool pc_launch_is_strip(int variant, int max_lb, int mode, int ppos) { re
 
 // aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
 int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);
+// the same over the query rows of a rows fill, chunked over ranges of rows; out: f64[rows.nrows][N] (pc_align.hip)
+int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);

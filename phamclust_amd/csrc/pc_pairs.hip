@@ -1508,6 +1508,177 @@ int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs
 }
 
 // ---------------------------------------------------------------------------------
+// The walker over a ROWS domain (pc_fill_rows): the pairs {q, g} of the query genomes q = rows[k], kb <= k < ke, with every
+// other genome g.  The reference has the container half of this (SymMatrix.append_node, matrix.py:169-213) and nothing that
+// produces its values; a pair runs here exactly as in the whole fill: s = min(q, g) is the reference's `source`, t = max(q, g)
+// its `target` (matrix.py:479-486; aai is not symmetric: a query is the source of some of its pairs and the target of others).
+//
+// A tile is TS query rows x TS genomes.  Lanes run over g, so the stores into out[k * N + g] are coalesced and a thread's four
+// slots (rows q + 8 m of the tile) share one genome: its bitmap word is read once per scanned word, from 32 distinct LDS rows of
+// odd stride (conflict free), the query's word is a broadcast.  What k_walk's comments say on the word scan (record which words
+// intersect, visit afterwards) and on the XCD-aware tile order holds unchanged; no tile is skipped, the domain is a rectangle.
+// Slot (k, g) is live iff g != q and not (g is a query itself and g < q): a pair of two queries belongs to the slot of the
+// smaller one, which also writes the mirror cell out[row_of[g] * N + q].  The slot g == q writes the diagonal, 1 - as_distance
+// (matrix.py:467-468).  Slot arrays (na, off) are [ke - kb][N]: slot (k - kb) * N + g; dead slots count zero alignments.
+// COUNT also sums a row's alignments into aln_t[k] (where a rows fill is cut into chunks); ENUM emits k_walk's keys, so the
+// sort, k_unique, the task builders and the alignment launches do not know which domain they serve.  GCS / JC count the shared
+// phams in the word scan itself and finish through pc_set_value's division, the tile kernels' own (table-free) epilogue.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ void pc_stage_tile_rows(const PcDev& d, const PcRows& rw, int g0, int k0, int ke, int w0, int wn,
+                                                   uint64_t (*rg)[WCH + 1], uint64_t (*rq)[WCH + 1]) {
+    for (int r = threadIdx.x >> 5; r < TS; r += 8) {
+        const int g = g0 + r, k = k0 + r;
+        const uint64_t* pg = g < d.N ? d.bitmap + (int64_t)g * d.Wstride + w0 : nullptr;
+        const uint64_t* pq = k < ke ? d.bitmap + (int64_t)rw.rows[k] * d.Wstride + w0 : nullptr;
+        for (int w = threadIdx.x & 31; w < wn; w += 32) {
+            rg[r][w] = pg ? pg[w] : 0ULL;
+            rq[r][w] = pq ? pq[w] : 0ULL;
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_walk_rows(PcDev d, PcRows rw, int kb, int ke, PcWalkArgs a) {
+    constexpr bool SETS = MODE == PCW_GCS || MODE == PCW_JC;                        // shared-pham counts: no visit
+    constexpr bool SLOTS = MODE == PCW_ENUM || MODE == PCW_AAI || MODE == PCW_PEQ;  // walks the pair's alignment slots
+    __shared__ uint64_t rg[TS][WCH + 1];                    // the tile's genomes g
+    __shared__ uint64_t rq[TS][WCH + 1];                    // the tile's query rows
+    __shared__ unsigned long long red[3];
+    int tile_x, tile_y;
+    if (!pc_tile_of_block((d.N + TS - 1) / TS, (ke - kb + TS - 1) / TS, tile_x, tile_y)) return;
+    const int g0 = tile_x * TS, k0 = kb + tile_y * TS;
+    const int f = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    const int g = g0 + f;
+    const int g_row = g < d.N ? rw.row_of[g] : -1;          // g's own query row, or -1
+    PcPairAcc acc[4];
+    int kk[4], qq[4]; bool ok[4], diag[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        kk[m] = k0 + r0 + 8 * m;
+        const bool in = g < d.N && kk[m] < ke;
+        qq[m] = in ? rw.rows[kk[m]] : 0;
+        diag[m] = in && g == qq[m];
+        ok[m] = in && g != qq[m] && !(g_row >= 0 && g < qq[m]);
+        acc[m].k = 0; acc[m].cons = 0; acc[m].num = 0.0; acc[m].den = 0; acc[m].any = 0;
+        if (ok[m] && SLOTS) acc[m].k = a.off[(int64_t)(kk[m] - kb) * d.N + g];
+    }
+    unsigned long long cells = 0, rbytes = 0;
+    if (MODE == PCW_COUNT) { if (threadIdx.x < 3) red[threadIdx.x] = 0; }
+
+    for (int w0 = 0; w0 < d.Wb; w0 += WCH) {
+        const int wn = min(WCH, d.Wb - w0);
+        if (w0) __syncthreads();
+        pc_stage_tile_rows(d, rw, g0, k0, ke, w0, wn, rg, rq);
+        __syncthreads();
+        uint32_t nz[4] = {0u, 0u, 0u, 0u};
+        for (int i = 0; i < wn; ++i) {
+            const uint64_t common = rg[f][i];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint64_t both = rq[r0 + 8 * m][i] & common;
+                if (SETS) acc[m].k += (uint32_t)__popcll(both);
+                else nz[m] |= (both != 0 ? 1u : 0u) << i;
+            }
+        }
+        if constexpr (!SETS) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (!ok[m]) continue;
+                const bool q_is_source = qq[m] < g;
+                const int s = q_is_source ? qq[m] : g, t = q_is_source ? g : qq[m];
+                const uint32_t* rps = d.rankpre + (int64_t)s * d.Wb + w0;
+                const uint32_t* rpt = d.rankpre + (int64_t)t * d.Wb + w0;
+                uint32_t todo = nz[m];
+                while (todo) {
+                    const int w = __ffs((int)todo) - 1;
+                    todo &= todo - 1;
+                    const uint64_t qw = rq[r0 + 8 * m][w], gw = rg[f][w];
+                    const uint64_t sw = q_is_source ? qw : gw, tw = q_is_source ? gw : qw;
+                    uint64_t x = sw & tw;
+                    const uint32_t bs = rps[w], bt = rpt[w];
+                    while (x) {
+                        const int b = __ffsll((long long)x) - 1;
+                        x &= x - 1;
+                        const uint64_t below = (1ULL << b) - 1;
+                        pc_visit<MODE>(d, a, acc[m], bs + __popcll(sw & below), bt + __popcll(tw & below), cells, rbytes);
+                    }
+                }
+            }
+        }
+    }
+
+    if (MODE == PCW_COUNT) {
+        unsigned long long nal = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t n = ok[m] ? acc[m].k : 0u;
+            if (ok[m] && a.na) a.na[(int64_t)(kk[m] - kb) * d.N + g] = n;
+            nal += n;
+            if (a.aln_t) {                                                // the 32 lanes of a half-wave hold one row's slots: one add per tile and row
+                unsigned long long row_sum = n;
+                for (int o = 16; o > 0; o >>= 1) row_sum += __shfl_down(row_sum, o, 32);
+                if (f == 0 && row_sum && kk[m] < ke) atomicAdd(&a.aln_t[kk[m]], row_sum);
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            nal += __shfl_down(nal, o); cells += __shfl_down(cells, o); rbytes += __shfl_down(rbytes, o);
+        }
+        if ((threadIdx.x & 63) == 0) { atomicAdd(&red[0], nal); atomicAdd(&red[1], cells); atomicAdd(&red[2], rbytes); }
+        __syncthreads();
+        if (threadIdx.x < 3 && red[threadIdx.x]) atomicAdd(&a.totals[threadIdx.x], red[threadIdx.x]);
+        return;
+    }
+    if (MODE == PCW_ENUM) return;
+
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (diag[m]) a.out[(int64_t)kk[m] * d.N + g] = a.as_distance ? 0.0 : 1.0;
+        if (!ok[m]) continue;
+        const int q = qq[m];
+        const int s = q < g ? q : g, t = q < g ? g : q;
+        double v;
+        if (MODE == PCW_GCS) v = pc_set_value<PC_GCS>((int)acc[m].k, d.nph[s] + d.nph[t], a.as_distance);
+        else if (MODE == PCW_JC) v = pc_set_value<PC_JC>((int)acc[m].k, d.nph[s] + d.nph[t], a.as_distance);
+        else if (MODE == PCW_POCP) {
+            const double sim = acc[m].any ? (double)acc[m].cons / (double)(d.ngen[s] + d.ngen[t]) : 0.0;   // metrics.py:104-110
+            v = pc_finish(sim, a.as_distance);
+        } else if (MODE == PCW_AF) {
+            const double sim = acc[m].any ? (double)acc[m].cons / (double)(d.tlen[s] + d.tlen[t]) : 0.0;   // metrics.py:149-152
+            v = pc_finish(sim, a.as_distance);
+        } else {
+            const double aai = acc[m].any ? acc[m].num / (double)acc[m].den : 0.0;                         // metrics.py:227
+            if (MODE == PCW_AAI) v = pc_finish(aai, a.as_distance);
+            else {
+                const double af = acc[m].any ? (double)acc[m].cons / (double)(d.tlen[s] + d.tlen[t]) : 0.0;
+                v = pc_finish(pc_round6(af) * pc_round6(aai), a.as_distance);                              // metrics.py:247-253
+            }
+        }
+        a.out[(int64_t)kk[m] * d.N + g] = v;
+        if (g_row >= 0) a.out[(int64_t)g_row * d.N + q] = v;               // two queries: the mirror cell of the larger one's row
+    }
+}
+
+int pc_launch_walk_rows(int mode, const PcDev& d, const PcRows& rw, int kb, int ke, const PcWalkArgs& a, hipStream_t st) {
+    if (kb < 0 || ke > rw.nrows || kb > ke) { pc_set_error("pc_launch_walk_rows: rows [%d, %d) of %d", kb, ke, rw.nrows); return PC_ERR_ARG; }
+    if (ke == kb || d.N < 1) return PC_OK;
+    dim3 grid(pc_tile_grid((d.N + TS - 1) / TS, (ke - kb + TS - 1) / TS)), block(256);
+    switch (mode) {
+    case PCW_GCS: hipLaunchKernelGGL(k_walk_rows<PCW_GCS>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_JC: hipLaunchKernelGGL(k_walk_rows<PCW_JC>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_POCP: hipLaunchKernelGGL(k_walk_rows<PCW_POCP>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_AF: hipLaunchKernelGGL(k_walk_rows<PCW_AF>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_COUNT: hipLaunchKernelGGL(k_walk_rows<PCW_COUNT>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_ENUM: hipLaunchKernelGGL(k_walk_rows<PCW_ENUM>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_AAI: hipLaunchKernelGGL(k_walk_rows<PCW_AAI>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    case PCW_PEQ: hipLaunchKernelGGL(k_walk_rows<PCW_PEQ>, grid, block, 0, st, d, rw, kb, ke, a); break;
+    default: pc_set_error("pc_launch_walk_rows: bad mode %d", mode); return PC_ERR_ARG;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_walk_rows launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------------------
 // Exclusive prefix sum of u32 (n elements).  2048 elements per workgroup, block sums
 // scanned recursively.  Callers that need the total pass n+1 elements with in[n] = 0.
 // ---------------------------------------------------------------------------------

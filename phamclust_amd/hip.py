@@ -72,7 +72,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
            "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
-           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow"]
+           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -129,6 +129,8 @@ def load():
     L.pc_fill_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_fill_shard_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_assemble_dev.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    L.pc_fill_rows.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _f64p, ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -380,6 +382,29 @@ class Context:
         self._check(self._lib.pc_fill(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(buf, _f64p),
                                       ctypes.byref(stats)))
         return (out, stats.as_dict()) if want_stats else out
+
+    def fill_rows(self, metric, rows, as_distance=True, want_stats=False):
+        """The query genomes ``rows`` (distinct indices, strictly ascending) against every other genome -> an ``(M, N)`` float64
+        array: ``out[k, g]`` is the whole fill's value of the pair {rows[k], g}, ``out[k, rows[k]]`` the diagonal
+        (``1.0 - as_distance``).  New genomes against a filled matrix: what ``matrix.matrix_extend`` calls."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        out = np.empty((rows.shape[0], self.n_genomes), dtype=np.float64)
+        buf = out if out.size else np.zeros(1)
+        self._check(self._lib.pc_fill_rows(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(rows, _i32p), int(rows.shape[0]),
+                                           _ptr(buf, _f64p), ctypes.byref(stats)))
+        return (out, stats.as_dict()) if want_stats else out
+
+    def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        self._check(self._lib.pc_fill_rows_dev(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(rows, _i32p), int(rows.shape[0]),
+                                               ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0), ctypes.byref(stats) if want_stats else None))
+        return stats.as_dict() if want_stats else None
 
     def fill_dev(self, metric, as_distance, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -444,6 +444,119 @@ def _row_adjacency(source, targets, func, distance):
     return [calculate_adjacency(source, target, func, distance) for target in targets]
 
 
+def _pairs_adjacency(pairs, func, distance):
+    """One worker task of matrix_extend's generic path: a run of (source, target) pairs."""
+    return [calculate_adjacency(source, target, func, distance) for source, target in pairs]
+
+
+def _square_matrix(nodes, data, is_distance):
+    """A SymMatrix over ``nodes`` that takes ``data`` (N x N, already rounded, diagonal set) as its storage."""
+    m = SymMatrix.__new__(SymMatrix)
+    m._nodes = list(nodes)
+    m._slot = {name: k for k, name in enumerate(m._nodes)}
+    m._data = data
+    m._is_distance = is_distance
+    m._locked = False
+    return m
+
+
+def matrix_extend(matrix, genomes, func, cpus, verify=4):
+    """New genomes against a filled matrix: the ``SymMatrix`` over all of ``genomes`` (in that order -- the fill order, which
+    is name-sorted in the pipeline) that ``matrix_de_novo(genomes, func, cpus, matrix.is_distance)`` would return, computing
+    only the pairs ``matrix`` lacks.  ``matrix`` holds a subset of the genomes' names; its block is copied, the rows of the
+    genomes it lacks come from ONE rows fill (``Context.fill_rows``: k new genomes cost k N pairs, not N^2 / 2).  The reference
+    has the container half of this (``SymMatrix.append_node``, matrix.py:169-213) and nothing that produces the values.
+
+    ``verify`` old genomes -- spread evenly over the old ones in list order, at most all of them -- are refilled with the new
+    rows, and every refilled value must EQUAL the stored one: the guard against a stale file, another metric, a changed genome
+    or another genome order (pair orientation follows the order, and aai is not symmetric).  A mismatch raises ``ValueError``
+    naming the first differing pair; ``verify=0`` switches the guard off.
+
+    Nothing new: the matrix re-laid in ``genomes`` order.  Every genome new: ``matrix_de_novo``.  An unset (NaN) old cell:
+    ``ValueError``.  A node of ``matrix`` that is no genome: ``KeyError`` (``extract_submatrix`` the shared nodes first).  A
+    callable outside ``METRICS`` is run per new pair on the host (over ``cpus`` joblib workers), the reference's way.  One GPU:
+    with ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` the first listed device; under a launcher (``WORLD_SIZE`` > 1) it raises.
+    """
+    if len(genomes) == 0:
+        raise ValueError("need at least 1 genome to extend a matrix")
+    names = [g.name for g in genomes]
+    index = {name: k for k, name in enumerate(names)}
+    if len(index) != len(names):
+        raise ValueError("genome names must be distinct")
+    stranger = next((node for node in matrix.nodes if node not in index), None)
+    if stranger is not None:
+        raise KeyError(f"node '{stranger}' of the matrix is not among the genomes: extract_submatrix() the nodes they share first")
+    as_distance = matrix.is_distance
+    n = len(names)
+    old_idx = [k for k, name in enumerate(names) if name in matrix]
+    new_idx = [k for k, name in enumerate(names) if name not in matrix]
+    if not old_idx:
+        return matrix_de_novo(genomes, func, cpus, as_distance=as_distance)
+    slots = np.fromiter((matrix._slot[names[k]] for k in old_idx), dtype=np.int64, count=len(old_idx))
+    block = matrix._data[np.ix_(slots, slots)]
+    if np.isnan(block).any():
+        i, j = (int(x) for x in np.argwhere(np.isnan(block))[0])
+        raise ValueError(f"the matrix has an unset cell ({names[old_idx[i]]}, {names[old_idx[j]]}): only a filled matrix can be extended")
+    if not new_idx:
+        return _square_matrix(names, block.copy(), as_distance)
+    old_at = np.asarray(old_idx, dtype=np.int64)
+    full = np.full((n, n), np.nan, dtype=np.float64)
+    full[np.ix_(old_at, old_at)] = block
+    metric = _metric_name(func)
+    if metric is not None:
+        import time
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise RuntimeError("matrix_extend: the rows fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+        devices = in_process_devices()
+        if devices:
+            logging.debug(f"matrix_extend: the rows fill is a one-GPU call: using device {devices[0]} of {devices}")
+        t0 = time.perf_counter()
+        packed = _packed_of(genomes)
+        t1 = time.perf_counter()
+        ctx = get_context(devices[0] if devices else None)
+        ctx.upload(packed, residues=metric in ("aai", "peq"))
+        t2 = time.perf_counter()
+        n_verify = max(0, min(int(verify), len(old_idx)))
+        checked = sorted({old_idx[(i * len(old_idx)) // n_verify] for i in range(n_verify)})
+        rows = sorted(set(new_idx) | set(checked))
+        values, stats = ctx.fill_rows(metric, rows, as_distance=as_distance, want_stats=True)
+        t3 = time.perf_counter()
+        row_at = {q: k for k, q in enumerate(rows)}
+        for q in checked:
+            stored, refilled = full[q, old_at], values[row_at[q], old_at]
+            if not np.array_equal(stored, refilled):
+                g = int(old_at[np.flatnonzero(stored != refilled)[0]])
+                raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the matrix holds {full[q, g]!r}, the {metric} fill gives "
+                                 f"{values[row_at[q], g]!r}: the matrix was not filled with this metric from these genomes in this order")
+        for q in new_idx:
+            full[q, :] = values[row_at[q]]
+            full[:, q] = values[row_at[q]]
+        LAST_FILL.clear()
+        LAST_FILL.update(stats, metric=metric, n_genomes=n, genome_pairs=int(stats["n_pairs"]), rows=len(rows), n_gpus=1, rank=0,
+                         pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
+        logging.debug(f"{len(new_idx)} new of {n} genomes -> {len(rows)} rows, {stats['n_pairs']} edges on one device: pack {t1 - t0:.3f} s, "
+                      f"upload {t2 - t1:.3f} s, fill+D2H {t3 - t2:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+        return _square_matrix(names, full, as_distance)
+
+    # any other callable: the reference's per-pair semantics over the new pairs only, source = the earlier genome of the list
+    result = _square_matrix(names, full, as_distance)
+    is_new = set(new_idx)
+    pairs = [(genomes[min(q, g)], genomes[max(q, g)]) for q in new_idx for g in range(n) if g != q and not (g in is_new and g < q)]
+    for q in new_idx:
+        result.set_weight(names[q], names[q], 1.0 - as_distance)
+    if cpus is None or cpus <= 1 or len(pairs) < 2 * cpus:
+        batches = [_pairs_adjacency(pairs, func, as_distance)]
+    else:
+        import joblib
+        step = max(1, min(2500, (len(pairs) + cpus - 1) // cpus))
+        runner = joblib.Parallel(n_jobs=cpus, return_as="generator_unordered", max_nbytes=None)
+        batches = runner(joblib.delayed(_pairs_adjacency)(pairs[i:i + step], func, as_distance) for i in range(0, len(pairs), step))
+    for edges in batches:
+        for s, t, w in edges:
+            result.set_weight(s, t, w)
+    return result
+
+
 # ---------------------------------------------------------------------------------------
 # TSV I/O: adjacency, squareform, lower triangle (matrix.py:500-670); "%.6f" everywhere
 # ---------------------------------------------------------------------------------------

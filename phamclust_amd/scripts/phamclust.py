@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import matrix_de_novo, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
+from phamclust_amd.matrix import matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -110,6 +110,7 @@ class _Run:
         self.outdir, self.metric, self.colors, self.midpoint = outdir, metric, colors, midpoint
         self.genomes, self.by_name, self.cache, self.stage = [], {}, None, None
         self.rank, self.world = 0, 1          # this process's place in the job (one process per GPU)
+        self.extend = None                    # --extend FILE: a distance matrix over a subset of the genomes
 
     @staticmethod
     def _dir(path, fresh=False):
@@ -167,6 +168,9 @@ class _Run:
                 return None
             matrix = matrix_from_squareform(cached)
             log.info(f"read cached matrix in {time.perf_counter() - t0:.3f} s")
+        elif self.extend is not None:
+            matrix = self.extended(cpus, t0)
+            matrix_to_squareform(matrix, cached, lower_triangle=True)
         else:
             matrix = matrix_de_novo(self.genomes, METRICS[self.metric], cpus)
             if matrix is None:                # not rank 0: this rank's shard went into the gather, nothing else to do
@@ -203,6 +207,26 @@ class _Run:
             log.error(f"matrix failed integrity checks: edge count off by {edges}, diagonal off by {diagonal}, {unfilled} unfilled")
             print("matrix validation failed - check log for details")
             sys.exit(1)
+        return matrix
+
+    def extended(self, cpus, t0):
+        """Stage 2 under --extend: the old matrix's block is kept, the rows of the genomes it lacks are filled (matrix_extend)."""
+        try:
+            old = matrix_from_squareform(self.extend)
+            if not old.is_distance:
+                raise ValueError(f"'{self.extend}' holds similarities; --extend takes the distance matrix a run wrote (02_distmats/)")
+            matrix = matrix_extend(old, self.genomes, METRICS[self.metric], cpus)
+        except (ValueError, KeyError, OSError) as exc:
+            log.error(f"--extend {self.extend}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
+            print("matrix extension failed - check log for details")
+            sys.exit(1)
+        st, n = _matrix.LAST_FILL, len(matrix)
+        added = n - len(old)
+        filled = st.get("genome_pairs", added * (n - 1) - added * (added - 1) // 2) if added else 0
+        log.info(f"extended {len(old):,} -> {n:,} genomes: {st.get('rows', added) if added else 0:,} rows, {filled:,} pairs filled instead of "
+                 f"{n * (n - 1) // 2:,} in {time.perf_counter() - t0:.3f} s")
+        if added and self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
         return matrix
 
     # 3
@@ -267,17 +291,21 @@ class _Run:
 
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
-              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug):
-    """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds)."""
+              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None):
+    """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
+    distance matrix of an earlier run over a subset of the genomes (``--extend``), or None."""
     if nr_distance >= clu_distance:          # pre-grouping must be tighter than clustering, else switch it off
         nr_distance = 0.0
     settings = dict(infile=infile, outdir=outdir, metric=metric, nr=(nr_distance, nr_linkage), clu=(clu_distance, clu_linkage),
                     sub=(sub_distance, sub_linkage), k_min=k_min, subcluster=not no_sub, colors=",".join(colors),
                     midpoint=midpoint, cpus=cpus, remove_tmp=rm_tmp, debug=debug)
+    if extend is not None:
+        settings["extend"] = extend
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
     run = _Run(outdir, metric, colors, midpoint)
+    run.extend = extend
     run.rank, run.world = distributed.ensure_process_group()      # (0, 1) unless started by torch.distributed.run
     _mark("torch_import_and_process_group")
     run.read(infile, is_genome_dir)
@@ -340,7 +368,11 @@ def main(argv=None):
 def _run(args, argv):
     rank, _, world = distributed.env_world()
     gpus_note = None
-    if args.gpus > 1 and world == 1:
+    if args.gpus > 1 and world == 1 and args.extend is not None:
+        # the rows fill of --extend is a one-GPU call (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
+        gpus_note = "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
+        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
+    elif args.gpus > 1 and world == 1:
         # `--gpus N`.  Two routes (startup.multi_gpu_route): by default THIS process drives the N GPUs (pc_multi_*: nothing to
         # launch); PHAMCLUST_MULTI=launcher re-runs the command as N ranks under torch.distributed.run, which costs seconds
         # before the first pair (an interpreter, a torch import and a process group per rank).  Either way the reference's rule
@@ -387,7 +419,7 @@ def _run(args, argv):
                   clu_distance=as_distance(args.clu_thresh), clu_linkage=args.clu_linkage,
                   sub_distance=as_distance(args.sub_thresh), sub_linkage=args.sub_linkage, k_min=max(1, args.k_min),
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
-                  cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug)
+                  cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
