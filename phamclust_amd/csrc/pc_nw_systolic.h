@@ -140,12 +140,74 @@ __device__ __forceinline__ double pc_retag_from(double v) {
     else return pc_retag(v, (uint32_t)TO);
 }
 
+// ---- issue policy (r06: profiles/r06/experiments/valu2_priority_ab.txt) -----------------------------------------
+// The cell's four plain VOP2 instructions (the two re-tags; v_and + v_sub that make Ho) go to the second VALU pipe only as the
+// partner of ANOTHER wave's plain VOP2 instruction in the same issue slot, and wave priority is the one handle a
+// kernel has on the issue arbiter.  A policy brackets those instructions with s_setprio (scalar: no VALU instruction is added):
+//   BATCH      priority 1 by default, 0 across each of the two cheap pairs: a wave at its cheap instructions yields to waves on
+//              four-clock work, so that cheap-ready waves collect and issue together;
+//   BATCH_ONE  the same with ONE window per cell: from the first re-tag to v_sub, H's two maxima inside it;
+//   EAGER      the mirror image of BATCH (priority 1 only across the cheap pairs): the control arm;
+//   NONE       no s_setprio anywhere: the device code of r05, byte for byte.
+// Measured (N = 5,000 fill, alignment stage, every family on the one policy): BATCH -8.3 %, BATCH_ONE -7.3 %, EAGER +10 %; share
+// of the executed VALU instructions that retire on the second pipe 0.105 -> 0.221, 0.197, 0.034; executed instructions unchanged.
+// BATCH pays where several waves share a SIMD -- every tier width, +2 ... +19 % kernel rate -- and costs where one or two do: the
+// wide variants (-3 ... -20 %) and both strip forms (four-wave -20 %, pipelined -15 %), whose lone waves have nobody to pair with and issue
+// the four s_setprio per cell in their own time.  So the policy is per kernel family; a compile-time argument of pc_cell64 / PcRow /
+// pc_nw_body (k_nw_strip: a constant, so that no kernel's name changes), and only the defaults below are ever instantiated.
+#define PC_POL_NONE 0
+#define PC_POL_BATCH 1
+#define PC_POL_EAGER 2
+#define PC_POL_BATCH_ONE 3
+#ifndef PC_ISSUE_POLICY
+#define PC_ISSUE_POLICY PC_POL_BATCH                       // pc_nw_body, the widths of the tier kernels (W <= 24: pc_tier_of)
+#endif
+#ifndef PC_WIDE_ISSUE_POLICY
+#define PC_WIDE_ISSUE_POLICY PC_POL_NONE                   // pc_nw_body, W = 32, 48, 64
+#endif
+#ifndef PC_STRIP_ISSUE_POLICY
+#define PC_STRIP_ISSUE_POLICY PC_POL_NONE                  // both forms of k_nw_strip
+#endif
+__host__ __device__ constexpr int pc_issue_policy(int W) { return W <= 24 ? PC_ISSUE_POLICY : PC_WIDE_ISSUE_POLICY; }
+// Start phase: waves that begin a task together run in lockstep, the arrangement that pairs nothing (tests/hw/valu_mix.hip).
+// 1: odd waves of a workgroup sleep 64 clocks once before the step loop; 2: the same for every other wave of a SIMD (waves w and
+// w + 4 of a workgroup share one, and so do the waves of neighbouring workgroups).  One scalar branch per task, no VALU instruction.
+// Measured: no gain (+0.2 ... +0.5 % of the fill's time either way) -- the waves of a SIMD drift apart within a few steps on their own.
+#ifndef PC_START_PHASE
+#define PC_START_PHASE 0
+#endif
+template <int PRIO>
+__device__ __forceinline__ void pc_setprio(double& x) {                   // s_setprio after whatever writes x, before whatever reads it
+    if constexpr (PRIO) asm volatile("s_setprio 1" : "+v"(x)); else asm volatile("s_setprio 0" : "+v"(x));
+}
+// ... and inside the cell's asm blocks, as their first / last instruction (a statement of its own costs one more `s_nop 0`: the compiler
+// pads between any two asm statements that share a register).  M(PRE, POST, ...) is the block; FIRST: the row's first cell, which
+// the step's prologue reaches at the outer priority already.
+#define PC_PRIO_PRE(n) "s_setprio " #n "\n\t"
+#define PC_PRIO_POST(n) "\n\ts_setprio " #n
+#define PC_POL_BLOCK1(M, ...)                                                                                          \
+    do {                                                                                                               \
+        if constexpr (POL == PC_POL_NONE) M("", "", __VA_ARGS__);                                                      \
+        else if constexpr (POL == PC_POL_EAGER) { if constexpr (FIRST) M("", PC_PRIO_POST(1), __VA_ARGS__); else M(PC_PRIO_PRE(0), PC_PRIO_POST(1), __VA_ARGS__); } \
+        else { if constexpr (FIRST) M("", PC_PRIO_POST(0), __VA_ARGS__); else M(PC_PRIO_PRE(1), PC_PRIO_POST(0), __VA_ARGS__); }                                    \
+    } while (0)
+#define PC_POL_BLOCK2(M)                                                                                               \
+    do {                                                                                                               \
+        if constexpr (POL == PC_POL_BATCH) M(PC_PRIO_PRE(1), PC_PRIO_POST(0));                                         \
+        else if constexpr (POL == PC_POL_EAGER) M(PC_PRIO_PRE(0), PC_PRIO_POST(1));                                    \
+        else M("", "");                                                                                                \
+    } while (0)
+__device__ __forceinline__ void pc_start_phase(int wv, uint32_t task) {   // wv, task: wave-uniform (scalar registers)
+    if constexpr (PC_START_PHASE == 1) { if (wv & 1) __builtin_amdgcn_s_sleep(1); }
+    else if constexpr (PC_START_PHASE == 2) { if (((uint32_t)(wv >> 2) ^ task) & 1u) __builtin_amdgcn_s_sleep(1); }
+}
+
 // One cell.  In: D (this cell's diagonal candidate, tag 3), chain values HoL [tag tOF] and EL [tE], row code ac.
 // In/out (in place): column state Hou -> Ho, Fu -> F.  Out: E (chain), and for the next cell Dn = old Hou + score of the
 // next cell (+ 3 - tOF, folded into the profile byte) with statistics old Hou's + 0x10000 + (ac == bcn).
 // The first block is asm because of its SDWA forms and because v_cmp's SGPR result must not be read by v_addc sooner than
 // two instructions later (gfx950; nothing pads inside asm): the two independent v_max_f64 sit in between.
-template <int NEXT_COL, int RULE, bool INC16>
+template <int NEXT_COL, int RULE, bool INC16, int POL = PC_POL_NONE>
 __device__ __forceinline__ void pc_cell64(double D, double HoL, double EL, double& Hou, double& Fu, double& E, double& Dn,
                                           uint32_t ac, uint32_t bcn, uint32_t pwn, uint32_t pmn, uint32_t K) {
     using T = PcTag<RULE>;
@@ -153,44 +215,52 @@ __device__ __forceinline__ void pc_cell64(double D, double HoL, double EL, doubl
     if constexpr (T::cyclic) HoL = pc_pack(pc_hi(HoL) + (uint32_t)(T::tOE - T::tOF), pc_lo(HoL));
     const uint32_t ohi = pc_hi(Hou), olo = pc_lo(Hou);
     uint32_t dn_hi = 0, dn_lo = 0;
+    constexpr bool FIRST = NEXT_COL == 1;            // column 0 (every variant has at least two columns per lane)
     if constexpr (NEXT_COL < 0) {
-        asm("v_max_f64 %[E], %[HoL], %[EL]\n\tv_max_f64 %[Fu], %[Hou], %[Fu]" : [E] "=&v"(E), [Fu] "+v"(Fu) : [HoL] "v"(HoL), [EL] "v"(EL), [Hou] "v"(Hou));
+#define PC_CELL64_L(PRE, POST, X)                                                                                      \
+    asm(PRE "v_max_f64 %[E], %[HoL], %[EL]\n\tv_max_f64 %[Fu], %[Hou], %[Fu]" POST : [E] "=&v"(E), [Fu] "+v"(Fu) : [HoL] "v"(HoL), [EL] "v"(EL), [Hou] "v"(Hou))
+        PC_POL_BLOCK1(PC_CELL64_L, 0);
+#undef PC_CELL64_L
     } else if constexpr (INC16) {
         // the statistics' increment comes from the profile too: a 16-bit entry 0x2000 + (row residue == column residue)
-#define PC_CELL64_B(SEL, WSEL)                                                                                         \
-    asm("v_max_f64 %[E], %[HoL], %[EL]\n\t"                                                                            \
+#define PC_CELL64_B(PRE, POST, SEL, WSEL)                                                                              \
+    asm(PRE "v_max_f64 %[E], %[HoL], %[EL]\n\t"                                                                        \
         "v_max_f64 %[Fu], %[Hou], %[Fu]\n\t"                                                                           \
         "v_add_u32_sdwa %[dh], %[pwn], %[ohi] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" SEL " src1_sel:DWORD\n\t" \
-        "v_add_u32_sdwa %[dl], %[pmn], %[olo] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" WSEL " src1_sel:DWORD"    \
+        "v_add_u32_sdwa %[dl], %[pmn], %[olo] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" WSEL " src1_sel:DWORD" POST \
         : [E] "=&v"(E), [Fu] "+v"(Fu), [dh] "=&v"(dn_hi), [dl] "=&v"(dn_lo)                                            \
         : [HoL] "v"(HoL), [EL] "v"(EL), [Hou] "v"(Hou), [ohi] "v"(ohi), [olo] "v"(olo), [pwn] "v"(pwn), [pmn] "v"(pmn))
-        if constexpr (NEXT_BYTE == 0) PC_CELL64_B("BYTE_0", "WORD_0");
-        else if constexpr (NEXT_BYTE == 1) PC_CELL64_B("BYTE_1", "WORD_1");
-        else if constexpr (NEXT_BYTE == 2) PC_CELL64_B("BYTE_2", "WORD_0");
-        else PC_CELL64_B("BYTE_3", "WORD_1");
+        if constexpr (NEXT_BYTE == 0) PC_POL_BLOCK1(PC_CELL64_B, "BYTE_0", "WORD_0");
+        else if constexpr (NEXT_BYTE == 1) PC_POL_BLOCK1(PC_CELL64_B, "BYTE_1", "WORD_1");
+        else if constexpr (NEXT_BYTE == 2) PC_POL_BLOCK1(PC_CELL64_B, "BYTE_2", "WORD_0");
+        else PC_POL_BLOCK1(PC_CELL64_B, "BYTE_3", "WORD_1");
 #undef PC_CELL64_B
     } else {
         unsigned long long c2;
-#define PC_CELL64_A(SEL)                                                                                               \
-    asm("v_cmp_eq_u32_sdwa %[c2], %[ac], %[bcn] src0_sel:BYTE_0 src1_sel:" SEL "\n\t"                                  \
+#define PC_CELL64_A(PRE, POST, SEL)                                                                                    \
+    asm(PRE "v_cmp_eq_u32_sdwa %[c2], %[ac], %[bcn] src0_sel:BYTE_0 src1_sel:" SEL "\n\t"                              \
         "v_max_f64 %[E], %[HoL], %[EL]\n\t"                                                                            \
         "v_max_f64 %[Fu], %[Hou], %[Fu]\n\t"                                                                           \
         "v_add_u32_sdwa %[dh], %[pwn], %[ohi] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" SEL " src1_sel:DWORD\n\t" \
-        "v_addc_co_u32 %[dl], %[c2], %[K], %[olo], %[c2]"                                                              \
+        "v_addc_co_u32 %[dl], %[c2], %[K], %[olo], %[c2]" POST                                                         \
         : [E] "=&v"(E), [Fu] "+v"(Fu), [dh] "=&v"(dn_hi), [dl] "=&v"(dn_lo), [c2] "=&s"(c2)                            \
         : [HoL] "v"(HoL), [EL] "v"(EL), [Hou] "v"(Hou), [ohi] "v"(ohi), [olo] "v"(olo), [ac] "v"(ac), [bcn] "v"(bcn),  \
           [pwn] "v"(pwn), [K] "v"(K))
-        if constexpr (NEXT_BYTE == 0) PC_CELL64_A("BYTE_0");
-        else if constexpr (NEXT_BYTE == 1) PC_CELL64_A("BYTE_1");
-        else if constexpr (NEXT_BYTE == 2) PC_CELL64_A("BYTE_2");
-        else PC_CELL64_A("BYTE_3");
+        if constexpr (NEXT_BYTE == 0) PC_POL_BLOCK1(PC_CELL64_A, "BYTE_0");
+        else if constexpr (NEXT_BYTE == 1) PC_POL_BLOCK1(PC_CELL64_A, "BYTE_1");
+        else if constexpr (NEXT_BYTE == 2) PC_POL_BLOCK1(PC_CELL64_A, "BYTE_2");
+        else PC_POL_BLOCK1(PC_CELL64_A, "BYTE_3");
 #undef PC_CELL64_A
     }
     E = pc_retag_from<T::tOE, T::tE>(E);             // E came from HoL [tOE] or EL [tE]
     Fu = pc_retag_from<T::tOF, T::tF>(Fu);           // F from Hou [tOF] or Fu [tF]
     double H;
-    asm("v_max_f64 %0, %1, %2\n\tv_max_f64 %0, %0, %3" : "=&v"(H) : "v"(D), "v"(Fu), "v"(E));
+#define PC_CELL64_H(PRE, POST) asm(PRE "v_max_f64 %0, %1, %2\n\tv_max_f64 %0, %0, %3" POST : "=&v"(H) : "v"(D), "v"(Fu), "v"(E))
+    PC_POL_BLOCK2(PC_CELL64_H);
+#undef PC_CELL64_H
     Hou = pc_pack((pc_hi(H) & ~3u) + (uint32_t)(T::tOF - 40), pc_lo(H));
+    // back to the outer priority: the next cell's first block does it; behind the row's last cell, a statement of its own
+    if constexpr (POL != PC_POL_NONE && NEXT_COL < 0) pc_setprio<POL == PC_POL_EAGER ? 0 : 1>(Hou);
     Dn = pc_pack(dn_hi, dn_lo);
 }
 
@@ -207,7 +277,7 @@ __host__ __device__ constexpr int pc_prof_row_dwords(int W, bool inc16) {   // s
     return (W + 3) / 4 + (inc16 ? (W + 1) / 2 : 0);
 }
 
-template <int W, int C, int RULE, bool INC16>
+template <int W, int C, int RULE, bool INC16, int POL = PC_POL_NONE>
 struct PcRow {          // compile-time unrolled sweep over the lane's W columns
     static constexpr int NDM = INC16 ? (W + 1) / 2 : 1;
     static constexpr int ND = (W + 3) / 4;
@@ -219,14 +289,14 @@ struct PcRow {          // compile-time unrolled sweep over the lane's W columns
                                                pc_lds_u32* nxt, uint32_t ac, uint32_t K, double& E_out) {
         double E, Dn;
         constexpr int N = (C + 1 < W) ? C + 1 : -1;                      // the column whose diagonal term this cell prepares
-        pc_cell64<N, RULE, INC16>(D, HoL, EL, Hou[C], Fu[C], E, Dn, ac, bc[N < 0 ? 0 : (N >> 2)], pw[N < 0 ? 0 : (N >> 2)], pm[(N < 0 || !INC16) ? 0 : (N >> 1)], K);
+        pc_cell64<N, RULE, INC16, POL>(D, HoL, EL, Hou[C], Fu[C], E, Dn, ac, bc[N < 0 ? 0 : (N >> 2)], pw[N < 0 ? 0 : (N >> 2)], pm[(N < 0 || !INC16) ? 0 : (N >> 1)], K);
         if constexpr (N >= 0 && (((N & 1) && INC16) || (N & 3) == 3 || N == W - 1)) {
             __builtin_amdgcn_sched_barrier(0);           // load here, into registers that have just died: hoisted, the loads cost a register each
             if constexpr ((N & 3) == 3 || N == W - 1) pw[N >> 2] = nxt[(N >> 2) * 64];
             if constexpr (INC16) pm[N >> 1] = nxt[(ND + (N >> 1)) * 64];
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (C + 1 < W) PcRow<W, C + 1, RULE, INC16>::run(Dn, Hou[C], E, Hou, Fu, bc, pw, pm, nxt, ac, K, E_out);
+        if constexpr (C + 1 < W) PcRow<W, C + 1, RULE, INC16, POL>::run(Dn, Hou[C], E, Hou, Fu, bc, pw, pm, nxt, ac, K, E_out);
         else E_out = E;
     }
 };
@@ -269,7 +339,7 @@ typedef __attribute__((address_space(3))) const pc_u32x4 pc_lds_u32x4;
 
 // The kernel's body for one workgroup task (a device function: the wide variants get a kernel of their own, the others are
 // bundled by register tier into k_nw_systolic_tier below, which picks the body by the task's launch segment).
-template <int W, int RULE, bool INC16>
+template <int W, int RULE, bool INC16, int POL = pc_issue_policy(W)>
 __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restrict__ tasks, const uint32_t task_index,
                                            const int32_t* __restrict__ bucket_row, const uint32_t* __restrict__ bucket_dest,
                                            uint2* __restrict__ res, const int ppos) {
@@ -548,7 +618,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
         }
         const double HoL = pc_pack(HoL_hi, HoL_lo);
         p_HoL = HoL;
-        PcRow<W, 0, RULE, INC16>::run(pc_pack(D0_hi, D0_lo), HoL, pc_pack(EL_hi, EL_lo), Hou, Fu, bc, pw, pm, nxt, a, K, o_E);
+        PcRow<W, 0, RULE, INC16, POL>::run(pc_pack(D0_hi, D0_lo), HoL, pc_pack(EL_hi, EL_lo), Hou, Fu, bc, pw, pm, nxt, a, K, o_E);
         asm volatile("" : "+s"(lastm));                                   // test here, not 140 instructions earlier (the compiler would carry the result as a lane mask: one VALU compare)
         if (lastm != 0) {                                                 // a row's last cell left the lane holding column lb-1
             asm volatile("" ::: "memory");                                // keep this wave-uniform (scalar) test a branch of its own
@@ -562,6 +632,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
     };
     // two steps per iteration with the two stream-entry registers swapping roles: no copies.  An odd T runs one
     // extra step past the end of every stream (idle entries: no flags, no output).
+    pc_start_phase(wv, task_index);
     uint32_t a2 = 0;
 #pragma unroll 1
     for (int t = 0; t < T; t += 2) {
@@ -871,7 +942,7 @@ __global__ __launch_bounds__(64 * (PIPE ? PC_PIPE_WAVES_MAX : PC_STRIP_WAVES), (
                 }
                 const double HoL = pc_pack(HoL_hi, HoL_lo);
                 p_HoL = HoL;
-                PcRow<W, 0, RULE, INC16>::run(pc_pack(D0_hi, D0_lo), HoL, pc_pack(EL_hi, EL_lo), Hou, Fu, bc, pw, pm, nxt, a, K, o_E);
+                PcRow<W, 0, RULE, INC16, PC_STRIP_ISSUE_POLICY>::run(pc_pack(D0_hi, D0_lo), HoL, pc_pack(EL_hi, EL_lo), Hou, Fu, bc, pw, pm, nxt, a, K, o_E);
                 if (!last_pass) {                                   // what lane 64 would have received for this row: the next pass's boundary
                     const int p = t - 63;
                     if (lane == 63 && p >= 0 && p < seg_len)
@@ -887,6 +958,7 @@ __global__ __launch_bounds__(64 * (PIPE ? PC_PIPE_WAVES_MAX : PC_STRIP_WAVES), (
                     }
                 }
             };
+            if constexpr (!PIPE) pc_start_phase(wv, (uint32_t)unit);        // (PIPE: the waves of a row start 64 steps apart as it is)
             uint32_t a2 = 0;
 #pragma unroll 1
             for (int t = 0; t < T; t += 2) {
