@@ -21,11 +21,16 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # tools/build_variant.py adds -ffinite-math-only to these units for the builds that use __builtin_fmax on the cell's 64-bit words
 # (PC_MAX_BUILTIN / PC_CELL_ORDER: experiment switches of pc_nw_systolic.h); the product build uses asm maxima and needs no flag.
 NW_FLAGS = []
-# The host side of the C-ABI is five units (pc_ctx, pc_upload, pc_align, pc_fill, pc_multi; internal header pc_host.h): they hold
-# no device code, so the library's .hip_fatbin comes from the kernel units alone.
+# The host side of the C-ABI is five units (pc_ctx, pc_upload, pc_align, pc_fill, pc_multi; internal header pc_host.h), and
+# pc_set_shape is the host arithmetic of the set-metric launch shapes: they hold no device code, so the library's .hip_fatbin comes
+# from the kernel units alone.  Those are, by family (internal header pc_pairs.h): pc_set_popc (popcount tiles), pc_sparse (sparse
+# tiles and their entry lists), pc_sparse_col (the column kernel), pc_walk (the shared-pham walker over both pair domains), pc_util
+# (scan, gather, shard assembly, test probes); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
 HIP_UNITS = [("pc_ctx.hip", "pc_ctx.o", []), ("pc_upload.hip", "pc_upload.o", []), ("pc_align.hip", "pc_align.o", []),
              ("pc_fill.hip", "pc_fill.o", []), ("pc_multi.hip", "pc_multi.o", []),
-             ("pc_pairs.hip", "pc_pairs.o", []), ("pc_plan.hip", "pc_plan.o", []),
+             ("pc_set_popc.hip", "pc_set_popc.o", []), ("pc_sparse.hip", "pc_sparse.o", []), ("pc_sparse_col.hip", "pc_sparse_col.o", []),
+             ("pc_set_shape.hip", "pc_set_shape.o", []), ("pc_walk.hip", "pc_walk.o", []), ("pc_util.hip", "pc_util.o", []),
+             ("pc_plan.hip", "pc_plan.o", []),
              ("pc_nw.hip", "pc_nw.o", NW_FLAGS),
              ("pc_nw_rules.hip", "pc_nw_r23.o", NW_FLAGS + ["-DPC_RULE_A=2", "-DPC_RULE_B=3"]),
              ("pc_nw_rules.hip", "pc_nw_r45.o", NW_FLAGS + ["-DPC_RULE_A=4", "-DPC_RULE_B=5"]),
@@ -52,10 +57,15 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+def hip_headers():
+    """The headers whose change makes every HIP object stale: each csrc/*.h and the public C-ABI header."""
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
+        [os.path.join(CSRC, "..", "..", "include", "phamclust_hip.h")]
+
+
 def build_hip(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "pc_common.h"), os.path.join(CSRC, "pc_nw_systolic.h"), os.path.join(CSRC, "pc_host.h"),
-               os.path.join(CSRC, "..", "..", "include", "phamclust_hip.h")]
+    headers = hip_headers()
     objs, jobs = [], []
     for src, obj_name, extra in HIP_UNITS + [HOOKS_UNIT]:
         src_path = os.path.join(CSRC, src)

@@ -83,7 +83,7 @@ struct PcTaskPlan {
     int32_t variant_w[32];            // columns per lane of variant v
 };
 
-// walker modes (pc_pairs.hip)
+// walker modes (pc_walk.hip)
 enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5,
        PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows only (whole fills count gcs / jc on the tile kernels)
 enum { PCW_SPARSE_GCS = 10, PCW_SPARSE_JC = 11 };   // k_sparse_tile64 only: shared-pham counts, one direction
@@ -118,7 +118,7 @@ void pc_set_error(const char* fmt, ...);
     } while (0)
 
 // The set metrics' kernel families (pc_set_family of the C-ABI; pc_last_set_kernel) and their launch shapes.  pc_set_shape_of is the one
-// statement of every launcher's arithmetic (pc_pairs.hip): tile and super-tile edge, grid, units per workgroup, mask chunks, instance,
+// statement of every launcher's arithmetic (pc_set_shape.hip): tile and super-tile edge, grid, units per workgroup, mask chunks, instance,
 // seg / runs, LDS, epilogue table.  It reads nothing but its arguments; the launchers pass it the knobs they read from the environment.
 enum { K_POPC, K_SPARSE32, K_SPARSE64, K_WALKER, K_SPARSE_COL };
 struct pc_set_shape;
@@ -129,7 +129,8 @@ void pc_set_shape_of(int family, int metric, int N, int nown, int Wb, int sp_W, 
 // dimensions of the popcount tiles' epilogue table; false: too large (4 Mi entries), the division runs in place
 bool pc_set_table_dims(int metric, int top, int* sh_dim, int* tot_dim);
 
-// launchers (defined next to their kernels); shape_out: NULL or where the shape they launched with is left
+// launchers (defined next to their kernels: pc_set_popc.hip, pc_walk.hip, pc_sparse.hip, pc_sparse_col.hip, pc_util.hip); shape_out: NULL or
+// where the shape they launched with is left
 int pc_launch_set_popc(const PcDev& d, const PcShard& sh, int metric, int as_distance, double* out, int condensed,
                        double* lut, bool build_lut, int top, hipStream_t st, pc_set_shape* shape_out = nullptr);
 int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st, pc_set_shape* shape_out = nullptr);

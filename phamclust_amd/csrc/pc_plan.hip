@@ -1,6 +1,6 @@
 // pc_plan.hip -- planning of one fill's alignment batch (aai / peq).
 //
-// The pair walk (pc_pairs.hip, mode ENUM) writes one 64-bit key per alignment the reference would run
+// The pair walk (pc_walk.hip, mode ENUM) writes one 64-bit key per alignment the reference would run
 // (metrics.py:211-217): (rank of the column sequence << ubits) | rank of the row sequence, ranks taken over the
 // DISTINCT gene sequences of the upload in launch-class order.  A radix sort of (key, slot) then does three jobs
 // at once:

@@ -10,7 +10,7 @@ genomes; `count` recounts alignments, cells and buckets from the packed arrays a
 Layout of the collection: source genomes (names sort first) and target genomes (names sort last).  A case of ``rows`` rows is
 ``rows`` phams, each held by its target (the SAME gene sequence of ``lb`` residues every time) and by exactly one source (a
 distinct short gene).  Both hold one gene of the pham, so the later genome's gene -- the target's -- is the column
-(pc_pairs.hip, pc_visit) and the column sequence's bucket is the case's distinct rows.  No two sources and no two targets
+(pc_walk.hip, pc_visit) and the column sequence's bucket is the case's distinct rows.  No two sources and no two targets
 share a case's pham: a bucket of n rows costs n alignments, not n^2 / 2.
 """
 

@@ -241,7 +241,7 @@ PPOS_GENERAL = (8192, 9000)
 def _ppos_collection(rng, lengths, row_len):
     """Genome "a" holds one row gene per length, genome "b<L>" the column gene of L residues in the same pham: every pair
     (a, b<L>) is ONE alignment, and its column is b<L>'s gene -- each genome holds one gene of the pham, so the anchor (the
-    genome with fewer genes, tie -> the source, metrics.py:208-209; pc_pairs.hip pc_visit) is the source "a", whose gene is
+    genome with fewer genes, tie -> the source, metrics.py:208-209; pc_walk.hip pc_visit) is the source "a", whose gene is
     the row (pc_plan.hip: the column sequence is the other side of the key).  The b genomes share no pham with each other,
     except the identical / mutated 8,191-residue pair (both columns at most 8,191)."""
     from phamclust_amd.genome import Genome

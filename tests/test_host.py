@@ -393,7 +393,7 @@ def test_planner_collection_reaches_every_launch_class(native_built):
     assert all(1 <= lb <= 65535 and 1 <= rows <= pc.MAX_ROWS for lb, rows, _ in cases)
 
 
-# ---- the set-metric selector and its launch shapes (host arithmetic of pc_fill.hip / pc_pairs.hip) -----------------------
+# ---- the set-metric selector and its launch shapes (host arithmetic of pc_fill.hip / pc_set_shape.hip) -----------------------
 def _choice_base(**over):
     """synth(N, 5000)'s profile: 79 bitmap words, 5,000 phams with two holders (5,056 mask entries), 2.85 phams shared per pair;
     blocks of 6,500 entries against the value table's 7,231 at that mask count."""
@@ -518,7 +518,7 @@ def test_set_block_entries_counts_the_ragged_block(native_built):
 
 
 def test_set_launch_shape_pins(native_built):
-    """pc_set_launch_shape on both sides of every threshold inside the five launchers, by hand from pc_pairs.hip (256 compute units)."""
+    """pc_set_launch_shape on both sides of every threshold inside the five launchers, by hand from pc_set_shape.hip (256 compute units)."""
     from phamclust_amd import hip
     C = hip.Context
 
@@ -753,6 +753,19 @@ def test_product_never_imports_the_oracle():
             if f.endswith((".py", ".hip", ".h", ".c")):
                 text = open(os.path.join(root, f)).read()
                 assert "import oracle" not in text and "from oracle" not in text and "pc_oracle" not in text, f
+
+
+def test_build_knows_every_unit_and_header():
+    """The build's lists follow the sources: every csrc/*.hip is a unit of the HIP library (build.HIP_UNITS), and every csrc/*.h,
+    with the public C-ABI header, is among the headers whose change makes an object stale."""
+    from phamclust_amd import build
+    on_disk = sorted(os.listdir(build.CSRC))
+    units = {src for src, _, _ in build.HIP_UNITS}
+    assert [f for f in on_disk if f.endswith(".hip") and f not in units] == []
+    assert [u for u in units if u not in on_disk] == []
+    stale_on = {os.path.realpath(h) for h in build.hip_headers()}
+    assert [f for f in on_disk if f.endswith(".h") and os.path.realpath(os.path.join(build.CSRC, f)) not in stale_on] == []
+    assert os.path.realpath(os.path.join(REPO, "include", "phamclust_hip.h")) in stale_on
 
 
 def test_graft_entry_build(native_built):
