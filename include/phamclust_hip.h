@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 155   /* 0.5.4: pc_fill_rows, pc_fill_rows_dev */
+#define PC_VERSION 156   /* 0.5.5: pc_fill_edges */
 
 typedef enum {
     PC_OK = 0,
@@ -191,6 +191,35 @@ int pc_fill_shard_dev(pc_ctx* ctx, int metric, int as_distance, void* shard_dev,
  */
 int pc_fill_rows(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, double* out_host, pc_stats* stats);
 int pc_fill_rows_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, void* out_dev, void* stream, pc_stats* stats);
+
+/*
+ * Edge-list fill: the pairs within a threshold, without the dense matrix.  The reference knows this form of its result twice --
+ * matrix_to_adjacency(dist_mat, skip_zero=True) writes it as the pipeline's final file (matrix.py:536-551, scripts/phamclust.py:462-464)
+ * and SymMatrix.nearest_neighbors(source, threshold) queries it per node (matrix.py:265-296) -- and derives it from the dense
+ * matrix both times.  This call delivers the pairs (s, t), s < t, whose value passes the predicate -- value <= threshold for a
+ * distance fill (as_distance != 0), value >= threshold for a similarity fill; a plain f64 compare on the delivered, already
+ * round(x, 6) value -- as three parallel arrays src[E], tgt[E], val[E], SORTED BY t, THEN s, in page-locked memory the context
+ * owns: valid until the next fill or upload on this context or its destruction (pc_fill_borrow's loan rule).  Values are the
+ * whole fill's, bit for bit.  The six metrics and PC_AAI_PPOS.
+ * The dense matrix never crosses PCIe and need not fit in HBM: the call fills and compacts successive contiguous ranges of
+ * target genomes ("slabs"), one resident at a time, cut by the chunking rule -- pc_chunk_plan over count[t] = t with
+ * max_per_chunk = slab_bytes / 8, clamped to 2^31-1 pairs.  slab_bytes = 0: the smallest of the dense triangle, a quarter of the
+ * HBM free at the call (the plan of an aai / peq slab takes its own half, pc_set_plan_budget) and the 2^31-1 pair cap.  Each slab
+ * is filled as a shard of its targets (every kernel family takes one; same values), then count -> scan -> one 4-byte read-back ->
+ * emit -> a copy of exactly that slab's edges.  Consequences: aai / peq merge duplicate sequence pairs per slab only, as a pair
+ * shard does per rank; pc_last_set_kernel, pc_last_set_launch and pc_last_plan_tasks describe the LAST slab's fill.  The caller's
+ * unsharded state is back in force when the call returns, whatever it returns.
+ * stats: summed over the slabs' fills -- n_pairs = N(N-1)/2, n_chunks, the counts and the times added up (the compaction and the
+ * copy are not in them: pc_last_edge_times).  *n_slabs: ranges the rule cut (a range holding target 0 alone counts, though it has no pair).
+ * PC_OK also for N <= 1 or nothing passing, with *n_edges = 0.  PC_ERR_ARG: bad metric, NaN threshold, negative slab_bytes, a NULL
+ * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA:
+ * as for a whole fill.  Runs on the context's own stream and returns with everything finished.
+ */
+int pc_fill_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, int64_t slab_bytes,
+                  const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook: HIP-event milliseconds of the last pc_fill_edges call that was given stats, summed over its slabs:
+ * *ms_compact count + scan + emit, *ms_d2h the copy of the edges to the host; either pointer may be NULL. */
+int pc_last_edge_times(const pc_ctx* ctx, float* ms_compact, float* ms_d2h);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -25,11 +25,12 @@ NW_FLAGS = []
 # pc_set_shape is the host arithmetic of the set-metric launch shapes: they hold no device code, so the library's .hip_fatbin comes
 # from the kernel units alone.  Those are, by family (internal header pc_pairs.h): pc_set_popc (popcount tiles), pc_sparse (sparse
 # tiles and their entry lists), pc_sparse_col (the column kernel), pc_walk (the shared-pham walker over both pair domains), pc_util
-# (scan, gather, shard assembly, test probes); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
+# (scan, gather, shard assembly, test probes), pc_edges (the edge-list compaction of pc_fill_edges); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
 HIP_UNITS = [("pc_ctx.hip", "pc_ctx.o", []), ("pc_upload.hip", "pc_upload.o", []), ("pc_align.hip", "pc_align.o", []),
              ("pc_fill.hip", "pc_fill.o", []), ("pc_multi.hip", "pc_multi.o", []),
              ("pc_set_popc.hip", "pc_set_popc.o", []), ("pc_sparse.hip", "pc_sparse.o", []), ("pc_sparse_col.hip", "pc_sparse_col.o", []),
              ("pc_set_shape.hip", "pc_set_shape.o", []), ("pc_walk.hip", "pc_walk.o", []), ("pc_util.hip", "pc_util.o", []),
+             ("pc_edges.hip", "pc_edges.o", []),
              ("pc_plan.hip", "pc_plan.o", []),
              ("pc_nw.hip", "pc_nw.o", NW_FLAGS),
              ("pc_nw_rules.hip", "pc_nw_r23.o", NW_FLAGS + ["-DPC_RULE_A=2", "-DPC_RULE_B=3"]),
@@ -66,6 +67,11 @@ def hip_headers():
 def build_hip(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = hip_headers()
+    # both libraries newer than every source and header: nothing to do, whether or not the object files are still around (a tree
+    # copied without them -- they are build products -- must not compile everything again)
+    every = [os.path.join(CSRC, src) for src in HIP_SOURCES] + headers
+    if not force and not _stale(HIP_LIB, every) and not _stale(HIP_HOOKS_LIB, every):
+        return HIP_LIB
     objs, jobs = [], []
     for src, obj_name, extra in HIP_UNITS + [HOOKS_UNIT]:
         src_path = os.path.join(CSRC, src)

@@ -48,6 +48,10 @@ _OPTIONS = (
     (None, "-x", "--extend", dict(type=pathlib.Path, default=None, help="distance matrix an earlier run wrote over a SUBSET of these genomes (its cache's "
                                                                        "02_distmats/<metric>_distance_matrix.tsv, or a squareform file): only the rows "
                                                                        "of the genomes it lacks are filled, on one GPU")),
+    (None, "-A", "--adjacency-only", dict(action="store_true", help="stop after the matrix stage and write only pairwise_<metric>_adjacency.tsv, from an "
+                                                                    "edge-list fill: the dense matrix is neither delivered nor cached, and no clustering runs")),
+    (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
+                                                                      "(default: every non-zero similarity, what the pipeline's file holds)")),
     (None, "-t", "--threads", dict(type=int, default=CPUS, help="accepted for compatibility; the six metrics run on the GPU (see --gpus)")),
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),
@@ -74,4 +78,12 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.edge_thresh is not None and not args.adjacency_only:
+        parser.error("--edge-thresh selects the edges of --adjacency-only; without it there is nothing to select")
+    if args.edge_thresh is not None and not 0.0 <= args.edge_thresh <= 1.0:          # (also refuses NaN)
+        parser.error("--edge-thresh is a similarity in [0, 1]")
+    if args.adjacency_only and args.extend is not None:
+        parser.error("--adjacency-only fills an edge list from scratch; it cannot be combined with --extend")
+    return args

@@ -147,6 +147,12 @@ int pc_sparse_col_vals_cap(int P64);             // pocp / af: entries (of phams
 int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);
 int pc_scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* tmp, int64_t tmp_elems, hipStream_t st);
 int64_t pc_scan_tmp_elems(int64_t n);
+// edge list of a filled slab (pc_edges.hip): chunks of the flat f64[Lp]; passing elements per chunk; (s, t, value) of each at
+// offs[chunk] + its rank within the chunk, in element order
+int64_t pc_edge_chunks(int64_t Lp);
+int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, uint32_t* counts, hipStream_t st);
+int pc_launch_edge_emit(const double* vals, int64_t Lp, int as_distance, double thr, const PcShard& sh, const uint32_t* offs,
+                        int32_t* src, int32_t* tgt, double* val, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

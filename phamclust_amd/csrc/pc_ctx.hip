@@ -87,6 +87,22 @@ int PinnedBuf::ensure(size_t bytes) {
     cap = want; return PC_OK;
 }
 
+// For a result that is appended to over one call (pc_fill_edges): ensure() would drop what is already there.  Grows to twice the
+// request so that a run of appends copies O(total) bytes.
+int PinnedBuf::grow_keep(size_t bytes, size_t used) {
+    if (bytes <= cap) return PC_OK;
+    if (!p || used == 0) return ensure(bytes);
+    void* q = nullptr;
+    size_t want = bytes * 2;
+    hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
+    if (e != hipSuccess) { (void)hipGetLastError(); want = bytes; e = hipHostMalloc(&q, want, hipHostMallocDefault); }   // (no room for the slack: the request alone)
+    if (e != hipSuccess) { pc_set_error("hipHostMalloc(%zu): %s", want, hipGetErrorString(e)); (void)hipGetLastError(); return PC_ERR_HIP; }
+    memcpy(q, p, used);
+    (void)hipHostFree(p);
+    p = q; cap = want;
+    return PC_OK;
+}
+
 #ifndef PC_TIE_RULE_DEFAULT
 #define PC_TIE_RULE_DEFAULT 0
 #endif
@@ -135,6 +151,7 @@ extern "C" void pc_ctx_destroy(pc_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < 5; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
+    for (int i = 0; i < 5; ++i) if (c->ev_edge[i]) (void)hipEventDestroy(c->ev_edge[i]);
     for (int i = 0; i < pc_ctx::kAux; ++i) if (c->aux[i]) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); }
     for (int i = 0; i <= pc_ctx::kAux; ++i) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
     for (int i = 0; i < pc_ctx::kLong; ++i) {

@@ -1,5 +1,5 @@
 // pc_fill.hip -- the fill entry points of libphamclust_hip.so (pc_fill, pc_fill_borrow, pc_fill_dev, pc_fill_shard_dev,
-// pc_assemble_dev, pc_fill_rows, pc_fill_rows_dev) and the set-metric kernel selector.
+// pc_assemble_dev, pc_fill_rows, pc_fill_rows_dev, pc_fill_edges) and the set-metric kernel selector.
 #include "pc_host.h"
 
 #ifndef PC_COL_MIN_N
@@ -302,6 +302,156 @@ extern "C" int pc_fill_rows(pc_ctx* c, int metric, int as_distance, const int32_
     if (n_rows > 0 && cells) PC_HIP(hipMemcpyAsync(out_host, c->b_out.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     PC_HIP(hipStreamSynchronize(c->stream));
     c->busy = false;
+    return PC_OK;
+}
+
+// ---- edge-list fill: the pairs whose value passes a threshold, as (source, target, value) arrays sorted by target, then source --
+// what matrix_to_adjacency(skip_zero) writes and SymMatrix.nearest_neighbors answers from the dense matrix (matrix.py:536-551,
+// 265-296), without the dense matrix ever crossing PCIe.  The call walks successive contiguous ranges of target genomes ("slabs":
+// pc_chunk_plan over count[t] = t under slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is
+// installed as a PcShard (owned = t0 .. t1-1, shard-local layout), filled by fill_impl into the context's slab buffer, compacted
+// (count -> scan -> one 4-byte read-back -> emit, pc_edges.hip) and its edges appended to the pinned host result.  Slabs in
+// ascending target order make the concatenation globally ordered.  One slab is resident at a time.
+#define PC_EDGE_MAX_PAIRS 0x7fffffffLL
+
+// the caller's unsharded state, put back however the call ends (the slab shards live in buffers of their own: b_owned / b_lbase,
+// the deal tables, rank / world and the stride are never touched)
+namespace {
+struct EdgeShardScope {
+    pc_ctx* c; PcShard shard; int64_t pairs; std::vector<int32_t> owned; std::vector<int64_t> lbase;
+    explicit EdgeShardScope(pc_ctx* ctx) : c(ctx), shard(ctx->shard), pairs(ctx->shard_pairs), owned(ctx->h_owned), lbase(ctx->h_lbase) {}
+    ~EdgeShardScope() { c->shard = shard; c->shard_pairs = pairs; c->h_owned.swap(owned); c->h_lbase.swap(lbase); c->plan.valid = false; }
+    EdgeShardScope(const EdgeShardScope&) = delete; EdgeShardScope& operator=(const EdgeShardScope&) = delete;
+};
+}  // namespace
+
+extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
+                             const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_edges: upload first"); return PC_ERR_STATE; }
+    if (!src || !tgt || !val || !n_edges || !n_slabs) { pc_set_error("pc_fill_edges: an output pointer is NULL"); return PC_ERR_ARG; }
+    if (metric < PC_GCS || metric > PC_AAI_PPOS) { pc_set_error("pc_fill_edges: metric %d", metric); return PC_ERR_ARG; }
+    if (threshold != threshold) { pc_set_error("pc_fill_edges: the threshold is NaN"); return PC_ERR_ARG; }
+    if (slab_bytes < 0) { pc_set_error("pc_fill_edges: slab_bytes %lld", (long long)slab_bytes); return PC_ERR_ARG; }
+    if (c->world != 1) { pc_set_error("pc_fill_edges: context is sharded (%d/%d); an edge-list fill is a one-GPU call on an unsharded context", c->rank, c->world); return PC_ERR_STATE; }
+    if (metric >= PC_AAI && !c->residues_ready) { pc_set_error("pc_fill_edges: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    PC_ON_DEVICE(c);
+    PcRange range("pc:fill_edges");
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const int N = c->dev.N;
+    pc_stats sum; memset(&sum, 0, sizeof(sum));
+    c->last_edge_ms[0] = c->last_edge_ms[1] = 0.f;
+    as_distance = as_distance ? 1 : 0;
+    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffers are rewritten)
+    if ((rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
+    if (N <= 1) {
+        *src = c->h_edge_src.as<int32_t>(); *tgt = c->h_edge_tgt.as<int32_t>(); *val = c->h_edge_val.as<double>();
+        if (stats) *stats = sum;
+        return PC_OK;
+    }
+    // ---- the cut: ranges of targets whose pairs fit the slab
+    const int64_t np = (int64_t)N * (N - 1) / 2;
+    int64_t max_pairs;
+    if (slab_bytes > 0) max_pairs = std::max<int64_t>(slab_bytes / 8, 1);
+    else {                                                                  // the dense triangle, or a quarter of what is free now (an aai / peq slab's plan takes its own half)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
+        max_pairs = std::min<int64_t>(np, std::max<int64_t>((int64_t)((free_b + c->b_edge_slab.cap) / 4 / 8), 1));
+    }
+    max_pairs = std::min<int64_t>(max_pairs, PC_EDGE_MAX_PAIRS);
+    std::vector<uint64_t> per_target((size_t)N);
+    for (int t = 0; t < N; ++t) per_target[t] = (uint64_t)t;
+    const int nsl = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, nullptr, 0);
+    if (nsl < 0) return nsl;
+    std::vector<int32_t> cut((size_t)nsl + 1);
+    if ((rc = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, cut.data(), nsl + 1)) < 0) return rc;
+    auto pairs_below = [](int64_t t) { return t * (t - 1) / 2; };           // pairs (s, t'), s < t' < t
+    int64_t most = 1;
+    for (int i = 0; i < nsl; ++i) most = std::max(most, pairs_below(cut[i + 1]) - pairs_below(cut[i]));
+    if ((rc = c->b_edge_slab.ensure((size_t)most * 8))) return abi_rc(rc);
+    if (stats) for (hipEvent_t& e : c->ev_edge) if (!e) PC_HIP(hipEventCreate(&e));
+    double* const slab = c->b_edge_slab.as<double>();
+    uint32_t* const h_total = c->h_plan.as<uint32_t>();
+
+    EdgeShardScope restore(c);
+    int64_t E = 0;
+    std::vector<int32_t> owned; std::vector<int64_t> lbase;
+    for (int i = 0; i < nsl; ++i) {
+        const int t0 = cut[i], t1 = cut[i + 1];
+        const int64_t Lp = pairs_below(t1) - pairs_below(t0);
+        if (Lp == 0) continue;                                              // (target 0 alone: no pair)
+        owned.resize((size_t)(t1 - t0)); lbase.resize((size_t)(t1 - t0) + 1);
+        for (int t = t0; t < t1; ++t) { owned[t - t0] = t; lbase[t - t0] = pairs_below(t) - pairs_below(t0); }
+        lbase[t1 - t0] = Lp;
+        if ((rc = upload_vec(c->b_edge_owned, owned)) || (rc = upload_vec(c->b_edge_lbase, lbase))) return rc;
+        // install the slab's shard as apply_shard installs one: a plan belongs to the shard it was made for, and pick_set_kernel
+        // gathers its per-shard inputs (nown, max_block_entries) from what is in force
+        c->plan.valid = false;
+        c->shard.nown = t1 - t0; c->shard.ident = 0;
+        c->shard.owned = c->b_edge_owned.as<int32_t>(); c->shard.lbase = c->b_edge_lbase.as<int64_t>();
+        c->h_owned = owned; c->h_lbase = lbase; c->shard_pairs = Lp;
+        pc_stats one; memset(&one, 0, sizeof(one));
+        if ((rc = fill_impl(c, metric, as_distance, slab, 0, st, stats ? &one : nullptr))) return rc;
+        sum.n_pairs += Lp; sum.n_alignments += one.n_alignments; sum.n_cells += one.n_cells; sum.n_tasks += one.n_tasks;
+        sum.n_residue_bytes += one.n_residue_bytes; sum.n_align_launches += one.n_align_launches; sum.n_chunks += one.n_chunks;
+        sum.ms_total += one.ms_total; sum.ms_plan += one.ms_plan; sum.ms_align += one.ms_align; sum.ms_reduce += one.ms_reduce;
+        sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
+        // ---- compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit
+        const int64_t nch = pc_edge_chunks(Lp);
+        if ((rc = c->b_edge_cnt.ensure((size_t)(nch + 1) * 4)) || (rc = c->b_edge_off.ensure((size_t)(nch + 1) * 4)) ||
+            (rc = c->b_scan_tmp.ensure((size_t)pc_scan_tmp_elems(nch + 1) * 4))) return abi_rc(rc);
+        uint32_t* const cnt = c->b_edge_cnt.as<uint32_t>(); uint32_t* const off = c->b_edge_off.as<uint32_t>();
+        if (stats) PC_HIP(hipEventRecord(c->ev_edge[0], st));
+        PC_HIP(hipMemsetAsync(cnt + nch, 0, 4, st));
+        if ((rc = pc_launch_edge_count(slab, Lp, as_distance, threshold, cnt, st))) return rc;
+        if ((rc = pc_scan_exclusive_u32(cnt, off, nch + 1, c->b_scan_tmp.as<uint32_t>(), (int64_t)(c->b_scan_tmp.cap / 4), st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_edge[1], st));
+        PC_HIP(hipMemcpyAsync(h_total, off + nch, 4, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipStreamSynchronize(st));
+        c->busy = false;
+        const int64_t Es = (int64_t)h_total[0];
+        if (Es == 0) {
+            if (stats) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_edge[0], c->ev_edge[1])); c->last_edge_ms[0] += x; }
+            continue;
+        }
+        if ((rc = c->b_edge_src.ensure((size_t)Es * 4)) || (rc = c->b_edge_tgt.ensure((size_t)Es * 4)) || (rc = c->b_edge_val.ensure((size_t)Es * 8))) return abi_rc(rc);
+        if ((rc = c->h_edge_src.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) || (rc = c->h_edge_tgt.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) ||
+            (rc = c->h_edge_val.grow_keep((size_t)(E + Es) * 8, (size_t)E * 8))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_edge[2], st));
+        if ((rc = pc_launch_edge_emit(slab, Lp, as_distance, threshold, c->shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+                                      c->b_edge_val.as<double>(), st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_edge[3], st));
+        PC_HIP(hipMemcpyAsync(c->h_edge_src.as<int32_t>() + E, c->b_edge_src.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipMemcpyAsync(c->h_edge_tgt.as<int32_t>() + E, c->b_edge_tgt.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipMemcpyAsync(c->h_edge_val.as<double>() + E, c->b_edge_val.p, (size_t)Es * 8, hipMemcpyDeviceToHost, st));
+        if (stats) PC_HIP(hipEventRecord(c->ev_edge[4], st));
+        PC_HIP(hipStreamSynchronize(st));                                   // the slab, its tables and the edge buffers are rewritten by the next range
+        if (stats) {
+            float x = 0.f, y = 0.f, z = 0.f;
+            PC_HIP(hipEventElapsedTime(&x, c->ev_edge[0], c->ev_edge[1]));
+            PC_HIP(hipEventElapsedTime(&y, c->ev_edge[2], c->ev_edge[3]));
+            PC_HIP(hipEventElapsedTime(&z, c->ev_edge[3], c->ev_edge[4]));
+            c->last_edge_ms[0] += x + y; c->last_edge_ms[1] += z;
+        }
+        E += Es;
+    }
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    *src = c->h_edge_src.as<int32_t>(); *tgt = c->h_edge_tgt.as<int32_t>(); *val = c->h_edge_val.as<double>();
+    *n_edges = E; *n_slabs = nsl;
+    if (stats) *stats = sum;
+    return PC_OK;
+}
+
+extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_d2h) {
+    if (!c) { pc_set_error("pc_last_edge_times: NULL context"); return PC_ERR_ARG; }
+    if (ms_compact) *ms_compact = c->last_edge_ms[0];
+    if (ms_d2h) *ms_d2h = c->last_edge_ms[1];
     return PC_OK;
 }
 

@@ -41,6 +41,7 @@ struct PinnedBuf {
     PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
     ~PinnedBuf() { if (p) (void)hipHostFree(p); }
     int ensure(size_t bytes);
+    int grow_keep(size_t bytes, size_t used);   // as ensure, but the first `used` bytes survive a growth (new buffer, copy, free)
     template <class T> T* as() const { return (T*)p; }
 };
 
@@ -112,6 +113,11 @@ struct pc_ctx {
     DevBuf b_na, b_off, b_key0, b_key1, b_val0, b_val1, b_sort_tmp, b_flags, b_excl, b_alias, b_start_q, b_end_q, b_ntask_q, b_task_off_q, b_scan_tmp;
     DevBuf b_tasks, b_tasks_sorted, b_bucket_row, b_bucket_dest, b_res, b_totals, b_plan, b_scratch, b_out, b_lut, b_slice_begin, b_aln_t;
     DevBuf b_rows, b_row_of;                // the domain of the last rows fill (PcRows: the query genomes, and every genome's position among them)
+    // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
+    DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
+    PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
+    hipEvent_t ev_edge[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_edges that is asked for stats
+    float last_edge_ms[2] = {0.f, 0.f};     // count + scan + emit, edges' D2H of the last pc_fill_edges with stats (pc_last_edge_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {

@@ -309,6 +309,24 @@ int64_t pcp_format_adjacency(const char* src, int64_t src_len, const char* names
     return (int64_t)(p - out);
 }
 
+/* adjacency lines of an edge list: for e in [0, n_edges) "names[src[e]]<TAB>names[tgt[e]]<TAB>weight[e]\n", in the order given
+ * (matrix.edges_to_adjacency passes the reference's: source-major, each node's self-edge first); n_names bounds the indices.
+ * skip_zero drops weights equal to 0.  Returns bytes written, -1 when `cap` cannot hold them, -2 for an index outside the names. */
+int64_t pcp_format_edges(const char* names, const int64_t* name_off, int64_t n_names, const int32_t* src, const int32_t* tgt,
+                         const double* weight, int64_t n_edges, int skip_zero, char* out, int64_t cap) {
+    char* p = out; char* const end = out + cap;
+    for (int64_t e = 0; e < n_edges; ++e) {
+        if (skip_zero && weight[e] == 0.0) continue;
+        if (src[e] < 0 || src[e] >= n_names || tgt[e] < 0 || tgt[e] >= n_names) return -2;
+        const int64_t ls = name_off[src[e] + 1] - name_off[src[e]], lt = name_off[tgt[e] + 1] - name_off[tgt[e]];
+        if (end - p < ls + lt + PCP_FMT_MAX + 3) return -1;
+        memcpy(p, names + name_off[src[e]], (size_t)ls); p += ls; *p++ = '\t';
+        memcpy(p, names + name_off[tgt[e]], (size_t)lt); p += lt; *p++ = '\t';
+        p = fmt6(weight[e], p); *p++ = '\n';
+    }
+    return (int64_t)(p - out);
+}
+
 /* tab-separated decimal fields of one line -> doubles (strtod: same values as Python's float()); returns the
  * count parsed, or -(position+1) of the first field that is not a number */
 int64_t pcp_parse_row(const char* text, int64_t len, double* out, int64_t cap) {

@@ -72,7 +72,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
            "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
-           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev"]
+           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -131,6 +131,9 @@ def load():
     L.pc_assemble_dev.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.pc_fill_rows.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _f64p, ctypes.POINTER(PcStats)]
     L.pc_fill_rows_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
+    L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_edge_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -396,6 +399,51 @@ class Context:
         self._check(self._lib.pc_fill_rows(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(rows, _i32p), int(rows.shape[0]),
                                            _ptr(buf, _f64p), ctypes.byref(stats)))
         return (out, stats.as_dict()) if want_stats else out
+
+    EDGE_MAX_PAIRS = 2 ** 31 - 1          # pairs one slab of an edge-list fill may hold (u32 counts and offsets on the device)
+
+    @staticmethod
+    def edge_slabs(n, slab_bytes):
+        """The ranges of target genomes an edge-list fill of ``n`` genomes walks under ``slab_bytes`` (> 0) of slab: range starts
+        + [n] (host arithmetic, no GPU).  It is :meth:`chunk_plan` over ``count[t] = t`` -- target t has t pairs (s, t), s < t --
+        with ``slab_bytes // 8`` pairs per range, clamped to 2^31-1; a target above that gets a range of its own."""
+        if int(slab_bytes) <= 0:
+            raise ValueError("edge_slabs: slab_bytes must be positive (0 = automatic is decided on the device, by the free HBM)")
+        return Context.chunk_plan(np.arange(int(n), dtype=np.uint64), min(max(int(slab_bytes) // 8, 1), Context.EDGE_MAX_PAIRS))
+
+    def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
+        for a similarity fill -- as ``(src, tgt, val)``: int32, int32, float64 arrays sorted by ``t``, then ``s``; the values are
+        the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time; 0 = automatic) held.
+        The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s terms.
+        ``want_stats`` adds the fills' summed stats with ``n_edges``, ``n_slabs``, ``ms_compact`` and ``ms_d2h``."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        self._invalidate_loans()
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_fill_edges(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(slab_bytes),
+                                            ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl),
+                                            ctypes.byref(stats)))
+        out = []
+        for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64)):
+            if n.value == 0 or not ptr:
+                out.append(np.empty(0, dtype=dtype))
+                continue
+            view = np.ctypeslib.as_array(ptr, shape=(n.value,))
+            if borrow:
+                view.flags.writeable = False
+                view = BorrowedArray(view, self)
+                self._loans.append(weakref.ref(view))
+            else:
+                view = view.copy()
+            out.append(view)
+        if not want_stats:
+            return tuple(out)
+        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.pc_last_edge_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return (*out, dict(stats.as_dict(), n_edges=int(n.value), n_slabs=int(nsl.value), ms_compact=float(a.value), ms_d2h=float(b.value)))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

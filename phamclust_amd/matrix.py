@@ -611,6 +611,9 @@ def _text_lib():
             lib.pcp_format_adjacency.restype = ctypes.c_int64
             lib.pcp_format_adjacency.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64]
+            lib.pcp_format_edges.restype = ctypes.c_int64
+            lib.pcp_format_edges.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64]
             lib.pcp_parse_row.restype = ctypes.c_int64
             lib.pcp_parse_row.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
             _TEXT_LIB = lib
@@ -646,6 +649,158 @@ def matrix_to_adjacency(matrix, filepath, skip_zero=False):
             if size < 0:
                 raise ValueError(f"{filepath}: a row of '{source.decode()}' does not fit its buffer (weights outside [0, 1]?)")
             handle.write(buf.raw[:size] if size < 65536 else memoryview(buf)[:size])
+    return filepath
+
+
+# ---------------------------------------------------------------------------------------
+# Sparse delivery: the pairs within a threshold, without the dense matrix
+# ---------------------------------------------------------------------------------------
+class SparseEdges:
+    """The edges of a matrix that pass a threshold -- ``weight <= threshold`` on distances, ``>= threshold`` on similarities -- as
+    three parallel arrays over ``nodes``: ``source[e] < target[e]`` (indices into ``nodes``), sorted by target, then source, and
+    ``weight[e]``.  It is the sparse form the reference derives from its dense matrix twice: ``matrix_to_adjacency(...,
+    skip_zero=True)`` (matrix.py:536-551) and ``SymMatrix.nearest_neighbors`` (matrix.py:265-296); ``edges_de_novo`` fills it on the
+    GPU without the dense matrix.  The diagonal is implied: ``1.0 - is_distance`` (matrix.py:467-468)."""
+
+    def __init__(self, nodes, source, target, weight, is_distance=True, threshold=None):
+        self.nodes = list(nodes)
+        self.source = np.ascontiguousarray(source, dtype=np.int32)
+        self.target = np.ascontiguousarray(target, dtype=np.int32)
+        self.weight = np.ascontiguousarray(weight, dtype=np.float64)
+        if not (self.source.shape == self.target.shape == self.weight.shape and self.source.ndim == 1):
+            raise ValueError("source, target and weight must be three 1-D arrays of one length")
+        self.is_distance = bool(is_distance)
+        self.threshold = threshold
+        self._slot = None
+        self._incident = None
+
+    @classmethod
+    def from_dense(cls, matrix, threshold):
+        """The edges of a filled ``SymMatrix`` within ``threshold``, in its current node order (tests and small inputs)."""
+        data = matrix._ordered()
+        s, t = np.triu_indices(len(matrix), k=1)
+        w = data[s, t]
+        keep = np.flatnonzero((w <= threshold) if matrix.is_distance else (w >= threshold))
+        keep = keep[np.lexsort((s[keep], t[keep]))]
+        return cls(matrix.nodes, s[keep], t[keep], w[keep], is_distance=matrix.is_distance, threshold=threshold)
+
+    def __len__(self):
+        return int(self.weight.shape[0])
+
+    def _adjacency_order(self):
+        """(source, target, weight) index / value arrays in the reference's adjacency order (matrix.py:368-379, 536-551):
+        source-major, each node's self-edge first, then its targets ascending -- one stable argsort of the source over the
+        (target, source)-sorted edges behind the diagonal."""
+        n = len(self.nodes)
+        loop = np.arange(n, dtype=np.int32)
+        src = np.concatenate([loop, self.source])
+        order = np.argsort(src, kind="stable")
+        tgt = np.concatenate([loop, self.target])[order]
+        w = np.concatenate([np.full(n, 0.0 if self.is_distance else 1.0), self.weight])[order]
+        return np.ascontiguousarray(src[order]), np.ascontiguousarray(tgt), np.ascontiguousarray(w)
+
+    def __iter__(self):
+        src, tgt, w = self._adjacency_order()
+        for i, j, x in zip(src.tolist(), tgt.tolist(), w.tolist()):
+            yield self.nodes[i], self.nodes[j], x
+
+    def neighbors(self, name):
+        """The names ``SymMatrix.nearest_neighbors(name, threshold)`` gives on the dense matrix, in its order: closest first,
+        equally close ones in node order."""
+        if self._slot is None:
+            self._slot = {node: k for k, node in enumerate(self.nodes)}
+        if name not in self._slot:
+            raise KeyError(f"node '{name}' not in matrix")
+        if self._incident is None:                               # every edge from both ends, grouped by node, the other end ascending
+            node = np.concatenate([self.source, self.target])
+            other = np.concatenate([self.target, self.source])
+            order = np.lexsort((other, node))
+            node = node[order]
+            self._incident = (np.searchsorted(node, np.arange(len(self.nodes) + 1)), other[order], np.concatenate([self.weight, self.weight])[order])
+        starts, other, w = self._incident
+        k = self._slot[name]
+        other, w = other[starts[k]:starts[k + 1]], w[starts[k]:starts[k + 1]]
+        ranked = other[np.argsort(w if self.is_distance else -w, kind="stable")]
+        return [self.nodes[j] for j in ranked]
+
+    def inverted(self):
+        """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SymMatrix.invert`` does (matrix.py:236-247)."""
+        return SparseEdges(self.nodes, self.source, self.target, np.round(1.0 - self.weight, 6), is_distance=not self.is_distance,
+                           threshold=None if self.threshold is None else round(1.0 - self.threshold, 6))
+
+    def to_symmatrix(self, fill):
+        """The dense ``SymMatrix`` over ``nodes``: the edges' weights, ``fill`` for every absent pair, the diagonal preset."""
+        n = len(self.nodes)
+        data = np.full((n, n), float(fill), dtype=np.float64)
+        data[self.source, self.target] = self.weight
+        data[self.target, self.source] = self.weight
+        np.fill_diagonal(data, 0.0 if self.is_distance else 1.0)
+        return _square_matrix(self.nodes, data, self.is_distance)
+
+
+def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
+    """The edges of ``matrix_de_novo(genomes, func, cpus, as_distance)`` within ``threshold`` as a :class:`SparseEdges`, filled
+    on the GPU by ``Context.fill_edges``: the dense matrix is never delivered, and beyond ``slab_bytes`` of HBM (0: automatic)
+    never held.  ``func`` must be one of the six ``METRICS`` callables: there is no CPU route for this call (a generic callable
+    has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  One GPU: with ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` the first
+    listed device; under a launcher (``WORLD_SIZE`` > 1) it raises."""
+    if len(genomes) == 0:
+        raise ValueError("need at least 1 genome to construct edges de novo")
+    metric = _metric_name(func)
+    if metric is None:
+        raise ValueError("edges_de_novo: func must be one of the six METRICS callables -- the edge-list fill runs on the GPU only and has no "
+                         "CPU route (for another callable: SparseEdges.from_dense(matrix_de_novo(...), threshold))")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("edges_de_novo: the edge-list fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+    import time
+    devices = in_process_devices()
+    if devices:
+        logging.debug(f"edges_de_novo: the edge-list fill is a one-GPU call: using device {devices[0]} of {devices}")
+    t0 = time.perf_counter()
+    packed = _packed_of(genomes)
+    t1 = time.perf_counter()
+    ctx = get_context(devices[0] if devices else None)
+    ctx.upload(packed, residues=metric in ("aai", "peq"))
+    t2 = time.perf_counter()
+    src, tgt, val, stats = ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    t3 = time.perf_counter()
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=1, rank=0,
+                     pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
+    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} of {packed.n_pairs} edges in {stats['n_slabs']} slab(s) on one device: "
+                  f"pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+compact+D2H {t3 - t2:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    return SparseEdges([g.name for g in genomes], src, tgt, val, is_distance=as_distance, threshold=threshold)
+
+
+def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):
+    """The bytes ``matrix_to_adjacency`` writes for the dense matrix restricted to these pairs (diagonal included).
+    ``use_lib=False`` takes the Python formatter even when csrc/libpc_pack.so is there (same bytes)."""
+    src, tgt, w = edges._adjacency_order()
+    lib = _text_lib() if use_lib else None
+    if lib is None or np.isnan(w).any():
+        with open(filepath, "w") as handle:
+            for i, j, x in zip(src.tolist(), tgt.tolist(), w.tolist()):
+                if skip_zero and not x:
+                    continue
+                handle.write(f"{edges.nodes[i]}\t{edges.nodes[j]}\t{x:.6f}\n")
+        return filepath
+    import ctypes
+    names = [name.encode() for name in edges.nodes]
+    blob = b"".join(names)
+    offsets = np.zeros(len(names) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in names], out=offsets[1:])
+    step = 65536
+    cap = step * (max((len(x) for x in names), default=0) * 2 + 32) + 1024
+    buf = ctypes.create_string_buffer(cap)
+    with open(filepath, "wb") as handle:
+        for e0 in range(0, src.shape[0], step):
+            n = min(step, src.shape[0] - e0)
+            size = lib.pcp_format_edges(blob, offsets.ctypes.data, len(names), src[e0:].ctypes.data, tgt[e0:].ctypes.data, w[e0:].ctypes.data,
+                                        n, 1 if skip_zero else 0, buf, cap)
+            if size < 0:
+                raise ValueError(f"{filepath}: edges {e0}..{e0 + n} do not fit their buffer (weights outside [0, 1]?)" if size == -1 else
+                                 f"{filepath}: an edge names a node outside 0..{len(names) - 1}")
+            handle.write(memoryview(buf)[:size])
     return filepath
 
 

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
+from phamclust_amd.matrix import edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -209,6 +209,28 @@ class _Run:
             sys.exit(1)
         return matrix
 
+    # 2, --adjacency-only
+    def adjacency(self, similarity):
+        """Stage 2 as an edge-list fill: the pairs of similarity >= ``similarity`` (None: every non-zero one) straight into
+        ``pairwise_<metric>_adjacency.tsv`` -- the file ``finish`` writes from the dense matrix (name order instead of cluster
+        order), without the dense matrix: nothing is cached, nothing is clustered."""
+        self.banner(2, f"{self.metric} adjacency (edge-list fill)")
+        t0 = time.perf_counter()
+        distance = 0.999999 if similarity is None else round(1.0 - similarity, 6)       # 6-place values: d <= 0.999999 is sim > 0
+        edges = edges_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True)
+        st = _matrix.LAST_FILL
+        pairs = st.get("genome_pairs", 0)
+        log.info(f"{len(edges):,} of {pairs:,} pairs ({100.0 * len(edges) / max(pairs, 1):.1f} %) within distance {distance:.6f} from "
+                 f"{st.get('n_slabs', 1)} slab(s) on 1 GPU in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
+                 f"{st.get('upload_s', 0.0):.3f}, fill+compact+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, "
+                 f"compaction {st.get('ms_compact', 0.0):.3f} ms, edge copy {st.get('ms_d2h', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        target = self.outdir / f"pairwise_{self.metric}_adjacency.tsv"
+        edges_to_adjacency(edges.inverted(), target, skip_zero=True)
+        log.info(f"wrote {target.name}")
+        return edges
+
     def extended(self, cpus, t0):
         """Stage 2 under --extend: the old matrix's block is kept, the rows of the genomes it lacks are filled (matrix_extend)."""
         try:
@@ -291,9 +313,14 @@ class _Run:
 
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
-              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None):
+              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
-    distance matrix of an earlier run over a subset of the genomes (``--extend``), or None."""
+    distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
+    edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file."""
+    if adjacency_only and extend is not None:
+        raise ValueError("adjacency_only cannot be combined with extend")
+    if edge_thresh is not None and not adjacency_only:
+        raise ValueError("edge_thresh selects the edges of adjacency_only")
     if nr_distance >= clu_distance:          # pre-grouping must be tighter than clustering, else switch it off
         nr_distance = 0.0
     settings = dict(infile=infile, outdir=outdir, metric=metric, nr=(nr_distance, nr_linkage), clu=(clu_distance, clu_linkage),
@@ -301,6 +328,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
                     midpoint=midpoint, cpus=cpus, remove_tmp=rm_tmp, debug=debug)
     if extend is not None:
         settings["extend"] = extend
+    if adjacency_only:
+        settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}")
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
@@ -309,6 +338,13 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     run.rank, run.world = distributed.ensure_process_group()      # (0, 1) unless started by torch.distributed.run
     _mark("torch_import_and_process_group")
     run.read(infile, is_genome_dir)
+    if adjacency_only:
+        if run.world > 1:
+            log.error("--adjacency-only is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.adjacency(edge_thresh)
+        run.banner(3, "done (--adjacency-only: no clustering)")
+        return
     matrix = run.distances(cpus)
     if matrix is None:                        # ranks other than 0 are done once their shard is gathered
         return
@@ -368,7 +404,11 @@ def main(argv=None):
 def _run(args, argv):
     rank, _, world = distributed.env_world()
     gpus_note = None
-    if args.gpus > 1 and world == 1 and args.extend is not None:
+    if args.gpus > 1 and world == 1 and args.adjacency_only:
+        # the edge-list fill is a one-GPU call too (pc_fill_edges refuses a sharded context)
+        gpus_note = "--adjacency-only fills an edge list, which is a one-GPU call: the matrix stage stays on one GPU"
+        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
+    elif args.gpus > 1 and world == 1 and args.extend is not None:
         # the rows fill of --extend is a one-GPU call (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
         gpus_note = "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
         os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
@@ -419,7 +459,8 @@ def _run(args, argv):
                   clu_distance=as_distance(args.clu_thresh), clu_linkage=args.clu_linkage,
                   sub_distance=as_distance(args.sub_thresh), sub_linkage=args.sub_linkage, k_min=max(1, args.k_min),
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
-                  cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend)
+                  cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
+                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
