@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 156   /* 0.5.5: pc_fill_edges */
+#define PC_VERSION 157   /* 0.5.6: pc_fill_components */
 
 typedef enum {
     PC_OK = 0,
@@ -220,6 +220,30 @@ int pc_fill_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, in
 /* Test / tuning hook: HIP-event milliseconds of the last pc_fill_edges call that was given stats, summed over its slabs:
  * *ms_compact count + scan + emit, *ms_d2h the copy of the edges to the host; either pointer may be NULL. */
 int pc_last_edge_times(const pc_ctx* ctx, float* ms_compact, float* ms_d2h);
+
+/*
+ * Components fill: the single-linkage clusters at a threshold, without the dense matrix and without an edge list.  labels[g] is
+ * the smallest genome index of g's connected component in the graph whose edges are the pairs (s, t) that pass the predicate --
+ * pc_fill_edges' (value <= threshold on distances, >= on similarities), or with strict != 0 the strict forms (<, >); a plain f64
+ * compare on the delivered, already round(x, 6) value.  With as_distance and strict this is exactly what the reference's
+ * hierarchical_clustering(matrix, "single", eps) partitions into (clustering.py:4-51: scikit-learn's distance_threshold is "at or
+ * above which clusters will not be merged"), and every "average" / "complete" cluster at eps lies inside one such component.
+ * Same walk as pc_fill_edges: the same slab cut (pc_chunk_plan over count[t] = t, slab_bytes / 8 pairs, <= 2^31-1; 0 = automatic),
+ * each slab filled as a shard into the resident slab buffer, then ONE pass over it (a lock-free union-find over a parent[N] array
+ * that lives on the device across the slabs); after the last slab one labelling pass and one copy of labels[N] plus the 8-byte
+ * count.  Nothing is read back per slab.  The labels are canonical: they do not depend on how races between workgroups resolved.
+ * *labels points into page-locked memory the context owns (pc_fill_borrow's loan rule: valid until the next fill or upload on this
+ * context or its destruction); *n_components = genomes g with labels[g] == g; *n_edges = pairs that passed; *n_slabs and stats as
+ * pc_fill_edges gives them (the union and labelling passes are not in stats: pc_last_component_times).
+ * PC_OK also for N <= 1 or nothing passing (identity labels).  PC_ERR_ARG: bad metric, NaN threshold, negative slab_bytes, a NULL
+ * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1), aai / peq before pc_upload_residues.  On a refusal
+ * *labels is NULL and the counts are 0.  The caller's unsharded state is back in force when the call returns, whatever it returns.
+ */
+int pc_fill_components(pc_ctx* ctx, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
+                       const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook: HIP-event milliseconds of the last pc_fill_components call that was given stats: *ms_union the union passes
+ * summed over its slabs, *ms_labels the labelling pass; either pointer may be NULL. */
+int pc_last_component_times(const pc_ctx* ctx, float* ms_union, float* ms_labels);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -50,8 +50,13 @@ _OPTIONS = (
                                                                        "of the genomes it lacks are filled, on one GPU")),
     (None, "-A", "--adjacency-only", dict(action="store_true", help="stop after the matrix stage and write only pairwise_<metric>_adjacency.tsv, from an "
                                                                     "edge-list fill: the dense matrix is neither delivered nor cached, and no clustering runs")),
+    (None, "-C", "--components-only", dict(action="store_true", help="stop after the matrix stage and write only components_<metric>.tsv, from a "
+                                                                     "components fill: the single-linkage groups at --edge-thresh (genomes joined "
+                                                                     "when distance < 1 - SIM); no matrix, no edge list, no clustering")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
-                                                                      "(default: every non-zero similarity, what the pipeline's file holds)")),
+                                                                      "(default: every non-zero similarity, what the pipeline's file holds); with "
+                                                                      "--components-only: join genomes of distance below 1 - this similarity "
+                                                                      "(default 0.0: any non-zero similarity joins)")),
     (None, "-t", "--threads", dict(type=int, default=CPUS, help="accepted for compatibility; the six metrics run on the GPU (see --gpus)")),
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),
@@ -80,10 +85,14 @@ def build_parser():
 def parse_args(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.edge_thresh is not None and not args.adjacency_only:
-        parser.error("--edge-thresh selects the edges of --adjacency-only; without it there is nothing to select")
+    if args.edge_thresh is not None and not (args.adjacency_only or args.components_only):
+        parser.error("--edge-thresh selects the edges of --adjacency-only or --components-only; without one of them there is nothing to select")
     if args.edge_thresh is not None and not 0.0 <= args.edge_thresh <= 1.0:          # (also refuses NaN)
         parser.error("--edge-thresh is a similarity in [0, 1]")
     if args.adjacency_only and args.extend is not None:
         parser.error("--adjacency-only fills an edge list from scratch; it cannot be combined with --extend")
+    if args.components_only and args.adjacency_only:
+        parser.error("--components-only and --adjacency-only each stop after a fill of their own; give one of them")
+    if args.components_only and args.extend is not None:
+        parser.error("--components-only fills from scratch; it cannot be combined with --extend")
     return args

@@ -153,6 +153,12 @@ int64_t pc_edge_chunks(int64_t Lp);
 int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, uint32_t* counts, hipStream_t st);
 int pc_launch_edge_emit(const double* vals, int64_t Lp, int as_distance, double thr, const PcShard& sh, const uint32_t* offs,
                         int32_t* src, int32_t* tgt, double* val, hipStream_t st);
+// connected components of a filled slab's passing pairs (pc_components.hip): parent[g] = g and the pair counter zeroed; one slab's
+// passing pairs hooked into parent[] (strict: < / > instead of <= / >=) and counted into *n_pass; labels[g] = root of g
+int pc_launch_cc_init(int32_t* parent, int n, unsigned long long* n_pass, hipStream_t st);
+int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, const PcShard& sh, int32_t* parent,
+                       unsigned long long* n_pass, hipStream_t st);
+int pc_launch_cc_labels(int32_t* parent, int32_t* labels, int n, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

@@ -1,0 +1,175 @@
+// pc_components.hip -- the kernels of pc_fill_components: the connected components of the graph whose edges are the pairs of a
+// filled slab that pass a threshold, by a lock-free union-find over parent[N] (i32, device-resident across the call's slabs).
+// With a strict distance predicate (d < eps) the components ARE the reference's single-linkage clusters at eps
+// (clustering.py:4-51: AgglomerativeClustering(linkage="single", distance_threshold=eps) merges below eps, never at it), and every
+// average / complete cluster at eps lies inside one of them.
+//   k_cc_init     parent[g] = g, the pair counter = 0                                   (once per call)
+//   k_cc_union    streams a slab exactly as k_edge_count does (pc_edges.hip: flat f64[Lp], chunks of 4,096 elements, 256 threads,
+//                 eight 16-byte loads per thread, the odd last element alone, nothing read beyond Lp); (s, t) of a passing element
+//                 as k_edge_emit finds it (one binary search of lbase per chunk, then the forward walk over empty and short rows);
+//                 per passing pair: find both roots, equal -> done, else hook the LARGER root under the SMALLER by compare-and-swap
+//   k_cc_labels   pointer jumping, launched ceil(log2 N) times after the last slab: labels[g] = the root of g
+// Two invariants carry the correctness argument:
+//   I1  parent[x] <= x, always.  (init: equal; a hook writes lo < hi into parent[hi]; a shortening writes an ancestor, which by I1
+//       is smaller still.)  So every walk towards a root strictly descends: it ends after at most x steps, and no cycle can form.
+//   I2  a word only ever decreases (CAS hi -> lo < hi; atomicMin), so a non-root (parent[x] < x) never becomes a root again.
+// From them: a value ever read from parent[x], however stale, is a node of x's component and <= x, so a walk over stale values
+// still ends at a node of the component that WAS a root; whether it still is one is decided by the CAS alone, which succeeds
+// only on a root (parent[hi] == hi) and joins two different trees (lo < hi keeps the forest acyclic).  A pair is done when both
+// walks met in one node or its own CAS succeeded -- connected either way -- and connections are never undone (a shortening
+// replaces a parent by an ancestor).  The smallest genome m of a component has parent[m] <= m inside the component, i.e. is its
+// root: labels are the smallest member's index, whatever order the races resolved in.
+// Memory: inside k_cc_union EVERY access to parent[] is a relaxed agent-scope atomic (__hip_atomic_load, atomicCAS, atomicMin;
+// no plain load or store): the XCDs' L2s are not coherent with each other and a CU's L1 is never refreshed by another CU's writes.
+// Progress: no workgroup ever waits for another.  The only loops are the walk (bounded by I1) and the CAS retry, whose larger
+// root strictly descends with every round (a failed CAS returns the word's true value, < hi, and the walks go on from there).
+// No flags, no spinning on a value another wave is to write, no sleeping.
+#include "pc_pairs.h"
+
+#define CC_THREADS 256
+#define CC_ITERS 8
+#define CC_STRIDE (CC_THREADS * 2)                     // as EDGE_STRIDE: two consecutive elements per thread and iteration
+#define CC_CHUNK (CC_STRIDE * CC_ITERS)                // 4,096 elements = 32 KB of slab per workgroup
+
+template <int DIST, int STRICT> __device__ __forceinline__ bool pc_cc_pass(double v, double thr) {
+    if (DIST) return STRICT ? v < thr : v <= thr;
+    return STRICT ? v > thr : v >= thr;
+}
+
+// elements i and i + 1 of the slab (i even, 16-byte aligned as in pc_edge_load); returns how many of the two exist
+__device__ __forceinline__ int pc_cc_load(const double* __restrict__ vals, int64_t i, int64_t Lp, double& a, double& b) {
+    a = b = 0.0;
+    if (i + 1 < Lp) {
+        const double2 v = *reinterpret_cast<const double2*>(vals + i);
+        a = v.x; b = v.y;
+        return 2;
+    }
+    if (i < Lp) { a = vals[i]; return 1; }
+    return 0;
+}
+
+__device__ __forceinline__ int pc_cc_read(int32_t* parent, int x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root above x, halving the path on the way: a node v whose parent p is not a root gets its grandparent (atomicMin on a
+// non-root only -- p < v was read, so by I2 v is none; gp < p by I1: the word decreases)
+__device__ __forceinline__ int pc_cc_find(int32_t* parent, int x) {
+    int v = x, p = pc_cc_read(parent, v);
+    while (p != v) {
+        const int gp = pc_cc_read(parent, p);
+        if (gp != p) atomicMin(parent + v, gp);
+        v = p; p = gp;
+    }
+    return v;
+}
+
+__device__ __forceinline__ void pc_cc_unite(int32_t* parent, int x, int y) {
+    int a = pc_cc_find(parent, x), b = pc_cc_find(parent, y);
+    while (a != b) {                                   // (most pairs of a dense component never enter)
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        const int was = atomicCAS(parent + hi, hi, lo);
+        if (was == hi) break;                          // hooked: hi was a root, and is none from now on
+        a = pc_cc_find(parent, was);                   // somebody else hooked hi (or the walk read a stale root): was < hi is its parent
+        b = pc_cc_find(parent, lo);                    // a, b < hi: the larger root descends with every round
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cc_init(int32_t* __restrict__ parent, int n, unsigned long long* __restrict__ n_pass) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g < n) parent[g] = g;
+    if (g == 0) *n_pass = 0ull;
+}
+
+template <int DIST, int STRICT>
+__global__ __launch_bounds__(CC_THREADS) void k_cc_union(const double* __restrict__ vals, int64_t Lp, double thr, PcShard sh,
+                                                         int32_t* parent, unsigned long long* n_pass) {
+    __shared__ uint32_t wsum[CC_THREADS / 64];
+    __shared__ int k_first;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * CC_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    uint32_t n = 0;                                    // the wave's count (the same in every lane)
+    uint32_t pass_a = 0, pass_b = 0;
+#pragma unroll
+    for (int j = 0; j < CC_ITERS; ++j) {
+        double a, b;
+        const int have = pc_cc_load(vals, base + (int64_t)j * CC_STRIDE, Lp, a, b);
+        const bool pa = have > 0 && pc_cc_pass<DIST, STRICT>(a, thr), pb = have > 1 && pc_cc_pass<DIST, STRICT>(b, thr);
+        n += (uint32_t)__popcll(__ballot(pa)) + (uint32_t)__popcll(__ballot(pb));
+        pass_a |= (uint32_t)pa << j; pass_b |= (uint32_t)pb << j;
+    }
+    if (lane == 0) wsum[wv] = n;
+    if (threadIdx.x == 0) {
+        // the row of the chunk's first element: lbase[k] <= i0 < lbase[k + 1] (lbase[0] = 0 <= i0 < Lp = lbase[nown]); rows of
+        // length 0 repeat an lbase value and can never be the answer
+        int lo = 0, hi = sh.nown;
+        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (sh.lbase[mid] <= i0) lo = mid; else hi = mid; }
+        k_first = lo;
+    }
+    __syncthreads();
+    uint32_t tot = 0;
+#pragma unroll
+    for (int w = 0; w < CC_THREADS / 64; ++w) tot += wsum[w];
+    if (tot == 0) return;                              // (the whole workgroup)
+    if (threadIdx.x == 0) atomicAdd(n_pass, (unsigned long long)tot);
+    if ((pass_a | pass_b) == 0) return;
+    int k = k_first;
+#pragma unroll 1
+    for (int j = 0; j < CC_ITERS; ++j) {
+        const int64_t i = base + (int64_t)j * CC_STRIDE;
+        if ((pass_a >> j) & 1u) {                      // (a passing element lies below Lp = lbase[nown]: the walk stops at k + 1 <= nown)
+            while (i >= sh.lbase[k + 1]) ++k;
+            pc_cc_unite(parent, (int)(i - sh.lbase[k]), sh.owned[k]);
+        }
+        if ((pass_b >> j) & 1u) {
+            while (i + 1 >= sh.lbase[k + 1]) ++k;
+            pc_cc_unite(parent, (int)(i + 1 - sh.lbase[k]), sh.owned[k]);
+        }
+    }
+}
+
+// one round of pointer jumping (a launch of its own: plain accesses).  Thread g alone writes parent[g]; the grandparent it reads is
+// the old one or one already jumped, an ancestor either way, so a node of depth d is at depth <= ceil(d / 2) afterwards.
+__global__ __launch_bounds__(256) void k_cc_labels(int32_t* parent, int32_t* __restrict__ labels, int n) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const int r = parent[parent[g]];
+    parent[g] = r;
+    labels[g] = r;
+}
+
+static int cc_check(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+int pc_launch_cc_init(int32_t* parent, int n, unsigned long long* n_pass, hipStream_t st) {
+    hipLaunchKernelGGL(k_cc_init, dim3((unsigned)((std::max(n, 1) + 255) / 256)), dim3(256), 0, st, parent, n, n_pass);
+    return cc_check("k_cc_init");
+}
+
+// sh: the slab's shard (owned / lbase on the device, nown targets); parent: [N], N above every owned target
+int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, const PcShard& sh, int32_t* parent,
+                       unsigned long long* n_pass, hipStream_t st) {
+    if (Lp <= 0) return PC_OK;
+    const dim3 grid((unsigned)((Lp + CC_CHUNK - 1) / CC_CHUNK)), block(CC_THREADS);
+    if (as_distance && strict) hipLaunchKernelGGL((k_cc_union<1, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
+    else if (as_distance) hipLaunchKernelGGL((k_cc_union<1, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
+    else if (strict) hipLaunchKernelGGL((k_cc_union<0, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
+    else hipLaunchKernelGGL((k_cc_union<0, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
+    return cc_check("k_cc_union");
+}
+
+// depth <= n - 1 before; ceil(log2 n) halvings leave depth <= 1, and the last round's labels read two levels up: the root
+int pc_launch_cc_labels(int32_t* parent, int32_t* labels, int n, hipStream_t st) {
+    if (n <= 0) return PC_OK;
+    int rounds = 1;
+    while ((1 << rounds) < n && rounds < 31) ++rounds;
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(k_cc_labels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parent, labels, n);
+        const int rc = cc_check("k_cc_labels");
+        if (rc != PC_OK) return rc;
+    }
+    return PC_OK;
+}

@@ -455,6 +455,127 @@ extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_
     return PC_OK;
 }
 
+// ---- components fill: the connected components of the graph {pairs that pass the threshold} -- with a strict distance predicate the
+// reference's single-linkage clusters at that eps (clustering.py:4-51) -- as labels[N], the smallest member's index.  pc_fill_edges'
+// walk (the same cut, the same shard install, the same restore; the loop is written out a second time so that pc_fill_edges stays
+// as it is), but each filled slab goes through ONE pass, k_cc_union (pc_components.hip), over a parent[N] array that stays on the
+// device from the first slab to the last; nothing is read back per slab.  After the last slab: k_cc_labels, then one D2H of
+// labels[N] and the 8-byte count of passing pairs behind them.
+extern "C" int pc_fill_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
+                                  const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (labels) *labels = nullptr;
+    if (n_components) *n_components = 0;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_components: upload first"); return PC_ERR_STATE; }
+    if (!labels || !n_components || !n_edges || !n_slabs) { pc_set_error("pc_fill_components: an output pointer is NULL"); return PC_ERR_ARG; }
+    if (metric < PC_GCS || metric > PC_AAI_PPOS) { pc_set_error("pc_fill_components: metric %d", metric); return PC_ERR_ARG; }
+    if (threshold != threshold) { pc_set_error("pc_fill_components: the threshold is NaN"); return PC_ERR_ARG; }
+    if (slab_bytes < 0) { pc_set_error("pc_fill_components: slab_bytes %lld", (long long)slab_bytes); return PC_ERR_ARG; }
+    if (c->world != 1) { pc_set_error("pc_fill_components: context is sharded (%d/%d); a components fill is a one-GPU call on an unsharded context", c->rank, c->world); return PC_ERR_STATE; }
+    if (metric >= PC_AAI && !c->residues_ready) { pc_set_error("pc_fill_components: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    PC_ON_DEVICE(c);
+    PcRange range("pc:fill_components");
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const int N = c->dev.N;
+    pc_stats sum; memset(&sum, 0, sizeof(sum));
+    c->last_cc_ms[0] = c->last_cc_ms[1] = 0.f;
+    as_distance = as_distance ? 1 : 0; strict = strict ? 1 : 0;
+    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffer is rewritten)
+    const size_t label_bytes = ((size_t)std::max(N, 1) * 4 + 7) / 8 * 8;    // the 64-bit count sits behind the labels, aligned
+    if ((rc = c->h_cc_labels.ensure(label_bytes + 8))) return rc;
+    int32_t* const h_labels = c->h_cc_labels.as<int32_t>();
+    if (N <= 1) {
+        if (N == 1) { h_labels[0] = 0; *n_components = 1; }
+        *labels = h_labels;
+        if (stats) *stats = sum;
+        return PC_OK;
+    }
+    // ---- the cut: pc_fill_edges' (ranges of targets whose pairs fit the slab)
+    const int64_t np = (int64_t)N * (N - 1) / 2;
+    int64_t max_pairs;
+    if (slab_bytes > 0) max_pairs = std::max<int64_t>(slab_bytes / 8, 1);
+    else {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
+        max_pairs = std::min<int64_t>(np, std::max<int64_t>((int64_t)((free_b + c->b_edge_slab.cap) / 4 / 8), 1));
+    }
+    max_pairs = std::min<int64_t>(max_pairs, PC_EDGE_MAX_PAIRS);
+    std::vector<uint64_t> per_target((size_t)N);
+    for (int t = 0; t < N; ++t) per_target[t] = (uint64_t)t;
+    const int nsl = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, nullptr, 0);
+    if (nsl < 0) return nsl;
+    std::vector<int32_t> cut((size_t)nsl + 1);
+    if ((rc = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, cut.data(), nsl + 1)) < 0) return rc;
+    auto pairs_below = [](int64_t t) { return t * (t - 1) / 2; };           // pairs (s, t'), s < t' < t
+    int64_t most = 1;
+    for (int i = 0; i < nsl; ++i) most = std::max(most, pairs_below(cut[i + 1]) - pairs_below(cut[i]));
+    if ((rc = c->b_edge_slab.ensure((size_t)most * 8)) || (rc = c->b_cc_parent.ensure((size_t)N * 4)) || (rc = c->b_cc_labels.ensure(label_bytes + 8))) return abi_rc(rc);
+    if (stats) for (hipEvent_t& e : c->ev_cc) if (!e) PC_HIP(hipEventCreate(&e));
+    double* const slab = c->b_edge_slab.as<double>();
+    int32_t* const parent = c->b_cc_parent.as<int32_t>();
+    unsigned long long* const d_pass = (unsigned long long*)((char*)c->b_cc_labels.p + label_bytes);
+    if ((rc = pc_launch_cc_init(parent, N, d_pass, st))) return rc;
+
+    EdgeShardScope restore(c);
+    std::vector<int32_t> owned; std::vector<int64_t> lbase;
+    bool pending = false;                                                   // a union pass is in flight (and, with stats, its two events recorded)
+    for (int i = 0; i < nsl; ++i) {
+        const int t0 = cut[i], t1 = cut[i + 1];
+        const int64_t Lp = pairs_below(t1) - pairs_below(t0);
+        if (Lp == 0) continue;                                              // (target 0 alone: no pair)
+        owned.resize((size_t)(t1 - t0)); lbase.resize((size_t)(t1 - t0) + 1);
+        for (int t = t0; t < t1; ++t) { owned[t - t0] = t; lbase[t - t0] = pairs_below(t) - pairs_below(t0); }
+        lbase[t1 - t0] = Lp;
+        // (a blocking copy into tables the previous slab's union pass may still read: wait for it)
+        if (pending) {
+            PC_HIP(hipStreamSynchronize(st));
+            c->busy = false;
+            if (stats) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_cc[0], c->ev_cc[1])); c->last_cc_ms[0] += x; }
+        }
+        if ((rc = upload_vec(c->b_edge_owned, owned)) || (rc = upload_vec(c->b_edge_lbase, lbase))) return rc;
+        c->plan.valid = false;
+        c->shard.nown = t1 - t0; c->shard.ident = 0;
+        c->shard.owned = c->b_edge_owned.as<int32_t>(); c->shard.lbase = c->b_edge_lbase.as<int64_t>();
+        c->h_owned = owned; c->h_lbase = lbase; c->shard_pairs = Lp;
+        pc_stats one; memset(&one, 0, sizeof(one));
+        if ((rc = fill_impl(c, metric, as_distance, slab, 0, st, stats ? &one : nullptr))) return rc;
+        sum.n_pairs += Lp; sum.n_alignments += one.n_alignments; sum.n_cells += one.n_cells; sum.n_tasks += one.n_tasks;
+        sum.n_residue_bytes += one.n_residue_bytes; sum.n_align_launches += one.n_align_launches; sum.n_chunks += one.n_chunks;
+        sum.ms_total += one.ms_total; sum.ms_plan += one.ms_plan; sum.ms_align += one.ms_align; sum.ms_reduce += one.ms_reduce;
+        sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
+        if (stats) PC_HIP(hipEventRecord(c->ev_cc[0], st));
+        if ((rc = pc_launch_cc_union(slab, Lp, as_distance, strict, threshold, c->shard, parent, d_pass, st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_cc[1], st));
+        pending = true;
+    }
+    if (stats) PC_HIP(hipEventRecord(c->ev_cc[2], st));
+    if ((rc = pc_launch_cc_labels(parent, c->b_cc_labels.as<int32_t>(), N, st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_cc[3], st));
+    PC_HIP(hipMemcpyAsync(h_labels, c->b_cc_labels.p, label_bytes + 8, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if (stats) {
+        if (pending) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_cc[0], c->ev_cc[1])); c->last_cc_ms[0] += x; }   // (the last slab's pass)
+        PC_HIP(hipEventElapsedTime(&c->last_cc_ms[1], c->ev_cc[2], c->ev_cc[3]));
+    }
+    int32_t comps = 0;
+    for (int g = 0; g < N; ++g) comps += h_labels[g] == g;
+    unsigned long long passed = 0;
+    memcpy(&passed, (const char*)h_labels + label_bytes, 8);
+    *labels = h_labels; *n_components = comps; *n_edges = (int64_t)passed; *n_slabs = nsl;
+    if (stats) *stats = sum;
+    return PC_OK;
+}
+
+extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* ms_labels) {
+    if (!c) { pc_set_error("pc_last_component_times: NULL context"); return PC_ERR_ARG; }
+    if (ms_union) *ms_union = c->last_cc_ms[0];
+    if (ms_labels) *ms_labels = c->last_cc_ms[1];
+    return PC_OK;
+}
+
 extern "C" int pc_assemble_dev(pc_ctx* c, const void* gathered_dev, int world, void* out_condensed_dev, void* stream) {
     if (!c || !c->uploaded) { pc_set_error("pc_assemble_dev: upload first"); return PC_ERR_STATE; }
     if (world != c->world) { pc_set_error("pc_assemble_dev: world %d != shard world %d", world, c->world); return PC_ERR_ARG; }

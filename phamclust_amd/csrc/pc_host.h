@@ -118,6 +118,11 @@ struct pc_ctx {
     PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
     hipEvent_t ev_edge[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_edges that is asked for stats
     float last_edge_ms[2] = {0.f, 0.f};     // count + scan + emit, edges' D2H of the last pc_fill_edges with stats (pc_last_edge_times)
+    // pc_fill_components: parent[N], labels[N] + the 8-byte count of passing pairs behind them (one D2H), and their pinned host image
+    DevBuf b_cc_parent, b_cc_labels;
+    PinnedBuf h_cc_labels;                  // the labels lent out by pc_fill_components
+    hipEvent_t ev_cc[4] = {nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_components that is asked for stats
+    float last_cc_ms[2] = {0.f, 0.f};       // union passes, labels pass of the last pc_fill_components with stats (pc_last_component_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {

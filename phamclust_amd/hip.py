@@ -72,7 +72,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_plan_dev", "pc_align_slice_dev", "pc_reduce_dev", "pc_upload_sets", "pc_upload_residues", "pc_set_plan_budget", "pc_chunk_plan",
            "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
-           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times"]
+           "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times",
+           "pc_fill_components", "pc_last_component_times"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -134,6 +135,9 @@ def load():
     L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                 ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_edge_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_fill_components.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_component_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -444,6 +448,41 @@ class Context:
         a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._lib.pc_last_edge_times(self._h, ctypes.byref(a), ctypes.byref(b)))
         return (*out, dict(stats.as_dict(), n_edges=int(n.value), n_slabs=int(nsl.value), ms_compact=float(a.value), ms_d2h=float(b.value)))
+
+    def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The connected components of the graph whose edges are the pairs that pass ``threshold`` -- ``d < threshold`` for a
+        distance fill (``d <= threshold`` with ``strict=False``), ``sim > threshold`` (``>=``) for a similarity fill -- as
+        ``labels``: int32[N], ``labels[g]`` = the smallest genome index of g's component.  On distances with ``strict`` these are the
+        single-linkage clusters at ``eps = threshold``.  Neither the dense matrix nor an edge list is delivered; the matrix is held
+        in HBM ``slab_bytes`` at a time (0 = automatic), as by :meth:`fill_edges`.  The array is a copy; ``borrow=True`` lends the
+        context's page-locked memory instead, on ``fill(borrow=True)``'s terms.  ``want_stats`` adds the fills' summed stats with
+        ``n_components``, ``n_edges`` (pairs that passed), ``n_slabs``, ``ms_union`` and ``ms_labels``."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        self._invalidate_loans()
+        pl = _i32p()
+        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_fill_components(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(bool(strict)),
+                                                 int(slab_bytes), ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl),
+                                                 ctypes.byref(stats)))
+        n = self.n_genomes
+        if n == 0 or not pl:
+            labels = np.empty(0, dtype=np.int32)
+        else:
+            labels = np.ctypeslib.as_array(pl, shape=(n,))
+            if borrow:
+                labels.flags.writeable = False
+                labels = BorrowedArray(labels, self)
+                self._loans.append(weakref.ref(labels))
+            else:
+                labels = labels.copy()
+        if not want_stats:
+            return labels
+        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.pc_last_component_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return labels, dict(stats.as_dict(), n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value),
+                            ms_union=float(a.value), ms_labels=float(b.value))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -723,6 +723,28 @@ class SparseEdges:
         ranked = other[np.argsort(w if self.is_distance else -w, kind="stable")]
         return [self.nodes[j] for j in ranked]
 
+    def components(self, threshold=None, strict=True):
+        """Connected components of the graph over ``nodes`` whose edges are this list's pairs within ``threshold`` -- ``weight <
+        threshold`` on distances, ``> threshold`` on similarities; ``<=`` / ``>=`` with ``strict=False``; ``None``: every pair
+        of the list -- as int32 labels, ``labels[g]`` = the smallest index of g's component.  On distances with ``strict`` these are
+        the single-linkage clusters at ``eps = threshold`` (scikit-learn merges below its ``distance_threshold``, never at it).  Host
+        arithmetic (``scipy.sparse.csgraph``): the statement ``Context.fill_components`` is held to."""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        n = len(self.nodes)
+        if threshold is None:
+            keep = np.ones(len(self), dtype=bool)
+        elif self.is_distance:
+            keep = self.weight < threshold if strict else self.weight <= threshold
+        else:
+            keep = self.weight > threshold if strict else self.weight >= threshold
+        src, tgt = self.source[keep], self.target[keep]
+        graph = coo_matrix((np.ones(src.shape[0], dtype=np.int8), (src, tgt)), shape=(n, n))
+        _, comp = connected_components(graph, directed=False)
+        smallest = np.full(int(comp.max()) + 1 if n else 0, n, dtype=np.int64)
+        np.minimum.at(smallest, comp, np.arange(n))
+        return smallest[comp].astype(np.int32)
+
     def inverted(self):
         """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SymMatrix.invert`` does (matrix.py:236-247)."""
         return SparseEdges(self.nodes, self.source, self.target, np.round(1.0 - self.weight, 6), is_distance=not self.is_distance,
@@ -770,6 +792,76 @@ def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
     logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} of {packed.n_pairs} edges in {stats['n_slabs']} slab(s) on one device: "
                   f"pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+compact+D2H {t3 - t2:.3f} s (kernels {stats['ms_total']:.3f} ms)")
     return SparseEdges([g.name for g in genomes], src, tgt, val, is_distance=as_distance, threshold=threshold)
+
+
+class Components:
+    """A partition of ``nodes`` into connected components: ``labels[g]`` is the smallest index of g's component (what
+    ``Context.fill_components`` and ``SparseEdges.components`` deliver)."""
+
+    def __init__(self, nodes, labels):
+        self.nodes = list(nodes)
+        self.labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if self.labels.shape != (len(self.nodes),):
+            raise ValueError("labels must hold one entry per node")
+        at = np.arange(len(self.nodes))
+        if len(self.nodes) and not ((self.labels >= 0).all() and (self.labels <= at).all() and (self.labels[self.labels] == self.labels).all()):
+            raise ValueError("labels[g] must be the smallest index of g's component")
+
+    @property
+    def n_components(self):
+        return int((self.labels == np.arange(len(self.nodes))).sum())
+
+    def __len__(self):
+        return self.n_components
+
+    def group_indices(self):
+        """The components as index arrays in the order ``hierarchical_clustering`` returns its parts: largest first, equal sizes
+        in order of their smallest member (``sorted(parts, reverse=True)`` over first-appearance order: Python's reverse sort is
+        stable), members ascending."""
+        order = np.argsort(self.labels, kind="stable")                         # grouped by label = by smallest member, members ascending
+        roots, starts = np.unique(self.labels[order], return_index=True)
+        groups = np.split(order, starts[1:]) if len(roots) else []
+        return sorted(groups, key=len, reverse=True)
+
+    def groups(self):
+        """The same as lists of node names."""
+        return [[self.nodes[i] for i in group.tolist()] for group in self.group_indices()]
+
+
+def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, slab_bytes=0):
+    """The connected components of the graph {pairs of ``matrix_de_novo(genomes, func, cpus, as_distance)`` within ``threshold``}
+    (``<`` on distances, ``>`` on similarities; ``<=`` / ``>=`` with ``strict=False``) as a :class:`Components`, by
+    ``Context.fill_components``: neither the dense matrix nor an edge list leaves the GPU, only the N labels.  On distances with
+    ``strict`` the groups are ``hierarchical_clustering(matrix, "single", eps=threshold)``'s.  ``func`` must be one of the six
+    ``METRICS`` callables (no CPU route: ``SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)`` serves another
+    callable).  One GPU, as ``edges_de_novo``: under a launcher (``WORLD_SIZE`` > 1) it raises."""
+    if len(genomes) == 0:
+        raise ValueError("need at least 1 genome to construct components de novo")
+    metric = _metric_name(func)
+    if metric is None:
+        raise ValueError("components_de_novo: func must be one of the six METRICS callables -- the components fill runs on the GPU only and has "
+                         "no CPU route (for another callable: SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold))")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("components_de_novo: the components fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+    import time
+    devices = in_process_devices()
+    if devices:
+        logging.debug(f"components_de_novo: the components fill is a one-GPU call: using device {devices[0]} of {devices}")
+    t0 = time.perf_counter()
+    packed = _packed_of(genomes)
+    t1 = time.perf_counter()
+    ctx = get_context(devices[0] if devices else None)
+    ctx.upload(packed, residues=metric in ("aai", "peq"))
+    t2 = time.perf_counter()
+    labels, stats = ctx.fill_components(metric, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes, want_stats=True)
+    t3 = time.perf_counter()
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=1, rank=0,
+                     pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
+    logging.debug(f"{len(genomes)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {packed.n_pairs} pairs in "
+                  f"{stats['n_slabs']} slab(s) on one device: pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+union+labels {t3 - t2:.3f} s "
+                  f"(kernels {stats['ms_total']:.3f} ms)")
+    return Components([g.name for g in genomes], labels)
 
 
 def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
+from phamclust_amd.matrix import components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -231,6 +231,34 @@ class _Run:
         log.info(f"wrote {target.name}")
         return edges
 
+    # 2, --components-only
+    def components(self, similarity):
+        """Stage 2 as a components fill: genomes are joined when their distance is below ``round(1 - similarity, 6)`` -- the
+        single-linkage groups at that eps -- and only ``components_<metric>.tsv`` is written: ``name<TAB>number`` in genome order,
+        number 1 for the largest group (``Components.groups()``'s order).  No matrix, no edge list, nothing cached or clustered."""
+        self.banner(2, f"{self.metric} components (components fill)")
+        t0 = time.perf_counter()
+        distance = round(1.0 - similarity, 6)
+        found = components_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True, strict=True)
+        st = _matrix.LAST_FILL
+        groups = found.group_indices()
+        log.info(f"{len(self.genomes):,} genomes, {st.get('n_edges', 0):,} of {st.get('genome_pairs', 0):,} pairs within distance < {distance:.6f}: "
+                 f"{len(groups):,} components, the largest of {len(groups[0]) if groups else 0:,}, from {st.get('n_slabs', 1)} slab(s) on 1 GPU in "
+                 f"{time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, fill+union+labels "
+                 f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, union {st.get('ms_union', 0.0):.3f} ms, labels "
+                 f"{st.get('ms_labels', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        number = [0] * len(found.nodes)
+        for k, group in enumerate(groups, start=1):
+            for i in group.tolist():
+                number[i] = k
+        target = self.outdir / f"components_{self.metric}.tsv"
+        with open(target, "w") as handle:
+            handle.writelines(f"{name}\t{k}\n" for name, k in zip(found.nodes, number))
+        log.info(f"wrote {target.name}")
+        return found
+
     def extended(self, cpus, t0):
         """Stage 2 under --extend: the old matrix's block is kept, the rows of the genomes it lacks are filled (matrix_extend)."""
         try:
@@ -313,14 +341,19 @@ class _Run:
 
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
-              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None):
+              sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
+              components_only=False):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
-    edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file."""
+    edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
+    ``components_only``: stop after a components fill -- genomes joined when distance < round(1 - ``edge_thresh``, 6), None: 0.0 --
+    and write only ``components_<metric>.tsv``."""
     if adjacency_only and extend is not None:
         raise ValueError("adjacency_only cannot be combined with extend")
-    if edge_thresh is not None and not adjacency_only:
-        raise ValueError("edge_thresh selects the edges of adjacency_only")
+    if components_only and (adjacency_only or extend is not None):
+        raise ValueError("components_only cannot be combined with adjacency_only or extend")
+    if edge_thresh is not None and not (adjacency_only or components_only):
+        raise ValueError("edge_thresh selects the edges of adjacency_only or components_only")
     if nr_distance >= clu_distance:          # pre-grouping must be tighter than clustering, else switch it off
         nr_distance = 0.0
     settings = dict(infile=infile, outdir=outdir, metric=metric, nr=(nr_distance, nr_linkage), clu=(clu_distance, clu_linkage),
@@ -330,6 +363,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["extend"] = extend
     if adjacency_only:
         settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}")
+    if components_only:
+        settings["components"] = f"only, joined at similarity > {0.0 if edge_thresh is None else edge_thresh}"
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
@@ -344,6 +379,13 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             sys.exit(1)
         run.adjacency(edge_thresh)
         run.banner(3, "done (--adjacency-only: no clustering)")
+        return
+    if components_only:
+        if run.world > 1:
+            log.error("--components-only is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.components(0.0 if edge_thresh is None else edge_thresh)
+        run.banner(3, "done (--components-only: no clustering)")
         return
     matrix = run.distances(cpus)
     if matrix is None:                        # ranks other than 0 are done once their shard is gathered
@@ -408,6 +450,10 @@ def _run(args, argv):
         # the edge-list fill is a one-GPU call too (pc_fill_edges refuses a sharded context)
         gpus_note = "--adjacency-only fills an edge list, which is a one-GPU call: the matrix stage stays on one GPU"
         os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
+    elif args.gpus > 1 and world == 1 and args.components_only:
+        # and so is the components fill (pc_fill_components refuses a sharded context)
+        gpus_note = "--components-only fills component labels, which is a one-GPU call: the matrix stage stays on one GPU"
+        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
     elif args.gpus > 1 and world == 1 and args.extend is not None:
         # the rows fill of --extend is a one-GPU call (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
         gpus_note = "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
@@ -460,7 +506,7 @@ def _run(args, argv):
                   sub_distance=as_distance(args.sub_thresh), sub_linkage=args.sub_linkage, k_min=max(1, args.k_min),
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
-                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh)
+                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
