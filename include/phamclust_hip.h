@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 157   /* 0.5.6: pc_fill_components */
+#define PC_VERSION 158   /* 0.5.7: pc_fill_groups */
 
 typedef enum {
     PC_OK = 0,
@@ -191,6 +191,40 @@ int pc_fill_shard_dev(pc_ctx* ctx, int metric, int as_distance, void* shard_dev,
  */
 int pc_fill_rows(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, double* out_host, pc_stats* stats);
 int pc_fill_rows_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows, void* out_dev, void* stream, pc_stats* stats);
+
+/*
+ * Groups fill: every within-group pair of a family of groups in one call.  The reference takes the sub-matrix of a group out of
+ * the dense matrix (SymMatrix.extract_submatrix, matrix.py:155-167; the pipeline's per-cluster matrices, scripts/phamclust.py:300-317);
+ * this call fills the blocks alone: the pairs (s, t), s < t, whose two genomes lie in the same group -- sum of n_c (n_c - 1) / 2
+ * pairs instead of N (N - 1) / 2 -- from one upload, with one plan (per chunk) that merges duplicate sequence pairs across ALL groups.
+ * members[M]: genome indices, group by group; group_off[n_groups + 1]: group c is members[group_off[c] .. group_off[c + 1]).  Inside
+ * a group the members are strictly ascending, so the smaller index is the reference's `source` as in the whole fill (aai is not
+ * symmetric); groups may share genomes; a group of 0 or 1 members has no pair.
+ * out: the groups' condensed triangles end to end, f64[L]: pair (i, j), i < j, of group c (positions inside the group, n its size)
+ * sits at pair_off[c] + i n - i (i + 1) / 2 + (j - i - 1), pair_off[c] = sum over c' < c of n_c' (n_c' - 1) / 2, L = pair_off[n_groups]
+ * (scipy's condensed order per group; pc_group_pair_offsets).  All pair indices are 64-bit.  Values are the whole fill's, bit for
+ * bit.  The six metrics and PC_AAI_PPOS.  gcs / jc / pocp / af always run on the groups walker: no selector, and pc_last_set_kernel /
+ * pc_last_set_launch keep reporting the last whole fill.  aai / peq are cut into successive ranges of row blocks (32 positions) under
+ * the rule of pc_set_plan_budget, the 8 bytes per slot of the per-pair count / offset arrays counting against the budget as in a rows
+ * fill; same values whatever the cut.  stats: n_pairs = L; n_alignments, n_cells, n_residue_bytes summed over the slots (a pair that
+ * sits in two groups counts twice); n_distinct_* per plan; n_chunks and the times as for a rows fill; pc_last_plan_tasks covers a
+ * groups fill too.
+ * PC_OK, nothing written: n_groups == 0 or L == 0.  PC_ERR_ARG: bad metric; a NULL pointer with L > 0; group_off[0] != 0; group_off
+ * decreasing; a member out of range; a group not strictly ascending; M > 2^31-1.  PC_ERR_STATE: before upload, on a sharded context
+ * (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA: as a whole fill.  pc_fill_groups delivers into host memory;
+ * pc_fill_groups_dev leaves the result in HBM (out_dev: device f64[L]; stream as for pc_fill_dev).
+ */
+int pc_fill_groups(pc_ctx* ctx, int metric, int as_distance, const int32_t* members, const int64_t* group_off, int n_groups,
+                   double* out_host, pc_stats* stats);
+int pc_fill_groups_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* members, const int64_t* group_off, int n_groups,
+                       void* out_dev, void* stream, pc_stats* stats);
+/* Host arithmetic of the groups domain (no GPU; exported for tests, as pc_chunk_plan is).  pc_group_pair_offsets writes pair_off
+ * [n_groups + 1] (NULL: nothing) and returns L.  pc_group_tiles lists the live 32 x 32 tiles over the M positions of the groups laid
+ * end to end -- (a, b), a <= b: some pair of one group has its first member in block a and its second in block b -- sorted by a,
+ * then b, writes at most cap of them (NULL arrays: none) and returns their number T.  Both return PC_ERR_ARG (negative) for
+ * group_off[0] != 0 or a decreasing group_off. */
+int64_t pc_group_pair_offsets(const int64_t* group_off, int n_groups, int64_t* pair_off);
+int64_t pc_group_tiles(const int64_t* group_off, int n_groups, int32_t* tile_row, int32_t* tile_col, int64_t cap);
 
 /*
  * Edge-list fill: the pairs within a threshold, without the dense matrix.  The reference knows this form of its result twice --

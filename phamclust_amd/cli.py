@@ -53,6 +53,10 @@ _OPTIONS = (
     (None, "-C", "--components-only", dict(action="store_true", help="stop after the matrix stage and write only components_<metric>.tsv, from a "
                                                                      "components fill: the single-linkage groups at --edge-thresh (genomes joined "
                                                                      "when distance < 1 - SIM); no matrix, no edge list, no clustering")),
+    (None, "-N", "--no-matrix", dict(action="store_true", help="cluster without the dense matrix: components fills find the groups, groups fills "
+                                                               "their sub-matrices (sum of n_c^2 cells, not N^2); same cluster_* / singletons "
+                                                               "output; the adjacency file comes from an edge-list fill; no "
+                                                               "pairwise_<metric>_similarities.tsv, no dataset heatmap, no matrix cache; one GPU")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -95,4 +99,10 @@ def parse_args(argv=None):
         parser.error("--components-only and --adjacency-only each stop after a fill of their own; give one of them")
     if args.components_only and args.extend is not None:
         parser.error("--components-only fills from scratch; it cannot be combined with --extend")
+    if args.no_matrix:
+        for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
+            if given:
+                parser.error(f"--no-matrix runs the whole pipeline without the dense matrix; it cannot be combined with {flag}")
+        if args.gpus > 1:
+            parser.error("--no-matrix: the components and groups fills are one-GPU calls; it cannot be combined with --gpus N")
     return args

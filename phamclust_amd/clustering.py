@@ -64,23 +64,36 @@ def cluster_by_component(groups, submatrix_of, linkage, eps, nodes=None):
 def hierarchical_clustering_de_novo(genomes, func, linkage, eps=None, cpus=1, n_clusters=None):
     """``hierarchical_clustering(matrix_de_novo(genomes, func, cpus), linkage, eps=eps)`` without the N x N matrix.
 
-    The connected components of {d < eps} come from one components fill on the GPU (``components_de_novo(genomes, func, eps,
-    strict=True)``: N labels cross PCIe); each component of two or more genomes is then filled by a ``matrix_de_novo`` of its own --
-    its genomes in their original relative order, so every pair keeps its orientation and its value bit for bit (aai included) -- and
-    clustered alone (``cluster_by_component``).  Memory is the sum of n_c^2 over the components, not N^2.
+    The connected components of {d < eps} come from one components fill on the GPU (``Context.fill_components``: N labels cross
+    PCIe); every component of two or more genomes is then filled by ONE groups fill over the same upload (``Context.fill_groups``:
+    the components' condensed triangles) -- its genomes in their original relative order, so every pair keeps its orientation and its
+    value bit for bit (aai included) -- and clustered alone (``cluster_by_component``).  One pack, one upload, two fills, whatever the
+    number of components; memory is the sum of n_c^2 over the components, not N^2.
 
     The result equals the dense route's as a list of node lists, order included: always for ``single``; for ``average`` and
     ``complete`` wherever the dense route's own result does not hinge on how scipy breaks a tie between two merges (that is every
     committed fixture).  ``ward`` and ``n_clusters=`` raise ``ValueError``: ward's height is not bounded below by a pair distance,
-    and a cluster count is a property of the whole dendrogram.  ``func`` must be one of the six ``METRICS`` callables; one GPU."""
+    and a cluster count is a property of the whole dendrogram.  ``func`` must be one of the six ``METRICS`` callables; one GPU.
+    ``cpus`` is accepted for signature compatibility only (nothing runs on a worker pool).  ``matrix.LAST_FILL`` afterwards holds the
+    groups fill's stats (``genome_pairs`` = the pairs it filled, ``groups``) beside ``n_components`` / ``n_edges`` / ``n_slabs`` /
+    ``ms_components`` of the components fill."""
     if n_clusters:
         raise ValueError("hierarchical_clustering_de_novo cuts at a distance threshold: n_clusters needs the whole dendrogram (the dense route)")
     if linkage == "ward":
         raise ValueError("hierarchical_clustering_de_novo: ward's merge height is not bounded below by a pair distance (the dense route serves it)")
     if eps is None:
         raise ValueError("need a distance threshold (eps) to proceed")
-    from phamclust_amd.matrix import components_de_novo, matrix_de_novo
-    components = components_de_novo(genomes, func, eps, as_distance=True, strict=True)
-    by_name = {g.name: g for g in genomes}
-    return cluster_by_component(components.groups(), lambda names: matrix_de_novo([by_name[name] for name in names], func, cpus, as_distance=True),
-                                linkage, eps, nodes=[g.name for g in genomes])
+    import time
+    from phamclust_amd import matrix as M
+    ctx, metric, names, record = M.upload_for_fills(genomes, func, "hierarchical_clustering_de_novo")
+    t0 = time.perf_counter()
+    labels, cc = ctx.fill_components(metric, eps, as_distance=True, strict=True, want_stats=True)
+    components = M.Components(names, labels)
+    groups = [g for g in components.group_indices() if len(g) > 1]
+    condensed, stats = ctx.fill_groups(metric, groups, as_distance=True, want_stats=True)
+    M.LAST_FILL.clear()                                  # the groups fill's counts; the components fill's under its own names
+    M.LAST_FILL.update(stats, metric=metric, n_genomes=len(names), genome_pairs=int(stats["n_pairs"]), groups=len(groups), n_gpus=1, rank=0,
+                       n_components=cc["n_components"], n_edges=cc["n_edges"], n_slabs=cc["n_slabs"], ms_components=cc["ms_total"],
+                       pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=time.perf_counter() - t0)
+    filled = {names[int(g[0])]: M.SymMatrix.from_condensed([names[i] for i in g.tolist()], values, is_distance=True) for g, values in zip(groups, condensed)}
+    return cluster_by_component(components.groups(), lambda group: filled[group[0]], linkage, eps, nodes=names)

@@ -271,27 +271,35 @@ static int count_per_target(pc_ctx* c, int condensed, hipStream_t st, std::vecto
 
 // Which walk a stage launches, over which slots: the owned targets [k0, k1) of the context's shard (k_walk; slot arrays indexed
 // by the shard-local pair index), or -- rows != NULL -- the query rows [k0, k1) of a rows fill (k_walk_rows; slot arrays
-// [k1 - k0][N], filled for that range alone).
-static int walk_domain(pc_ctx* c, int mode, const PcRows* rows, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
+// [k1 - k0][N], filled for that range alone), or -- groups != NULL -- the row blocks [k0, k1) of a groups fill (k_walk_groups; slot
+// arrays hold that range's slots, first slot block_slot[k0]).
+static int walk_domain(pc_ctx* c, int mode, const PcRows* rows, const PcGroupsHost* groups, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
     if (rows) return pc_launch_walk_rows(mode, c->dev, *rows, k0, k1, a, st);
+    if (groups) {
+        PcGroups sub = groups->dev;
+        sub.slot_base = groups->block_slot[k0];
+        return pc_launch_walk_groups(mode, c->dev, sub, groups->block_tile[k0], groups->block_tile[k1], a, st);
+    }
     PcShard sub = c->shard;
     sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
     return pc_launch_walk(mode, c->dev, sub, a, st);
 }
 
-// PLAN of the owned targets (or query rows) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
+// PLAN of the owned targets (or query rows, or row blocks of a groups fill) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
 // sorted by launch class.  Leaves its results in the context's work buffers and c->plan; two small read-backs.
-static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A, const PcRows* rows = nullptr) {
+static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A, const PcRows* rows = nullptr,
+                      const PcGroupsHost* groups = nullptr) {
     int rc = PC_OK;
     PcRange range("pc:plan");
     PlanningScope planning;
     const PcDev& d = c->dev;
     pc_ctx::PlanState& P = c->plan;
     P.valid = false; P.ppos = ppos; P.condensed = condensed; P.A = (int64_t)A; P.n_distinct = 0; P.ntasks = 0; P.tb.assign(c->nlc + 1, 0);
-    P.k0 = k0; P.k1 = k1; P.whole = !rows && c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
+    P.k0 = k0; P.k1 = k1; P.whole = !rows && !groups && c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
     memset(&P.st, 0, sizeof(P.st));
     pc_stats& local = P.st;
-    const int64_t base = rows ? 0 : c->h_lbase[k0], Lc = rows ? (int64_t)(k1 - k0) * d.N : c->h_lbase[k1] - base;
+    const int64_t base = (rows || groups) ? 0 : c->h_lbase[k0];
+    const int64_t Lc = rows ? (int64_t)(k1 - k0) * d.N : groups ? groups->block_slot[k1] - groups->block_slot[k0] : c->h_lbase[k1] - base;
     local.n_pairs = Lc;
     local.n_alignments = (int64_t)A;
     if (A > (uint64_t)PC_PLAN_MAX_ALIGNMENTS) {
@@ -323,7 +331,7 @@ static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0
         const int64_t tmp_elems = (int64_t)(c->b_scan_tmp.cap / 4);
         // 2 ENUM: one sort key per alignment slot; 3 sort; 4 distinct alignments, aliases, buckets (pc_plan.hip)
         a.key = c->b_key0.as<unsigned long long>(); a.val = c->b_val0.as<uint32_t>();
-        if ((rc = walk_domain(c, PCW_ENUM, rows, k0, k1, a, st))) return rc;
+        if ((rc = walk_domain(c, PCW_ENUM, rows, groups, k0, k1, a, st))) return rc;
         if ((rc = pc_sort_pairs(c->b_sort_tmp.p, c->b_sort_tmp.cap, c->b_key0.as<unsigned long long>(), c->b_key1.as<unsigned long long>(),
                                 c->b_val0.as<uint32_t>(), c->b_val1.as<uint32_t>(), An, key_bits, st))) return rc;
         if ((rc = pc_launch_mark_heads(c->b_key1.as<unsigned long long>(), c->b_flags.as<uint32_t>(), An, st))) return rc;
@@ -398,14 +406,15 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
 }
 
 // REDUCE: best match per anchor gene through the aliases, fp64 epilogue (metrics.py:204-232, 247-253), over the plan's targets
-static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcRows* rows = nullptr) {
+static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcRows* rows = nullptr,
+                        const PcGroupsHost* groups = nullptr) {
     PcRange range("pc:reduce");
     pc_ctx::PlanState& P = c->plan;
     if (!P.valid) { pc_set_error("reduce: no plan (pc_plan_dev first)"); return PC_ERR_STATE; }
     PcWalkArgs a; memset(&a, 0, sizeof(a));
     a.off = c->b_off.as<uint32_t>(); a.alias = c->b_alias.as<uint32_t>(); a.res = res; a.out = out;
     a.as_distance = as_distance ? 1 : 0; a.condensed = P.condensed;
-    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, rows, P.k0, P.k1, a, st);
+    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, rows, groups, P.k0, P.k1, a, st);
 }
 
 // a finished chunk: its plan's counts, and its tasks per launch class for pc_last_plan_tasks
@@ -499,16 +508,21 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
     return PC_OK;
 }
 
-// aai / peq of a rows fill (pc_fill_rows*): COUNT over every query row (totals, alignments per row), then plan -> align -> reduce over
-// successive ranges of the rows.  The ranges follow pc_chunk_plan over the rows' costs under the budget a whole fill has
-// (pc_set_plan_budget / PC_PLAN_BYTES, 2^31-2 alignments per plan, a failed allocation halves the range); a row costs its
-// alignments plus its N slots of na / off (8 bytes each, stated in alignments), so a request of many rows never holds more
-// than a chunk's worth of slot arrays.  `out` is the whole f64[n_rows][N]; the reduce of a range writes its rows and the mirror
-// cells of pairs of two queries.  Values do not depend on the cut: every pair's alignments stay in one range.
-int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
+// aai / peq over a domain that is cut into UNITS -- the query rows of a rows fill (pc_fill_rows*), the row blocks of TS positions of a
+// groups fill (pc_fill_groups*): COUNT over every unit (totals, alignments per unit: aln_t), then plan -> align -> reduce over successive
+// ranges of units.  The ranges follow pc_chunk_plan over the units' costs under the budget a whole fill has (pc_set_plan_budget /
+// PC_PLAN_BYTES, 2^31-2 alignments per plan, a failed allocation halves the range); a unit costs its alignments plus its slots of na /
+// off (8 bytes each, stated in alignments), so a request of many units never holds more than a range's worth of slot arrays.  A range of
+// units is a range of slots: N per query row; for row blocks block_slot[] says where (and a range of the tile list, block_tile[]).  One
+// plan per range merges the duplicate sequence pairs of everything the range touches.  `out` is the whole result; the reduce of a range
+// writes its cells (a rows fill: also the mirror cells of pairs of two queries).  Values do not depend on the cut: every pair's
+// alignments stay in one range.
+static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out,
+                              hipStream_t st, pc_stats& local, bool timed) {
     int rc = PC_OK;
     const PcDev& d = c->dev;
-    const int M = rows.nrows;
+    const int U = rows ? rows->nrows : groups->nblocks;
+    auto slots = [&](int k0, int k1) { return rows ? (int64_t)(k1 - k0) * d.N : groups->block_slot[k1] - groups->block_slot[k0]; };
     if (!c->residues_ready) { pc_set_error("fill: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
     if (d.G > 0 && c->min_gene_len == 0) {
         pc_set_error("fill: an empty translation cannot be aligned (aai/peq); the reference fails on it too"); return PC_ERR_DATA;
@@ -516,38 +530,44 @@ int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int a
     c->last_plan_tasks_valid = false;
     c->last_plan_tasks.assign(c->nlc, 0);
     c->plan.valid = false;
-    // COUNT over all rows: totals and aln_row (no slot array yet)
-    std::vector<uint64_t> cost(M);
+    // COUNT over all units: totals and alignments per unit (no slot array yet)
+    std::vector<uint64_t> own(U);
     {
         PcRange range("pc:count");
-        if ((rc = c->b_totals.ensure(64)) || (rc = c->b_aln_t.ensure((size_t)M * 8))) return rc;
+        if ((rc = c->b_totals.ensure(64)) || (rc = c->b_aln_t.ensure((size_t)std::max(U, 1) * 8))) return rc;
         PC_HIP(hipMemsetAsync(c->b_totals.p, 0, 64, st));
-        PC_HIP(hipMemsetAsync(c->b_aln_t.p, 0, (size_t)M * 8, st));
+        PC_HIP(hipMemsetAsync(c->b_aln_t.p, 0, (size_t)U * 8, st));
         PcWalkArgs a; memset(&a, 0, sizeof(a));
         a.totals = c->b_totals.as<unsigned long long>(); a.aln_t = c->b_aln_t.as<unsigned long long>();
-        if ((rc = pc_launch_walk_rows(PCW_COUNT, d, rows, 0, M, a, st))) return rc;
+        if ((rc = walk_domain(c, PCW_COUNT, rows, groups, 0, U, a, st))) return rc;
         uint64_t* h_tot = (uint64_t*)(c->h_plan.as<uint32_t>() + 1000);
         PC_HIP(hipMemcpyAsync(h_tot, c->b_totals.p, 24, hipMemcpyDeviceToHost, st));
-        PC_HIP(hipMemcpyAsync(cost.data(), c->b_aln_t.p, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipMemcpyAsync(own.data(), c->b_aln_t.p, (size_t)U * 8, hipMemcpyDeviceToHost, st));
         PC_HIP(hipStreamSynchronize(st));
         local.n_alignments = (int64_t)h_tot[0]; local.n_cells = (int64_t)h_tot[1]; local.n_residue_bytes = (int64_t)h_tot[2];
     }
     const uint64_t A = (uint64_t)local.n_alignments;
-    // a row's cost in alignments: its own + the 8 bytes per slot of its N entries of na / off
-    const uint64_t slot_cost = ((uint64_t)d.N * 8 + PC_PLAN_BYTES_PER_ALIGNMENT - 1) / PC_PLAN_BYTES_PER_ALIGNMENT;
-    for (uint64_t& x : cost) x += slot_cost;
+    // a unit's cost in alignments: its own + the 8 bytes per slot of its entries of na / off
+    std::vector<uint64_t> slot_cost(U), cost(U);
+    uint64_t all_slot_cost = 0;
+    for (int k = 0; k < U; ++k) {
+        slot_cost[k] = ((uint64_t)slots(k, k + 1) * 8 + PC_PLAN_BYTES_PER_ALIGNMENT - 1) / PC_PLAN_BYTES_PER_ALIGNMENT;
+        cost[k] = own[k] + slot_cost[k];
+        all_slot_cost += slot_cost[k];
+    }
     uint64_t max_aln = (uint64_t)PC_PLAN_MAX_ALIGNMENTS;
-    if (c->plan_budget > 0 || (A + slot_cost * (uint64_t)M) * PC_PLAN_BYTES_PER_ALIGNMENT > ((uint64_t)1 << 30))
+    if (c->plan_budget > 0 || (A + all_slot_cost) * PC_PLAN_BYTES_PER_ALIGNMENT > ((uint64_t)1 << 30))
         max_aln = std::min<uint64_t>(max_aln, (uint64_t)std::max<int64_t>(plan_budget_bytes(c) / PC_PLAN_BYTES_PER_ALIGNMENT, 1));
     float ms_plan = 0.f, ms_align = 0.f, ms_reduce = 0.f;
     int k = 0, nchunks = 0;
-    while (k < M) {
+    while (k < U) {
         int32_t cut[2] = {0, 0};
-        if ((rc = pc_chunk_plan(cost.data() + k, M - k, max_aln, cut, 2)) < 0) return rc;
+        if ((rc = pc_chunk_plan(cost.data() + k, U - k, max_aln, cut, 2)) < 0) return rc;
         const int k1 = k + cut[1];
-        const int64_t Lc = (int64_t)(k1 - k) * d.N;
-        uint64_t run = 0;
-        for (int i = k; i < k1; ++i) run += cost[i] - slot_cost;
+        const int64_t Lc = slots(k, k1);
+        uint64_t run = 0, run_slot_cost = 0;
+        for (int i = k; i < k1; ++i) { run += own[i]; run_slot_cost += slot_cost[i]; }
+        if (Lc == 0) { k = k1; continue; }                                    // (row blocks of one-member groups: no slot, no tile)
         if (timed) PC_HIP(hipEventRecord(c->ev[4], st));
         // the range's own COUNT: alignments per slot (its totals go to scratch words nobody reads)
         rc = c->b_na.ensure((Lc + 1) * 4);
@@ -556,16 +576,16 @@ int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int a
             PC_HIP(hipMemsetAsync(c->b_na.p, 0, (Lc + 1) * 4, st));
             PcWalkArgs a; memset(&a, 0, sizeof(a));
             a.na = c->b_na.as<uint32_t>(); a.totals = c->b_totals.as<unsigned long long>() + 5;
-            rc = pc_launch_walk_rows(PCW_COUNT, d, rows, k, k1, a, st);
+            rc = walk_domain(c, PCW_COUNT, rows, groups, k, k1, a, st);
         }
-        if (rc == PC_OK) rc = stage_plan(c, ppos, 0, st, k, k1, run, &rows);
+        if (rc == PC_OK) rc = stage_plan(c, ppos, 0, st, k, k1, run, rows, groups);
         if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
-        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, &rows); }
+        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, rows, groups); }
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller range, not an error
             PC_HIP(hipStreamSynchronize(st));
             release_plan_buffers(c);
             c->b_scratch.release(); c->b_na.release(); c->b_off.release();
-            max_aln = std::max<uint64_t>(std::min(max_aln, run + slot_cost * (uint64_t)(k1 - k)) / 2, 1);
+            max_aln = std::max<uint64_t>(std::min(max_aln, run + run_slot_cost) / 2, 1);
             continue;
         }
         if (rc != PC_OK) return rc;
@@ -580,11 +600,20 @@ int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int a
         }
         ++nchunks; k = k1;
     }
-    c->plan.valid = false;                                                // a rows plan serves no later stage
+    c->plan.valid = false;                                                // such a plan serves no later stage
     local.n_chunks = nchunks;
     c->last_plan_tasks_valid = true;
     local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;
     return PC_OK;
+}
+
+// a rows fill: the units are the query rows; out: f64[rows.nrows][N]
+int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
+    return fill_units_aligned(c, &rows, nullptr, metric, ppos, as_distance, out, st, local, timed);
+}
+// a groups fill: the units are the row blocks of TS positions; out: f64[L]
+int fill_groups_aligned(pc_ctx* c, const PcGroupsHost& groups, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
+    return fill_units_aligned(c, nullptr, &groups, metric, ppos, as_distance, out, st, local, timed);
 }
 
 

@@ -64,6 +64,19 @@ struct PcRows {
     const int32_t* row_of;            // [N] position of genome g in rows, or -1
 };
 
+// Pair domain of a groups fill: every pair of two positions p < q of one group, over the members of a family of groups laid
+// end to end (k_walk_groups).  Members ascend inside a group, so the genome at p is the pair's source and the one at q its target.
+#define PC_GROUP_TILE 32      // positions per tile edge: the walkers' TS (pc_pairs.h), named here for the host units that list the tiles
+struct PcGroups {
+    int32_t M, pad_;                  // positions (members over all groups)
+    const int32_t* pos_genome;        // [M] genome at position p
+    const int32_t* pos_end;           // [M] end position of p's group: slot (p, q) is live iff p < q < pos_end[p]
+    const int64_t* pos_rowbase;       // [M+1] output index of p's first pair; slot (p, q) = pos_rowbase[p] + q - p - 1; [M] = L
+    const int32_t* tile_row;          // [T] the live TS x TS tiles over positions (row block a, column block b >= a), sorted by a, then b
+    const int32_t* tile_col;          // [T]
+    int64_t slot_base;                // first slot the na / off arrays of this launch hold (a range of row blocks is a range of slots)
+};
+
 // One wave task of the alignment kernels: column gene + a range of its bucket.
 struct PcTask { int32_t gene, begin, end, pad; };   // pad: launch class of the task (planning only)
 
@@ -85,7 +98,7 @@ struct PcTaskPlan {
 
 // walker modes (pc_walk.hip)
 enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5,
-       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows only (whole fills count gcs / jc on the tile kernels)
+       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows / k_walk_groups only (whole fills count gcs / jc on the tile kernels)
 enum { PCW_SPARSE_GCS = 10, PCW_SPARSE_JC = 11 };   // k_sparse_tile64 only: shared-pham counts, one direction
 
 struct PcWalkArgs {
@@ -94,9 +107,10 @@ struct PcWalkArgs {
     unsigned long long* totals;       // [0] alignments [1] cells [2] residue bytes (as the reference would run them)
     unsigned long long* cost_t;       // [N] or NULL: DP cells per target genome (input of the cost-balanced deal)
     unsigned long long* aln_t;        // [N] or NULL: alignments per target genome (where a fill that exceeds its memory budget is cut);
-                                      //   k_walk_rows: [nrows], alignments per query row (aln_row)
+                                      //   k_walk_rows: [nrows], alignments per query row (aln_row); k_walk_groups: per row block of positions
     // ENUM: alignment slot k of a pair = off[pair] + its position in the reference's loop order
-    const uint32_t* off;              // [Lp] exclusive scan of na   (k_walk_rows: na / off are [rows of the range][N], slot (k - kb) * N + g)
+    const uint32_t* off;              // [Lp] exclusive scan of na   (k_walk_rows: na / off are [rows of the range][N], slot (k - kb) * N + g;
+                                      //   k_walk_groups: the range's slots, slot - slot_base)
     unsigned long long* key;          // [A] (column sequence rank << ubits) | row sequence rank
     uint32_t* val;                    // [A] k
     // AAI / PEQ
@@ -136,6 +150,8 @@ int pc_launch_set_popc(const PcDev& d, const PcShard& sh, int metric, int as_dis
 int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs& a, hipStream_t st, pc_set_shape* shape_out = nullptr);
 // the walker over the query rows [kb, ke) of a rows fill; a.out is the whole f64[nrows][N], a.condensed is not read
 int pc_launch_walk_rows(int mode, const PcDev& d, const PcRows& rw, int kb, int ke, const PcWalkArgs& a, hipStream_t st);
+// the walker over the tiles [tb, te) of a groups fill; a.out is the whole f64[L], a.condensed is not read
+int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t tb, int64_t te, const PcWalkArgs& a, hipStream_t st);
 int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);   // pocp / af
 int pc_launch_pair_entries(const int32_t* pham, const int32_t* len, const int32_t* cnt, uint2* pair_len, uint2* pair_cnt, int64_t n, hipStream_t st);
 int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, const int32_t* len, const int32_t* cnt, const int32_t* dense, int W2,

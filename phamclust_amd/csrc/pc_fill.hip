@@ -1,5 +1,5 @@
 // pc_fill.hip -- the fill entry points of libphamclust_hip.so (pc_fill, pc_fill_borrow, pc_fill_dev, pc_fill_shard_dev,
-// pc_assemble_dev, pc_fill_rows, pc_fill_rows_dev, pc_fill_edges) and the set-metric kernel selector.
+// pc_assemble_dev, pc_fill_rows, pc_fill_rows_dev, pc_fill_groups, pc_fill_groups_dev, pc_fill_edges) and the set-metric kernel selector.
 #include "pc_host.h"
 
 #ifndef PC_COL_MIN_N
@@ -300,6 +300,164 @@ extern "C" int pc_fill_rows(pc_ctx* c, int metric, int as_distance, const int32_
     if ((rc = c->b_out.ensure(std::max<int64_t>(cells, 1) * 8))) return abi_rc(rc);
     if ((rc = pc_fill_rows_dev(c, metric, as_distance, rows, n_rows, c->b_out.p, c->stream, stats))) return rc;
     if (n_rows > 0 && cells) PC_HIP(hipMemcpyAsync(out_host, c->b_out.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    c->busy = false;
+    return PC_OK;
+}
+
+// ---- groups fill: every pair (s, t), s < t, of two genomes in the same group of a caller-given family of groups, as the groups'
+// condensed triangles end to end, f64[L].  members[M]: genome indices group by group, strictly ascending inside a group (position
+// order = index order, so every pair keeps the whole fill's orientation); group_off[G+1]: each group's range.  Groups may share
+// genomes; a group of 0 or 1 members has no pair.  The set metrics always run on the groups walker (no selector: pc_last_set_kernel /
+// pc_last_set_launch keep reporting the last whole fill); aai / peq run COUNT -> plan -> align -> reduce over ranges of row blocks
+// (fill_groups_aligned).
+
+// Host arithmetic, exported for tests: pair_off[c] = sum over c' < c of n_c' (n_c' - 1) / 2; returns L = pair_off[n_groups].
+extern "C" int64_t pc_group_pair_offsets(const int64_t* group_off, int n_groups, int64_t* pair_off) {
+    if (n_groups < 0 || (n_groups > 0 && !group_off)) { pc_set_error("pc_group_pair_offsets: bad argument"); return PC_ERR_ARG; }
+    if (n_groups > 0 && group_off[0] != 0) { pc_set_error("pc_group_pair_offsets: group_off[0] = %lld, not 0", (long long)group_off[0]); return PC_ERR_ARG; }
+    int64_t L = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int64_t n = group_off[g + 1] - group_off[g];
+        if (n < 0) { pc_set_error("pc_group_pair_offsets: group_off decreases at group %d", g); return PC_ERR_ARG; }
+        if (pair_off) pair_off[g] = L;
+        L += n * (n - 1) / 2;
+    }
+    if (pair_off) pair_off[n_groups] = L;
+    return L;
+}
+
+// Per row block of PC_GROUP_TILE positions the live column blocks: a contiguous range [lo, hi] (or none).  A position p with a later member in
+// its group reaches the columns p + 1 .. end - 1; only the LAST group that starts in a block can leave it, every other interval lies
+// inside the block, so the union of the blocks the intervals touch has no gap.
+static void group_block_ranges(const int64_t* group_off, int n_groups, int64_t M, std::vector<int32_t>& lo, std::vector<int32_t>& hi) {
+    const int64_t B = (M + PC_GROUP_TILE - 1) / PC_GROUP_TILE;
+    lo.assign((size_t)B, INT32_MAX); hi.assign((size_t)B, -1);
+    for (int g = 0; g < n_groups; ++g) {
+        const int64_t b = group_off[g], e = group_off[g + 1];
+        if (e - b < 2) continue;
+        const int32_t last = (int32_t)((e - 1) / PC_GROUP_TILE);
+        for (int64_t a = b / PC_GROUP_TILE; a <= (e - 2) / PC_GROUP_TILE; ++a) {               // row blocks holding a position p in [b, e - 2]
+            const int64_t p_first = std::max(b, a * PC_GROUP_TILE);                  // its first such p reaches column p + 1 first
+            lo[a] = std::min(lo[a], (int32_t)((p_first + 1) / PC_GROUP_TILE));
+            hi[a] = std::max(hi[a], last);
+        }
+    }
+}
+
+// Host arithmetic, exported for tests: the live tiles (row block a, column block b), a <= b, sorted by a, then b: some slot (p, q),
+// p < q, both of one group, has p in block a and q in block b.  At most cap entries are written; returns their number T.
+extern "C" int64_t pc_group_tiles(const int64_t* group_off, int n_groups, int32_t* tile_row, int32_t* tile_col, int64_t cap) {
+    const int64_t L = pc_group_pair_offsets(group_off, n_groups, nullptr);
+    if (L < 0) return L;
+    const int64_t M = n_groups > 0 ? group_off[n_groups] : 0;
+    if (M > 0x7fffffffLL) { pc_set_error("pc_group_tiles: %lld members exceed 2^31-1", (long long)M); return PC_ERR_ARG; }
+    std::vector<int32_t> lo, hi;
+    group_block_ranges(group_off, n_groups, M, lo, hi);
+    int64_t T = 0;
+    for (size_t a = 0; a < lo.size(); ++a)
+        for (int32_t b = lo[a]; b <= hi[a]; ++b, ++T)
+            if (T < cap) { if (tile_row) tile_row[T] = (int32_t)a; if (tile_col) tile_col[T] = b; }
+    return T;
+}
+
+extern "C" int pc_fill_groups_dev(pc_ctx* c, int metric, int as_distance, const int32_t* members, const int64_t* group_off, int n_groups,
+                                  void* out_dev, void* stream, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_groups: upload first"); return PC_ERR_STATE; }
+    if (c->world != 1) { pc_set_error("pc_fill_groups: context is sharded (%d/%d); a groups fill is a one-GPU call on an unsharded context", c->rank, c->world); return PC_ERR_STATE; }
+    if (metric < PC_GCS || metric > PC_AAI_PPOS) { pc_set_error("pc_fill_groups: metric %d", metric); return PC_ERR_ARG; }
+    const int ppos = metric == PC_AAI_PPOS;
+    if (ppos) metric = PC_AAI;
+    if (n_groups < 0) { pc_set_error("pc_fill_groups: n_groups %d", n_groups); return PC_ERR_ARG; }
+    pc_stats local; memset(&local, 0, sizeof(local));
+    if (n_groups == 0) { if (stats) *stats = local; return PC_OK; }
+    if (!group_off) { pc_set_error("pc_fill_groups: group_off is NULL"); return PC_ERR_ARG; }
+    const int64_t L = pc_group_pair_offsets(group_off, n_groups, nullptr);
+    if (L < 0) return (int)L;
+    const int64_t M = group_off[n_groups];
+    if (M > 0x7fffffffLL) { pc_set_error("pc_fill_groups: %lld members exceed 2^31-1", (long long)M); return PC_ERR_ARG; }
+    if (M > 0 && !members) {
+        if (L == 0) { if (stats) *stats = local; return PC_OK; }
+        pc_set_error("pc_fill_groups: members is NULL"); return PC_ERR_ARG;
+    }
+    const PcDev& d = c->dev;
+    const int N = d.N;
+    for (int g = 0; g < n_groups; ++g)
+        for (int64_t p = group_off[g]; p < group_off[g + 1]; ++p)
+            if (members[p] < 0 || members[p] >= N || (p > group_off[g] && members[p] <= members[p - 1])) {
+                pc_set_error("pc_fill_groups: a group's members must be strictly ascending genome indices below %d (group %d, members[%lld] = %d)",
+                             N, g, (long long)p, members[p]);
+                return PC_ERR_ARG;
+            }
+    if (L == 0) { if (stats) *stats = local; return PC_OK; }
+    if (!out_dev) { pc_set_error("pc_fill_groups: out is NULL"); return PC_ERR_ARG; }
+    if (metric >= PC_AAI && !c->residues_ready) { pc_set_error("pc_fill_groups: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    PC_ON_DEVICE(c);
+    static const char* const fill_names[] = {"pc:fill_groups:gcs", "pc:fill_groups:jc", "pc:fill_groups:pocp", "pc:fill_groups:af", "pc:fill_groups:aai", "pc:fill_groups:peq"};
+    PcRange range(fill_names[metric]);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = PC_OK;
+    if ((rc = wait_last_work(c, st, false))) return rc;                    // (the domain tables below are rewritten by a blocking copy: nothing may still read them)
+    // the per-position tables and the tile list
+    PcGroupsHost gh;
+    std::vector<int32_t> h_genome(members, members + M), h_end((size_t)M), h_trow, h_tcol;
+    std::vector<int64_t> h_rowbase((size_t)M + 1);
+    {
+        int64_t at = 0;
+        for (int g = 0; g < n_groups; ++g)
+            for (int64_t p = group_off[g], e = group_off[g + 1]; p < e; ++p) { h_end[p] = (int32_t)e; h_rowbase[p] = at; at += e - p - 1; }
+        h_rowbase[M] = at;                                                  // = L
+        std::vector<int32_t> lo, hi;
+        group_block_ranges(group_off, n_groups, M, lo, hi);
+        gh.nblocks = (int)lo.size();
+        gh.block_tile.resize(lo.size() + 1); gh.block_slot.resize(lo.size() + 1);
+        for (size_t a = 0; a < lo.size(); ++a) {
+            gh.block_tile[a] = (int64_t)h_trow.size(); gh.block_slot[a] = h_rowbase[a * PC_GROUP_TILE];
+            for (int32_t b = lo[a]; b <= hi[a]; ++b) { h_trow.push_back((int32_t)a); h_tcol.push_back(b); }
+        }
+        gh.block_tile[lo.size()] = (int64_t)h_trow.size(); gh.block_slot[lo.size()] = L;
+    }
+    if ((rc = upload_vec(c->b_grp_genome, h_genome)) || (rc = upload_vec(c->b_grp_end, h_end)) || (rc = upload_vec(c->b_grp_rowbase, h_rowbase)) ||
+        (rc = upload_vec(c->b_grp_trow, h_trow)) || (rc = upload_vec(c->b_grp_tcol, h_tcol))) return rc;
+    gh.dev = PcGroups{(int32_t)M, 0, c->b_grp_genome.as<int32_t>(), c->b_grp_end.as<int32_t>(), c->b_grp_rowbase.as<int64_t>(),
+                      c->b_grp_trow.as<int32_t>(), c->b_grp_tcol.as<int32_t>(), 0};
+    local.n_pairs = L;
+    as_distance = as_distance ? 1 : 0;
+    PC_HIP(hipEventRecord(c->ev[0], st));
+    if (metric < PC_AAI) {
+        PcWalkArgs a; memset(&a, 0, sizeof(a));
+        a.out = (double*)out_dev; a.as_distance = as_distance;
+        const int mode = metric == PC_GCS ? PCW_GCS : metric == PC_JC ? PCW_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
+        if ((rc = pc_launch_walk_groups(mode, d, gh.dev, 0, (int64_t)h_trow.size(), a, st))) return rc;
+        PC_HIP(hipEventRecord(c->ev[3], st));
+        local.n_chunks = 1;
+    } else {
+        rc = fill_groups_aligned(c, gh, metric, ppos, as_distance, (double*)out_dev, st, local, stats != nullptr);
+        if (rc != PC_OK) { (void)mark_work(c, st); return abi_rc(rc); }
+    }
+    if ((rc = mark_work(c, st))) return rc;
+    if (stats) {
+        PC_HIP(hipEventSynchronize(c->ev[3]));
+        c->busy = false;
+        PC_HIP(hipEventElapsedTime(&local.ms_total, c->ev[0], c->ev[3]));
+        if (metric < PC_AAI) local.ms_reduce = local.ms_total;
+        *stats = local;
+    }
+    return PC_OK;
+}
+
+extern "C" int pc_fill_groups(pc_ctx* c, int metric, int as_distance, const int32_t* members, const int64_t* group_off, int n_groups,
+                              double* out_host, pc_stats* stats) {
+    if (!c || !c->uploaded) { pc_set_error("pc_fill_groups: upload first"); return PC_ERR_STATE; }
+    const int64_t L = (n_groups > 0 && group_off) ? pc_group_pair_offsets(group_off, n_groups, nullptr) : 0;
+    if (L > 0 && !out_host) { pc_set_error("pc_fill_groups: out is NULL"); return PC_ERR_ARG; }
+    if (L > 0 && group_off[n_groups] > 0x7fffffffLL) { pc_set_error("pc_fill_groups: %lld members exceed 2^31-1", (long long)group_off[n_groups]); return PC_ERR_ARG; }
+    PC_ON_DEVICE(c);
+    int rc = PC_OK;
+    if ((rc = wait_last_work(c, c->stream, false))) return rc;             // (b_out may still be read by a fill left on another stream)
+    if ((rc = c->b_out.ensure(std::max<int64_t>(L, 1) * 8))) return abi_rc(rc);
+    if ((rc = pc_fill_groups_dev(c, metric, as_distance, members, group_off, n_groups, c->b_out.p, c->stream, stats))) return rc;
+    if (L > 0) PC_HIP(hipMemcpyAsync(out_host, c->b_out.p, L * 8, hipMemcpyDeviceToHost, c->stream));
     PC_HIP(hipStreamSynchronize(c->stream));
     c->busy = false;
     return PC_OK;

@@ -113,6 +113,7 @@ struct pc_ctx {
     DevBuf b_na, b_off, b_key0, b_key1, b_val0, b_val1, b_sort_tmp, b_flags, b_excl, b_alias, b_start_q, b_end_q, b_ntask_q, b_task_off_q, b_scan_tmp;
     DevBuf b_tasks, b_tasks_sorted, b_bucket_row, b_bucket_dest, b_res, b_totals, b_plan, b_scratch, b_out, b_lut, b_slice_begin, b_aln_t;
     DevBuf b_rows, b_row_of;                // the domain of the last rows fill (PcRows: the query genomes, and every genome's position among them)
+    DevBuf b_grp_genome, b_grp_end, b_grp_rowbase, b_grp_trow, b_grp_tcol;   // the domain of the last groups fill (PcGroups)
     // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
     DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
     PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
@@ -243,7 +244,18 @@ static int pc_task_launch_class(int lb, int rows, int base, bool modes) {
 // a launch whose longest column gene exceeds its variant's 64 x W columns runs strip-mined and needs the scratch slab
 static bool pc_launch_is_strip(int variant, int max_lb, int mode, int ppos) { return pc_nw_launch_is_strip(variant, max_lb, mode, ppos) != 0; }
 
+// A groups fill's domain as the host sees it: the device view, and per row block of TS positions where its tiles and its slots
+// begin (both ascend: a range of row blocks is a range of the tile list and of the slots).
+struct PcGroupsHost {
+    PcGroups dev{};
+    int nblocks = 0;                        // row blocks = ceil(M / TS)
+    std::vector<int64_t> block_tile;        // [nblocks+1] first tile of row block a; [nblocks] = T
+    std::vector<int64_t> block_slot;        // [nblocks+1] first slot of row block a = pos_rowbase[a * TS]; [nblocks] = L
+};
+
 // aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
 int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);
 // the same over the query rows of a rows fill, chunked over ranges of rows; out: f64[rows.nrows][N] (pc_align.hip)
 int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);
+// the same over the within-group pairs of a groups fill, chunked over ranges of row blocks; out: f64[L] (pc_align.hip)
+int fill_groups_aligned(pc_ctx* c, const PcGroupsHost& groups, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);

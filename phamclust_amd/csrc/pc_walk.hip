@@ -1,12 +1,14 @@
-// pc_walk.hip -- the shared-pham walker over its two pair domains: k_walk (whole fills: pocp / af, alignment counting and planning,
-// the best-match reduce of aai / peq) and k_walk_rows (rows fills: the same and gcs / jc).  One core -- the visit of a shared pham,
-// the visits of a bitmap word, the value epilogue, the COUNT totals -- serves both kernels, so each rule of the reference is stated once.
+// pc_walk.hip -- the shared-pham walker over its three pair domains: k_walk (whole fills: pocp / af, alignment counting and planning,
+// the best-match reduce of aai / peq), k_walk_rows (rows fills: the same and gcs / jc) and k_walk_groups (groups fills: as the rows
+// walker, over the within-group pairs of a family of groups).  One core -- the visit of a shared pham, the visits of a bitmap word,
+// the value epilogue, the COUNT totals -- serves all three kernels, so each rule of the reference is stated once.
 //
 // Reference semantics restated here (metrics.py of the reference unless named):
 //   metrics.py:83-115, 118-157   pocp / af: sums over shared phams of gene counts / lengths     (pc_visit, pc_walk_value)
 //   metrics.py:203-227           aai: anchor rule, best match (ties -> last), weighted mean      (pc_visit, pc_walk_value)
 //   metrics.py:247-253           peq = round(af, 6) * round(aai, 6), then round(., 6)            (pc_walk_value)
 //   matrix.py:169-213, 467-486   the rows domain: source = min, target = max, the diagonal      (k_walk_rows)
+//   matrix.py:155-167, 479-486   the groups domain: a sub-matrix's pairs, source = the smaller index (k_walk_groups)
 #include "pc_pairs.h"
 
 #define WCH 32         // bitmap words staged per chunk (17 KB of LDS per workgroup: nine workgroups per CU hide the staging latency)
@@ -344,5 +346,127 @@ int pc_launch_walk_rows(int mode, const PcDev& d, const PcRows& rw, int kb, int 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("k_walk_rows launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// The walker over a GROUPS domain (pc_fill_groups): every pair of two genomes that lie in the same group of a caller-given family of
+// groups -- a block diagonal, sum of n_c^2 cells instead of N^2.  The reference reads such blocks out of the dense matrix
+// (SymMatrix.extract_submatrix, matrix.py:155-167); here they are filled alone.  The groups' members are laid end to end as M
+// positions; members ascend inside a group, so for two positions p < q of one group genome[p] < genome[q]: the row's genome is the
+// reference's `source`, the column's its `target` (matrix.py:479-486), the whole fill's orientation.
+//
+// Tiles are TS x TS over POSITIONS, not per group, so many small groups share a tile; the host lists the live ones -- row block a,
+// column block b >= a, some slot of the tile live: a band along the diagonal -- sorted by a, and a workgroup takes tile tb +
+// blockIdx.x of that list (neighbouring workgroups then share rows, which is all the affinity a band has to offer).  Slot (p, q) is
+// live iff p < q < pos_end[p]; its index in out, and (less slot_base) in the slot arrays na / off, is pos_rowbase[p] + q - p - 1:
+// a group's condensed triangle, the groups' triangles end to end, no dead slot.  Lanes run over q: a row's stores are contiguous
+// and a thread's four slots (rows r0 + 8 m) share the column genome, whose word is read once per scanned word from 32 LDS rows of
+// odd stride; the row's word is a broadcast.  What k_walk says on the word scan holds unchanged.  COUNT sums a workgroup's
+// alignments into aln_t[a], its ROW BLOCK (where a groups fill is cut: a range of row blocks is a range of the tile list and of
+// the slots); ENUM emits k_walk's keys.  GCS / JC count in the word scan, as in k_walk_rows.
+// ---------------------------------------------------------------------------------
+static_assert(PC_GROUP_TILE == TS, "the host lists the groups walker's tiles by PC_GROUP_TILE");
+__device__ __forceinline__ void pc_stage_tile_groups(const PcDev& d, const PcGroups& gr, int64_t p0, int64_t q0, int w0, int wn,
+                                                     uint64_t (*rp)[WCH + 1], uint64_t (*rq)[WCH + 1]) {
+    for (int r = threadIdx.x >> 5; r < TS; r += 8) {
+        const int64_t p = p0 + r, q = q0 + r;
+        const uint64_t* pp = p < gr.M ? d.bitmap + (int64_t)gr.pos_genome[p] * d.Wstride + w0 : nullptr;
+        const uint64_t* pq = q < gr.M ? d.bitmap + (int64_t)gr.pos_genome[q] * d.Wstride + w0 : nullptr;
+        for (int w = threadIdx.x & 31; w < wn; w += 32) {
+            rp[r][w] = pp ? pp[w] : 0ULL;
+            rq[r][w] = pq ? pq[w] : 0ULL;
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_walk_groups(PcDev d, PcGroups gr, int64_t tb, PcWalkArgs a) {
+    constexpr bool SETS = MODE == PCW_GCS || MODE == PCW_JC;                        // shared-pham counts: no visit
+    constexpr bool SLOTS = MODE == PCW_ENUM || MODE == PCW_AAI || MODE == PCW_PEQ;  // walks the pair's alignment slots
+    __shared__ uint64_t rp[TS][WCH + 1];                    // the tile's row positions p (sources)
+    __shared__ uint64_t rq[TS][WCH + 1];                    // the tile's column positions q (targets)
+    __shared__ unsigned long long red[3];
+    const int64_t tile = tb + blockIdx.x;
+    const int row_block = gr.tile_row[tile];
+    const int64_t p0 = (int64_t)row_block * TS, q0 = (int64_t)gr.tile_col[tile] * TS;
+    const int f = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    const int64_t q = q0 + f;
+    const bool q_in = q < gr.M;
+    const int t = q_in ? gr.pos_genome[q] : 0;
+    PcPairAcc acc[4];
+    int ss[4]; int64_t slot[4]; bool ok[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int64_t p = p0 + r0 + 8 * m;
+        ok[m] = q_in && p < q && q < gr.pos_end[p];          // (p < q < M: pos_end[p] is in bounds)
+        ss[m] = ok[m] ? gr.pos_genome[p] : 0;
+        slot[m] = ok[m] ? gr.pos_rowbase[p] + (q - p - 1) : 0;
+        acc[m].reset();
+        if (ok[m] && SLOTS) acc[m].k = a.off[slot[m] - gr.slot_base];
+    }
+    unsigned long long cells = 0, rbytes = 0;
+    if (MODE == PCW_COUNT) { if (threadIdx.x < 3) red[threadIdx.x] = 0; }
+
+    for (int w0 = 0; w0 < d.Wb; w0 += WCH) {
+        const int wn = min(WCH, d.Wb - w0);
+        if (w0) __syncthreads();
+        pc_stage_tile_groups(d, gr, p0, q0, w0, wn, rp, rq);
+        __syncthreads();
+        uint32_t nz[4] = {0u, 0u, 0u, 0u};
+        for (int i = 0; i < wn; ++i) {
+            const uint64_t common = rq[f][i];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint64_t both = rp[r0 + 8 * m][i] & common;
+                if (SETS) acc[m].k += (uint32_t)__popcll(both);
+                else nz[m] |= (both != 0 ? 1u : 0u) << i;
+            }
+        }
+        if constexpr (!SETS) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (!ok[m]) continue;
+                const uint32_t* rps = d.rankpre + (int64_t)ss[m] * d.Wb + w0;
+                const uint32_t* rpt = d.rankpre + (int64_t)t * d.Wb + w0;
+                uint32_t todo = nz[m];
+                while (todo) {
+                    const int w = __ffs((int)todo) - 1;
+                    todo &= todo - 1;
+                    pc_walk_word<MODE>(d, a, acc[m], rp[r0 + 8 * m][w], rq[f][w], rps[w], rpt[w], cells, rbytes);
+                }
+            }
+        }
+    }
+
+    if (MODE == PCW_COUNT) {
+        unsigned long long nal = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            if (!ok[m]) continue;
+            if (a.na) a.na[slot[m] - gr.slot_base] = acc[m].k;
+            nal += acc[m].k;
+        }
+        pc_walk_totals(red, a.totals, nal, cells, rbytes);
+        if (a.aln_t && threadIdx.x == 0 && red[0]) atomicAdd(&a.aln_t[row_block], red[0]);     // (red[] is final behind the barrier of pc_walk_totals)
+        return;
+    }
+    if (MODE == PCW_ENUM) return;
+
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+        if (ok[m]) a.out[slot[m]] = pc_walk_value<MODE>(d, acc[m], ss[m], t, a.as_distance);
+}
+
+int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t tb, int64_t te, const PcWalkArgs& a, hipStream_t st) {
+    if (tb < 0 || tb > te || te - tb > 0x7fffffffLL) { pc_set_error("pc_launch_walk_groups: tiles [%lld, %lld)", (long long)tb, (long long)te); return PC_ERR_ARG; }
+    if (te == tb || gr.M < 2) return PC_OK;
+    dim3 grid((unsigned)(te - tb)), block(256);
+    if (!pc_dispatch<PCW_GCS, PCW_JC, PCW_POCP, PCW_AF, PCW_COUNT, PCW_ENUM, PCW_AAI, PCW_PEQ>(
+            mode, [&](auto m) { hipLaunchKernelGGL(k_walk_groups<decltype(m)::value>, grid, block, 0, st, d, gr, tb, a); })) {
+        pc_set_error("pc_launch_walk_groups: bad mode %d", mode); return PC_ERR_ARG;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_walk_groups launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
     return PC_OK;
 }

@@ -73,7 +73,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times",
-           "pc_fill_components", "pc_last_component_times"]
+           "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -132,6 +132,12 @@ def load():
     L.pc_assemble_dev.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.pc_fill_rows.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _f64p, ctypes.POINTER(PcStats)]
     L.pc_fill_rows_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
+    L.pc_fill_groups.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i64p, ctypes.c_int, _f64p, ctypes.POINTER(PcStats)]
+    L.pc_fill_groups_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i64p, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
+    L.pc_group_pair_offsets.argtypes = [_i64p, ctypes.c_int, _i64p]
+    L.pc_group_pair_offsets.restype = ctypes.c_int64
+    L.pc_group_tiles.argtypes = [_i64p, ctypes.c_int, _i32p, _i32p, ctypes.c_int64]
+    L.pc_group_tiles.restype = ctypes.c_int64
     L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                 ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_edge_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
@@ -403,6 +409,66 @@ class Context:
         self._check(self._lib.pc_fill_rows(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(rows, _i32p), int(rows.shape[0]),
                                            _ptr(buf, _f64p), ctypes.byref(stats)))
         return (out, stats.as_dict()) if want_stats else out
+
+    @staticmethod
+    def _group_arrays(groups):
+        """``groups`` (sequences of genome indices) as the C-ABI's ``members`` / ``group_off`` arrays."""
+        groups = [np.ascontiguousarray(g, dtype=np.int32).reshape(-1) for g in groups]
+        off = np.zeros(len(groups) + 1, dtype=np.int64)
+        if groups:
+            np.cumsum([g.shape[0] for g in groups], out=off[1:])
+        members = np.concatenate(groups) if groups else np.empty(0, dtype=np.int32)
+        return np.ascontiguousarray(members, dtype=np.int32), off
+
+    @staticmethod
+    def group_pair_offsets(group_off):
+        """``pair_off[G + 1]`` of a groups fill: where each group's condensed triangle starts; the last entry is L (host arithmetic)."""
+        group_off = np.ascontiguousarray(group_off, dtype=np.int64)
+        pair_off = np.zeros(group_off.shape[0], dtype=np.int64)
+        total = load().pc_group_pair_offsets(_ptr(group_off, _i64p), int(group_off.shape[0]) - 1, _ptr(pair_off, _i64p))
+        if total < 0:
+            raise ValueError(load().pc_last_error().decode())
+        return pair_off
+
+    @staticmethod
+    def group_tiles(group_off):
+        """The live 32 x 32 tiles ``(row block, column block)`` of a groups fill as an ``(T, 2)`` int32 array, sorted (host arithmetic)."""
+        group_off = np.ascontiguousarray(group_off, dtype=np.int64)
+        lib, n = load(), int(group_off.shape[0]) - 1
+        count = lib.pc_group_tiles(_ptr(group_off, _i64p), n, None, None, 0)
+        if count < 0:
+            raise ValueError(lib.pc_last_error().decode())
+        tiles = np.zeros((2, max(int(count), 1)), dtype=np.int32)
+        lib.pc_group_tiles(_ptr(group_off, _i64p), n, _ptr(tiles[0], _i32p), _ptr(tiles[1], _i32p), int(count))
+        return np.ascontiguousarray(tiles[:, :int(count)].T)
+
+    def fill_groups(self, metric, groups, as_distance=True, want_stats=False):
+        """Every within-group pair of ``groups`` -- sequences of genome indices, each strictly ascending; groups may share genomes
+        -- in one call: a list of condensed float64 arrays, one per group (scipy order: what ``SymMatrix.from_condensed`` takes; a
+        group of fewer than two members gives an empty array).  Values are the whole fill's, each pair in its orientation."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        members, off = self._group_arrays(groups)
+        pair_off = self.group_pair_offsets(off)
+        out = np.empty(int(pair_off[-1]), dtype=np.float64)
+        buf = out if out.size else np.zeros(1)
+        self._check(self._lib.pc_fill_groups(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(members if members.size else np.zeros(1, np.int32), _i32p),
+                                             _ptr(off, _i64p), len(off) - 1, _ptr(buf, _f64p), ctypes.byref(stats)))
+        parts = [out[pair_off[k]:pair_off[k + 1]] for k in range(len(off) - 1)]
+        return (parts, stats.as_dict()) if want_stats else parts
+
+    def fill_groups_dev(self, metric, as_distance, groups, out_ptr, stream=None, want_stats=True):
+        """The same, left in HBM at ``out_ptr`` as one float64 vector: the groups' condensed triangles end to end
+        (:meth:`group_pair_offsets` of the groups' sizes gives the cuts)."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        members, off = self._group_arrays(groups)
+        self._check(self._lib.pc_fill_groups_dev(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(members if members.size else np.zeros(1, np.int32), _i32p),
+                                                 _ptr(off, _i64p), len(off) - 1, ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0),
+                                                 ctypes.byref(stats) if want_stats else None))
+        return stats.as_dict() if want_stats else None
 
     EDGE_MAX_PAIRS = 2 ** 31 - 1          # pairs one slab of an edge-list fill may hold (u32 counts and offsets on the device)
 

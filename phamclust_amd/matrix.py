@@ -864,6 +864,93 @@ def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, 
     return Components([g.name for g in genomes], labels)
 
 
+def upload_for_fills(genomes, func, caller):
+    """What the one-GPU routes without a dense matrix share ahead of their fills: the refusals (no genome, a callable outside the
+    six ``METRICS``, a launcher), then ONE pack and ONE upload.  Returns ``(context, metric name, genome names, record)`` -- the
+    record holds ``pack_s``, ``upload_s`` and the collection's ``genome_pairs`` for ``LAST_FILL`` -- and the caller runs as many fills
+    on the context as it needs (``submatrices_de_novo``: a groups fill; ``hierarchical_clustering_de_novo``: a components fill, then
+    a groups fill; ``phamclust --no-matrix``: two and three of them)."""
+    if len(genomes) == 0:
+        raise ValueError(f"{caller}: need at least 1 genome")
+    metric = _metric_name(func)
+    if metric is None:
+        raise ValueError(f"{caller}: func must be one of the six METRICS callables -- the components and groups fills run on the GPU only and "
+                         f"have no CPU route (the dense route, matrix_de_novo, serves another callable)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError(f"{caller}: the components and groups fills are one-GPU calls; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+    import time
+    devices = in_process_devices()
+    if devices:
+        logging.debug(f"{caller}: one-GPU calls: using device {devices[0]} of {devices}")
+    t0 = time.perf_counter()
+    packed = _packed_of(genomes)
+    t1 = time.perf_counter()
+    ctx = get_context(devices[0] if devices else None)
+    ctx.upload(packed, residues=metric in ("aai", "peq"))
+    t2 = time.perf_counter()
+    logging.debug(f"{caller}: {len(genomes)} genomes: pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s")
+    return ctx, metric, [g.name for g in genomes], dict(pack_s=t1 - t0, upload_s=t2 - t1, genome_pairs=packed.n_pairs)
+
+
+def _group_indices(names, index, groups):
+    """``groups`` -- each a sequence of genome names or of indices into the genome list -- as ascending index lists.  KeyError
+    for an unknown name, IndexError for an index outside the list, ValueError for a genome twice in one group."""
+    out = []
+    for k, group in enumerate(groups):
+        idx = []
+        for member in group:
+            if isinstance(member, (int, np.integer)) and not isinstance(member, bool):
+                if not 0 <= int(member) < len(names):
+                    raise IndexError(f"group {k}: genome index {int(member)} is outside 0..{len(names) - 1}")
+                idx.append(int(member))
+            elif member in index:
+                idx.append(index[member])
+            else:
+                raise KeyError(f"group {k}: '{member}' is not among the genomes")
+        if len(set(idx)) != len(idx):
+            twice = next(names[i] for i in idx if idx.count(i) > 1)
+            raise ValueError(f"group {k}: genome '{twice}' is listed twice")
+        out.append(sorted(idx))
+    return out
+
+
+def submatrices_de_novo(genomes, func, groups, as_distance=True):
+    """``[matrix_de_novo(genomes, func, cpus, as_distance).extract_submatrix(names of group) for group in groups]`` without the
+    N x N matrix: one ``SymMatrix`` per group, filled by ONE groups fill (``Context.fill_groups``) -- one pack and one upload
+    whatever the number of groups, sum of n_c^2 cells instead of N^2, and a sequence pair that occurs in several groups aligned
+    once.  A group is a sequence of genome names or of indices into ``genomes``; groups may share genomes.  Each matrix's nodes are
+    the group's genomes in genome-list order, so every pair keeps the whole fill's orientation and its value bit for bit (aai
+    included); a group of one gives a one-node matrix with the diagonal preset (matrix.py:467-468), an empty group an empty matrix.
+    ``func`` must be one of the six ``METRICS`` callables (no CPU route).  One GPU, as ``edges_de_novo``: under a launcher
+    (``WORLD_SIZE`` > 1) it raises.  Every refusal comes before the first GPU call."""
+    names = [g.name for g in genomes]
+    index = {name: k for k, name in enumerate(names)}
+    if len(index) != len(names):
+        raise ValueError("genome names must be distinct")
+    members = _group_indices(names, index, groups)
+    ctx, metric, names, record = upload_for_fills(genomes, func, "submatrices_de_novo")
+    import time
+    t0 = time.perf_counter()
+    parts, stats = ctx.fill_groups(metric, members, as_distance=as_distance, want_stats=True)
+    fill_s = time.perf_counter() - t0
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=int(stats["n_pairs"]), groups=len(members), n_gpus=1, rank=0,
+                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
+    logging.debug(f"{len(genomes)} genomes, {len(members)} groups -> {stats['n_pairs']} of {record['genome_pairs']} edges on one device: "
+                  f"fill+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    out = []
+    for idx, condensed in zip(members, parts):
+        nodes = [names[i] for i in idx]
+        if len(nodes) < 2:
+            one = SymMatrix(nodes=nodes, is_distance=as_distance)
+            for node in nodes:
+                one.set_weight(node, node, 1.0 - as_distance)
+            out.append(one)
+        else:
+            out.append(SymMatrix.from_condensed(nodes, condensed, is_distance=as_distance))
+    return out
+
+
 def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):
     """The bytes ``matrix_to_adjacency`` writes for the dense matrix restricted to these pairs (diagonal included).
     ``use_lib=False`` takes the Python formatter even when csrc/libpc_pack.so is there (same bytes)."""

@@ -23,10 +23,10 @@ from phamclust_amd import distributed
 from phamclust_amd import matrix as _matrix
 from phamclust_amd import metrics as _metrics
 from phamclust_amd.cli import METRICS, parse_args
-from phamclust_amd.clustering import hierarchical_clustering
+from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform
+from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -108,7 +108,7 @@ def check_matrix_integrity(matrix):
 class _Run:
     def __init__(self, outdir, metric, colors, midpoint):
         self.outdir, self.metric, self.colors, self.midpoint = outdir, metric, colors, midpoint
-        self.genomes, self.by_name, self.cache, self.stage = [], {}, None, None
+        self.genomes, self.by_name, self.cache, self.stage, self.fills = [], {}, None, None, None
         self.rank, self.world = 0, 1          # this process's place in the job (one process per GPU)
         self.extend = None                    # --extend FILE: a distance matrix over a subset of the genomes
 
@@ -294,6 +294,60 @@ class _Run:
         log.info(f"{len(groups)} pre-groups -> {len(multi)} clusters + {len(single)} singletons")
         return multi, single
 
+    # 2 + 3, --no-matrix
+    def clusters_no_matrix(self, nr, clu):
+        """Stages 2 and 3 without the dense matrix: what ``clusters(distances(), nr, clu)`` returns, from ONE upload, two components
+        fills (N labels each) and three groups fills (the sub-matrices, sum of n_c^2 cells).  Every pass clusters component by
+        component (``cluster_by_component``: a cluster cut at eps never spans two components of {d < eps}), so its parts and their
+        order are the dense route's."""
+        self.banner(2, f"{self.metric} clusters without the dense matrix (components and groups fills)")
+        t0 = time.perf_counter()
+        ctx, metric, names, _ = upload_for_fills(self.genomes, METRICS[self.metric], "--no-matrix")
+        self.fills = (ctx, metric, names)                   # finish_no_matrix fills the adjacency file's edges on the same upload
+        index = {name: k for k, name in enumerate(names)}
+        filled = [0, 0]
+
+        def submatrices(groups):
+            """One groups fill: the distance matrix of each group of names, its nodes in the group's own order."""
+            out = [None] * len(groups)
+            multi = [k for k, group in enumerate(groups) if len(group) > 1]
+            ascending = [sorted(index[name] for name in groups[k]) for k in multi]
+            values, st = ctx.fill_groups(metric, ascending, as_distance=True, want_stats=True)
+            filled[0] += 1; filled[1] += int(st["n_pairs"])
+            for k, idx, condensed in zip(multi, ascending, values):
+                block = SymMatrix.from_condensed([names[i] for i in idx], condensed, is_distance=True)
+                out[k] = block if block.nodes == list(groups[k]) else block.extract_submatrix(list(groups[k]))
+            for k, group in enumerate(groups):
+                if out[k] is None:
+                    out[k] = SymMatrix(nodes=list(group), is_distance=True)
+                    for node in group:
+                        out[k].set_weight(node, node, 0.0)
+            return out
+
+        # near-identical genomes: the components at nr, each clustered alone with the nr linkage
+        near = Components(names, ctx.fill_components(metric, nr[0], as_distance=True, strict=True)).groups()
+        of_first = {m.nodes[0]: m for m in submatrices([g for g in near if len(g) > 1])}
+        groups = cluster_by_component(near, lambda group: of_first[group[0]], nr[1], nr[0], nodes=names)
+        by_medoid = {group.medoid[0]: group for group in groups}
+        # the medoids: the components at clu over ALL genomes are no finer than the medoids' own, so no cluster of medoids spans two
+        order = {medoid: k for k, medoid in enumerate(by_medoid)}
+        wide = Components(names, ctx.fill_components(metric, clu[0], as_distance=True, strict=True)).groups()
+        medoid_groups = [sorted((name for name in group if name in order), key=order.__getitem__) for group in wide]
+        medoid_groups = [group for group in medoid_groups if group]
+        of_first = {m.nodes[0]: m for m in submatrices(medoid_groups)}
+        merged = []
+        for cluster in cluster_by_component(medoid_groups, lambda group: of_first[group[0]], clu[1], clu[0], nodes=list(by_medoid)):
+            merged.append([node for medoid in cluster.nodes for node in by_medoid[medoid].nodes])
+        merged = submatrices(merged)
+        multi = sorted((m for m in merged if len(m) > 1), reverse=True)
+        single = [m for m in merged if len(m) == 1]
+        n = len(names)
+        log.info(f"{len(groups)} pre-groups -> {len(multi)} clusters + {len(single)} singletons in {time.perf_counter() - t0:.3f} s: one upload, "
+                 f"2 components fills, {filled[0]} groups fills of {filled[1]:,} pairs in all instead of {n * (n - 1) // 2:,}")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        return multi, single
+
     # 4
     def write_cluster(self, number, cluster, sub, k_min, no_sub):
         root = self._dir(self.stage / f"cluster_{number}", fresh=True)
@@ -340,14 +394,39 @@ class _Run:
             shutil.rmtree(self.cache)
 
 
+    # 5 + 6, --no-matrix
+    def finish_no_matrix(self, rm_tmp):
+        self.banner(5, "dataset outputs")
+        log.info(f"--no-matrix: pairwise_{self.metric}_similarities.tsv and the dataset heatmap need the dense matrix and are not written; "
+                 f"the adjacency file comes from an edge-list fill")
+        for old in self.outdir.iterdir():                      # clear earlier results, keep cache and log
+            if old.name == self.cache.name or old.suffix == ".log":
+                continue
+            shutil.rmtree(old) if old.is_dir() else old.unlink()
+        ctx, metric, names = self.fills                        # the upload of clusters_no_matrix: the run's only one
+        src, tgt, val, st = ctx.fill_edges(metric, 0.999999, as_distance=True, want_stats=True)    # 6-place values: d <= 0.999999 is sim > 0
+        edges = SparseEdges(names, src, tgt, val, is_distance=True, threshold=0.999999)
+        log.info(f"{len(edges):,} pairs of non-zero similarity from {st.get('n_slabs', 1)} slab(s) of the edge-list fill")
+        edges_to_adjacency(edges.inverted(), self.outdir / f"pairwise_{self.metric}_adjacency.tsv", skip_zero=True)
+        shutil.copytree(self.stage, self.outdir, dirs_exist_ok=True)
+        shutil.rmtree(self.stage)
+        if rm_tmp:
+            shutil.rmtree(self.cache)
+
+
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False):
+              components_only=False, no_matrix=False):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
     ``components_only``: stop after a components fill -- genomes joined when distance < round(1 - ``edge_thresh``, 6), None: 0.0 --
-    and write only ``components_<metric>.tsv``."""
+    and write only ``components_<metric>.tsv``; ``no_matrix``: stages 2-3 from components and groups fills, without the dense matrix
+    (same clusters; no similarities file, no dataset heatmap, no matrix cache; the adjacency file from an edge-list fill)."""
+    if no_matrix and (adjacency_only or components_only or extend is not None):
+        raise ValueError("no-matrix cannot be combined with adjacency_only, components_only or extend")
+    if no_matrix and "ward" in (nr_linkage, clu_linkage):
+        raise ValueError("no-matrix: ward's clusters can span components; the nr and clu passes take single, average or complete")
     if adjacency_only and extend is not None:
         raise ValueError("adjacency_only cannot be combined with extend")
     if components_only and (adjacency_only or extend is not None):
@@ -363,6 +442,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["extend"] = extend
     if adjacency_only:
         settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}")
+    if no_matrix:
+        settings["matrix"] = "none (--no-matrix: components and groups fills)"
     if components_only:
         settings["components"] = f"only, joined at similarity > {0.0 if edge_thresh is None else edge_thresh}"
     log.info("--- 0: settings ---")
@@ -387,10 +468,17 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         run.components(0.0 if edge_thresh is None else edge_thresh)
         run.banner(3, "done (--components-only: no clustering)")
         return
-    matrix = run.distances(cpus)
-    if matrix is None:                        # ranks other than 0 are done once their shard is gathered
-        return
-    multi, single = run.clusters(matrix, (nr_distance, nr_linkage), (clu_distance, clu_linkage))
+    matrix = None
+    if no_matrix:
+        if run.world > 1:
+            log.error("--no-matrix runs on one GPU: run it in one process, not under a launcher")
+            sys.exit(1)
+        multi, single = run.clusters_no_matrix((nr_distance, nr_linkage), (clu_distance, clu_linkage))
+    else:
+        matrix = run.distances(cpus)
+        if matrix is None:                    # ranks other than 0 are done once their shard is gathered
+            return
+        multi, single = run.clusters(matrix, (nr_distance, nr_linkage), (clu_distance, clu_linkage))
     run.banner(4, "sub-clusters")
     run.stage = run._dir(run.cache / "03_clusters")
     for number, cluster in enumerate(multi, start=1):
@@ -401,7 +489,10 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         for one in single:
             name = one.nodes[0]
             run.by_name[name].save(lone / f"{name}.faa")
-    run.finish(matrix, multi, single, clu_distance, rm_tmp)
+    if no_matrix:
+        run.finish_no_matrix(rm_tmp)
+    else:
+        run.finish(matrix, multi, single, clu_distance, rm_tmp)
 
 
 def _colors(text):
@@ -506,7 +597,7 @@ def _run(args, argv):
                   sub_distance=as_distance(args.sub_thresh), sub_linkage=args.sub_linkage, k_min=max(1, args.k_min),
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
-                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only)
+                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
