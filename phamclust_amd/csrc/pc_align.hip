@@ -429,10 +429,38 @@ static void set_last_plan_tasks(pc_ctx* c, const std::vector<uint32_t>& per_clas
     c->last_plan_tasks_valid = true;
 }
 
+// One plan -> align -> reduce over the owned targets (or query rows, or row blocks) [k0, k1) holding A alignments, and its counts added
+// to `local`.  events: ev[1] and ev[2] are recorded between the stages (ev[3] after them always); ms != NULL: the step is waited for and its
+// three stage times, the first counted from `from`, are added to ms[0..2].
+static int chunk_step(pc_ctx* c, int metric, int ppos, int as_distance, int condensed, double* out, hipStream_t st, int k0, int k1, uint64_t A,
+                      const PcRows* rows, const PcGroupsHost* groups, pc_stats& local, bool events, hipEvent_t from, float* ms) {
+    int rc = stage_plan(c, ppos, condensed, st, k0, k1, A, rows, groups);
+    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
+    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, rows, groups); }
+    if (rc != PC_OK) return rc;
+    PC_HIP(hipEventRecord(c->ev[3], st));
+    add_plan_stats(c, local);
+    if (ms) {
+        const hipEvent_t at[4] = {from, c->ev[1], c->ev[2], c->ev[3]};
+        PC_HIP(hipEventSynchronize(c->ev[3]));
+        for (int i = 0; i < 3; ++i) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, at[i], at[i + 1])); ms[i] += x; }
+    }
+    return PC_OK;
+}
+// out of HBM in a step: free the plan (and the strip-mined launches' slab; slots: and the slot arrays of a range of units) once nothing
+// reads them any more; the caller goes on with half the chunk
+static int release_for_retry(pc_ctx* c, hipStream_t st, bool slots) {
+    PC_HIP(hipStreamSynchronize(st));
+    release_plan_buffers(c);
+    c->b_scratch.release();
+    if (slots) { c->b_na.release(); c->b_off.release(); }
+    return PC_OK;
+}
+
 // aai / peq: COUNT once, then plan -> align -> reduce -- in one piece when the plan fits the budget, else chunk by chunk
 int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed) {
     int rc = PC_OK;
-    if (!c->residues_ready) { pc_set_error("fill: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    if ((rc = fill_check_residues(c, "fill", metric))) return rc;
     uint64_t tot[3] = {0, 0, 0};
     c->last_plan_tasks_valid = false;
     c->last_plan_tasks.assign(c->nlc, 0);
@@ -446,65 +474,41 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
         max_aln = std::min<uint64_t>(max_aln, (uint64_t)std::max<int64_t>(plan_budget_bytes(c) / PC_PLAN_BYTES_PER_ALIGNMENT, 1));
     local.n_chunks = 0;
     if (A <= max_aln) {
-        rc = stage_plan(c, ppos, condensed, st, 0, nown, A);
+        // (its stage times are read by fill_impl: ev[0] .. ev[3])
+        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, 0, nown, A, nullptr, nullptr, local, true, nullptr, nullptr);
         if (rc == PC_OK) {
-            PC_HIP(hipEventRecord(c->ev[1], st));
-            rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local);
-        }
-        if (rc == PC_OK) {
-            PC_HIP(hipEventRecord(c->ev[2], st));
-            rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st);
-        }
-        if (rc == PC_OK) {
-            add_plan_stats(c, local);
             local.n_chunks = 1;
             c->last_plan_tasks_valid = true;
-            PC_HIP(hipEventRecord(c->ev[3], st));
             return PC_OK;
         }
         if (rc != PC_ERR_NOMEM_INTERNAL) return rc;
-        PC_HIP(hipStreamSynchronize(st));                                 // out of HBM: free the plan (and the strip-mined launches' slab), go on in chunks of half the size
-        release_plan_buffers(c);
-        c->b_scratch.release();
+        if ((rc = release_for_retry(c, st, false))) return rc;            // go on in chunks of half the size
         max_aln = std::max<uint64_t>(A / 2, 1);
         local.n_tasks = 0; local.n_distinct_alignments = local.n_distinct_cells = 0; local.n_align_launches = 0;
     }
     // ---- chunked: successive ranges of the owned targets, each planned, aligned and reduced before the next
     std::vector<uint64_t> per_owned;
     if ((rc = count_per_target(c, condensed, st, per_owned))) return rc;
-    float ms_plan = 0.f, ms_align = 0.f, ms_reduce = 0.f;
+    float ms[3] = {0.f, 0.f, 0.f};                                        // plan, align, reduce
     int k = 0, nchunks = 0;
     while (k < nown) {
         // the next chunk: as many targets from k on as stay within max_aln (pc_chunk_plan's rule)
         uint64_t run = per_owned[k]; int k1 = k + 1;
         while (k1 < nown && run + per_owned[k1] <= max_aln) { run += per_owned[k1]; ++k1; }
         if (timed) PC_HIP(hipEventRecord(c->ev[4], st));
-        rc = stage_plan(c, ppos, condensed, st, k, k1, run);
-        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
-        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st); }
+        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, k, k1, run, nullptr, nullptr, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller chunk, not an error
-            PC_HIP(hipStreamSynchronize(st));
-            release_plan_buffers(c);
-            c->b_scratch.release();
+            if ((rc = release_for_retry(c, st, false))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run) / 2, 1);
             continue;
         }
         if (rc != PC_OK) return rc;
-        PC_HIP(hipEventRecord(c->ev[3], st));
-        add_plan_stats(c, local);
-        if (timed) {
-            float x = 0.f;
-            PC_HIP(hipEventSynchronize(c->ev[3]));
-            PC_HIP(hipEventElapsedTime(&x, c->ev[4], c->ev[1])); ms_plan += x;
-            PC_HIP(hipEventElapsedTime(&x, c->ev[1], c->ev[2])); ms_align += x;
-            PC_HIP(hipEventElapsedTime(&x, c->ev[2], c->ev[3])); ms_reduce += x;
-        }
         ++nchunks; k = k1;
     }
     c->plan.valid = false;                                                // the last chunk's plan is not "the plan of the fill"
     local.n_chunks = nchunks;
     c->last_plan_tasks_valid = true;
-    local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;
+    local.ms_plan = ms[0]; local.ms_align = ms[1]; local.ms_reduce = ms[2];
     return PC_OK;
 }
 
@@ -523,7 +527,7 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
     const PcDev& d = c->dev;
     const int U = rows ? rows->nrows : groups->nblocks;
     auto slots = [&](int k0, int k1) { return rows ? (int64_t)(k1 - k0) * d.N : groups->block_slot[k1] - groups->block_slot[k0]; };
-    if (!c->residues_ready) { pc_set_error("fill: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)"); return PC_ERR_STATE; }
+    if ((rc = fill_check_residues(c, "fill", metric))) return rc;
     if (d.G > 0 && c->min_gene_len == 0) {
         pc_set_error("fill: an empty translation cannot be aligned (aai/peq); the reference fails on it too"); return PC_ERR_DATA;
     }
@@ -558,7 +562,7 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
     uint64_t max_aln = (uint64_t)PC_PLAN_MAX_ALIGNMENTS;
     if (c->plan_budget > 0 || (A + all_slot_cost) * PC_PLAN_BYTES_PER_ALIGNMENT > ((uint64_t)1 << 30))
         max_aln = std::min<uint64_t>(max_aln, (uint64_t)std::max<int64_t>(plan_budget_bytes(c) / PC_PLAN_BYTES_PER_ALIGNMENT, 1));
-    float ms_plan = 0.f, ms_align = 0.f, ms_reduce = 0.f;
+    float ms[3] = {0.f, 0.f, 0.f};                                        // plan (with the range's COUNT), align, reduce
     int k = 0, nchunks = 0;
     while (k < U) {
         int32_t cut[2] = {0, 0};
@@ -578,44 +582,32 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
             a.na = c->b_na.as<uint32_t>(); a.totals = c->b_totals.as<unsigned long long>() + 5;
             rc = walk_domain(c, PCW_COUNT, rows, groups, k, k1, a, st);
         }
-        if (rc == PC_OK) rc = stage_plan(c, ppos, 0, st, k, k1, run, rows, groups);
-        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
-        if (rc == PC_OK) { if (timed) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, rows, groups); }
+        if (rc == PC_OK) rc = chunk_step(c, metric, ppos, as_distance, 0, out, st, k, k1, run, rows, groups, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller range, not an error
-            PC_HIP(hipStreamSynchronize(st));
-            release_plan_buffers(c);
-            c->b_scratch.release(); c->b_na.release(); c->b_off.release();
+            if ((rc = release_for_retry(c, st, true))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run + run_slot_cost) / 2, 1);
             continue;
         }
         if (rc != PC_OK) return rc;
-        PC_HIP(hipEventRecord(c->ev[3], st));
-        add_plan_stats(c, local);
-        if (timed) {
-            float x = 0.f;
-            PC_HIP(hipEventSynchronize(c->ev[3]));
-            PC_HIP(hipEventElapsedTime(&x, c->ev[4], c->ev[1])); ms_plan += x;
-            PC_HIP(hipEventElapsedTime(&x, c->ev[1], c->ev[2])); ms_align += x;
-            PC_HIP(hipEventElapsedTime(&x, c->ev[2], c->ev[3])); ms_reduce += x;
-        }
         ++nchunks; k = k1;
     }
     c->plan.valid = false;                                                // such a plan serves no later stage
     local.n_chunks = nchunks;
     c->last_plan_tasks_valid = true;
-    local.ms_plan = ms_plan; local.ms_align = ms_align; local.ms_reduce = ms_reduce;
+    local.ms_plan = ms[0]; local.ms_align = ms[1]; local.ms_reduce = ms[2];
     return PC_OK;
 }
 
-// a rows fill: the units are the query rows; out: f64[rows.nrows][N]
-int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
-    return fill_units_aligned(c, &rows, nullptr, metric, ppos, as_distance, out, st, local, timed);
+// a rows fill (the units are the query rows) or a groups fill (the row blocks of TS positions), every metric: the set metrics always run
+// on the domain's walker, all units in one launch (no selector: pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill)
+int fill_units(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out, hipStream_t st,
+               pc_stats& local, bool timed) {
+    if (metric >= PC_AAI) return fill_units_aligned(c, rows, groups, metric, ppos, as_distance, out, st, local, timed);
+    PcWalkArgs a; memset(&a, 0, sizeof(a));
+    a.out = out; a.as_distance = as_distance;
+    const int mode = metric == PC_GCS ? PCW_GCS : metric == PC_JC ? PCW_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
+    return walk_domain(c, mode, rows, groups, 0, rows ? rows->nrows : groups->nblocks, a, st);
 }
-// a groups fill: the units are the row blocks of TS positions; out: f64[L]
-int fill_groups_aligned(pc_ctx* c, const PcGroupsHost& groups, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
-    return fill_units_aligned(c, nullptr, &groups, metric, ppos, as_distance, out, st, local, timed);
-}
-
 
 // ---- alignment-sliced multi-GPU route (aai / peq): every rank plans the whole (unsharded) fill -- milliseconds --, aligns
 // every world-th task of each launch class, the per-alignment results are summed to the root (entries of foreign tasks are

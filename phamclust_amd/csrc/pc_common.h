@@ -140,6 +140,9 @@ struct PcSetKnobs { int popc_tile, s64_chunks, col_seg; };        // PC_POPC_TIL
 PcSetKnobs pc_set_knobs_env();                                    // (read per launch: the tests switch them between fills)
 // metric: PC_GCS ... PC_AF; sp_W: 64-id words of the phams with two holders; table_top: max_nph (gcs / jc) or max_ngen (pocp)
 void pc_set_shape_of(int family, int metric, int N, int nown, int Wb, int sp_W, int n_cu, int table_top, const PcSetKnobs& knobs, pc_set_shape* out);
+// which family fills a set metric: a function of its inputs alone (pc_set_shape.hip; pc_set_kernel_choice of the C-ABI)
+struct pc_set_inputs;
+int pc_set_choice(const pc_set_inputs& in);
 // dimensions of the popcount tiles' epilogue table; false: too large (4 Mi entries), the division runs in place
 bool pc_set_table_dims(int metric, int top, int* sh_dim, int* tot_dim);
 

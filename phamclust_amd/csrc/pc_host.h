@@ -1,4 +1,4 @@
-// pc_host.h -- internal header of the host units of libphamclust_hip.so (pc_ctx, pc_upload, pc_align, pc_fill, pc_multi.hip):
+// pc_host.h -- internal header of the host units of libphamclust_hip.so (pc_ctx, pc_upload, pc_align, pc_fill, pc_fill_slabs, pc_multi.hip):
 // the context, its buffers and the helpers they share.  Not installed, not part of the C-ABI.
 #pragma once
 #include <algorithm>
@@ -253,9 +253,35 @@ struct PcGroupsHost {
     std::vector<int64_t> block_slot;        // [nblocks+1] first slot of row block a = pos_rowbase[a * TS]; [nblocks] = L
 };
 
+// What every fill entry point checks of its context and its metric before anything of its own.  `who` names the caller in the message
+// texts; `kind` != NULL ("a rows fill"): the call takes an unsharded context only.  ppos != NULL: PC_AAI_PPOS is folded into PC_AAI + *ppos.
+static int fill_check(const pc_ctx* c, const char* who, const char* kind, int* metric, int* ppos) {
+    if (!c || !c->uploaded) { pc_set_error("%s: upload first", who); return PC_ERR_STATE; }
+    if (kind && c->world != 1) { pc_set_error("%s: context is sharded (%d/%d); %s is a one-GPU call on an unsharded context", who, c->rank, c->world, kind); return PC_ERR_STATE; }
+    if (*metric < PC_GCS || *metric > PC_AAI_PPOS) { pc_set_error("%s: metric %d", who, *metric); return PC_ERR_ARG; }
+    if (ppos && (*ppos = *metric == PC_AAI_PPOS)) *metric = PC_AAI;
+    return PC_OK;
+}
+// ... and, once the call is known to have pairs to fill: aai / peq align residues
+static int fill_check_residues(const pc_ctx* c, const char* who, int metric) {
+    if (metric < PC_AAI || c->residues_ready) return PC_OK;
+    pc_set_error("%s: aai / peq need the residues on the device (pc_upload, or pc_upload_residues after pc_upload_sets)", who);
+    return PC_ERR_STATE;
+}
+
+// sum += one, field by field (the fills of a slab walk)
+static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
+    sum.n_pairs += one.n_pairs; sum.n_alignments += one.n_alignments; sum.n_cells += one.n_cells; sum.n_tasks += one.n_tasks;
+    sum.n_residue_bytes += one.n_residue_bytes; sum.n_align_launches += one.n_align_launches; sum.n_chunks += one.n_chunks;
+    sum.ms_total += one.ms_total; sum.ms_plan += one.ms_plan; sum.ms_align += one.ms_align; sum.ms_reduce += one.ms_reduce;
+    sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
+}
+
+// the whole fill of the shard in force into out (pc_fill.hip): what pc_fill_dev / pc_fill_shard_dev run, and every slab of a slab walk
+int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st, pc_stats* stats);
 // aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
 int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);
-// the same over the query rows of a rows fill, chunked over ranges of rows; out: f64[rows.nrows][N] (pc_align.hip)
-int fill_rows_aligned(pc_ctx* c, const PcRows& rows, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);
-// the same over the within-group pairs of a groups fill, chunked over ranges of row blocks; out: f64[L] (pc_align.hip)
-int fill_groups_aligned(pc_ctx* c, const PcGroupsHost& groups, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);
+// a rows fill (rows != NULL; out: f64[rows->nrows][N]) or a groups fill (groups != NULL; out: f64[L]) once its domain tables are on the
+// device: the set metrics in one launch of the domain's walker, aai / peq chunked over ranges of query rows / of row blocks (pc_align.hip)
+int fill_units(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out, hipStream_t st,
+               pc_stats& local, bool timed);

@@ -1,5 +1,6 @@
-// pc_set_shape.hip -- the launch shapes of the five set-metric families as host arithmetic (pc_set_launch_shape of the C-ABI): every
-// launcher takes its numbers from pc_set_shape_of.  Host only, no device code; the constants come from pc_pairs.h, the column kernel's
+// pc_set_shape.hip -- the set metrics' host arithmetic: the launch shapes of the five kernel families (pc_set_launch_shape of the C-ABI;
+// every launcher takes its numbers from pc_set_shape_of) and the selector that picks the family (pc_set_choice; pc_set_kernel_choice and
+// pc_set_max_block_entries of the C-ABI).  Host only, no device code, no context; the constants come from pc_pairs.h, the column kernel's
 // LDS budget from pc_sparse_col.hip.  Restates nothing of metrics.py.
 #include "pc_pairs.h"
 #include <algorithm>
@@ -86,4 +87,88 @@ void pc_set_shape_of(int family, int metric, int N, int nown, int Wb, int sp_W, 
         out->seg = seg; out->runs = (ntx + seg - 1) / seg;
         out->grid = out->units = (int)(((unsigned)nty + 7u) / 8u * 8u * ((unsigned)out->runs + 2u));     // (runs 0, 1: every block's diagonal run and the one below; then the runs, highest first)
     }
+}
+
+#ifndef PC_COL_MIN_N
+#define PC_COL_MIN_N 2200        // genomes from which k_sparse_col takes over from the popcount tiles (r05 sweep: profiles/r05/experiments/sparse_col.txt)
+#endif
+
+// Which kernel fills a set metric (measured crossovers, `profiles/r03/experiments/p_sparse64_record.txt`, `r03_z_pocp_kernel_by_density.txt`;
+// PC_SET_KERNEL = popc | sparse | sparse64 | sparsecol | walker forces one where it exists, applied last, for A/B runs and for the
+// tests that keep every one of them honest):
+//   gcs, jc          popcount tiles; a collection of many phams (long bitmap rows, few of them shared): the 64 x 64 sparse tile
+//                    kernel in its counting mode
+//   pocp             popcount tiles + paralog excess; from ~2,500 genomes the 64 x 64 sparse tile kernel where pairs share few
+//                    enough of the phams
+//   af               the 64 x 64 sparse tile kernel (the 32 x 32 one where that kernel's preconditions fail), the column kernel from ~1,400 genomes
+// The popcount tiles cost ~ pairs x bitmap words W, the sparse tiles ~ pairs x (a constant + the phams a pair shares).  Measured on
+// synth(5000, P), P = 300 ... 40,000, in ms: pocp 0.15 + 0.002 W against 0.207 + 0.0085 shared (sparse wins where W > 28 + 4.3 shared:
+// the synthetic collection's 79 words and 2.85 shared phams yes, 300 phams -- 5 words, 34 shared -- three times no); gcs / jc
+// 0.05 + 0.0014 W against 0.155 + 0.0004 W + ~0.005 shared (W > 113 + 5.4 shared: from ~7,500 phams; at 40,000: 0.43 against 0.90).
+// `shared` of an average pair = sum over phams of n_p (n_p - 1) / (N (N - 1)), counted at upload.
+// The 64 x 64 kernel takes "sum == 0" for "no shared pham" and sums in 32 bits: it needs every entry value >= 1 (a
+// genome with an empty translation fails that for af) and genome totals below 2^31; else af falls back to the
+// 32 x 32 kernel / the shared-pham walker (crossover ~3,500 genomes), pocp to the popcount tiles.
+// The choice itself is pc_set_choice: a function of pc_set_inputs alone (pc_set_kernel_choice of the C-ABI); pick_set_kernel
+// (pc_fill.hip) gathers the inputs from the context and the environment.
+int pc_set_choice(const pc_set_inputs& in) {
+    int kernel = K_POPC;
+    const int metric = in.metric, Wb = in.words;
+    const int P64 = std::max(1, (in.two_holder + 63) / 64) * 64;       // mask entries: the phams with two holders, in 64-id words
+    const int64_t area = in.n * in.nown;
+    const double shared = std::max(in.avg_shared, 0.0);
+    const bool counts = metric == PC_GCS || metric == PC_JC;
+    const bool s64_ok = counts ? in.max_nph < (1 << 30) : metric == PC_POCP ? in.max_ngen < (1 << 16) /* two gene counts per register */ : (in.min_gene_len >= 1 && in.max_tlen < (int64_t)1 << 31);
+    if (counts) kernel = (((double)Wb > 113.0 + 5.4 * shared && area >= (int64_t)3000 * 3000) ||
+                          ((double)Wb > 60.0 + 5.4 * shared && area >= (int64_t)6000 * 6000)) ? K_SPARSE64 : K_POPC;   // (the sparse tiles gain on the popcount tiles as N grows: 5,056 phams, r04 with four workgroups per CU: N = 5,000 0.162 against 0.157 ms, 6,000 0.218 / 0.219, 7,000 0.258 / 0.282, 20,000 1.56 / 2.03)
+    else if (metric == PC_POCP) kernel = (s64_ok && (double)Wb > 28.0 + 4.3 * shared && area >= (int64_t)2500 * 2500) ? K_SPARSE64 : K_POPC;
+    else if (s64_ok) kernel = K_SPARSE64;                                  // (af; r05, ms, 32 x 32 / 64 x 64 tiles: N = 200 0.060 / 0.058, 800 0.095 / 0.061, 1,300 0.082 / 0.069 -- since r04's dense broadcast path the larger tile wins at every size)
+    else kernel = area > (int64_t)3500 * 3500 ? K_WALKER : K_SPARSE32;
+    // r05: the column kernel for all four (k_sparse_col: the masks over a block of targets stay in LDS for a run of source tiles, no
+    // barrier per tile) -- while its masks fit 78 KB of LDS (pocp / af: beside a table of the block's entry values).  Against the popcount tiles
+    // (profiles/r05/experiments/sparse_col.txt; ms, popcount / column): 5,056 phams (79 words, 2.85 shared) N = 2,000 0.035 / 0.034,
+    // 3,000 0.070 / 0.046, 8,000 0.35 / 0.20, 20,000 2.03 / 0.99; 2,500 phams (40 words) N = 5,000 0.098 / 0.110; 1,200: 0.067 / 0.146
+    const int sp_mode = counts ? (metric == PC_GCS ? PCW_SPARSE_GCS : PCW_SPARSE_JC) : metric == PC_POCP ? PCW_POCP : PCW_AF;
+    bool col_ok = s64_ok && pc_sparse_col_lds(sp_mode, P64) > 0;
+    if (col_ok && !counts)                                             // ... pocp / af: every block's entries fit its LDS value table, as 16-bit values
+        col_ok = (metric == PC_POCP || in.max_ent_len < 65536) &&      // (pocp: s64_ok already holds the gene counts below 65,536)
+                 in.max_block_entries <= (int64_t)pc_sparse_col_vals_cap(P64);
+    // (ms, popcount tiles / 64 x 64 sparse tiles / column -- pocp: N = 2,000 0.066 / 0.082 / 0.078, 3,000 0.137 / 0.118 / 0.083, 5,000 0.304 / 0.217 / 0.156,
+    // 20,000 3.89 / 2.23 / 1.45; af: 2,000 - / 0.089 / 0.078, 3,000 - / 0.121 / 0.081, 5,000 - / 0.258 / 0.150, 20,000 - / 2.41 / 1.42)
+    const int64_t col_min_n = metric == PC_AF ? 1400 : PC_COL_MIN_N;        // (af, 64 x 64 tiles / column: N = 1,000 0.062 / 0.072, 1,300 0.069 / 0.073, 1,500 0.087 / 0.074, 1,800 0.088 / 0.077)
+    if (col_ok && (double)Wb > 40.0 + 8.0 * shared && area >= col_min_n * col_min_n) kernel = K_SPARSE_COL;
+    if (in.forced == K_SPARSE_COL && col_ok) kernel = K_SPARSE_COL;         // a forced family is taken where it exists for the metric and its guards hold
+    else if (in.forced == K_POPC && metric != PC_AF) kernel = K_POPC;
+    else if (in.forced == K_SPARSE32 && !counts) kernel = K_SPARSE32;
+    else if (in.forced == K_SPARSE64 && s64_ok) kernel = K_SPARSE64;
+    else if (in.forced == K_WALKER && !counts) kernel = K_WALKER;
+    return kernel;
+}
+// pc_set_inputs.max_block_entries: the targets a rank owns, ascending, in blocks of 64 as k_sparse_col takes them -- the last block of a
+// shard is ragged and counts like any other
+extern "C" int64_t pc_set_max_block_entries(const uint32_t* entries_per_genome, const int32_t* owned, int64_t nown) {
+    if (nown < 0 || (nown > 0 && (!entries_per_genome || !owned))) { pc_set_error("pc_set_max_block_entries: bad argument"); return PC_ERR_ARG; }
+    int64_t most = 0;
+    for (int64_t k0 = 0; k0 < nown; k0 += 64) {
+        int64_t n = 0;
+        for (int64_t k = k0; k < std::min(k0 + 64, nown); ++k) n += entries_per_genome[(size_t)owned[k]];
+        most = std::max(most, n);
+    }
+    return most;
+}
+extern "C" int pc_set_kernel_choice(const pc_set_inputs* in) {
+    if (!in || in->metric < PC_GCS || in->metric > PC_AF || in->n < 0 || in->nown < 0 || in->nown > in->n || in->words < 1 || in->two_holder < 0) {
+        pc_set_error("pc_set_kernel_choice: bad argument"); return PC_ERR_ARG;
+    }
+    return pc_set_choice(*in);
+}
+extern "C" int pc_set_launch_shape(int family, int metric, int64_t n, int64_t nown, int words, int two_holder, int n_cu, int table_top,
+                                   const int32_t* knobs, pc_set_shape* out) {
+    if (!out || family < K_POPC || family > K_SPARSE_COL || metric < PC_GCS || metric > PC_AF || n < 0 || n > INT32_MAX || nown < 0 || nown > n ||
+        words < 1 || two_holder < 0 || table_top < 0 || (metric == PC_AF && family == K_POPC) || (metric <= PC_JC && (family == K_SPARSE32 || family == K_WALKER))) {
+        pc_set_error("pc_set_launch_shape: bad argument"); return PC_ERR_ARG;
+    }
+    const PcSetKnobs k = knobs ? PcSetKnobs{knobs[0], knobs[1], knobs[2]} : PcSetKnobs{0, 0, 0};
+    pc_set_shape_of(family, metric, (int)n, (int)nown, words, std::max(1, (two_holder + 63) / 64), n_cu, table_top, k, out);
+    return PC_OK;
 }

@@ -337,6 +337,17 @@ class Context:
                 arr._end_loan()
         self._loans = []
 
+    def _lend(self, ptr, shape, borrow=True):
+        """``shape`` elements at ``ptr``, the context's page-locked memory: lent as a read-only view that is told when its loan
+        ends (``borrow``), or copied."""
+        view = np.ctypeslib.as_array(ptr, shape=shape)
+        if not borrow:
+            return view.copy()
+        view.flags.writeable = False
+        out = BorrowedArray(view, self)
+        self._loans.append(weakref.ref(out))
+        return out
+
     @property
     def n_genomes(self):
         return self._packed.n_genomes
@@ -385,10 +396,7 @@ class Context:
         if borrow:
             ptr = _f64p()
             self._check(self._lib.pc_fill_borrow(self._h, METRIC_IDS[metric], int(bool(as_distance)), ctypes.byref(ptr), ctypes.byref(stats)))
-            view = np.ctypeslib.as_array(ptr, shape=(max(self.n_pairs, 1),))[:self.n_pairs]
-            view.flags.writeable = False
-            out = BorrowedArray(view, self)
-            self._loans.append(weakref.ref(out))
+            out = self._lend(ptr, (max(self.n_pairs, 1),))[:self.n_pairs]
             return (out, stats.as_dict()) if want_stats else out
         out = np.empty(max(self.n_pairs, 0), dtype=np.float64)
         buf = out if out.size else np.zeros(1)
@@ -496,19 +504,8 @@ class Context:
         self._check(self._lib.pc_fill_edges(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(slab_bytes),
                                             ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl),
                                             ctypes.byref(stats)))
-        out = []
-        for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64)):
-            if n.value == 0 or not ptr:
-                out.append(np.empty(0, dtype=dtype))
-                continue
-            view = np.ctypeslib.as_array(ptr, shape=(n.value,))
-            if borrow:
-                view.flags.writeable = False
-                view = BorrowedArray(view, self)
-                self._loans.append(weakref.ref(view))
-            else:
-                view = view.copy()
-            out.append(view)
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
         if not want_stats:
             return tuple(out)
         a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
@@ -533,16 +530,7 @@ class Context:
                                                  int(slab_bytes), ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl),
                                                  ctypes.byref(stats)))
         n = self.n_genomes
-        if n == 0 or not pl:
-            labels = np.empty(0, dtype=np.int32)
-        else:
-            labels = np.ctypeslib.as_array(pl, shape=(n,))
-            if borrow:
-                labels.flags.writeable = False
-                labels = BorrowedArray(labels, self)
-                self._loans.append(weakref.ref(labels))
-            else:
-                labels = labels.copy()
+        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
         if not want_stats:
             return labels
         a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
@@ -777,6 +765,7 @@ class MultiContext:
     _check = Context._check
     _struct = staticmethod(Context._struct)
     _invalidate_loans = Context._invalidate_loans
+    _lend = Context._lend
 
     @property
     def n_devices(self):
@@ -830,10 +819,7 @@ class MultiContext:
         ptr, x_ms, a_ms = _f64p(), ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._lib.pc_multi_fill_borrow(self._h, METRIC_IDS[metric], int(bool(as_distance)), ctypes.byref(ptr), stats,
                                                    ctypes.byref(x_ms), ctypes.byref(a_ms)))
-        view = np.ctypeslib.as_array(ptr, shape=(max(self.n_pairs, 1),))[:self.n_pairs]
-        view.flags.writeable = False
-        out = BorrowedArray(view, self)
-        self._loans.append(weakref.ref(out))
+        out = self._lend(ptr, (max(self.n_pairs, 1),))[:self.n_pairs]
         if not borrow:
             out = out.copy()
         if not want_stats:

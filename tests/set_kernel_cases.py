@@ -254,7 +254,7 @@ CASES = {
     "uniform4000": (VALUES, (2,), "sample"), "uniform6000": (SET_METRICS, WORLDS, "sample"),
     "col2500": (SET_METRICS, (), "whole"), "col4100": (SET_METRICS, WORLDS, "whole"), "col7200": (SET_METRICS, WORLDS, "sample"),
 }
-# The family each collection's UNSHARDED fill runs on, (gcs, jc, pocp, af), stated from pc_fill.hip's rules and the collections' profiles --
+# The family each collection's UNSHARDED fill runs on, (gcs, jc, pocp, af), stated from pc_set_shape.hip's rules and the collections' profiles --
 # few*: 19 words against 113 / 28 / 40 + a multiple of 8.4 shared: popcount tiles, af on sparse64 (with an empty translation: 32 x 32 tiles
 # up to 3,500^2 pairs, then the walker); many*: 157 / 313 words, masks beyond the column kernel: sparse64 from 3,000^2 (pocp 2,500^2);
 # real*: 267 words at N = 3,000 (9,000,000 pairs: sparse64), 175 at 2,000 (popcount tiles); uniform*: gcs / jc on the column kernel, pocp / af

@@ -338,6 +338,29 @@ def test_state_restored_and_errors(ctx, small_packed):
     assert st["ms_union"] > 0.0 and st["ms_labels"] > 0.0
 
 
+def test_a_refusal_inside_the_walk_restores_the_shard(ctx):
+    """A slab's fill refused in the middle of the walk: three genomes, one with an empty translation in a shared pham, slab_bytes=8 --
+    two slabs, target 2 gets a range of its own.  peq is refused with the library's data status (-5) from inside the first slab's
+    fill, while that slab's one-target shard is in force; afterwards the context is the unsharded one it was: three pairs, the
+    dense jc fill unchanged, and a components fill over the same two slabs agrees with it."""
+    from phamclust_amd.genome import Genome
+    from phamclust_amd.hip import HipLibraryError
+    from phamclust_amd.pack import pack_genomes
+    empty, other, third = Genome("e1"), Genome("e2"), Genome("e3")
+    empty.add("p1", "")
+    other.add("p1", "MK")
+    third.add("p1", "MKV"); third.add("p2", "MA")
+    ctx.upload(pack_genomes([empty, other, third]))
+    before = ctx.fill("jc")
+    assert before.shape == (3,)
+    with pytest.raises(HipLibraryError, match="status -5.*empty translation"):
+        ctx.fill_components("peq", 0.75, slab_bytes=8)
+    assert ctx.shard_pairs() == 3 == ctx.shard_stride()
+    assert np.array_equal(ctx.fill("jc"), before)
+    for thr in (2.0, float(before.max())):                        # every pair; strictly below the largest distance
+        check(ctx, "jc", Dense(before, 3), thr, True, 8, n_slabs=2)
+
+
 # ---- 7: above the C-ABI ------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric", ["jc", "peq"])
 def test_components_de_novo_gives_the_single_linkage_groups(small_genomes, native_built, metric):

@@ -241,6 +241,31 @@ def test_state_restored_and_errors(ctx, small_packed):
     assert lib.pc_fill_edges(h, 1, 1, 0.75, 0, ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(ne), ctypes.byref(ns), None) == 0 and ne.value > 0
 
 
+def test_a_refusal_inside_the_walk_restores_the_shard(ctx):
+    """A slab's fill refused in the middle of the walk: three genomes, one with an empty translation in a shared pham, slab_bytes=8 --
+    two slabs, target 2 gets a range of its own.  peq is refused with the library's data status (-5) from inside the first slab's
+    fill, while that slab's one-target shard is in force; afterwards the context is the unsharded one it was: three pairs, the
+    dense jc fill unchanged, and an edge-list fill over the same two slabs agrees with it."""
+    from phamclust_amd.genome import Genome
+    from phamclust_amd.hip import HipLibraryError
+    from phamclust_amd.pack import pack_genomes
+    empty, other, third = Genome("e1"), Genome("e2"), Genome("e3")
+    empty.add("p1", "")
+    other.add("p1", "MK")
+    third.add("p1", "MKV"); third.add("p2", "MA")
+    ctx.upload(pack_genomes([empty, other, third]))
+    before = ctx.fill("jc")
+    assert before.shape == (3,)
+    with pytest.raises(HipLibraryError, match="status -5.*empty translation"):
+        ctx.fill_edges("peq", 0.75, slab_bytes=8)
+    assert ctx.shard_pairs() == 3 == ctx.shard_stride()
+    assert np.array_equal(ctx.fill("jc"), before)
+    for thr in (2.0, 0.25):                                       # every pair; the pairs of equal genomes only
+        *got, st = ctx.fill_edges("jc", thr, slab_bytes=8, want_stats=True)
+        assert st["n_slabs"] == 2 and st["n_pairs"] == 3
+        assert_edges(got, expected_edges(before, 3, thr, True), ("after the refusal", thr))
+
+
 # ---- 6: the reference's own file --------------------------------------------------------------------
 def test_adjacency_only_run_writes_the_reference_file(tmp_path, small_genomes, native_built):
     from phamclust_amd import cli

@@ -1423,7 +1423,7 @@ def _set_kernel_case(rng, n_genomes, n_phams, wide_rows=(), shared_by_all=(), em
 
 def test_every_pocp_af_kernel_agrees(gpu_ctx, native_built):
     """pocp / af have four kernels behind one selector (popcount tiles + paralog excess, the 32 x 32 and 64 x 64 sparse tile
-    kernels, the shared-pham walker; pc_fill.hip picks by size).  Each one, forced through PC_SET_KERNEL, must give the oracle's
+    kernels, the shared-pham walker; pc_set_shape.hip picks by size).  Each one, forced through PC_SET_KERNEL, must give the oracle's
     matrix (metrics.py:83-157) on a data set that reaches their corners: more phams than one mask chunk holds (64 x 64: three
     chunks), rows with more entries than a wave keeps in registers, phams shared by every genome and by blocks of genomes
     (broadcast adds), genomes without genes, similarity and distance, unsharded and as a shard."""

@@ -393,7 +393,7 @@ def test_planner_collection_reaches_every_launch_class(native_built):
     assert all(1 <= lb <= 65535 and 1 <= rows <= pc.MAX_ROWS for lb, rows, _ in cases)
 
 
-# ---- the set-metric selector and its launch shapes (host arithmetic of pc_fill.hip / pc_set_shape.hip) -----------------------
+# ---- the set-metric selector and its launch shapes (host arithmetic of pc_set_shape.hip) -----------------------
 def _choice_base(**over):
     """synth(N, 5000)'s profile: 79 bitmap words, 5,000 phams with two holders (5,056 mask entries), 2.85 phams shared per pair;
     blocks of 6,500 entries against the value table's 7,231 at that mask count."""
@@ -405,7 +405,7 @@ def _choice_base(**over):
 
 def test_set_kernel_choice_pins(native_built):
     """pc_set_kernel_choice, the selector as a function of its inputs (no GPU, no context), on both sides of every threshold and
-    guard of pick_set_kernel -- worked out by hand from pc_fill.hip, not read off the function."""
+    guard of pick_set_kernel -- worked out by hand from pc_set_shape.hip, not read off the function."""
     from phamclust_amd import hip
     C = hip.Context
 

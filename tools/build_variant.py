@@ -2,7 +2,7 @@
 """Build csrc/libphamclust_hip_<name>.so from the current sources with extra compiler flags, for A/B runs in one GPU call
 (PHAMCLUST_NATIVE_VARIANT=<name> loads it: phamclust_amd/hip.py).
 
-usage: build_variant.py NAME [--only pc_sparse.hip[,pc_fill.hip]] [-DFLAG=VALUE ...]
+usage: build_variant.py NAME [--only pc_sparse.hip[,pc_set_shape.hip]] [-DFLAG=VALUE ...]
 --only: compile just these units with the flags and link them with the release build's objects of the others (seconds, not a minute).
 """
 import os
