@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "pc_common.h"
+#include "pc_nw_events.h"
 #include "../../include/phamclust_hip.h"
 
 // NCBI BLOSUM62 over ARNDCQEGHILKMFPSTWYVBZX* (SURVEY.md section 8c); codes >= 23 use the '*' row.
@@ -81,6 +82,7 @@ static __constant__ int8_t c_b62[24][24] = {
 #define PCF_RESET 0x200
 #define PC_MAX_SEG 16
 #define PC_WIN 32                                   // stream entries staged per refill (one segment per 64-lane pass; 64 was measured: no gain)
+static_assert(PC_WIN == PC_EV_WIN, "pc_nw_events.h schedules the flag events of windows of PC_WIN entries");
 
 // ---------------------------------------------------------------------------------
 // The DP cell as a LEXICOGRAPHIC MAX on 64-bit words (r02; the r01 cell carried scores and statistics in separate
@@ -483,8 +485,13 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
     const uint32_t ring_lane = (uint32_t)(in_seg ? seg : 0) * PC_WIN;
 
     // Stage PC_WIN stream entries of every segment starting at stream position `base` (64 / PC_WIN segments per pass).
+    // The entries' flags go into the event schedule `ev` (pc_nw_events.h) on the way: two ballots per pass, the pass's two segments in
+    // the two halves of each.
+    PcEvents ev;
+    pc_ev_init(ev);
     auto refill = [&](int base) {
         pc_wave_lds_sync();
+        uint32_t resetw = 0, lastw = 0;
         for (int s0 = 0; s0 < nseg; s0 += 64 / PC_WIN) {
             const int sg = s0 + half;
             uint32_t entry = 0;
@@ -504,7 +511,12 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
                 }
                 ring[sg * PC_WIN + hl] = entry;
             }
+            const unsigned long long rb = __builtin_amdgcn_ballot_w64((entry & PCF_RESET) != 0), lb2 = __builtin_amdgcn_ballot_w64((entry & PCF_LAST) != 0);
+            resetw |= (uint32_t)rb | (uint32_t)(rb >> 32);
+            lastw |= (uint32_t)lb2 | (uint32_t)(lb2 >> 32);
         }
+        if (base != 0) pc_ev_advance(ev);
+        pc_ev_place(ev, resetw, lastw, (uint32_t)k_out);
         pc_wave_lds_sync();
     };
     auto row_addr = [&](uint32_t entry) -> uint32_t {               // LDS address of my strip of the entry's profile row
@@ -533,7 +545,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
             for (int q = 0; q < NDM; ++q) pm[q] = r0[(ND + q) * 64];
         } else pm[0] = 0;
     }
-    const unsigned long long headm = __builtin_amdgcn_ballot_w64(is_head), outm = __builtin_amdgcn_ballot_w64(is_out), headoutm = headm | outm;
+    const unsigned long long headm = __builtin_amdgcn_ballot_w64(is_head);
     // boundary values the head lanes take (VGPR operands): E = -inf, statistics 0, the base step
     const uint32_t v_nege = (uint32_t)(PC_NEG4 + TG::tE), v_zero = 0, v_base_step = PC_BASE_STEP;
     // A head lane's boundary values sit on the base of the alignment its stream is in: Ho^(i,-1) = -22 and Ho^(-1,-1) = -12
@@ -543,14 +555,13 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
     auto step = [&](int t, auto even_tag, uint32_t a, uint32_t& a_nxt) {
         constexpr bool even = decltype(even_tag)::value;
         if (even && ((t + 2) & (PC_WIN - 1)) == 0) refill(t + 2);
-        // Step prologue, 9 VALU instructions.  The five neighbour exchanges are v_cndmask_b32_dpp: lane k takes lane
+        // Step prologue, 8 VALU instructions.  The five neighbour exchanges are v_cndmask_b32_dpp: lane k takes lane
         // k-1's value (DPP wave_shr:1 on src0, executed with every lane active), head lanes (vcc) take src1 = their
         // boundary value instead: the next entry from the ring, Ho^(i,-1) = -22, E = -inf, stats 0.  Ho and E are 64-bit
         // words now, so the four value exchanges are their two halves each -- the same count as the r01 kernel's
-        // (Ho, E, SH, SE).  The flag tests and the first cell's diagonal term use SDWA byte selects on the raw entry.
-        // K.BYTE_2 == 1.
+        // (Ho, E, SH, SE).  The first cell's diagonal term uses SDWA byte selects on the raw entry.  No lane looks at its
+        // entry's flags here: whether this step has a flag event is a bit of `ev`.
         uint32_t HoL_hi, HoL_lo, EL_hi, EL_lo, D0_hi, D0_lo;
-        unsigned long long anym;
         if constexpr (INC16) {
             asm volatile(
                 "s_nop 1\n\t"                                               // VALU (previous step's cells) -> DPP read: 2 wait states
@@ -560,16 +571,14 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
                 "v_cndmask_b32_dpp %[Eh], %[oEh], %[neg], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                 "v_cndmask_b32_dpp %[Hl], %[Hwl], %[zero], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                 "v_mov_b32_dpp %[El], %[oEl] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    // head: E = -inf never wins, its statistics are never read
-                "v_cmp_ne_u32_sdwa %[anym], %[a], %[zero] src0_sel:BYTE_1 src1_sel:DWORD\n\t"                    // any flag (LAST, RESET) on my entry
                 "v_add_u32_sdwa %[D0h], %[pw0], %[Hodh] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n\t"
-                "v_add_u32_sdwa %[D0l], %[pm0], %[Hodl] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD\n\t"
-                "s_and_b64 %[anym], %[anym], %[hom]\n\t"                    // ... in a head lane or in the lane that holds column lb-1 (scalar: the compiler would do this AND on the VALU)
+                "v_add_u32_sdwa %[D0l], %[pm0], %[Hodl] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD"
                 : [an] "=&v"(a_nxt), [Hh] "=&v"(HoL_hi), [Eh] "=&v"(EL_hi), [Hl] "=&v"(HoL_lo), [El] "=&v"(EL_lo), [D0h] "=&v"(D0_hi),
-                  [D0l] "=&v"(D0_lo), [anym] "=&s"(anym)
-                : [hm] "s"(headm), [hom] "s"(headoutm), [a] "v"(a), [en] "v"(e_nxt), [Hwh] "v"(pc_hi(Hou[W - 1])), [hb] "v"(v_hb), [oEh] "v"(pc_hi(o_E)), [neg] "v"(v_nege),
+                  [D0l] "=&v"(D0_lo)
+                : [hm] "s"(headm), [a] "v"(a), [en] "v"(e_nxt), [Hwh] "v"(pc_hi(Hou[W - 1])), [hb] "v"(v_hb), [oEh] "v"(pc_hi(o_E)), [neg] "v"(v_nege),
                   [Hwl] "v"(pc_lo(Hou[W - 1])), [zero] "v"(v_zero), [oEl] "v"(pc_lo(o_E)), [K] "v"(K), [pw0] "v"(pw[0]), [pm0] "v"(pm[0]),
                   [Hodh] "v"(pc_hi(p_HoL)), [Hodl] "v"(pc_lo(p_HoL))
-                : "vcc", "scc");
+                : "vcc");
         } else {
             unsigned long long c2;
             asm volatile(
@@ -581,16 +590,14 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
                 "v_cndmask_b32_dpp %[Eh], %[oEh], %[neg], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                 "v_cndmask_b32_dpp %[Hl], %[Hwl], %[zero], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                 "v_mov_b32_dpp %[El], %[oEl] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                "v_cmp_ne_u32_sdwa %[anym], %[a], %[zero] src0_sel:BYTE_1 src1_sel:DWORD\n\t"                    // any flag (LAST, RESET) on my entry
                 "v_add_u32_sdwa %[D0h], %[pw0], %[Hodh] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n\t"
-                "v_addc_co_u32 %[D0l], %[c2], %[K], %[Hodl], %[c2]\n\t"
-                "s_and_b64 %[anym], %[anym], %[hom]\n\t"
+                "v_addc_co_u32 %[D0l], %[c2], %[K], %[Hodl], %[c2]"
                 : [an] "=&v"(a_nxt), [Hh] "=&v"(HoL_hi), [Eh] "=&v"(EL_hi), [Hl] "=&v"(HoL_lo), [El] "=&v"(EL_lo), [D0h] "=&v"(D0_hi),
-                  [D0l] "=&v"(D0_lo), [anym] "=&s"(anym), [c2] "=&s"(c2)
-                : [hm] "s"(headm), [hom] "s"(headoutm), [a] "v"(a), [en] "v"(e_nxt), [Hwh] "v"(pc_hi(Hou[W - 1])), [hb] "v"(v_hb), [oEh] "v"(pc_hi(o_E)), [neg] "v"(v_nege),
+                  [D0l] "=&v"(D0_lo), [c2] "=&s"(c2)
+                : [hm] "s"(headm), [a] "v"(a), [en] "v"(e_nxt), [Hwh] "v"(pc_hi(Hou[W - 1])), [hb] "v"(v_hb), [oEh] "v"(pc_hi(o_E)), [neg] "v"(v_nege),
                   [Hwl] "v"(pc_lo(Hou[W - 1])), [zero] "v"(v_zero), [oEl] "v"(pc_lo(o_E)), [K] "v"(K), [bc0] "v"(bc[0]), [pw0] "v"(pw[0]),
                   [Hodh] "v"(pc_hi(p_HoL)), [Hodl] "v"(pc_lo(p_HoL))
-                : "vcc", "scc");
+                : "vcc");
         }
         const uint32_t nxt_addr = row_addr(a_nxt);                        // the next row's strip
         pc_lds_u32* nxt = (pc_lds_u32*)(size_t)nxt_addr;
@@ -598,17 +605,13 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
             const uint2 e2 = *(const uint2*)&ring[ring_lane + ((t + 2) & (PC_WIN - 1))];
             e_nxt = e2.x; e_b = e2.y;
         } else e_nxt = e_b;
-        // Flags are rare (two entries per row, and only a head lane or the output lane acts on them): one compare per step,
-        // the two that tell them apart only when it fires
-        unsigned long long rstm = 0, lastm = 0;
-        asm volatile("" : "+s"(anym));                                    // scalar test (left alone, the compiler carries it as a lane mask: one VALU compare per step)
-        if (anym != 0)
-            asm volatile("v_cmp_lt_u32_sdwa %0, %2, %3 src0_sel:BYTE_2 src1_sel:BYTE_1\n\t"       // RESET: flag byte > 1 (K.BYTE_2 == 1)
-                         "v_cmp_eq_u32_sdwa %1, %2, %3 src0_sel:BYTE_2 src1_sel:BYTE_1\n\t"       // LAST:  flag byte == 1
-                         "s_and_b64 %0, %0, %4\n\t"                                              // head lanes whose stream starts an alignment
-                         "s_and_b64 %1, %1, %5"                                                  // rows ending in the lane that holds column lb-1
-                         : "=&s"(rstm), "=&s"(lastm) : "v"(K), "v"(a), "s"(headm), "s"(outm) : "scc");
-        if (rstm != 0) {                                                  // a stream starts an alignment this step (virtual row -1)
+        // Flags are rare (two entries per row, and only a head lane or the output lane acts on them): whether this step has one is
+        // a bit of the schedule, tested with scalar instructions; which lanes, only when it fires
+        if (pc_ev_reset_at(ev, t)) {                                      // a stream starts an alignment this step (virtual row -1)
+            unsigned long long rstm;
+            asm volatile("v_cmp_lt_u32_sdwa %0, %1, %2 src0_sel:BYTE_2 src1_sel:BYTE_1\n\t"       // RESET: flag byte > 1 (K.BYTE_2 == 1)
+                         "s_and_b64 %0, %0, %3"                                                  // head lanes whose stream starts an alignment
+                         : "=&s"(rstm) : "v"(K), "v"(a), "s"(headm) : "scc");
             // Nothing is cleared.  The new alignment's scores sit PC_BASE_STEP above the previous one's (only the
             // path statistics leave the kernel, never a score), so whatever the lanes still hold of the previous
             // alignment -- Hou, Fu, the diagonal term -- loses every max from here on, exactly as -inf would.
@@ -619,8 +622,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
         const double HoL = pc_pack(HoL_hi, HoL_lo);
         p_HoL = HoL;
         PcRow<W, 0, RULE, INC16, POL>::run(pc_pack(D0_hi, D0_lo), HoL, pc_pack(EL_hi, EL_lo), Hou, Fu, bc, pw, pm, nxt, a, K, o_E);
-        asm volatile("" : "+s"(lastm));                                   // test here, not 140 instructions earlier (the compiler would carry the result as a lane mask: one VALU compare)
-        if (lastm != 0) {                                                 // a row's last cell left the lane holding column lb-1
+        if (pc_ev_last_at(ev, t)) {                                       // a row's last cell left the lane holding column lb-1
             asm volatile("" ::: "memory");                                // keep this wave-uniform (scalar) test a branch of its own
             if ((a & PCF_LAST) && is_out) {
                 const uint32_t st = PcPick<W, 0>::get(Hou, c_out);
