@@ -344,6 +344,8 @@ int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, const double*
  * genomes.  n_ident = comp.count("|"), n_diag = aligned (non-gap) columns, so
  * len(traceback.query) = la + lb - n_diag.  variant: 0 = as pc_fill would choose,
  * -1 = general fallback kernel, w > 0 = force the systolic kernel with w columns per lane
+ * (every task in its class's own workgroup shape; 1000 + w: that variant with the buckets cut as pc_fill cuts
+ * them -- left-over rows to the remainder chooser's variant, small tasks in one- / two-wave workgroups)
  * (a pair whose COLUMN gene holds a byte outside the 24-letter alphabet runs that variant's
  * residue-compare cell, as in pc_fill: the profile cell keeps one row for all such bytes).
  */
@@ -466,7 +468,9 @@ int pc_round6_probe(pc_ctx* ctx, const double* in, double* out, int64_t n);
  *   tuning / A-B switches (read once per process; every setting gives the same matrix, tests/ hold them to that)
  *     PC_TASK_BUDGET=n          cell slots per row stream of an alignment task (49,152)
  *     PC_REMAINDER=0            no narrower variant for a bucket's left-over rows
- *     PC_INC16=0|1              the 11- / 10-instruction DP cell wherever both are compiled
+ *     PC_INC16=0|1|2            the 11- / 10-instruction DP cell wherever both are compiled (2: the 10-instruction cell also on segments of up to 64 lanes, where a workgroup shape holds its profile)
+ *     PC_RATE_TABLE=0..3        which choosers read the measured rate table (pc_nw_rates.h): bit 0 variant and remainder, bit 1 the cell of a launch class (3)
+ *     PC_CHOOSE_MAX_W=w         no variant wider than w columns per lane for a column gene that a narrower one holds
  *     PC_SMALL_MODES=0          no one- / two-wave workgroups for tasks of few rows;  PC_SMALL_LAUNCH_MIN=n  fewest such tasks that get a launch of their own (192)
  *     PC_FUSE=0                 one launch per launch class instead of one per register tier
  *     PC_STRIP=0                column genes beyond 4,096 residues on the one-lane-per-alignment kernel instead of strip-mined passes

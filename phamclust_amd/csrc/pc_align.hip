@@ -706,6 +706,8 @@ extern "C" int pc_align_pairs(pc_ctx* c, const int32_t* a_gene, const int32_t* b
     const int G = c->dev.G;
     const int nvar = pc_nw_num_variants();
     int forced = -2;                                   // -2: automatic
+    const bool like_fill = variant >= 1000;            // 1000 + w: variant w, its buckets cut as a fill cuts them (tools/class_rates.py)
+    if (like_fill) variant -= 1000;
     if (variant < 0) forced = -1;
     else if (variant > 0) {
         for (int v = 0; v < nvar; ++v) if (pc_nw_variant_w(v) == variant) forced = v;
@@ -736,19 +738,19 @@ extern "C" int pc_align_pairs(pc_ctx* c, const int32_t* a_gene, const int32_t* b
     {
         // Buckets (runs of one column gene) are cut the way the fill's planner cuts them (pc_plan.hip): tasks of the class's row
         // count; with the automatic variant also the left-over rows of a wave round to the remainder chooser's variant, and every
-        // task in the launch mode its row count asks for.  A forced variant keeps its class's own workgroup shape.
+        // task in the launch mode its row count asks for.  A forced variant keeps its class's own workgroup shape (unless asked as 1000 + w).
         for (int64_t i = 0; i < n;) {
             const int64_t k = order[i];
             int64_t j = i;
             while (j < n && cls[order[j]] == cls[k] && b_gene[order[j]] == b_gene[k]) ++j;
             const int lb = c->h_gene_len[b_gene[k]];
             const bool odd = c->h_gene_odd[b_gene[k]] != 0;
-            const PcBucketCut cut = pc_bucket_cut(lb, j - i, cls[k], odd, forced == -2);
+            const PcBucketCut cut = pc_bucket_cut(lb, j - i, cls[k], odd, forced == -2 || like_fill);
             const int per = cut.per, rem_cls = cut.rem_base;
             const int64_t jmain = i + cut.n_main;
             auto put = [&](int64_t r0, int64_t r1, int base) {
                 PcTask t; t.gene = b_gene[k]; t.begin = (int32_t)r0; t.end = (int32_t)r1;
-                t.pad = pc_task_launch_class(lb, (int)(r1 - r0), base, forced == -2);
+                t.pad = pc_task_launch_class(lb, (int)(r1 - r0), base, forced == -2 || like_fill);
                 cls_maxlb[t.pad] = std::max(cls_maxlb[t.pad], lb);
                 tasks.push_back(t);
             };

@@ -21,6 +21,9 @@
 // lexicographic max over them (see "The DP cell as a LEXICOGRAPHIC MAX" below).
 // VALU work: no MFMA (there is no dense contraction in this recurrence).
 #include "pc_nw_systolic.h"     // the systolic kernel (shared with pc_nw_rules.hip), BLOSUM62
+#include "pc_nw_rates.h"        // measured step costs the choosers read
+#include <algorithm>
+#include <vector>
 
 
 // One DP cell in the Ho convention.  In:  Hol/El/SHl/SEl from (i,j-1), Hou/Fu/SHu/SFu from
@@ -128,7 +131,9 @@ int pc_nw_num_variants() { return g_num_variants; }
 int pc_nw_variant_w(int v) { return (v >= 0 && v < g_num_variants) ? g_variant_w[v] : 0; }
 int pc_nw_variant_takes_any_byte(int v) { return v < 0 || v >= g_num_variants || g_variant_w[v] > PC_INC16_MAX_W; }   // 0: some class of this variant may run the profile cell
 
-// Variant for a column gene of lb residues.  Time per row step ~ (W + c0 + c1 nseg) cell-equivalents (x 1.014 at
+// Variant for a column gene of lb residues: the model below, corrected by the measured rate table (pc_nw_rates.h) where the record prices
+// both the model's choice and a cheaper variant -- see choose_variant_uncached.
+// The model.  Time per row step ~ (W + c0 + c1 nseg) cell-equivalents (x 1.014 at
 // W = 22, x 1.022 at W = 24: three waves per SIMD), during which a wave retires nseg rows of lb cells; c1 = 0.535
 // from a least-squares fit to measured kernel-only GCUPS of every variant over L = 60..1200
 // (profiles/r01/experiments/l_variant_gcups.txt), c0 = 0.3 after the step prologue shrank to ~12 instructions (end-to-end
@@ -164,55 +169,156 @@ static int choose_strip_variant(int lb) {
     }
     return best;
 }
-int pc_nw_choose_variant(int lb) {
-    if (lb <= 0) return -1;
-    if (lb > 64 * PC_MAX_W) return choose_strip_variant(lb);
+// ---- the model (r01-r04): what a point the rate table does not cover is priced by, and "today's choice" that a tabulated
+// point has to beat by more than its spread.  Time per row step ~ (W + c0 + c1 nseg) cell-equivalents, x the occupancy penalty of
+// the wide tiers, x 0.94 where the class runs the profile cell.
+static double model_step(int W, int nseg) {
+    const double pen = W >= 64 ? 1.15 : W >= 48 ? 1.08 : W >= 32 ? 1.04 : W >= 24 ? 1.022 : (W >= 22 ? 1.014 : 1.0);
+    return (W + 0.3 + 0.535 * nseg) * pen;
+}
+static int inc16_forced() { static const int force = getenv("PC_INC16") ? atoi(getenv("PC_INC16")) : -1; return force; }   // tuning: 0 = never, 1 = wherever compiled (up to 32 lanes per segment), 2 = wherever a workgroup shape fits (64 lanes included: tools/class_rates.py)
+static bool model_inc16(int W, int Gb) {                                            // the r02 rule (see class_inc16)
+    if (W > PC_INC16_MAX_W || Gb > 32) return false;
+    if (inc16_forced() >= 0) return inc16_forced() != 0;
+    return (Gb <= 16 && W <= 22) || (Gb == 32 && W >= 11 && W <= 19);
+}
+static int nseg_of(int G) { const int n = 64 / G; return n > PC_MAX_SEG ? PC_MAX_SEG : n; }
+static int model_choose_variant(int lb) {
     int best = -1; double best_cost = 0;
     for (int v = 0; v < g_num_variants; ++v) {
         const int W = g_variant_w[v];
         const int G = (lb + W - 1) / W;
         if (G > 64) continue;
-        int nseg = 64 / G; if (nseg > 16) nseg = 16;
-        // W >= 32 exist for very long column genes (up to 4,096 residues).  They run at 2 or 1 waves per SIMD yet
-        // measure 1.9-2.2 TCUPS at full lane use (profiles/r01/experiments/o_wide_variant_gcups.txt): one wave can keep its
-        // SIMD's VALU busy, so the penalty is small
-        const double pen = W >= 64 ? 1.15 : W >= 48 ? 1.08 : W >= 32 ? 1.04 : W >= 24 ? 1.022 : (W >= 22 ? 1.014 : 1.0);
-        // constants of the cost model; their sweeps came out flat (profiles/r02/experiments, profiles/r04/experiments/choose_sweep_after_retag.txt) and the
-        // environment knobs that drove them (PC_CHOOSE_C0 / _C1 / _CELL) are gone (r05)
-        constexpr double c0 = 0.3, c1 = 0.535;
-        constexpr double cell = 0.94;  // relative cost of the 10-instruction cell's classes (sweep 1.0 / 0.96 / 0.93 / 0.90: 239.6 / 237.8 / 238.1 / 237.9 ms at N=3,000)
-        const double cost = (W + c0 + c1 * nseg) * pen * (class_inc16(W, G) ? cell : 1.0) / nseg;
+        const int nseg = nseg_of(G);
+        const bool inc16 = model_inc16(W, pc_nw_g_bucket(G));
+        const double cost = model_step(W, nseg) * (inc16 ? 0.94 : 1.0) / nseg;
         if (best < 0 || cost < best_cost) { best = v; best_cost = cost; }
     }
     return best;
 }
 
+// ---- the rate table (pc_nw_rates.h): step cost of (W, G lanes per segment, cell) where the record holds it.  Between two measured
+// lengths of one lanes-per-segment bucket: linear in G; beyond them only as far as the segments per wave stay those of the
+// nearest point (a wave's step does not depend on how many of a segment's lanes work).
+static bool rate_at(int W, int G, int cell, double& step, double& spread) {
+    const int Gb = pc_nw_g_bucket(G);
+    const PcRatePoint *lo = nullptr, *hi = nullptr;
+    for (int i = 0; i < pc_nw_n_rates; ++i) {
+        const PcRatePoint& p = pc_nw_rates[i];
+        if (p.W != W || p.cell != cell || pc_nw_g_bucket(p.G) != Gb) continue;
+        if (p.G <= G && (!lo || p.G > lo->G)) lo = &p;
+        if (p.G >= G && (!hi || p.G < hi->G)) hi = &p;
+    }
+    if (lo && hi) {
+        const double t = hi->G == lo->G ? 0.0 : (double)(G - lo->G) / (hi->G - lo->G);
+        step = lo->step + t * (hi->step - lo->step);
+        spread = std::max(lo->spread, hi->spread);
+        return true;
+    }
+    const PcRatePoint* p = lo ? lo : hi;
+    if (!p || nseg_of(p->G) != nseg_of(G)) return false;
+    step = p->step; spread = p->spread;
+    return true;
+}
+// PC_RATE_TABLE=0|1|2|3 (A/B): bit 0 the variant and remainder choosers read the table, bit 1 the cell rule does; default both
+static int rate_table_use() { static const int m = getenv("PC_RATE_TABLE") ? atoi(getenv("PC_RATE_TABLE")) : 3; return m; }
+static bool rate_pinned(int lb) {
+    if (!(rate_table_use() & 1)) return true;
+    for (int i = 0; i < pc_nw_n_rate_pins; ++i) if (lb >= pc_nw_rate_pins[i][0] && lb <= pc_nw_rate_pins[i][1]) return true;
+    return false;
+}
+static bool inc16_fits(int W, int Gb);
+// Cost per alignment row of a column gene of lb residues on variant v in the cell its class runs, from the table
+static bool rate_of(int v, int lb, double& cost, double& spread) {
+    const int W = g_variant_w[v], G = (lb + W - 1) / W;
+    if (G > 64) return false;
+    double s, e;
+    if (!rate_at(W, G, class_inc16(W, G) ? 1 : 0, s, e)) return false;
+    cost = s / nseg_of(G); spread = e / nseg_of(G);
+    return true;
+}
+// PC_CHOOSE_MAX_W=w (A/B): no variant wider than w for a column gene that a narrower one holds
+static int choose_max_w() { static const int w = getenv("PC_CHOOSE_MAX_W") ? atoi(getenv("PC_CHOOSE_MAX_W")) : 0; return w; }
+static int choose_variant_uncached(int lb) {
+    int best = model_choose_variant(lb);
+    const int cap = choose_max_w();
+    if (cap > 0 && best >= 0 && g_variant_w[best] > cap && lb <= 64 * cap) {
+        best = -1; double best_cost = 0;
+        for (int v = 0; v < g_num_variants; ++v) {
+            const int W = g_variant_w[v], G = (lb + W - 1) / W;
+            if (G > 64 || W > cap) continue;
+            const double cost = model_step(W, nseg_of(G)) / nseg_of(G);
+            if (best < 0 || cost < best_cost) { best = v; best_cost = cost; }
+        }
+        return best;
+    }
+    // the table's say: a variant takes the place of the model's choice only if the record prices both and it is cheaper by more
+    // than the two points' spread (noise stays out of the policy); the cheapest of those that are
+    double c0, e0;
+    if (best < 0 || rate_pinned(lb) || !rate_of(best, lb, c0, e0)) return best;
+    double best_cost = c0;
+    for (int v = 0; v < g_num_variants; ++v) {
+        double c, e;
+        if (!rate_of(v, lb, c, e)) continue;
+        if (c + e + e0 < c0 && c < best_cost) { best = v; best_cost = c; }
+    }
+    return best;
+}
+int pc_nw_choose_variant(int lb) {
+    if (lb <= 0) return -1;
+    if (lb > 64 * PC_MAX_W) return choose_strip_variant(lb);
+    static const std::vector<int8_t> memo = [] {                         // (a fill asks once per distinct length, pc_align_pairs once per pair)
+        std::vector<int8_t> m(64 * PC_MAX_W + 1, -1);
+        for (int l = 1; l <= 64 * PC_MAX_W; ++l) m[l] = (int8_t)choose_variant_uncached(l);
+        return m;
+    }();
+    return memo[lb];
+}
+
 // A bucket whose row count is not a multiple of its variant's nseg leaves r = n mod nseg rows for a last wave round in
 // which only r of the nseg segments work.  Those r rows can go to a variant with fewer, longer segments instead:
 // returns that variant, or -1 when staying is as cheap (the cost of a wave round is the step cost of the variant;
-// 30 % margin for the extra workgroup).
+// 30 % margin for the extra workgroup).  Step costs: the model's; the table's (compare cell: such a task runs in a one-wave
+// workgroup) where it prices the staying round and the candidate both, under the same rule as the variant chooser -- the
+// model's answer stands unless the record contradicts it by more than the spread.
 int pc_nw_choose_remainder(int lb, int r, int main_variant) {
     static const bool off = getenv("PC_REMAINDER") && !strcmp(getenv("PC_REMAINDER"), "0");
     if (off || lb <= 0 || r <= 0 || main_variant < 0 || main_variant >= g_num_variants) return -1;
-    constexpr double c0 = 0.3, c1 = 0.535;
-    auto step_cost = [&](int v, int& nseg) {
-        const int W = g_variant_w[v], G = (lb + W - 1) / W;
-        if (G > 64) { nseg = 0; return 0.0; }
-        nseg = 64 / G; if (nseg > PC_MAX_SEG) nseg = PC_MAX_SEG;
-        const double pen = W >= 64 ? 1.15 : W >= 48 ? 1.08 : W >= 32 ? 1.04 : W >= 24 ? 1.022 : (W >= 22 ? 1.014 : 1.0);
-        return (W + c0 + c1 * nseg) * pen;
-    };
-    int nseg0; const double stay = step_cost(main_variant, nseg0);
+    const int W0 = g_variant_w[main_variant], G0 = (lb + W0 - 1) / W0;
+    if (G0 > 64) return -1;
+    const int nseg0 = nseg_of(G0);
     if (nseg0 <= 1 || r >= nseg0) return -1;
     constexpr double margin = 0.7;
-    int best = -1; double best_cost = margin * stay;
+    int best = -1; double best_cost = margin * model_step(W0, nseg0);
     for (int v = 0; v < g_num_variants; ++v) {
-        int nseg; const double sc = step_cost(v, nseg);
-        if (!nseg) continue;
-        const double cost = sc * ((r + nseg - 1) / nseg);
+        const int W = g_variant_w[v], G = (lb + W - 1) / W;
+        if (G > 64) continue;
+        const int nseg = nseg_of(G);
+        const double cost = model_step(W, nseg) * ((r + nseg - 1) / nseg);
         if (cost < best_cost) { best = v; best_cost = cost; }
     }
-    return best;
+    double s0, e0;
+    if (rate_pinned(lb) || !rate_at(W0, G0, 0, s0, e0)) return best;
+    auto tab = [&](int v, double& c, double& e) {
+        const int W = g_variant_w[v], G = (lb + W - 1) / W;
+        if (G > 64 || !rate_at(W, G, 0, c, e)) return false;
+        const int rounds = (r + nseg_of(G) - 1) / nseg_of(G);
+        c *= rounds; e *= rounds;
+        return true;
+    };
+    double cur = margin * s0, cur_e = margin * e0;                        // today's choice in the table's units: stay ...
+    if (best >= 0) {                                                      // ... or the model's move, unless the record says it loses
+        double c, e;
+        if (!tab(best, c, e)) return best;
+        if (c - e > cur + cur_e) best = -1; else { cur = c; cur_e = e; }
+    }
+    int pick = best; double pick_cost = cur;
+    for (int v = 0; v < g_num_variants; ++v) {
+        double c, e;
+        if (v == main_variant || !tab(v, c, e)) continue;
+        if (c + e + cur_e < cur && c < pick_cost) { pick = v; pick_cost = c; }
+    }
+    return pick;
 }
 
 // LDS of one workgroup: score table, the waves' private regions, the profile of a column gene spread over G lanes
@@ -226,19 +332,45 @@ static size_t systolic_lds_bytes(int W, int G, int nw, bool inc16, bool any_buck
 // Lanes-per-segment bucket of a launch class (pc_host.h's classes use the same bounds): every column gene of a launch
 // lies in one bucket, so launch, task sizes and LDS agree on the waves per workgroup without passing it around
 int pc_nw_g_bucket(int G) { return G <= 8 ? 8 : (G <= 16 ? 16 : (G <= 32 ? 32 : 64)); }
-// Which cell a launch class runs (measured per class with the launches serialised, profiles/r02/experiments/l_class_times.txt):
+// Which cell a launch class runs: the cheaper one of the rate table (pc_nw_rates.h) where it holds both, else the r02 rule
+// (measured per class with the launches serialised, profiles/r02/experiments/l_class_times.txt):
 // the 16-bit increment profile wins 5-7 % where four workgroups still fit a CU beside it (segments of up to 16 lanes)
 // and 3-5 % with 8-wave workgroups on segments of up to 32 lanes for W = 11..19 (W <= 9: -15..-40 %, short strips; W = 20: nothing; W = 24: -6 % in
 // either bucket, its profile needs 8-wave groups even at 16 lanes); with
 // one segment per wave (up to 64 lanes) the profile of a long gene leaves room for a single 16-wave workgroup per CU
 // and loses 5-10 %.  Elsewhere the residue compare.
 static bool class_inc16(int W, int G) {
-    static const int force = getenv("PC_INC16") ? atoi(getenv("PC_INC16")) : -1;      // tuning: 0 = never, 1 = wherever compiled
+    const int force = inc16_forced();
     if (W > PC_INC16_MAX_W) return false;
     const int Gb = pc_nw_g_bucket(G);
+    if (force == 2) return inc16_fits(W, Gb);
     if (Gb > 32) return false;                                                        // (measured: no room for enough waves; only percent-positives launches run the profile cell there)
     if (force >= 0) return force != 0;
-    return (Gb <= 16 && W <= 22) || (Gb == 32 && W >= 11 && W <= 19);
+    // The cheaper cell of the rate table for this launch class (W, lanes-per-segment bucket), summed over the lengths at which the
+    // record holds both -- where the profile cell is compiled and a workgroup shape holds its profile (inc16_fits); the r02 rule
+    // stands where the record is silent or the two differ by less than their spread
+    static const std::vector<int8_t> by_table = [] {
+        std::vector<int8_t> t((PC_INC16_MAX_W + 1) * 4, -1);
+        for (int w = 1; w <= PC_INC16_MAX_W; ++w)
+            for (int b = 0; b < 3; ++b) {
+                const int gb = 8 << b;
+                if (!inc16_fits(w, gb) || !(rate_table_use() & 2)) continue;
+                double prof = 0, comp = 0, err = 0; int n = 0;
+                for (int i = 0; i < pc_nw_n_rates; ++i) {
+                    const PcRatePoint& p = pc_nw_rates[i];
+                    if (p.W != w || p.cell != 1 || pc_nw_g_bucket(p.G) != gb) continue;
+                    for (int k = 0; k < pc_nw_n_rates; ++k) {
+                        const PcRatePoint& q = pc_nw_rates[k];
+                        if (q.W == w && q.cell == 0 && q.G == p.G) { prof += p.step; comp += q.step; err += p.spread + q.spread; ++n; }
+                    }
+                }
+                if (n && prof + err < comp) t[w * 4 + b] = 1;
+                if (n && comp + err < prof) t[w * 4 + b] = 0;
+            }
+        return t;
+    }();
+    const int said = by_table[W * 4 + (Gb == 8 ? 0 : Gb == 16 ? 1 : 2)];
+    return said >= 0 ? said != 0 : model_inc16(W, Gb);
 }
 // Waves per workgroup: the fewest (4, 8; at most what the variant's registers allow) that put 16 waves on a CU
 // given the LDS the class's largest profile takes; the most allowed if none does
@@ -254,6 +386,13 @@ static int waves_for(int W, int G, int cell_mode) {
     for (int nw = PC_MIN_WAVES; nw <= top; nw *= 2)
         if ((int)((size_t)160 * 1024 / systolic_lds_bytes(W, Gb, nw, inc16)) * nw >= 16) return nw;
     return top;
+}
+// Does a workgroup shape hold the profile cell's profile of this launch class with 16 waves on a CU (the loop above succeeds)?
+static bool inc16_fits(int W, int Gb) {
+    if (W > PC_INC16_MAX_W) return false;
+    for (int nw = PC_MIN_WAVES; nw <= pc_max_waves(W); nw *= 2)
+        if ((int)((size_t)160 * 1024 / systolic_lds_bytes(W, Gb, nw, true)) * nw >= 16) return true;
+    return false;
 }
 int pc_nw_class_waves(int variant, int lb, int compare_only) {
     if (variant < 0 || variant >= g_num_variants || lb <= 0) return PC_MIN_WAVES;

@@ -588,7 +588,11 @@ class Context:
                                             ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0)))
 
     # -- test hooks --------------------------------------------------------------
-    def align_pairs(self, a_gene, b_gene, variant=0):
+    def align_pairs(self, a_gene, b_gene, variant=0, like_fill=False):
+        """``variant``: 0 the chooser's, -1 the general kernel, w > 0 the systolic variant of w columns per lane -- with
+        ``like_fill`` its buckets cut as a fill cuts them (remainder chooser, small-task modes)."""
+        if like_fill and variant > 0:
+            variant += 1000
         self.ensure_residues()
         a = np.ascontiguousarray(a_gene, dtype=np.int32)
         b = np.ascontiguousarray(b_gene, dtype=np.int32)
