@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 158   /* 0.5.7: pc_fill_groups */
+#define PC_VERSION 159   /* 0.5.8: pc_fill_nearest */
 
 typedef enum {
     PC_OK = 0,
@@ -278,6 +278,37 @@ int pc_fill_components(pc_ctx* ctx, int metric, int as_distance, double threshol
 /* Test / tuning hook: HIP-event milliseconds of the last pc_fill_components call that was given stats: *ms_union the union passes
  * summed over its slabs, *ms_labels the labelling pass; either pointer may be NULL. */
 int pc_last_component_times(const pc_ctx* ctx, float* ms_union, float* ms_labels);
+
+/*
+ * Nearest-neighbours fill: each genome's k closest, without the dense matrix and without a threshold.  The reference answers this per
+ * node from its dense matrix -- SymMatrix.nearest_neighbors(source, threshold), matrix.py:265-296: the neighbours closest first,
+ * equally close ones in node order.  Let kk = min(k, N - 1).  Row g of nbr[N][kk] and val[N][kk] (row-major) lists the kk genomes
+ * h != g that come first in ONE total order: the better value first -- the smaller on a distance fill (as_distance != 0), the larger
+ * on a similarity fill; a plain f64 compare on the delivered, already round(x, 6) value of the pair {g, h} -- and among equal values
+ * the smaller genome index.  That is nearest_neighbors(g, threshold) with the threshold wide open, cut after kk.  One total order:
+ * the result is canonical, it depends neither on the slab cut nor on how any race resolved.  Values are the whole fill's, bit for
+ * bit, each pair in the whole fill's orientation.  The six metrics and PC_AAI_PPOS.
+ * *nbr and *val point into page-locked memory the context owns (pc_fill_borrow's loan rule: valid until the next fill or upload on
+ * this context or its destruction); *k_out = kk; *n_slabs and stats as pc_fill_edges gives them -- the fills' stats summed; the
+ * selection passes are not in them: pc_last_nearest_times.
+ * Same walk as pc_fill_edges: the same slab cut (pc_chunk_plan over count[t] = t, slab_bytes / 8 pairs, <= 2^31-1; 0 = automatic),
+ * each slab filled as a shard into the resident slab buffer, then TWO passes over it -- a slab holds the pairs (s, t), s < t, of its
+ * targets, so a genome receives candidates as a target (the row pass) and as a source (the column pass) -- that merge into k slots per
+ * genome which live on the device across the slabs; after the last slab one finishing pass and one copy of the N * kk entries.
+ * Nothing is read back per slab.  Consequences as for pc_fill_edges: aai / peq merge duplicate sequence pairs per slab only;
+ * pc_last_set_kernel, pc_last_set_launch and pc_last_plan_tasks describe the LAST slab's fill.  The caller's unsharded state is back
+ * in force when the call returns, whatever it returns.
+ * PC_OK also for N <= 1, with *k_out = 0 and nothing written.  PC_ERR_ARG: bad metric, k < 1, negative slab_bytes, a NULL out pointer.
+ * PC_ERR_LIMIT: k > PC_NEAREST_MAX_K (a genome's list lives one entry per lane of a wave).  PC_ERR_STATE: before upload, on a sharded
+ * context (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill.  On a refusal *nbr and *val are NULL
+ * and *k_out is 0.  Runs on the context's own stream and returns with everything finished.
+ */
+#define PC_NEAREST_MAX_K 64
+int pc_fill_nearest(pc_ctx* ctx, int metric, int as_distance, int k, int64_t slab_bytes,
+                    const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook: HIP-event milliseconds of the last pc_fill_nearest call that was given stats: *ms_select the row and column
+ * passes summed over its slabs, *ms_finish the finishing pass; either pointer may be NULL. */
+int pc_last_nearest_times(const pc_ctx* ctx, float* ms_select, float* ms_finish);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -19,6 +19,7 @@ METRIC, K_MIN = "peq", 6
 NR_THRESH, NR_LINKAGE = 0.75, "complete"     # 1st pass: glue near-identical genomes together
 CLU_THRESH, CLU_LINKAGE = 0.25, "average"    # 2nd pass: clusters
 SUB_THRESH, SUB_LINKAGE = 0.6, "single"      # 3rd pass: sub-clusters
+NEAREST_MAX_K = 64                           # --nearest: the k a nearest-neighbours fill takes at most (PC_NEAREST_MAX_K)
 
 _PAPERS = (("gcs", "gene content similarity", "10.1038/nmicrobiol.2017.112"),
            ("jc", "jaccard coefficient", "10.1111/j.1469-8137.1912.tb05611.x"),
@@ -57,6 +58,9 @@ _OPTIONS = (
                                                                "their sub-matrices (sum of n_c^2 cells, not N^2); same cluster_* / singletons "
                                                                "output; the adjacency file comes from an edge-list fill; no "
                                                                "pairwise_<metric>_similarities.tsv, no dataset heatmap, no matrix cache; one GPU")),
+    (None, "-K", "--nearest", dict(type=int, default=None, help="stop after the matrix stage and write only nearest_<metric>.tsv, from a nearest-neighbours "
+                                                               "fill: each genome's K most similar genomes (1..64), most similar first; no matrix, "
+                                                               "no threshold, no clustering")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -99,6 +103,13 @@ def parse_args(argv=None):
         parser.error("--components-only and --adjacency-only each stop after a fill of their own; give one of them")
     if args.components_only and args.extend is not None:
         parser.error("--components-only fills from scratch; it cannot be combined with --extend")
+    if args.nearest is not None:
+        if not 1 <= args.nearest <= NEAREST_MAX_K:
+            parser.error(f"--nearest takes a number of neighbours in 1..{NEAREST_MAX_K}")
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--no-matrix", args.no_matrix),
+                            ("--extend", args.extend is not None)):
+            if given:
+                parser.error(f"--nearest stops after a nearest-neighbours fill of its own; it cannot be combined with {flag}")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

@@ -153,6 +153,7 @@ extern "C" void pc_ctx_destroy(pc_ctx* c) {
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
     for (int i = 0; i < 5; ++i) if (c->ev_edge[i]) (void)hipEventDestroy(c->ev_edge[i]);
     for (int i = 0; i < 4; ++i) if (c->ev_cc[i]) (void)hipEventDestroy(c->ev_cc[i]);
+    for (int i = 0; i < 4; ++i) if (c->ev_nn[i]) (void)hipEventDestroy(c->ev_nn[i]);
     for (int i = 0; i < pc_ctx::kAux; ++i) if (c->aux[i]) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); }
     for (int i = 0; i <= pc_ctx::kAux; ++i) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
     for (int i = 0; i < pc_ctx::kLong; ++i) {

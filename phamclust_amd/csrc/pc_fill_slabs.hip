@@ -1,6 +1,7 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
-// pc_last_component_times.  Host only.
+// pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
+// pc_last_nearest_times.  Host only.
 //
 // The walk they share goes over successive contiguous ranges of target genomes ("slabs": pc_chunk_plan over count[t] = t under
 // slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is installed as a PcShard (owned = t0 .. t1-1,
@@ -23,7 +24,7 @@ struct SlabShardScope {
 
 static int64_t pairs_below(int64_t t) { return t * (t - 1) / 2; }           // pairs (s, t'), s < t' < t
 
-// The checks both calls make, after fill_check's; outputs: every output pointer is there
+// The checks the calls make, after fill_check's (pc_fill_nearest has no threshold and passes 0); outputs: every output pointer is there
 static int slab_check(const pc_ctx* c, const char* who, bool outputs, int metric, double threshold, int64_t slab_bytes) {
     if (!outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
     if (threshold != threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
@@ -251,5 +252,84 @@ extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* 
     if (!c) { pc_set_error("pc_last_component_times: NULL context"); return PC_ERR_ARG; }
     if (ms_union) *ms_union = c->last_cc_ms[0];
     if (ms_labels) *ms_labels = c->last_cc_ms[1];
+    return PC_OK;
+}
+
+// ---- nearest-neighbours fill: each genome's k best neighbours in the total order (value, better first; then index) -- what
+// SymMatrix.nearest_neighbors answers per node from the dense matrix (matrix.py:265-296), cut after k -- as nbr[N][kk], val[N][kk].
+// Each filled slab goes through two passes (pc_nearest.hip: k_nn_rows, k_nn_cols) over key[N][kk] / nbr[N][kk], which stay on the
+// device from the first slab to the last; nothing is read back per slab.  After the last slab: k_nn_finish, then one D2H of
+// val[N][kk] with nbr[N][kk] behind it.
+extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, int64_t slab_bytes,
+                               const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats) {
+    if (nbr) *nbr = nullptr;
+    if (val) *val = nullptr;
+    if (k_out) *k_out = 0;
+    if (n_slabs) *n_slabs = 0;
+    int rc = PC_OK;
+    if ((rc = fill_check(c, "pc_fill_nearest", "a nearest-neighbours fill", &metric, nullptr))) return rc;
+    if (k < 1) { pc_set_error("pc_fill_nearest: k %d", k); return PC_ERR_ARG; }
+    if (k > PC_NEAREST_MAX_K) { pc_set_error("pc_fill_nearest: k %d is above PC_NEAREST_MAX_K = %d", k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
+    if ((rc = slab_check(c, "pc_fill_nearest", nbr && val && k_out && n_slabs, metric, 0.0, slab_bytes))) return rc;
+    PC_ON_DEVICE(c);
+    PcRange range("pc:fill_nearest");
+    hipStream_t st = c->stream;
+    const int N = c->dev.N;
+    const int kk = std::max(std::min(k, N - 1), 0);
+    const size_t n_ent = (size_t)std::max(N, 0) * kk, val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4;
+    pc_stats sum; memset(&sum, 0, sizeof(sum));
+    c->last_nn_ms[0] = c->last_nn_ms[1] = 0.f;
+    as_distance = as_distance ? 1 : 0;
+    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffer is rewritten)
+    if ((rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
+    const double* const h_val = c->h_nn.as<double>();
+    const int32_t* const h_nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes);
+    if (N <= 1) {
+        *nbr = h_nbr; *val = h_val;
+        if (stats) *stats = sum;
+        return PC_OK;
+    }
+    std::vector<int32_t> cut;
+    if ((rc = slab_cut(c, slab_bytes, cut))) return rc;
+    if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes))) return abi_rc(rc);
+    if (stats) for (hipEvent_t& e : c->ev_nn) if (!e) PC_HIP(hipEventCreate(&e));
+    unsigned long long* const d_key = c->b_nn_key.as<unsigned long long>();
+    double* const d_val = c->b_nn_out.as<double>();
+    int32_t* const d_nbr = (int32_t*)((char*)c->b_nn_out.p + val_bytes);
+    if ((rc = pc_launch_nn_init(d_key, d_nbr, (int64_t)n_ent, st))) return rc;
+    bool pending = false;                                                   // a slab's passes were launched and, with stats, their time not yet added
+    auto add_select_time = [&]() -> int { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_nn[0], c->ev_nn[1])); c->last_nn_ms[0] += x; return PC_OK; };
+    // ---- a slab's hook: the row pass, then the column pass, left running (the walk has waited for the passes before them: their two
+    // events can be read).  The slab's targets are the consecutive range that starts at its first owned one.
+    rc = slab_walk(c, cut, metric, as_distance, stats ? &sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
+        int rc = PC_OK;
+        const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
+        if (stats && pending && (rc = add_select_time())) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_nn[0], st));
+        if ((rc = pc_launch_nn_select(slab, Lp, t0, t1, as_distance, kk, d_key, d_nbr, st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_nn[1], st));
+        pending = true;
+        return mark_work(c, st);
+    });
+    if (rc != PC_OK) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_nn[2], st));
+    if ((rc = pc_launch_nn_finish(d_key, d_val, (int64_t)n_ent, as_distance, st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_nn[3], st));
+    PC_HIP(hipMemcpyAsync(c->h_nn.p, c->b_nn_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if (stats) {
+        if (pending && (rc = add_select_time())) return rc;                 // (the last slab's passes)
+        PC_HIP(hipEventElapsedTime(&c->last_nn_ms[1], c->ev_nn[2], c->ev_nn[3]));
+    }
+    *nbr = h_nbr; *val = h_val; *k_out = kk; *n_slabs = (int32_t)cut.size() - 1;
+    if (stats) *stats = sum;
+    return PC_OK;
+}
+
+extern "C" int pc_last_nearest_times(const pc_ctx* c, float* ms_select, float* ms_finish) {
+    if (!c) { pc_set_error("pc_last_nearest_times: NULL context"); return PC_ERR_ARG; }
+    if (ms_select) *ms_select = c->last_nn_ms[0];
+    if (ms_finish) *ms_finish = c->last_nn_ms[1];
     return PC_OK;
 }

@@ -124,6 +124,11 @@ struct pc_ctx {
     PinnedBuf h_cc_labels;                  // the labels lent out by pc_fill_components
     hipEvent_t ev_cc[4] = {nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_components that is asked for stats
     float last_cc_ms[2] = {0.f, 0.f};       // union passes, labels pass of the last pc_fill_components with stats (pc_last_component_times)
+    // pc_fill_nearest: key[N][K] (order-preserving u64 of the value), then val[N][K] | nbr[N][K] (one D2H), and their pinned host image
+    DevBuf b_nn_key, b_nn_out;
+    PinnedBuf h_nn;                         // the neighbours and values lent out by pc_fill_nearest
+    hipEvent_t ev_nn[4] = {nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_nearest that is asked for stats
+    float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest with stats (pc_last_nearest_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {

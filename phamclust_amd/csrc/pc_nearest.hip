@@ -1,0 +1,188 @@
+// pc_nearest.hip -- the kernels of pc_fill_nearest: every genome's K best neighbours (K <= 64), merged slab by slab into K slots per
+// genome that stay on the device for the length of the call, as parent[N] does for the components fill.
+//   state   key[N][K] u64, nbr[N][K] i32, each row sorted best first.  The key is an order-preserving transform of the value's f64
+//           bits (sign bit flipped for values >= 0, every bit for values < 0: unsigned order = f64 order), complemented on a
+//           similarity fill, so that BETTER IS THE SMALLER KEY in both directions and the kernels have one code path; behind it the
+//           genome index is compared, smaller first.  (key, index) is the total order of the header: the K smallest of it are the
+//           result, whatever order the candidates arrive in.  Empty slots hold the worst sentinel (key ~0, index INT32_MAX); every
+//           genome meets N - 1 >= K candidates in the course of a call, so none is left at the end.
+//   k_nn_init    the sentinel
+//   k_nn_rows    a slab of targets [t0, t1) holds for target t the values of (s, t), s < t, contiguously at lbase(t) + s with
+//                lbase(t) = t(t-1)/2 - t0(t0-1)/2 (the slab's shard layout in closed form: its targets are consecutive).  One wave per
+//                target: 64 lanes read 64 consecutive sources, 512 contiguous bytes.
+//   k_nn_cols    source s takes the candidates (t, v), t in [max(s + 1, t0), t1).  For one t the values of 64 consecutive sources are
+//                512 contiguous bytes: a workgroup owns a block of 64 sources and walks the targets in tiles of 64, each tile read
+//                row by row (lanes across sources, one 512-byte run per target) into LDS as keys; then each of its four waves takes 16
+//                of the sources, whose lists it keeps in registers across all the tiles, and reads a source's column of the tile
+//                lanes across targets (row stride 65: no bank conflict).
+//   k_nn_finish  val = the value behind each key
+// A genome's list lives one entry per lane of a wave (why K <= 64).  The K-th entry is "the bar": a ballot of `candidate beats the
+// bar` finds the few candidates that matter (after the warm-up about K ln(n / K) per genome); each of them is inserted at the
+// position popcount(ballot(entry comes before the candidate)), the lanes behind it taking their lower neighbour's entry.
+// Who writes what: the list of genome g is written by exactly one wave per launch -- in k_nn_rows the wave of target g, in k_nn_cols
+// the wave that owns source g -- and the launches are ordered on the stream.  No atomics, no flags, nothing one workgroup waits for
+// from another.  Nothing is read beyond Lp: an element lbase(t) + s is read only for s < t < t1; loads are 8 bytes wide.
+#include "pc_pairs.h"
+
+#define NN_THREADS 256
+#define NN_WAVES (NN_THREADS / 64)
+#define NN_TILE 64                                     // targets and sources of a column-pass tile
+#define NN_LD (NN_TILE + 1)                            // row stride of the tile in LDS (u64 elements)
+#define NN_SRC_PER_WAVE (NN_TILE / NN_WAVES)           // 16 lists in a wave's registers
+#define NN_WORST_KEY (~0ull)
+#define NN_WORST_IDX 0x7fffffff
+
+typedef unsigned long long nn_key;
+
+// flip: 0 on a distance fill, ~0 on a similarity fill
+__device__ __forceinline__ nn_key nn_key_of(double v, nn_key flip) {
+    const nn_key u = (nn_key)__double_as_longlong(v);
+    return (u ^ ((u >> 63) ? ~0ull : (1ull << 63))) ^ flip;
+}
+__device__ __forceinline__ double nn_value_of(nn_key k, nn_key flip) {
+    const nn_key u = k ^ flip;
+    return __longlong_as_double((long long)(u ^ ((u >> 63) ? (1ull << 63) : ~0ull)));
+}
+__device__ __forceinline__ bool nn_before(nn_key ka, int ia, nn_key kb, int ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// lane `src` of x for the whole wave; src is wave-uniform (K - 1, or a bit position of a ballot): v_readlane, no trip through the LDS crossbar
+__device__ __forceinline__ int nn_lane(int x, int src) { return __builtin_amdgcn_readlane(x, src); }
+__device__ __forceinline__ nn_key nn_lane(nn_key x, int src) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, src), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), src);
+    return ((nn_key)hi << 32) | lo;
+}
+__device__ __forceinline__ nn_key nn_shfl_up1(nn_key x) {
+    const unsigned lo = (unsigned)__shfl_up((int)(unsigned)x, 1), hi = (unsigned)__shfl_up((int)(unsigned)(x >> 32), 1);
+    return ((nn_key)hi << 32) | lo;
+}
+
+// One wave's step over up to 64 candidates, one per lane ((ck, ci), have): those that beat the bar go into the list (ek, ei) that the
+// wave holds one entry per lane (lanes >= K carry nothing that is ever read).  Wave-uniform control flow throughout.
+__device__ __forceinline__ void nn_take(nn_key& ek, int& ei, nn_key ck, int ci, bool have, int K, int lane) {
+    nn_key bk = nn_lane(ek, K - 1);
+    int bi = nn_lane(ei, K - 1);
+    unsigned long long m = __ballot(have && nn_before(ck, ci, bk, bi));
+    while (m) {
+        const int j = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const nn_key k = nn_lane(ck, j);
+        const int i = nn_lane(ci, j);
+        if (!nn_before(k, i, bk, bi)) continue;        // (an earlier candidate of this step raised the bar)
+        // entries that come before the candidate are a prefix of the sorted list, and lane K - 1 (the bar) is not among them: pos < K
+        const int pos = __popcll(__ballot(lane < K && nn_before(ek, ei, k, i)));
+        const nn_key uk = nn_shfl_up1(ek);
+        const int ui = __shfl_up(ei, 1);
+        if (lane > pos) { ek = uk; ei = ui; }
+        else if (lane == pos) { ek = k; ei = i; }
+        bk = nn_lane(ek, K - 1);
+        bi = nn_lane(ei, K - 1);
+    }
+}
+
+__device__ __forceinline__ int64_t nn_pairs_below(int t) { return (int64_t)t * (t - 1) / 2; }
+
+__global__ __launch_bounds__(256) void k_nn_init(nn_key* __restrict__ key, int32_t* __restrict__ nbr, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { key[i] = NN_WORST_KEY; nbr[i] = NN_WORST_IDX; }
+}
+
+// row pass: wave w of workgroup b takes target t0 + b * NN_WAVES + w
+__global__ __launch_bounds__(NN_THREADS) void k_nn_rows(const double* __restrict__ vals, int t0, int t1, nn_key flip, int K,
+                                                        nn_key* __restrict__ key, int32_t* __restrict__ nbr) {
+    const int lane = threadIdx.x & 63;
+    const int t = t0 + (int)blockIdx.x * NN_WAVES + (int)(threadIdx.x >> 6);
+    if (t >= t1 || t == 0) return;                     // (the whole wave; genome 0 has no row part)
+    const double* __restrict__ row = vals + (nn_pairs_below(t) - nn_pairs_below(t0));
+    const size_t at = (size_t)t * K + lane;
+    nn_key ek = NN_WORST_KEY; int ei = NN_WORST_IDX;
+    if (lane < K) { ek = key[at]; ei = nbr[at]; }      // the list as the slabs before left it: the bar is tight from the second slab on
+    for (int base = 0; base < t; base += 128) {        // two independent 512-byte loads in flight
+        const int s0 = base + lane, s1 = base + 64 + lane;
+        const bool h0 = s0 < t, h1 = s1 < t;
+        const double v0 = h0 ? row[s0] : 0.0, v1 = h1 ? row[s1] : 0.0;
+        nn_take(ek, ei, nn_key_of(v0, flip), s0, h0, K, lane);
+        if (base + 64 < t) nn_take(ek, ei, nn_key_of(v1, flip), s1, h1, K, lane);
+    }
+    if (lane < K) { key[at] = ek; nbr[at] = ei; }
+}
+
+// column pass: workgroup b takes the sources [64 b, 64 b + 64) below t1 - 1 (genome t1 - 1 has no column part in this slab, genome
+// N - 1 in none)
+__global__ __launch_bounds__(NN_THREADS) void k_nn_cols(const double* __restrict__ vals, int t0, int t1, nn_key flip, int K,
+                                                        nn_key* __restrict__ key, int32_t* __restrict__ nbr) {
+    __shared__ nn_key tile[NN_TILE * NN_LD];           // [target of the tile][source of the block], 33,280 bytes
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int sb = (int)blockIdx.x * NN_TILE;          // first source of the block
+    const int s_end = t1 - 1;                          // sources of the slab: s < t1 - 1
+    const int64_t below0 = nn_pairs_below(t0);
+    nn_key lk[NN_SRC_PER_WAVE]; int li[NN_SRC_PER_WAVE];
+#pragma unroll
+    for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+        const int s = sb + wv * NN_SRC_PER_WAVE + q;
+        lk[q] = NN_WORST_KEY; li[q] = NN_WORST_IDX;
+        if (s < s_end && lane < K) { lk[q] = key[(size_t)s * K + lane]; li[q] = nbr[(size_t)s * K + lane]; }
+    }
+    // the block's first target: above its first source, inside the slab (sb < t1 - 1: the range is not empty)
+    for (int tb = max(sb + 1, t0); tb < t1; tb += NN_TILE) {
+        // stage: row r of the tile = target tb + r, lanes across the block's sources; only elements with s < t < t1 exist
+#pragma unroll
+        for (int i = 0; i < NN_TILE / NN_WAVES; ++i) {  // (sixteen independent 512-byte loads in flight per wave)
+            const int r = wv + i * NN_WAVES, t = tb + r, s = sb + lane;
+            nn_key k = NN_WORST_KEY;
+            if (t < t1 && s < t) k = nn_key_of(vals[nn_pairs_below(t) - below0 + s], flip);
+            tile[r * NN_LD + lane] = k;
+        }
+        __syncthreads();
+        const int t = tb + lane;                       // this lane's candidate of every source of the wave
+#pragma unroll
+        for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+            const int c = wv * NN_SRC_PER_WAVE + q, s = sb + c;
+            if (s >= s_end) break;                     // (wave-uniform; the ragged last block)
+            nn_take(lk[q], li[q], tile[lane * NN_LD + c], t, t < t1 && t > s, K, lane);
+        }
+        __syncthreads();                               // the tile is rewritten by the next round
+    }
+#pragma unroll
+    for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+        const int s = sb + wv * NN_SRC_PER_WAVE + q;
+        if (s < s_end && lane < K) { key[(size_t)s * K + lane] = lk[q]; nbr[(size_t)s * K + lane] = li[q]; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_nn_finish(const nn_key* __restrict__ key, double* __restrict__ val, int64_t n, nn_key flip) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) val[i] = nn_value_of(key[i], flip);
+}
+
+static int nn_check(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+int pc_launch_nn_init(unsigned long long* key, int32_t* nbr, int64_t n, hipStream_t st) {
+    if (n <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_nn_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key, nbr, n);
+    return nn_check("k_nn_init");
+}
+
+// vals: the filled slab of the targets [t0, t1), f64[Lp] with Lp = t1(t1-1)/2 - t0(t0-1)/2; key / nbr: [N][K], N >= t1, 1 <= K <= 64
+int pc_launch_nn_select(const double* vals, int64_t Lp, int t0, int t1, int as_distance, int K, unsigned long long* key, int32_t* nbr, hipStream_t st) {
+    if (K < 1 || K > 64 || t0 < 0 || t1 <= t0 || Lp != (int64_t)t1 * (t1 - 1) / 2 - (int64_t)t0 * (t0 - 1) / 2) {
+        pc_set_error("pc_launch_nn_select: targets [%d, %d) with %lld pairs, K = %d", t0, t1, (long long)Lp, K);
+        return PC_ERR_ARG;
+    }
+    if (Lp == 0) return PC_OK;
+    const nn_key flip = as_distance ? 0ull : ~0ull;
+    hipLaunchKernelGGL(k_nn_rows, dim3((unsigned)((t1 - t0 + NN_WAVES - 1) / NN_WAVES)), dim3(NN_THREADS), 0, st, vals, t0, t1, flip, K, key, nbr);
+    int rc = nn_check("k_nn_rows");
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(k_nn_cols, dim3((unsigned)((t1 - 1 + NN_TILE - 1) / NN_TILE)), dim3(NN_THREADS), 0, st, vals, t0, t1, flip, K, key, nbr);   // (Lp > 0: t1 >= 2)
+    return nn_check("k_nn_cols");
+}
+
+int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st) {
+    if (n <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key, val, n, as_distance ? 0ull : ~0ull);
+    return nn_check("k_nn_finish");
+}

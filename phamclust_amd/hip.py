@@ -73,7 +73,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_variant_width", "pc_task_shape", "pc_ppos_width", "pc_bucket_launch_classes", "pc_last_plan_tasks", "pc_last_set_kernel",
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times",
-           "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles"]
+           "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles",
+           "pc_fill_nearest", "pc_last_nearest_times"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -144,6 +145,9 @@ def load():
     L.pc_fill_components.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p),
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_component_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_fill_nearest.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_f64p),
+                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_nearest_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -537,6 +541,35 @@ class Context:
         self._check(self._lib.pc_last_component_times(self._h, ctypes.byref(a), ctypes.byref(b)))
         return labels, dict(stats.as_dict(), n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value),
                             ms_union=float(a.value), ms_labels=float(b.value))
+
+    NEAREST_MAX_K = 64                    # PC_NEAREST_MAX_K: a genome's list lives one entry per lane of a wave
+
+    def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """Each genome's ``kk = min(k, N - 1)`` nearest neighbours as ``(nbr, val)``: int32[N, kk] genome indices and float64[N, kk]
+        values, row g listing the genomes h != g best first -- the smallest distance (``as_distance``), else the largest
+        similarity -- and equal values in index order: ``SymMatrix.nearest_neighbors(g, threshold)`` with the threshold wide
+        open, cut after kk.  The values are the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of
+        HBM at a time; 0 = automatic) held, as by :meth:`fill_edges`.  ``k`` above :attr:`NEAREST_MAX_K` is refused by the
+        library.  The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s
+        terms.  ``want_stats`` adds the fills' summed stats with ``k`` (= kk), ``n_slabs``, ``ms_select`` and ``ms_finish``."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        self._invalidate_loans()
+        pn, pv = _i32p(), _f64p()
+        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_fill_nearest(self._h, METRIC_IDS[metric], int(bool(as_distance)), int(k), int(slab_bytes),
+                                              ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl), ctypes.byref(stats)))
+        n = self.n_genomes
+        if n and kk.value and pn and pv:
+            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
+        else:
+            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
+        if not want_stats:
+            return nbr, val
+        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.pc_last_nearest_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return nbr, val, dict(stats.as_dict(), k=int(kk.value), n_slabs=int(nsl.value), ms_select=float(a.value), ms_finish=float(b.value))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -352,6 +352,7 @@ def _metric_name(func):
     return metrics.ACCELERATED.get(func)
 
 
+NEAREST_MAX_K = 64      # PC_NEAREST_MAX_K of the C-ABI: the k a nearest-neighbours fill takes at most
 LAST_FILL = {}          # what the last accelerated matrix_de_novo did: the pipeline's log line reads it
 
 
@@ -949,6 +950,110 @@ def submatrices_de_novo(genomes, func, groups, as_distance=True):
         else:
             out.append(SymMatrix.from_condensed(nodes, condensed, is_distance=as_distance))
     return out
+
+
+class NearestNeighbors:
+    """Each node's ``k`` nearest neighbours: ``indices[g]`` (int32[N, k], indices into ``nodes``) lists the nodes h != g best first
+    -- the smallest weight on distances, the largest on similarities -- equally good ones in node order, and ``weights[g]``
+    (float64[N, k]) their weights.  It is ``SymMatrix.nearest_neighbors(node, threshold)`` of the reference (matrix.py:265-296) with
+    the threshold wide open, cut after ``k``, for every node at once; ``neighbors_de_novo`` fills it on the GPU without the dense
+    matrix, ``from_dense`` states it on the host."""
+
+    def __init__(self, nodes, indices, weights, is_distance=True):
+        self.nodes = list(nodes)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if self.indices.ndim != 2 or self.indices.shape != self.weights.shape or self.indices.shape[0] != len(self.nodes):
+            raise ValueError("indices and weights must be two (len(nodes), k) arrays")
+        self.is_distance = bool(is_distance)
+        self._slot = None
+
+    @classmethod
+    def from_dense(cls, matrix, k):
+        """The ``min(k, N - 1)`` nearest neighbours of every node of a filled ``SymMatrix``, in its current node order: per row
+        one ``np.lexsort`` over (index, weight) -- the better weight first by a plain float compare, equal weights by index --
+        cut after k.  Host arithmetic: the statement ``Context.fill_nearest`` is held to."""
+        if int(k) < 1:
+            raise ValueError("k must be at least 1")
+        data = matrix._ordered()
+        n = len(matrix)
+        kk = max(min(int(k), n - 1), 0)
+        indices = np.empty((n, kk), dtype=np.int32)
+        weights = np.empty((n, kk), dtype=np.float64)
+        for g in range(n):
+            others = np.concatenate([np.arange(g), np.arange(g + 1, n)])
+            row = data[g, others]
+            if np.isnan(row).any():
+                raise TypeError("cannot rank neighbours of a node with unset edges")
+            order = np.lexsort((others, row if matrix.is_distance else -row))[:kk]
+            indices[g] = others[order]
+            weights[g] = row[order]
+        return cls(matrix.nodes, indices, weights, is_distance=matrix.is_distance)
+
+    @property
+    def k(self):
+        return int(self.indices.shape[1])
+
+    def __len__(self):
+        return len(self.nodes)
+
+    def _row(self, name):
+        if self._slot is None:
+            self._slot = {node: g for g, node in enumerate(self.nodes)}
+        if name not in self._slot:
+            raise KeyError(f"node '{name}' not in matrix")
+        return self._slot[name]
+
+    def neighbors(self, name):
+        """The names of ``name``'s neighbours, nearest first."""
+        return [self.nodes[h] for h in self.indices[self._row(name)].tolist()]
+
+    def weights_of(self, name):
+        """Their weights, in the same order."""
+        return self.weights[self._row(name)].tolist()
+
+    def __iter__(self):
+        for g, source in enumerate(self.nodes):
+            for h, w in zip(self.indices[g].tolist(), self.weights[g].tolist()):
+                yield source, self.nodes[h], w
+
+    def inverted(self):
+        """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SparseEdges.inverted``; the order is kept."""
+        return NearestNeighbors(self.nodes, self.indices, np.round(1.0 - self.weights, 6), is_distance=not self.is_distance)
+
+    def to_edges(self, mutual=False):
+        """The undirected k-nearest-neighbours graph as a :class:`SparseEdges`: the pair {g, h} is an edge when either end lists
+        the other -- with ``mutual`` when both do -- once each, sorted by target, then source."""
+        n, k = len(self.nodes), self.k
+        g = np.repeat(np.arange(n, dtype=np.int64), k)
+        h = self.indices.reshape(-1).astype(np.int64)
+        pair = np.maximum(g, h) * n + np.minimum(g, h)                   # ascending = by target, then source
+        pair, first, listed = np.unique(pair, return_index=True, return_counts=True)
+        keep = listed == 2 if mutual else np.ones(pair.shape[0], dtype=bool)
+        pair, first = pair[keep], first[keep]
+        return SparseEdges(self.nodes, pair % max(n, 1), pair // max(n, 1), self.weights.reshape(-1)[first], is_distance=self.is_distance)
+
+
+def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
+    """Each genome's ``k`` nearest neighbours in ``matrix_de_novo(genomes, func, cpus, as_distance)`` as a
+    :class:`NearestNeighbors`, filled on the GPU by ``Context.fill_nearest``: the dense matrix is never delivered, and beyond
+    ``slab_bytes`` of HBM (0: automatic) never held; N * k entries cross PCIe.  ``func`` must be one of the six ``METRICS``
+    callables (no CPU route: ``NearestNeighbors.from_dense(matrix_de_novo(...), k)`` serves another callable).  One GPU, as
+    ``edges_de_novo``: under a launcher (``WORLD_SIZE`` > 1) it raises.  Every refusal comes before the first GPU call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NEAREST_MAX_K:
+        raise ValueError(f"neighbors_de_novo: k must be an integer in 1..{NEAREST_MAX_K}, not {k!r}")
+    ctx, metric, names, record = upload_for_fills(genomes, func, "neighbors_de_novo")
+    import time
+    t0 = time.perf_counter()
+    nbr, val, stats = ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    fill_s = time.perf_counter() - t0
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=record["genome_pairs"], n_gpus=1, rank=0,
+                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
+    logging.debug(f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in {stats['n_slabs']} "
+                  f"slab(s) on one device: fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection "
+                  f"{stats['ms_select']:.3f} ms)")
+    return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 
 def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, upload_for_fills
+from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -259,6 +259,27 @@ class _Run:
         log.info(f"wrote {target.name}")
         return found
 
+    # 2, --nearest
+    def nearest(self, k):
+        """Stage 2 as a nearest-neighbours fill: each genome's ``k`` closest genomes, and only ``nearest_<metric>.tsv`` is written:
+        ``source<TAB>target<TAB>similarity``, sources in genome order, targets nearest first (equally near ones in genome order).
+        Distances are filled and inverted, as for the adjacency file.  No matrix, no threshold, nothing cached or clustered."""
+        self.banner(2, f"{self.metric} nearest neighbours (nearest-neighbours fill)")
+        t0 = time.perf_counter()
+        found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True)
+        st = _matrix.LAST_FILL
+        log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {found.k} nearest of each of {len(found):,} genomes from {st.get('n_slabs', 1)} slab(s) "
+                 f"on 1 GPU in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, "
+                 f"fill+select+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, selection "
+                 f"{st.get('ms_select', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        target = self.outdir / f"nearest_{self.metric}.tsv"
+        with open(target, "w") as handle:
+            handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in found.inverted())
+        log.info(f"wrote {target.name}")
+        return found
+
     def extended(self, cpus, t0):
         """Stage 2 under --extend: the old matrix's block is kept, the rows of the genomes it lacks are filled (matrix_extend)."""
         try:
@@ -416,13 +437,19 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False):
+              components_only=False, no_matrix=False, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
     ``components_only``: stop after a components fill -- genomes joined when distance < round(1 - ``edge_thresh``, 6), None: 0.0 --
     and write only ``components_<metric>.tsv``; ``no_matrix``: stages 2-3 from components and groups fills, without the dense matrix
-    (same clusters; no similarities file, no dataset heatmap, no matrix cache; the adjacency file from an edge-list fill)."""
+    (same clusters; no similarities file, no dataset heatmap, no matrix cache; the adjacency file from an edge-list fill);
+    ``nearest``: stop after a nearest-neighbours fill of that many neighbours per genome and write only ``nearest_<metric>.tsv``."""
+    if nearest is not None:
+        if isinstance(nearest, bool) or not isinstance(nearest, int) or not 1 <= nearest <= _matrix.NEAREST_MAX_K:
+            raise ValueError(f"nearest is a number of neighbours in 1..{_matrix.NEAREST_MAX_K}")
+        if adjacency_only or components_only or no_matrix or extend is not None:
+            raise ValueError("nearest cannot be combined with adjacency_only, components_only, no_matrix or extend")
     if no_matrix and (adjacency_only or components_only or extend is not None):
         raise ValueError("no-matrix cannot be combined with adjacency_only, components_only or extend")
     if no_matrix and "ward" in (nr_linkage, clu_linkage):
@@ -446,6 +473,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["matrix"] = "none (--no-matrix: components and groups fills)"
     if components_only:
         settings["components"] = f"only, joined at similarity > {0.0 if edge_thresh is None else edge_thresh}"
+    if nearest is not None:
+        settings["nearest"] = f"only, {nearest} neighbours per genome"
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
@@ -467,6 +496,13 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             sys.exit(1)
         run.components(0.0 if edge_thresh is None else edge_thresh)
         run.banner(3, "done (--components-only: no clustering)")
+        return
+    if nearest is not None:
+        if run.world > 1:
+            log.error("--nearest is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.nearest(nearest)
+        run.banner(3, "done (--nearest: no clustering)")
         return
     matrix = None
     if no_matrix:
@@ -545,6 +581,10 @@ def _run(args, argv):
         # and so is the components fill (pc_fill_components refuses a sharded context)
         gpus_note = "--components-only fills component labels, which is a one-GPU call: the matrix stage stays on one GPU"
         os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
+    elif args.gpus > 1 and world == 1 and args.nearest is not None:
+        # and the nearest-neighbours fill (pc_fill_nearest refuses a sharded context)
+        gpus_note = "--nearest fills nearest-neighbour lists, which is a one-GPU call: the matrix stage stays on one GPU"
+        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
     elif args.gpus > 1 and world == 1 and args.extend is not None:
         # the rows fill of --extend is a one-GPU call (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
         gpus_note = "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
@@ -597,7 +637,8 @@ def _run(args, argv):
                   sub_distance=as_distance(args.sub_thresh), sub_linkage=args.sub_linkage, k_min=max(1, args.k_min),
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
-                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix)
+                  adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
+                  nearest=args.nearest)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
