@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 159   /* 0.5.8: pc_fill_nearest */
+#define PC_VERSION 160   /* 0.5.9: pc_multi_fill_edges / _components / _nearest, pc_stretch_plan */
 
 typedef enum {
     PC_OK = 0,
@@ -246,7 +246,8 @@ int64_t pc_group_tiles(const int64_t* group_off, int n_groups, int32_t* tile_row
  * stats: summed over the slabs' fills -- n_pairs = N(N-1)/2, n_chunks, the counts and the times added up (the compaction and the
  * copy are not in them: pc_last_edge_times).  *n_slabs: ranges the rule cut (a range holding target 0 alone counts, though it has no pair).
  * PC_OK also for N <= 1 or nothing passing, with *n_edges = 0.  PC_ERR_ARG: bad metric, NaN threshold, negative slab_bytes, a NULL
- * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA:
+ * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1: one context walks all the slabs; several GPUs of a
+ * node share the walk through pc_multi_fill_edges), aai / peq before pc_upload_residues.  PC_ERR_DATA:
  * as for a whole fill.  Runs on the context's own stream and returns with everything finished.
  */
 int pc_fill_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, int64_t slab_bytes,
@@ -270,7 +271,8 @@ int pc_last_edge_times(const pc_ctx* ctx, float* ms_compact, float* ms_d2h);
  * context or its destruction); *n_components = genomes g with labels[g] == g; *n_edges = pairs that passed; *n_slabs and stats as
  * pc_fill_edges gives them (the union and labelling passes are not in stats: pc_last_component_times).
  * PC_OK also for N <= 1 or nothing passing (identity labels).  PC_ERR_ARG: bad metric, NaN threshold, negative slab_bytes, a NULL
- * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1), aai / peq before pc_upload_residues.  On a refusal
+ * out pointer.  PC_ERR_STATE: before upload, on a sharded context (world != 1: several GPUs share the walk through
+ * pc_multi_fill_components), aai / peq before pc_upload_residues.  On a refusal
  * *labels is NULL and the counts are 0.  The caller's unsharded state is back in force when the call returns, whatever it returns.
  */
 int pc_fill_components(pc_ctx* ctx, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
@@ -300,7 +302,7 @@ int pc_last_component_times(const pc_ctx* ctx, float* ms_union, float* ms_labels
  * in force when the call returns, whatever it returns.
  * PC_OK also for N <= 1, with *k_out = 0 and nothing written.  PC_ERR_ARG: bad metric, k < 1, negative slab_bytes, a NULL out pointer.
  * PC_ERR_LIMIT: k > PC_NEAREST_MAX_K (a genome's list lives one entry per lane of a wave).  PC_ERR_STATE: before upload, on a sharded
- * context (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill.  On a refusal *nbr and *val are NULL
+ * context (world != 1: several GPUs share the walk through pc_multi_fill_nearest), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill.  On a refusal *nbr and *val are NULL
  * and *k_out is 0.  Runs on the context's own stream and returns with everything finished.
  */
 #define PC_NEAREST_MAX_K 64
@@ -367,6 +369,49 @@ int pc_multi_upload(pc_multi* m, const pc_packed* genomes, int with_residues);
 int pc_multi_upload_residues(pc_multi* m, const pc_packed* genomes);
 int pc_multi_set_tie_rule(pc_multi* m, int rule);
 int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, const double** out_host, pc_stats* stats, float* exchange_ms, float* assemble_ms);
+
+/*
+ * The three fills that deliver a result without the dense matrix, over the devices of `m`: pc_multi_fill_edges, _components and
+ * _nearest.  Each has the contract of its single-context namesake (pc_fill_edges, pc_fill_components, pc_fill_nearest) word for word
+ * -- values, order, canonical result, PC_OK for N <= 1, PC_ERR_ARG / LIMIT / STATE / DATA, output pointers nulled on a refusal --
+ * and its result does not depend on the number of devices.  Results live in page-locked memory of the ROOT context under the loan
+ * rule (valid until the next fill or upload on `m`).  stats: NULL or an array of pc_multi_devices(m) entries, each device's summed
+ * fills (a device whose stretch is empty reports zeros); *n_slabs: the sum over the devices.  One device (world == 1): the
+ * single-context call.  Every context is unsharded when a call returns, whatever it returns; pc_multi_fill_borrow deals anew on every
+ * call, so the two kinds of fill do not disturb each other.  PC_ERR_STATE: before pc_multi_upload; aai / peq before the residues.
+ * The deal.  The slab walk needs consecutive targets, so the pair shard's scattered deal cannot serve: device r walks ONE contiguous
+ * stretch [bounds[r], bounds[r + 1]) of targets and cuts it into slabs by the single-context rule -- pc_chunk_plan over count[t] = t
+ * for the targets of the stretch, so its first range starts at bounds[r].  The root computes the bounds once per call:
+ * pc_stretch_plan over cost[t] = target_cost[t] + 2000 t for aai / peq (pc_set_shard_balanced's formula; target_cost the DP cells per
+ * target of its COUNT walk, computed on the root without leaving a deal in force), cost[t] = t for gcs / jc / pocp / af.  aai / peq
+ * merge duplicate sequence pairs per slab only, so target_cost overstates a stretch's work unevenly: the deal balances what it can
+ * count (profiles/multi_slab_fill.txt states the imbalance it leaves).  pc_multi_last_stretches: the bounds of the last such call.
+ * What travels.  Every device runs its stretch with the call's state on ITS device; then, once:
+ *   nearest     key[N][kk] and nbr[N][kk], 12 N kk bytes per device, into a staging slice on the root (hipMemcpyPeerAsync, or a
+ *               device-to-device copy on the root's own GPU); ONE launch of k_nn_merge (one wave per genome) merges them, in key space,
+ *               into the root's lists before its finishing pass: the result is the K smallest of one total order, so lists merge by it
+ *   components  parent[N], 4 N bytes per device, and its 8-byte count of passing pairs (summed on the host: a pair lies in exactly one
+ *               stretch); ONE launch of k_cc_merge unites every genome with its parent in each foreign forest, then the root labels
+ *   edges       no kernel: the devices' counts are known after their walks, the root's pinned arrays are grown to the total and each
+ *               device's edges copied behind those of the ranks before it -- stretches ascend in targets and each list is sorted by
+ *               (t, s), so the concatenation is
+ * Devices with an empty stretch (more devices than targets with pairs) launch nothing and ship nothing.
+ * pc_multi_last_slab_times: of the last such call, *ms_exchange the slowest device's copy to the root (HIP events; edges: the host
+ * copy into the root's arrays, wall clock) and *ms_merge the root's merge kernel (edges: 0); either pointer may be NULL.
+ */
+int pc_multi_fill_edges(pc_multi* m, int metric, int as_distance, double threshold, int64_t slab_bytes,
+                        const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+int pc_multi_fill_components(pc_multi* m, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
+                             const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, int k, int64_t slab_bytes,
+                          const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats);
+int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds /* pc_multi_devices(m) + 1 entries */);
+int pc_multi_last_slab_times(const pc_multi* m, float* ms_exchange, float* ms_merge);
+/* The stretch deal itself, host arithmetic only (no GPU, no context; exported for tests as pc_chunk_plan is): bounds[world + 1] with
+ * bounds[0] = 0, bounds[world] = n, and for 0 < r < world bounds[r] the smallest t in [0, n] with P(t) * world >= r * P(n),
+ * P(t) = cost[0] + ... + cost[t-1] (sums below 2^63; the products are 128-bit).  Non-decreasing; a stretch may be empty (world > n,
+ * or zero costs).  PC_ERR_ARG: n < 0, world < 1, a NULL pointer. */
+int pc_stretch_plan(const uint64_t* cost, int n, int world, int32_t* bounds);
 
 /*
  * Test hook for the alignment kernels (replaces parasail.nw_trace_diag_16 +

@@ -50,17 +50,19 @@ _OPTIONS = (
                                                                        "02_distmats/<metric>_distance_matrix.tsv, or a squareform file): only the rows "
                                                                        "of the genomes it lacks are filled, on one GPU")),
     (None, "-A", "--adjacency-only", dict(action="store_true", help="stop after the matrix stage and write only pairwise_<metric>_adjacency.tsv, from an "
-                                                                    "edge-list fill: the dense matrix is neither delivered nor cached, and no clustering runs")),
+                                                                    "edge-list fill: the dense matrix is neither delivered nor cached, and no clustering runs; "
+                                                                    "with --gpus N the fill is spread over N GPUs of this process")),
     (None, "-C", "--components-only", dict(action="store_true", help="stop after the matrix stage and write only components_<metric>.tsv, from a "
                                                                      "components fill: the single-linkage groups at --edge-thresh (genomes joined "
-                                                                     "when distance < 1 - SIM); no matrix, no edge list, no clustering")),
+                                                                     "when distance < 1 - SIM); no matrix, no edge list, no clustering; with --gpus N "
+                                                                     "the fill is spread over N GPUs of this process")),
     (None, "-N", "--no-matrix", dict(action="store_true", help="cluster without the dense matrix: components fills find the groups, groups fills "
                                                                "their sub-matrices (sum of n_c^2 cells, not N^2); same cluster_* / singletons "
                                                                "output; the adjacency file comes from an edge-list fill; no "
                                                                "pairwise_<metric>_similarities.tsv, no dataset heatmap, no matrix cache; one GPU")),
     (None, "-K", "--nearest", dict(type=int, default=None, help="stop after the matrix stage and write only nearest_<metric>.tsv, from a nearest-neighbours "
                                                                "fill: each genome's K most similar genomes (1..64), most similar first; no matrix, "
-                                                               "no threshold, no clustering")),
+                                                               "no threshold, no clustering; with --gpus N the fill is spread over N GPUs of this process")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -69,7 +71,9 @@ _OPTIONS = (
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),
     (None, "-G", "--gpus", dict(type=int, default=GPUS, help="GPUs of this node to spread the matrix fill over (one process per GPU "
-                                                              "under torch.distributed.run, static pair shard, one RCCL gather)")),
+                                                              "under torch.distributed.run, static pair shard, one RCCL gather); "
+                                                              "--adjacency-only, --components-only and --nearest spread over them "
+                                                              "from one process, a stretch of target genomes per GPU")),
 )
 DEFAULTS = {long.lstrip("-").replace("-", "_"): kw.get("default", False) for _, _, long, kw in _OPTIONS}
 

@@ -178,11 +178,15 @@ int pc_launch_cc_init(int32_t* parent, int n, unsigned long long* n_pass, hipStr
 int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, const PcShard& sh, int32_t* parent,
                        unsigned long long* n_pass, hipStream_t st);
 int pc_launch_cc_labels(int32_t* parent, int32_t* labels, int n, hipStream_t st);
+// the forests of other devices united into parent[] (pc_multi_fill_components): fparent[n_foreign][n], each a forest k_cc_union left
+int pc_launch_cc_merge(int32_t* parent, const int32_t* fparent, int n_foreign, int n, hipStream_t st);
 // nearest neighbours of a filled slab (pc_nearest.hip): key[N * K] / nbr[N * K] set to the worst sentinel; the pairs of the slab of
 // targets [t0, t1) merged into the K slots of every genome they touch (the row pass, then the column pass); values back from the keys
 int pc_launch_nn_init(unsigned long long* key, int32_t* nbr, int64_t n, hipStream_t st);
 int pc_launch_nn_select(const double* vals, int64_t Lp, int t0, int t1, int as_distance, int K, unsigned long long* key, int32_t* nbr, hipStream_t st);
 int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st);
+// the lists of other devices merged into key / nbr [N][K] (pc_multi_fill_nearest): fkey / fnbr [n_foreign][N][K], in key space
+int pc_launch_nn_merge(unsigned long long* key, int32_t* nbr, const unsigned long long* fkey, const int32_t* fnbr, int n_foreign, int N, int K, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

@@ -8,6 +8,10 @@
 //                 eight 16-byte loads per thread, the odd last element alone, nothing read beyond Lp); (s, t) of a passing element
 //                 as k_edge_emit finds it (one binary search of lbase per chunk, then the forward walk over empty and short rows);
 //                 per passing pair: find both roots, equal -> done, else hook the LARGER root under the SMALLER by compare-and-swap
+//   k_cc_merge    several devices, each with the forest of its own stretch of targets (pc_multi_fill_components): thread g unites g
+//                 with its parent in every foreign forest fparent[f][n].  By I1 that parent p <= g is a node of g's foreign component,
+//                 and the edges (g, fparent[g]) span every foreign component, so the root's forest ends up with exactly the components
+//                 of the union of all devices' passing pairs; pc_cc_unite hooks larger under smaller, so I1 / I2 go on holding.
 //   k_cc_labels   pointer jumping, launched ceil(log2 N) times after the last slab: labels[g] = the root of g
 // Two invariants carry the correctness argument:
 //   I1  parent[x] <= x, always.  (init: equal; a hook writes lo < hi into parent[hi]; a shortening writes an ancestor, which by I1
@@ -128,6 +132,16 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_union(const double* __restric
     }
 }
 
+// the same relaxed agent-scope atomics on parent[] as k_cc_union (through pc_cc_unite); the foreign forests are read-only here
+__global__ __launch_bounds__(256) void k_cc_merge(int32_t* parent, const int32_t* __restrict__ fparent, int n_foreign, int n) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    for (int f = 0; f < n_foreign; ++f) {
+        const int p = fparent[(size_t)f * n + g];
+        if (p != g) pc_cc_unite(parent, g, p);
+    }
+}
+
 // one round of pointer jumping (a launch of its own: plain accesses).  Thread g alone writes parent[g]; the grandparent it reads is
 // the old one or one already jumped, an ancestor either way, so a node of depth d is at depth <= ceil(d / 2) afterwards.
 __global__ __launch_bounds__(256) void k_cc_labels(int32_t* parent, int32_t* __restrict__ labels, int n) {
@@ -159,6 +173,13 @@ int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int stri
     else if (strict) hipLaunchKernelGGL((k_cc_union<0, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
     else hipLaunchKernelGGL((k_cc_union<0, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
     return cc_check("k_cc_union");
+}
+
+// fparent: [n_foreign][n], every value in [0, n) (a forest k_cc_union left: I1)
+int pc_launch_cc_merge(int32_t* parent, const int32_t* fparent, int n_foreign, int n, hipStream_t st) {
+    if (n_foreign <= 0 || n <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_cc_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parent, fparent, n_foreign, n);
+    return cc_check("k_cc_merge");
 }
 
 // depth <= n - 1 before; ceil(log2 n) halvings leave depth <= 1, and the last round's labels read two levels up: the root

@@ -1,7 +1,8 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
-// pc_last_nearest_times.  Host only.
+// pc_last_nearest_times.  Each call is four phases on its context (check, begin, walk over a stretch of targets, end: PcSlabRun in
+// pc_host.h); the public calls walk [0, N), pc_multi_fill_* (pc_multi.hip) runs the same phases on a stretch per device.  Host only.
 //
 // The walk they share goes over successive contiguous ranges of target genomes ("slabs": pc_chunk_plan over count[t] = t under
 // slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is installed as a PcShard (owned = t0 .. t1-1,
@@ -24,18 +25,27 @@ struct SlabShardScope {
 
 static int64_t pairs_below(int64_t t) { return t * (t - 1) / 2; }           // pairs (s, t'), s < t' < t
 
-// The checks the calls make, after fill_check's (pc_fill_nearest has no threshold and passes 0); outputs: every output pointer is there
-static int slab_check(const pc_ctx* c, const char* who, bool outputs, int metric, double threshold, int64_t slab_bytes) {
+// The checks the calls make, in the public calls' order: fill_check's, pc_fill_nearest's k, then outputs (every output pointer is
+// there), the threshold (pc_fill_nearest has none and passes 0), slab_bytes, and the residues aai / peq need.  Nothing is touched.
+int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* kind, bool outputs) {
+    int rc = PC_OK;
+    const char* who = run.who;
+    if ((rc = fill_check(c, who, kind, &run.metric, nullptr))) return rc;
+    if (run.k != 0 || run.kk < 0) {                                         // (a nearest-neighbours fill: kk < 0 marks it until begin sets it)
+        if (run.k < 1) { pc_set_error("%s: k %d", who, run.k); return PC_ERR_ARG; }
+        if (run.k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, run.k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
+    }
     if (!outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
-    if (threshold != threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
-    if (slab_bytes < 0) { pc_set_error("%s: slab_bytes %lld", who, (long long)slab_bytes); return PC_ERR_ARG; }
-    return fill_check_residues(c, who, metric);
+    if (run.threshold != run.threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
+    if (run.slab_bytes < 0) { pc_set_error("%s: slab_bytes %lld", who, (long long)run.slab_bytes); return PC_ERR_ARG; }
+    if ((rc = fill_check_residues(c, who, run.metric))) return rc;
+    run.as_distance = run.as_distance ? 1 : 0; run.strict = run.strict ? 1 : 0;
+    return PC_OK;
 }
 
-// The cut (N > 1): ranges of targets whose pairs fit the slab, range starts followed by N, and the slab buffer sized for the largest.
-// slab_bytes == 0: the dense triangle, or a quarter of what is free now (an aai / peq slab's plan takes its own half) -- so this runs
-// before the call allocates anything of its own.
-static int slab_cut(pc_ctx* c, int64_t slab_bytes, std::vector<int32_t>& cut) {
+// Pairs one slab may hold (N > 1).  slab_bytes == 0: the dense triangle, or a quarter of what is free now (an aai / peq slab's plan
+// takes its own half) -- so this runs before the call allocates anything of its own.
+static int64_t slab_max_pairs(pc_ctx* c, int64_t slab_bytes) {
     const int N = c->dev.N;
     int64_t max_pairs;
     if (slab_bytes > 0) max_pairs = std::max<int64_t>(slab_bytes / 8, 1);
@@ -44,17 +54,29 @@ static int slab_cut(pc_ctx* c, int64_t slab_bytes, std::vector<int32_t>& cut) {
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
         max_pairs = std::min<int64_t>(pairs_below(N), std::max<int64_t>((int64_t)((free_b + c->b_edge_slab.cap) / 4 / 8), 1));
     }
-    max_pairs = std::min<int64_t>(max_pairs, PC_EDGE_MAX_PAIRS);
-    std::vector<uint64_t> per_target((size_t)N);
-    for (int t = 0; t < N; ++t) per_target[t] = (uint64_t)t;
-    const int nsl = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, nullptr, 0);
+    return std::min<int64_t>(max_pairs, PC_EDGE_MAX_PAIRS);
+}
+
+// The cut of the targets [ta, tb), 0 <= ta < tb <= N: ranges of targets whose pairs fit the slab -- the chunking rule over count[t] = t
+// for the targets of the stretch, so the first range starts at ta -- range starts followed by tb, and the slab buffer sized for the largest.
+static int slab_cut(pc_ctx* c, int64_t max_pairs, int ta, int tb, std::vector<int32_t>& cut) {
+    const int n = tb - ta;
+    std::vector<uint64_t> per_target((size_t)n);
+    for (int t = ta; t < tb; ++t) per_target[t - ta] = (uint64_t)t;
+    const int nsl = pc_chunk_plan(per_target.data(), n, (uint64_t)max_pairs, nullptr, 0);
     if (nsl < 0) return nsl;
     cut.resize((size_t)nsl + 1);
     int rc = PC_OK;
-    if ((rc = pc_chunk_plan(per_target.data(), N, (uint64_t)max_pairs, cut.data(), nsl + 1)) < 0) return rc;
+    if ((rc = pc_chunk_plan(per_target.data(), n, (uint64_t)max_pairs, cut.data(), nsl + 1)) < 0) return rc;
+    for (int32_t& x : cut) x += ta;
     int64_t most = 1;
     for (int i = 0; i < nsl; ++i) most = std::max(most, pairs_below(cut[i + 1]) - pairs_below(cut[i]));
     return abi_rc(c->b_edge_slab.ensure((size_t)most * 8));
+}
+static bool stretch_ok(const pc_ctx* c, const PcSlabRun& run, int ta, int tb) {
+    if (0 <= ta && ta <= tb && tb <= c->dev.N) return true;
+    pc_set_error("%s: targets [%d, %d) of %d", run.who, ta, tb, c->dev.N);
+    return false;
 }
 
 // The walk: slab by slab the shard installed, the slab filled (its stats added to *sum when sum != NULL), then hook(slab, Lp, shard) --
@@ -94,36 +116,31 @@ template <class Hook> static int slab_walk(pc_ctx* c, const std::vector<int32_t>
 // what matrix_to_adjacency(skip_zero) writes and SymMatrix.nearest_neighbors answers from the dense matrix (matrix.py:536-551,
 // 265-296), without the dense matrix ever crossing PCIe.  Each filled slab is compacted (count -> scan -> one 4-byte read-back -> emit,
 // pc_edges.hip) and its edges appended to the pinned host result; slabs in ascending target order make the concatenation globally ordered.
-extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
-                             const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
+int pc_edges_begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
-    if ((rc = fill_check(c, "pc_fill_edges", "an edge-list fill", &metric, nullptr)) ||
-        (rc = slab_check(c, "pc_fill_edges", src && tgt && val && n_edges && n_slabs, metric, threshold, slab_bytes))) return rc;
-    PC_ON_DEVICE(c);
-    PcRange range("pc:fill_edges");
-    hipStream_t st = c->stream;
-    pc_stats sum; memset(&sum, 0, sizeof(sum));
+    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.n_edges = 0;
     c->last_edge_ms[0] = c->last_edge_ms[1] = 0.f;
-    as_distance = as_distance ? 1 : 0;
-    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffers are rewritten)
+    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffers are rewritten)
     if ((rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
-    if (c->dev.N <= 1) {
-        *src = c->h_edge_src.as<int32_t>(); *tgt = c->h_edge_tgt.as<int32_t>(); *val = c->h_edge_val.as<double>();
-        if (stats) *stats = sum;
-        return PC_OK;
-    }
+    if (c->dev.N <= 1) return PC_OK;
+    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if (run.timed) for (hipEvent_t& e : c->ev_edge) if (!e) PC_HIP(hipEventCreate(&e));
+    return PC_OK;
+}
+
+int pc_edges_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
+    if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
+    if (c->dev.N <= 1 || ta == tb) return PC_OK;
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const bool stats = run.timed;
+    const int as_distance = run.as_distance; const double threshold = run.threshold;
     std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, slab_bytes, cut))) return rc;
-    if (stats) for (hipEvent_t& e : c->ev_edge) if (!e) PC_HIP(hipEventCreate(&e));
+    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
     uint32_t* const h_total = c->h_plan.as<uint32_t>();
-    int64_t E = 0;
+    int64_t& E = run.n_edges;
     // ---- a slab's hook, compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit
-    rc = slab_walk(c, cut, metric, as_distance, stats ? &sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
+    rc = slab_walk(c, cut, run.metric, as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
         int rc = PC_OK;
         const int64_t nch = pc_edge_chunks(Lp);
         if ((rc = c->b_edge_cnt.ensure((size_t)(nch + 1) * 4)) || (rc = c->b_edge_off.ensure((size_t)(nch + 1) * 4)) ||
@@ -165,9 +182,28 @@ extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double thre
         return PC_OK;
     });
     if (rc != PC_OK) return rc;
+    run.n_slabs += (int32_t)cut.size() - 1;
+    return PC_OK;
+}
+
+// (an edge-list fill has no end phase of its own: the edges are in the context's pinned arrays when a walk returns)
+extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
+                             const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    int rc = PC_OK;
+    PcSlabRun run; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
+    if ((rc = pc_slab_check(c, run, "an edge-list fill", src && tgt && val && n_edges && n_slabs))) return rc;
+    PC_ON_DEVICE(c);
+    PcRange range("pc:fill_edges");
+    if ((rc = pc_edges_begin(c, run)) || (rc = pc_edges_walk(c, run, 0, c->dev.N))) return rc;
     *src = c->h_edge_src.as<int32_t>(); *tgt = c->h_edge_tgt.as<int32_t>(); *val = c->h_edge_val.as<double>();
-    *n_edges = E; *n_slabs = (int32_t)cut.size() - 1;
-    if (stats) *stats = sum;
+    *n_edges = run.n_edges; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
     return PC_OK;
 }
 
@@ -183,6 +219,81 @@ extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_
 // goes through ONE pass, k_cc_union (pc_components.hip), over a parent[N] array that stays on the device from the first slab to the
 // last; nothing is read back per slab.  After the last slab: k_cc_labels, then one D2H of labels[N] and the 8-byte count of passing
 // pairs behind them.
+static int cc_add_union_time(pc_ctx* c) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_cc[0], c->ev_cc[1])); c->last_cc_ms[0] += x; return PC_OK; }
+
+int pc_components_begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.n_edges = 0; run.pending = false;
+    c->last_cc_ms[0] = c->last_cc_ms[1] = 0.f;
+    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffer is rewritten)
+    const size_t label_bytes = pc_cc_label_bytes(N);
+    if ((rc = c->h_cc_labels.ensure(label_bytes + 8))) return rc;
+    if (N <= 1) return PC_OK;
+    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if ((rc = c->b_cc_parent.ensure((size_t)N * 4)) || (rc = c->b_cc_labels.ensure(label_bytes + 8))) return abi_rc(rc);
+    if (run.timed) for (hipEvent_t& e : c->ev_cc) if (!e) PC_HIP(hipEventCreate(&e));
+    return pc_launch_cc_init(c->b_cc_parent.as<int32_t>(), N, pc_cc_pass_counter(c), c->stream);
+}
+
+int pc_components_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
+    if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
+    if (c->dev.N <= 1 || ta == tb) return PC_OK;
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const bool stats = run.timed;
+    std::vector<int32_t> cut;
+    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
+    int32_t* const parent = c->b_cc_parent.as<int32_t>();
+    unsigned long long* const d_pass = pc_cc_pass_counter(c);
+    // ---- a slab's hook: the union pass, left running (the walk has waited for the pass before it: its two events can be read)
+    rc = slab_walk(c, cut, run.metric, run.as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
+        int rc = PC_OK;
+        if (stats && run.pending && (rc = cc_add_union_time(c))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_cc[0], st));
+        if ((rc = pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, shard, parent, d_pass, st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_cc[1], st));
+        run.pending = true;
+        return mark_work(c, st);
+    });
+    if (rc != PC_OK) return rc;
+    run.n_slabs += (int32_t)cut.size() - 1;
+    return PC_OK;
+}
+
+// foreign_pass: pairs that passed on other devices (pc_multi_fill_components; a pair lies in exactly one stretch)
+int pc_components_end(pc_ctx* c, PcSlabRun& run, int64_t foreign_pass, const int32_t** labels, int32_t* n_components, int64_t* n_edges) {
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const int N = c->dev.N;
+    const bool stats = run.timed;
+    const size_t label_bytes = pc_cc_label_bytes(N);
+    int32_t* const h_labels = c->h_cc_labels.as<int32_t>();
+    if (N <= 1) {
+        if (N == 1) { h_labels[0] = 0; *n_components = 1; }
+        *labels = h_labels;
+        return PC_OK;
+    }
+    if (stats) PC_HIP(hipEventRecord(c->ev_cc[2], st));
+    if ((rc = pc_launch_cc_labels(c->b_cc_parent.as<int32_t>(), c->b_cc_labels.as<int32_t>(), N, st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_cc[3], st));
+    PC_HIP(hipMemcpyAsync(h_labels, c->b_cc_labels.p, label_bytes + 8, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if (stats) {
+        if (run.pending && (rc = cc_add_union_time(c))) return rc;          // (the last slab's pass)
+        PC_HIP(hipEventElapsedTime(&c->last_cc_ms[1], c->ev_cc[2], c->ev_cc[3]));
+    }
+    run.pending = false;
+    int32_t comps = 0;
+    for (int g = 0; g < N; ++g) comps += h_labels[g] == g;
+    unsigned long long passed = 0;
+    memcpy(&passed, (const char*)h_labels + label_bytes, 8);
+    run.n_edges = (int64_t)passed + foreign_pass;
+    *labels = h_labels; *n_components = comps; *n_edges = run.n_edges;
+    return PC_OK;
+}
+
 extern "C" int pc_fill_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
                                   const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     if (labels) *labels = nullptr;
@@ -190,61 +301,15 @@ extern "C" int pc_fill_components(pc_ctx* c, int metric, int as_distance, double
     if (n_edges) *n_edges = 0;
     if (n_slabs) *n_slabs = 0;
     int rc = PC_OK;
-    if ((rc = fill_check(c, "pc_fill_components", "a components fill", &metric, nullptr)) ||
-        (rc = slab_check(c, "pc_fill_components", labels && n_components && n_edges && n_slabs, metric, threshold, slab_bytes))) return rc;
+    PcSlabRun run; run.who = "pc_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
+    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
+    if ((rc = pc_slab_check(c, run, "a components fill", labels && n_components && n_edges && n_slabs))) return rc;
     PC_ON_DEVICE(c);
     PcRange range("pc:fill_components");
-    hipStream_t st = c->stream;
-    const int N = c->dev.N;
-    pc_stats sum; memset(&sum, 0, sizeof(sum));
-    c->last_cc_ms[0] = c->last_cc_ms[1] = 0.f;
-    as_distance = as_distance ? 1 : 0; strict = strict ? 1 : 0;
-    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffer is rewritten)
-    const size_t label_bytes = ((size_t)std::max(N, 1) * 4 + 7) / 8 * 8;    // the 64-bit count sits behind the labels, aligned
-    if ((rc = c->h_cc_labels.ensure(label_bytes + 8))) return rc;
-    int32_t* const h_labels = c->h_cc_labels.as<int32_t>();
-    if (N <= 1) {
-        if (N == 1) { h_labels[0] = 0; *n_components = 1; }
-        *labels = h_labels;
-        if (stats) *stats = sum;
-        return PC_OK;
-    }
-    std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, slab_bytes, cut))) return rc;
-    if ((rc = c->b_cc_parent.ensure((size_t)N * 4)) || (rc = c->b_cc_labels.ensure(label_bytes + 8))) return abi_rc(rc);
-    if (stats) for (hipEvent_t& e : c->ev_cc) if (!e) PC_HIP(hipEventCreate(&e));
-    int32_t* const parent = c->b_cc_parent.as<int32_t>();
-    unsigned long long* const d_pass = (unsigned long long*)((char*)c->b_cc_labels.p + label_bytes);
-    if ((rc = pc_launch_cc_init(parent, N, d_pass, st))) return rc;
-    bool pending = false;                                                   // a union pass was launched and, with stats, its time not yet added
-    auto add_union_time = [&]() -> int { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_cc[0], c->ev_cc[1])); c->last_cc_ms[0] += x; return PC_OK; };
-    // ---- a slab's hook: the union pass, left running (the walk has waited for the pass before it: its two events can be read)
-    rc = slab_walk(c, cut, metric, as_distance, stats ? &sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
-        int rc = PC_OK;
-        if (stats && pending && (rc = add_union_time())) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_cc[0], st));
-        if ((rc = pc_launch_cc_union(slab, Lp, as_distance, strict, threshold, shard, parent, d_pass, st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_cc[1], st));
-        pending = true;
-        return mark_work(c, st);
-    });
-    if (rc != PC_OK) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_cc[2], st));
-    if ((rc = pc_launch_cc_labels(parent, c->b_cc_labels.as<int32_t>(), N, st))) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_cc[3], st));
-    PC_HIP(hipMemcpyAsync(h_labels, c->b_cc_labels.p, label_bytes + 8, hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    c->busy = false;
-    if (stats) {
-        if (pending && (rc = add_union_time())) return rc;                  // (the last slab's pass)
-        PC_HIP(hipEventElapsedTime(&c->last_cc_ms[1], c->ev_cc[2], c->ev_cc[3]));
-    }
-    int32_t comps = 0;
-    for (int g = 0; g < N; ++g) comps += h_labels[g] == g;
-    unsigned long long passed = 0;
-    memcpy(&passed, (const char*)h_labels + label_bytes, 8);
-    *labels = h_labels; *n_components = comps; *n_edges = (int64_t)passed; *n_slabs = (int32_t)cut.size() - 1;
-    if (stats) *stats = sum;
+    if ((rc = pc_components_begin(c, run)) || (rc = pc_components_walk(c, run, 0, c->dev.N)) ||
+        (rc = pc_components_end(c, run, 0, labels, n_components, n_edges))) return rc;
+    *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
     return PC_OK;
 }
 
@@ -260,6 +325,75 @@ extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* 
 // Each filled slab goes through two passes (pc_nearest.hip: k_nn_rows, k_nn_cols) over key[N][kk] / nbr[N][kk], which stay on the
 // device from the first slab to the last; nothing is read back per slab.  After the last slab: k_nn_finish, then one D2H of
 // val[N][kk] with nbr[N][kk] behind it.
+static int nn_add_select_time(pc_ctx* c) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_nn[0], c->ev_nn[1])); c->last_nn_ms[0] += x; return PC_OK; }
+static size_t nn_entries(const pc_ctx* c, const PcSlabRun& run) { return (size_t)std::max(c->dev.N, 0) * run.kk; }
+
+int pc_nearest_begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    run.kk = std::max(std::min(run.k, N - 1), 0);
+    const size_t n_ent = nn_entries(c, run), out_bytes = n_ent * 8 + n_ent * 4;
+    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.pending = false;
+    c->last_nn_ms[0] = c->last_nn_ms[1] = 0.f;
+    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffer is rewritten)
+    if ((rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
+    if (N <= 1) return PC_OK;
+    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes))) return abi_rc(rc);
+    if (run.timed) for (hipEvent_t& e : c->ev_nn) if (!e) PC_HIP(hipEventCreate(&e));
+    return pc_launch_nn_init(c->b_nn_key.as<unsigned long long>(), pc_nn_nbr(c, run), (int64_t)n_ent, c->stream);
+}
+
+int pc_nearest_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
+    if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
+    if (c->dev.N <= 1 || ta == tb) return PC_OK;
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const bool stats = run.timed;
+    std::vector<int32_t> cut;
+    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
+    unsigned long long* const d_key = c->b_nn_key.as<unsigned long long>();
+    int32_t* const d_nbr = pc_nn_nbr(c, run);
+    // ---- a slab's hook: the row pass, then the column pass, left running (the walk has waited for the passes before them: their two
+    // events can be read).  The slab's targets are the consecutive range that starts at its first owned one.
+    rc = slab_walk(c, cut, run.metric, run.as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
+        int rc = PC_OK;
+        const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
+        if (stats && run.pending && (rc = nn_add_select_time(c))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_nn[0], st));
+        if ((rc = pc_launch_nn_select(slab, Lp, t0, t1, run.as_distance, run.kk, d_key, d_nbr, st))) return rc;
+        if (stats) PC_HIP(hipEventRecord(c->ev_nn[1], st));
+        run.pending = true;
+        return mark_work(c, st);
+    });
+    if (rc != PC_OK) return rc;
+    run.n_slabs += (int32_t)cut.size() - 1;
+    return PC_OK;
+}
+
+int pc_nearest_end(pc_ctx* c, PcSlabRun& run, const int32_t** nbr, const double** val) {
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const bool stats = run.timed;
+    const size_t n_ent = nn_entries(c, run), val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4;
+    const double* const h_val = c->h_nn.as<double>();
+    const int32_t* const h_nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes);
+    if (c->dev.N <= 1) { *nbr = h_nbr; *val = h_val; return PC_OK; }
+    if (stats) PC_HIP(hipEventRecord(c->ev_nn[2], st));
+    if ((rc = pc_launch_nn_finish(c->b_nn_key.as<unsigned long long>(), c->b_nn_out.as<double>(), (int64_t)n_ent, run.as_distance, st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_nn[3], st));
+    PC_HIP(hipMemcpyAsync(c->h_nn.p, c->b_nn_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if (stats) {
+        if (run.pending && (rc = nn_add_select_time(c))) return rc;         // (the last slab's passes)
+        PC_HIP(hipEventElapsedTime(&c->last_nn_ms[1], c->ev_nn[2], c->ev_nn[3]));
+    }
+    run.pending = false;
+    *nbr = h_nbr; *val = h_val;
+    return PC_OK;
+}
+
 extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, int64_t slab_bytes,
                                const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats) {
     if (nbr) *nbr = nullptr;
@@ -267,63 +401,14 @@ extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, in
     if (k_out) *k_out = 0;
     if (n_slabs) *n_slabs = 0;
     int rc = PC_OK;
-    if ((rc = fill_check(c, "pc_fill_nearest", "a nearest-neighbours fill", &metric, nullptr))) return rc;
-    if (k < 1) { pc_set_error("pc_fill_nearest: k %d", k); return PC_ERR_ARG; }
-    if (k > PC_NEAREST_MAX_K) { pc_set_error("pc_fill_nearest: k %d is above PC_NEAREST_MAX_K = %d", k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
-    if ((rc = slab_check(c, "pc_fill_nearest", nbr && val && k_out && n_slabs, metric, 0.0, slab_bytes))) return rc;
+    PcSlabRun run; run.who = "pc_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.kk = -1;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
+    if ((rc = pc_slab_check(c, run, "a nearest-neighbours fill", nbr && val && k_out && n_slabs))) return rc;
     PC_ON_DEVICE(c);
     PcRange range("pc:fill_nearest");
-    hipStream_t st = c->stream;
-    const int N = c->dev.N;
-    const int kk = std::max(std::min(k, N - 1), 0);
-    const size_t n_ent = (size_t)std::max(N, 0) * kk, val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4;
-    pc_stats sum; memset(&sum, 0, sizeof(sum));
-    c->last_nn_ms[0] = c->last_nn_ms[1] = 0.f;
-    as_distance = as_distance ? 1 : 0;
-    if ((rc = wait_last_work(c, st, false))) return rc;                     // (the loan of an earlier call ends here: its buffer is rewritten)
-    if ((rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
-    const double* const h_val = c->h_nn.as<double>();
-    const int32_t* const h_nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes);
-    if (N <= 1) {
-        *nbr = h_nbr; *val = h_val;
-        if (stats) *stats = sum;
-        return PC_OK;
-    }
-    std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, slab_bytes, cut))) return rc;
-    if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes))) return abi_rc(rc);
-    if (stats) for (hipEvent_t& e : c->ev_nn) if (!e) PC_HIP(hipEventCreate(&e));
-    unsigned long long* const d_key = c->b_nn_key.as<unsigned long long>();
-    double* const d_val = c->b_nn_out.as<double>();
-    int32_t* const d_nbr = (int32_t*)((char*)c->b_nn_out.p + val_bytes);
-    if ((rc = pc_launch_nn_init(d_key, d_nbr, (int64_t)n_ent, st))) return rc;
-    bool pending = false;                                                   // a slab's passes were launched and, with stats, their time not yet added
-    auto add_select_time = [&]() -> int { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_nn[0], c->ev_nn[1])); c->last_nn_ms[0] += x; return PC_OK; };
-    // ---- a slab's hook: the row pass, then the column pass, left running (the walk has waited for the passes before them: their two
-    // events can be read).  The slab's targets are the consecutive range that starts at its first owned one.
-    rc = slab_walk(c, cut, metric, as_distance, stats ? &sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
-        int rc = PC_OK;
-        const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
-        if (stats && pending && (rc = add_select_time())) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_nn[0], st));
-        if ((rc = pc_launch_nn_select(slab, Lp, t0, t1, as_distance, kk, d_key, d_nbr, st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_nn[1], st));
-        pending = true;
-        return mark_work(c, st);
-    });
-    if (rc != PC_OK) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_nn[2], st));
-    if ((rc = pc_launch_nn_finish(d_key, d_val, (int64_t)n_ent, as_distance, st))) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_nn[3], st));
-    PC_HIP(hipMemcpyAsync(c->h_nn.p, c->b_nn_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    c->busy = false;
-    if (stats) {
-        if (pending && (rc = add_select_time())) return rc;                 // (the last slab's passes)
-        PC_HIP(hipEventElapsedTime(&c->last_nn_ms[1], c->ev_nn[2], c->ev_nn[3]));
-    }
-    *nbr = h_nbr; *val = h_val; *k_out = kk; *n_slabs = (int32_t)cut.size() - 1;
-    if (stats) *stats = sum;
+    if ((rc = pc_nearest_begin(c, run)) || (rc = pc_nearest_walk(c, run, 0, c->dev.N)) || (rc = pc_nearest_end(c, run, nbr, val))) return rc;
+    if (c->dev.N > 1) { *k_out = run.kk; *n_slabs = run.n_slabs; }
+    if (stats) *stats = run.sum;
     return PC_OK;
 }
 

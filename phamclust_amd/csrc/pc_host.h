@@ -282,6 +282,46 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest) in three phases on one context (pc_fill_slabs.hip), so that
+// pc_multi_fill_* can run begin -> walk(its stretch of targets) on every device and merge before the root's end:
+//   check   the refusals of the public call, in its order (metric folded, flags normalised); nothing is touched
+//   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
+//           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
+//   walk    the chunking rule over count[t] = t for the targets [ta, tb), each range filled and handed to the call's hook; the
+//           state stays on the device, the edges go behind the n_edges already in the pinned arrays
+//   end     labels / finish and the D2H copy; the counts and pointers of the public call
+// The public calls are check -> begin -> walk [0, N) -> end.  For N <= 1 begin and walk do nothing on the device.
+struct PcSlabRun {
+    const char* who = "";
+    int metric = 0, as_distance = 0, strict = 0, k = 0;
+    double threshold = 0.0;
+    int64_t slab_bytes = 0;
+    bool timed = false;                     // the caller asked for stats: events around the hooks' passes
+    int kk = 0;                             // nearest: min(k, N - 1)
+    int64_t max_pairs = 0;                  // pairs one slab may hold
+    pc_stats sum{};                         // the walks' fills, summed
+    int32_t n_slabs = 0;                    // ranges the walks cut
+    int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (set by end)
+    bool pending = false;                   // components / nearest: a slab's passes were launched and, timed, their time not yet added
+};
+int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* kind, bool outputs);
+int pc_edges_begin(pc_ctx* c, PcSlabRun& run);
+int pc_edges_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
+int pc_components_begin(pc_ctx* c, PcSlabRun& run);
+int pc_components_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
+int pc_components_end(pc_ctx* c, PcSlabRun& run, int64_t foreign_pass, const int32_t** labels, int32_t* n_components, int64_t* n_edges);
+int pc_nearest_begin(pc_ctx* c, PcSlabRun& run);
+int pc_nearest_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
+int pc_nearest_end(pc_ctx* c, PcSlabRun& run, const int32_t** nbr, const double** val);
+// where the state of a components / nearest fill lives between begin and end (what a non-root device ships to the root)
+static inline size_t pc_cc_label_bytes(int N) { return ((size_t)std::max(N, 1) * 4 + 7) / 8 * 8; }   // the 64-bit count sits behind the labels, aligned
+static inline unsigned long long* pc_cc_pass_counter(const pc_ctx* c) { return (unsigned long long*)((char*)c->b_cc_labels.p + pc_cc_label_bytes(c->dev.N)); }
+static inline int32_t* pc_nn_nbr(const pc_ctx* c, const PcSlabRun& run) { return (int32_t*)((char*)c->b_nn_out.p + (size_t)std::max(c->dev.N, 0) * run.kk * 8); }
+
+// DP cells per target genome into c->target_cost, once per upload: one COUNT walk over all pairs (pc_upload.hip).  The context must
+// be unsharded (rank 0 of 1 in force) and idle; no deal is installed or left behind.
+int pc_count_target_costs(pc_ctx* c);
+
 // the whole fill of the shard in force into out (pc_fill.hip): what pc_fill_dev / pc_fill_shard_dev run, and every slab of a slab walk
 int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st, pc_stats* stats);
 // aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)

@@ -16,6 +16,10 @@
 //                of the sources, whose lists it keeps in registers across all the tiles, and reads a source's column of the tile
 //                lanes across targets (row stride 65: no bank conflict).
 //   k_nn_finish  val = the value behind each key
+//   k_nn_merge   several devices, each with the lists of its own stretch of targets (pc_multi_fill_nearest): the lists of the other
+//                devices, staged on the root as fkey / fnbr [n_foreign][N][K], go into the root's, one wave per genome.  A pair lies
+//                in exactly one stretch (its target's), so no real entry occurs twice; a foreign list may end in worst sentinels (its
+//                device need not have met K candidates of the genome), which are no candidates.
 // A genome's list lives one entry per lane of a wave (why K <= 64).  The K-th entry is "the bar": a ballot of `candidate beats the
 // bar` finds the few candidates that matter (after the warm-up about K ln(n / K) per genome); each of them is inserted at the
 // position popcount(ballot(entry comes before the candidate)), the lanes behind it taking their lower neighbour's entry.
@@ -154,6 +158,25 @@ __global__ __launch_bounds__(256) void k_nn_finish(const nn_key* __restrict__ ke
     if (i < n) val[i] = nn_value_of(key[i], flip);
 }
 
+// merge pass: wave w of workgroup b takes genome b * NN_WAVES + w, as k_nn_rows deals targets.  The list of g is written by this wave
+// alone; nothing is read beyond n_foreign * N * K entries.
+__global__ __launch_bounds__(NN_THREADS) void k_nn_merge(nn_key* __restrict__ key, int32_t* __restrict__ nbr, const nn_key* __restrict__ fkey,
+                                                         const int32_t* __restrict__ fnbr, int n_foreign, int N, int K) {
+    const int lane = threadIdx.x & 63;
+    const int g = (int)blockIdx.x * NN_WAVES + (int)(threadIdx.x >> 6);
+    if (g >= N) return;                                // (the whole wave)
+    const size_t at = (size_t)g * K + lane;
+    nn_key ek = NN_WORST_KEY; int ei = NN_WORST_IDX;
+    if (lane < K) { ek = key[at]; ei = nbr[at]; }
+    for (int f = 0; f < n_foreign; ++f) {
+        const size_t fat = ((size_t)f * N + g) * K + lane;
+        nn_key fk = NN_WORST_KEY; int fi = NN_WORST_IDX;
+        if (lane < K) { fk = fkey[fat]; fi = fnbr[fat]; }
+        nn_take(ek, ei, fk, fi, lane < K && fi != NN_WORST_IDX, K, lane);
+    }
+    if (lane < K) { key[at] = ek; nbr[at] = ei; }
+}
+
 static int nn_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
@@ -185,4 +208,12 @@ int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, i
     if (n <= 0) return PC_OK;
     hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key, val, n, as_distance ? 0ull : ~0ull);
     return nn_check("k_nn_finish");
+}
+
+// key / nbr: [N][K]; fkey / fnbr: [n_foreign][N][K], 1 <= K <= 64
+int pc_launch_nn_merge(unsigned long long* key, int32_t* nbr, const unsigned long long* fkey, const int32_t* fnbr, int n_foreign, int N, int K, hipStream_t st) {
+    if (n_foreign <= 0 || N <= 0) return PC_OK;
+    if (K < 1 || K > 64) { pc_set_error("pc_launch_nn_merge: K = %d", K); return PC_ERR_ARG; }
+    hipLaunchKernelGGL(k_nn_merge, dim3((unsigned)((N + NN_WAVES - 1) / NN_WAVES)), dim3(NN_THREADS), 0, st, key, nbr, fkey, fnbr, n_foreign, N, K);
+    return nn_check("k_nn_merge");
 }

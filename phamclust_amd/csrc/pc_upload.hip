@@ -1,5 +1,5 @@
 // pc_upload.hip -- the two upload stages of libphamclust_hip.so (part 1: the pham sets; part 2: residues, distinct sequences
-// and launch classes) and the shard deal (pc_set_shard*, pc_shard_table, pc_target_costs).
+// and launch classes) and the deals (pc_set_shard*, pc_shard_table, pc_target_costs; pc_stretch_plan: the stretches of pc_multi_fill_*).
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -578,6 +578,43 @@ extern "C" int pc_set_shard(pc_ctx* c, int rank, int world) {
     PC_HIP(hipStreamSynchronize(c->stream));
     return apply_shard(c, rank, world);
 }
+// The COUNT walk behind the cost-balanced deals (pc_set_shard_balanced here, the stretch deal of pc_multi_fill_*): DP cells per
+// target genome over all pairs, integer sums (identical on every device), kept in c->target_cost until the next upload.  The
+// unsharded shard must be in force; nothing but the count buffers is written.
+int pc_count_target_costs(pc_ctx* c) {
+    if (!c->target_cost.empty()) return PC_OK;
+    if (c->world != 1) { pc_set_error("pc_count_target_costs: context is sharded (%d/%d)", c->rank, c->world); return PC_ERR_STATE; }
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    if ((rc = c->b_cost.ensure((size_t)N * 8)) || (rc = c->b_totals.ensure(64))) return abi_rc(rc);
+    PC_HIP(hipMemsetAsync(c->b_cost.p, 0, (size_t)N * 8, c->stream));
+    PC_HIP(hipMemsetAsync(c->b_totals.p, 0, 64, c->stream));
+    PcWalkArgs a; memset(&a, 0, sizeof(a));
+    a.totals = c->b_totals.as<unsigned long long>(); a.cost_t = c->b_cost.as<unsigned long long>(); a.condensed = 1;
+    if (c->dev.G > 0 && (rc = pc_launch_walk(PCW_COUNT, c->dev, c->shard, a, c->stream))) return rc;
+    c->target_cost.resize(N);
+    PC_HIP(hipMemcpyAsync(c->target_cost.data(), c->b_cost.p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    return PC_OK;
+}
+
+// The stretch deal of pc_multi_fill_edges / _components / _nearest as host arithmetic: contiguous stretches of targets of about
+// equal summed cost (see the header).  P(t) * world >= r * P(n) in 128-bit products; P ascends, so one forward walk serves every r.
+extern "C" int pc_stretch_plan(const uint64_t* cost, int n, int world, int32_t* bounds) {
+    if (!cost || !bounds || n < 0 || world < 1) { pc_set_error("pc_stretch_plan: bad argument"); return PC_ERR_ARG; }
+    unsigned __int128 total = 0;
+    for (int t = 0; t < n; ++t) total += cost[t];
+    bounds[0] = 0;
+    unsigned __int128 below = 0;                       // P(t)
+    int t = 0;
+    for (int r = 1; r < world; ++r) {
+        while (t < n && below * (unsigned)world < total * (unsigned)r) below += cost[t++];
+        bounds[r] = t;
+    }
+    bounds[world] = n;
+    return PC_OK;
+}
+
 // Cost-balanced deal.  The boustrophedon deal balances pair counts; alignment work per target genome also follows its
 // gene count and how much it shares with the genomes before it.  One COUNT walk over all pairs gives the DP cells per
 // target (integer sums: identical on every rank), then targets go, heaviest first, to the rank with the least work
@@ -591,15 +628,7 @@ extern "C" int pc_set_shard_balanced(pc_ctx* c, int rank, int world) {
     const int N = c->dev.N;
     if (c->target_cost.empty()) {
         if ((rc = apply_shard(c, 0, 1))) return rc;                       // walk every pair
-        if ((rc = c->b_cost.ensure((size_t)N * 8)) || (rc = c->b_totals.ensure(64))) return abi_rc(rc);
-        PC_HIP(hipMemsetAsync(c->b_cost.p, 0, (size_t)N * 8, c->stream));
-        PC_HIP(hipMemsetAsync(c->b_totals.p, 0, 64, c->stream));
-        PcWalkArgs a; memset(&a, 0, sizeof(a));
-        a.totals = c->b_totals.as<unsigned long long>(); a.cost_t = c->b_cost.as<unsigned long long>(); a.condensed = 1;
-        if (c->dev.G > 0 && (rc = pc_launch_walk(PCW_COUNT, c->dev, c->shard, a, c->stream))) return rc;
-        c->target_cost.resize(N);
-        PC_HIP(hipMemcpyAsync(c->target_cost.data(), c->b_cost.p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-        PC_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = pc_count_target_costs(c))) return rc;
     }
     // every pair also costs a walk visit and an output value: a floor of 2,000 cell-equivalents per pair keeps the
     // set metrics and sparse data balanced too

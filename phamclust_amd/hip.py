@@ -74,7 +74,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_set_kernel_choice", "pc_set_launch_shape", "pc_set_max_block_entries", "pc_last_set_launch", "pc_multi_create", "pc_multi_destroy", "pc_multi_devices", "pc_multi_peer_access", "pc_multi_upload",
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times",
            "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles",
-           "pc_fill_nearest", "pc_last_nearest_times"]
+           "pc_fill_nearest", "pc_last_nearest_times", "pc_multi_fill_edges", "pc_multi_fill_components", "pc_multi_fill_nearest",
+           "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -174,6 +175,12 @@ def load():
     L.pc_multi_set_tie_rule.argtypes = [vp, ctypes.c_int]
     L.pc_multi_fill_borrow.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_f64p), ctypes.POINTER(PcStats),
                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_multi_fill_edges.argtypes = L.pc_fill_edges.argtypes
+    L.pc_multi_fill_components.argtypes = L.pc_fill_components.argtypes
+    L.pc_multi_fill_nearest.argtypes = L.pc_fill_nearest.argtypes
+    L.pc_multi_last_stretches.argtypes = [vp, _i32p]
+    L.pc_multi_last_slab_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_stretch_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_int, _i32p]
     L.pc_set_tie_rule.argtypes = [vp, ctypes.c_int]
     L.pc_get_tie_rule.argtypes = [vp]
     _lib = L
@@ -812,6 +819,10 @@ class MultiContext:
     def n_pairs(self):
         return self._packed.n_pairs
 
+    @property
+    def n_genomes(self):
+        return self._packed.n_genomes
+
     def close(self):
         self._invalidate_loans()
         if getattr(self, "_h", None) is not None and self._h:
@@ -865,3 +876,86 @@ class MultiContext:
         merged = dict(per[0], per_device=per, ms_exchange=float(x_ms.value), ms_assemble=float(a_ms.value), n_devices=self.n_devices,
                       ms_total=max(p["ms_total"] for p in per), peer_access=self.peer_access())
         return out, merged
+
+    # -- the fills that deliver no dense matrix, over all devices (pc_multi_fill_edges / _components / _nearest) ------------
+    @staticmethod
+    def slab_stretches(cost, world):
+        """The deal of those fills as host arithmetic (``pc_stretch_plan``; no GPU): ``bounds[world + 1]`` -- device r walks the
+        contiguous targets ``[bounds[r], bounds[r + 1])``, stretches of about equal summed ``cost`` (uint64 per target: ``t`` for
+        gcs / jc / pocp / af, ``target_costs()[t] + 2000 * t`` for aai / peq); a stretch may be empty."""
+        cost = np.ascontiguousarray(cost, dtype=np.uint64).reshape(-1)
+        bounds = np.zeros(int(world) + 1 if int(world) >= 1 else 1, dtype=np.int32)
+        lib = load()
+        if lib.pc_stretch_plan(_ptr(cost if cost.size else np.zeros(1, np.uint64), _u64p), int(cost.shape[0]), int(world), _ptr(bounds, _i32p)) != 0:
+            raise HipLibraryError(lib.pc_last_error().decode())
+        return bounds
+
+    def _before_slab_fill(self, metric):
+        """What the three calls share ahead of the library call: the residues on demand, earlier loans ended, a stats array."""
+        if self._packed is not None and metric in NEEDS_RESIDUES and not self._residues:     # (before an upload the library refuses the call itself)
+            s = self._struct(self._packed)
+            self._check(self._lib.pc_multi_upload_residues(self._h, ctypes.byref(s)))
+            self._residues = True
+        self._invalidate_loans()
+        return (PcStats * self.n_devices)()
+
+    def _slab_stats(self, stats, **own):
+        """The stats dict of such a fill: the counts summed over the devices, the times of the slowest, and what the route adds --
+        ``n_devices``, ``per_device``, ``stretches``, ``ms_exchange``, ``ms_merge``, ``peer_access``."""
+        per = [s.as_dict() for s in stats]
+        merged = {name: (max if name.startswith("ms_") else sum)(p[name] for p in per) for name in per[0]}
+        bounds = np.zeros(self.n_devices + 1, dtype=np.int32)
+        self._check(self._lib.pc_multi_last_stretches(self._h, _ptr(bounds, _i32p)))
+        x, y = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.pc_multi_last_slab_times(self._h, ctypes.byref(x), ctypes.byref(y)))
+        return dict(merged, **own, n_devices=self.n_devices, per_device=per, stretches=bounds.tolist(), ms_exchange=float(x.value),
+                    ms_merge=float(y.value), peer_access=self.peer_access())
+
+    def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """``Context.fill_edges`` over all devices: the same ``(src, tgt, val)`` arrays, element for element, whatever the number
+        of devices -- each walks one contiguous stretch of targets, and the lists are laid end to end in the root's page-locked
+        memory.  ``want_stats`` adds the summed stats with ``n_edges``, ``n_slabs`` and the route's own entries (``per_device``,
+        ``stretches``, ``ms_exchange``, ``ms_merge``, ``n_devices``, ``peer_access``)."""
+        stats = self._before_slab_fill(metric)
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_multi_fill_edges(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(slab_bytes),
+                                                  ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl), stats))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        return (*out, self._slab_stats(stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
+
+    def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
+        """``Context.fill_components`` over all devices: the same canonical ``labels`` -- every device builds the forest of its
+        stretch of targets, the root unites them (``k_cc_merge``) and labels.  ``want_stats`` adds the summed stats with
+        ``n_components``, ``n_edges`` (pairs that passed, over all devices), ``n_slabs`` and the route's own entries."""
+        stats = self._before_slab_fill(metric)
+        pl = _i32p()
+        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_multi_fill_components(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(bool(strict)),
+                                                       int(slab_bytes), ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl), stats))
+        n = self.n_genomes
+        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
+        if not want_stats:
+            return labels
+        return labels, self._slab_stats(stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+
+    def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """``Context.fill_nearest`` over all devices: the same ``(nbr, val)`` -- the k smallest of one total order, so the lists
+        the devices build over their stretches of targets merge by that order on the root (``k_nn_merge``).  ``want_stats`` adds
+        the summed stats with ``k`` (= kk), ``n_slabs`` and the route's own entries."""
+        stats = self._before_slab_fill(metric)
+        pn, pv = _i32p(), _f64p()
+        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_multi_fill_nearest(self._h, METRIC_IDS[metric], int(bool(as_distance)), int(k), int(slab_bytes),
+                                                    ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl), stats))
+        n = self.n_genomes
+        if n and kk.value and pn and pv:
+            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
+        else:
+            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
+        if not want_stats:
+            return nbr, val
+        return nbr, val, self._slab_stats(stats, k=int(kk.value), n_slabs=int(nsl.value))

@@ -761,12 +761,23 @@ class SparseEdges:
         return _square_matrix(self.nodes, data, self.is_distance)
 
 
+def _slab_fill_context():
+    """(context, devices used) of an edge-list, components or nearest-neighbours fill: the ``MultiContext`` over the devices
+    ``in_process_devices()`` names when there are several -- the three fills spread over them, a stretch of targets per device --
+    else the one-GPU context (of the one device named, or the default device)."""
+    devices = in_process_devices()
+    if devices and len(devices) > 1:
+        return get_multi_context(devices), len(devices)
+    return get_context(devices[0] if devices else None), 1
+
+
 def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
     """The edges of ``matrix_de_novo(genomes, func, cpus, as_distance)`` within ``threshold`` as a :class:`SparseEdges`, filled
     on the GPU by ``Context.fill_edges``: the dense matrix is never delivered, and beyond ``slab_bytes`` of HBM (0: automatic)
     never held.  ``func`` must be one of the six ``METRICS`` callables: there is no CPU route for this call (a generic callable
-    has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  One GPU: with ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` the first
-    listed device; under a launcher (``WORLD_SIZE`` > 1) it raises."""
+    has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  With ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` naming more than one
+    device the fill is spread over them from this process (``MultiContext.fill_edges``: a contiguous stretch of targets per device,
+    the same edges); under a launcher (``WORLD_SIZE`` > 1) it raises."""
     if len(genomes) == 0:
         raise ValueError("need at least 1 genome to construct edges de novo")
     metric = _metric_name(func)
@@ -776,21 +787,18 @@ def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("edges_de_novo: the edge-list fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
     import time
-    devices = in_process_devices()
-    if devices:
-        logging.debug(f"edges_de_novo: the edge-list fill is a one-GPU call: using device {devices[0]} of {devices}")
     t0 = time.perf_counter()
     packed = _packed_of(genomes)
     t1 = time.perf_counter()
-    ctx = get_context(devices[0] if devices else None)
+    ctx, n_gpus = _slab_fill_context()
     ctx.upload(packed, residues=metric in ("aai", "peq"))
     t2 = time.perf_counter()
     src, tgt, val, stats = ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
     t3 = time.perf_counter()
     LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=1, rank=0,
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=n_gpus, rank=0,
                      pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
-    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} of {packed.n_pairs} edges in {stats['n_slabs']} slab(s) on one device: "
+    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} of {packed.n_pairs} edges in {stats['n_slabs']} slab(s) on {n_gpus} device(s): "
                   f"pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+compact+D2H {t3 - t2:.3f} s (kernels {stats['ms_total']:.3f} ms)")
     return SparseEdges([g.name for g in genomes], src, tgt, val, is_distance=as_distance, threshold=threshold)
 
@@ -835,7 +843,8 @@ def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, 
     ``Context.fill_components``: neither the dense matrix nor an edge list leaves the GPU, only the N labels.  On distances with
     ``strict`` the groups are ``hierarchical_clustering(matrix, "single", eps=threshold)``'s.  ``func`` must be one of the six
     ``METRICS`` callables (no CPU route: ``SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)`` serves another
-    callable).  One GPU, as ``edges_de_novo``: under a launcher (``WORLD_SIZE`` > 1) it raises."""
+    callable).  Several devices as ``edges_de_novo`` (``MultiContext.fill_components``: the same labels); under a launcher
+    (``WORLD_SIZE`` > 1) it raises."""
     if len(genomes) == 0:
         raise ValueError("need at least 1 genome to construct components de novo")
     metric = _metric_name(func)
@@ -845,30 +854,29 @@ def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("components_de_novo: the components fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
     import time
-    devices = in_process_devices()
-    if devices:
-        logging.debug(f"components_de_novo: the components fill is a one-GPU call: using device {devices[0]} of {devices}")
     t0 = time.perf_counter()
     packed = _packed_of(genomes)
     t1 = time.perf_counter()
-    ctx = get_context(devices[0] if devices else None)
+    ctx, n_gpus = _slab_fill_context()
     ctx.upload(packed, residues=metric in ("aai", "peq"))
     t2 = time.perf_counter()
     labels, stats = ctx.fill_components(metric, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes, want_stats=True)
     t3 = time.perf_counter()
     LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=1, rank=0,
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=n_gpus, rank=0,
                      pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
     logging.debug(f"{len(genomes)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {packed.n_pairs} pairs in "
-                  f"{stats['n_slabs']} slab(s) on one device: pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+union+labels {t3 - t2:.3f} s "
+                  f"{stats['n_slabs']} slab(s) on {n_gpus} device(s): pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+union+labels {t3 - t2:.3f} s "
                   f"(kernels {stats['ms_total']:.3f} ms)")
     return Components([g.name for g in genomes], labels)
 
 
-def upload_for_fills(genomes, func, caller):
+def upload_for_fills(genomes, func, caller, several=False):
     """What the one-GPU routes without a dense matrix share ahead of their fills: the refusals (no genome, a callable outside the
     six ``METRICS``, a launcher), then ONE pack and ONE upload.  Returns ``(context, metric name, genome names, record)`` -- the
-    record holds ``pack_s``, ``upload_s`` and the collection's ``genome_pairs`` for ``LAST_FILL`` -- and the caller runs as many fills
+    record holds ``pack_s``, ``upload_s``, ``n_gpus`` and the collection's ``genome_pairs`` for ``LAST_FILL`` -- and the caller runs as
+    many fills as it needs.  ``several``: the caller's fill also runs over several devices (``neighbors_de_novo``), so the context is
+    ``_slab_fill_context()``'s; the groups and rows routes leave it off and stay on one GPU.  The caller runs as many fills
     on the context as it needs (``submatrices_de_novo``: a groups fill; ``hierarchical_clustering_de_novo``: a components fill, then
     a groups fill; ``phamclust --no-matrix``: two and three of them)."""
     if len(genomes) == 0:
@@ -881,16 +889,16 @@ def upload_for_fills(genomes, func, caller):
         raise RuntimeError(f"{caller}: the components and groups fills are one-GPU calls; run it in one process, not under a launcher (WORLD_SIZE > 1)")
     import time
     devices = in_process_devices()
-    if devices:
+    if devices and not (several and len(devices) > 1):
         logging.debug(f"{caller}: one-GPU calls: using device {devices[0]} of {devices}")
     t0 = time.perf_counter()
     packed = _packed_of(genomes)
     t1 = time.perf_counter()
-    ctx = get_context(devices[0] if devices else None)
+    ctx, n_gpus = _slab_fill_context() if several else (get_context(devices[0] if devices else None), 1)
     ctx.upload(packed, residues=metric in ("aai", "peq"))
     t2 = time.perf_counter()
     logging.debug(f"{caller}: {len(genomes)} genomes: pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s")
-    return ctx, metric, [g.name for g in genomes], dict(pack_s=t1 - t0, upload_s=t2 - t1, genome_pairs=packed.n_pairs)
+    return ctx, metric, [g.name for g in genomes], dict(pack_s=t1 - t0, upload_s=t2 - t1, genome_pairs=packed.n_pairs, n_gpus=n_gpus)
 
 
 def _group_indices(names, index, groups):
@@ -1038,21 +1046,22 @@ def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     """Each genome's ``k`` nearest neighbours in ``matrix_de_novo(genomes, func, cpus, as_distance)`` as a
     :class:`NearestNeighbors`, filled on the GPU by ``Context.fill_nearest``: the dense matrix is never delivered, and beyond
     ``slab_bytes`` of HBM (0: automatic) never held; N * k entries cross PCIe.  ``func`` must be one of the six ``METRICS``
-    callables (no CPU route: ``NearestNeighbors.from_dense(matrix_de_novo(...), k)`` serves another callable).  One GPU, as
-    ``edges_de_novo``: under a launcher (``WORLD_SIZE`` > 1) it raises.  Every refusal comes before the first GPU call."""
+    callables (no CPU route: ``NearestNeighbors.from_dense(matrix_de_novo(...), k)`` serves another callable).  Several devices as
+    ``edges_de_novo`` (``MultiContext.fill_nearest``: the same lists); under a launcher (``WORLD_SIZE`` > 1) it raises.  Every
+    refusal comes before the first GPU call."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NEAREST_MAX_K:
         raise ValueError(f"neighbors_de_novo: k must be an integer in 1..{NEAREST_MAX_K}, not {k!r}")
-    ctx, metric, names, record = upload_for_fills(genomes, func, "neighbors_de_novo")
+    ctx, metric, names, record = upload_for_fills(genomes, func, "neighbors_de_novo", several=True)
     import time
     t0 = time.perf_counter()
     nbr, val, stats = ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
     fill_s = time.perf_counter() - t0
     LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=record["genome_pairs"], n_gpus=1, rank=0,
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"], rank=0,
                      pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
     logging.debug(f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in {stats['n_slabs']} "
-                  f"slab(s) on one device: fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection "
-                  f"{stats['ms_select']:.3f} ms)")
+                  f"slab(s) on {record['n_gpus']} device(s): fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection "
+                  f"{stats.get('ms_select', 0.0):.3f} ms)")
     return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 

@@ -43,6 +43,17 @@ def _mark(name):
         TIMELINE.mark(name)
 
 
+def _gpus_text(st):
+    """How many GPUs an edge-list, components or nearest fill ran on, for its log line: "1 GPU", or "N GPUs" with every device's
+    stretch of targets and the times of the exchange and the merge."""
+    n = st.get("n_gpus", 1)
+    if n <= 1:
+        return "1 GPU"
+    bounds = st.get("stretches") or []
+    parts = ", ".join(f"{a}..{b}" for a, b in zip(bounds, bounds[1:]))
+    return f"{n} GPUs (targets {parts}; exchange {st.get('ms_exchange', 0.0):.3f} ms, merge {st.get('ms_merge', 0.0):.3f} ms)"
+
+
 # ---- input ---------------------------------------------------------------------------------
 def load_genomes_from_tsv(filepath):
     """Rows ``genome, pham[, translation]``; a missing translation is "M"; genomes in first-seen order."""
@@ -221,7 +232,7 @@ class _Run:
         st = _matrix.LAST_FILL
         pairs = st.get("genome_pairs", 0)
         log.info(f"{len(edges):,} of {pairs:,} pairs ({100.0 * len(edges) / max(pairs, 1):.1f} %) within distance {distance:.6f} from "
-                 f"{st.get('n_slabs', 1)} slab(s) on 1 GPU in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
+                 f"{st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
                  f"{st.get('upload_s', 0.0):.3f}, fill+compact+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, "
                  f"compaction {st.get('ms_compact', 0.0):.3f} ms, edge copy {st.get('ms_d2h', 0.0):.3f} ms)")
         if self.metric in _metrics.PARITY_NOTE:
@@ -243,7 +254,7 @@ class _Run:
         st = _matrix.LAST_FILL
         groups = found.group_indices()
         log.info(f"{len(self.genomes):,} genomes, {st.get('n_edges', 0):,} of {st.get('genome_pairs', 0):,} pairs within distance < {distance:.6f}: "
-                 f"{len(groups):,} components, the largest of {len(groups[0]) if groups else 0:,}, from {st.get('n_slabs', 1)} slab(s) on 1 GPU in "
+                 f"{len(groups):,} components, the largest of {len(groups[0]) if groups else 0:,}, from {st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in "
                  f"{time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, fill+union+labels "
                  f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, union {st.get('ms_union', 0.0):.3f} ms, labels "
                  f"{st.get('ms_labels', 0.0):.3f} ms)")
@@ -269,7 +280,7 @@ class _Run:
         found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True)
         st = _matrix.LAST_FILL
         log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {found.k} nearest of each of {len(found):,} genomes from {st.get('n_slabs', 1)} slab(s) "
-                 f"on 1 GPU in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, "
+                 f"on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, "
                  f"fill+select+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, selection "
                  f"{st.get('ms_select', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
         if self.metric in _metrics.PARITY_NOTE:
@@ -545,6 +556,37 @@ def _colors(text):
     return colors
 
 
+SLAB_FILL_FLAGS = (("adjacency_only", "--adjacency-only", "fills an edge list"), ("components_only", "--components-only", "fills component labels"),
+                   ("nearest", "--nearest", "fills nearest-neighbour lists"))
+
+
+def gpus_plan(args, route, packed):
+    """What ``--gpus N`` (N > 1, one process, no launcher around it) comes to: ``(n_gpus, how, note)`` with ``how`` "process" (this
+    process drives n_gpus devices: PHAMCLUST_GPUS), "launcher" (n_gpus ranks are started) or "one" (the matrix stage stays on one
+    GPU; ``note`` says why).  Host arithmetic on the parsed arguments and the packed genomes (None: no estimate) -- no GPU call.
+    --extend's rows fill is a one-GPU call.  --adjacency-only, --components-only and --nearest spread over the GPUs of this process
+    (pc_multi_fill_edges / _components / _nearest) under the same estimate as the dense fill; one process per GPU has no route for
+    them, so under PHAMCLUST_MULTI=launcher they stay on one GPU."""
+    if args.extend is not None:
+        # (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
+        return 1, "one", "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
+    if route == "launcher":
+        for attr, flag, what in SLAB_FILL_FLAGS:
+            if getattr(args, attr) not in (None, False):
+                return 1, "one", f"{flag} {what}, which is a one-GPU call: the matrix stage stays on one GPU"
+    n_gpus, note = args.gpus, None
+    if packed is not None:
+        n_gpus, note = startup.choose_gpus(args.gpus, packed, args.metric, route)
+    if n_gpus > 1 and route == "launcher":
+        return n_gpus, "launcher", note
+    if n_gpus > 1:
+        if args.device is not None:
+            note = (note or "") + (f"; --device {args.device} is IGNORED: {n_gpus} GPUs from one process are devices 0..{n_gpus - 1} "
+                                   f"(name others with PHAMCLUST_GPU_IDS)")
+        return n_gpus, "process", note
+    return 1, "one", note
+
+
 def main(argv=None):
     if argv is None and len(sys.argv) == 1:
         sys.argv.append("-h")
@@ -573,47 +615,28 @@ def main(argv=None):
 def _run(args, argv):
     rank, _, world = distributed.env_world()
     gpus_note = None
-    if args.gpus > 1 and world == 1 and args.adjacency_only:
-        # the edge-list fill is a one-GPU call too (pc_fill_edges refuses a sharded context)
-        gpus_note = "--adjacency-only fills an edge list, which is a one-GPU call: the matrix stage stays on one GPU"
-        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
-    elif args.gpus > 1 and world == 1 and args.components_only:
-        # and so is the components fill (pc_fill_components refuses a sharded context)
-        gpus_note = "--components-only fills component labels, which is a one-GPU call: the matrix stage stays on one GPU"
-        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
-    elif args.gpus > 1 and world == 1 and args.nearest is not None:
-        # and the nearest-neighbours fill (pc_fill_nearest refuses a sharded context)
-        gpus_note = "--nearest fills nearest-neighbour lists, which is a one-GPU call: the matrix stage stays on one GPU"
-        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
-    elif args.gpus > 1 and world == 1 and args.extend is not None:
-        # the rows fill of --extend is a one-GPU call (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
-        gpus_note = "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
-        os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
-    elif args.gpus > 1 and world == 1:
+    if args.gpus > 1 and world == 1:
         # `--gpus N`.  Two routes (startup.multi_gpu_route): by default THIS process drives the N GPUs (pc_multi_*: nothing to
         # launch); PHAMCLUST_MULTI=launcher re-runs the command as N ranks under torch.distributed.run, which costs seconds
         # before the first pair (an interpreter, a torch import and a process group per rank).  Either way the reference's rule
         # applies -- never more workers than work (matrix.py:460-462): load the genomes (host code only, no GPU call), estimate
-        # the fill, and spread it only when N GPUs can win their start-up back.
+        # the fill, and spread it only when N GPUs can win their start-up back (gpus_plan).
         route = startup.multi_gpu_route()
-        n_gpus = args.gpus
-        if not args.genome_dir:
+        packed = None
+        if not args.genome_dir and gpus_plan(args, route, None)[0] > 1:
             genomes = load_genomes(args.infile)
             TIMELINE.mark("load_genomes_for_estimate")
             packed = packed_behind(genomes)
             if packed is not None:
-                n_gpus, gpus_note = startup.choose_gpus(args.gpus, packed, args.metric, route)
                 _PRELOADED[str(args.infile)] = genomes
-        if n_gpus > 1 and route == "launcher":
+        n_gpus, how, gpus_note = gpus_plan(args, route, packed)
+        if how == "launcher":
             # as N ranks, one per GPU -- as a child process, before this process has made a single GPU call
             passed = list(sys.argv[1:] if argv is None else argv)
             sys.exit(distributed.launch_ranks(n_gpus, "phamclust_amd", [str(x) for x in passed],
                                               env={"PHAMCLUST_T0": repr(TIMELINE.t_launch), "PHAMCLUST_FORCE_GPUS": "1"}))
-        if n_gpus > 1:
-            os.environ["PHAMCLUST_GPUS"] = str(n_gpus)             # matrix_de_novo: devices 0..N-1 from this process (PHAMCLUST_GPU_IDS names others)
-            if args.device is not None:
-                gpus_note = (gpus_note or "") + (f"; --device {args.device} is IGNORED: {n_gpus} GPUs from one process are devices 0..{n_gpus - 1} "
-                                                 f"(name others with PHAMCLUST_GPU_IDS)")
+        if how == "process":
+            os.environ["PHAMCLUST_GPUS"] = str(n_gpus)             # matrix_de_novo and the edge / components / nearest fills: devices 0..N-1 from this process (PHAMCLUST_GPU_IDS names others)
         else:
             os.environ.pop("PHAMCLUST_GPUS", None); os.environ.pop("PHAMCLUST_GPU_IDS", None)
     if world == 1:
