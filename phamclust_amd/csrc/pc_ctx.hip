@@ -151,9 +151,7 @@ extern "C" void pc_ctx_destroy(pc_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < 5; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
-    for (int i = 0; i < 5; ++i) if (c->ev_edge[i]) (void)hipEventDestroy(c->ev_edge[i]);
-    for (int i = 0; i < 4; ++i) if (c->ev_cc[i]) (void)hipEventDestroy(c->ev_cc[i]);
-    for (int i = 0; i < 4; ++i) if (c->ev_nn[i]) (void)hipEventDestroy(c->ev_nn[i]);
+    for (hipEvent_t e : c->ev_slab) if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < pc_ctx::kAux; ++i) if (c->aux[i]) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); }
     for (int i = 0; i <= pc_ctx::kAux; ++i) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
     for (int i = 0; i < pc_ctx::kLong; ++i) {

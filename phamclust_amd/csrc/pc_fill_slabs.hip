@@ -1,13 +1,17 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
-// pc_last_nearest_times.  Each call is four phases on its context (check, begin, walk over a stretch of targets, end: PcSlabRun in
-// pc_host.h); the public calls walk [0, N), pc_multi_fill_* (pc_multi.hip) runs the same phases on a stretch per device.  Host only.
+// pc_last_nearest_times.  Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill: begin, slab, end, and what several
+// devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
+// multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
+// fills a PcSlabRun, calls the driver and copies the results out.  Host only.
 //
 // The walk they share goes over successive contiguous ranges of target genomes ("slabs": pc_chunk_plan over count[t] = t under
 // slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is installed as a PcShard (owned = t0 .. t1-1,
-// shard-local layout), filled by fill_impl into the context's slab buffer and handed to the caller's hook.  Slabs come in ascending target
-// order; one slab is resident at a time.
+// shard-local layout), filled by fill_impl into the context's slab buffer and handed to the description's slab().  Slabs come in
+// ascending target order; one slab is resident at a time.
+#include <chrono>
+
 #include "pc_host.h"
 
 #define PC_EDGE_MAX_PAIRS 0x7fffffffLL
@@ -25,17 +29,19 @@ struct SlabShardScope {
 
 static int64_t pairs_below(int64_t t) { return t * (t - 1) / 2; }           // pairs (s, t'), s < t' < t
 
-// The checks the calls make, in the public calls' order: fill_check's, pc_fill_nearest's k, then outputs (every output pointer is
-// there), the threshold (pc_fill_nearest has none and passes 0), slab_bytes, and the residues aai / peq need.  Nothing is touched.
-int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* kind, bool outputs) {
+// The checks the calls make, in the public calls' order: fill_check's, a nearest-neighbours fill's k (and with it kk: the one place
+// that settles it), then outputs (every output pointer is there), the threshold, slab_bytes, and the residues aai / peq need.  Nothing
+// but the run is touched.
+int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
     int rc = PC_OK;
     const char* who = run.who;
-    if ((rc = fill_check(c, who, kind, &run.metric, nullptr))) return rc;
-    if (run.k != 0 || run.kk < 0) {                                         // (a nearest-neighbours fill: kk < 0 marks it until begin sets it)
+    if ((rc = fill_check(c, who, what, &run.metric, nullptr))) return rc;
+    if (run.kind == PC_SLAB_NEAREST) {
         if (run.k < 1) { pc_set_error("%s: k %d", who, run.k); return PC_ERR_ARG; }
         if (run.k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, run.k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
+        run.kk = std::max(std::min(run.k, c->dev.N - 1), 0);
     }
-    if (!outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
+    if (!run.outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
     if (run.threshold != run.threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
     if (run.slab_bytes < 0) { pc_set_error("%s: slab_bytes %lld", who, (long long)run.slab_bytes); return PC_ERR_ARG; }
     if ((rc = fill_check_residues(c, who, run.metric))) return rc;
@@ -112,81 +118,180 @@ template <class Hook> static int slab_walk(pc_ctx* c, const std::vector<int32_t>
     return PC_OK;
 }
 
-// ---- edge-list fill: the pairs whose value passes a threshold, as (source, target, value) arrays sorted by target, then source --
-// what matrix_to_adjacency(skip_zero) writes and SymMatrix.nearest_neighbors answers from the dense matrix (matrix.py:536-551,
-// 265-296), without the dense matrix ever crossing PCIe.  Each filled slab is compacted (count -> scan -> one 4-byte read-back -> emit,
-// pc_edges.hip) and its edges appended to the pinned host result; slabs in ascending target order make the concatenation globally ordered.
-int pc_edges_begin(pc_ctx* c, PcSlabRun& run) {
-    int rc = PC_OK;
-    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.n_edges = 0;
-    c->last_edge_ms[0] = c->last_edge_ms[1] = 0.f;
-    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffers are rewritten)
-    if ((rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
-    if (c->dev.N <= 1) return PC_OK;
-    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
-    if (run.timed) for (hipEvent_t& e : c->ev_edge) if (!e) PC_HIP(hipEventCreate(&e));
-    return PC_OK;
-}
-
-int pc_edges_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
+// ---- the drivers ----
+// The walk of a fill over the targets [ta, tb): the cut, and every slab to the description's slab().
+template <class Fill> int pc_slab_stretch(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
     if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
     if (c->dev.N <= 1 || ta == tb) return PC_OK;
-    int rc = PC_OK;
-    hipStream_t st = c->stream;
-    const bool stats = run.timed;
-    const int as_distance = run.as_distance; const double threshold = run.threshold;
     std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
-    uint32_t* const h_total = c->h_plan.as<uint32_t>();
-    int64_t& E = run.n_edges;
-    // ---- a slab's hook, compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit
-    rc = slab_walk(c, cut, run.metric, as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
-        int rc = PC_OK;
-        const int64_t nch = pc_edge_chunks(Lp);
-        if ((rc = c->b_edge_cnt.ensure((size_t)(nch + 1) * 4)) || (rc = c->b_edge_off.ensure((size_t)(nch + 1) * 4)) ||
-            (rc = c->b_scan_tmp.ensure((size_t)pc_scan_tmp_elems(nch + 1) * 4))) return abi_rc(rc);
-        uint32_t* const cnt = c->b_edge_cnt.as<uint32_t>(); uint32_t* const off = c->b_edge_off.as<uint32_t>();
-        if (stats) PC_HIP(hipEventRecord(c->ev_edge[0], st));
-        PC_HIP(hipMemsetAsync(cnt + nch, 0, 4, st));
-        if ((rc = pc_launch_edge_count(slab, Lp, as_distance, threshold, cnt, st))) return rc;
-        if ((rc = pc_scan_exclusive_u32(cnt, off, nch + 1, c->b_scan_tmp.as<uint32_t>(), (int64_t)(c->b_scan_tmp.cap / 4), st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_edge[1], st));
-        PC_HIP(hipMemcpyAsync(h_total, off + nch, 4, hipMemcpyDeviceToHost, st));
-        PC_HIP(hipStreamSynchronize(st));
-        c->busy = false;
-        const int64_t Es = (int64_t)h_total[0];
-        if (Es == 0) {
-            if (stats) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_edge[0], c->ev_edge[1])); c->last_edge_ms[0] += x; }
-            return PC_OK;
-        }
-        if ((rc = c->b_edge_src.ensure((size_t)Es * 4)) || (rc = c->b_edge_tgt.ensure((size_t)Es * 4)) || (rc = c->b_edge_val.ensure((size_t)Es * 8))) return abi_rc(rc);
-        if ((rc = c->h_edge_src.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) || (rc = c->h_edge_tgt.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) ||
-            (rc = c->h_edge_val.grow_keep((size_t)(E + Es) * 8, (size_t)E * 8))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_edge[2], st));
-        if ((rc = pc_launch_edge_emit(slab, Lp, as_distance, threshold, shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
-                                      c->b_edge_val.as<double>(), st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_edge[3], st));
-        PC_HIP(hipMemcpyAsync(c->h_edge_src.as<int32_t>() + E, c->b_edge_src.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
-        PC_HIP(hipMemcpyAsync(c->h_edge_tgt.as<int32_t>() + E, c->b_edge_tgt.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
-        PC_HIP(hipMemcpyAsync(c->h_edge_val.as<double>() + E, c->b_edge_val.p, (size_t)Es * 8, hipMemcpyDeviceToHost, st));
-        if (stats) PC_HIP(hipEventRecord(c->ev_edge[4], st));
-        PC_HIP(hipStreamSynchronize(st));                                   // the slab, its tables and the edge buffers are rewritten by the next range
-        if (stats) {
-            float x = 0.f, y = 0.f, z = 0.f;
-            PC_HIP(hipEventElapsedTime(&x, c->ev_edge[0], c->ev_edge[1]));
-            PC_HIP(hipEventElapsedTime(&y, c->ev_edge[2], c->ev_edge[3]));
-            PC_HIP(hipEventElapsedTime(&z, c->ev_edge[3], c->ev_edge[4]));
-            c->last_edge_ms[0] += x + y; c->last_edge_ms[1] += z;
-        }
-        E += Es;
-        return PC_OK;
-    });
+    int rc = slab_cut(c, run.max_pairs, ta, tb, cut);
+    if (rc != PC_OK) return rc;
+    rc = slab_walk(c, cut, run.metric, run.as_distance, run.timed ? &run.sum : nullptr,
+                   [&](const double* slab, int64_t Lp, const PcShard& shard) -> int { return Fill::slab(c, run, slab, Lp, shard); });
     if (rc != PC_OK) return rc;
     run.n_slabs += (int32_t)cut.size() - 1;
     return PC_OK;
 }
+// A fill on one context.
+template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, Fill::what))) return rc;
+    PC_ON_DEVICE(c);
+    PcRange range(Fill::range);
+    if ((rc = Fill::begin(c, run)) || (rc = pc_slab_stretch<Fill>(c, run, 0, c->dev.N))) return rc;
+    return Fill::end(c, run);
+}
+template int pc_slab_fill<PcEdgesFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_fill<PcComponentsFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_fill<PcNearestFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_stretch<PcEdgesFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_stretch<PcComponentsFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_stretch<PcNearestFill>(pc_ctx*, PcSlabRun&, int, int);
 
-// (an edge-list fill has no end phase of its own: the edges are in the context's pinned arrays when a walk returns)
+// ---- what the descriptions share ----
+// begin, ahead of anything of the fill's own: the run and the fill's two times (last_ms) reset, the loan of an earlier call ended (its
+// buffers are rewritten) ...
+static int slab_begin(pc_ctx* c, PcSlabRun& run, float* last_ms) {
+    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.n_edges = 0; run.pending = false;
+    last_ms[0] = last_ms[1] = 0.f;
+    return wait_last_work(c, c->stream, false);
+}
+// ... and, N > 1, before the fill allocates anything on the device: the slab size, the events of a timed run
+static int slab_size(pc_ctx* c, PcSlabRun& run) {
+    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if (run.timed) for (hipEvent_t& e : c->ev_slab) if (!e) PC_HIP(hipEventCreate(&e));
+    return PC_OK;
+}
+// the pending pass's time (events 0 and 1) added to *slot
+static int slab_add_pass_time(pc_ctx* c, const PcSlabRun& run, float* slot) {
+    if (!run.timed || !run.pending) return PC_OK;
+    float x = 0.f;
+    PC_HIP(hipEventElapsedTime(&x, c->ev_slab[0], c->ev_slab[1]));
+    *slot += x;
+    return PC_OK;
+}
+// A slab's pass of a components / nearest fill, left running (the walk has waited for the pass before it: its two events can be read).
+template <class Launch> static int slab_pass(pc_ctx* c, PcSlabRun& run, float* last_ms, Launch launch) {
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    if ((rc = slab_add_pass_time(c, run, &last_ms[0]))) return rc;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[0], st));
+    if ((rc = launch(st))) return rc;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[1], st));
+    run.pending = true;
+    return mark_work(c, st);
+}
+// ... and after the last slab: the closing pass, ONE D2H of what it wrote, the stream drained; the last slab's pass and this one timed.
+template <class Launch> static int slab_finish(pc_ctx* c, PcSlabRun& run, float* last_ms, void* host, const void* dev, size_t bytes, Launch launch) {
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[2], st));
+    if ((rc = launch(st))) return rc;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[3], st));
+    PC_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if ((rc = slab_add_pass_time(c, run, &last_ms[0]))) return rc;
+    if (run.timed) PC_HIP(hipEventElapsedTime(&last_ms[1], c->ev_slab[2], c->ev_slab[3]));
+    run.pending = false;
+    return PC_OK;
+}
+static int last_times(const pc_ctx* c, const char* who, const float* last_ms, float* a, float* b) {
+    if (!c) { pc_set_error("%s: NULL context", who); return PC_ERR_ARG; }
+    if (a) *a = last_ms[0];
+    if (b) *b = last_ms[1];
+    return PC_OK;
+}
+
+// ---- edge-list fill: the pairs whose value passes a threshold, as (source, target, value) arrays sorted by target, then source --
+// what matrix_to_adjacency(skip_zero) writes and SymMatrix.nearest_neighbors answers from the dense matrix (matrix.py:536-551,
+// 265-296), without the dense matrix ever crossing PCIe.  Each filled slab is compacted (count -> scan -> one 4-byte read-back -> emit,
+// pc_edges.hip) and its edges appended to the pinned host result; slabs in ascending target order make the concatenation globally ordered.
+int PcEdgesFill::begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    if ((rc = slab_begin(c, run, c->last_edge_ms)) || (rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
+    return c->dev.N <= 1 ? (int)PC_OK : slab_size(c, run);
+}
+// compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit
+int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const bool stats = run.timed;
+    const int as_distance = run.as_distance; const double threshold = run.threshold;
+    uint32_t* const h_total = c->h_plan.as<uint32_t>();
+    int64_t& E = run.n_edges;
+    const int64_t nch = pc_edge_chunks(Lp);
+    if ((rc = c->b_edge_cnt.ensure((size_t)(nch + 1) * 4)) || (rc = c->b_edge_off.ensure((size_t)(nch + 1) * 4)) ||
+        (rc = c->b_scan_tmp.ensure((size_t)pc_scan_tmp_elems(nch + 1) * 4))) return abi_rc(rc);
+    uint32_t* const cnt = c->b_edge_cnt.as<uint32_t>(); uint32_t* const off = c->b_edge_off.as<uint32_t>();
+    if (stats) PC_HIP(hipEventRecord(c->ev_slab[0], st));
+    PC_HIP(hipMemsetAsync(cnt + nch, 0, 4, st));
+    if ((rc = pc_launch_edge_count(slab, Lp, as_distance, threshold, cnt, st))) return rc;
+    if ((rc = pc_scan_exclusive_u32(cnt, off, nch + 1, c->b_scan_tmp.as<uint32_t>(), (int64_t)(c->b_scan_tmp.cap / 4), st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_slab[1], st));
+    PC_HIP(hipMemcpyAsync(h_total, off + nch, 4, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    const int64_t Es = (int64_t)h_total[0];
+    if (Es == 0) {
+        if (stats) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_slab[0], c->ev_slab[1])); c->last_edge_ms[0] += x; }
+        return PC_OK;
+    }
+    if ((rc = c->b_edge_src.ensure((size_t)Es * 4)) || (rc = c->b_edge_tgt.ensure((size_t)Es * 4)) || (rc = c->b_edge_val.ensure((size_t)Es * 8))) return abi_rc(rc);
+    if ((rc = c->h_edge_src.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) || (rc = c->h_edge_tgt.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) ||
+        (rc = c->h_edge_val.grow_keep((size_t)(E + Es) * 8, (size_t)E * 8))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_slab[2], st));
+    if ((rc = pc_launch_edge_emit(slab, Lp, as_distance, threshold, shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+                                  c->b_edge_val.as<double>(), st))) return rc;
+    if (stats) PC_HIP(hipEventRecord(c->ev_slab[3], st));
+    PC_HIP(hipMemcpyAsync(c->h_edge_src.as<int32_t>() + E, c->b_edge_src.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipMemcpyAsync(c->h_edge_tgt.as<int32_t>() + E, c->b_edge_tgt.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipMemcpyAsync(c->h_edge_val.as<double>() + E, c->b_edge_val.p, (size_t)Es * 8, hipMemcpyDeviceToHost, st));
+    if (stats) PC_HIP(hipEventRecord(c->ev_slab[4], st));
+    PC_HIP(hipStreamSynchronize(st));                                       // the slab, its tables and the edge buffers are rewritten by the next range
+    if (stats) {
+        float x = 0.f, y = 0.f, z = 0.f;
+        PC_HIP(hipEventElapsedTime(&x, c->ev_slab[0], c->ev_slab[1]));
+        PC_HIP(hipEventElapsedTime(&y, c->ev_slab[2], c->ev_slab[3]));
+        PC_HIP(hipEventElapsedTime(&z, c->ev_slab[3], c->ev_slab[4]));
+        c->last_edge_ms[0] += x + y; c->last_edge_ms[1] += z;
+    }
+    E += Es;
+    return PC_OK;
+}
+// (no end phase of its own: the edges are in the context's pinned arrays when a walk returns)
+int PcEdgesFill::end(pc_ctx* c, PcSlabRun& run) {
+    run.src = c->h_edge_src.as<int32_t>(); run.tgt = c->h_edge_tgt.as<int32_t>(); run.val = c->h_edge_val.as<double>();
+    return PC_OK;
+}
+// Several devices: nothing travels between them.  The root's pinned arrays are grown to the total and every device's edges laid behind
+// those of the ranks before it (ascending stretches: the concatenation is globally ordered); the copy's host time is the exchange.
+size_t PcEdgesFill::ship_bytes(const pc_ctx*, const PcSlabRun&) { return 0; }
+int PcEdgesFill::ship(pc_ctx*, pc_ctx*, PcSlabRun&, void*, int, int) { return PC_OK; }
+int PcEdgesFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void*, int, float* ms_exchange) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    int64_t total = 0;
+    for (const PcSlabRun& run : runs) total += run.n_edges;
+    const int64_t own = runs[0].n_edges;
+    if (total == own) return PC_OK;
+    if ((rc = root->h_edge_src.grow_keep((size_t)total * 4, (size_t)own * 4)) || (rc = root->h_edge_tgt.grow_keep((size_t)total * 4, (size_t)own * 4)) ||
+        (rc = root->h_edge_val.grow_keep((size_t)total * 8, (size_t)own * 8))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int64_t at = own;
+    for (size_t r = 1; r < ctx.size(); ++r) {
+        const int64_t E = runs[r].n_edges;
+        if (E == 0) continue;
+        memcpy(root->h_edge_src.as<int32_t>() + at, ctx[r]->h_edge_src.p, (size_t)E * 4);
+        memcpy(root->h_edge_tgt.as<int32_t>() + at, ctx[r]->h_edge_tgt.p, (size_t)E * 4);
+        memcpy(root->h_edge_val.as<double>() + at, ctx[r]->h_edge_val.p, (size_t)E * 8);
+        at += E;
+    }
+    *ms_exchange = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    runs[0].n_edges = total;
+    return PC_OK;
+}
+
 extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
                              const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     if (src) *src = nullptr;
@@ -194,24 +299,17 @@ extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double thre
     if (val) *val = nullptr;
     if (n_edges) *n_edges = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun run; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
-    if ((rc = pc_slab_check(c, run, "an edge-list fill", src && tgt && val && n_edges && n_slabs))) return rc;
-    PC_ON_DEVICE(c);
-    PcRange range("pc:fill_edges");
-    if ((rc = pc_edges_begin(c, run)) || (rc = pc_edges_walk(c, run, 0, c->dev.N))) return rc;
-    *src = c->h_edge_src.as<int32_t>(); *tgt = c->h_edge_tgt.as<int32_t>(); *val = c->h_edge_val.as<double>();
-    *n_edges = run.n_edges; *n_slabs = run.n_slabs;
+    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    const int rc = pc_slab_fill<PcEdgesFill>(c, run);
+    if (rc != PC_OK) return rc;
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
     if (stats) *stats = run.sum;
     return PC_OK;
 }
 
 extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_d2h) {
-    if (!c) { pc_set_error("pc_last_edge_times: NULL context"); return PC_ERR_ARG; }
-    if (ms_compact) *ms_compact = c->last_edge_ms[0];
-    if (ms_d2h) *ms_d2h = c->last_edge_ms[1];
-    return PC_OK;
+    return last_times(c, "pc_last_edge_times", c ? c->last_edge_ms : nullptr, ms_compact, ms_d2h);
 }
 
 // ---- components fill: the connected components of the graph {pairs that pass the threshold} -- with a strict distance predicate the
@@ -219,78 +317,64 @@ extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_
 // goes through ONE pass, k_cc_union (pc_components.hip), over a parent[N] array that stays on the device from the first slab to the
 // last; nothing is read back per slab.  After the last slab: k_cc_labels, then one D2H of labels[N] and the 8-byte count of passing
 // pairs behind them.
-static int cc_add_union_time(pc_ctx* c) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_cc[0], c->ev_cc[1])); c->last_cc_ms[0] += x; return PC_OK; }
+static size_t cc_label_bytes(int N) { return ((size_t)std::max(N, 1) * 4 + 7) / 8 * 8; }   // the 64-bit count sits behind the labels, aligned
+static unsigned long long* cc_pass_counter(const pc_ctx* c) { return (unsigned long long*)((char*)c->b_cc_labels.p + cc_label_bytes(c->dev.N)); }
 
-int pc_components_begin(pc_ctx* c, PcSlabRun& run) {
+int PcComponentsFill::begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
     const int N = c->dev.N;
-    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.n_edges = 0; run.pending = false;
-    c->last_cc_ms[0] = c->last_cc_ms[1] = 0.f;
-    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffer is rewritten)
-    const size_t label_bytes = pc_cc_label_bytes(N);
-    if ((rc = c->h_cc_labels.ensure(label_bytes + 8))) return rc;
+    const size_t label_bytes = cc_label_bytes(N);
+    if ((rc = slab_begin(c, run, c->last_cc_ms)) || (rc = c->h_cc_labels.ensure(label_bytes + 8))) return rc;
     if (N <= 1) return PC_OK;
-    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if ((rc = slab_size(c, run))) return rc;
     if ((rc = c->b_cc_parent.ensure((size_t)N * 4)) || (rc = c->b_cc_labels.ensure(label_bytes + 8))) return abi_rc(rc);
-    if (run.timed) for (hipEvent_t& e : c->ev_cc) if (!e) PC_HIP(hipEventCreate(&e));
-    return pc_launch_cc_init(c->b_cc_parent.as<int32_t>(), N, pc_cc_pass_counter(c), c->stream);
+    return pc_launch_cc_init(c->b_cc_parent.as<int32_t>(), N, cc_pass_counter(c), c->stream);
 }
-
-int pc_components_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
-    if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
-    if (c->dev.N <= 1 || ta == tb) return PC_OK;
-    int rc = PC_OK;
-    hipStream_t st = c->stream;
-    const bool stats = run.timed;
-    std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
-    int32_t* const parent = c->b_cc_parent.as<int32_t>();
-    unsigned long long* const d_pass = pc_cc_pass_counter(c);
-    // ---- a slab's hook: the union pass, left running (the walk has waited for the pass before it: its two events can be read)
-    rc = slab_walk(c, cut, run.metric, run.as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
-        int rc = PC_OK;
-        if (stats && run.pending && (rc = cc_add_union_time(c))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_cc[0], st));
-        if ((rc = pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, shard, parent, d_pass, st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_cc[1], st));
-        run.pending = true;
-        return mark_work(c, st);
+int PcComponentsFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+    return slab_pass(c, run, c->last_cc_ms, [&](hipStream_t st) {
+        return pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, shard, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
     });
-    if (rc != PC_OK) return rc;
-    run.n_slabs += (int32_t)cut.size() - 1;
-    return PC_OK;
 }
-
-// foreign_pass: pairs that passed on other devices (pc_multi_fill_components; a pair lies in exactly one stretch)
-int pc_components_end(pc_ctx* c, PcSlabRun& run, int64_t foreign_pass, const int32_t** labels, int32_t* n_components, int64_t* n_edges) {
+// (run.n_edges comes in as the pairs that passed on other devices: a pair lies in exactly one stretch)
+int PcComponentsFill::end(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
-    hipStream_t st = c->stream;
     const int N = c->dev.N;
-    const bool stats = run.timed;
-    const size_t label_bytes = pc_cc_label_bytes(N);
+    const size_t label_bytes = cc_label_bytes(N);
     int32_t* const h_labels = c->h_cc_labels.as<int32_t>();
+    run.labels = h_labels;
     if (N <= 1) {
-        if (N == 1) { h_labels[0] = 0; *n_components = 1; }
-        *labels = h_labels;
+        if (N == 1) { h_labels[0] = 0; run.n_components = 1; }
         return PC_OK;
     }
-    if (stats) PC_HIP(hipEventRecord(c->ev_cc[2], st));
-    if ((rc = pc_launch_cc_labels(c->b_cc_parent.as<int32_t>(), c->b_cc_labels.as<int32_t>(), N, st))) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_cc[3], st));
-    PC_HIP(hipMemcpyAsync(h_labels, c->b_cc_labels.p, label_bytes + 8, hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    c->busy = false;
-    if (stats) {
-        if (run.pending && (rc = cc_add_union_time(c))) return rc;          // (the last slab's pass)
-        PC_HIP(hipEventElapsedTime(&c->last_cc_ms[1], c->ev_cc[2], c->ev_cc[3]));
-    }
-    run.pending = false;
+    if ((rc = slab_finish(c, run, c->last_cc_ms, h_labels, c->b_cc_labels.p, label_bytes + 8, [&](hipStream_t st) {
+            return pc_launch_cc_labels(c->b_cc_parent.as<int32_t>(), c->b_cc_labels.as<int32_t>(), N, st);
+        }))) return rc;
     int32_t comps = 0;
     for (int g = 0; g < N; ++g) comps += h_labels[g] == g;
     unsigned long long passed = 0;
     memcpy(&passed, (const char*)h_labels + label_bytes, 8);
-    run.n_edges = (int64_t)passed + foreign_pass;
-    *labels = h_labels; *n_components = comps; *n_edges = run.n_edges;
+    run.n_components = comps; run.n_edges += (int64_t)passed;
+    return PC_OK;
+}
+// Several devices: a device ships its forest, parent[N], and copies its 8-byte count of passing pairs to the host (into its run); the
+// root unites the forests with its own in one launch (k_cc_merge) and takes the counts in.
+size_t PcComponentsFill::ship_bytes(const pc_ctx* root, const PcSlabRun&) { return (size_t)root->dev.N * 4; }
+int PcComponentsFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int) {
+    int rc = PC_OK;
+    const size_t N = (size_t)c->dev.N;
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, (int32_t*)stage + (size_t)slot * N, c->b_cc_parent.p, N * 4))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
+    PC_HIP(hipMemcpyAsync(&run.n_edges, cc_pass_counter(c), 8, hipMemcpyDeviceToHost, c->stream));
+    return PC_OK;
+}
+int PcComponentsFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    for (size_t r = 1; r < runs.size(); ++r) runs[0].n_edges += runs[r].n_edges;
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if ((rc = pc_launch_cc_merge(root->b_cc_parent.as<int32_t>(), (const int32_t*)stage, n_foreign, root->dev.N, root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
     return PC_OK;
 }
 
@@ -300,24 +384,17 @@ extern "C" int pc_fill_components(pc_ctx* c, int metric, int as_distance, double
     if (n_components) *n_components = 0;
     if (n_edges) *n_edges = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun run; run.who = "pc_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
-    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
-    if ((rc = pc_slab_check(c, run, "a components fill", labels && n_components && n_edges && n_slabs))) return rc;
-    PC_ON_DEVICE(c);
-    PcRange range("pc:fill_components");
-    if ((rc = pc_components_begin(c, run)) || (rc = pc_components_walk(c, run, 0, c->dev.N)) ||
-        (rc = pc_components_end(c, run, 0, labels, n_components, n_edges))) return rc;
-    *n_slabs = run.n_slabs;
+    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
+    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
+    const int rc = pc_slab_fill<PcComponentsFill>(c, run);
+    if (rc != PC_OK) return rc;
+    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
     if (stats) *stats = run.sum;
     return PC_OK;
 }
 
 extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* ms_labels) {
-    if (!c) { pc_set_error("pc_last_component_times: NULL context"); return PC_ERR_ARG; }
-    if (ms_union) *ms_union = c->last_cc_ms[0];
-    if (ms_labels) *ms_labels = c->last_cc_ms[1];
-    return PC_OK;
+    return last_times(c, "pc_last_component_times", c ? c->last_cc_ms : nullptr, ms_union, ms_labels);
 }
 
 // ---- nearest-neighbours fill: each genome's k best neighbours in the total order (value, better first; then index) -- what
@@ -325,72 +402,56 @@ extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* 
 // Each filled slab goes through two passes (pc_nearest.hip: k_nn_rows, k_nn_cols) over key[N][kk] / nbr[N][kk], which stay on the
 // device from the first slab to the last; nothing is read back per slab.  After the last slab: k_nn_finish, then one D2H of
 // val[N][kk] with nbr[N][kk] behind it.
-static int nn_add_select_time(pc_ctx* c) { float x = 0.f; PC_HIP(hipEventElapsedTime(&x, c->ev_nn[0], c->ev_nn[1])); c->last_nn_ms[0] += x; return PC_OK; }
 static size_t nn_entries(const pc_ctx* c, const PcSlabRun& run) { return (size_t)std::max(c->dev.N, 0) * run.kk; }
+static int32_t* nn_nbr(const pc_ctx* c, const PcSlabRun& run) { return (int32_t*)((char*)c->b_nn_out.p + nn_entries(c, run) * 8); }
 
-int pc_nearest_begin(pc_ctx* c, PcSlabRun& run) {
+int PcNearestFill::begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
-    const int N = c->dev.N;
-    run.kk = std::max(std::min(run.k, N - 1), 0);
     const size_t n_ent = nn_entries(c, run), out_bytes = n_ent * 8 + n_ent * 4;
-    memset(&run.sum, 0, sizeof(run.sum)); run.n_slabs = 0; run.pending = false;
-    c->last_nn_ms[0] = c->last_nn_ms[1] = 0.f;
-    if ((rc = wait_last_work(c, c->stream, false))) return rc;              // (the loan of an earlier call ends here: its buffer is rewritten)
-    if ((rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
-    if (N <= 1) return PC_OK;
-    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    if ((rc = slab_begin(c, run, c->last_nn_ms)) || (rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
+    if (c->dev.N <= 1) return PC_OK;
+    if ((rc = slab_size(c, run))) return rc;
     if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes))) return abi_rc(rc);
-    if (run.timed) for (hipEvent_t& e : c->ev_nn) if (!e) PC_HIP(hipEventCreate(&e));
-    return pc_launch_nn_init(c->b_nn_key.as<unsigned long long>(), pc_nn_nbr(c, run), (int64_t)n_ent, c->stream);
+    return pc_launch_nn_init(c->b_nn_key.as<unsigned long long>(), nn_nbr(c, run), (int64_t)n_ent, c->stream);
 }
-
-int pc_nearest_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb) {
-    if (!stretch_ok(c, run, ta, tb)) return PC_ERR_ARG;
-    if (c->dev.N <= 1 || ta == tb) return PC_OK;
-    int rc = PC_OK;
-    hipStream_t st = c->stream;
-    const bool stats = run.timed;
-    std::vector<int32_t> cut;
-    if ((rc = slab_cut(c, run.max_pairs, ta, tb, cut))) return rc;
-    unsigned long long* const d_key = c->b_nn_key.as<unsigned long long>();
-    int32_t* const d_nbr = pc_nn_nbr(c, run);
-    // ---- a slab's hook: the row pass, then the column pass, left running (the walk has waited for the passes before them: their two
-    // events can be read).  The slab's targets are the consecutive range that starts at its first owned one.
-    rc = slab_walk(c, cut, run.metric, run.as_distance, stats ? &run.sum : nullptr, [&](const double* slab, int64_t Lp, const PcShard& shard) -> int {
-        int rc = PC_OK;
-        const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
-        if (stats && run.pending && (rc = nn_add_select_time(c))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_nn[0], st));
-        if ((rc = pc_launch_nn_select(slab, Lp, t0, t1, run.as_distance, run.kk, d_key, d_nbr, st))) return rc;
-        if (stats) PC_HIP(hipEventRecord(c->ev_nn[1], st));
-        run.pending = true;
-        return mark_work(c, st);
+// the row pass, then the column pass; the slab's targets are the consecutive range that starts at its first owned one
+int PcNearestFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+    const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
+    return slab_pass(c, run, c->last_nn_ms, [&](hipStream_t st) {
+        return pc_launch_nn_select(slab, Lp, t0, t1, run.as_distance, run.kk, c->b_nn_key.as<unsigned long long>(), nn_nbr(c, run), st);
     });
-    if (rc != PC_OK) return rc;
-    run.n_slabs += (int32_t)cut.size() - 1;
+}
+int PcNearestFill::end(pc_ctx* c, PcSlabRun& run) {
+    const size_t n_ent = nn_entries(c, run), val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4;
+    run.val = c->h_nn.as<double>(); run.nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes);
+    if (c->dev.N <= 1) return PC_OK;
+    return slab_finish(c, run, c->last_nn_ms, c->h_nn.p, c->b_nn_out.p, out_bytes, [&](hipStream_t st) {
+        return pc_launch_nn_finish(c->b_nn_key.as<unsigned long long>(), c->b_nn_out.as<double>(), (int64_t)n_ent, run.as_distance, st);
+    });
+}
+// Several devices: a device ships its lists in key space -- the staging buffer holds [n_foreign][N][kk] keys, then as many indices --
+// and the root merges them into its own by the one total order (k_nn_merge).
+size_t PcNearestFill::ship_bytes(const pc_ctx* root, const PcSlabRun& run) { return nn_entries(root, run) * 12; }
+int PcNearestFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int n_foreign) {
+    int rc = PC_OK;
+    const size_t n_ent = nn_entries(c, run);
+    unsigned long long* const stage_key = (unsigned long long*)stage;
+    int32_t* const stage_nbr = (int32_t*)(stage_key + (size_t)n_foreign * n_ent);
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, stage_key + (size_t)slot * n_ent, c->b_nn_key.p, n_ent * 8)) ||
+        (rc = pc_ship(c, root, stage_nbr + (size_t)slot * n_ent, nn_nbr(c, run), n_ent * 4))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
     return PC_OK;
 }
-
-int pc_nearest_end(pc_ctx* c, PcSlabRun& run, const int32_t** nbr, const double** val) {
+int PcNearestFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
     int rc = PC_OK;
-    hipStream_t st = c->stream;
-    const bool stats = run.timed;
-    const size_t n_ent = nn_entries(c, run), val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4;
-    const double* const h_val = c->h_nn.as<double>();
-    const int32_t* const h_nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes);
-    if (c->dev.N <= 1) { *nbr = h_nbr; *val = h_val; return PC_OK; }
-    if (stats) PC_HIP(hipEventRecord(c->ev_nn[2], st));
-    if ((rc = pc_launch_nn_finish(c->b_nn_key.as<unsigned long long>(), c->b_nn_out.as<double>(), (int64_t)n_ent, run.as_distance, st))) return rc;
-    if (stats) PC_HIP(hipEventRecord(c->ev_nn[3], st));
-    PC_HIP(hipMemcpyAsync(c->h_nn.p, c->b_nn_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    c->busy = false;
-    if (stats) {
-        if (run.pending && (rc = nn_add_select_time(c))) return rc;         // (the last slab's passes)
-        PC_HIP(hipEventElapsedTime(&c->last_nn_ms[1], c->ev_nn[2], c->ev_nn[3]));
-    }
-    run.pending = false;
-    *nbr = h_nbr; *val = h_val;
+    pc_ctx* root = ctx[0];
+    const unsigned long long* const stage_key = (const unsigned long long*)stage;
+    const int32_t* const stage_nbr = (const int32_t*)(stage_key + (size_t)n_foreign * nn_entries(root, runs[0]));
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if ((rc = pc_launch_nn_merge(root->b_nn_key.as<unsigned long long>(), nn_nbr(root, runs[0]), stage_key, stage_nbr, n_foreign, root->dev.N, runs[0].kk,
+                                 root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
     return PC_OK;
 }
 
@@ -400,21 +461,15 @@ extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, in
     if (val) *val = nullptr;
     if (k_out) *k_out = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun run; run.who = "pc_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.kk = -1;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr;
-    if ((rc = pc_slab_check(c, run, "a nearest-neighbours fill", nbr && val && k_out && n_slabs))) return rc;
-    PC_ON_DEVICE(c);
-    PcRange range("pc:fill_nearest");
-    if ((rc = pc_nearest_begin(c, run)) || (rc = pc_nearest_walk(c, run, 0, c->dev.N)) || (rc = pc_nearest_end(c, run, nbr, val))) return rc;
-    if (c->dev.N > 1) { *k_out = run.kk; *n_slabs = run.n_slabs; }
+    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
+    const int rc = pc_slab_fill<PcNearestFill>(c, run);
+    if (rc != PC_OK) return rc;
+    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
     if (stats) *stats = run.sum;
     return PC_OK;
 }
 
 extern "C" int pc_last_nearest_times(const pc_ctx* c, float* ms_select, float* ms_finish) {
-    if (!c) { pc_set_error("pc_last_nearest_times: NULL context"); return PC_ERR_ARG; }
-    if (ms_select) *ms_select = c->last_nn_ms[0];
-    if (ms_finish) *ms_finish = c->last_nn_ms[1];
-    return PC_OK;
+    return last_times(c, "pc_last_nearest_times", c ? c->last_nn_ms : nullptr, ms_select, ms_finish);
 }

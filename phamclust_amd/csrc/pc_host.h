@@ -117,17 +117,15 @@ struct pc_ctx {
     // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
     DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
     PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
-    hipEvent_t ev_edge[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_edges that is asked for stats
+    hipEvent_t ev_slab[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the passes over a slab, of whichever of the three fills runs: created by the first one that is asked for stats
     float last_edge_ms[2] = {0.f, 0.f};     // count + scan + emit, edges' D2H of the last pc_fill_edges with stats (pc_last_edge_times)
     // pc_fill_components: parent[N], labels[N] + the 8-byte count of passing pairs behind them (one D2H), and their pinned host image
     DevBuf b_cc_parent, b_cc_labels;
     PinnedBuf h_cc_labels;                  // the labels lent out by pc_fill_components
-    hipEvent_t ev_cc[4] = {nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_components that is asked for stats
     float last_cc_ms[2] = {0.f, 0.f};       // union passes, labels pass of the last pc_fill_components with stats (pc_last_component_times)
     // pc_fill_nearest: key[N][K] (order-preserving u64 of the value), then val[N][K] | nbr[N][K] (one D2H), and their pinned host image
     DevBuf b_nn_key, b_nn_out;
     PinnedBuf h_nn;                         // the neighbours and values lent out by pc_fill_nearest
-    hipEvent_t ev_nn[4] = {nullptr, nullptr, nullptr, nullptr};   // created by the first pc_fill_nearest that is asked for stats
     float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest with stats (pc_last_nearest_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
@@ -282,41 +280,64 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
-// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest) in three phases on one context (pc_fill_slabs.hip), so that
-// pc_multi_fill_* can run begin -> walk(its stretch of targets) on every device and merge before the root's end:
-//   check   the refusals of the public call, in its order (metric folded, flags normalised); nothing is touched
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest, and pc_multi_fill_* over several devices) is ONE description of the
+// fill -- a struct of static functions, declared here and defined next to the launchers of its kernels in pc_fill_slabs.hip -- handed as
+// a template argument to the drivers:
+//   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
+//   pc_slab_stretch<Fill>   the walk over the targets [ta, tb): the slab cut, each slab filled and handed to Fill::slab
+//   multi_slab_fill<Fill>   (pc_multi.hip) begin -> walk(its stretch) -> ship on every device, then merge -> end on the root
+// What a description says:
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
-//   walk    the chunking rule over count[t] = t for the targets [ta, tb), each range filled and handed to the call's hook; the
-//           state stays on the device, the edges go behind the n_edges already in the pinned arrays
-//   end     labels / finish and the D2H copy; the counts and pointers of the public call
-// The public calls are check -> begin -> walk [0, N) -> end.  For N <= 1 begin and walk do nothing on the device.
+//   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device
+//   end     labels / finish and the D2H copy; the result pointers and counts into the run
+//   ship_bytes, ship, merge   several devices: the state a non-root device sends to its slice of the root's staging buffer (0 bytes:
+//           nothing travels between devices), and how the root takes the others' state in before its end
+// For N <= 1 begin and the walk do nothing on the device.  PcSlabRun is the call as its entry point was given it (pc_slab_check
+// refuses in the public calls' order, folds the metric, normalises the flags and settles kk), its working state, and its results.
+enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST };
 struct PcSlabRun {
-    const char* who = "";
+    PcSlabKind kind = PC_SLAB_EDGES;
+    const char* who = "";                   // the entry point, for the message texts
+    bool outputs = false;                   // every output pointer was there
     int metric = 0, as_distance = 0, strict = 0, k = 0;
-    double threshold = 0.0;
+    double threshold = 0.0;                 // (nearest: none, stays 0)
     int64_t slab_bytes = 0;
-    bool timed = false;                     // the caller asked for stats: events around the hooks' passes
-    int kk = 0;                             // nearest: min(k, N - 1)
+    bool timed = false;                     // the caller asked for stats: events around the passes over a slab
+    int kk = 0;                             // nearest: min(k, N - 1), at least 0 (pc_slab_check)
     int64_t max_pairs = 0;                  // pairs one slab may hold
     pc_stats sum{};                         // the walks' fills, summed
     int32_t n_slabs = 0;                    // ranges the walks cut
-    int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (set by end)
     bool pending = false;                   // components / nearest: a slab's passes were launched and, timed, their time not yet added
+    // results: the context's pinned memory, set by end
+    const int32_t *src = nullptr, *tgt = nullptr, *labels = nullptr, *nbr = nullptr;
+    const double* val = nullptr;            // edges: the values; nearest: val[N][kk]
+    int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (before end: on the other devices)
+    int32_t n_components = 0;
 };
-int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* kind, bool outputs);
-int pc_edges_begin(pc_ctx* c, PcSlabRun& run);
-int pc_edges_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
-int pc_components_begin(pc_ctx* c, PcSlabRun& run);
-int pc_components_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
-int pc_components_end(pc_ctx* c, PcSlabRun& run, int64_t foreign_pass, const int32_t** labels, int32_t* n_components, int64_t* n_edges);
-int pc_nearest_begin(pc_ctx* c, PcSlabRun& run);
-int pc_nearest_walk(pc_ctx* c, PcSlabRun& run, int ta, int tb);
-int pc_nearest_end(pc_ctx* c, PcSlabRun& run, const int32_t** nbr, const double** val);
-// where the state of a components / nearest fill lives between begin and end (what a non-root device ships to the root)
-static inline size_t pc_cc_label_bytes(int N) { return ((size_t)std::max(N, 1) * 4 + 7) / 8 * 8; }   // the 64-bit count sits behind the labels, aligned
-static inline unsigned long long* pc_cc_pass_counter(const pc_ctx* c) { return (unsigned long long*)((char*)c->b_cc_labels.p + pc_cc_label_bytes(c->dev.N)); }
-static inline int32_t* pc_nn_nbr(const pc_ctx* c, const PcSlabRun& run) { return (int32_t*)((char*)c->b_nn_out.p + (size_t)std::max(c->dev.N, 0) * run.kk * 8); }
+#define PC_SLAB_FILL(Name, tag, text)                                                                                                   \
+    struct Name {                                                                                                                       \
+        static constexpr const char *what = text, *who = "pc_fill_" tag, *range = "pc:fill_" tag, *multi_range = "pc:multi_fill_" tag; \
+        static int begin(pc_ctx* c, PcSlabRun& run);                                                                                    \
+        static int slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard);                               \
+        static int end(pc_ctx* c, PcSlabRun& run);                                                                                      \
+        static size_t ship_bytes(const pc_ctx* root, const PcSlabRun& run);                                                             \
+        static int ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int n_foreign);                                 \
+        static int merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float* ms_exchange); \
+    }
+PC_SLAB_FILL(PcEdgesFill, "edges", "an edge-list fill");
+PC_SLAB_FILL(PcComponentsFill, "components", "a components fill");
+PC_SLAB_FILL(PcNearestFill, "nearest", "a nearest-neighbours fill");
+#undef PC_SLAB_FILL
+int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what);
+template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run);
+template <class Fill> int pc_slab_stretch(pc_ctx* c, PcSlabRun& run, int ta, int tb);
+// `bytes` of device c's state into the root's staging buffer, on c's stream
+static int pc_ship(pc_ctx* c, pc_ctx* root, void* dst, const void* src, size_t bytes) {
+    if (c->device == root->device) PC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    else PC_HIP(hipMemcpyPeerAsync(dst, root->device, src, c->device, bytes, c->stream));
+    return PC_OK;
+}
 
 // DP cells per target genome into c->target_cost, once per upload: one COUNT walk over all pairs (pc_upload.hip).  The context must
 // be unsharded (rank 0 of 1 in force) and idle; no deal is installed or left behind.

@@ -1,5 +1,4 @@
 // pc_multi.hip -- one process, several GPUs: the pc_multi_* entry points of libphamclust_hip.so.
-#include <chrono>
 #include <cstdio>
 #include <new>
 #include <string>
@@ -212,15 +211,16 @@ extern "C" int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Edge, component and nearest fills over the devices of a pc_multi.  Each device runs the phases of the single-context call
-// (pc_fill_slabs.hip: begin -> walk) over ONE contiguous stretch of targets with the call's state on its own device; the state merges
-// exactly -- lists by their total order, forests by uniting g with its foreign parent, edge lists over ascending stretches by
-// concatenation -- so the root's end phase delivers what one context would have.  See the header for the deal and for what travels.
+// Edge, component and nearest fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
+// (pc_host.h, pc_fill_slabs.hip).  Each device runs the description's begin and the walk over ONE contiguous stretch of targets with
+// the call's state on its own device, and ships that state to the root; the state merges exactly -- lists by their total order,
+// forests by uniting g with its foreign parent, edge lists over ascending stretches by concatenation -- so the root's end delivers
+// what one context would have.  See the header for the deal and for what travels.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-// Ahead of the phases: the refusals, every context unsharded, and the deal.  Returns PC_OK with `single` set when the root alone
+// Ahead of the devices' work: the refusals, every context unsharded, and the deal.  Returns PC_OK with `single` set when the root alone
 // serves the call (one device, or no pair to fill).
-int slab_prepare(pc_multi* m, PcSlabRun& run, const char* kind, bool outputs, bool& single) {
+int slab_prepare(pc_multi* m, PcSlabRun& run, const char* what, bool& single) {
     int rc = PC_OK;
     single = false;
     if (!m) { pc_set_error("%s: NULL argument", run.who); return PC_ERR_ARG; }
@@ -233,7 +233,7 @@ int slab_prepare(pc_multi* m, PcSlabRun& run, const char* kind, bool outputs, bo
     m->stretches.assign((size_t)world + 1, 0);
     m->stretches[world] = N;
     if (world == 1 || N <= 1) { for (int r = 1; r < world; ++r) m->stretches[r] = N; single = true; return PC_OK; }
-    if ((rc = pc_slab_check(root, run, kind, outputs))) return rc;
+    if ((rc = pc_slab_check(root, run, what))) return rc;
     // the deal: contiguous stretches of about equal cost, computed once, on the root
     std::vector<uint64_t> cost((size_t)N);
     if (run.metric >= PC_AAI) {
@@ -249,27 +249,65 @@ int slab_prepare(pc_multi* m, PcSlabRun& run, const char* kind, bool outputs, bo
     return pc_stretch_plan(cost.data(), N, world, m->stretches.data());
 }
 
-// which slice of the root's staging buffer a device ships into: its position among the non-root devices with a stretch (-1: none)
-std::vector<int> staging_slots(const pc_multi* m, int& n_foreign) {
+// The call `run` over the devices of m; on PC_OK the run holds the results (the root's) and stats[r], when asked for, device r's fills.
+template <class Fill> int multi_slab_fill(pc_multi* m, PcSlabRun& run, pc_stats* stats) {
+    int rc = PC_OK;
+    bool single = false;
+    if ((rc = slab_prepare(m, run, Fill::what, single))) return rc;
     const int world = (int)m->ctx.size();
+    pc_ctx* root = m->ctx[0];
+    if (single) {                                                           // the single-context call, under its own name
+        if (stats) for (int r = 1; r < world; ++r) memset(&stats[r], 0, sizeof(pc_stats));
+        run.who = Fill::who;
+        if ((rc = pc_slab_fill<Fill>(root, run))) return rc;
+        if (stats) stats[0] = run.sum;
+        return PC_OK;
+    }
+    PcRange range(Fill::multi_range);
+    // a slice of the root's staging buffer for every device that ships: the non-root devices with a stretch, in rank order
     std::vector<int> slot((size_t)world, -1);
-    n_foreign = 0;
+    int n_foreign = 0;
     for (int r = 1; r < world; ++r) if (m->stretches[r] < m->stretches[r + 1]) slot[r] = n_foreign++;
-    return slot;
-}
-
-// `bytes` of device r's state into the root's staging buffer, on r's stream
-int ship(pc_ctx* c, pc_ctx* root, void* dst, const void* src, size_t bytes) {
-    if (c->device == root->device) PC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-    else PC_HIP(hipMemcpyPeerAsync(dst, root->device, src, c->device, bytes, c->stream));
+    const size_t bytes = Fill::ship_bytes(root, run);
+    if (bytes) {
+        PcDeviceGuard guard(root->device);
+        if (!guard.ok) return PC_ERR_HIP;
+        if ((rc = abi_rc(m->b_stage.ensure(std::max<size_t>((size_t)n_foreign * bytes, 16))))) return rc;
+    }
+    std::vector<PcSlabRun> runs((size_t)world, run);
+    std::vector<float> xms((size_t)world, 0.f);
+    rc = multi_each(m, [&](int r) -> int {
+        pc_ctx* c = m->ctx[r];
+        const int ta = m->stretches[r], tb = m->stretches[r + 1];
+        if (r != 0 && ta == tb) return (int)PC_OK;                          // an empty stretch: nothing launched, nothing shipped
+        PcDeviceGuard guard(c->device);
+        if (!guard.ok) return (int)PC_ERR_HIP;
+        int e = PC_OK;
+        if ((e = Fill::begin(c, runs[r])) || (e = pc_slab_stretch<Fill>(c, runs[r], ta, tb))) return e;
+        if (r == 0 || !bytes) return (int)PC_OK;
+        // the one exchange: this device's state into its slice on the root, timed between its events 0 and 1
+        if ((e = Fill::ship(c, root, runs[r], m->b_stage.p, slot[r], n_foreign))) return e;
+        PC_HIP(hipStreamSynchronize(c->stream));
+        c->busy = false;
+        PC_HIP(hipEventElapsedTime(&xms[r], c->ev[0], c->ev[1]));
+        return (int)PC_OK;
+    });
+    if (rc != PC_OK) return rc;
+    int64_t slabs = 0;
+    for (const PcSlabRun& one : runs) slabs += one.n_slabs;
+    m->last_slab_ms[0] = *std::max_element(xms.begin(), xms.end());
+    {
+        // the merge on the root (the copies have arrived: every shipping stream was drained), between the root's events 0 and 1 where it
+        // is a launch, then the root's own end
+        PcDeviceGuard guard(root->device);
+        if (!guard.ok) return PC_ERR_HIP;
+        if ((rc = Fill::merge(m->ctx, runs, m->b_stage.p, n_foreign, &m->last_slab_ms[0])) || (rc = Fill::end(root, runs[0]))) return rc;
+        if (bytes) PC_HIP(hipEventElapsedTime(&m->last_slab_ms[1], root->ev[0], root->ev[1]));
+    }
+    run = runs[0];
+    run.n_slabs = (int32_t)slabs;
+    if (stats) for (int r = 0; r < world; ++r) stats[r] = runs[r].sum;
     return PC_OK;
-}
-
-void give_stats(pc_stats* stats, const std::vector<PcSlabRun>& runs) {
-    if (stats) for (size_t r = 0; r < runs.size(); ++r) stats[r] = runs[r].sum;
-}
-void zero_tail(pc_stats* stats, int world) {
-    if (stats) for (int r = 1; r < world; ++r) memset(&stats[r], 0, sizeof(pc_stats));
 }
 }  // namespace
 
@@ -280,51 +318,11 @@ extern "C" int pc_multi_fill_edges(pc_multi* m, int metric, int as_distance, dou
     if (val) *val = nullptr;
     if (n_edges) *n_edges = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun proto; proto.who = "pc_multi_fill_edges"; proto.metric = metric; proto.as_distance = as_distance; proto.threshold = threshold;
-    proto.slab_bytes = slab_bytes; proto.timed = stats != nullptr;
-    bool single = false;
-    if ((rc = slab_prepare(m, proto, "an edge-list fill", src && tgt && val && n_edges && n_slabs, single))) return rc;
-    const int world = (int)m->ctx.size();
-    pc_ctx* root = m->ctx[0];
-    if (single) { zero_tail(stats, world); return pc_fill_edges(root, metric, as_distance, threshold, slab_bytes, src, tgt, val, n_edges, n_slabs, stats); }
-    PcRange range("pc:multi_fill_edges");
-    std::vector<PcSlabRun> runs((size_t)world, proto);
-    rc = multi_each(m, [&](int r) -> int {
-        pc_ctx* c = m->ctx[r];
-        const int ta = m->stretches[r], tb = m->stretches[r + 1];
-        if (r != 0 && ta == tb) return (int)PC_OK;                          // an empty stretch: nothing launched, nothing to copy
-        PcDeviceGuard guard(c->device);
-        if (!guard.ok) return (int)PC_ERR_HIP;
-        int e = pc_edges_begin(c, runs[r]);
-        return e ? e : pc_edges_walk(c, runs[r], ta, tb);
-    });
+    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_multi_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    const int rc = multi_slab_fill<PcEdgesFill>(m, run, stats);
     if (rc != PC_OK) return rc;
-    // the root's pinned arrays grown to the total, every device's edges behind those of the ranks before it
-    int64_t total = 0, slabs = 0;
-    for (const PcSlabRun& run : runs) { total += run.n_edges; slabs += run.n_slabs; }
-    const int64_t own = runs[0].n_edges;
-    if (total > own) {
-        PcDeviceGuard guard(root->device);
-        if (!guard.ok) return PC_ERR_HIP;
-        if ((rc = root->h_edge_src.grow_keep((size_t)total * 4, (size_t)own * 4)) || (rc = root->h_edge_tgt.grow_keep((size_t)total * 4, (size_t)own * 4)) ||
-            (rc = root->h_edge_val.grow_keep((size_t)total * 8, (size_t)own * 8))) return rc;
-        const auto t0 = std::chrono::steady_clock::now();
-        int64_t at = own;
-        for (int r = 1; r < world; ++r) {
-            const int64_t E = runs[r].n_edges;
-            if (E == 0) continue;
-            const pc_ctx* c = m->ctx[r];
-            memcpy(root->h_edge_src.as<int32_t>() + at, c->h_edge_src.p, (size_t)E * 4);
-            memcpy(root->h_edge_tgt.as<int32_t>() + at, c->h_edge_tgt.p, (size_t)E * 4);
-            memcpy(root->h_edge_val.as<double>() + at, c->h_edge_val.p, (size_t)E * 8);
-            at += E;
-        }
-        m->last_slab_ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    *src = root->h_edge_src.as<int32_t>(); *tgt = root->h_edge_tgt.as<int32_t>(); *val = root->h_edge_val.as<double>();
-    *n_edges = total; *n_slabs = (int32_t)slabs;
-    give_stats(stats, runs);
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
     return PC_OK;
 }
 
@@ -334,61 +332,11 @@ extern "C" int pc_multi_fill_components(pc_multi* m, int metric, int as_distance
     if (n_components) *n_components = 0;
     if (n_edges) *n_edges = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun proto; proto.who = "pc_multi_fill_components"; proto.metric = metric; proto.as_distance = as_distance; proto.strict = strict;
-    proto.threshold = threshold; proto.slab_bytes = slab_bytes; proto.timed = stats != nullptr;
-    bool single = false;
-    if ((rc = slab_prepare(m, proto, "a components fill", labels && n_components && n_edges && n_slabs, single))) return rc;
-    const int world = (int)m->ctx.size();
-    pc_ctx* root = m->ctx[0];
-    if (single) { zero_tail(stats, world); return pc_fill_components(root, metric, as_distance, threshold, strict, slab_bytes, labels, n_components, n_edges, n_slabs, stats); }
-    PcRange range("pc:multi_fill_components");
-    const int N = root->dev.N;
-    int n_foreign = 0;
-    const std::vector<int> slot = staging_slots(m, n_foreign);
-    {
-        PcDeviceGuard guard(root->device);
-        if (!guard.ok) return PC_ERR_HIP;
-        if ((rc = abi_rc(m->b_stage.ensure(std::max<size_t>((size_t)n_foreign * (size_t)N * 4, 16))))) return rc;
-    }
-    std::vector<PcSlabRun> runs((size_t)world, proto);
-    std::vector<float> xms((size_t)world, 0.f);
-    std::vector<unsigned long long> passed((size_t)world, 0ull);
-    rc = multi_each(m, [&](int r) -> int {
-        pc_ctx* c = m->ctx[r];
-        const int ta = m->stretches[r], tb = m->stretches[r + 1];
-        if (r != 0 && ta == tb) return (int)PC_OK;                          // an empty stretch: nothing launched, nothing shipped
-        PcDeviceGuard guard(c->device);
-        if (!guard.ok) return (int)PC_ERR_HIP;
-        int e = PC_OK;
-        if ((e = pc_components_begin(c, runs[r])) || (e = pc_components_walk(c, runs[r], ta, tb))) return e;
-        if (r == 0) return (int)PC_OK;
-        // the one exchange: this device's forest into its slice on the root, its count of passing pairs to the host
-        PC_HIP(hipEventRecord(c->ev[0], c->stream));
-        if ((e = ship(c, root, m->b_stage.as<int32_t>() + (size_t)slot[r] * (size_t)N, c->b_cc_parent.p, (size_t)N * 4))) return e;
-        PC_HIP(hipEventRecord(c->ev[1], c->stream));
-        PC_HIP(hipMemcpyAsync(&passed[r], pc_cc_pass_counter(c), 8, hipMemcpyDeviceToHost, c->stream));
-        PC_HIP(hipStreamSynchronize(c->stream));
-        c->busy = false;
-        PC_HIP(hipEventElapsedTime(&xms[r], c->ev[0], c->ev[1]));
-        return (int)PC_OK;
-    });
+    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_multi_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
+    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
+    const int rc = multi_slab_fill<PcComponentsFill>(m, run, stats);
     if (rc != PC_OK) return rc;
-    int64_t foreign_pass = 0, slabs = 0;
-    for (int r = 0; r < world; ++r) { foreign_pass += (int64_t)passed[r]; slabs += runs[r].n_slabs; }
-    {
-        // one merge launch on the root (the copies have arrived: every shipping stream was drained), then the root's own end phase
-        PcDeviceGuard guard(root->device);
-        if (!guard.ok) return PC_ERR_HIP;
-        PC_HIP(hipEventRecord(root->ev[0], root->stream));
-        if ((rc = pc_launch_cc_merge(root->b_cc_parent.as<int32_t>(), m->b_stage.as<int32_t>(), n_foreign, N, root->stream))) return rc;
-        PC_HIP(hipEventRecord(root->ev[1], root->stream));
-        if ((rc = pc_components_end(root, runs[0], foreign_pass, labels, n_components, n_edges))) { *labels = nullptr; *n_components = 0; *n_edges = 0; return rc; }
-        PC_HIP(hipEventElapsedTime(&m->last_slab_ms[1], root->ev[0], root->ev[1]));
-    }
-    m->last_slab_ms[0] = *std::max_element(xms.begin(), xms.end());
-    *n_slabs = (int32_t)slabs;
-    give_stats(stats, runs);
+    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
     return PC_OK;
 }
 
@@ -398,64 +346,11 @@ extern "C" int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, i
     if (val) *val = nullptr;
     if (k_out) *k_out = 0;
     if (n_slabs) *n_slabs = 0;
-    int rc = PC_OK;
-    PcSlabRun proto; proto.who = "pc_multi_fill_nearest"; proto.metric = metric; proto.as_distance = as_distance; proto.k = k; proto.kk = -1;
-    proto.slab_bytes = slab_bytes; proto.timed = stats != nullptr;
-    bool single = false;
-    if ((rc = slab_prepare(m, proto, "a nearest-neighbours fill", nbr && val && k_out && n_slabs, single))) return rc;
-    const int world = (int)m->ctx.size();
-    pc_ctx* root = m->ctx[0];
-    if (single) { zero_tail(stats, world); return pc_fill_nearest(root, metric, as_distance, k, slab_bytes, nbr, val, k_out, n_slabs, stats); }
-    PcRange range("pc:multi_fill_nearest");
-    const int N = root->dev.N;
-    const int kk = std::min(k, N - 1);                                      // (N > 1, 1 <= k <= 64: what every device's begin arrives at)
-    const size_t n_ent = (size_t)N * kk;
-    int n_foreign = 0;
-    const std::vector<int> slot = staging_slots(m, n_foreign);
-    {
-        PcDeviceGuard guard(root->device);
-        if (!guard.ok) return PC_ERR_HIP;
-        if ((rc = abi_rc(m->b_stage.ensure(std::max<size_t>((size_t)n_foreign * n_ent * 12, 16))))) return rc;
-    }
-    unsigned long long* const stage_key = m->b_stage.as<unsigned long long>();         // [n_foreign][N][kk] keys, then as many indices
-    int32_t* const stage_nbr = (int32_t*)(stage_key + (size_t)n_foreign * n_ent);
-    std::vector<PcSlabRun> runs((size_t)world, proto);
-    std::vector<float> xms((size_t)world, 0.f);
-    rc = multi_each(m, [&](int r) -> int {
-        pc_ctx* c = m->ctx[r];
-        const int ta = m->stretches[r], tb = m->stretches[r + 1];
-        if (r != 0 && ta == tb) return (int)PC_OK;                          // an empty stretch: nothing launched, nothing shipped
-        PcDeviceGuard guard(c->device);
-        if (!guard.ok) return (int)PC_ERR_HIP;
-        int e = PC_OK;
-        if ((e = pc_nearest_begin(c, runs[r])) || (e = pc_nearest_walk(c, runs[r], ta, tb))) return e;
-        if (r == 0) return (int)PC_OK;
-        // the one exchange: this device's lists, in key space, into its slice on the root
-        PC_HIP(hipEventRecord(c->ev[0], c->stream));
-        if ((e = ship(c, root, stage_key + (size_t)slot[r] * n_ent, c->b_nn_key.p, n_ent * 8)) ||
-            (e = ship(c, root, stage_nbr + (size_t)slot[r] * n_ent, pc_nn_nbr(c, runs[r]), n_ent * 4))) return e;
-        PC_HIP(hipEventRecord(c->ev[1], c->stream));
-        PC_HIP(hipStreamSynchronize(c->stream));
-        c->busy = false;
-        PC_HIP(hipEventElapsedTime(&xms[r], c->ev[0], c->ev[1]));
-        return (int)PC_OK;
-    });
+    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_multi_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
+    const int rc = multi_slab_fill<PcNearestFill>(m, run, stats);
     if (rc != PC_OK) return rc;
-    int64_t slabs = 0;
-    for (const PcSlabRun& run : runs) slabs += run.n_slabs;
-    {
-        // one merge launch on the root (the copies have arrived: every shipping stream was drained), then the root's own end phase
-        PcDeviceGuard guard(root->device);
-        if (!guard.ok) return PC_ERR_HIP;
-        PC_HIP(hipEventRecord(root->ev[0], root->stream));
-        if ((rc = pc_launch_nn_merge(root->b_nn_key.as<unsigned long long>(), pc_nn_nbr(root, runs[0]), stage_key, stage_nbr, n_foreign, N, kk, root->stream))) return rc;
-        PC_HIP(hipEventRecord(root->ev[1], root->stream));
-        if ((rc = pc_nearest_end(root, runs[0], nbr, val))) { *nbr = nullptr; *val = nullptr; return rc; }
-        PC_HIP(hipEventElapsedTime(&m->last_slab_ms[1], root->ev[0], root->ev[1]));
-    }
-    m->last_slab_ms[0] = *std::max_element(xms.begin(), xms.end());
-    *k_out = kk; *n_slabs = (int32_t)slabs;
-    give_stats(stats, runs);
+    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
     return PC_OK;
 }
 

@@ -274,7 +274,87 @@ class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
         return f"BorrowedArray({'live' if self._root._live else 'loan ended'}, shape={self.shape}, dtype={self.dtype})"
 
 
-class Context:
+class _SlabFills:
+    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` -- the fills that deliver no dense matrix -- once for :class:`Context`
+    and :class:`MultiContext`.  The class supplies ``_SLAB_CALL`` (the prefix of the library's symbols), ``_before_slab_fill(metric)``
+    (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
+    dict of such a fill)."""
+
+    def _slab_fill(self, kind, metric, *args):
+        stats = self._before_slab_fill(metric)
+        self._check(getattr(self._lib, self._SLAB_CALL + kind)(self._h, METRIC_IDS[metric], *args, stats))
+        return stats
+
+    def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
+        for a similarity fill -- as ``(src, tgt, val)``: int32, int32, float64 arrays sorted by ``t``, then ``s``; the values are
+        the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time; 0 = automatic) held.
+        The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s terms.
+        ``want_stats`` adds the fills' summed stats with ``n_edges``, ``n_slabs``, ``ms_compact`` and ``ms_d2h``.
+
+        On a :class:`MultiContext`: the same arrays, element for element, whatever the number of devices -- each walks one
+        contiguous stretch of targets, and the lists are laid end to end in the root's page-locked memory.  The stats are summed
+        over the devices and carry the route's own entries (``per_device``, ``stretches``, ``ms_exchange``, ``ms_merge``,
+        ``n_devices``, ``peer_access``) in place of the two times."""
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._slab_fill("edges", metric, int(bool(as_distance)), float(threshold), int(slab_bytes),
+                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        return (*out, self._slab_stats("edges", stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
+
+    def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The connected components of the graph whose edges are the pairs that pass ``threshold`` -- ``d < threshold`` for a
+        distance fill (``d <= threshold`` with ``strict=False``), ``sim > threshold`` (``>=``) for a similarity fill -- as
+        ``labels``: int32[N], ``labels[g]`` = the smallest genome index of g's component.  On distances with ``strict`` these are the
+        single-linkage clusters at ``eps = threshold``.  Neither the dense matrix nor an edge list is delivered; the matrix is held
+        in HBM ``slab_bytes`` at a time (0 = automatic), as by :meth:`fill_edges`.  The array is a copy; ``borrow=True`` lends the
+        context's page-locked memory instead, on ``fill(borrow=True)``'s terms.  ``want_stats`` adds the fills' summed stats with
+        ``n_components``, ``n_edges`` (pairs that passed), ``n_slabs``, ``ms_union`` and ``ms_labels``.
+
+        On a :class:`MultiContext`: the same canonical ``labels`` -- every device builds the forest of its stretch of targets, the
+        root unites them (``k_cc_merge``) and labels; ``n_edges`` counts over all devices, and the stats carry the route's own
+        entries (as for :meth:`fill_edges`) in place of the two times."""
+        pl = _i32p()
+        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._slab_fill("components", metric, int(bool(as_distance)), float(threshold), int(bool(strict)), int(slab_bytes),
+                                ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl))
+        n = self.n_genomes
+        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
+        if not want_stats:
+            return labels
+        return labels, self._slab_stats("components", stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+
+    def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """Each genome's ``kk = min(k, N - 1)`` nearest neighbours as ``(nbr, val)``: int32[N, kk] genome indices and float64[N, kk]
+        values, row g listing the genomes h != g best first -- the smallest distance (``as_distance``), else the largest
+        similarity -- and equal values in index order: ``SymMatrix.nearest_neighbors(g, threshold)`` with the threshold wide
+        open, cut after kk.  The values are the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of
+        HBM at a time; 0 = automatic) held, as by :meth:`fill_edges`.  ``k`` above ``Context.NEAREST_MAX_K`` is refused by the
+        library.  The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s
+        terms.  ``want_stats`` adds the fills' summed stats with ``k`` (= kk), ``n_slabs``, ``ms_select`` and ``ms_finish``.
+
+        On a :class:`MultiContext`: the same ``(nbr, val)`` -- the k smallest of one total order, so the lists the devices build
+        over their stretches of targets merge by that order on the root (``k_nn_merge``); the stats carry the route's own entries
+        (as for :meth:`fill_edges`) in place of the two times."""
+        pn, pv = _i32p(), _f64p()
+        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        stats = self._slab_fill("nearest", metric, int(bool(as_distance)), int(k), int(slab_bytes),
+                                ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl))
+        n = self.n_genomes
+        if n and kk.value and pn and pv:
+            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
+        else:
+            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
+        if not want_stats:
+            return nbr, val
+        return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
+
+
+class Context(_SlabFills):
     """One GPU.  ``upload`` once, then ``fill`` any of the six metrics."""
 
     def __init__(self, device_id=0):
@@ -500,83 +580,25 @@ class Context:
             raise ValueError("edge_slabs: slab_bytes must be positive (0 = automatic is decided on the device, by the free HBM)")
         return Context.chunk_plan(np.arange(int(n), dtype=np.uint64), min(max(int(slab_bytes) // 8, 1), Context.EDGE_MAX_PAIRS))
 
-    def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
-        """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
-        for a similarity fill -- as ``(src, tgt, val)``: int32, int32, float64 arrays sorted by ``t``, then ``s``; the values are
-        the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time; 0 = automatic) held.
-        The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s terms.
-        ``want_stats`` adds the fills' summed stats with ``n_edges``, ``n_slabs``, ``ms_compact`` and ``ms_d2h``."""
-        stats = PcStats()
-        if metric in NEEDS_RESIDUES:
-            self.ensure_residues()
-        self._invalidate_loans()
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_fill_edges(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(slab_bytes),
-                                            ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl),
-                                            ctypes.byref(stats)))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
-        self._check(self._lib.pc_last_edge_times(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return (*out, dict(stats.as_dict(), n_edges=int(n.value), n_slabs=int(nsl.value), ms_compact=float(a.value), ms_d2h=float(b.value)))
+    # -- fill_edges / fill_components / fill_nearest (_SlabFills): what this class supplies ----------------------------------
+    _SLAB_CALL = "pc_fill_"
+    _SLAB_TIMES = {"edges": ("pc_last_edge_times", "ms_compact", "ms_d2h"), "components": ("pc_last_component_times", "ms_union", "ms_labels"),
+                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish")}
 
-    def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
-        """The connected components of the graph whose edges are the pairs that pass ``threshold`` -- ``d < threshold`` for a
-        distance fill (``d <= threshold`` with ``strict=False``), ``sim > threshold`` (``>=``) for a similarity fill -- as
-        ``labels``: int32[N], ``labels[g]`` = the smallest genome index of g's component.  On distances with ``strict`` these are the
-        single-linkage clusters at ``eps = threshold``.  Neither the dense matrix nor an edge list is delivered; the matrix is held
-        in HBM ``slab_bytes`` at a time (0 = automatic), as by :meth:`fill_edges`.  The array is a copy; ``borrow=True`` lends the
-        context's page-locked memory instead, on ``fill(borrow=True)``'s terms.  ``want_stats`` adds the fills' summed stats with
-        ``n_components``, ``n_edges`` (pairs that passed), ``n_slabs``, ``ms_union`` and ``ms_labels``."""
-        stats = PcStats()
+    def _before_slab_fill(self, metric):
         if metric in NEEDS_RESIDUES:
             self.ensure_residues()
         self._invalidate_loans()
-        pl = _i32p()
-        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_fill_components(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(bool(strict)),
-                                                 int(slab_bytes), ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl),
-                                                 ctypes.byref(stats)))
-        n = self.n_genomes
-        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
-        if not want_stats:
-            return labels
+        return PcStats()
+
+    def _slab_stats(self, kind, stats, **own):
+        """The stats dict of such a fill: the fills' summed stats, the call's counts and the kind's two times."""
+        call, first, second = self._SLAB_TIMES[kind]
         a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
-        self._check(self._lib.pc_last_component_times(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return labels, dict(stats.as_dict(), n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value),
-                            ms_union=float(a.value), ms_labels=float(b.value))
+        self._check(getattr(self._lib, call)(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return dict(stats.as_dict(), **own, **{first: float(a.value), second: float(b.value)})
 
     NEAREST_MAX_K = 64                    # PC_NEAREST_MAX_K: a genome's list lives one entry per lane of a wave
-
-    def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
-        """Each genome's ``kk = min(k, N - 1)`` nearest neighbours as ``(nbr, val)``: int32[N, kk] genome indices and float64[N, kk]
-        values, row g listing the genomes h != g best first -- the smallest distance (``as_distance``), else the largest
-        similarity -- and equal values in index order: ``SymMatrix.nearest_neighbors(g, threshold)`` with the threshold wide
-        open, cut after kk.  The values are the whole fill's.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of
-        HBM at a time; 0 = automatic) held, as by :meth:`fill_edges`.  ``k`` above :attr:`NEAREST_MAX_K` is refused by the
-        library.  The arrays are copies; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s
-        terms.  ``want_stats`` adds the fills' summed stats with ``k`` (= kk), ``n_slabs``, ``ms_select`` and ``ms_finish``."""
-        stats = PcStats()
-        if metric in NEEDS_RESIDUES:
-            self.ensure_residues()
-        self._invalidate_loans()
-        pn, pv = _i32p(), _f64p()
-        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_fill_nearest(self._h, METRIC_IDS[metric], int(bool(as_distance)), int(k), int(slab_bytes),
-                                              ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl), ctypes.byref(stats)))
-        n = self.n_genomes
-        if n and kk.value and pn and pv:
-            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
-        else:
-            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
-        if not want_stats:
-            return nbr, val
-        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
-        self._check(self._lib.pc_last_nearest_times(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return nbr, val, dict(stats.as_dict(), k=int(kk.value), n_slabs=int(nsl.value), ms_select=float(a.value), ms_finish=float(b.value))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()
@@ -774,7 +796,7 @@ class Context:
         return out
 
 
-class MultiContext:
+class MultiContext(_SlabFills):
     """Several GPUs of this node driven from THIS process (``pc_multi_*``: a context and a host thread per device inside the
     library, the shard exchange as device-to-device copies) -- the multi-GPU route that costs no launcher, no interpreter and no
     process group per GPU.  ``device_ids[0]`` delivers the matrix; an id may repeat (several contexts on one GPU: rehearsal).
@@ -877,7 +899,9 @@ class MultiContext:
                       ms_total=max(p["ms_total"] for p in per), peer_access=self.peer_access())
         return out, merged
 
-    # -- the fills that deliver no dense matrix, over all devices (pc_multi_fill_edges / _components / _nearest) ------------
+    # -- the fills that deliver no dense matrix, over all devices (_SlabFills: pc_multi_fill_edges / _components / _nearest) ----
+    _SLAB_CALL = "pc_multi_fill_"
+
     @staticmethod
     def slab_stretches(cost, world):
         """The deal of those fills as host arithmetic (``pc_stretch_plan``; no GPU): ``bounds[world + 1]`` -- device r walks the
@@ -899,7 +923,7 @@ class MultiContext:
         self._invalidate_loans()
         return (PcStats * self.n_devices)()
 
-    def _slab_stats(self, stats, **own):
+    def _slab_stats(self, kind, stats, **own):
         """The stats dict of such a fill: the counts summed over the devices, the times of the slowest, and what the route adds --
         ``n_devices``, ``per_device``, ``stretches``, ``ms_exchange``, ``ms_merge``, ``peer_access``."""
         per = [s.as_dict() for s in stats]
@@ -910,52 +934,3 @@ class MultiContext:
         self._check(self._lib.pc_multi_last_slab_times(self._h, ctypes.byref(x), ctypes.byref(y)))
         return dict(merged, **own, n_devices=self.n_devices, per_device=per, stretches=bounds.tolist(), ms_exchange=float(x.value),
                     ms_merge=float(y.value), peer_access=self.peer_access())
-
-    def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
-        """``Context.fill_edges`` over all devices: the same ``(src, tgt, val)`` arrays, element for element, whatever the number
-        of devices -- each walks one contiguous stretch of targets, and the lists are laid end to end in the root's page-locked
-        memory.  ``want_stats`` adds the summed stats with ``n_edges``, ``n_slabs`` and the route's own entries (``per_device``,
-        ``stretches``, ``ms_exchange``, ``ms_merge``, ``n_devices``, ``peer_access``)."""
-        stats = self._before_slab_fill(metric)
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_multi_fill_edges(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(slab_bytes),
-                                                  ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl), stats))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        return (*out, self._slab_stats(stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
-
-    def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
-        """``Context.fill_components`` over all devices: the same canonical ``labels`` -- every device builds the forest of its
-        stretch of targets, the root unites them (``k_cc_merge``) and labels.  ``want_stats`` adds the summed stats with
-        ``n_components``, ``n_edges`` (pairs that passed, over all devices), ``n_slabs`` and the route's own entries."""
-        stats = self._before_slab_fill(metric)
-        pl = _i32p()
-        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_multi_fill_components(self._h, METRIC_IDS[metric], int(bool(as_distance)), float(threshold), int(bool(strict)),
-                                                       int(slab_bytes), ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl), stats))
-        n = self.n_genomes
-        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
-        if not want_stats:
-            return labels
-        return labels, self._slab_stats(stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
-
-    def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
-        """``Context.fill_nearest`` over all devices: the same ``(nbr, val)`` -- the k smallest of one total order, so the lists
-        the devices build over their stretches of targets merge by that order on the root (``k_nn_merge``).  ``want_stats`` adds
-        the summed stats with ``k`` (= kk), ``n_slabs`` and the route's own entries."""
-        stats = self._before_slab_fill(metric)
-        pn, pv = _i32p(), _f64p()
-        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        self._check(self._lib.pc_multi_fill_nearest(self._h, METRIC_IDS[metric], int(bool(as_distance)), int(k), int(slab_bytes),
-                                                    ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl), stats))
-        n = self.n_genomes
-        if n and kk.value and pn and pv:
-            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
-        else:
-            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
-        if not want_stats:
-            return nbr, val
-        return nbr, val, self._slab_stats(stats, k=int(kk.value), n_slabs=int(nsl.value))

@@ -778,29 +778,15 @@ def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
     has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  With ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` naming more than one
     device the fill is spread over them from this process (``MultiContext.fill_edges``: a contiguous stretch of targets per device,
     the same edges); under a launcher (``WORLD_SIZE`` > 1) it raises."""
-    if len(genomes) == 0:
-        raise ValueError("need at least 1 genome to construct edges de novo")
-    metric = _metric_name(func)
-    if metric is None:
-        raise ValueError("edges_de_novo: func must be one of the six METRICS callables -- the edge-list fill runs on the GPU only and has no "
-                         "CPU route (for another callable: SparseEdges.from_dense(matrix_de_novo(...), threshold))")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("edges_de_novo: the edge-list fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+    ctx, metric, names, record = upload_for_fills(genomes, func, "edges_de_novo", several=True,
+                                                  advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), threshold)")
     import time
     t0 = time.perf_counter()
-    packed = _packed_of(genomes)
-    t1 = time.perf_counter()
-    ctx, n_gpus = _slab_fill_context()
-    ctx.upload(packed, residues=metric in ("aai", "peq"))
-    t2 = time.perf_counter()
     src, tgt, val, stats = ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    t3 = time.perf_counter()
-    LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=n_gpus, rank=0,
-                     pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
-    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} of {packed.n_pairs} edges in {stats['n_slabs']} slab(s) on {n_gpus} device(s): "
-                  f"pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+compact+D2H {t3 - t2:.3f} s (kernels {stats['ms_total']:.3f} ms)")
-    return SparseEdges([g.name for g in genomes], src, tgt, val, is_distance=as_distance, threshold=threshold)
+    fill_s = _record_fill(stats, metric, names, record, t0)
+    logging.debug(f"{len(names)} genomes -> {stats['n_edges']} of {record['genome_pairs']} edges in {stats['n_slabs']} slab(s) on {record['n_gpus']} "
+                  f"device(s): fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    return SparseEdges(names, src, tgt, val, is_distance=as_distance, threshold=threshold)
 
 
 class Components:
@@ -845,38 +831,24 @@ def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, 
     ``METRICS`` callables (no CPU route: ``SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)`` serves another
     callable).  Several devices as ``edges_de_novo`` (``MultiContext.fill_components``: the same labels); under a launcher
     (``WORLD_SIZE`` > 1) it raises."""
-    if len(genomes) == 0:
-        raise ValueError("need at least 1 genome to construct components de novo")
-    metric = _metric_name(func)
-    if metric is None:
-        raise ValueError("components_de_novo: func must be one of the six METRICS callables -- the components fill runs on the GPU only and has "
-                         "no CPU route (for another callable: SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold))")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("components_de_novo: the components fill is a one-GPU call; run it in one process, not under a launcher (WORLD_SIZE > 1)")
+    ctx, metric, names, record = upload_for_fills(genomes, func, "components_de_novo", several=True,
+                                                  advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)")
     import time
     t0 = time.perf_counter()
-    packed = _packed_of(genomes)
-    t1 = time.perf_counter()
-    ctx, n_gpus = _slab_fill_context()
-    ctx.upload(packed, residues=metric in ("aai", "peq"))
-    t2 = time.perf_counter()
     labels, stats = ctx.fill_components(metric, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes, want_stats=True)
-    t3 = time.perf_counter()
-    LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=packed.n_pairs, n_gpus=n_gpus, rank=0,
-                     pack_s=t1 - t0, upload_s=t2 - t1, fill_s=t3 - t2)
-    logging.debug(f"{len(genomes)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {packed.n_pairs} pairs in "
-                  f"{stats['n_slabs']} slab(s) on {n_gpus} device(s): pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s, fill+union+labels {t3 - t2:.3f} s "
-                  f"(kernels {stats['ms_total']:.3f} ms)")
-    return Components([g.name for g in genomes], labels)
+    fill_s = _record_fill(stats, metric, names, record, t0)
+    logging.debug(f"{len(names)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {record['genome_pairs']} pairs in "
+                  f"{stats['n_slabs']} slab(s) on {record['n_gpus']} device(s): fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    return Components(names, labels)
 
 
-def upload_for_fills(genomes, func, caller, several=False):
+def upload_for_fills(genomes, func, caller, several=False, advice="the dense route, matrix_de_novo, serves another callable"):
     """What the one-GPU routes without a dense matrix share ahead of their fills: the refusals (no genome, a callable outside the
     six ``METRICS``, a launcher), then ONE pack and ONE upload.  Returns ``(context, metric name, genome names, record)`` -- the
     record holds ``pack_s``, ``upload_s``, ``n_gpus`` and the collection's ``genome_pairs`` for ``LAST_FILL`` -- and the caller runs as
-    many fills as it needs.  ``several``: the caller's fill also runs over several devices (``neighbors_de_novo``), so the context is
-    ``_slab_fill_context()``'s; the groups and rows routes leave it off and stay on one GPU.  The caller runs as many fills
+    many fills as it needs.  ``several``: the caller's fill also runs over several devices (``edges_de_novo``, ``components_de_novo``,
+    ``neighbors_de_novo``), so the context is ``_slab_fill_context()``'s; the groups and rows routes leave it off and stay on one GPU.
+    ``advice``: what the refusal of a generic callable tells its reader to use instead.  The caller runs as many fills
     on the context as it needs (``submatrices_de_novo``: a groups fill; ``hierarchical_clustering_de_novo``: a components fill, then
     a groups fill; ``phamclust --no-matrix``: two and three of them)."""
     if len(genomes) == 0:
@@ -884,7 +856,7 @@ def upload_for_fills(genomes, func, caller, several=False):
     metric = _metric_name(func)
     if metric is None:
         raise ValueError(f"{caller}: func must be one of the six METRICS callables -- the components and groups fills run on the GPU only and "
-                         f"have no CPU route (the dense route, matrix_de_novo, serves another callable)")
+                         f"have no CPU route ({advice})")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError(f"{caller}: the components and groups fills are one-GPU calls; run it in one process, not under a launcher (WORLD_SIZE > 1)")
     import time
@@ -899,6 +871,17 @@ def upload_for_fills(genomes, func, caller, several=False):
     t2 = time.perf_counter()
     logging.debug(f"{caller}: {len(genomes)} genomes: pack {t1 - t0:.3f} s, upload {t2 - t1:.3f} s")
     return ctx, metric, [g.name for g in genomes], dict(pack_s=t1 - t0, upload_s=t2 - t1, genome_pairs=packed.n_pairs, n_gpus=n_gpus)
+
+
+def _record_fill(stats, metric, names, record, t0):
+    """``LAST_FILL`` after the one fill of a route behind ``upload_for_fills(..., several=True)``, begun at ``t0``: its stats, the
+    collection and the upload's record.  Returns ``fill_s``."""
+    import time
+    fill_s = time.perf_counter() - t0
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(names), genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"], rank=0,
+                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
+    return fill_s
 
 
 def _group_indices(names, index, groups):
@@ -1055,10 +1038,7 @@ def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     import time
     t0 = time.perf_counter()
     nbr, val, stats = ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = time.perf_counter() - t0
-    LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(genomes), genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"], rank=0,
-                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
+    fill_s = _record_fill(stats, metric, names, record, t0)
     logging.debug(f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in {stats['n_slabs']} "
                   f"slab(s) on {record['n_gpus']} device(s): fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection "
                   f"{stats.get('ms_select', 0.0):.3f} ms)")

@@ -323,6 +323,35 @@ def test_state_and_loans(ctx, multis, small_packed):
         assert ctx.shard_pairs() == n * (n - 1) // 2 == ctx.shard_stride()
 
 
+def test_each_kind_keeps_its_own_times(ctx, multis, small_packed):
+    """An edge-list, a components and a nearest fill in turn on ONE context, each with stats and over several slabs: afterwards
+    pc_last_edge_times, pc_last_component_times and pc_last_nearest_times each still report exactly the pair their own call's stats
+    carried.  The three calls time their passes with the same events of the context; a later call of another kind must not
+    overwrite an earlier one's times.  The same sequence on two contexts of device 0 gives the single context's results."""
+    slab_bytes = 8 * 40
+    ctx.upload(small_packed)
+
+    def sequence(on):
+        *edges, edge_st = on.fill_edges("jc", 0.75, slab_bytes=slab_bytes, want_stats=True)
+        labels, cc_st = on.fill_components("jc", 0.75, slab_bytes=slab_bytes, want_stats=True)
+        nbr, val, nn_st = on.fill_nearest("jc", 5, slab_bytes=slab_bytes, want_stats=True)
+        assert min(edge_st["n_slabs"], cc_st["n_slabs"], nn_st["n_slabs"]) > 1
+        return (*edges, labels, nbr, val), (edge_st, cc_st, nn_st)
+
+    single, (edge_st, cc_st, nn_st) = sequence(ctx)
+    for call, st, first, second in (("pc_last_edge_times", edge_st, "ms_compact", "ms_d2h"), ("pc_last_component_times", cc_st, "ms_union", "ms_labels"),
+                                    ("pc_last_nearest_times", nn_st, "ms_select", "ms_finish")):
+        a, b = ctypes.c_float(-1.0), ctypes.c_float(-1.0)
+        assert getattr(ctx._lib, call)(ctx._h, ctypes.byref(a), ctypes.byref(b)) == 0, call
+        print(call, a.value, b.value, st[first], st[second])
+        assert (a.value, b.value) == (st[first], st[second]) and a.value > 0.0, call
+    multi = multis(2)
+    multi.upload(small_packed, residues=False)
+    several, _ = sequence(multi)
+    for g, w in zip(several, single):
+        assert g.dtype == w.dtype and np.array_equal(g, w)
+
+
 # ---- refusals --------------------------------------------------------------------------------------------
 def test_refusals_through_the_binding(multis, small_packed):
     from phamclust_amd import hip
