@@ -22,7 +22,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # (PC_MAX_BUILTIN / PC_CELL_ORDER: experiment switches of pc_nw_systolic.h); the product build uses asm maxima and needs no flag.
 NW_FLAGS = []
 # The host side of the C-ABI is six units (pc_ctx, pc_upload, pc_align, pc_fill, pc_fill_slabs, pc_multi; internal header pc_host.h), and
-# pc_set_shape is the host arithmetic of the set metrics, their kernel selector and launch shapes: they hold no device code, so the
+# pc_set_shape is the host arithmetic of the set metrics, their kernel selector and launch shapes, pc_nw_shape that of the alignment
+# kernels (choosers, launch classes, launch shapes; what it shares with the kernels is pc_nw_geometry.h): they hold no device code, so the
 # library's .hip_fatbin comes from the kernel units alone.  Those are, by family (internal header pc_pairs.h): pc_set_popc (popcount tiles), pc_sparse (sparse
 # tiles and their entry lists), pc_sparse_col (the column kernel), pc_walk (the shared-pham walker over both pair domains), pc_util
 # (scan, gather, shard assembly, test probes), pc_edges (the edge-list compaction of pc_fill_edges), pc_components (the union-find of pc_fill_components), pc_nearest (the k-best selection of pc_fill_nearest); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
@@ -31,7 +32,7 @@ HIP_UNITS = [("pc_ctx.hip", "pc_ctx.o", []), ("pc_upload.hip", "pc_upload.o", []
              ("pc_set_popc.hip", "pc_set_popc.o", []), ("pc_sparse.hip", "pc_sparse.o", []), ("pc_sparse_col.hip", "pc_sparse_col.o", []),
              ("pc_set_shape.hip", "pc_set_shape.o", []), ("pc_walk.hip", "pc_walk.o", []), ("pc_util.hip", "pc_util.o", []),
              ("pc_edges.hip", "pc_edges.o", []), ("pc_components.hip", "pc_components.o", []), ("pc_nearest.hip", "pc_nearest.o", []),
-             ("pc_plan.hip", "pc_plan.o", []),
+             ("pc_plan.hip", "pc_plan.o", []), ("pc_nw_shape.hip", "pc_nw_shape.o", []),
              ("pc_nw.hip", "pc_nw.o", NW_FLAGS),
              ("pc_nw_rules.hip", "pc_nw_r23.o", NW_FLAGS + ["-DPC_RULE_A=2", "-DPC_RULE_B=3"]),
              ("pc_nw_rules.hip", "pc_nw_r45.o", NW_FLAGS + ["-DPC_RULE_A=4", "-DPC_RULE_B=5"]),

@@ -62,7 +62,7 @@ static int run_align_classes(pc_ctx* c, const PcTask* task_list, const uint32_t*
     // what does not fit PC_SLAB_BUDGET (3 GB) shares the first region, in order, as before.
     // percent-positives: systolic where the profile cell can run (it reads "positive" from a table), general kernel elsewhere
     auto launch_variant = [&](const Launch& l) { const int v = pc_class_variant(l.base); return (ppos && !pc_nw_ppos_systolic(v, l.max_lb)) ? pc_nw_ppos_variant(l.max_lb) : v; };
-    auto uses_slab = [&](const Launch& l) { const int v = launch_variant(l); return v < 0 || pc_launch_is_strip(v, l.max_lb, l.mode, ppos); };
+    auto uses_slab = [&](const Launch& l) { const int v = launch_variant(l); return v < 0 || pc_nw_launch_is_strip(v, l.max_lb, l.mode, ppos); };
     struct Region { size_t off, bytes; bool own; };
     std::vector<Region> region(launches.size(), Region{0, 0, false});
     static const size_t slab_budget = [] { const char* e = getenv("PC_SLAB_BUDGET"); const long long v = e ? atoll(e) : 0; return v > 0 ? (size_t)v : (size_t)3 << 30; }();
@@ -76,7 +76,7 @@ static int run_align_classes(pc_ctx* c, const PcTask* task_list, const uint32_t*
         for (size_t i = 0; i < launches.size(); ++i) {
             const Launch& l = launches[i];
             const int v = launch_variant(l);
-            if (v < 0 || !pc_launch_is_strip(v, l.max_lb, l.mode, ppos)) continue;
+            if (v < 0 || !pc_nw_launch_is_strip(v, l.max_lb, l.mode, ppos)) continue;
             const size_t need = up256(pc_nw_strip_launch_bytes(l.mode, (int)(l.end - l.begin), c->max_gene_len, c->n_cu, ppos));
             if (!in_line && c->n_streams > 1 && own_total + need <= slab_budget) { region[i] = Region{own_total, need, true}; own_total += need; }
             else shared = std::max(shared, pc_nw_strip_scratch_bytes(c->max_gene_len, c->n_cu));
@@ -780,7 +780,7 @@ extern "C" int pc_align_pairs(pc_ctx* c, const int32_t* a_gene, const int32_t* b
         if (nt <= 0) continue;
         void* scratch = nullptr; size_t sbytes = 0;
         const int base = lc / PC_WAVE_MODES, v = pc_class_variant(base);
-        if (v < 0 || pc_launch_is_strip(v, cls_maxlb[lc], lc % PC_WAVE_MODES, 0)) {
+        if (v < 0 || pc_nw_launch_is_strip(v, cls_maxlb[lc], lc % PC_WAVE_MODES, 0)) {
             sbytes = v < 0 ? pc_nw_fallback_scratch_bytes(cls_maxlb[lc]) : pc_nw_strip_scratch_bytes(c->max_gene_len, c->n_cu);
             if ((rc = c->b_scratch.ensure(sbytes))) return abi_rc(rc);
             scratch = c->b_scratch.p; sbytes = c->b_scratch.cap;

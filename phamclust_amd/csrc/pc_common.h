@@ -213,11 +213,10 @@ int pc_launch_assemble_table(const double* gathered, int64_t stride, int N, cons
 int pc_launch_round6_probe(const double* in, double* out, int64_t n, hipStream_t st);
 int pc_launch_unpack_res(const uint2* res, const int32_t* la_plus_lb, int32_t* n_ident, int32_t* n_diag, int64_t n, hipStream_t st);
 
-// alignment kernels (pc_nw.hip)
+// K4's launch arithmetic (pc_nw_shape.hip: host only, no device code; the geometry it shares with the kernels: pc_nw_geometry.h)
 int pc_nw_num_variants();
 int pc_nw_variant_w(int v);                       // columns per lane of variant v
 int pc_nw_choose_variant(int lb);                 // -1: general fallback
-int pc_nw_g_bucket(int G);                        // lanes-per-segment bucket bound (8, 16, 32, 64) of a launch class
 // compare_only: the launch class is the one for column genes holding a byte outside the 24-letter alphabet, which must run
 // the residue-compare cell (the profile cell keeps ONE row for all such bytes: exact only while the column holds none)
 int pc_nw_class_waves(int variant, int lb, int compare_only);   // waves per workgroup of the launch class a column gene of lb residues falls in
@@ -228,18 +227,43 @@ int pc_nw_ppos_variant(int max_lb);               // the variant to run it on wh
 int pc_nw_choose_remainder(int lb, int r, int main_variant);   // variant for a bucket's last r < nseg rows, -1: keep them
 int pc_nw_task_mode(int lb, int rows, int variant);            // PC_MODE_* of a task of `rows` rows on that variant
 int pc_nw_small_modes_enabled();
-int pc_launch_nw(int variant, const PcDev& d, const PcTask* tasks, int ntasks, const int32_t* bucket_row,
-                 const uint32_t* bucket_dest, uint2* res, void* scratch, size_t scratch_bytes, int max_lb, int ppos, int tie_rule, int compare_only, hipStream_t st,
-                 int wave_mode = 0,    // wave_mode: PC_MODE_* -- workgroup shape of the launch's tasks
-                 int max_row_len = 65535);   // longest row sequence (sizes a strip-mined launch's boundary lines; see pc_nw_strip_scratch_bytes)
 // several launch classes in ONE launch (k_nw_systolic_tier): classes whose pc_nw_fuse_key agrees (and is >= 0) may share it
-#define PC_FUSE_MAX_SEGMENTS 32
-struct PcNwSegment { uint32_t task_begin, ntasks; int variant, max_lb, compare_only, wave_mode; };
 int pc_nw_fuse_key(int variant, int max_lb, int ppos, int compare_only, int wave_mode);
-int pc_launch_nw_group(const PcNwSegment* segs, int nsegs, const PcDev& d, const PcTask* task_list, const int32_t* bucket_row,
-                       const uint32_t* bucket_dest, uint2* res, int ppos, int tie_rule, hipStream_t st);
 size_t pc_nw_strip_scratch_bytes(int max_row_len, int n_cu);    // scratch a strip-mined launch (max_lb > 64 x W of its variant) wants
 size_t pc_nw_strip_launch_bytes(int wave_mode, int ntasks, int max_row_len, int n_cu, int ppos);   // ... and one such launch with a region of its own
 int pc_nw_launch_is_strip(int variant, int max_lb, int wave_mode, int ppos);   // the launch runs on k_nw_strip and needs the scratch slab
 int pc_nw_strip_passes(int lb, int variant);                   // passes of 64 x W columns a column gene of lb residues takes on that variant (1: not strip-mined)
 size_t pc_nw_fallback_scratch_bytes(int max_lb);
+// Shape of ONE systolic or strip-mined launch, as the launchers (pc_nw.hip) take it: the width to instantiate and its cell, waves per
+// workgroup, dynamic LDS; strip: it runs on k_nw_strip, pipe: in the form that deals one alignment's passes over the waves, per_cu:
+// the resident workgroups per CU its scratch is sized for (0: not strip-mined).  ntasks, n_cu: read for strip-mined launches only.
+struct PcLaunchShape { int W, nw; bool inc16, strip, pipe; size_t lds; int per_cu; };
+int pc_nw_launch_shape(int variant, int max_lb, int ppos, int compare_only, int wave_mode, int ntasks, int n_cu, PcLaunchShape& sh);
+
+// The launch classes.  Base class of a column gene: variant * 4 + bucket of lanes per segment (<=8, <=16, <=32, <=64); the same again,
+// nvar * 4 higher, for column genes that hold a byte outside the 24-letter alphabet ("any byte" classes: they must run
+// the residue-compare cell, see above); then one class per wide variant for column genes longer than its 64 x W columns
+// (strip-mined passes, k_nw_strip); last class: the general kernel.
+#define PC_STRIP_CLASSES 3                                 // W = 32, 48, 64: the last three variants
+int pc_num_classes();
+int pc_class_of(int lb, int variant, bool any_byte);
+int pc_class_variant(int cls);
+int pc_class_compare_only(int cls);
+// How a bucket of `rows` distinct rows against a column gene of lb residues is cut into tasks -- the host statement of the cut
+// that pc_plan.hip makes on the device from the upload's tables (q_class, q_nseg, task_rows, rem_class): pc_align_pairs cuts its
+// buckets with it and pc_bucket_launch_classes reports it.  base: the column gene's base class (pc_class_of of its variant);
+// move_remainder: the left-over rows of a wave round may go to the remainder chooser's variant (the automatic variant only).
+struct PcBucketCut { int per; int64_t n_main; int rem_base; };     // rows per main task, rows of the main tasks, base class of the remainder task (-1: none)
+PcBucketCut pc_bucket_cut(int lb, int64_t rows, int base, bool any_byte, bool move_remainder);
+// launch class of a task of `rows` rows of that bucket on base class `base`; modes: 0 = every task in its class's own workgroup shape (a forced variant)
+int pc_task_launch_class(int lb, int rows, int base, bool modes);
+
+// the alignment launchers (pc_nw.hip)
+int pc_launch_nw(int variant, const PcDev& d, const PcTask* tasks, int ntasks, const int32_t* bucket_row,
+                 const uint32_t* bucket_dest, uint2* res, void* scratch, size_t scratch_bytes, int max_lb, int ppos, int tie_rule, int compare_only, hipStream_t st,
+                 int wave_mode = 0,    // wave_mode: PC_MODE_* -- workgroup shape of the launch's tasks
+                 int max_row_len = 65535);   // longest row sequence (sizes a strip-mined launch's boundary lines; see pc_nw_strip_scratch_bytes)
+#define PC_FUSE_MAX_SEGMENTS 32
+struct PcNwSegment { uint32_t task_begin, ntasks; int variant, max_lb, compare_only, wave_mode; };
+int pc_launch_nw_group(const PcNwSegment* segs, int nsegs, const PcDev& d, const PcTask* task_list, const int32_t* bucket_row,
+                       const uint32_t* bucket_dest, uint2* res, int ppos, int tie_rule, hipStream_t st);

@@ -173,11 +173,11 @@ extern "C" int pc_task_shape(int lb, int width, int32_t* out) {
     if (width == 0) v = pc_nw_choose_variant(lb);
     else for (int k = 0; k < pc_nw_num_variants(); ++k) if (pc_nw_variant_w(k) == width) v = k;
     if (v < 0) { pc_set_error("pc_task_shape: no systolic variant for w = %d, %d columns", width, lb); return PC_ERR_ARG; }
-    const int W = pc_nw_variant_w(v), G = (lb + W - 1) / W;
-    const bool strip = G > 64;
+    const int W = pc_nw_variant_w(v);
+    const bool strip = pc_nw_lanes(lb, W) > 64;
     out[0] = pc_nw_task_rows(lb, v, 0);
     out[1] = strip ? out[0] : pc_nw_class_waves(v, lb, 0);                   // strip-mined: one row per wave
-    out[2] = strip ? 1 : std::min(64 / G, 16);                              // (as pc_align_pairs cuts buckets)
+    out[2] = pc_nw_segs(lb, W);                                             // (as pc_align_pairs cuts buckets)
     out[3] = strip ? pc_nw_strip_passes(lb, v) : 0;
     return PC_OK;
 }

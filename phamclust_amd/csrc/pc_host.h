@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pc_common.h"
+#include "pc_nw_geometry.h"
 #include "../../include/phamclust_hip.h"
 
 // roctx range around a stage of a fill (the marker library is looked up in pc_ctx.hip)
@@ -201,51 +202,6 @@ static int mark_work(pc_ctx* c, hipStream_t st) {
     c->busy = true; c->last_stream = st;
     return PC_OK;
 }
-
-// Base class of a column gene: variant * 4 + bucket of lanes per segment (<=8, <=16, <=32, <=64); the same again,
-// nvar * 4 higher, for column genes that hold a byte outside the 24-letter alphabet ("any byte" classes: they must run
-// the residue-compare cell, see pc_common.h); then one class per wide variant for column genes longer than its 64 x W columns
-// (strip-mined passes, k_nw_strip); last class: the general kernel.
-#define PC_STRIP_CLASSES 3                                 // W = 32, 48, 64: the last three variants
-static int pc_num_classes() { return pc_nw_num_variants() * 8 + PC_STRIP_CLASSES + 1; }
-static int pc_class_of(int lb, int variant, bool any_byte) {
-    const int nvar = pc_nw_num_variants();
-    if (variant < 0) return nvar * 8 + PC_STRIP_CLASSES;
-    const int W = pc_nw_variant_w(variant);
-    if (lb > 64 * W) return nvar * 8 + std::max(0, variant - (nvar - PC_STRIP_CLASSES));       // strip-mined (the chooser only picks a wide variant for these)
-    const int Gs = (lb + W - 1) / W;
-    const int Gb = pc_nw_g_bucket(Gs);
-    return variant * 4 + (Gb == 8 ? 0 : Gb == 16 ? 1 : Gb == 32 ? 2 : 3) + (any_byte && !pc_nw_variant_takes_any_byte(variant) ? nvar * 4 : 0);
-}
-static int pc_class_variant(int cls) {
-    const int nvar = pc_nw_num_variants();
-    if (cls >= nvar * 8 + PC_STRIP_CLASSES) return -1;
-    if (cls >= nvar * 8) return nvar - PC_STRIP_CLASSES + (cls - nvar * 8);
-    return (cls % (nvar * 4)) / 4;
-}
-static int pc_class_compare_only(int cls) { const int nvar = pc_nw_num_variants(); return cls >= nvar * 4 && cls < nvar * 8; }
-// How a bucket of `rows` distinct rows against a column gene of lb residues is cut into tasks -- the host statement of the cut
-// that pc_plan.hip makes on the device from the upload's tables (q_class, q_nseg, task_rows, rem_class): pc_align_pairs cuts its
-// buckets with it and pc_bucket_launch_classes reports it.  base: the column gene's base class (pc_class_of of its variant);
-// move_remainder: the left-over rows of a wave round may go to the remainder chooser's variant (the automatic variant only).
-struct PcBucketCut { int per; int64_t n_main; int rem_base; };     // rows per main task, rows of the main tasks, base class of the remainder task (-1: none)
-static PcBucketCut pc_bucket_cut(int lb, int64_t rows, int base, bool any_byte, bool move_remainder) {
-    const int v = pc_class_variant(base);
-    PcBucketCut cut{pc_nw_task_rows(lb, v, pc_class_compare_only(base)), rows, -1};
-    if (move_remainder && v >= 0) {
-        const int W = pc_nw_variant_w(v), G = (lb + W - 1) / W, nseg = std::min(G > 64 ? 1 : 64 / G, 16);
-        const int r = nseg > 1 ? (int)(rows % nseg) : 0;
-        const int vr = r ? pc_nw_choose_remainder(lb, r, v) : -1;
-        if (vr >= 0) { cut.n_main = rows - r; cut.rem_base = pc_class_of(lb, vr, any_byte); }
-    }
-    return cut;
-}
-// launch class of a task of `rows` rows of that bucket on base class `base`; modes: 0 = every task in its class's own workgroup shape (a forced variant)
-static int pc_task_launch_class(int lb, int rows, int base, bool modes) {
-    return base * PC_WAVE_MODES + (modes ? pc_nw_task_mode(lb, rows, pc_class_variant(base)) : (int)PC_MODE_CLASS);
-}
-// a launch whose longest column gene exceeds its variant's 64 x W columns runs strip-mined and needs the scratch slab
-static bool pc_launch_is_strip(int variant, int max_lb, int mode, int ppos) { return pc_nw_launch_is_strip(variant, max_lb, mode, ppos) != 0; }
 
 // A groups fill's domain as the host sees it: the device view, and per row block of TS positions where its tiles and its slots
 // begin (both ascend: a range of row blocks is a range of the tile list and of the slots).

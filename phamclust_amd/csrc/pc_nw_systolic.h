@@ -1,5 +1,5 @@
 // pc_nw_systolic.h -- the systolic alignment kernel (K4) and the launch wrapper its translation units instantiate.
-// Included by pc_nw.hip (tie rules 0 and 1, the general kernel, everything host-side) and by pc_nw_rules.hip, which is
+// Included by pc_nw.hip (tie rules 0 and 1, the general kernel, the launchers) and by pc_nw_rules.hip, which is
 // compiled three times (rules 2-3, 4-5, 6-7): 8 rules x (24 widths + 21 with the profile cell) kernels take ~2 1/4 min in
 // one hipcc process and ~40 s in four.
 #pragma once
@@ -9,6 +9,7 @@
 
 #include "pc_common.h"
 #include "pc_nw_events.h"
+#include "pc_nw_geometry.h"     // the constants and the launch geometry the kernels share with the host's launch arithmetic
 #include "../../include/phamclust_hip.h"
 
 // NCBI BLOSUM62 over ARNDCQEGHILKMFPSTWYVBZX* (SURVEY.md section 8c); codes >= 23 use the '*' row.
@@ -80,8 +81,6 @@ static __constant__ int8_t c_b62[24][24] = {
 // (bytes, so that the row's address is one SDWA add; dwords for W >= 48, whose tables pass 64 KB); each flag is one SDWA compare.
 #define PCF_LAST 0x100
 #define PCF_RESET 0x200
-#define PC_MAX_SEG 16
-#define PC_WIN 32                                   // stream entries staged per refill (one segment per 64-lane pass; 64 was measured: no gain)
 static_assert(PC_WIN == PC_EV_WIN, "pc_nw_events.h schedules the flag events of windows of PC_WIN entries");
 
 // ---------------------------------------------------------------------------------
@@ -268,16 +267,7 @@ __device__ __forceinline__ void pc_cell64(double D, double HoL, double EL, doubl
 
 typedef __attribute__((address_space(3))) const uint32_t pc_lds_u32;
 
-// Every variant up to this W exists twice.  INC16: the statistics' increment comes from a second, 16-bit profile, 10
-// instructions per cell, 3 x the LDS; the other compares residues, 11 instructions.  The launcher picks per launch
-// class (pc_nw_class_inc16): the big profile pays while four waves per SIMD still fit beside it.
-#define PC_INC16_MAX_W 24
-#define PC_INC16_K 0x2000u                           // statistics word: n_ident | n_diag << 13 (both <= lb <= 64 * 24)
-
-__host__ __device__ constexpr int pc_prof_rows(bool inc16) { return inc16 ? 25 : 24; }
-__host__ __device__ constexpr int pc_prof_row_dwords(int W, bool inc16) {   // scores (4 per dword), then increments (2 per dword)
-    return (W + 3) / 4 + (inc16 ? (W + 1) / 2 : 0);
-}
+#define PC_INC16_K 0x2000u                           // profile cell's statistics word: n_ident | n_diag << 13 (both <= lb <= 64 * PC_INC16_MAX_W)
 
 template <int W, int C, int RULE, bool INC16, int POL = PC_POL_NONE>
 struct PcRow {          // compile-time unrolled sweep over the lane's W columns
@@ -302,14 +292,6 @@ struct PcRow {          // compile-time unrolled sweep over the lane's W columns
         else E_out = E;
     }
 };
-
-// Waves per workgroup, sharing one profile: 4, or 8 where the profile of a longer column gene would otherwise leave
-// fewer than four waves per SIMD in the CU's 160 KB of LDS (chosen per launch class by pc_nw_class_waves; the kernel
-// reads it from blockDim).  16-wave workgroups were tried for segments of 64 lanes: one workgroup per CU, 5-10 % slower
-// than the residue-compare cell with its small profile, which those classes run instead.
-#define PC_MIN_WAVES 4
-__host__ __device__ constexpr int pc_max_waves(int W) { return W <= 24 ? 8 : 4; }
-__host__ __device__ constexpr int pc_wave_lds_dwords(int nseg) { return 4 * 64 + 2 * PC_MAX_SEG + nseg * PC_WIN; }   // private LDS of a wave with nseg row streams
 
 __device__ __forceinline__ void pc_wave_lds_sync() {        // LDS write -> read inside ONE wave (in-order LDS queue)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -384,7 +366,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
     const int nseg = min(64 / G, PC_MAX_SEG);
     const int NS = NWV * nseg;                      // row slots of the workgroup
     // LDS: score table | the waves' private regions (sized by nseg) | the shared profile
-    uint32_t* wreg = smem + 144 + wv * pc_wave_lds_dwords(nseg);
+    uint32_t* wreg = smem + PC_WG_HEADER_DWORDS + wv * pc_wave_lds_dwords(nseg);
     uint32_t* row_la = wreg;                                         // [64] this wave's rows: length
     uint32_t* row_pos = row_la + 64;                                 // [64] start of the row's record in its segment's stream
     uint32_t* row_lo = row_pos + 64;                                 // [64] code offset, low / high dword
@@ -392,7 +374,7 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
     uint32_t* seg_len = row_hi + 64;                                 // [16] stream length per segment
     uint32_t* seg_cur = seg_len + PC_MAX_SEG;                        // [16] local row whose record holds the window start
     uint32_t* ring = seg_cur + PC_MAX_SEG;                           // [nseg][PC_WIN] staged stream entries
-    uint32_t* prof = smem + 144 + NWV * pc_wave_lds_dwords(nseg);
+    uint32_t* prof = smem + PC_WG_HEADER_DWORDS + NWV * pc_wave_lds_dwords(nseg);
     const int seg = lane / G, k = lane - seg * G;
     const bool in_seg = seg < nseg;
     const bool is_head = in_seg && k == 0;
@@ -667,10 +649,6 @@ __device__ __forceinline__ void pc_nw_body(const PcDev& d, const PcTask* __restr
 // Limits: statistics are 16-bit fields (compare cell: la, lb <= 65,535) or 13-bit ones (profile cell, used for percent-positives:
 // lb <= 8,191).
 // ---------------------------------------------------------------------------------
-#define PC_STRIP_WAVES 4                                           // most waves per workgroup = rows per task (one row per wave)
-#define PC_STRIP_WIN 32                                            // stream entries a strip wave stages per refill (the idle half of the wave stages the boundary line: fixed)
-#define PC_STRIP_BND 64                                            // boundary entries a wave keeps staged (two refill windows)
-__host__ __device__ constexpr int pc_strip_wave_lds_dwords() { return 16 + PC_STRIP_WIN + 4 * PC_STRIP_BND; }
 
 // PIPE (r04, second form): the passes of ONE alignment spread over the workgroup's waves.  Wave w takes passes w, w + NWV, ... of the
 // task's rows, one row after the other; each wave builds the profile of its own pass (private LDS), writes its boundary line as
@@ -682,7 +660,6 @@ __host__ __device__ constexpr int pc_strip_wave_lds_dwords() { return 16 + PC_ST
 // its SIMD it issues an instruction every ~12 clocks -- and a collection's few such alignments were the critical path of small
 // fills (synth_real(1000): 58 ms for 4.0e10 cells); over eight waves it takes an eighth.  Launches with many tasks keep the
 // one-row-per-wave form above, which holds more waves per CU.
-#define PC_PIPE_WAVES_MAX 8
 template <int W, int RULE, bool INC16, bool PIPE = false>
 __global__ __launch_bounds__(64 * (PIPE ? PC_PIPE_WAVES_MAX : PC_STRIP_WAVES), (W == 48 ? 2 : 1)) void k_nw_strip(PcDev d, const PcTask* __restrict__ tasks, int ntasks,
                                                                           const int32_t* __restrict__ bucket_row,
@@ -705,11 +682,11 @@ __global__ __launch_bounds__(64 * (PIPE ? PC_PIPE_WAVES_MAX : PC_STRIP_WAVES), (
     constexpr int Gl = INC16 ? 32 : 64;
     constexpr uint32_t half_dw = INC16 ? (uint32_t)(((ROWS + 1) / 2) * RS * 64) : 0u;
     auto row_part = [&](uint32_t r) { return (INC16 ? ((r >> 1) * (uint32_t)(RS * 64) + (r & 1u) * 32u) : r * (uint32_t)(RS * 64)) * (BYTE_OFF ? 4u : 1u); };
-    uint32_t* wreg = smem + 144 + wv * pc_strip_wave_lds_dwords();
+    uint32_t* wreg = smem + PC_WG_HEADER_DWORDS + wv * pc_strip_wave_lds_dwords();
     uint32_t* ring = wreg + 16;                                    // [PC_STRIP_WIN] staged stream entries
     uint32_t* bnd = ring + PC_STRIP_WIN;                                 // [PC_STRIP_BND][4] staged boundary entries (Ho.hi, Ho.lo, E.hi, E.lo)
     constexpr int PROF_DW = (INC16 ? 2 * ((ROWS + 1) / 2) : ROWS) * RS * 64;     // one profile (PIPE: one per wave)
-    uint32_t* prof = smem + 144 + NWV * pc_strip_wave_lds_dwords() + (PIPE ? wv * PROF_DW : 0);
+    uint32_t* prof = smem + PC_WG_HEADER_DWORDS + NWV * pc_strip_wave_lds_dwords() + (PIPE ? wv * PROF_DW : 0);
     // PIPE: word 0 of a wave's region = its progress (passes done << 17 | row steps done of the pass it is in).  Written with a
     // workgroup-scope RELEASE store and read with an ACQUIRE load (r05): the order "boundary entries, then the word that announces
     // them" is stated in the memory model, not only in the instruction stream.  What the model does not promise at that scope is that
@@ -719,7 +696,7 @@ __global__ __launch_bounds__(64 * (PIPE ? PC_PIPE_WAVES_MAX : PC_STRIP_WAVES), (
     // before a progress store is vmcnt(0).  (An agent-scope release would write the L2 back, every 32 steps.)
     typedef __attribute__((address_space(3))) uint32_t pc_lds_w32;           // (LDS-typed: ds_write / ds_read, not flat accesses)
     pc_lds_w32* const prog_me = (pc_lds_w32*)(size_t)(pc_lds_w32*)wreg;
-    pc_lds_w32* const prog_prev = (pc_lds_w32*)(size_t)(pc_lds_w32*)(smem + 144 + ((wv + NWV - 1) % NWV) * pc_strip_wave_lds_dwords());
+    pc_lds_w32* const prog_prev = (pc_lds_w32*)(size_t)(pc_lds_w32*)(smem + PC_WG_HEADER_DWORDS + ((wv + NWV - 1) % NWV) * pc_strip_wave_lds_dwords());
     auto publish = [&](uint32_t value) {
         asm volatile("s_waitcnt vmcnt(0) ; pc_publish: boundary entries before the progress word" ::: "memory");
         if (lane == 0) __hip_atomic_store(prog_me, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -982,11 +959,6 @@ int pc_strip_launch(unsigned nblocks, int nw, size_t lds, hipStream_t st, const 
     return (int)hipGetLastError();
 }
 #define PC_STRIP_SIG (unsigned, int, size_t, hipStream_t, const PcDev&, const PcTask*, int, const int32_t*, const uint32_t*, uint2*, int, uint4*, unsigned)
-// the strip-mined kernel's widths: the wide variants for tasks of 3-4 rows (four waves share the profile of a pass), W = 12 / W = 8
-// for tasks of two rows / one row -- the profile of a pass is 24 x W x 64 bytes of LDS PER COLUMN GENE, 49 KB at W = 32: with one
-// row to align against it a CU would hold three waves; at W = 8 it holds twelve, for 9 % more instructions per cell
-#define PC_STRIP_W_ONE_ROW 8
-#define PC_STRIP_W_TWO_ROWS 12
 
 // ---- kernels over the body -------------------------------------------------------------------------------------
 // (second launch bound = waves per SIMD the compiler must leave room for: W = 48 needs 257 registers left to itself, one more
@@ -1007,7 +979,7 @@ __global__ __launch_bounds__(64 * pc_max_waves(W), (W == 48 ? 2 : 1)) void k_nw_
 // the same registers -- the same waves per SIMD -- so their bodies share one kernel at no cost in occupancy; a launch then
 // holds the tasks of ~20 classes (its SEGMENTS: a block range each, with the variant that runs it), far more than the chip
 // holds at once, and only the last launches of a fill have a tail.  LDS and workgroup size are the launch's: the segments of a
-// launch agree on waves per workgroup, and the dynamic LDS is the largest any of them needs (pc_nw.hip groups them so that
+// launch agree on waves per workgroup, and the dynamic LDS is the largest any of them needs (pc_nw_fuse_key groups them so that
 // this stays within what the tier's register budget lets a CU hold anyway).
 #define PC_FUSE_MAX_SEG PC_FUSE_MAX_SEGMENTS
 struct PcFuseArgs {
@@ -1016,9 +988,6 @@ struct PcFuseArgs {
     uint32_t task_begin[PC_FUSE_MAX_SEG];             // ... which are tasks task_begin[i] + (block - block_end[i-1])
     int32_t w[PC_FUSE_MAX_SEG];                       // ... run by the body of this many columns per lane
 };
-// tiers by registers (waves per SIMD): 2..8 (<= 72: seven or more), 9..12 (<= 92: five), 13..19 (<= 128: four), 20..24 (<= 152: three)
-#define PC_NUM_TIERS 4
-__host__ __device__ constexpr int pc_tier_of(int W) { return W <= 8 ? 0 : W <= 12 ? 1 : W <= 19 ? 2 : W <= 24 ? 3 : -1; }
 
 // (second launch bound: the waves per SIMD the tier's widest body reaches on its own -- bundled, tier 2's profile-cell kernel
 // came out at 130 registers, two past the 128 of four waves per SIMD)

@@ -18,6 +18,7 @@
 
 #include "../../include/phamclust_hip.h"
 #include "pc_common.h"
+#include "pc_nw_geometry.h"
 
 size_t pc_sort_temp_bytes(int64_t n, int bits) {
     size_t bytes = 0;
@@ -126,9 +127,8 @@ __device__ __forceinline__ int32_t pc_launch_class(const PcTaskPlan& tp, uint32_
     int mode = PC_MODE_CLASS;
     const uint32_t nv4 = (uint32_t)tp.nvar * 4u;
     if (tp.small_modes && base_cls < 2u * nv4 + (uint32_t)tp.n_strip) {     // (the last base class is the general kernel: no modes)
-        const int W = base_cls < 2u * nv4 ? tp.variant_w[(base_cls % nv4) / 4u] : 64, G = (lb + W - 1) / W;   // (strip-mined classes: one row per wave)
-        const uint32_t nseg = base_cls < 2u * nv4 ? (uint32_t)min(G > 64 ? 1 : 64 / G, 16) : 1u;
-        mode = rows <= nseg ? PC_MODE_ONE_WAVE : rows <= 2u * nseg ? PC_MODE_TWO_WAVES : PC_MODE_CLASS;
+        const uint32_t nseg = base_cls < 2u * nv4 ? (uint32_t)pc_nw_segs(lb, tp.variant_w[(base_cls % nv4) / 4u]) : 1u;   // (strip-mined classes: one row per wave)
+        mode = pc_nw_mode_of(rows, nseg);
     }
     return (int32_t)(base_cls * PC_WAVE_MODES + (uint32_t)mode);
 }

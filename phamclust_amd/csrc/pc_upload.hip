@@ -401,7 +401,7 @@ static int upload_residues(pc_ctx* c, const pc_packed* g) {
         }
         // A column sequence with a byte outside the alphabet goes to its variant's "any byte" class: the profile cell
         // takes "identical residues" from a profile row per alphabet letter plus ONE row for every other byte
-        // (pc_nw.hip, PC_INC16_MAX_W), which is exact only while the column holds none of those (as a row, it is fine)
+        // (pc_nw_geometry.h, PC_INC16_MAX_W), which is exact only while the column holds none of those (as a row, it is fine)
         u_cls[u] = godd[u_gene[u]] ? pc_class_of(len, len_var[len], true) : len_cls[len]; ++cls_count[u_cls[u]];
     }
     lap("  classes per sequence");
@@ -422,8 +422,7 @@ static int upload_residues(pc_ctx* c, const pc_packed* g) {
         for (int64_t len = l0 + 1; len <= l1; ++len) {
             const int v = len_var[len];
             if (len_cls[len] < 0 || v < 0) continue;
-            const int Wv = pc_nw_variant_w(v), Gv = ((int)len + Wv - 1) / Wv;
-            const int nseg = std::max(1, std::min(64 / Gv, 16));        // (Gv > 64: a strip-mined gene, one row per wave)
+            const int nseg = pc_nw_segs((int)len, pc_nw_variant_w(v));  // (a strip-mined gene: one row per wave)
             len_nseg[len] = (uint8_t)nseg;
             for (int r = 1; r < nseg; ++r) {
                 const int vr = pc_nw_choose_remainder((int)len, r, v);

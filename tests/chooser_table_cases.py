@@ -1,4 +1,4 @@
-"""A brute-force mirror in Python of the choosers of pc_nw.hip (variant, cell, remainder) and of its launch arithmetic, reading the
+"""A brute-force mirror in Python of the choosers of pc_nw_shape.hip (variant, cell, remainder) and of its launch arithmetic, reading the
 same numbers the library was compiled with from profiles/r10/class_rates.json (no GPU call here).  tests/test_chooser_table_host.py
 holds the library to it for every column length; tests/test_gpu_chooser_refit.py takes from it the lengths at which the table moved
 a choice.

@@ -1,4 +1,4 @@
-"""The variant, cell and remainder choosers of pc_nw.hip against the rate table they were compiled with (pc_nw_rates.h, written from
+"""The variant, cell and remainder choosers of pc_nw_shape.hip against the rate table they were compiled with (pc_nw_rates.h, written from
 profiles/r10/class_rates.json): for every column length 1 ... 1,536, through Context.task_shape and bucket_launch_classes, no GPU.
 
 * the chosen class is launchable: at most 64 lanes per segment, the LDS launch_shape asks for at most a CU's 160 KB in every

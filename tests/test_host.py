@@ -320,7 +320,7 @@ def test_task_shape_and_percent_positives_route(native_built):
 
 def test_bucket_launch_classes_hook(native_built):
     """pc_bucket_launch_classes, the host cut of one bucket (no GPU call): task size, rows kept by the main variant and the
-    launch classes of a full, a last and a remainder task, at shapes worked out by hand from pc_nw.hip; pc_last_plan_tasks
+    launch classes of a full, a last and a remainder task, at shapes worked out by hand from pc_nw_shape.hip; pc_last_plan_tasks
     refuses a NULL context."""
     from phamclust_amd import hip
     C = hip.Context

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Serialised per-class rates of the K4 systolic variants, the record the choosers of pc_nw.hip read.
+"""Serialised per-class rates of the K4 systolic variants, the record the choosers of pc_nw_shape.hip read.
 
     python tools/class_rates.py --out profiles/r10/class_rates.json          (on the GPU: measure)
     python tools/class_rates.py --fill-ab label=file.json ... --out ...      (add whole-fill bench lines to the record)
@@ -11,7 +11,7 @@ modes) and the cell through PC_INC16 (read once: a child process per cell; 2 = t
 holds its profile, segments of 64 lanes included).  A run is as many calls as sum to 50 ms of kernel time (pc_last_align_ms);
 a point is three runs: mean and largest distance from the mean.
 
-Grid: per length every variant whose cost under the model (pc_nw.hip, model_step: the r01-r04 fit) is within 20 % of the
+Grid: per length every variant whose cost under the model (pc_nw_shape.hip, model_step: the r01-r04 fit) is within 20 % of the
 cheapest, plus the chooser's; both cells where compiled and the LDS arithmetic of waves_for allows.
 """
 import argparse
@@ -29,7 +29,7 @@ VARIANTS = [2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 
 INC16_MAX_W, MAX_SEG, WIN = 24, 16, 32
 
 
-# ---- host arithmetic of pc_nw.hip, mirrored --------------------------------------------------------------------
+# ---- host arithmetic of pc_nw_shape.hip, mirrored --------------------------------------------------------------------
 def nseg_of(G):
     return min(64 // G, MAX_SEG)
 
