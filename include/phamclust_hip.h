@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 160   /* 0.5.9: pc_multi_fill_edges / _components / _nearest, pc_stretch_plan */
+#define PC_VERSION 161   /* 0.5.10: pc_fill_tree / pc_multi_fill_tree, pc_tree_key */
 
 typedef enum {
     PC_OK = 0,
@@ -312,6 +312,53 @@ int pc_fill_nearest(pc_ctx* ctx, int metric, int as_distance, int k, int64_t sla
  * passes summed over its slabs, *ms_finish the finishing pass; either pointer may be NULL. */
 int pc_last_nearest_times(const pc_ctx* ctx, float* ms_select, float* ms_finish);
 
+/*
+ * Tree fill: the single-linkage dendrogram, without the dense matrix and without a threshold -- the one delivery form that answers
+ * every threshold at once.  The reference computes it from its dense matrix (scipy.cluster.hierarchy.linkage(..., 'single') in
+ * _get_tree_order, matrix.py:673-686; AgglomerativeClustering(linkage="single"), clustering.py:4-51).  The dendrogram of single
+ * linkage is the minimum spanning tree of the complete graph over the genomes: N - 1 edges, from which the clusters at any
+ * threshold (strict or not), the clusters for any cluster count, the linkage matrix and the leaf order follow on the host.
+ * ONE total order on the pairs (s, t), s < t: the better value first -- the smaller on a distance fill (as_distance != 0), the larger
+ * on a similarity fill; a plain f64 compare on the delivered, already round(x, 6) value -- among equal values the smaller t, then the
+ * smaller s (the order of pc_fill_edges' list).  The result is the unique spanning tree Kruskal's algorithm accepts when it takes the
+ * pairs in that order: *n_edges = N - 1 edges src[i] < tgt[i] with val[i], delivered ASCENDING in that order -- the merge order of
+ * single linkage (on a similarity fill: the maximum spanning tree).  The order is strict, so the tree is canonical: it depends
+ * neither on the slab cut, nor on the number of devices, nor on how any race resolved.  Values are the whole fill's, bit for bit,
+ * each pair in the whole fill's orientation.  The six metrics and PC_AAI_PPOS.
+ * The key.  Every delivered value is k / 10^6 for an integer 0 <= k <= 10^6 (the map is an order-preserving bijection), so the order
+ * fits one word: key = micro << 44 | t << 22 | s, micro = k on a distance fill and 10^6 - k on a similarity fill, k = rint(v * 1e6);
+ * 20 + 22 + 22 bits, hence PC_TREE_MAX_GENOMES.  ~0 is no key (its value field is above 10^6).  One unsigned 64-bit minimum is the
+ * minimum of the total order, and a forest is an array of keys.  pc_tree_key packs a key and pc_tree_key_parts unpacks one (PC_ERR_ARG
+ * for a word that is no key: micro > 10^6 or s >= t; host arithmetic, no GPU, exported for tests as pc_chunk_plan is).  The pass over a
+ * slab checks what the key relies on -- 0 <= k <= 10^6 and k / 10^6 == v, bit for bit -- and counts violations: PC_ERR_DATA.
+ * Same walk as pc_fill_edges: the same slab cut (pc_chunk_plan over count[t] = t, slab_bytes / 8 pairs, <= 2^31-1; 0 = automatic),
+ * each slab filled as a shard into the resident slab buffer.  MST(A + B) = MST(MST(A) + B): a forest of at most N - 1 keys stays on
+ * the device across the slabs, and per slab Boruvka rounds run over that forest and the slab (ceil(log2 N) rounds are enqueued; a
+ * round returns at once when the one before it joined nothing).  Nothing is read back per slab; after the last one the N - 1 keys
+ * and the violation count are copied once, sorted and decoded on the host (val = k / 1000000.0).  Consequences as for pc_fill_edges:
+ * aai / peq merge duplicate sequence pairs per slab only; pc_last_set_kernel, pc_last_set_launch and pc_last_plan_tasks describe the
+ * LAST slab's fill.  The caller's unsharded state is back in force when the call returns, whatever it returns.
+ * *src, *tgt and *val point into page-locked memory the context owns (pc_fill_borrow's loan rule); *n_slabs and stats as pc_fill_edges
+ * gives them -- the fills' stats summed; the rounds are not in them: pc_last_tree_times.
+ * PC_OK also for N <= 1, with *n_edges = 0.  PC_ERR_ARG: bad metric, negative slab_bytes, a NULL out pointer.  PC_ERR_LIMIT: N above
+ * PC_TREE_MAX_GENOMES.  PC_ERR_STATE: before upload, on a sharded context (world != 1: several GPUs share the walk through
+ * pc_multi_fill_tree), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill, and a slab value outside the key's
+ * domain.  On a refusal *src, *tgt and *val are NULL and the counts are 0.  Runs on the context's own stream and returns with
+ * everything finished.
+ */
+#define PC_TREE_MAX_GENOMES (1 << 22)
+int pc_fill_tree(pc_ctx* ctx, int metric, int as_distance, int64_t slab_bytes,
+                 const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook, of the last pc_fill_tree call: *ms_rounds the Boruvka rounds summed over its slabs (HIP events; 0 unless the
+ * call was given stats), *ms_finish the copy of the keys, their sort and their decoding (host wall clock); either pointer may be NULL. */
+int pc_last_tree_times(const pc_ctx* ctx, float* ms_rounds, float* ms_finish);
+/* ... *live_rounds the rounds that did work (the round before them joined something, or they were a slab's first) and
+ * *launched_rounds the rounds enqueued, both summed over the slabs; live <= launched = slabs with pairs x ceil(log2 N).  Either
+ * pointer may be NULL. */
+int pc_last_tree_rounds(const pc_ctx* ctx, int32_t* live_rounds, int32_t* launched_rounds);
+uint64_t pc_tree_key(int32_t micro, int32_t s, int32_t t);
+int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
+
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */
 int pc_assemble_dev(pc_ctx* ctx, const void* gathered_dev, int world, void* out_condensed_dev, void* stream);
@@ -405,6 +452,12 @@ int pc_multi_fill_components(pc_multi* m, int metric, int as_distance, double th
                              const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
 int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, int k, int64_t slab_bytes,
                           const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats);
+/* pc_fill_tree over the devices of `m`, on the same terms and with the same deal.  MST(A + B) = MST(MST(A) + MST(B)): every device
+ * builds the forest of its stretch and ships its keys and their count once, 8 N + 16 bytes, into a staging slice on the root; the root
+ * runs Boruvka rounds over its own forest and the staged ones (lists of keys only, no slab), then finishes as the single-context call
+ * does.  pc_multi_last_slab_times: the slowest device's copy and the root's merge rounds. */
+int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int64_t slab_bytes,
+                       const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats);
 int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds /* pc_multi_devices(m) + 1 entries */);
 int pc_multi_last_slab_times(const pc_multi* m, float* ms_exchange, float* ms_merge);
 /* The stretch deal itself, host arithmetic only (no GPU, no context; exported for tests as pc_chunk_plan is): bounds[world + 1] with

@@ -63,6 +63,10 @@ _OPTIONS = (
     (None, "-K", "--nearest", dict(type=int, default=None, help="stop after the matrix stage and write only nearest_<metric>.tsv, from a nearest-neighbours "
                                                                "fill: each genome's K most similar genomes (1..64), most similar first; no matrix, "
                                                                "no threshold, no clustering; with --gpus N the fill is spread over N GPUs of this process")),
+    (None, "-T", "--tree", dict(action="store_true", help="stop after the matrix stage and write only tree_<metric>.tsv, from a tree fill: the "
+                                                          "single-linkage dendrogram as N-1 lines source<TAB>target<TAB>similarity in merge "
+                                                          "order, from which the clusters at every threshold follow; no matrix, no threshold, no "
+                                                          "clustering; with --gpus N the devices of this process share the fill")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -72,7 +76,7 @@ _OPTIONS = (
                                                                "with --gpus N the ranks take devices 0..N-1")),
     (None, "-G", "--gpus", dict(type=int, default=GPUS, help="GPUs of this node to spread the matrix fill over (one process per GPU "
                                                               "under torch.distributed.run, static pair shard, one RCCL gather); "
-                                                              "--adjacency-only, --components-only and --nearest spread over them "
+                                                              "--adjacency-only, --components-only, --nearest and --tree spread over them "
                                                               "from one process, a stretch of target genomes per GPU")),
 )
 DEFAULTS = {long.lstrip("-").replace("-", "_"): kw.get("default", False) for _, _, long, kw in _OPTIONS}
@@ -114,6 +118,11 @@ def parse_args(argv=None):
                             ("--extend", args.extend is not None)):
             if given:
                 parser.error(f"--nearest stops after a nearest-neighbours fill of its own; it cannot be combined with {flag}")
+    if args.tree:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--no-matrix", args.no_matrix),
+                            ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
+            if given:
+                parser.error(f"--tree stops after a tree fill of its own; it cannot be combined with {flag}")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

@@ -78,7 +78,8 @@ def hierarchical_clustering_de_novo(genomes, func, linkage, eps=None, cpus=1, n_
     groups fill's stats (``genome_pairs`` = the pairs it filled, ``groups``) beside ``n_components`` / ``n_edges`` / ``n_slabs`` /
     ``ms_components`` of the components fill."""
     if n_clusters:
-        raise ValueError("hierarchical_clustering_de_novo cuts at a distance threshold: n_clusters needs the whole dendrogram (the dense route)")
+        raise ValueError("hierarchical_clustering_de_novo cuts at a distance threshold: n_clusters needs the whole dendrogram (the dense route, or "
+                         "for single linkage tree_de_novo(...).cut_n)")
     if linkage == "ward":
         raise ValueError("hierarchical_clustering_de_novo: ward's merge height is not bounded below by a pair distance (the dense route serves it)")
     if eps is None:

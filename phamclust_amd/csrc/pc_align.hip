@@ -205,6 +205,21 @@ extern "C" int pc_chunk_plan(const uint64_t* count, int n, uint64_t max_per_chun
     return nch;
 }
 
+// The tree fill's key (the C-ABI header states it), host arithmetic as the rule above: packed and unpacked for callers and tests.
+extern "C" uint64_t pc_tree_key(int32_t micro, int32_t s, int32_t t) {
+    if (micro < 0 || micro > PC_TREE_MICRO_MAX || s < 0 || t <= s || t >= PC_TREE_MAX_GENOMES) return (uint64_t)PC_TREE_NONE;
+    return (uint64_t)pc_tree_key_of(micro, s, t);
+}
+extern "C" int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t) {
+    const int m = pc_tree_key_micro(key), ks = pc_tree_key_s(key), kt = pc_tree_key_t(key);
+    const bool ok = m <= PC_TREE_MICRO_MAX && ks < kt;
+    if (micro) *micro = ok ? m : -1;
+    if (s) *s = ok ? ks : -1;
+    if (t) *t = ok ? kt : -1;
+    if (!ok) { pc_set_error("pc_tree_key_parts: %llx is no key", (unsigned long long)key); return PC_ERR_ARG; }
+    return PC_OK;
+}
+
 extern "C" int pc_set_plan_budget(pc_ctx* c, int64_t bytes) {
     if (!c || bytes < 0) { pc_set_error("pc_set_plan_budget: bad argument"); return PC_ERR_ARG; }
     c->plan_budget = bytes;

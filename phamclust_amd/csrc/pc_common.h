@@ -187,6 +187,34 @@ int pc_launch_nn_select(const double* vals, int64_t Lp, int t0, int t1, int as_d
 int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st);
 // the lists of other devices merged into key / nbr [N][K] (pc_multi_fill_nearest): fkey / fnbr [n_foreign][N][K], in key space
 int pc_launch_nn_merge(unsigned long long* key, int32_t* nbr, const unsigned long long* fkey, const int32_t* fnbr, int n_foreign, int N, int K, hipStream_t st);
+// single-linkage tree of a filled slab (pc_tree.hip).  A pair's place in the total order is one word (the C-ABI header states it):
+// key = micro << 44 | t << 22 | s, PC_TREE_NONE is no key.  A forest ("list") is u64[N + PC_TREE_TAIL]: at most N - 1 keys, then from
+// word N - 1 its three tail words -- the number of keys, the values found outside the key's domain, the rounds that did work.
+#define PC_TREE_NONE (~0ull)
+#define PC_TREE_MICRO_MAX 1000000
+#define PC_TREE_TAIL 2                             // words a list holds beyond its N: [N - 1] count, [N] violations, [N + 1] live rounds
+__host__ __device__ inline unsigned long long pc_tree_key_of(int micro, int s, int t) {
+    return ((unsigned long long)(uint32_t)micro << 44) | ((unsigned long long)(uint32_t)t << 22) | (unsigned long long)(uint32_t)s;
+}
+__host__ __device__ inline int pc_tree_key_micro(unsigned long long key) { return (int)(key >> 44); }
+__host__ __device__ inline int pc_tree_key_t(unsigned long long key) { return (int)((key >> 22) & 0x3fffffu); }
+__host__ __device__ inline int pc_tree_key_s(unsigned long long key) { return (int)(key & 0x3fffffu); }
+int pc_tree_round_count(int n);                    // rounds enqueued per pass: max(1, ceil(log2 n))
+// `out` takes over `in`'s violation and round counts (in == NULL: zeros) and is emptied; comp / best / live set for a pass's first round
+int pc_launch_tree_reset(int32_t* comp, unsigned long long* best, uint32_t* live, int rounds, const unsigned long long* in,
+                         unsigned long long* out, int n, hipStream_t st);
+// the counts of n_foreign staged lists (each n + PC_TREE_TAIL words) added to `out`'s
+int pc_launch_tree_take_counts(unsigned long long* out, const unsigned long long* lists, int n_foreign, int n, hipStream_t st);
+// round r of a pass, in four steps: the slab's pairs and any number of lists lower best[], the roots hook and append to `out`, comp[] is
+// flattened and best[] reset.  live: [rounds + 1]
+int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, const PcShard& sh, const int32_t* comp, unsigned long long* best,
+                             unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st);
+int pc_launch_tree_scan_list(const unsigned long long* list, const int32_t* comp, unsigned long long* best, int n, const uint32_t* live, int r,
+                             hipStream_t st);
+int pc_launch_tree_hook(const int32_t* comp, int32_t* next, const unsigned long long* best, unsigned long long* out, int n, uint32_t* live, int r,
+                        hipStream_t st);
+int pc_launch_tree_flatten(int32_t* comp, const int32_t* next, unsigned long long* best, unsigned long long* out, int n, const uint32_t* live, int r,
+                           hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

@@ -1,7 +1,8 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
-// pc_last_nearest_times.  Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill: begin, slab, end, and what several
+// pc_last_nearest_times, and pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds.
+// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill: begin, slab, end, and what several
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
 // fills a PcSlabRun, calls the driver and copies the results out.  Host only.
@@ -40,6 +41,10 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         if (run.k < 1) { pc_set_error("%s: k %d", who, run.k); return PC_ERR_ARG; }
         if (run.k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, run.k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
         run.kk = std::max(std::min(run.k, c->dev.N - 1), 0);
+    }
+    if (run.kind == PC_SLAB_TREE && c->dev.N > PC_TREE_MAX_GENOMES) {
+        pc_set_error("%s: %d genomes are above PC_TREE_MAX_GENOMES = %d", who, c->dev.N, PC_TREE_MAX_GENOMES);
+        return PC_ERR_LIMIT;
     }
     if (!run.outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
     if (run.threshold != run.threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
@@ -144,9 +149,11 @@ template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run) {
 template int pc_slab_fill<PcEdgesFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_fill<PcComponentsFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_fill<PcNearestFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_fill<PcTreeFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_stretch<PcEdgesFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcComponentsFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcNearestFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_stretch<PcTreeFill>(pc_ctx*, PcSlabRun&, int, int);
 
 // ---- what the descriptions share ----
 // begin, ahead of anything of the fill's own: the run and the fill's two times (last_ms) reset, the loan of an earlier call ended (its
@@ -472,4 +479,133 @@ extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, in
 
 extern "C" int pc_last_nearest_times(const pc_ctx* c, float* ms_select, float* ms_finish) {
     return last_times(c, "pc_last_nearest_times", c ? c->last_nn_ms : nullptr, ms_select, ms_finish);
+}
+
+// ---- tree fill: the single-linkage dendrogram as the N - 1 edges of the minimum spanning tree under the one total order (value, better
+// first; then t; then s), delivered in that order -- the merge order.  Each filled slab goes through one PASS of Boruvka rounds
+// (pc_tree.hip) over the resident forest and the slab, into the context's second list; then the lists swap.  The forest, a list of keys
+// with its counters behind them, stays on the device from the first slab to the last; nothing is read back per slab.  After the last
+// slab: one D2H of the list, then the host sorts the keys and decodes them into the pinned result.
+static size_t tree_list_words(const pc_ctx* c) { return (size_t)std::max(c->dev.N, 1) + PC_TREE_TAIL; }
+static unsigned long long* tree_list(const pc_ctx* c, int which) { return c->b_tree_list.as<unsigned long long>() + (size_t)which * tree_list_words(c); }
+
+int PcTreeFill::begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    const size_t words = tree_list_words(c);
+    run.tree_launched = 0;
+    c->last_tree_rounds[0] = c->last_tree_rounds[1] = 0; c->tree_cur = 0;
+    if ((rc = slab_begin(c, run, c->last_tree_ms)) || (rc = c->h_tree.ensure((size_t)std::max(N, 1) * 16)) || (rc = c->h_tree_keys.ensure(words * 8))) return rc;
+    if (N <= 1) return PC_OK;
+    if ((rc = slab_size(c, run))) return rc;
+    if ((rc = c->b_tree_comp.ensure((size_t)N * 8)) || (rc = c->b_tree_best.ensure((size_t)N * 8)) || (rc = c->b_tree_list.ensure(words * 16)) ||
+        (rc = c->b_tree_live.ensure(((size_t)pc_tree_round_count(N) + 1) * 4))) return abi_rc(rc);
+    PC_HIP(hipMemsetAsync(tree_list(c, 0) + (N - 1), 0, 24, c->stream));       // the empty forest: no key, no violation, no round
+    return PC_OK;
+}
+// One pass: the resident forest, the slab (slab != NULL) and n_foreign staged lists into the other list, which becomes the resident one.
+static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard* shard, const unsigned long long* foreign, int n_foreign,
+                     hipStream_t st) {
+    int rc = PC_OK;
+    const int N = c->dev.N, rounds = pc_tree_round_count(N);
+    const size_t words = tree_list_words(c);
+    int32_t* const comp = c->b_tree_comp.as<int32_t>(); int32_t* const next = comp + N;
+    unsigned long long* const best = c->b_tree_best.as<unsigned long long>();
+    uint32_t* const live = c->b_tree_live.as<uint32_t>();
+    const unsigned long long* const kept = tree_list(c, c->tree_cur);
+    unsigned long long* const out = tree_list(c, c->tree_cur ^ 1);
+    if ((rc = pc_launch_tree_reset(comp, best, live, rounds, kept, out, N, st)) || (rc = pc_launch_tree_take_counts(out, foreign, n_foreign, N, st))) return rc;
+    for (int r = 0; r < rounds; ++r) {
+        if (slab && (rc = pc_launch_tree_scan_slab(slab, Lp, run.as_distance, *shard, comp, best, out, N, live, r, st))) return rc;
+        if ((rc = pc_launch_tree_scan_list(kept, comp, best, N, live, r, st))) return rc;
+        for (int f = 0; f < n_foreign; ++f) if ((rc = pc_launch_tree_scan_list(foreign + (size_t)f * words, comp, best, N, live, r, st))) return rc;
+        if ((rc = pc_launch_tree_hook(comp, next, best, out, N, live, r, st)) || (rc = pc_launch_tree_flatten(comp, next, best, out, N, live, r, st))) return rc;
+    }
+    c->tree_cur ^= 1;
+    run.tree_launched += rounds;
+    return PC_OK;
+}
+int PcTreeFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, &shard, nullptr, 0, st); });
+}
+int PcTreeFill::end(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    double* const val = c->h_tree.as<double>();
+    int32_t* const src = (int32_t*)(val + std::max(N, 1)); int32_t* const tgt = src + std::max(N, 1);
+    run.val = val; run.src = src; run.tgt = tgt; run.n_edges = 0;
+    if (N <= 1) return PC_OK;
+    hipStream_t st = c->stream;
+    PC_HIP(hipStreamSynchronize(st));                                       // (the last pass's rounds: not part of the finish)
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long* const keys = c->h_tree_keys.as<unsigned long long>();
+    PC_HIP(hipMemcpyAsync(keys, tree_list(c, c->tree_cur), tree_list_words(c) * 8, hipMemcpyDeviceToHost, st));
+    PC_HIP(hipStreamSynchronize(st));
+    c->busy = false;
+    if ((rc = slab_add_pass_time(c, run, &c->last_tree_ms[0]))) return rc;
+    run.pending = false;
+    const unsigned long long count = keys[N - 1], bad = keys[N];
+    c->last_tree_rounds[0] = (int32_t)keys[N + 1]; c->last_tree_rounds[1] = run.tree_launched;
+    if (bad) {
+        pc_set_error("%s: %llu values of the fill are no millionth in [0, 1]: the order of the tree is not defined on them", run.who, bad);
+        return PC_ERR_DATA;
+    }
+    if (count != (unsigned long long)(N - 1)) { pc_set_error("%s: the forest holds %llu edges, not %d", run.who, count, N - 1); return PC_ERR_HIP; }
+    std::sort(keys, keys + count);
+    for (int i = 0; i < N - 1; ++i) {
+        const int micro = pc_tree_key_micro(keys[i]), s = pc_tree_key_s(keys[i]), t = pc_tree_key_t(keys[i]);
+        if (micro > PC_TREE_MICRO_MAX || s >= t || t >= N) { pc_set_error("%s: edge %d of the forest is no key (%llx)", run.who, i, keys[i]); return PC_ERR_HIP; }
+        src[i] = s; tgt[i] = t;
+        val[i] = (double)(run.as_distance ? micro : PC_TREE_MICRO_MAX - micro) / 1000000.0;
+    }
+    run.n_edges = N - 1;
+    c->last_tree_ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PC_OK;
+}
+// Several devices: a device ships its forest -- the list, its counters behind the keys -- and the root runs one pass over its own
+// forest and the staged ones (lists only), which takes their counters in; the rounds the devices enqueued are summed on the host.
+size_t PcTreeFill::ship_bytes(const pc_ctx* root, const PcSlabRun&) { return tree_list_words(root) * 8; }
+int PcTreeFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun&, void* stage, int slot, int) {
+    int rc = PC_OK;
+    const size_t words = tree_list_words(c);
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, (unsigned long long*)stage + (size_t)slot * words, tree_list(c, c->tree_cur), words * 8))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
+    return PC_OK;
+}
+int PcTreeFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    for (size_t r = 1; r < runs.size(); ++r) runs[0].tree_launched += runs[r].tree_launched;
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if (n_foreign > 0 && (rc = tree_pass(root, runs[0], nullptr, 0, nullptr, (const unsigned long long*)stage, n_foreign, root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
+    return PC_OK;
+}
+
+extern "C" int pc_fill_tree(pc_ctx* c, int metric, int as_distance, int64_t slab_bytes,
+                            const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_fill_tree"; run.metric = metric; run.as_distance = as_distance;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    const int rc = pc_slab_fill<PcTreeFill>(c, run);
+    if (rc != PC_OK) return rc;
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
+    return PC_OK;
+}
+
+extern "C" int pc_last_tree_times(const pc_ctx* c, float* ms_rounds, float* ms_finish) {
+    return last_times(c, "pc_last_tree_times", c ? c->last_tree_ms : nullptr, ms_rounds, ms_finish);
+}
+
+extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_t* launched_rounds) {
+    if (!c) { pc_set_error("pc_last_tree_rounds: NULL context"); return PC_ERR_ARG; }
+    if (live_rounds) *live_rounds = c->last_tree_rounds[0];
+    if (launched_rounds) *launched_rounds = c->last_tree_rounds[1];
+    return PC_OK;
 }

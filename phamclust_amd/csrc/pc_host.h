@@ -128,6 +128,13 @@ struct pc_ctx {
     DevBuf b_nn_key, b_nn_out;
     PinnedBuf h_nn;                         // the neighbours and values lent out by pc_fill_nearest
     float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest with stats (pc_last_nearest_times)
+    // pc_fill_tree: comp[N] | next[N], best[N], two lists of N + PC_TREE_TAIL keys (the resident forest and the one a pass writes), the
+    // rounds' live words; the keys' pinned host image and the pinned result val[N] | src[N] | tgt[N]
+    DevBuf b_tree_comp, b_tree_best, b_tree_list, b_tree_live;
+    PinnedBuf h_tree_keys, h_tree;          // the edges lent out by pc_fill_tree
+    int tree_cur = 0;                       // which of the two lists is the resident forest
+    float last_tree_ms[2] = {0.f, 0.f};     // rounds (with stats), finish of the last pc_fill_tree (pc_last_tree_times)
+    int32_t last_tree_rounds[2] = {0, 0};   // ... its rounds that did work, and those enqueued (pc_last_tree_rounds)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -236,7 +243,7 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
-// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest, and pc_multi_fill_* over several devices) is ONE description of the
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree, and pc_multi_fill_* over several devices) is ONE description of the
 // fill -- a struct of static functions, declared here and defined next to the launchers of its kernels in pc_fill_slabs.hip -- handed as
 // a template argument to the drivers:
 //   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
@@ -251,7 +258,7 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //           nothing travels between devices), and how the root takes the others' state in before its end
 // For N <= 1 begin and the walk do nothing on the device.  PcSlabRun is the call as its entry point was given it (pc_slab_check
 // refuses in the public calls' order, folds the metric, normalises the flags and settles kk), its working state, and its results.
-enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST };
+enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE };
 struct PcSlabRun {
     PcSlabKind kind = PC_SLAB_EDGES;
     const char* who = "";                   // the entry point, for the message texts
@@ -270,6 +277,7 @@ struct PcSlabRun {
     const double* val = nullptr;            // edges: the values; nearest: val[N][kk]
     int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (before end: on the other devices)
     int32_t n_components = 0;
+    int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
 };
 #define PC_SLAB_FILL(Name, tag, text)                                                                                                   \
     struct Name {                                                                                                                       \
@@ -284,6 +292,7 @@ struct PcSlabRun {
 PC_SLAB_FILL(PcEdgesFill, "edges", "an edge-list fill");
 PC_SLAB_FILL(PcComponentsFill, "components", "a components fill");
 PC_SLAB_FILL(PcNearestFill, "nearest", "a nearest-neighbours fill");
+PC_SLAB_FILL(PcTreeFill, "tree", "a tree fill");
 #undef PC_SLAB_FILL
 int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what);
 template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run);

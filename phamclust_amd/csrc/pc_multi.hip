@@ -15,7 +15,7 @@
 // partition by itself), and ONE exchange -- every device copies its shard to the root's gather buffer, device to device (peer
 // copies: xGMI between the GPUs of a node) -- before the root permutes the shards into condensed order and delivers them to the
 // host.  The reference spreads the same pair list over `cpus` worker processes (matrix.py:471-493).
-// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest, at the end of this file) deal contiguous
+// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest / _tree, at the end of this file) deal contiguous
 // stretches of targets instead, one per device, and merge the devices' small per-genome state on the root.
 // ---------------------------------------------------------------------------------------------------------------------
 struct pc_multi {
@@ -25,7 +25,7 @@ struct pc_multi {
     std::vector<int32_t> peer;              // device r -> root: PC_PEER_* (how its shard will travel), see pc_multi_peer_access
     std::vector<std::string> peer_note;     // the runtime's own words where access was refused
     bool uploaded = false, residues = false;
-    // pc_multi_fill_edges / _components / _nearest
+    // pc_multi_fill_edges / _components / _nearest / _tree
     DevBuf b_stage;                         // root device: the other devices' state (lists or forests), one slice per shipping device
     std::vector<int32_t> stretches;         // [world + 1] the deal of the last such call (pc_multi_last_stretches)
     float last_slab_ms[2] = {0.f, 0.f};     // ... its exchange and merge (pc_multi_last_slab_times)
@@ -211,7 +211,7 @@ extern "C" int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Edge, component and nearest fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
+// Edge, component, nearest and tree fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
 // (pc_host.h, pc_fill_slabs.hip).  Each device runs the description's begin and the walk over ONE contiguous stretch of targets with
 // the call's state on its own device, and ships that state to the root; the state merges exactly -- lists by their total order,
 // forests by uniting g with its foreign parent, edge lists over ascending stretches by concatenation -- so the root's end delivers
@@ -354,9 +354,24 @@ extern "C" int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, i
     return PC_OK;
 }
 
+extern "C" int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int64_t slab_bytes,
+                                  const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_multi_fill_tree"; run.metric = metric; run.as_distance = as_distance;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    const int rc = multi_slab_fill<PcTreeFill>(m, run, stats);
+    if (rc != PC_OK) return rc;
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
+    return PC_OK;
+}
+
 extern "C" int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds) {
     if (!m || !bounds) { pc_set_error("pc_multi_last_stretches: NULL argument"); return PC_ERR_ARG; }
-    if (m->stretches.size() != m->ctx.size() + 1) { pc_set_error("pc_multi_last_stretches: no edge, component or nearest fill has run on these devices"); return PC_ERR_STATE; }
+    if (m->stretches.size() != m->ctx.size() + 1) { pc_set_error("pc_multi_last_stretches: no edge, component, nearest or tree fill has run on these devices"); return PC_ERR_STATE; }
     memcpy(bounds, m->stretches.data(), m->stretches.size() * sizeof(int32_t));
     return PC_OK;
 }

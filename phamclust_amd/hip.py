@@ -75,7 +75,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_multi_upload_residues", "pc_multi_set_tie_rule", "pc_multi_fill_borrow", "pc_fill_rows", "pc_fill_rows_dev", "pc_fill_edges", "pc_last_edge_times",
            "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles",
            "pc_fill_nearest", "pc_last_nearest_times", "pc_multi_fill_edges", "pc_multi_fill_components", "pc_multi_fill_nearest",
-           "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan"]
+           "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan", "pc_fill_tree", "pc_multi_fill_tree", "pc_last_tree_times",
+           "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -149,6 +150,13 @@ def load():
     L.pc_fill_nearest.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_f64p),
                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_nearest_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_fill_tree.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_f64p),
+                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_tree_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_last_tree_rounds.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.pc_tree_key.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    L.pc_tree_key.restype = ctypes.c_uint64
+    L.pc_tree_key_parts.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -178,6 +186,7 @@ def load():
     L.pc_multi_fill_edges.argtypes = L.pc_fill_edges.argtypes
     L.pc_multi_fill_components.argtypes = L.pc_fill_components.argtypes
     L.pc_multi_fill_nearest.argtypes = L.pc_fill_nearest.argtypes
+    L.pc_multi_fill_tree.argtypes = L.pc_fill_tree.argtypes
     L.pc_multi_last_stretches.argtypes = [vp, _i32p]
     L.pc_multi_last_slab_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_stretch_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_int, _i32p]
@@ -275,7 +284,7 @@ class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
 
 
 class _SlabFills:
-    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` -- the fills that deliver no dense matrix -- once for :class:`Context`
+    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` -- the fills that deliver no dense matrix -- once for :class:`Context`
     and :class:`MultiContext`.  The class supplies ``_SLAB_CALL`` (the prefix of the library's symbols), ``_before_slab_fill(metric)``
     (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
     dict of such a fill)."""
@@ -352,6 +361,31 @@ class _SlabFills:
         if not want_stats:
             return nbr, val
         return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
+
+    def fill_tree(self, metric, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The single-linkage dendrogram as the ``N - 1`` edges ``(src, tgt, val)`` -- int32, int32, float64, ``src < tgt`` -- of the
+        minimum spanning tree under one total order on the pairs: the better value first (the smallest distance with ``as_distance``,
+        else the largest similarity), then the smaller target, then the smaller source; delivered ascending in that order, which is
+        the merge order of single linkage.  It is the tree Kruskal's algorithm accepts in that order
+        (``matrix.SingleLinkageTree.from_dense`` states it on the host), canonical whatever the slab cut or the number of devices;
+        the values are the whole fill's.  From it the clusters at any threshold or for any cluster count, the linkage matrix and the
+        leaf order follow on the host.  The dense matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time;
+        0 = automatic) held, as by :meth:`fill_edges`.  The arrays are copies; ``borrow=True`` lends the context's page-locked memory
+        instead, on ``fill(borrow=True)``'s terms.  ``want_stats`` adds the fills' summed stats with ``n_edges``, ``n_slabs``,
+        ``ms_rounds``, ``ms_finish``, ``live_rounds`` and ``launched_rounds``.
+
+        On a :class:`MultiContext`: the same arrays -- every device builds the forest of its stretch of targets, the root merges
+        the forests by rounds over the lists alone; the stats carry the route's own entries (as for :meth:`fill_edges`) in place of
+        the two times."""
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        stats = self._slab_fill("tree", metric, int(bool(as_distance)), int(slab_bytes),
+                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        return (*out, self._slab_stats("tree", stats, n_edges=int(n.value), n_slabs=int(nsl.value), **self._tree_rounds()))
 
 
 class Context(_SlabFills):
@@ -580,10 +614,30 @@ class Context(_SlabFills):
             raise ValueError("edge_slabs: slab_bytes must be positive (0 = automatic is decided on the device, by the free HBM)")
         return Context.chunk_plan(np.arange(int(n), dtype=np.uint64), min(max(int(slab_bytes) // 8, 1), Context.EDGE_MAX_PAIRS))
 
-    # -- fill_edges / fill_components / fill_nearest (_SlabFills): what this class supplies ----------------------------------
+    # -- fill_edges / fill_components / fill_nearest / fill_tree (_SlabFills): what this class supplies ----------------------------------
     _SLAB_CALL = "pc_fill_"
     _SLAB_TIMES = {"edges": ("pc_last_edge_times", "ms_compact", "ms_d2h"), "components": ("pc_last_component_times", "ms_union", "ms_labels"),
-                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish")}
+                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish")}
+    TREE_MAX_GENOMES = 1 << 22            # PC_TREE_MAX_GENOMES: a genome index takes 22 bits of a tree key
+
+    def _tree_rounds(self):
+        """``live_rounds`` / ``launched_rounds`` of the last tree fill (``pc_last_tree_rounds``)."""
+        live, launched = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.pc_last_tree_rounds(self._h, ctypes.byref(live), ctypes.byref(launched)))
+        return dict(live_rounds=int(live.value), launched_rounds=int(launched.value))
+
+    @staticmethod
+    def tree_key(micro, s, t):
+        """The word a pair takes in the tree fill's total order (``pc_tree_key``): ``micro << 44 | t << 22 | s``; ``2**64 - 1`` for
+        arguments that make no key."""
+        return int(load().pc_tree_key(int(micro), int(s), int(t)))
+
+    @staticmethod
+    def tree_key_parts(key):
+        """``(micro, s, t)`` of a key, or None for a word that is none (``pc_tree_key_parts``)."""
+        micro, s, t = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = load().pc_tree_key_parts(int(key), ctypes.byref(micro), ctypes.byref(s), ctypes.byref(t))
+        return None if rc != 0 else (int(micro.value), int(s.value), int(t.value))
 
     def _before_slab_fill(self, metric):
         if metric in NEEDS_RESIDUES:
@@ -899,8 +953,12 @@ class MultiContext(_SlabFills):
                       ms_total=max(p["ms_total"] for p in per), peer_access=self.peer_access())
         return out, merged
 
-    # -- the fills that deliver no dense matrix, over all devices (_SlabFills: pc_multi_fill_edges / _components / _nearest) ----
+    # -- the fills that deliver no dense matrix, over all devices (_SlabFills: pc_multi_fill_edges / _components / _nearest / _tree) ----
     _SLAB_CALL = "pc_multi_fill_"
+
+    def _tree_rounds(self):
+        """(the round counts are a single context's: ``pc_last_tree_rounds`` takes one)"""
+        return {}
 
     @staticmethod
     def slab_stretches(cost, world):

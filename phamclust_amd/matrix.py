@@ -1045,6 +1045,150 @@ def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 
+class SingleLinkageTree:
+    """The single-linkage dendrogram of a matrix as the ``N - 1`` edges of its minimum spanning tree, in merge order: ``source[i] <
+    target[i]`` (indices into ``nodes``) joined at ``weight[i]``.  ONE total order on the pairs decides everything: the better weight
+    first -- the smaller on distances, the larger on similarities, a plain float compare -- then the smaller target, then the
+    smaller source; the tree is the one Kruskal's algorithm accepts when it takes the pairs in that order, so it is unique, ties
+    included.  The reference derives the same dendrogram from its dense matrix (``scipy.cluster.hierarchy.linkage(..., 'single')``
+    in ``_get_tree_order``, matrix.py:673-686; scikit-learn's single linkage in clustering.py:4-51); ``tree_de_novo`` fills it on the
+    GPU without the dense matrix, ``from_dense`` states it on the host.  Clusters at any threshold (``cut``), for any cluster count
+    (``cut_n``), scipy's ``Z`` (``linkage``) and the leaf order (``leaves``) follow from the edges alone."""
+
+    def __init__(self, nodes, source, target, weight, is_distance=True):
+        self.nodes = list(nodes)
+        self.source = np.ascontiguousarray(source, dtype=np.int32)
+        self.target = np.ascontiguousarray(target, dtype=np.int32)
+        self.weight = np.ascontiguousarray(weight, dtype=np.float64)
+        n = len(self.nodes)
+        if not (self.source.shape == self.target.shape == self.weight.shape == (max(n - 1, 0),)):
+            raise ValueError("source, target and weight must be three 1-D arrays of len(nodes) - 1 entries")
+        if n > 1 and not ((self.source >= 0).all() and (self.source < self.target).all() and (self.target < n).all()):
+            raise ValueError("an edge must join source < target, both indices into nodes")
+        self.is_distance = bool(is_distance)
+
+    @classmethod
+    def from_dense(cls, matrix):
+        """The tree of a filled ``SymMatrix``, in its current node order: every pair sorted by ``np.lexsort`` over (source,
+        target, weight) -- the weight first, better first -- then Kruskal's algorithm with a union-find.  Host arithmetic: the
+        statement ``Context.fill_tree`` is held to."""
+        data = matrix._ordered()
+        n = len(matrix)
+        s, t = np.triu_indices(n, k=1)
+        w = data[s, t]
+        if np.isnan(w).any():
+            raise TypeError("cannot build the tree of a matrix with unset edges")
+        order = np.lexsort((s, t, w if matrix.is_distance else -w))
+        parent = list(range(n))
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        kept = []
+        for e, a, b in zip(order.tolist(), s[order].tolist(), t[order].tolist()):
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+                kept.append(e)
+                if len(kept) == n - 1:
+                    break
+        kept = np.asarray(kept, dtype=np.int64)
+        return cls(matrix.nodes, s[kept], t[kept], w[kept], is_distance=matrix.is_distance)
+
+    def __len__(self):
+        return int(self.weight.shape[0])
+
+    def heights(self):
+        """The merge heights: the weights in merge order (ascending on distances, descending on similarities)."""
+        return self.weight.copy()
+
+    def _labels(self, count):
+        """Labels (the smallest member's index) of the components the first ``count`` edges span."""
+        edges = SparseEdges(self.nodes, self.source[:count], self.target[:count], self.weight[:count], is_distance=self.is_distance)
+        return edges.components()
+
+    def cut(self, eps, strict=True):
+        """The single-linkage clusters at ``eps`` as int32 labels, ``labels[g]`` = the smallest index of g's cluster (what
+        :class:`Components` takes): the components of the pairs with ``weight < eps`` on distances, ``> eps`` on similarities;
+        ``<=`` / ``>=`` with ``strict=False``.  The edges are in merge order, so the cut keeps a prefix of them."""
+        w = self.weight
+        if self.is_distance:
+            keep = w < eps if strict else w <= eps
+        else:
+            keep = w > eps if strict else w >= eps
+        return self._labels(int(keep.sum()))
+
+    def cut_n(self, n_clusters):
+        """``n_clusters`` clusters as labels: the first ``N - n_clusters`` merges of the total order.  Canonical, ties included; it
+        is scikit-learn's single linkage for ``n_clusters`` wherever the two heights at the cut differ."""
+        n = len(self.nodes)
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= max(n, 1):
+            raise ValueError(f"n_clusters must be an integer in 1..{max(n, 1)}, not {n_clusters!r}")
+        return self._labels(max(n - int(n_clusters), 0))
+
+    def linkage(self):
+        """scipy's linkage matrix ``Z``, float64[N - 1, 4], of a distance tree: row i joins clusters ``Z[i, 0] < Z[i, 1]`` (a leaf's
+        index, or N + the row that made the cluster) at ``Z[i, 2]`` into one of ``Z[i, 3]`` leaves."""
+        if not self.is_distance:
+            raise ValueError("linkage() takes a tree over distances (inverted() gives one)")
+        n = len(self.nodes)
+        z = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
+        parent = list(range(n))
+        ident, size = list(range(n)), [1] * n
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for i, (a, b, w) in enumerate(zip(self.source.tolist(), self.target.tolist(), self.weight.tolist())):
+            ra, rb = find(a), find(b)
+            if ra == rb:
+                raise ValueError("the edges do not form a tree")
+            z[i] = (min(ident[ra], ident[rb]), max(ident[ra], ident[rb]), w, size[ra] + size[rb])
+            parent[rb] = ra
+            ident[ra], size[ra] = n + i, size[ra] + size[rb]
+        return z
+
+    def leaves(self):
+        """The dendrogram's leaf order as the reference computes it (``_get_tree_order``, matrix.py:673-686): indices into ``nodes``."""
+        if len(self.nodes) < 2:
+            return list(range(len(self.nodes)))
+        return dendrogram(self.linkage(), no_plot=True, count_sort="descending")["leaves"]
+
+    def __iter__(self):
+        for i, j, w in zip(self.source.tolist(), self.target.tolist(), self.weight.tolist()):
+            yield self.nodes[i], self.nodes[j], w
+
+    def inverted(self):
+        """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SparseEdges.inverted``; the merge order is kept (the
+        better weight stays the better one, and the tie-break does not look at it)."""
+        return SingleLinkageTree(self.nodes, self.source, self.target, np.round(1.0 - self.weight, 6), is_distance=not self.is_distance)
+
+
+def tree_de_novo(genomes, func, as_distance=True, slab_bytes=0):
+    """The single-linkage dendrogram of ``matrix_de_novo(genomes, func, cpus, as_distance)`` as a :class:`SingleLinkageTree`, filled on
+    the GPU by ``Context.fill_tree``: the dense matrix is never delivered, and beyond ``slab_bytes`` of HBM (0: automatic) never
+    held; N - 1 edges cross PCIe.  ``func`` must be one of the six ``METRICS`` callables (no CPU route:
+    ``SingleLinkageTree.from_dense(matrix_de_novo(...))`` serves another callable).  Several devices as ``edges_de_novo``
+    (``MultiContext.fill_tree``: the same tree); under a launcher (``WORLD_SIZE`` > 1) it raises.  Every refusal comes before the
+    first GPU call."""
+    ctx, metric, names, record = upload_for_fills(genomes, func, "tree_de_novo", several=True,
+                                                  advice="for another callable: SingleLinkageTree.from_dense(matrix_de_novo(...))")
+    import time
+    t0 = time.perf_counter()
+    src, tgt, val, stats = ctx.fill_tree(metric, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    fill_s = _record_fill(stats, metric, names, record, t0)
+    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} tree edges from {record['genome_pairs']} pairs in {stats['n_slabs']} slab(s) on "
+                  f"{record['n_gpus']} device(s): fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds "
+                  f"{stats.get('ms_rounds', 0.0):.3f} ms)")
+    return SingleLinkageTree(names, src, tgt, val, is_distance=as_distance)
+
+
 def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):
     """The bytes ``matrix_to_adjacency`` writes for the dense matrix restricted to these pairs (diagonal included).
     ``use_lib=False`` takes the Python formatter even when csrc/libpc_pack.so is there (same bytes)."""

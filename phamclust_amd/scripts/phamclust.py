@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, upload_for_fills
+from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, tree_de_novo, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -291,6 +291,28 @@ class _Run:
         log.info(f"wrote {target.name}")
         return found
 
+    # 2, --tree
+    def tree(self):
+        """Stage 2 as a tree fill: the single-linkage dendrogram, and only ``tree_<metric>.tsv`` is written: one
+        ``source<TAB>target<TAB>similarity`` line per edge of the minimum spanning tree, in merge order (the most similar pair first;
+        equal similarities by target, then source, in genome order).  Distances are filled and inverted, as for the adjacency file.
+        No matrix, no threshold, nothing cached or clustered."""
+        self.banner(2, f"{self.metric} single-linkage tree (tree fill)")
+        t0 = time.perf_counter()
+        found = tree_de_novo(self.genomes, METRICS[self.metric], as_distance=True)
+        st = _matrix.LAST_FILL
+        log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {len(found):,} edges of the single-linkage tree of {len(found.nodes):,} genomes from "
+                 f"{st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
+                 f"{st.get('upload_s', 0.0):.3f}, fill+rounds+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, rounds "
+                 f"{st.get('ms_rounds', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        target = self.outdir / f"tree_{self.metric}.tsv"
+        with open(target, "w") as handle:
+            handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in found.inverted())
+        log.info(f"wrote {target.name}")
+        return found
+
     def extended(self, cpus, t0):
         """Stage 2 under --extend: the old matrix's block is kept, the rows of the genomes it lacks are filled (matrix_extend)."""
         try:
@@ -448,14 +470,17 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, nearest=None):
+              components_only=False, no_matrix=False, tree=False, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
     ``components_only``: stop after a components fill -- genomes joined when distance < round(1 - ``edge_thresh``, 6), None: 0.0 --
     and write only ``components_<metric>.tsv``; ``no_matrix``: stages 2-3 from components and groups fills, without the dense matrix
     (same clusters; no similarities file, no dataset heatmap, no matrix cache; the adjacency file from an edge-list fill);
-    ``nearest``: stop after a nearest-neighbours fill of that many neighbours per genome and write only ``nearest_<metric>.tsv``."""
+    ``nearest``: stop after a nearest-neighbours fill of that many neighbours per genome and write only ``nearest_<metric>.tsv``;
+    ``tree``: stop after a tree fill and write only ``tree_<metric>.tsv``, the single-linkage dendrogram's edges in merge order."""
+    if tree and (adjacency_only or components_only or no_matrix or nearest is not None or extend is not None):
+        raise ValueError("tree cannot be combined with adjacency_only, components_only, no_matrix, nearest or extend")
     if nearest is not None:
         if isinstance(nearest, bool) or not isinstance(nearest, int) or not 1 <= nearest <= _matrix.NEAREST_MAX_K:
             raise ValueError(f"nearest is a number of neighbours in 1..{_matrix.NEAREST_MAX_K}")
@@ -486,6 +511,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["components"] = f"only, joined at similarity > {0.0 if edge_thresh is None else edge_thresh}"
     if nearest is not None:
         settings["nearest"] = f"only, {nearest} neighbours per genome"
+    if tree:
+        settings["tree"] = "only (single-linkage dendrogram)"
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
@@ -514,6 +541,13 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             sys.exit(1)
         run.nearest(nearest)
         run.banner(3, "done (--nearest: no clustering)")
+        return
+    if tree:
+        if run.world > 1:
+            log.error("--tree is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.tree()
+        run.banner(3, "done (--tree: no clustering)")
         return
     matrix = None
     if no_matrix:
@@ -557,15 +591,15 @@ def _colors(text):
 
 
 SLAB_FILL_FLAGS = (("adjacency_only", "--adjacency-only", "fills an edge list"), ("components_only", "--components-only", "fills component labels"),
-                   ("nearest", "--nearest", "fills nearest-neighbour lists"))
+                   ("nearest", "--nearest", "fills nearest-neighbour lists"), ("tree", "--tree", "fills the single-linkage tree"))
 
 
 def gpus_plan(args, route, packed):
     """What ``--gpus N`` (N > 1, one process, no launcher around it) comes to: ``(n_gpus, how, note)`` with ``how`` "process" (this
     process drives n_gpus devices: PHAMCLUST_GPUS), "launcher" (n_gpus ranks are started) or "one" (the matrix stage stays on one
     GPU; ``note`` says why).  Host arithmetic on the parsed arguments and the packed genomes (None: no estimate) -- no GPU call.
-    --extend's rows fill is a one-GPU call.  --adjacency-only, --components-only and --nearest spread over the GPUs of this process
-    (pc_multi_fill_edges / _components / _nearest) under the same estimate as the dense fill; one process per GPU has no route for
+    --extend's rows fill is a one-GPU call.  --adjacency-only, --components-only, --nearest and --tree spread over the GPUs of this process
+    (pc_multi_fill_edges / _components / _nearest / _tree) under the same estimate as the dense fill; one process per GPU has no route for
     them, so under PHAMCLUST_MULTI=launcher they stay on one GPU."""
     if args.extend is not None:
         # (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
@@ -661,7 +695,7 @@ def _run(args, argv):
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
-                  nearest=args.nearest)
+                  nearest=args.nearest, tree=args.tree)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
