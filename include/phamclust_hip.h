@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 161   /* 0.5.10: pc_fill_tree / pc_multi_fill_tree, pc_tree_key */
+#define PC_VERSION 162   /* 0.5.11: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree, pc_rows_pass_span */
 
 typedef enum {
     PC_OK = 0,
@@ -358,6 +358,51 @@ int pc_last_tree_times(const pc_ctx* ctx, float* ms_rounds, float* ms_finish);
 int pc_last_tree_rounds(const pc_ctx* ctx, int32_t* live_rounds, int32_t* launched_rounds);
 uint64_t pc_tree_key(int32_t micro, int32_t s, int32_t t);
 int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
+
+/*
+ * The rows forms of the edge-list, components and tree fills: a STORED result grown by new genomes.  rows[n_rows] are the query genomes
+ * -- the new ones -- under pc_fill_rows' contract (strictly ascending indices of the uploaded collection, which holds old and new
+ * genomes in fill order); the pairs of the call are those that touch a query genome, each once (a pair of two query genomes in the row
+ * of the smaller): n_rows * (N - 1) - n_rows (n_rows - 1) / 2 pairs instead of N (N - 1) / 2.  What is stored stands for the pairs
+ * among the other genomes.  It can, exactly: the old genomes keep their relative order inside the grown collection, so the map from
+ * old to new indices is strictly increasing and every comparison the fills make among old pairs (value, then target, then source) is
+ * unchanged under it -- the stored result, re-indexed by the caller, is what a fill of the old block would deliver in the new indexing.
+ * Every index in these calls, seeds included, is in the UPLOADED collection's numbering.
+ * The walk: the query rows are cut into consecutive ranges of at most max(1, slab_bytes / 8 / N) rows (slab_bytes == 0: automatic, by
+ * the free HBM as pc_fill_edges decides it); each range is filled by the rows fill itself into the resident slab buffer as f64[m][N]
+ * and goes through the rows form of the fill's pass (the same predicate, ballot ranking, union and key as the triangular pass; the
+ * diagonal and the second copy of a pair of two query genomes are skipped).  *n_slabs = the ranges walked.  Values are the whole
+ * fill's, bit for bit, each pair in the whole fill's orientation.  One GPU; the six metrics and PC_AAI_PPOS.
+ *   pc_fill_rows_edges       the passing pairs of the call (threshold as pc_fill_edges), sorted by target, then source (one host sort:
+ *                            the passes emit row-major); at most n_rows * N.  The grown list is the stored list re-indexed, merged
+ *                            with this one by (target, source): the caller's part (matrix.edges_extend).
+ *   pc_fill_rows_components  seed_labels (i32[N], or NULL: every genome its own component) is the initial parent[]: the stored labelling
+ *                            re-indexed, a new genome labelling itself.  0 <= seed_labels[g] <= g and seed_labels[seed_labels[g]] ==
+ *                            seed_labels[g], else PC_ERR_ARG.  The passing pairs of the call are united into it (predicate and strict as
+ *                            pc_fill_components): *labels the grown collection's canonical labels; *n_edges counts the call's passing
+ *                            pairs only.
+ *   pc_fill_rows_tree        the n_seed seed edges (the stored tree re-indexed; a forest) are packed with pc_tree_key -- a seed that is
+ *                            no key (source < target < N, a value that is a millionth in [0, 1]) or n_seed > N - 1: PC_ERR_ARG -- and
+ *                            are the resident forest in place of the empty one: MST(A + B) = MST(MST(A) + B) with A the pairs among
+ *                            old genomes, B the call's.  The result has N - 1 edges iff seeds and the call's pairs connect the
+ *                            collection; otherwise PC_ERR_HIP ("the forest holds ... edges").
+ * n_rows == 0 is PC_OK: with seeds the seeds' labelling or tree, without them every genome its own component (and, N > 1, no tree).
+ * Outputs, loans, stats and the refusals' order are the triangular calls' (before upload, sharded context, PC_TREE_MAX_GENOMES, a NULL
+ * out pointer, a NaN threshold, negative slab_bytes, missing residues); then rows (pc_fill_rows' PC_ERR_ARG), then the seeds.
+ * pc_last_edge_times / pc_last_component_times / pc_last_tree_times / pc_last_tree_rounds report on these calls too (the edges' host
+ * sort is added to ms_d2h).  Not built: a rows form of pc_fill_nearest, several GPUs.
+ */
+int pc_fill_rows_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
+                       const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+int pc_fill_rows_components(pc_ctx* ctx, int metric, int as_distance, double threshold, int strict, const int32_t* rows, int n_rows,
+                            const int32_t* seed_labels /* i32[N] or NULL */, int64_t slab_bytes,
+                            const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+int pc_fill_rows_tree(pc_ctx* ctx, int metric, int as_distance, const int32_t* rows, int n_rows,
+                      const int32_t* seed_src, const int32_t* seed_tgt, const double* seed_val, int32_t n_seed, int64_t slab_bytes,
+                      const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+/* Test hook, host arithmetic: the values one workgroup of a rows pass covers (pass_kind 0: edge count / emit, 1: union, 2: tree scan;
+ * anything else: 0) -- what a test of the passes' workgroup seams sizes its slabs by. */
+int pc_rows_pass_span(int pass_kind);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -67,6 +67,11 @@ _OPTIONS = (
                                                           "single-linkage dendrogram as N-1 lines source<TAB>target<TAB>similarity in merge "
                                                           "order, from which the clusters at every threshold follow; no matrix, no threshold, no "
                                                           "clustering; with --gpus N the devices of this process share the fill")),
+    (None, "-w", "--grow", dict(type=pathlib.Path, default=None, help="with --tree: the tree_<metric>.tsv, with --components-only --edge-thresh SIM: the "
+                                                                     "components_<metric>.tsv an earlier run wrote over a SUBSET of these genomes: only "
+                                                                     "the pairs of the genomes it lacks are filled, on one GPU, and the file written is "
+                                                                     "the from-scratch run's, byte for byte; the adjacency file has no such route (it "
+                                                                     "does not say which genomes it covered: matrix.edges_extend is the API for it)")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -123,6 +128,17 @@ def parse_args(argv=None):
                             ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
             if given:
                 parser.error(f"--tree stops after a tree fill of its own; it cannot be combined with {flag}")
+    if args.grow is not None:
+        if not (args.tree or args.components_only):
+            parser.error("--grow FILE grows a stored tree (--tree) or stored components (--components-only --edge-thresh SIM); give one of them")
+        if args.components_only and args.edge_thresh is None:
+            parser.error("--grow with --components-only needs the --edge-thresh SIM the stored components were filled at")
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--no-matrix", args.no_matrix), ("--nearest", args.nearest is not None),
+                            ("--extend", args.extend is not None)):
+            if given:
+                parser.error(f"--grow goes with exactly one of --tree and --components-only; it cannot be combined with {flag}")
+        if args.gpus > 1:
+            parser.error("--grow: growing a stored result is a one-GPU call; it cannot be combined with --gpus N")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

@@ -132,6 +132,58 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_union(const double* __restric
     }
 }
 
+// k_cc_union over a rows slab (PcRowsSlab: vals = f64[m][n] seen flat, Lp = m * n; pc_fill_rows_components): the LIVE elements that
+// pass are counted and united.  The same loads, the same 64-bit count, the same pc_cc_unite (every access to parent[] a relaxed
+// agent-scope atomic); (row, column) carried in a PcRowsCursor instead of the walk over lbase.  parent[] may come in seeded with a
+// stored labelling (parent[g] = the smallest member of g's stored component <= g): I1 and I2 hold for it as for the identity.
+static_assert(CC_CHUNK == 4096, "pc_rows_slab_span");
+template <int DIST, int STRICT>
+__global__ __launch_bounds__(CC_THREADS) void k_cc_union_rows(const double* __restrict__ vals, int64_t Lp, double thr, PcRowsSlab dom,
+                                                              int32_t* parent, unsigned long long* n_pass) {
+    __shared__ uint32_t wsum[CC_THREADS / 64];
+    __shared__ int2 origin;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * CC_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
+    __syncthreads();
+    PcRowsCursor first, at;
+    first.start(origin, threadIdx.x * 2u, dom);
+    at = first;
+    uint32_t n = 0;                                    // the wave's count (the same in every lane)
+    uint32_t pass_a = 0, pass_b = 0;
+#pragma unroll
+    for (int j = 0; j < CC_ITERS; ++j) {
+        double a, b;
+        const int have = pc_cc_load(vals, base + (int64_t)j * CC_STRIDE, Lp, a, b);
+        int row1, col1, q;
+        at.next(dom, row1, col1);
+        const bool pa = have > 0 && pc_cc_pass<DIST, STRICT>(a, thr) && pc_rows_live(dom, at.row, at.col, q);
+        const bool pb = have > 1 && pc_cc_pass<DIST, STRICT>(b, thr) && pc_rows_live(dom, row1, col1, q);
+        n += (uint32_t)__popcll(__ballot(pa)) + (uint32_t)__popcll(__ballot(pb));
+        pass_a |= (uint32_t)pa << j; pass_b |= (uint32_t)pb << j;
+        at.advance(dom);
+    }
+    if (lane == 0) wsum[wv] = n;
+    __syncthreads();
+    uint32_t tot = 0;
+#pragma unroll
+    for (int w = 0; w < CC_THREADS / 64; ++w) tot += wsum[w];
+    if (tot == 0) return;                              // (the whole workgroup)
+    if (threadIdx.x == 0) atomicAdd(n_pass, (unsigned long long)tot);
+    if ((pass_a | pass_b) == 0) return;
+    at = first;
+#pragma unroll 1
+    for (int j = 0; j < CC_ITERS; ++j) {
+        if ((pass_a >> j) & 1u) pc_cc_unite(parent, dom.rows[at.row], at.col);      // (a passing element lies below Lp: its row is one of the slab's)
+        if ((pass_b >> j) & 1u) {
+            int row1, col1;
+            at.next(dom, row1, col1);
+            pc_cc_unite(parent, dom.rows[row1], col1);
+        }
+        at.advance(dom);
+    }
+}
+
 // the same relaxed agent-scope atomics on parent[] as k_cc_union (through pc_cc_unite); the foreign forests are read-only here
 __global__ __launch_bounds__(256) void k_cc_merge(int32_t* parent, const int32_t* __restrict__ fparent, int n_foreign, int n) {
     const int g = blockIdx.x * 256 + threadIdx.x;
@@ -173,6 +225,20 @@ int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int stri
     else if (strict) hipLaunchKernelGGL((k_cc_union<0, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
     else hipLaunchKernelGGL((k_cc_union<0, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
     return cc_check("k_cc_union");
+}
+
+// dom: rows / is_query on the device, Lp = m * n; parent: [n]
+int pc_launch_cc_union_rows(const double* vals, int64_t Lp, int as_distance, int strict, double thr, PcRowsSlab dom, int32_t* parent,
+                            unsigned long long* n_pass, hipStream_t st) {
+    if (Lp <= 0) return PC_OK;
+    if (dom.n <= 0 || dom.m <= 0 || Lp != (int64_t)dom.m * dom.n) { pc_set_error("k_cc_union_rows: a rows slab of %d x %d is not %lld values", dom.m, dom.n, (long long)Lp); return PC_ERR_ARG; }
+    dom.adv_rows = CC_STRIDE / dom.n; dom.adv_cols = CC_STRIDE % dom.n;
+    const dim3 grid((unsigned)((Lp + CC_CHUNK - 1) / CC_CHUNK)), block(CC_THREADS);
+    if (as_distance && strict) hipLaunchKernelGGL((k_cc_union_rows<1, 1>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
+    else if (as_distance) hipLaunchKernelGGL((k_cc_union_rows<1, 0>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
+    else if (strict) hipLaunchKernelGGL((k_cc_union_rows<0, 1>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
+    else hipLaunchKernelGGL((k_cc_union_rows<0, 0>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
+    return cc_check("k_cc_union_rows");
 }
 
 // fparent: [n_foreign][n], every value in [0, n) (a forest k_cc_union left: I1)

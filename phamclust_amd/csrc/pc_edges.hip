@@ -110,6 +110,132 @@ __global__ __launch_bounds__(EDGE_THREADS) void k_edge_emit(const double* __rest
     }
 }
 
+// ---- the same two passes over a rows slab (PcRowsSlab: vals = f64[m][n] seen flat, Lp = m * n; pc_fill_rows_edges): an element counts
+// iff it is LIVE (pc_rows_live) and passes.  The same chunks, loads and ballot ranking; where the triangular kernels find (s, t) by
+// lbase, these carry (row, column) in a PcRowsCursor.  Output order is element order: row-major, so by query row, then by the other
+// genome -- the host sorts the call's edges by (target, source) once.
+template <int DIST>
+__global__ __launch_bounds__(EDGE_THREADS) void k_edge_count_rows(const double* __restrict__ vals, int64_t Lp, double thr, PcRowsSlab dom,
+                                                                  uint32_t* __restrict__ counts) {
+    __shared__ uint32_t wsum[EDGE_THREADS / 64];
+    __shared__ int2 origin;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * EDGE_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
+    __syncthreads();
+    PcRowsCursor at;
+    at.start(origin, threadIdx.x * 2u, dom);
+    uint32_t n = 0;                                    // the wave's count (the same in every lane)
+#pragma unroll
+    for (int j = 0; j < EDGE_ITERS; ++j) {
+        double a, b;
+        const int have = pc_edge_load(vals, base + (int64_t)j * EDGE_STRIDE, Lp, a, b);
+        int row1, col1, q;
+        at.next(dom, row1, col1);
+        const bool pa = have > 0 && pc_edge_pass<DIST>(a, thr) && pc_rows_live(dom, at.row, at.col, q);
+        const bool pb = have > 1 && pc_edge_pass<DIST>(b, thr) && pc_rows_live(dom, row1, col1, q);
+        n += (uint32_t)__popcll(__ballot(pa)) + (uint32_t)__popcll(__ballot(pb));
+        at.advance(dom);
+    }
+    if (lane == 0) wsum[wv] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int w = 0; w < EDGE_THREADS / 64; ++w) tot += wsum[w];
+        counts[blockIdx.x] = tot;
+    }
+}
+
+template <int DIST>
+__global__ __launch_bounds__(EDGE_THREADS) void k_edge_emit_rows(const double* __restrict__ vals, int64_t Lp, double thr, PcRowsSlab dom,
+                                                                 const uint32_t* __restrict__ offs, int32_t* __restrict__ src,
+                                                                 int32_t* __restrict__ tgt, double* __restrict__ val) {
+    __shared__ uint32_t wcnt[EDGE_ITERS][EDGE_THREADS / 64];
+    __shared__ int2 origin;
+    const uint32_t off = offs[blockIdx.x];
+    if (offs[blockIdx.x + 1] == off) return;           // (the whole workgroup: no edge in this chunk, nothing to re-read)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * EDGE_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    const unsigned long long below = ((unsigned long long)1 << lane) - 1;
+    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
+    __syncthreads();
+    PcRowsCursor first, at;
+    first.start(origin, threadIdx.x * 2u, dom);
+    at = first;
+    double va[EDGE_ITERS], vb[EDGE_ITERS];
+    uint32_t pre[EDGE_ITERS];                          // passing elements of the wave's iteration j before this thread's first one, in ELEMENT order
+    uint32_t pass_a = 0, pass_b = 0;
+#pragma unroll
+    for (int j = 0; j < EDGE_ITERS; ++j) {
+        const int have = pc_edge_load(vals, base + (int64_t)j * EDGE_STRIDE, Lp, va[j], vb[j]);
+        int row1, col1, q;
+        at.next(dom, row1, col1);
+        const bool pa = have > 0 && pc_edge_pass<DIST>(va[j], thr) && pc_rows_live(dom, at.row, at.col, q);
+        const bool pb = have > 1 && pc_edge_pass<DIST>(vb[j], thr) && pc_rows_live(dom, row1, col1, q);
+        const unsigned long long ba = __ballot(pa), bb = __ballot(pb);
+        pre[j] = (uint32_t)__popcll(ba & below) + (uint32_t)__popcll(bb & below);
+        pass_a |= (uint32_t)pa << j; pass_b |= (uint32_t)pb << j;
+        if (lane == 0) wcnt[j][wv] = (uint32_t)__popcll(ba) + (uint32_t)__popcll(bb);
+        at.advance(dom);
+    }
+    __syncthreads();
+    at = first;
+    uint32_t run = off;
+#pragma unroll
+    for (int j = 0; j < EDGE_ITERS; ++j) {
+        uint32_t o = run;
+#pragma unroll
+        for (int w = 0; w < EDGE_THREADS / 64; ++w) { const uint32_t c = wcnt[j][w]; if (w < wv) o += c; run += c; }
+        o += pre[j];
+        if ((pass_a >> j) & 1u) {                      // (a passing element lies below Lp = m * n: its row is one of the slab's)
+            const int q = dom.rows[at.row], g = at.col;
+            src[o] = q < g ? q : g; tgt[o] = q < g ? g : q; val[o] = va[j];
+            ++o;
+        }
+        if ((pass_b >> j) & 1u) {
+            int row1, col1;
+            at.next(dom, row1, col1);
+            const int q = dom.rows[row1], g = col1;
+            src[o] = q < g ? q : g; tgt[o] = q < g ? g : q; val[o] = vb[j];
+        }
+        at.advance(dom);
+    }
+}
+
+// elements one workgroup of a rows pass covers: the three units' chunks are the same 4,096 (each asserts it)
+static_assert(EDGE_CHUNK == 4096, "pc_rows_slab_span");
+int pc_rows_slab_span(int pass) { return pass >= 0 && pass <= 2 ? EDGE_CHUNK : 0; }
+
+static int edge_rows_dom(PcRowsSlab& dom, int64_t Lp, const char* what) {
+    if (dom.n <= 0 || dom.m <= 0 || Lp != (int64_t)dom.m * dom.n) { pc_set_error("%s: a rows slab of %d x %d is not %lld values", what, dom.m, dom.n, (long long)Lp); return PC_ERR_ARG; }
+    dom.adv_rows = EDGE_STRIDE / dom.n; dom.adv_cols = EDGE_STRIDE % dom.n;
+    return PC_OK;
+}
+// counts: [pc_edge_chunks(Lp)] as for pc_launch_edge_count; dom: rows / is_query on the device, Lp = m * n
+int pc_launch_edge_count_rows(const double* vals, int64_t Lp, int as_distance, double thr, PcRowsSlab dom, uint32_t* counts, hipStream_t st) {
+    if (Lp <= 0) return PC_OK;
+    int rc = edge_rows_dom(dom, Lp, "k_edge_count_rows");
+    if (rc != PC_OK) return rc;
+    const dim3 grid((unsigned)pc_edge_chunks(Lp)), block(EDGE_THREADS);
+    if (as_distance) hipLaunchKernelGGL(k_edge_count_rows<1>, grid, block, 0, st, vals, Lp, thr, dom, counts);
+    else hipLaunchKernelGGL(k_edge_count_rows<0>, grid, block, 0, st, vals, Lp, thr, dom, counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_edge_count_rows launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+int pc_launch_edge_emit_rows(const double* vals, int64_t Lp, int as_distance, double thr, PcRowsSlab dom, const uint32_t* offs,
+                             int32_t* src, int32_t* tgt, double* val, hipStream_t st) {
+    if (Lp <= 0) return PC_OK;
+    int rc = edge_rows_dom(dom, Lp, "k_edge_emit_rows");
+    if (rc != PC_OK) return rc;
+    const dim3 grid((unsigned)pc_edge_chunks(Lp)), block(EDGE_THREADS);
+    if (as_distance) hipLaunchKernelGGL(k_edge_emit_rows<1>, grid, block, 0, st, vals, Lp, thr, dom, offs, src, tgt, val);
+    else hipLaunchKernelGGL(k_edge_emit_rows<0>, grid, block, 0, st, vals, Lp, thr, dom, offs, src, tgt, val);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_edge_emit_rows launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
 // counts: [pc_edge_chunks(Lp)] (the caller keeps one more element, zero, for the scan's total)
 int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, uint32_t* counts, hipStream_t st) {
     if (Lp <= 0) return PC_OK;

@@ -6,6 +6,8 @@
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
 // fills a PcSlabRun, calls the driver and copies the results out.  Host only.
+// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree (at the end of the file) grow a stored result by new genomes: the same
+// descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk, slab_rows).
 //
 // The walk they share goes over successive contiguous ranges of target genomes ("slabs": pc_chunk_plan over count[t] = t under
 // slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is installed as a PcShard (owned = t0 .. t1-1,
@@ -54,16 +56,15 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
     return PC_OK;
 }
 
-// Pairs one slab may hold (N > 1).  slab_bytes == 0: the dense triangle, or a quarter of what is free now (an aai / peq slab's plan
-// takes its own half) -- so this runs before the call allocates anything of its own.
-static int64_t slab_max_pairs(pc_ctx* c, int64_t slab_bytes) {
-    const int N = c->dev.N;
+// Pairs one slab may hold (N > 1).  slab_bytes == 0: the whole domain (`whole` values: the dense triangle; a rows slab fill's n_rows * N),
+// or a quarter of what is free now (an aai / peq slab's plan takes its own half) -- so this runs before the call allocates anything of its own.
+static int64_t slab_max_pairs(pc_ctx* c, int64_t slab_bytes, int64_t whole) {
     int64_t max_pairs;
     if (slab_bytes > 0) max_pairs = std::max<int64_t>(slab_bytes / 8, 1);
     else {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
-        max_pairs = std::min<int64_t>(pairs_below(N), std::max<int64_t>((int64_t)((free_b + c->b_edge_slab.cap) / 4 / 8), 1));
+        max_pairs = std::min<int64_t>(std::max<int64_t>(whole, 1), std::max<int64_t>((int64_t)((free_b + c->b_edge_slab.cap) / 4 / 8), 1));
     }
     return std::min<int64_t>(max_pairs, PC_EDGE_MAX_PAIRS);
 }
@@ -165,7 +166,7 @@ static int slab_begin(pc_ctx* c, PcSlabRun& run, float* last_ms) {
 }
 // ... and, N > 1, before the fill allocates anything on the device: the slab size, the events of a timed run
 static int slab_size(pc_ctx* c, PcSlabRun& run) {
-    run.max_pairs = slab_max_pairs(c, run.slab_bytes);
+    run.max_pairs = slab_max_pairs(c, run.slab_bytes, run.rows_form ? (int64_t)run.n_query * c->dev.N : pairs_below(c->dev.N));
     if (run.timed) for (hipEvent_t& e : c->ev_slab) if (!e) PC_HIP(hipEventCreate(&e));
     return PC_OK;
 }
@@ -219,12 +220,12 @@ int PcEdgesFill::begin(pc_ctx* c, PcSlabRun& run) {
     if ((rc = slab_begin(c, run, c->last_edge_ms)) || (rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
     return c->dev.N <= 1 ? (int)PC_OK : slab_size(c, run);
 }
-// compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit
-int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+// compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit; count(cnt, st) and emit(off, st) launch
+// the domain's two kernels
+template <class Count, class Emit> static int edges_slab(pc_ctx* c, PcSlabRun& run, int64_t Lp, Count count, Emit emit) {
     int rc = PC_OK;
     hipStream_t st = c->stream;
     const bool stats = run.timed;
-    const int as_distance = run.as_distance; const double threshold = run.threshold;
     uint32_t* const h_total = c->h_plan.as<uint32_t>();
     int64_t& E = run.n_edges;
     const int64_t nch = pc_edge_chunks(Lp);
@@ -233,7 +234,7 @@ int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp,
     uint32_t* const cnt = c->b_edge_cnt.as<uint32_t>(); uint32_t* const off = c->b_edge_off.as<uint32_t>();
     if (stats) PC_HIP(hipEventRecord(c->ev_slab[0], st));
     PC_HIP(hipMemsetAsync(cnt + nch, 0, 4, st));
-    if ((rc = pc_launch_edge_count(slab, Lp, as_distance, threshold, cnt, st))) return rc;
+    if ((rc = count(cnt, st))) return rc;
     if ((rc = pc_scan_exclusive_u32(cnt, off, nch + 1, c->b_scan_tmp.as<uint32_t>(), (int64_t)(c->b_scan_tmp.cap / 4), st))) return rc;
     if (stats) PC_HIP(hipEventRecord(c->ev_slab[1], st));
     PC_HIP(hipMemcpyAsync(h_total, off + nch, 4, hipMemcpyDeviceToHost, st));
@@ -248,8 +249,7 @@ int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp,
     if ((rc = c->h_edge_src.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) || (rc = c->h_edge_tgt.grow_keep((size_t)(E + Es) * 4, (size_t)E * 4)) ||
         (rc = c->h_edge_val.grow_keep((size_t)(E + Es) * 8, (size_t)E * 8))) return rc;
     if (stats) PC_HIP(hipEventRecord(c->ev_slab[2], st));
-    if ((rc = pc_launch_edge_emit(slab, Lp, as_distance, threshold, shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
-                                  c->b_edge_val.as<double>(), st))) return rc;
+    if ((rc = emit(off, st))) return rc;
     if (stats) PC_HIP(hipEventRecord(c->ev_slab[3], st));
     PC_HIP(hipMemcpyAsync(c->h_edge_src.as<int32_t>() + E, c->b_edge_src.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
     PC_HIP(hipMemcpyAsync(c->h_edge_tgt.as<int32_t>() + E, c->b_edge_tgt.p, (size_t)Es * 4, hipMemcpyDeviceToHost, st));
@@ -266,9 +266,40 @@ int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp,
     E += Es;
     return PC_OK;
 }
-// (no end phase of its own: the edges are in the context's pinned arrays when a walk returns)
+int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+    return edges_slab(c, run, Lp,
+        [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count(slab, Lp, run.as_distance, run.threshold, cnt, st); },
+        [&](const uint32_t* off, hipStream_t st) {
+            return pc_launch_edge_emit(slab, Lp, run.as_distance, run.threshold, shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+                                       c->b_edge_val.as<double>(), st);
+        });
+}
+int PcEdgesFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
+    return edges_slab(c, run, Lp,
+        [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count_rows(slab, Lp, run.as_distance, run.threshold, dom, cnt, st); },
+        [&](const uint32_t* off, hipStream_t st) {
+            return pc_launch_edge_emit_rows(slab, Lp, run.as_distance, run.threshold, dom, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+                                            c->b_edge_val.as<double>(), st);
+        });
+}
+// (no end phase of its own on the triangular walk: the edges are in the context's pinned arrays, in order, when a walk returns.  A rows
+// slab fill's edges came row-major -- by query row, then by the other genome: one host sort by (target, source), keys distinct)
 int PcEdgesFill::end(pc_ctx* c, PcSlabRun& run) {
-    run.src = c->h_edge_src.as<int32_t>(); run.tgt = c->h_edge_tgt.as<int32_t>(); run.val = c->h_edge_val.as<double>();
+    int32_t* const src = c->h_edge_src.as<int32_t>(); int32_t* const tgt = c->h_edge_tgt.as<int32_t>(); double* const val = c->h_edge_val.as<double>();
+    run.src = src; run.tgt = tgt; run.val = val;
+    if (!run.rows_form || run.n_edges < 2) return PC_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t E = (size_t)run.n_edges;
+    std::vector<uint64_t> key(E);
+    for (size_t e = 0; e < E; ++e) key[e] = ((uint64_t)(uint32_t)tgt[e] << 32) | (uint32_t)src[e];
+    if (!std::is_sorted(key.begin(), key.end())) {
+        std::vector<size_t> order(E);
+        for (size_t e = 0; e < E; ++e) order[e] = e;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+        std::vector<double> v(val, val + E);
+        for (size_t e = 0; e < E; ++e) { src[e] = (int32_t)(uint32_t)key[order[e]]; tgt[e] = (int32_t)(key[order[e]] >> 32); val[e] = v[order[e]]; }
+    }
+    if (run.timed) c->last_edge_ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PC_OK;
 }
 // Several devices: nothing travels between them.  The root's pinned arrays are grown to the total and every device's edges laid behind
@@ -340,6 +371,11 @@ int PcComponentsFill::begin(pc_ctx* c, PcSlabRun& run) {
 int PcComponentsFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
     return slab_pass(c, run, c->last_cc_ms, [&](hipStream_t st) {
         return pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, shard, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
+    });
+}
+int PcComponentsFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
+    return slab_pass(c, run, c->last_cc_ms, [&](hipStream_t st) {
+        return pc_launch_cc_union_rows(slab, Lp, run.as_distance, run.strict, run.threshold, dom, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
     });
 }
 // (run.n_edges comes in as the pairs that passed on other devices: a pair lies in exactly one stretch)
@@ -504,8 +540,9 @@ int PcTreeFill::begin(pc_ctx* c, PcSlabRun& run) {
     return PC_OK;
 }
 // One pass: the resident forest, the slab (slab != NULL) and n_foreign staged lists into the other list, which becomes the resident one.
-static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard* shard, const unsigned long long* foreign, int n_foreign,
-                     hipStream_t st) {
+// The slab is a triangular one (shard != NULL) or a rows slab (dom != NULL).
+static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard* shard, const PcRowsSlab* dom, const unsigned long long* foreign,
+                     int n_foreign, hipStream_t st) {
     int rc = PC_OK;
     const int N = c->dev.N, rounds = pc_tree_round_count(N);
     const size_t words = tree_list_words(c);
@@ -516,7 +553,8 @@ static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, 
     unsigned long long* const out = tree_list(c, c->tree_cur ^ 1);
     if ((rc = pc_launch_tree_reset(comp, best, live, rounds, kept, out, N, st)) || (rc = pc_launch_tree_take_counts(out, foreign, n_foreign, N, st))) return rc;
     for (int r = 0; r < rounds; ++r) {
-        if (slab && (rc = pc_launch_tree_scan_slab(slab, Lp, run.as_distance, *shard, comp, best, out, N, live, r, st))) return rc;
+        if (slab && shard && (rc = pc_launch_tree_scan_slab(slab, Lp, run.as_distance, *shard, comp, best, out, N, live, r, st))) return rc;
+        if (slab && dom && (rc = pc_launch_tree_scan_rows(slab, Lp, run.as_distance, *dom, comp, best, out, N, live, r, st))) return rc;
         if ((rc = pc_launch_tree_scan_list(kept, comp, best, N, live, r, st))) return rc;
         for (int f = 0; f < n_foreign; ++f) if ((rc = pc_launch_tree_scan_list(foreign + (size_t)f * words, comp, best, N, live, r, st))) return rc;
         if ((rc = pc_launch_tree_hook(comp, next, best, out, N, live, r, st)) || (rc = pc_launch_tree_flatten(comp, next, best, out, N, live, r, st))) return rc;
@@ -526,7 +564,10 @@ static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, 
     return PC_OK;
 }
 int PcTreeFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
-    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, &shard, nullptr, 0, st); });
+    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, &shard, nullptr, nullptr, 0, st); });
+}
+int PcTreeFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
+    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, nullptr, &dom, nullptr, 0, st); });
 }
 int PcTreeFill::end(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
@@ -578,7 +619,7 @@ int PcTreeFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& r
     pc_ctx* root = ctx[0];
     for (size_t r = 1; r < runs.size(); ++r) runs[0].tree_launched += runs[r].tree_launched;
     PC_HIP(hipEventRecord(root->ev[0], root->stream));
-    if (n_foreign > 0 && (rc = tree_pass(root, runs[0], nullptr, 0, nullptr, (const unsigned long long*)stage, n_foreign, root->stream))) return rc;
+    if (n_foreign > 0 && (rc = tree_pass(root, runs[0], nullptr, 0, nullptr, nullptr, (const unsigned long long*)stage, n_foreign, root->stream))) return rc;
     PC_HIP(hipEventRecord(root->ev[1], root->stream));
     return PC_OK;
 }
@@ -609,3 +650,159 @@ extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_
     if (launched_rounds) *launched_rounds = c->last_tree_rounds[1];
     return PC_OK;
 }
+
+// ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree grow a STORED result.  The pairs of the call are
+// those that touch a query genome (the new genomes of a grown collection): k query rows cost k N pairs, not N^2 / 2.  What is stored
+// stands for the pairs among the other genomes: the components fill takes their labelling as the initial parent[], the tree fill
+// their tree's keys as the resident forest (MST(A + B) = MST(MST(A) + B), the invariant the slabs already keep); a stored edge list
+// needs nothing on the device -- the caller merges the two lists.  The same descriptions run: check -> begin -> seed -> the rows walk
+// -> end.  The walk cuts the query rows into consecutive ranges of at most max(1, slab_bytes / 8 / N) rows (0: by slab_max_pairs'
+// rule), fills each with the rows fill itself (pc_fill_rows_dev) into the context's slab buffer as f64[m][N], and hands it to the
+// description's slab_rows with the PcRowsSlab that says which of its values are pairs of the call.  One slab is resident at a time; the
+// rows fill touches no shard state, so the caller's is in force throughout.
+static int rows_arg_check(const pc_ctx* c, const char* who, const int32_t* rows, int n_rows) {
+    const int N = c->dev.N;
+    if (n_rows < 0) { pc_set_error("%s: n_rows %d", who, n_rows); return PC_ERR_ARG; }
+    if (n_rows > 0 && !rows) { pc_set_error("%s: rows is NULL", who); return PC_ERR_ARG; }
+    for (int k = 0; k < n_rows; ++k)
+        if (rows[k] < 0 || rows[k] >= N || (k > 0 && rows[k] <= rows[k - 1])) {
+            pc_set_error("%s: rows must be strictly ascending genome indices below %d (rows[%d] = %d)", who, N, k, rows[k]); return PC_ERR_ARG;
+        }
+    return PC_OK;
+}
+
+template <class Fill> static int rows_walk(pc_ctx* c, PcSlabRun& run, const int32_t* rows, int n_rows) {
+    int rc = PC_OK;
+    const int N = c->dev.N;
+    hipStream_t st = c->stream;
+    const int per = (int)std::min<int64_t>(std::max<int64_t>(run.max_pairs / N, 1), n_rows);
+    if ((rc = c->b_edge_slab.ensure((size_t)per * N * 8))) return abi_rc(rc);
+    double* const slab = c->b_edge_slab.as<double>();
+    std::vector<int32_t> h_rows(rows, rows + n_rows);
+    std::vector<uint8_t> h_query((size_t)N, 0);
+    for (int k = 0; k < n_rows; ++k) h_query[rows[k]] = 1;
+    if ((rc = wait_last_work(c, st, false)) || (rc = upload_vec(c->b_rq_rows, h_rows)) || (rc = upload_vec(c->b_rq_query, h_query))) return rc;
+    for (int r0 = 0; r0 < n_rows; r0 += per) {
+        const int m = std::min(per, n_rows - r0);
+        pc_stats one; memset(&one, 0, sizeof(one));
+        // (the rows fill waits for the pass the slab before it left running before it rewrites the slab and its own tables)
+        if ((rc = pc_fill_rows_dev(c, run.metric, run.as_distance, rows + r0, m, slab, st, run.timed ? &one : nullptr))) return rc;
+        if (run.timed) pc_stats_add(run.sum, one);
+        const PcRowsSlab dom{m, N, c->b_rq_rows.as<int32_t>() + r0, c->b_rq_query.as<uint8_t>(), 0, 0};
+        if ((rc = Fill::slab_rows(c, run, slab, (int64_t)m * N, dom))) return rc;
+        ++run.n_slabs;
+    }
+    return PC_OK;
+}
+
+// seed(): the stored result onto the device, after begin has sized and initialised the state (N > 1 only)
+template <class Fill, class Seed> static int pc_rows_slab_fill(pc_ctx* c, PcSlabRun& run, const int32_t* rows, int n_rows, Seed seed) {
+    int rc = PC_OK;
+    PC_ON_DEVICE(c);
+    PcRange range(Fill::range);
+    run.rows_form = true; run.n_query = n_rows;
+    if ((rc = Fill::begin(c, run))) return rc;
+    if (c->dev.N > 1) {
+        if ((rc = seed())) return rc;
+        if (n_rows > 0 && (rc = rows_walk<Fill>(c, run, rows, n_rows))) return rc;
+    }
+    return Fill::end(c, run);
+}
+
+extern "C" int pc_fill_rows_edges(pc_ctx* c, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
+                                  const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_fill_rows_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, PcEdgesFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+    if ((rc = pc_rows_slab_fill<PcEdgesFill>(c, run, rows, n_rows, [] { return (int)PC_OK; }))) return rc;
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
+    return PC_OK;
+}
+
+extern "C" int pc_fill_rows_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, const int32_t* rows, int n_rows,
+                                       const int32_t* seed_labels, int64_t slab_bytes, const int32_t** labels, int32_t* n_components, int64_t* n_edges,
+                                       int32_t* n_slabs, pc_stats* stats) {
+    if (labels) *labels = nullptr;
+    if (n_components) *n_components = 0;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_fill_rows_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
+    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
+    int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, PcComponentsFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+    const int N = c->dev.N;
+    std::vector<int32_t> seed;                                              // (a copy: the caller may hand back the labels an earlier call lent out)
+    if (seed_labels) {
+        seed.assign(seed_labels, seed_labels + N);
+        for (int g = 0; g < N; ++g)
+            if (seed[g] < 0 || seed[g] > g || seed[seed[g]] != seed[g]) {
+                pc_set_error("%s: seed_labels[%d] = %d is not the smallest member of a component (0 <= label <= genome, a label labels itself)", run.who, g, seed[g]);
+                return PC_ERR_ARG;
+            }
+    }
+    rc = pc_rows_slab_fill<PcComponentsFill>(c, run, rows, n_rows, [&]() -> int {
+        if (seed.empty()) return PC_OK;
+        // parent[g] = the stored label, through the pinned labels image (end() rewrites it only after the stream has drained)
+        memcpy(c->h_cc_labels.p, seed.data(), (size_t)N * 4);
+        PC_HIP(hipMemcpyAsync(c->b_cc_parent.p, c->h_cc_labels.p, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        return PC_OK;
+    });
+    if (rc != PC_OK) return rc;
+    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
+    return PC_OK;
+}
+
+extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const int32_t* rows, int n_rows, const int32_t* seed_src, const int32_t* seed_tgt,
+                                 const double* seed_val, int32_t n_seed, int64_t slab_bytes, const int32_t** src, const int32_t** tgt, const double** val,
+                                 int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    if (src) *src = nullptr;
+    if (tgt) *tgt = nullptr;
+    if (val) *val = nullptr;
+    if (n_edges) *n_edges = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_fill_rows_tree"; run.metric = metric; run.as_distance = as_distance;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
+    int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, PcTreeFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+    const int N = c->dev.N;
+    if (n_seed < 0 || n_seed > std::max(N - 1, 0)) { pc_set_error("%s: %d seed edges for %d genomes (a forest holds at most N - 1)", run.who, n_seed, N); return PC_ERR_ARG; }
+    if (n_seed > 0 && !(seed_src && seed_tgt && seed_val)) { pc_set_error("%s: a seed array is NULL", run.who); return PC_ERR_ARG; }
+    std::vector<unsigned long long> keys((size_t)n_seed);                   // (packed before begin: the caller may hand back the edges an earlier call lent out)
+    for (int i = 0; i < n_seed; ++i) {
+        const double v = seed_val[i], k = __builtin_rint(v * 1.0e6);
+        const bool millionth = k >= 0.0 && k <= 1.0e6 && k / 1000000.0 == v;
+        const int micro = millionth ? (run.as_distance ? (int)k : PC_TREE_MICRO_MAX - (int)k) : -1;
+        keys[i] = seed_tgt[i] < N ? pc_tree_key(micro, seed_src[i], seed_tgt[i]) : PC_TREE_NONE;
+        if (keys[i] == PC_TREE_NONE) {
+            pc_set_error("%s: seed edge %d (%d, %d, %.17g) is no key: source < target < %d and a value that is a millionth in [0, 1]", run.who, i,
+                         seed_src[i], seed_tgt[i], v, N);
+            return PC_ERR_ARG;
+        }
+    }
+    rc = pc_rows_slab_fill<PcTreeFill>(c, run, rows, n_rows, [&]() -> int {
+        if (n_seed == 0) return PC_OK;
+        // the stored tree as the resident forest in place of the empty one, through the pinned key image (end() rewrites it after the stream has drained)
+        unsigned long long* const h = c->h_tree_keys.as<unsigned long long>();
+        memcpy(h, keys.data(), (size_t)n_seed * 8);
+        h[N - 1] = (unsigned long long)n_seed; h[N] = 0ull; h[N + 1] = 0ull;
+        PC_HIP(hipMemcpyAsync(tree_list(c, 0), h, tree_list_words(c) * 8, hipMemcpyHostToDevice, c->stream));
+        if (n_rows > 0) return PC_OK;
+        // no query row: one pass over the list alone leaves the tree of the seed edges (a seed that is no forest comes out short, and end() says so)
+        return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, nullptr, 0, nullptr, nullptr, nullptr, 0, st); });
+    });
+    if (rc != PC_OK) return rc;
+    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
+    return PC_OK;
+}
+
+// elements one workgroup of a rows pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by
+extern "C" int pc_rows_pass_span(int pass_kind) { return pc_rows_slab_span(pass_kind); }

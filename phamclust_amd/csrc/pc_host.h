@@ -117,6 +117,7 @@ struct pc_ctx {
     DevBuf b_grp_genome, b_grp_end, b_grp_rowbase, b_grp_trow, b_grp_tcol;   // the domain of the last groups fill (PcGroups)
     // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
     DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
+    DevBuf b_rq_rows, b_rq_query;           // a rows slab fill: every query row of the call, ascending, and is_query[N] (PcRowsSlab)
     PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
     hipEvent_t ev_slab[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the passes over a slab, of whichever of the three fills runs: created by the first one that is asked for stats
     float last_edge_ms[2] = {0.f, 0.f};     // count + scan + emit, edges' D2H of the last pc_fill_edges with stats (pc_last_edge_times)
@@ -253,6 +254,8 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
 //   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device
+//   slab_rows   the same for one slab of a rows slab fill (pc_rows_slab_fill, pc_fill_slabs.hip: f64[m][N] of a range of query rows, the
+//           pairs a PcRowsSlab says); edges, components and tree have one, begin and end are the triangular walk's
 //   end     labels / finish and the D2H copy; the result pointers and counts into the run
 //   ship_bytes, ship, merge   several devices: the state a non-root device sends to its slice of the root's staging buffer (0 bytes:
 //           nothing travels between devices), and how the root takes the others' state in before its end
@@ -278,12 +281,15 @@ struct PcSlabRun {
     int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (before end: on the other devices)
     int32_t n_components = 0;
     int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
+    bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
+    int32_t n_query = 0;                    // ... its query rows (all slabs)
 };
 #define PC_SLAB_FILL(Name, tag, text)                                                                                                   \
     struct Name {                                                                                                                       \
         static constexpr const char *what = text, *who = "pc_fill_" tag, *range = "pc:fill_" tag, *multi_range = "pc:multi_fill_" tag; \
         static int begin(pc_ctx* c, PcSlabRun& run);                                                                                    \
         static int slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard);                               \
+        static int slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom);                         \
         static int end(pc_ctx* c, PcSlabRun& run);                                                                                      \
         static size_t ship_bytes(const pc_ctx* root, const PcSlabRun& run);                                                             \
         static int ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int n_foreign);                                 \

@@ -176,6 +176,56 @@ __global__ __launch_bounds__(TREE_THREADS) void k_tree_scan_slab(const double* _
     if (bad) atomicAdd(out + n, (unsigned long long)bad);
 }
 
+// k_tree_scan_slab over a rows slab (PcRowsSlab: vals = f64[m][n] seen flat, Lp = m * n; pc_fill_rows_tree): the LIVE elements only.
+// The same key, domain check and violation count, the same early return.  A wave's 128 consecutive elements lie mostly in ONE row, so
+// here the side the lanes share is the QUERY genome's component -- whether the query is the pair's source or its target -- and that
+// side goes through the wave's reduction; the other genome's component is lowered at once.  (row, column) come from a PcRowsCursor.
+static_assert(TREE_CHUNK == 4096, "pc_rows_slab_span");
+template <int DIST> __device__ __forceinline__ void pc_tree_element_rows(double v, int q, int g, const int32_t* __restrict__ comp, tree_key_t* best,
+                                                                         tree_key_t& key, int& cq_out, uint32_t& bad) {
+    key = PC_TREE_NONE; cq_out = -1;
+    const int cq = comp[q], cg = comp[g];
+    if (cq == cg) return;
+    key = pc_tree_pair_key<DIST>(v, q < g ? q : g, q < g ? g : q, bad);
+    if (key == PC_TREE_NONE) return;
+    pc_tree_lower(best, cg, key);
+    if (key < pc_tree_read(best + cq)) cq_out = cq;
+}
+
+template <int DIST>
+__global__ __launch_bounds__(TREE_THREADS) void k_tree_scan_rows(const double* __restrict__ vals, int64_t Lp, PcRowsSlab dom, const int32_t* __restrict__ comp,
+                                                                 tree_key_t* best, tree_key_t* out, int n, const uint32_t* __restrict__ live) {
+    if (*live == 0u) return;                           // (the whole grid)
+    __shared__ int2 origin;
+    const int lane = threadIdx.x & 63;
+    const int64_t i0 = (int64_t)blockIdx.x * TREE_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
+    __syncthreads();
+    PcRowsCursor at;
+    at.start(origin, threadIdx.x * 2u, dom);
+    uint32_t bad = 0;
+#pragma unroll 1
+    for (int j = 0; j < TREE_ITERS; ++j) {             // (every lane takes every turn: the reductions below are the wave's)
+        const int64_t i = base + (int64_t)j * TREE_STRIDE;
+        double a, b;
+        const int have = pc_tree_load(vals, i, Lp, a, b);
+        tree_key_t key_a = PC_TREE_NONE, key_b = PC_TREE_NONE;
+        int cq_a = -1, cq_b = -1, q;
+        if (have > 0 && pc_rows_live(dom, at.row, at.col, q)) pc_tree_element_rows<DIST>(a, q, at.col, comp, best, key_a, cq_a, bad);
+        if (have > 1) {
+            int row1, col1;
+            at.next(dom, row1, col1);
+            if (pc_rows_live(dom, row1, col1, q)) pc_tree_element_rows<DIST>(b, q, col1, comp, best, key_b, cq_b, bad);
+        }
+        if (cq_b >= 0 && cq_b == cq_a) { key_a = key_b < key_a ? key_b : key_a; cq_b = -1; }
+        else if (cq_b >= 0 && cq_a < 0) { key_a = key_b; cq_a = cq_b; cq_b = -1; }
+        pc_tree_lower_shared(best, cq_a, key_a, lane);
+        if (__any(cq_b >= 0)) pc_tree_lower_shared(best, cq_b, key_b, lane);      // (a lane whose two elements lie in two rows)
+        at.advance(dom);
+    }
+    if (bad) atomicAdd(out + n, (unsigned long long)bad);
+}
+
 // list: [n + PC_TREE_TAIL], list[n - 1] keys in it
 __global__ __launch_bounds__(256) void k_tree_scan_list(const tree_key_t* __restrict__ list, const int32_t* __restrict__ comp, tree_key_t* best, int n,
                                                         const uint32_t* __restrict__ live) {
@@ -272,6 +322,18 @@ int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, co
     if (as_distance) hipLaunchKernelGGL((k_tree_scan_slab<1>), grid, block, 0, st, vals, Lp, sh, comp, best, out, n, live + r);
     else hipLaunchKernelGGL((k_tree_scan_slab<0>), grid, block, 0, st, vals, Lp, sh, comp, best, out, n, live + r);
     return tree_check("k_tree_scan_slab");
+}
+
+// dom: rows / is_query on the device, dom.n == n, Lp = m * n; comp, best: [n]; out: the list that takes the violations
+int pc_launch_tree_scan_rows(const double* vals, int64_t Lp, int as_distance, PcRowsSlab dom, const int32_t* comp, unsigned long long* best,
+                             unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st) {
+    if (Lp <= 0 || n < 2) return PC_OK;
+    if (dom.n != n || dom.m <= 0 || Lp != (int64_t)dom.m * dom.n) { pc_set_error("k_tree_scan_rows: a rows slab of %d x %d is not %lld values of %d genomes", dom.m, dom.n, (long long)Lp, n); return PC_ERR_ARG; }
+    dom.adv_rows = TREE_STRIDE / dom.n; dom.adv_cols = TREE_STRIDE % dom.n;
+    const dim3 grid((unsigned)((Lp + TREE_CHUNK - 1) / TREE_CHUNK)), block(TREE_THREADS);
+    if (as_distance) hipLaunchKernelGGL((k_tree_scan_rows<1>), grid, block, 0, st, vals, Lp, dom, comp, best, out, n, live + r);
+    else hipLaunchKernelGGL((k_tree_scan_rows<0>), grid, block, 0, st, vals, Lp, dom, comp, best, out, n, live + r);
+    return tree_check("k_tree_scan_rows");
 }
 
 int pc_launch_tree_scan_list(const unsigned long long* list, const int32_t* comp, unsigned long long* best, int n, const uint32_t* live, int r,

@@ -76,7 +76,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_fill_components", "pc_last_component_times", "pc_fill_groups", "pc_fill_groups_dev", "pc_group_pair_offsets", "pc_group_tiles",
            "pc_fill_nearest", "pc_last_nearest_times", "pc_multi_fill_edges", "pc_multi_fill_components", "pc_multi_fill_nearest",
            "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan", "pc_fill_tree", "pc_multi_fill_tree", "pc_last_tree_times",
-           "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts"]
+           "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
+           "pc_rows_pass_span"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -157,6 +158,16 @@ def load():
     L.pc_tree_key.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     L.pc_tree_key.restype = ctypes.c_uint64
     L.pc_tree_key_parts.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.pc_fill_rows_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _i32p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p),
+                                     ctypes.POINTER(_i32p), ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_components.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _i32p, ctypes.c_int, _i32p, ctypes.c_int64,
+                                          ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_tree.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int32, ctypes.c_int64,
+                                    ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int32),
+                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_rows_pass_span.argtypes = [ctypes.c_int]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -653,6 +664,100 @@ class Context(_SlabFills):
         return dict(stats.as_dict(), **own, **{first: float(a.value), second: float(b.value)})
 
     NEAREST_MAX_K = 64                    # PC_NEAREST_MAX_K: a genome's list lives one entry per lane of a wave
+
+    # -- the rows forms of fill_edges / fill_components / fill_tree: a stored result grown by new genomes (one GPU) -----------------------
+    ROWS_PASSES = ("edges", "components", "tree")
+
+    @staticmethod
+    def rows_pass_span(kind):
+        """Values one workgroup of the rows pass of ``kind`` (``"edges"``, ``"components"``, ``"tree"``) covers (``pc_rows_pass_span``;
+        host arithmetic, no GPU): what a test of the passes' workgroup seams sizes its slabs by."""
+        return int(load().pc_rows_pass_span(Context.ROWS_PASSES.index(kind)))
+
+    @staticmethod
+    def rows_slabs(n, n_rows, slab_bytes):
+        """The slabs a rows form walks for ``n_rows`` query rows of ``n`` genomes under ``slab_bytes`` (> 0): consecutive ranges of
+        at most ``max(1, slab_bytes // 8 // n)`` rows (host arithmetic, no GPU)."""
+        if int(slab_bytes) <= 0:
+            raise ValueError("rows_slabs: slab_bytes must be positive (0 = automatic is decided on the device, by the free HBM)")
+        per = max(1, int(slab_bytes) // 8 // max(int(n), 1))
+        return (int(n_rows) + per - 1) // per if int(n) > 1 else 0
+
+    def _rows_fill(self, kind, metric, *args):
+        stats = self._before_slab_fill(metric)
+        self._check(getattr(self._lib, "pc_fill_rows_" + kind)(self._h, METRIC_IDS[metric], *args, stats))
+        return stats
+
+    @staticmethod
+    def _rows_arg(rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        return rows, _ptr(rows if rows.size else np.zeros(1, dtype=np.int32), _i32p), int(rows.shape[0])
+
+    def fill_rows_edges(self, metric, threshold, rows, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The pairs that touch a query genome of ``rows`` (distinct indices, strictly ascending: the new genomes of a grown
+        collection) and pass ``threshold`` (:meth:`fill_edges`' predicate), each once, as ``(src, tgt, val)`` sorted by ``tgt``, then
+        ``src``: ``len(rows) * N`` pairs filled instead of ``N (N - 1) / 2``, the whole fill's values.  Merged with a stored list of
+        the other genomes' pairs (``matrix.edges_extend``) it is :meth:`fill_edges`' list of the whole collection.  ``slab_bytes`` cuts
+        the rows into slabs of ``max(1, slab_bytes // 8 // N)`` (0 = automatic).  Copies, or loans with ``borrow``; ``want_stats`` as
+        :meth:`fill_edges`."""
+        rows, prow, n_rows = self._rows_arg(rows)
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._rows_fill("edges", metric, int(bool(as_distance)), float(threshold), prow, n_rows, int(slab_bytes),
+                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        return (*out, self._slab_stats("edges", stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
+
+    def fill_rows_components(self, metric, threshold, rows, seed_labels=None, as_distance=True, strict=True, slab_bytes=0, want_stats=False,
+                             borrow=False):
+        """:meth:`fill_components`' labels of the whole collection from a stored labelling of the other genomes: ``seed_labels``
+        (int32[N]: the smallest member of each genome's stored component, a query genome labelling itself; None: every genome its
+        own component) is the initial forest, and the passing pairs that touch a query genome of ``rows`` are united into it.
+        ``n_edges`` of the stats counts those pairs only."""
+        rows, prow, n_rows = self._rows_arg(rows)
+        seed = None
+        if seed_labels is not None:
+            seed = np.ascontiguousarray(seed_labels, dtype=np.int32).reshape(-1)
+            if seed.shape[0] != self.n_genomes:
+                raise ValueError(f"fill_rows_components: seed_labels holds {seed.shape[0]} entries for {self.n_genomes} genomes")
+        pl = _i32p()
+        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._rows_fill("components", metric, int(bool(as_distance)), float(threshold), int(bool(strict)), prow, n_rows,
+                                _ptr(seed, _i32p) if seed is not None and seed.size else None, int(slab_bytes),
+                                ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl))
+        n = self.n_genomes
+        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
+        if not want_stats:
+            return labels
+        return labels, self._slab_stats("components", stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+
+    def fill_rows_tree(self, metric, rows, seed=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """:meth:`fill_tree`'s tree of the whole collection from the stored tree of the other genomes: ``seed = (src, tgt, val)``, its
+        edges in the uploaded collection's numbering (at most N - 1; values of the call's kind, millionths in [0, 1]), is the
+        resident forest the pairs that touch a query genome of ``rows`` are merged into -- MST(A + B) = MST(MST(A) + B).  The
+        library refuses a seed that is no key, and a result that does not span the collection."""
+        rows, prow, n_rows = self._rows_arg(rows)
+        if seed is None:
+            seed = ((), (), ())
+        s_src = np.ascontiguousarray(seed[0], dtype=np.int32).reshape(-1)
+        s_tgt = np.ascontiguousarray(seed[1], dtype=np.int32).reshape(-1)
+        s_val = np.ascontiguousarray(seed[2], dtype=np.float64).reshape(-1)
+        if not s_src.shape == s_tgt.shape == s_val.shape:
+            raise ValueError("fill_rows_tree: the seed's source, target and value arrays differ in length")
+        n_seed = int(s_src.shape[0])
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        stats = self._rows_fill("tree", metric, int(bool(as_distance)), prow, n_rows,
+                                _ptr(s_src, _i32p) if n_seed else None, _ptr(s_tgt, _i32p) if n_seed else None, _ptr(s_val, _f64p) if n_seed else None,
+                                n_seed, int(slab_bytes), ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        return (*out, self._slab_stats("tree", stats, n_edges=int(n.value), n_slabs=int(nsl.value), **self._tree_rounds()))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -656,6 +656,60 @@ def matrix_to_adjacency(matrix, filepath, skip_zero=False):
 # ---------------------------------------------------------------------------------------
 # Sparse delivery: the pairs within a threshold, without the dense matrix
 # ---------------------------------------------------------------------------------------
+def _grown_positions(stored_nodes, nodes, rows, caller):
+    """What the host statements of the ``*_extend`` calls share: ``old_at[k]`` = the position in ``nodes`` of stored node k (int64,
+    strictly increasing, else ValueError; KeyError for a stored node ``nodes`` lacks) and ``rows`` as an ascending int64 array that
+    must name exactly the positions of the nodes that are not stored."""
+    nodes = list(nodes)
+    index = {name: k for k, name in enumerate(nodes)}
+    if len(index) != len(nodes):
+        raise ValueError(f"{caller}: node names must be distinct")
+    stranger = next((node for node in stored_nodes if node not in index), None)
+    if stranger is not None:
+        raise KeyError(f"{caller}: stored node '{stranger}' is not among the nodes")
+    old_at = np.fromiter((index[node] for node in stored_nodes), dtype=np.int64, count=len(stored_nodes))
+    if old_at.shape[0] > 1 and not (np.diff(old_at) > 0).all():
+        k = int(np.flatnonzero(np.diff(old_at) <= 0)[0])
+        raise ValueError(f"{caller}: stored nodes '{stored_nodes[k]}' and '{stored_nodes[k + 1]}' come in another order in the grown collection: "
+                         "orientation and tie order follow the order, so a result can only be grown in its own order")
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    is_old = np.zeros(len(nodes), dtype=bool)
+    is_old[old_at] = True
+    if not np.array_equal(rows, np.flatnonzero(~is_old)):
+        raise ValueError(f"{caller}: rows must be the ascending positions of exactly the nodes that are not stored")
+    return old_at, rows
+
+
+def _live_row_pairs(n, rows, values):
+    """The pairs of a rows array, each once: ``values[i, g]`` is the pair {rows[i], g}; the diagonal is none, and a pair of two
+    rows is taken in the row of the smaller one (the rule of the library's rows passes).  Returns (source, target, weight) with
+    source < target, row-major."""
+    values = np.asarray(values, dtype=np.float64).reshape(len(rows), n)
+    if len(rows) == 0:
+        return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+    is_row = np.zeros(n, dtype=bool)
+    is_row[rows] = True
+    q = np.repeat(rows, n).reshape(len(rows), n)
+    g = np.tile(np.arange(n, dtype=np.int64), (len(rows), 1))
+    live = (g != q) & ~(is_row[g] & (g < q))
+    q, g = q[live], g[live]
+    return np.minimum(q, g), np.maximum(q, g), values[live]
+
+
+def _positions_without(nodes, names, caller):
+    """(positions kept, ascending; new position of every old one or -1) of ``nodes`` without ``names`` (KeyError for a stranger)."""
+    index = {name: k for k, name in enumerate(nodes)}
+    drop = set()
+    for name in names:
+        if name not in index:
+            raise KeyError(f"{caller}: '{name}' is not among the nodes")
+        drop.add(index[name])
+    keep_at = np.asarray([k for k in range(len(nodes)) if k not in drop], dtype=np.int64)
+    new_at = np.full(len(nodes), -1, dtype=np.int64)
+    new_at[keep_at] = np.arange(keep_at.shape[0])
+    return keep_at, new_at
+
+
 class SparseEdges:
     """The edges of a matrix that pass a threshold -- ``weight <= threshold`` on distances, ``>= threshold`` on similarities -- as
     three parallel arrays over ``nodes``: ``source[e] < target[e]`` (indices into ``nodes``), sorted by target, then source, and
@@ -746,6 +800,31 @@ class SparseEdges:
         np.minimum.at(smallest, comp, np.arange(n))
         return smallest[comp].astype(np.int32)
 
+    def extended(self, nodes, rows, values):
+        """This list grown to ``nodes``: the host statement of ``edges_extend``.  ``nodes`` holds this list's nodes in their order
+        and, at the ascending positions ``rows``, the new ones; ``values`` is float64[len(rows), len(nodes)], ``values[i, g]`` the
+        value of the pair {rows[i], g} (a rows fill; any callable's values on the host).  The result is the stored list re-indexed
+        -- the map from old to new positions is strictly increasing, so every edge keeps source < target and the list its order --
+        merged with the new pairs within the threshold: ``SparseEdges.from_dense`` of the grown matrix, element for element."""
+        if self.threshold is None:
+            raise ValueError("SparseEdges.extended: this list carries no threshold, so which new pairs belong to it is undefined")
+        old_at, rows = _grown_positions(self.nodes, nodes, rows, "SparseEdges.extended")
+        src, tgt, w = _live_row_pairs(len(nodes), rows, values)
+        keep = (w <= self.threshold) if self.is_distance else (w >= self.threshold)
+        src = np.concatenate([old_at[self.source], src[keep]])
+        tgt = np.concatenate([old_at[self.target], tgt[keep]])
+        w = np.concatenate([self.weight, w[keep]])
+        order = np.lexsort((src, tgt))
+        return SparseEdges(nodes, src[order], tgt[order], w[order], is_distance=self.is_distance, threshold=self.threshold)
+
+    def without(self, names):
+        """This list without the genomes ``names``: their edges dropped, the others re-indexed.  Exact: it is the list a fill of the
+        remaining genomes delivers (a pair's value and the order depend on nothing but its two genomes and their relative order)."""
+        keep_at, new_at = _positions_without(self.nodes, names, "SparseEdges.without")
+        keep = (new_at[self.source] >= 0) & (new_at[self.target] >= 0)
+        return SparseEdges([self.nodes[k] for k in keep_at.tolist()], new_at[self.source[keep]], new_at[self.target[keep]], self.weight[keep],
+                           is_distance=self.is_distance, threshold=self.threshold)
+
     def inverted(self):
         """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SymMatrix.invert`` does (matrix.py:236-247)."""
         return SparseEdges(self.nodes, self.source, self.target, np.round(1.0 - self.weight, 6), is_distance=not self.is_distance,
@@ -821,6 +900,38 @@ class Components:
     def groups(self):
         """The same as lists of node names."""
         return [[self.nodes[i] for i in group.tolist()] for group in self.group_indices()]
+
+    def extended(self, nodes, rows, values, threshold, is_distance=True, strict=True):
+        """This partition grown to ``nodes``: the host statement of ``components_extend`` (arguments as ``SparseEdges.extended``;
+        ``threshold``, ``is_distance`` and ``strict`` say which new pairs are edges, as ``SparseEdges.components`` does).  The stored
+        labels, re-indexed, are the forest the passing new pairs are united into; labels stay the smallest member's index."""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        old_at, rows = _grown_positions(self.nodes, nodes, rows, "Components.extended")
+        n = len(nodes)
+        src, tgt, w = _live_row_pairs(n, rows, values)
+        if is_distance:
+            keep = w < threshold if strict else w <= threshold
+        else:
+            keep = w > threshold if strict else w >= threshold
+        src = np.concatenate([old_at[self.labels], src[keep]])
+        tgt = np.concatenate([old_at, tgt[keep]])
+        graph = coo_matrix((np.ones(src.shape[0], dtype=np.int8), (src, tgt)), shape=(n, n))
+        _, comp = connected_components(graph, directed=False)
+        smallest = np.full(int(comp.max()) + 1 if n else 0, n, dtype=np.int64)
+        np.minimum.at(smallest, comp, np.arange(n))
+        return Components(nodes, smallest[comp].astype(np.int32))
+
+    def without(self, names):
+        """This partition restricted to the genomes that remain: every group loses the members named, labels stay the smallest
+        member's index.  Each group that remains is a union of whole components of the smaller collection, and the components of
+        the smaller collection itself wherever the genomes removed were no articulation points: a component held together only by
+        a removed genome stays one group here (the labels do not say which pairs were edges).  ``SparseEdges.without(names)
+        .components(...)`` is exact; so is a components fill of the remaining genomes."""
+        keep_at, _ = _positions_without(self.nodes, names, "Components.without")
+        labels = self.labels[keep_at]
+        _, first, inverse = np.unique(labels, return_index=True, return_inverse=True)       # first member kept of every group = its smallest
+        return Components([self.nodes[k] for k in keep_at.tolist()], first[inverse].astype(np.int32))
 
 
 def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, slab_bytes=0):
@@ -1045,6 +1156,29 @@ def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 
+def _kruskal(n, s, t, w, is_distance):
+    """Kruskal's algorithm over the pairs (s[e], t[e]) of weight w[e] in the tree's total order -- ``np.lexsort`` over (source, target,
+    weight): the weight first, better first -- with a union-find: the indices of the accepted pairs, in that order."""
+    order = np.lexsort((s, t, w if is_distance else -w))
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    kept = []
+    for e, a, b in zip(order.tolist(), s[order].tolist(), t[order].tolist()):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+            kept.append(e)
+            if len(kept) == n - 1:
+                break
+    return np.asarray(kept, dtype=np.int64)
+
+
 class SingleLinkageTree:
     """The single-linkage dendrogram of a matrix as the ``N - 1`` edges of its minimum spanning tree, in merge order: ``source[i] <
     target[i]`` (indices into ``nodes``) joined at ``weight[i]``.  ONE total order on the pairs decides everything: the better weight
@@ -1078,25 +1212,32 @@ class SingleLinkageTree:
         w = data[s, t]
         if np.isnan(w).any():
             raise TypeError("cannot build the tree of a matrix with unset edges")
-        order = np.lexsort((s, t, w if matrix.is_distance else -w))
-        parent = list(range(n))
-
-        def find(x):
-            while parent[x] != x:
-                parent[x] = parent[parent[x]]
-                x = parent[x]
-            return x
-
-        kept = []
-        for e, a, b in zip(order.tolist(), s[order].tolist(), t[order].tolist()):
-            ra, rb = find(a), find(b)
-            if ra != rb:
-                parent[max(ra, rb)] = min(ra, rb)
-                kept.append(e)
-                if len(kept) == n - 1:
-                    break
-        kept = np.asarray(kept, dtype=np.int64)
+        kept = _kruskal(n, s, t, w, matrix.is_distance)
         return cls(matrix.nodes, s[kept], t[kept], w[kept], is_distance=matrix.is_distance)
+
+    def extended(self, nodes, rows, values):
+        """This tree grown to ``nodes``: the host statement of ``tree_extend`` (arguments as ``SparseEdges.extended``).  MST(A + B) =
+        MST(MST(A) + B): Kruskal's algorithm in the one total order over the stored edges, re-indexed, and the new pairs -- the
+        order is strict and the re-indexing increasing, so the result is the canonical tree of the grown collection."""
+        old_at, rows = _grown_positions(self.nodes, nodes, rows, "SingleLinkageTree.extended")
+        n = len(nodes)
+        src, tgt, w = _live_row_pairs(n, rows, values)
+        if np.isnan(w).any():
+            raise TypeError("cannot grow a tree by unset edges")
+        s = np.concatenate([old_at[self.source], src])
+        t = np.concatenate([old_at[self.target], tgt])
+        w = np.concatenate([self.weight, w])
+        kept = _kruskal(n, s, t, w, self.is_distance)
+        if kept.shape[0] != max(n - 1, 0):
+            raise ValueError("SingleLinkageTree.extended: the stored edges and the new pairs do not connect the nodes")
+        return SingleLinkageTree(nodes, s[kept], t[kept], w[kept], is_distance=self.is_distance)
+
+    def without(self, names):
+        """Refused: a minimum spanning tree is not closed under vertex deletion -- the tree of the remaining genomes may need
+        pairs this tree dropped because a removed genome offered a better path -- so removal needs a fill (``tree_de_novo`` over the
+        remaining genomes; their stored tree edges may seed nothing: every pair among them is in question)."""
+        raise NotImplementedError("SingleLinkageTree.without: a minimum spanning tree is not closed under vertex deletion; removing genomes "
+                                  "needs a fill of the remaining ones (tree_de_novo)")
 
     def __len__(self):
         return int(self.weight.shape[0])
@@ -1187,6 +1328,254 @@ def tree_de_novo(genomes, func, as_distance=True, slab_bytes=0):
                   f"{record['n_gpus']} device(s): fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds "
                   f"{stats.get('ms_rounds', 0.0):.3f} ms)")
     return SingleLinkageTree(names, src, tgt, val, is_distance=as_distance)
+
+
+# ---------------------------------------------------------------------------------------
+# Growing a stored sparse result: new genomes against an edge list, a partition, a tree
+# ---------------------------------------------------------------------------------------
+def _extend_plan(stored_nodes, genomes, caller):
+    """What ``edges_extend`` / ``components_extend`` / ``tree_extend`` check of their arguments, as ``matrix_extend`` does: distinct
+    names, every stored node a genome (KeyError), the stored nodes in the genomes' relative order (ValueError).  Returns the genome
+    names, ``old_at`` (the position among the genomes of every stored node: int64, strictly increasing) and the new positions."""
+    if len(genomes) == 0:
+        raise ValueError(f"{caller}: need at least 1 genome")
+    names = [g.name for g in genomes]
+    index = {name: k for k, name in enumerate(names)}
+    if len(index) != len(names):
+        raise ValueError(f"{caller}: genome names must be distinct")
+    stranger = next((node for node in stored_nodes if node not in index), None)
+    if stranger is not None:
+        raise KeyError(f"{caller}: stored node '{stranger}' is not among the genomes: drop it first (without())")
+    stored = set(stored_nodes)
+    if len(stored) != len(stored_nodes):
+        raise ValueError(f"{caller}: the stored nodes must be distinct")
+    new_idx = [k for k, name in enumerate(names) if name not in stored]
+    old_at, _ = _grown_positions(stored_nodes, names, new_idx, caller)
+    return names, old_at, new_idx
+
+
+def _extend_upload(genomes, func, caller):
+    """The one pack and upload of an ``*_extend`` call on one GPU (``upload_for_fills``: its refusals -- a callable outside ``METRICS``,
+    a launcher -- come before any GPU call).  Returns (context, metric, record)."""
+    ctx, metric, _, record = upload_for_fills(genomes, func, caller, advice="for another callable: the extended() statement of the stored result "
+                                                                            "takes any rows of values")
+    return ctx, metric, record
+
+
+def _guard_rows(ctx, metric, as_distance, old_at, verify):
+    """The guard's refill: ``verify`` old genomes, chosen by ``matrix_extend``'s spread rule, against everyone through
+    ``Context.fill_rows``.  Returns (their positions, ascending; their rows of values)."""
+    n_verify = max(0, min(int(verify), int(old_at.shape[0])))
+    checked = sorted({int(old_at[(i * old_at.shape[0]) // n_verify]) for i in range(n_verify)})
+    if not checked:
+        return checked, np.empty((0, ctx.n_genomes), dtype=np.float64)
+    return checked, ctx.fill_rows(metric, checked, as_distance=as_distance)
+
+
+def _guard_edges(names, metric, checked, values, src, tgt, weight, what):
+    """Every stored edge (positions among the genomes) that touches a verified genome must carry exactly the refilled value."""
+    for i, q in enumerate(checked):
+        for mine, other in ((src, tgt), (tgt, src)):
+            at = np.flatnonzero(mine == q)
+            bad = at[weight[at] != values[i, other[at]]]
+            if bad.shape[0]:
+                e = int(bad[0])
+                raise ValueError(f"pair ({names[int(src[e])]}, {names[int(tgt[e])]}): the {what} holds {float(weight[e])!r}, the {metric} fill gives "
+                                 f"{float(values[i, int(other[e])])!r}: it was not filled with this metric from these genomes in this order")
+
+
+def merge_edge_lists(first, second):
+    """Two edge lists ``(source, target, weight)``, each sorted by (target, source) and sharing no pair, as one list in that order: the
+    second's places among the first's by one binary search per edge, no sort."""
+    (s1, t1, w1), (s2, t2, w2) = first, second
+    key1 = (np.asarray(t1, dtype=np.int64) << 32) | np.asarray(s1, dtype=np.int64)
+    key2 = (np.asarray(t2, dtype=np.int64) << 32) | np.asarray(s2, dtype=np.int64)
+    n = key1.shape[0] + key2.shape[0]
+    from_second = np.zeros(n, dtype=bool)
+    from_second[np.searchsorted(key1, key2) + np.arange(key2.shape[0])] = True
+    out = []
+    for x1, x2, dtype in ((s1, s2, np.int32), (t1, t2, np.int32), (w1, w2, np.float64)):
+        merged = np.empty(n, dtype=dtype)
+        merged[from_second] = x2
+        merged[~from_second] = x1
+        out.append(merged)
+    return tuple(out)
+
+
+def _record_extend(stats, metric, names, record, n_rows, t0):
+    """``LAST_FILL`` after an ``*_extend`` call, as ``matrix_extend`` fills it.  Returns ``fill_s``."""
+    import time
+    fill_s = time.perf_counter() - t0
+    LAST_FILL.clear()
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(names), genome_pairs=int(stats["n_pairs"]), rows=n_rows, n_gpus=1, rank=0,
+                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
+    return fill_s
+
+
+def edges_extend(edges, genomes, func, verify=4, slab_bytes=0):
+    """New genomes against a stored edge list: the :class:`SparseEdges` over all of ``genomes`` that ``edges_de_novo(genomes, func,
+    edges.threshold, edges.is_distance)`` would return, element for element, computing only the pairs that touch a genome ``edges``
+    lacks (``Context.fill_rows_edges``: k new genomes cost k N pairs).  ``edges.nodes`` are a subset of the genomes' names, in the
+    genomes' relative order (else ``ValueError``: orientation and tie order follow the order); a stored node that is no genome raises
+    ``KeyError``; ``edges.threshold`` must be set.  ``verify`` old genomes (``matrix_extend``'s spread rule) are refilled first: every
+    stored edge that touches one must carry exactly the refilled value, and every refilled pair of one with an old genome that passes
+    the threshold must be stored -- a mismatch raises ``ValueError`` naming the pair; ``verify=0`` switches the guard off.  Nothing new:
+    the list re-laid on the genomes' names.  Every genome new: ``edges_de_novo``.  One GPU; a callable outside ``METRICS`` and a
+    launcher (``WORLD_SIZE`` > 1) raise before any GPU call (``SparseEdges.extended`` serves another callable)."""
+    if edges.threshold is None:
+        raise ValueError("edges_extend: the stored list carries no threshold, so which new pairs belong to it is undefined")
+    names, old_at, new_idx = _extend_plan(edges.nodes, genomes, "edges_extend")
+    as_distance, threshold = edges.is_distance, edges.threshold
+    if old_at.shape[0] == 0:
+        return edges_de_novo(genomes, func, threshold, as_distance=as_distance, slab_bytes=slab_bytes)
+    src, tgt, weight = old_at[edges.source], old_at[edges.target], edges.weight
+    if not new_idx:
+        return SparseEdges(names, src, tgt, weight, is_distance=as_distance, threshold=threshold)
+    ctx, metric, record = _extend_upload(genomes, func, "edges_extend")
+    import time
+    t0 = time.perf_counter()
+    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
+    _guard_edges(names, metric, checked, values, src, tgt, weight, "edge list")
+    stored = set(zip(src.tolist(), tgt.tolist()))
+    for i, q in enumerate(checked):
+        w = values[i, old_at]
+        for g in old_at[(w <= threshold) if as_distance else (w >= threshold)].tolist():
+            if g != q and (min(q, g), max(q, g)) not in stored:
+                raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
+                                 f"{threshold!r}, and the edge list lacks it: it was not filled with this metric from these genomes in this order")
+    n_src, n_tgt, n_val, stats = ctx.fill_rows_edges(metric, threshold, new_idx, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    src, tgt, weight = merge_edge_lists((src, tgt, weight), (n_src, n_tgt, n_val))
+    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
+    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} new edges in {stats['n_slabs']} slab(s): "
+                  f"guard+fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    return SparseEdges(names, src, tgt, weight, is_distance=as_distance, threshold=threshold)
+
+
+def components_extend(components, genomes, func, threshold, strict=True, verify=4, as_distance=True, slab_bytes=0):
+    """New genomes against a stored partition: the :class:`Components` over all of ``genomes`` that ``components_de_novo(genomes,
+    func, threshold, as_distance, strict)`` would return, computing only the pairs that touch a genome ``components`` lacks
+    (``Context.fill_rows_components``: the stored labels seed the forest).  Arguments, refusals and routes as ``edges_extend``.  The
+    guard: a verified old genome and every old genome it passes the threshold with must share a stored label."""
+    names, old_at, new_idx = _extend_plan(components.nodes, genomes, "components_extend")
+    if old_at.shape[0] == 0:
+        return components_de_novo(genomes, func, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes)
+    seed = np.arange(len(names), dtype=np.int32)
+    seed[old_at] = old_at[components.labels]
+    if not new_idx:
+        return Components(names, seed)
+    ctx, metric, record = _extend_upload(genomes, func, "components_extend")
+    import time
+    t0 = time.perf_counter()
+    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
+    for i, q in enumerate(checked):
+        w = values[i, old_at]
+        if as_distance:
+            passing = w < threshold if strict else w <= threshold
+        else:
+            passing = w > threshold if strict else w >= threshold
+        for g in old_at[passing].tolist():
+            if g != q and seed[g] != seed[q]:
+                raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
+                                 f"{threshold!r}, and the stored components keep the two apart: they were not filled with this metric and threshold "
+                                 f"from these genomes")
+    labels, stats = ctx.fill_rows_components(metric, threshold, new_idx, seed_labels=seed, as_distance=as_distance, strict=strict,
+                                             slab_bytes=slab_bytes, want_stats=True)
+    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
+    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_components']} components in {stats['n_slabs']} "
+                  f"slab(s): guard+fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    return Components(names, labels)
+
+
+def tree_extend(tree, genomes, func, verify=4, slab_bytes=0):
+    """New genomes against a stored single-linkage tree: the :class:`SingleLinkageTree` over all of ``genomes`` that
+    ``tree_de_novo(genomes, func, tree.is_distance)`` would return, edge for edge, computing only the pairs that touch a genome
+    ``tree`` lacks (``Context.fill_rows_tree``: the stored edges seed the resident forest; MST(A + B) = MST(MST(A) + B)).  Arguments,
+    refusals and routes as ``edges_extend``.  The guard: every stored edge that touches a verified old genome must carry exactly the
+    refilled value.  Removing genomes is no such call: ``SingleLinkageTree.without`` says why."""
+    names, old_at, new_idx = _extend_plan(tree.nodes, genomes, "tree_extend")
+    as_distance = tree.is_distance
+    if old_at.shape[0] == 0:
+        return tree_de_novo(genomes, func, as_distance=as_distance, slab_bytes=slab_bytes)
+    src, tgt, weight = old_at[tree.source], old_at[tree.target], tree.weight
+    if not new_idx:
+        return SingleLinkageTree(names, src, tgt, weight, is_distance=as_distance)
+    ctx, metric, record = _extend_upload(genomes, func, "tree_extend")
+    import time
+    t0 = time.perf_counter()
+    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
+    _guard_edges(names, metric, checked, values, src, tgt, weight, "tree")
+    src, tgt, weight, stats = ctx.fill_rows_tree(metric, new_idx, seed=(src, tgt, weight), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
+    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} tree edges in {stats['n_slabs']} slab(s): "
+                  f"guard+fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds {stats.get('ms_rounds', 0.0):.3f} ms)")
+    return SingleLinkageTree(names, src, tgt, weight, is_distance=as_distance)
+
+
+def tree_to_file(tree, filepath):
+    """``tree_<metric>.tsv``: one ``source<TAB>target<TAB>similarity`` line per edge of a distance tree, in merge order; the weights
+    inverted as for the adjacency file, "%.6f"."""
+    with open(filepath, "w") as handle:
+        handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in tree.inverted())
+    return filepath
+
+
+def tree_from_file(filepath, names):
+    """The distance :class:`SingleLinkageTree` a ``tree_<metric>.tsv`` holds, bit for bit: its nodes are the names that occur in the
+    file, in the order of ``names`` (the genomes in fill order; ``KeyError`` for a name they lack), and a similarity of six places
+    comes back as k = rint(sim * 10^6), distance = (10^6 - k) / 10^6 -- the tree fill's own decode, equal to the fill's
+    round(1 - sim, 6).  ``ValueError`` for a line that is no edge, an edge whose source does not come before its target in that
+    order, or a file that is no tree over its names."""
+    index = {name: k for k, name in enumerate(names)}
+    rows = []
+    with open(filepath, "r") as handle:
+        for number, line in enumerate(handle, start=1):
+            fields = line.rstrip("\n").split("\t")
+            if len(fields) != 3:
+                raise ValueError(f"{filepath}:{number}: expected source<TAB>target<TAB>similarity")
+            for name in fields[:2]:
+                if name not in index:
+                    raise KeyError(f"{filepath}:{number}: '{name}' is not among the genomes")
+            k = int(np.rint(float(fields[2]) * 1.0e6))
+            if not 0 <= k <= 1000000:
+                raise ValueError(f"{filepath}:{number}: similarity {fields[2]} is outside [0, 1]")
+            rows.append((index[fields[0]], index[fields[1]], (1000000 - k) / 1000000.0))
+    present = sorted({g for s, t, _ in rows for g in (s, t)})
+    at = {g: k for k, g in enumerate(present)}
+    if len(rows) != max(len(present) - 1, 0):
+        raise ValueError(f"{filepath}: {len(rows)} edges over {len(present)} names are no tree")
+    bad = next(((s, t) for s, t, _ in rows if s >= t), None)
+    if bad is not None:
+        raise ValueError(f"{filepath}: edge ({names[bad[0]]}, {names[bad[1]]}) runs against the genomes' order: the file was written for another order")
+    return SingleLinkageTree([names[g] for g in present], [at[s] for s, _, _ in rows], [at[t] for _, t, _ in rows], [w for _, _, w in rows],
+                             is_distance=True)
+
+
+def components_to_file(components, filepath):
+    """``components_<metric>.tsv``: ``name<TAB>number`` in node order, number 1 for the largest group (``Components.groups()``'s order)."""
+    number = [0] * len(components.nodes)
+    for k, group in enumerate(components.group_indices(), start=1):
+        for i in group.tolist():
+            number[i] = k
+    with open(filepath, "w") as handle:
+        handle.writelines(f"{name}\t{k}\n" for name, k in zip(components.nodes, number))
+    return filepath
+
+
+def components_from_file(filepath):
+    """The :class:`Components` a ``components_<metric>.tsv`` holds: its nodes in file order, every group labelled by its first member."""
+    nodes, number = [], []
+    with open(filepath, "r") as handle:
+        for count, line in enumerate(handle, start=1):
+            fields = line.rstrip("\n").split("\t")
+            if len(fields) != 2 or not fields[1].isdigit():
+                raise ValueError(f"{filepath}:{count}: expected name<TAB>number")
+            nodes.append(fields[0])
+            number.append(int(fields[1]))
+    if len(set(nodes)) != len(nodes):
+        raise ValueError(f"{filepath}: a name occurs twice")
+    first = {}
+    labels = [first.setdefault(k, g) for g, k in enumerate(number)]
+    return Components(nodes, labels)
 
 
 def edges_to_adjacency(edges, filepath, skip_zero=False, use_lib=True):

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, tree_de_novo, upload_for_fills
+from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -122,6 +122,7 @@ class _Run:
         self.genomes, self.by_name, self.cache, self.stage, self.fills = [], {}, None, None, None
         self.rank, self.world = 0, 1          # this process's place in the job (one process per GPU)
         self.extend = None                    # --extend FILE: a distance matrix over a subset of the genomes
+        self.grow = None                      # --grow FILE: a tree_<metric>.tsv / components_<metric>.tsv over a subset of the genomes
 
     @staticmethod
     def _dir(path, fresh=False):
@@ -250,7 +251,11 @@ class _Run:
         self.banner(2, f"{self.metric} components (components fill)")
         t0 = time.perf_counter()
         distance = round(1.0 - similarity, 6)
-        found = components_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True, strict=True)
+        if self.grow is not None:
+            found = self.grown(lambda: components_from_file(self.grow),
+                               lambda old: components_extend(old, self.genomes, METRICS[self.metric], distance, strict=True, as_distance=True), t0)
+        else:
+            found = components_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True, strict=True)
         st = _matrix.LAST_FILL
         groups = found.group_indices()
         log.info(f"{len(self.genomes):,} genomes, {st.get('n_edges', 0):,} of {st.get('genome_pairs', 0):,} pairs within distance < {distance:.6f}: "
@@ -260,13 +265,8 @@ class _Run:
                  f"{st.get('ms_labels', 0.0):.3f} ms)")
         if self.metric in _metrics.PARITY_NOTE:
             log.info(f"parity: {_metrics.parity_note(self.metric)}")
-        number = [0] * len(found.nodes)
-        for k, group in enumerate(groups, start=1):
-            for i in group.tolist():
-                number[i] = k
         target = self.outdir / f"components_{self.metric}.tsv"
-        with open(target, "w") as handle:
-            handle.writelines(f"{name}\t{k}\n" for name, k in zip(found.nodes, number))
+        components_to_file(found, target)
         log.info(f"wrote {target.name}")
         return found
 
@@ -299,7 +299,11 @@ class _Run:
         No matrix, no threshold, nothing cached or clustered."""
         self.banner(2, f"{self.metric} single-linkage tree (tree fill)")
         t0 = time.perf_counter()
-        found = tree_de_novo(self.genomes, METRICS[self.metric], as_distance=True)
+        if self.grow is not None:
+            names = [g.name for g in self.genomes]
+            found = self.grown(lambda: tree_from_file(self.grow, names), lambda old: tree_extend(old, self.genomes, METRICS[self.metric]), t0)
+        else:
+            found = tree_de_novo(self.genomes, METRICS[self.metric], as_distance=True)
         st = _matrix.LAST_FILL
         log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {len(found):,} edges of the single-linkage tree of {len(found.nodes):,} genomes from "
                  f"{st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
@@ -308,9 +312,27 @@ class _Run:
         if self.metric in _metrics.PARITY_NOTE:
             log.info(f"parity: {_metrics.parity_note(self.metric)}")
         target = self.outdir / f"tree_{self.metric}.tsv"
-        with open(target, "w") as handle:
-            handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in found.inverted())
+        tree_to_file(found, target)
         log.info(f"wrote {target.name}")
+        return found
+
+    def grown(self, read, extend, t0):
+        """Stage 2 under --grow: the stored tree or components are read back, held against a refill of a few old genomes and grown by
+        the rows of the genomes they lack (tree_extend / components_extend)."""
+        try:
+            old = read()
+            found = extend(old)
+        except (ValueError, KeyError, OSError) as exc:
+            log.error(f"--grow {self.grow}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
+            print("growing the stored result failed - check log for details")
+            sys.exit(1)
+        st, n = _matrix.LAST_FILL, len(found.nodes)
+        added = n - len(old.nodes)
+        rows, filled = (st.get("rows", added), st.get("genome_pairs", 0)) if added else (0, 0)      # (nothing new: no fill ran)
+        log.info(f"grown {len(old.nodes):,} -> {n:,} genomes: {rows:,} rows, {filled:,} pairs filled instead of {n * (n - 1) // 2:,} in "
+                 f"{time.perf_counter() - t0:.3f} s")
+        if not added:
+            _matrix.LAST_FILL.clear()
         return found
 
     def extended(self, cpus, t0):
@@ -470,7 +492,7 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -478,7 +500,14 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     and write only ``components_<metric>.tsv``; ``no_matrix``: stages 2-3 from components and groups fills, without the dense matrix
     (same clusters; no similarities file, no dataset heatmap, no matrix cache; the adjacency file from an edge-list fill);
     ``nearest``: stop after a nearest-neighbours fill of that many neighbours per genome and write only ``nearest_<metric>.tsv``;
-    ``tree``: stop after a tree fill and write only ``tree_<metric>.tsv``, the single-linkage dendrogram's edges in merge order."""
+    ``tree``: stop after a tree fill and write only ``tree_<metric>.tsv``, the single-linkage dendrogram's edges in merge order;
+    ``grow``: with ``tree``, the ``tree_<metric>.tsv`` -- with ``components_only`` and an ``edge_thresh``, the ``components_<metric>.tsv`` --
+    an earlier run wrote over a subset of the genomes (``--grow``): only the pairs of the genomes it lacks are filled, on one GPU."""
+    if grow is not None:
+        if adjacency_only or no_matrix or nearest is not None or extend is not None or tree == bool(components_only):
+            raise ValueError("grow goes with exactly one of tree and components_only, and with nothing else")
+        if components_only and edge_thresh is None:
+            raise ValueError("grow with components_only needs the edge_thresh the stored components were filled at")
     if tree and (adjacency_only or components_only or no_matrix or nearest is not None or extend is not None):
         raise ValueError("tree cannot be combined with adjacency_only, components_only, no_matrix, nearest or extend")
     if nearest is not None:
@@ -513,11 +542,14 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["nearest"] = f"only, {nearest} neighbours per genome"
     if tree:
         settings["tree"] = "only (single-linkage dendrogram)"
+    if grow is not None:
+        settings["grow"] = grow
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
     run = _Run(outdir, metric, colors, midpoint)
     run.extend = extend
+    run.grow = grow
     run.rank, run.world = distributed.ensure_process_group()      # (0, 1) unless started by torch.distributed.run
     _mark("torch_import_and_process_group")
     run.read(infile, is_genome_dir)
@@ -601,6 +633,8 @@ def gpus_plan(args, route, packed):
     --extend's rows fill is a one-GPU call.  --adjacency-only, --components-only, --nearest and --tree spread over the GPUs of this process
     (pc_multi_fill_edges / _components / _nearest / _tree) under the same estimate as the dense fill; one process per GPU has no route for
     them, so under PHAMCLUST_MULTI=launcher they stay on one GPU."""
+    if getattr(args, "grow", None) is not None:
+        return 1, "one", "--grow fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
     if args.extend is not None:
         # (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
         return 1, "one", "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
@@ -695,7 +729,7 @@ def _run(args, argv):
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
-                  nearest=args.nearest, tree=args.tree)
+                  nearest=args.nearest, tree=args.tree, grow=args.grow)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
