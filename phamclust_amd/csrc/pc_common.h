@@ -68,13 +68,20 @@ struct PcRows {
 // out, value i the pair {q = rows[i / n], g = i % n} -- source the smaller, target the larger -- and LIVE iff g != q and not
 // (is_query[g] and g < q): the diagonal is no pair, and a pair of two query genomes is taken once, in the row of the smaller one,
 // across all slabs of the call (is_query covers every query row of the CALL).  The passes see the slab flat, as the triangular ones
-// do; a thread carries (row, column) of its elements by adds and a carry (PcRowsCursor, pc_pairs.h), adv_* being the launcher's
+// do; a thread carries (row, column) of its elements by adds and a carry (PcRowsDomain, pc_slab_pass.h), adv_* being the launcher's
 // stride between a thread's iterations.
 struct PcRowsSlab {
     int32_t m, n;                     // the slab's rows; N
     const int32_t* rows;              // [m] query genome of row r, ascending
     const uint8_t* is_query;          // [n] 1: the genome is a query row of the call
     int32_t adv_rows, adv_cols;       // stride / n, stride % n (set by the launcher)
+};
+// Which pairs the values of a filled slab are, as the launchers of the slab passes take it: a triangular slab's shard or a rows slab's
+// domain.  The converting constructors are meant: a description's slab() and the launchers are handed a PcShard or a PcRowsSlab as it is.
+struct PcSlabDomain {
+    bool is_rows; PcShard shard; PcRowsSlab rows;
+    PcSlabDomain(const PcShard& s) : is_rows(false), shard(s), rows{} {}
+    PcSlabDomain(const PcRowsSlab& r) : is_rows(true), shard{}, rows(r) {}
 };
 
 // Pair domain of a groups fill: every pair of two positions p < q of one group, over the members of a family of groups laid
@@ -179,26 +186,19 @@ int pc_sparse_col_vals_cap(int P64);             // pocp / af: entries (of phams
 int pc_launch_sparse_col(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);
 int pc_scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* tmp, int64_t tmp_elems, hipStream_t st);
 int64_t pc_scan_tmp_elems(int64_t n);
-// edge list of a filled slab (pc_edges.hip): chunks of the flat f64[Lp]; passing elements per chunk; (s, t, value) of each at
-// offs[chunk] + its rank within the chunk, in element order
+// edge list of a filled slab (pc_edges.hip): chunks of the flat f64[Lp]; the elements per chunk that are pairs of dom (a rows slab:
+// the LIVE ones, Lp = m * n) and pass; (s, t, value) of each at offs[chunk] + its rank within the chunk, in element order
 int64_t pc_edge_chunks(int64_t Lp);
-int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, uint32_t* counts, hipStream_t st);
-int pc_launch_edge_emit(const double* vals, int64_t Lp, int as_distance, double thr, const PcShard& sh, const uint32_t* offs,
+int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, PcSlabDomain dom, uint32_t* counts, hipStream_t st);
+int pc_launch_edge_emit(const double* vals, int64_t Lp, int as_distance, double thr, PcSlabDomain dom, const uint32_t* offs,
                         int32_t* src, int32_t* tgt, double* val, hipStream_t st);
-// ... and of a rows slab (vals = f64[Lp], Lp = m * n): the LIVE elements that pass; (min, max, value) of each, in element order
-int pc_launch_edge_count_rows(const double* vals, int64_t Lp, int as_distance, double thr, PcRowsSlab dom, uint32_t* counts, hipStream_t st);
-int pc_launch_edge_emit_rows(const double* vals, int64_t Lp, int as_distance, double thr, PcRowsSlab dom, const uint32_t* offs,
-                             int32_t* src, int32_t* tgt, double* val, hipStream_t st);
-int pc_rows_slab_span(int pass);                   // elements one workgroup of a rows pass covers (0: edges, 1: union, 2: tree scan)
+int pc_rows_slab_span(int pass);                   // elements one workgroup of a slab pass covers (0: edges, 1: union, 2: tree scan; else 0)
 // connected components of a filled slab's passing pairs (pc_components.hip): parent[g] = g and the pair counter zeroed; one slab's
 // passing pairs hooked into parent[] (strict: < / > instead of <= / >=) and counted into *n_pass; labels[g] = root of g
 int pc_launch_cc_init(int32_t* parent, int n, unsigned long long* n_pass, hipStream_t st);
-int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, const PcShard& sh, int32_t* parent,
+int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, PcSlabDomain dom, int32_t* parent,
                        unsigned long long* n_pass, hipStream_t st);
 int pc_launch_cc_labels(int32_t* parent, int32_t* labels, int n, hipStream_t st);
-// the same over the live pairs of a rows slab
-int pc_launch_cc_union_rows(const double* vals, int64_t Lp, int as_distance, int strict, double thr, PcRowsSlab dom, int32_t* parent,
-                            unsigned long long* n_pass, hipStream_t st);
 // the forests of other devices united into parent[] (pc_multi_fill_components): fparent[n_foreign][n], each a forest k_cc_union left
 int pc_launch_cc_merge(int32_t* parent, const int32_t* fparent, int n_foreign, int n, hipStream_t st);
 // nearest neighbours of a filled slab (pc_nearest.hip): key[N * K] / nbr[N * K] set to the worst sentinel; the pairs of the slab of
@@ -228,10 +228,7 @@ int pc_launch_tree_reset(int32_t* comp, unsigned long long* best, uint32_t* live
 int pc_launch_tree_take_counts(unsigned long long* out, const unsigned long long* lists, int n_foreign, int n, hipStream_t st);
 // round r of a pass, in four steps: the slab's pairs and any number of lists lower best[], the roots hook and append to `out`, comp[] is
 // flattened and best[] reset.  live: [rounds + 1]
-int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, const PcShard& sh, const int32_t* comp, unsigned long long* best,
-                             unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st);
-// the scan over the live pairs of a rows slab
-int pc_launch_tree_scan_rows(const double* vals, int64_t Lp, int as_distance, PcRowsSlab dom, const int32_t* comp, unsigned long long* best,
+int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, PcSlabDomain dom, const int32_t* comp, unsigned long long* best,
                              unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st);
 int pc_launch_tree_scan_list(const unsigned long long* list, const int32_t* comp, unsigned long long* best, int n, const uint32_t* live, int r,
                              hipStream_t st);

@@ -4,10 +4,13 @@
 // (clustering.py:4-51: AgglomerativeClustering(linkage="single", distance_threshold=eps) merges below eps, never at it), and every
 // average / complete cluster at eps lies inside one of them.
 //   k_cc_init     parent[g] = g, the pair counter = 0                                   (once per call)
-//   k_cc_union    streams a slab exactly as k_edge_count does (pc_edges.hip: flat f64[Lp], chunks of 4,096 elements, 256 threads,
-//                 eight 16-byte loads per thread, the odd last element alone, nothing read beyond Lp); (s, t) of a passing element
-//                 as k_edge_emit finds it (one binary search of lbase per chunk, then the forward walk over empty and short rows);
-//                 per passing pair: find both roots, equal -> done, else hook the LARGER root under the SMALLER by compare-and-swap
+//   k_cc_union    ONE body, pc_cc_union_body, under two kernels: k_cc_union over a triangular slab (PcTriDomain) and k_cc_union_rows
+//                 over a rows slab (PcRowsDomain; pc_fill_rows_components, where parent[] may come in seeded with a stored labelling,
+//                 parent[g] = the smallest member of g's stored component <= g: I1 and I2 hold for it as for the identity).  It
+//                 streams the slab as every slab pass does (pc_slab_pass.h: flat f64[Lp], chunks of 4,096 elements, 256 threads, eight
+//                 16-byte loads per thread, the odd last element alone, nothing read beyond Lp) and asks the domain which elements
+//                 are pairs and which two genomes a passing one joins; per passing pair: find both roots, equal -> done, else hook the
+//                 LARGER root under the SMALLER by compare-and-swap
 //   k_cc_merge    several devices, each with the forest of its own stretch of targets (pc_multi_fill_components): thread g unites g
 //                 with its parent in every foreign forest fparent[f][n].  By I1 that parent p <= g is a node of g's foreign component,
 //                 and the edges (g, fparent[g]) span every foreign component, so the root's forest ends up with exactly the components
@@ -23,33 +26,16 @@
 // walks met in one node or its own CAS succeeded -- connected either way -- and connections are never undone (a shortening
 // replaces a parent by an ancestor).  The smallest genome m of a component has parent[m] <= m inside the component, i.e. is its
 // root: labels are the smallest member's index, whatever order the races resolved in.
-// Memory: inside k_cc_union EVERY access to parent[] is a relaxed agent-scope atomic (__hip_atomic_load, atomicCAS, atomicMin;
+// Memory: inside the union pass EVERY access to parent[] is a relaxed agent-scope atomic (__hip_atomic_load, atomicCAS, atomicMin;
 // no plain load or store): the XCDs' L2s are not coherent with each other and a CU's L1 is never refreshed by another CU's writes.
 // Progress: no workgroup ever waits for another.  The only loops are the walk (bounded by I1) and the CAS retry, whose larger
 // root strictly descends with every round (a failed CAS returns the word's true value, < hi, and the walks go on from there).
 // No flags, no spinning on a value another wave is to write, no sleeping.
-#include "pc_pairs.h"
-
-#define CC_THREADS 256
-#define CC_ITERS 8
-#define CC_STRIDE (CC_THREADS * 2)                     // as EDGE_STRIDE: two consecutive elements per thread and iteration
-#define CC_CHUNK (CC_STRIDE * CC_ITERS)                // 4,096 elements = 32 KB of slab per workgroup
+#include "pc_slab_pass.h"
 
 template <int DIST, int STRICT> __device__ __forceinline__ bool pc_cc_pass(double v, double thr) {
     if (DIST) return STRICT ? v < thr : v <= thr;
     return STRICT ? v > thr : v >= thr;
-}
-
-// elements i and i + 1 of the slab (i even, 16-byte aligned as in pc_edge_load); returns how many of the two exist
-__device__ __forceinline__ int pc_cc_load(const double* __restrict__ vals, int64_t i, int64_t Lp, double& a, double& b) {
-    a = b = 0.0;
-    if (i + 1 < Lp) {
-        const double2 v = *reinterpret_cast<const double2*>(vals + i);
-        a = v.x; b = v.y;
-        return 2;
-    }
-    if (i < Lp) { a = vals[i]; return 1; }
-    return 0;
 }
 
 __device__ __forceinline__ int pc_cc_read(int32_t* parent, int x) {
@@ -85,103 +71,63 @@ __global__ __launch_bounds__(256) void k_cc_init(int32_t* __restrict__ parent, i
     if (g == 0) *n_pass = 0ull;
 }
 
-template <int DIST, int STRICT>
-__global__ __launch_bounds__(CC_THREADS) void k_cc_union(const double* __restrict__ vals, int64_t Lp, double thr, PcShard sh,
-                                                         int32_t* parent, unsigned long long* n_pass) {
-    __shared__ uint32_t wsum[CC_THREADS / 64];
-    __shared__ int k_first;
+// the passing pairs of the chunk counted (one 64-bit add per workgroup) and united
+template <int DIST, int STRICT, class Dom>
+__device__ __forceinline__ void pc_cc_union_body(const double* __restrict__ vals, int64_t Lp, double thr, const Dom dom, int32_t* parent,
+                                                 unsigned long long* n_pass) {
+    __shared__ uint32_t wsum[SLAB_THREADS / 64];
+    __shared__ typename Dom::Origin origin;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t i0 = (int64_t)blockIdx.x * CC_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
+    const int64_t base = (int64_t)blockIdx.x * SLAB_CHUNK + (int64_t)threadIdx.x * 2;
+    typename Dom::Cursor at{};
+    if constexpr (Dom::kLocateFirst) {
+        pc_slab_locate(dom, origin);
+        __syncthreads();
+        at = dom.start(origin);
+    }
+    const typename Dom::Cursor first = at;
     uint32_t n = 0;                                    // the wave's count (the same in every lane)
     uint32_t pass_a = 0, pass_b = 0;
 #pragma unroll
-    for (int j = 0; j < CC_ITERS; ++j) {
+    for (int j = 0; j < SLAB_ITERS; ++j) {
         double a, b;
-        const int have = pc_cc_load(vals, base + (int64_t)j * CC_STRIDE, Lp, a, b);
-        const bool pa = have > 0 && pc_cc_pass<DIST, STRICT>(a, thr), pb = have > 1 && pc_cc_pass<DIST, STRICT>(b, thr);
+        const int64_t i = base + (int64_t)j * SLAB_STRIDE;
+        const int have = pc_slab_load(vals, i, Lp, a, b);
+        const bool pa = have > 0 && pc_cc_pass<DIST, STRICT>(a, thr) && dom.live(at, i);
+        const bool pb = have > 1 && pc_cc_pass<DIST, STRICT>(b, thr) && dom.live(at, i + 1);
         n += (uint32_t)__popcll(__ballot(pa)) + (uint32_t)__popcll(__ballot(pb));
         pass_a |= (uint32_t)pa << j; pass_b |= (uint32_t)pb << j;
+        dom.step(at);
     }
     if (lane == 0) wsum[wv] = n;
-    if (threadIdx.x == 0) {
-        // the row of the chunk's first element: lbase[k] <= i0 < lbase[k + 1] (lbase[0] = 0 <= i0 < Lp = lbase[nown]); rows of
-        // length 0 repeat an lbase value and can never be the answer
-        int lo = 0, hi = sh.nown;
-        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (sh.lbase[mid] <= i0) lo = mid; else hi = mid; }
-        k_first = lo;
-    }
+    if constexpr (!Dom::kLocateFirst) pc_slab_locate(dom, origin);
     __syncthreads();
     uint32_t tot = 0;
 #pragma unroll
-    for (int w = 0; w < CC_THREADS / 64; ++w) tot += wsum[w];
+    for (int w = 0; w < SLAB_THREADS / 64; ++w) tot += wsum[w];
     if (tot == 0) return;                              // (the whole workgroup)
     if (threadIdx.x == 0) atomicAdd(n_pass, (unsigned long long)tot);
     if ((pass_a | pass_b) == 0) return;
-    int k = k_first;
+    if constexpr (Dom::kLocateFirst) at = first; else at = dom.start(origin);
 #pragma unroll 1
-    for (int j = 0; j < CC_ITERS; ++j) {
-        const int64_t i = base + (int64_t)j * CC_STRIDE;
-        if ((pass_a >> j) & 1u) {                      // (a passing element lies below Lp = lbase[nown]: the walk stops at k + 1 <= nown)
-            while (i >= sh.lbase[k + 1]) ++k;
-            pc_cc_unite(parent, (int)(i - sh.lbase[k]), sh.owned[k]);
-        }
-        if ((pass_b >> j) & 1u) {
-            while (i + 1 >= sh.lbase[k + 1]) ++k;
-            pc_cc_unite(parent, (int)(i + 1 - sh.lbase[k]), sh.owned[k]);
-        }
+    for (int j = 0; j < SLAB_ITERS; ++j) {
+        const int64_t i = base + (int64_t)j * SLAB_STRIDE;
+        int a, b;                                      // (the union takes a pair's genomes in either order)
+        if ((pass_a >> j) & 1u) { dom.pair(at, i, a, b); pc_cc_unite(parent, b, a); }
+        if ((pass_b >> j) & 1u) { dom.pair(at, i + 1, a, b); pc_cc_unite(parent, b, a); }
+        dom.step(at);
     }
 }
 
-// k_cc_union over a rows slab (PcRowsSlab: vals = f64[m][n] seen flat, Lp = m * n; pc_fill_rows_components): the LIVE elements that
-// pass are counted and united.  The same loads, the same 64-bit count, the same pc_cc_unite (every access to parent[] a relaxed
-// agent-scope atomic); (row, column) carried in a PcRowsCursor instead of the walk over lbase.  parent[] may come in seeded with a
-// stored labelling (parent[g] = the smallest member of g's stored component <= g): I1 and I2 hold for it as for the identity.
-static_assert(CC_CHUNK == 4096, "pc_rows_slab_span");
 template <int DIST, int STRICT>
-__global__ __launch_bounds__(CC_THREADS) void k_cc_union_rows(const double* __restrict__ vals, int64_t Lp, double thr, PcRowsSlab dom,
-                                                              int32_t* parent, unsigned long long* n_pass) {
-    __shared__ uint32_t wsum[CC_THREADS / 64];
-    __shared__ int2 origin;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t i0 = (int64_t)blockIdx.x * CC_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
-    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
-    __syncthreads();
-    PcRowsCursor first, at;
-    first.start(origin, threadIdx.x * 2u, dom);
-    at = first;
-    uint32_t n = 0;                                    // the wave's count (the same in every lane)
-    uint32_t pass_a = 0, pass_b = 0;
-#pragma unroll
-    for (int j = 0; j < CC_ITERS; ++j) {
-        double a, b;
-        const int have = pc_cc_load(vals, base + (int64_t)j * CC_STRIDE, Lp, a, b);
-        int row1, col1, q;
-        at.next(dom, row1, col1);
-        const bool pa = have > 0 && pc_cc_pass<DIST, STRICT>(a, thr) && pc_rows_live(dom, at.row, at.col, q);
-        const bool pb = have > 1 && pc_cc_pass<DIST, STRICT>(b, thr) && pc_rows_live(dom, row1, col1, q);
-        n += (uint32_t)__popcll(__ballot(pa)) + (uint32_t)__popcll(__ballot(pb));
-        pass_a |= (uint32_t)pa << j; pass_b |= (uint32_t)pb << j;
-        at.advance(dom);
-    }
-    if (lane == 0) wsum[wv] = n;
-    __syncthreads();
-    uint32_t tot = 0;
-#pragma unroll
-    for (int w = 0; w < CC_THREADS / 64; ++w) tot += wsum[w];
-    if (tot == 0) return;                              // (the whole workgroup)
-    if (threadIdx.x == 0) atomicAdd(n_pass, (unsigned long long)tot);
-    if ((pass_a | pass_b) == 0) return;
-    at = first;
-#pragma unroll 1
-    for (int j = 0; j < CC_ITERS; ++j) {
-        if ((pass_a >> j) & 1u) pc_cc_unite(parent, dom.rows[at.row], at.col);      // (a passing element lies below Lp: its row is one of the slab's)
-        if ((pass_b >> j) & 1u) {
-            int row1, col1;
-            at.next(dom, row1, col1);
-            pc_cc_unite(parent, dom.rows[row1], col1);
-        }
-        at.advance(dom);
-    }
+__global__ __launch_bounds__(SLAB_THREADS) void k_cc_union(const double* __restrict__ vals, int64_t Lp, double thr, PcShard sh,
+                                                           int32_t* parent, unsigned long long* n_pass) {
+    pc_cc_union_body<DIST, STRICT>(vals, Lp, thr, PcTriDomain{sh}, parent, n_pass);
+}
+template <int DIST, int STRICT>
+__global__ __launch_bounds__(SLAB_THREADS) void k_cc_union_rows(const double* __restrict__ vals, int64_t Lp, double thr, PcRowsSlab dom,
+                                                                int32_t* parent, unsigned long long* n_pass) {
+    pc_cc_union_body<DIST, STRICT>(vals, Lp, thr, PcRowsDomain{dom}, parent, n_pass);
 }
 
 // the same relaxed agent-scope atomics on parent[] as k_cc_union (through pc_cc_unite); the foreign forests are read-only here
@@ -204,48 +150,32 @@ __global__ __launch_bounds__(256) void k_cc_labels(int32_t* parent, int32_t* __r
     labels[g] = r;
 }
 
-static int cc_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
-    return PC_OK;
-}
-
 int pc_launch_cc_init(int32_t* parent, int n, unsigned long long* n_pass, hipStream_t st) {
     hipLaunchKernelGGL(k_cc_init, dim3((unsigned)((std::max(n, 1) + 255) / 256)), dim3(256), 0, st, parent, n, n_pass);
-    return cc_check("k_cc_init");
+    return pc_launch_check("k_cc_init");
 }
 
-// sh: the slab's shard (owned / lbase on the device, nown targets); parent: [N], N above every owned target
-int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, const PcShard& sh, int32_t* parent,
+// dom: the slab's shard or rows domain, its tables on the device; parent: [N], N above every genome of the slab's pairs
+int pc_launch_cc_union(const double* vals, int64_t Lp, int as_distance, int strict, double thr, PcSlabDomain dom, int32_t* parent,
                        unsigned long long* n_pass, hipStream_t st) {
     if (Lp <= 0) return PC_OK;
-    const dim3 grid((unsigned)((Lp + CC_CHUNK - 1) / CC_CHUNK)), block(CC_THREADS);
-    if (as_distance && strict) hipLaunchKernelGGL((k_cc_union<1, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
-    else if (as_distance) hipLaunchKernelGGL((k_cc_union<1, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
-    else if (strict) hipLaunchKernelGGL((k_cc_union<0, 1>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
-    else hipLaunchKernelGGL((k_cc_union<0, 0>), grid, block, 0, st, vals, Lp, thr, sh, parent, n_pass);
-    return cc_check("k_cc_union");
-}
-
-// dom: rows / is_query on the device, Lp = m * n; parent: [n]
-int pc_launch_cc_union_rows(const double* vals, int64_t Lp, int as_distance, int strict, double thr, PcRowsSlab dom, int32_t* parent,
-                            unsigned long long* n_pass, hipStream_t st) {
-    if (Lp <= 0) return PC_OK;
-    if (dom.n <= 0 || dom.m <= 0 || Lp != (int64_t)dom.m * dom.n) { pc_set_error("k_cc_union_rows: a rows slab of %d x %d is not %lld values", dom.m, dom.n, (long long)Lp); return PC_ERR_ARG; }
-    dom.adv_rows = CC_STRIDE / dom.n; dom.adv_cols = CC_STRIDE % dom.n;
-    const dim3 grid((unsigned)((Lp + CC_CHUNK - 1) / CC_CHUNK)), block(CC_THREADS);
-    if (as_distance && strict) hipLaunchKernelGGL((k_cc_union_rows<1, 1>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
-    else if (as_distance) hipLaunchKernelGGL((k_cc_union_rows<1, 0>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
-    else if (strict) hipLaunchKernelGGL((k_cc_union_rows<0, 1>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
-    else hipLaunchKernelGGL((k_cc_union_rows<0, 0>), grid, block, 0, st, vals, Lp, thr, dom, parent, n_pass);
-    return cc_check("k_cc_union_rows");
+    const char* const what = dom.is_rows ? "k_cc_union_rows" : "k_cc_union";
+    const int rc = pc_slab_domain_check(dom, Lp, what);
+    if (rc != PC_OK) return rc;
+    const dim3 grid((unsigned)pc_edge_chunks(Lp)), block(SLAB_THREADS);
+    pc_dispatch<0, 1, 2, 3>((as_distance ? 2 : 0) + (strict ? 1 : 0), [&](auto form) {
+        constexpr int DIST = decltype(form)::value >> 1, STRICT = decltype(form)::value & 1;
+        if (dom.is_rows) hipLaunchKernelGGL((k_cc_union_rows<DIST, STRICT>), grid, block, 0, st, vals, Lp, thr, dom.rows, parent, n_pass);
+        else hipLaunchKernelGGL((k_cc_union<DIST, STRICT>), grid, block, 0, st, vals, Lp, thr, dom.shard, parent, n_pass);
+    });
+    return pc_launch_check(what);
 }
 
 // fparent: [n_foreign][n], every value in [0, n) (a forest k_cc_union left: I1)
 int pc_launch_cc_merge(int32_t* parent, const int32_t* fparent, int n_foreign, int n, hipStream_t st) {
     if (n_foreign <= 0 || n <= 0) return PC_OK;
     hipLaunchKernelGGL(k_cc_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parent, fparent, n_foreign, n);
-    return cc_check("k_cc_merge");
+    return pc_launch_check("k_cc_merge");
 }
 
 // depth <= n - 1 before; ceil(log2 n) halvings leave depth <= 1, and the last round's labels read two levels up: the root
@@ -255,7 +185,7 @@ int pc_launch_cc_labels(int32_t* parent, int32_t* labels, int n, hipStream_t st)
     while ((1 << rounds) < n && rounds < 31) ++rounds;
     for (int r = 0; r < rounds; ++r) {
         hipLaunchKernelGGL(k_cc_labels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parent, labels, n);
-        const int rc = cc_check("k_cc_labels");
+        const int rc = pc_launch_check("k_cc_labels");
         if (rc != PC_OK) return rc;
     }
     return PC_OK;

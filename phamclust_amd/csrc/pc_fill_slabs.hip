@@ -7,7 +7,8 @@
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
 // fills a PcSlabRun, calls the driver and copies the results out.  Host only.
 // pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree (at the end of the file) grow a stored result by new genomes: the same
-// descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk, slab_rows).
+// descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
+// either slab's pair domain.
 //
 // The walk they share goes over successive contiguous ranges of target genomes ("slabs": pc_chunk_plan over count[t] = t under
 // slab_bytes / 8 pairs, at most 2^31-1 so that u32 counts and offsets do); each range is installed as a PcShard (owned = t0 .. t1-1,
@@ -221,7 +222,7 @@ int PcEdgesFill::begin(pc_ctx* c, PcSlabRun& run) {
     return c->dev.N <= 1 ? (int)PC_OK : slab_size(c, run);
 }
 // compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit; count(cnt, st) and emit(off, st) launch
-// the domain's two kernels
+// the two passes
 template <class Count, class Emit> static int edges_slab(pc_ctx* c, PcSlabRun& run, int64_t Lp, Count count, Emit emit) {
     int rc = PC_OK;
     hipStream_t st = c->stream;
@@ -266,20 +267,12 @@ template <class Count, class Emit> static int edges_slab(pc_ctx* c, PcSlabRun& r
     E += Es;
     return PC_OK;
 }
-int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
     return edges_slab(c, run, Lp,
-        [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count(slab, Lp, run.as_distance, run.threshold, cnt, st); },
+        [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count(slab, Lp, run.as_distance, run.threshold, dom, cnt, st); },
         [&](const uint32_t* off, hipStream_t st) {
-            return pc_launch_edge_emit(slab, Lp, run.as_distance, run.threshold, shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+            return pc_launch_edge_emit(slab, Lp, run.as_distance, run.threshold, dom, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
                                        c->b_edge_val.as<double>(), st);
-        });
-}
-int PcEdgesFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
-    return edges_slab(c, run, Lp,
-        [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count_rows(slab, Lp, run.as_distance, run.threshold, dom, cnt, st); },
-        [&](const uint32_t* off, hipStream_t st) {
-            return pc_launch_edge_emit_rows(slab, Lp, run.as_distance, run.threshold, dom, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
-                                            c->b_edge_val.as<double>(), st);
         });
 }
 // (no end phase of its own on the triangular walk: the edges are in the context's pinned arrays, in order, when a walk returns.  A rows
@@ -368,14 +361,9 @@ int PcComponentsFill::begin(pc_ctx* c, PcSlabRun& run) {
     if ((rc = c->b_cc_parent.ensure((size_t)N * 4)) || (rc = c->b_cc_labels.ensure(label_bytes + 8))) return abi_rc(rc);
     return pc_launch_cc_init(c->b_cc_parent.as<int32_t>(), N, cc_pass_counter(c), c->stream);
 }
-int PcComponentsFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
+int PcComponentsFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
     return slab_pass(c, run, c->last_cc_ms, [&](hipStream_t st) {
-        return pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, shard, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
-    });
-}
-int PcComponentsFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
-    return slab_pass(c, run, c->last_cc_ms, [&](hipStream_t st) {
-        return pc_launch_cc_union_rows(slab, Lp, run.as_distance, run.strict, run.threshold, dom, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
+        return pc_launch_cc_union(slab, Lp, run.as_distance, run.strict, run.threshold, dom, c->b_cc_parent.as<int32_t>(), cc_pass_counter(c), st);
     });
 }
 // (run.n_edges comes in as the pairs that passed on other devices: a pair lies in exactly one stretch)
@@ -539,9 +527,9 @@ int PcTreeFill::begin(pc_ctx* c, PcSlabRun& run) {
     PC_HIP(hipMemsetAsync(tree_list(c, 0) + (N - 1), 0, 24, c->stream));       // the empty forest: no key, no violation, no round
     return PC_OK;
 }
-// One pass: the resident forest, the slab (slab != NULL) and n_foreign staged lists into the other list, which becomes the resident one.
-// The slab is a triangular one (shard != NULL) or a rows slab (dom != NULL).
-static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard* shard, const PcRowsSlab* dom, const unsigned long long* foreign,
+// One pass: the resident forest, the slab with its pair domain (dom != NULL) and n_foreign staged lists into the other list, which becomes
+// the resident one.
+static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain* dom, const unsigned long long* foreign,
                      int n_foreign, hipStream_t st) {
     int rc = PC_OK;
     const int N = c->dev.N, rounds = pc_tree_round_count(N);
@@ -553,8 +541,7 @@ static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, 
     unsigned long long* const out = tree_list(c, c->tree_cur ^ 1);
     if ((rc = pc_launch_tree_reset(comp, best, live, rounds, kept, out, N, st)) || (rc = pc_launch_tree_take_counts(out, foreign, n_foreign, N, st))) return rc;
     for (int r = 0; r < rounds; ++r) {
-        if (slab && shard && (rc = pc_launch_tree_scan_slab(slab, Lp, run.as_distance, *shard, comp, best, out, N, live, r, st))) return rc;
-        if (slab && dom && (rc = pc_launch_tree_scan_rows(slab, Lp, run.as_distance, *dom, comp, best, out, N, live, r, st))) return rc;
+        if (dom && (rc = pc_launch_tree_scan_slab(slab, Lp, run.as_distance, *dom, comp, best, out, N, live, r, st))) return rc;
         if ((rc = pc_launch_tree_scan_list(kept, comp, best, N, live, r, st))) return rc;
         for (int f = 0; f < n_foreign; ++f) if ((rc = pc_launch_tree_scan_list(foreign + (size_t)f * words, comp, best, N, live, r, st))) return rc;
         if ((rc = pc_launch_tree_hook(comp, next, best, out, N, live, r, st)) || (rc = pc_launch_tree_flatten(comp, next, best, out, N, live, r, st))) return rc;
@@ -563,11 +550,8 @@ static int tree_pass(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, 
     run.tree_launched += rounds;
     return PC_OK;
 }
-int PcTreeFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
-    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, &shard, nullptr, nullptr, 0, st); });
-}
-int PcTreeFill::slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom) {
-    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, nullptr, &dom, nullptr, 0, st); });
+int PcTreeFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, slab, Lp, &dom, nullptr, 0, st); });
 }
 int PcTreeFill::end(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
@@ -619,7 +603,7 @@ int PcTreeFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& r
     pc_ctx* root = ctx[0];
     for (size_t r = 1; r < runs.size(); ++r) runs[0].tree_launched += runs[r].tree_launched;
     PC_HIP(hipEventRecord(root->ev[0], root->stream));
-    if (n_foreign > 0 && (rc = tree_pass(root, runs[0], nullptr, 0, nullptr, nullptr, (const unsigned long long*)stage, n_foreign, root->stream))) return rc;
+    if (n_foreign > 0 && (rc = tree_pass(root, runs[0], nullptr, 0, nullptr, (const unsigned long long*)stage, n_foreign, root->stream))) return rc;
     PC_HIP(hipEventRecord(root->ev[1], root->stream));
     return PC_OK;
 }
@@ -658,7 +642,7 @@ extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_
 // needs nothing on the device -- the caller merges the two lists.  The same descriptions run: check -> begin -> seed -> the rows walk
 // -> end.  The walk cuts the query rows into consecutive ranges of at most max(1, slab_bytes / 8 / N) rows (0: by slab_max_pairs'
 // rule), fills each with the rows fill itself (pc_fill_rows_dev) into the context's slab buffer as f64[m][N], and hands it to the
-// description's slab_rows with the PcRowsSlab that says which of its values are pairs of the call.  One slab is resident at a time; the
+// description's slab() with the PcRowsSlab that says which of its values are pairs of the call.  One slab is resident at a time; the
 // rows fill touches no shard state, so the caller's is in force throughout.
 static int rows_arg_check(const pc_ctx* c, const char* who, const int32_t* rows, int n_rows) {
     const int N = c->dev.N;
@@ -689,7 +673,7 @@ template <class Fill> static int rows_walk(pc_ctx* c, PcSlabRun& run, const int3
         if ((rc = pc_fill_rows_dev(c, run.metric, run.as_distance, rows + r0, m, slab, st, run.timed ? &one : nullptr))) return rc;
         if (run.timed) pc_stats_add(run.sum, one);
         const PcRowsSlab dom{m, N, c->b_rq_rows.as<int32_t>() + r0, c->b_rq_query.as<uint8_t>(), 0, 0};
-        if ((rc = Fill::slab_rows(c, run, slab, (int64_t)m * N, dom))) return rc;
+        if ((rc = Fill::slab(c, run, slab, (int64_t)m * N, dom))) return rc;
         ++run.n_slabs;
     }
     return PC_OK;
@@ -796,7 +780,7 @@ extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const i
         PC_HIP(hipMemcpyAsync(tree_list(c, 0), h, tree_list_words(c) * 8, hipMemcpyHostToDevice, c->stream));
         if (n_rows > 0) return PC_OK;
         // no query row: one pass over the list alone leaves the tree of the seed edges (a seed that is no forest comes out short, and end() says so)
-        return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, nullptr, 0, nullptr, nullptr, nullptr, 0, st); });
+        return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, nullptr, 0, nullptr, nullptr, 0, st); });
     });
     if (rc != PC_OK) return rc;
     *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
@@ -804,5 +788,5 @@ extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const i
     return PC_OK;
 }
 
-// elements one workgroup of a rows pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by
+// elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by
 extern "C" int pc_rows_pass_span(int pass_kind) { return pc_rows_slab_span(pass_kind); }

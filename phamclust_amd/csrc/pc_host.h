@@ -253,9 +253,10 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 // What a description says:
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
-//   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device
-//   slab_rows   the same for one slab of a rows slab fill (pc_rows_slab_fill, pc_fill_slabs.hip: f64[m][N] of a range of query rows, the
-//           pairs a PcRowsSlab says); edges, components and tree have one, begin and end are the triangular walk's
+//   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device.  dom says which pairs
+//           its values are: the shard of a triangular slab, or -- edges, components and tree; nearest refuses it at compile time -- the
+//           PcRowsSlab of one slab of a rows slab fill (pc_rows_slab_fill, pc_fill_slabs.hip: f64[m][N] of a range of query rows); begin
+//           and end are the triangular walk's
 //   end     labels / finish and the D2H copy; the result pointers and counts into the run
 //   ship_bytes, ship, merge   several devices: the state a non-root device sends to its slice of the root's staging buffer (0 bytes:
 //           nothing travels between devices), and how the root takes the others' state in before its end
@@ -284,21 +285,20 @@ struct PcSlabRun {
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
 };
-#define PC_SLAB_FILL(Name, tag, text)                                                                                                   \
+#define PC_SLAB_FILL(Name, Dom, tag, text)                                                                                              \
     struct Name {                                                                                                                       \
         static constexpr const char *what = text, *who = "pc_fill_" tag, *range = "pc:fill_" tag, *multi_range = "pc:multi_fill_" tag; \
         static int begin(pc_ctx* c, PcSlabRun& run);                                                                                    \
-        static int slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard);                               \
-        static int slab_rows(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcRowsSlab& dom);                         \
+        static int slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const Dom& dom);                                     \
         static int end(pc_ctx* c, PcSlabRun& run);                                                                                      \
         static size_t ship_bytes(const pc_ctx* root, const PcSlabRun& run);                                                             \
         static int ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int n_foreign);                                 \
         static int merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float* ms_exchange); \
     }
-PC_SLAB_FILL(PcEdgesFill, "edges", "an edge-list fill");
-PC_SLAB_FILL(PcComponentsFill, "components", "a components fill");
-PC_SLAB_FILL(PcNearestFill, "nearest", "a nearest-neighbours fill");
-PC_SLAB_FILL(PcTreeFill, "tree", "a tree fill");
+PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill");
+PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill");
+PC_SLAB_FILL(PcNearestFill, PcShard, "nearest", "a nearest-neighbours fill");
+PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill");
 #undef PC_SLAB_FILL
 int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what);
 template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run);

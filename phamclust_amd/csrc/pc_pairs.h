@@ -74,34 +74,6 @@ __device__ __forceinline__ double pc_round6(double x) {
     return pc_round6_exact(x);
 }
 
-// ---------------------------------------------------------------------------------
-// (row, column) of a thread's elements in a flat rows slab f64[m][n] (PcRowsSlab), without a division per value: the workgroup's
-// first element by ONE 64-bit division (pc_rows_origin: one thread, handed on through LDS), a thread's first by one 32-bit
-// division, every further iteration by two adds and a carry.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ int2 pc_rows_origin(int64_t i0, int n) { const int64_t r = i0 / n; return make_int2((int)r, (int)(i0 - r * n)); }
-struct PcRowsCursor {
-    int row, col;                                      // of the thread's even element; its odd one follows (next)
-    // origin: (row, column) of the workgroup's first element; e: the thread's offset in the workgroup's span (< 2^16)
-    __device__ __forceinline__ void start(int2 origin, uint32_t e, const PcRowsSlab& d) {
-        const uint32_t x = (uint32_t)origin.y + e, r = x / (uint32_t)d.n;
-        row = origin.x + (int)r; col = (int)(x - r * (uint32_t)d.n);
-    }
-    __device__ __forceinline__ void advance(const PcRowsSlab& d) {
-        row += d.adv_rows; col += d.adv_cols;
-        if (col >= d.n) { col -= d.n; ++row; }
-    }
-    __device__ __forceinline__ void next(const PcRowsSlab& d, int& row1, int& col1) const {
-        const bool wrap = col + 1 == d.n;
-        row1 = row + (wrap ? 1 : 0); col1 = wrap ? 0 : col + 1;
-    }
-};
-// element (row, g) of the slab (row < m): its query genome, and whether it is a pair the slab owns
-__device__ __forceinline__ bool pc_rows_live(const PcRowsSlab& d, int row, int g, int& q) {
-    q = d.rows[row];
-    return g != q && !(g < q && d.is_query[g]);
-}
-
 __device__ __forceinline__ double pc_finish(double sim, int as_distance) {
     return as_distance ? pc_round6(1.0 - sim) : pc_round6(sim);
 }

@@ -8,9 +8,11 @@
 // two lists swap.  MST(A + B) = MST(MST(A) + MST(B)): several devices' lists merge on the root by a pass over lists alone.
 //   k_tree_reset        comp[g] = g, best[g] = none, the new list emptied (it takes the old list's counters over), live[0] = 1
 //   one round r, four launches, each returning at once when live[r] == 0 (the round before it joined nothing):
-//   k_tree_scan_slab    streams the slab as k_cc_union does (flat f64[Lp], chunks of 4,096 elements, 16-byte loads, the odd last
-//                       element alone, nothing read beyond Lp; (s, t) by one binary search of lbase per chunk and the forward walk);
-//                       a pair whose ends lie in different components lowers best[comp[s]] and best[comp[t]] to its key
+//   k_tree_scan_slab    ONE body, pc_tree_scan_body, under two kernels: k_tree_scan_slab over a triangular slab (PcTriDomain) and
+//                       k_tree_scan_rows over a rows slab (PcRowsDomain; pc_fill_rows_tree: the LIVE elements only).  It streams the
+//                       slab as every slab pass does (pc_slab_pass.h: flat f64[Lp], chunks of 4,096 elements, 16-byte loads, the odd
+//                       last element alone, nothing read beyond Lp) and takes an element's two genomes from the domain; a pair whose ends
+//                       lie in different components lowers best[comp[s]] and best[comp[t]] to its key
 //   k_tree_scan_list    the same over a list of keys, s and t decoded from the key (the resident forest; on the root of a
 //                       several-device call the other devices' forests)
 //   k_tree_hook         a root c with an edge: d = the component of the edge's other end; next[c] = d, unless d chose the same edge
@@ -36,22 +38,18 @@
 // unsigned minimum): the XCDs' L2s are not coherent with each other, and a minimum must not be lost.  best[] only decreases inside a
 // launch, so a stale read lets a needless atomic through and never drops a smaller key.  Scattered atomics are the expensive part,
 // so no lane issues one it can avoid: a key that does not beat the word it read is skipped, and the lanes of a wave that share a
-// TARGET component (a wave reads 128 consecutive elements: mostly one target genome) reduce their keys in the wave first -- at most
-// one atomic per component and wave on that side.  comp[] is written by k_tree_flatten / k_tree_reset only, launches of their own:
-// plain loads elsewhere.  k_tree_hook reads best[] after the scans' launches ended (plain loads) and takes list slots with one
-// returning atomic add per wave on the list's count; live[r + 1] is set by an atomic store of the same value from every wave that
-// appended.  k_tree_flatten reads next[] (written by the hook launch) and writes its own words only.
-// Progress: no workgroup ever waits for another; no flag is spun on; nothing sleeps.  The loops are the forward walk over lbase
-// (bounded by the chunk's rows), the wave's reduction (one turn per distinct target component among 64 lanes) and the chain walk
-// (bounded by the chain, and by n).
+// component on the side the domain names (a wave reads 128 consecutive elements: mostly one target genome of a triangular slab, mostly
+// one row of a rows slab, i.e. the QUERY genome, whether it is the pair's source or its target) reduce their keys in the wave first --
+// at most one atomic per component and wave on that side; the other side is lowered at once.  comp[] is written by k_tree_flatten /
+// k_tree_reset only, launches of their own: plain loads elsewhere.  k_tree_hook reads best[] after the scans' launches ended (plain
+// loads) and takes list slots with one returning atomic add per wave on the list's count; live[r + 1] is set by an atomic store of the
+// same value from every wave that appended.  k_tree_flatten reads next[] (written by the hook launch) and writes its own words only.
+// Progress: no workgroup ever waits for another; no flag is spun on; nothing sleeps.  The loops are the triangular domain's forward
+// walk over lbase (bounded by the chunk's rows), the wave's reduction (one turn per distinct shared component among 64 lanes) and the
+// chain walk (bounded by the chain, and by n).
 // The scan checks what the key relies on -- k = rint(v * 1e6) lies in [0, 10^6] and pc_div_million(k) == v bit for bit -- and counts
 // what fails it in the list's violation word: the host answers a non-zero count with PC_ERR_DATA.
-#include "pc_pairs.h"
-
-#define TREE_THREADS 256
-#define TREE_ITERS 8
-#define TREE_STRIDE (TREE_THREADS * 2)                 // as CC_STRIDE: two consecutive elements per thread and iteration
-#define TREE_CHUNK (TREE_STRIDE * TREE_ITERS)          // 4,096 elements = 32 KB of slab per workgroup
+#include "pc_slab_pass.h"
 
 typedef unsigned long long tree_key_t;
 
@@ -82,18 +80,6 @@ __device__ __forceinline__ void pc_tree_lower_shared(tree_key_t* best, int c, tr
     }
 }
 
-// elements i and i + 1 of the slab (i even, 16-byte aligned as in pc_cc_load); returns how many of the two exist
-__device__ __forceinline__ int pc_tree_load(const double* __restrict__ vals, int64_t i, int64_t Lp, double& a, double& b) {
-    a = b = 0.0;
-    if (i + 1 < Lp) {
-        const double2 v = *reinterpret_cast<const double2*>(vals + i);
-        a = v.x; b = v.y;
-        return 2;
-    }
-    if (i < Lp) { a = vals[i]; return 1; }
-    return 0;
-}
-
 // the key of pair (s, t) with value v, or none (and one violation) when v is not a millionth in [0, 1]
 template <int DIST> __device__ __forceinline__ tree_key_t pc_tree_pair_key(double v, int s, int t, uint32_t& bad) {
     const double k = __builtin_rint(v * 1.0e6);
@@ -102,17 +88,19 @@ template <int DIST> __device__ __forceinline__ tree_key_t pc_tree_pair_key(doubl
     return pc_tree_key_of(DIST ? ki : PC_TREE_MICRO_MAX - ki, s, t);
 }
 
-// One element: its pair's key, the source side lowered at once, and the target component when the key may still beat best[] there
-// (else -1).  comp: [n], every owned target below n.
-template <int DIST> __device__ __forceinline__ void pc_tree_element(double v, int s, int t, const int32_t* __restrict__ comp, tree_key_t* best,
-                                                                    tree_key_t& key, int& ct_out, uint32_t& bad) {
-    key = PC_TREE_NONE; ct_out = -1;
-    const int cs = comp[s], ct = comp[t];
-    if (cs == ct) return;
+// One element, the pair of genome a -- on the side the wave's lanes mostly share -- and genome b: its key, b's side lowered at once,
+// and a's component when the key may still beat best[] there (else -1).  comp: [n], a, b < n.
+template <int DIST, class Dom> __device__ __forceinline__ void pc_tree_element(double v, int a, int b, const int32_t* __restrict__ comp, tree_key_t* best,
+                                                                               tree_key_t& key, int& shared_out, uint32_t& bad) {
+    key = PC_TREE_NONE; shared_out = -1;
+    const int cb = comp[b], ca = comp[a];
+    if (ca == cb) return;
+    int s, t;
+    Dom::sorted(a, b, s, t);
     key = pc_tree_pair_key<DIST>(v, s, t, bad);
     if (key == PC_TREE_NONE) return;
-    pc_tree_lower(best, cs, key);
-    if (key < pc_tree_read(best + ct)) ct_out = ct;
+    pc_tree_lower(best, cb, key);
+    if (key < pc_tree_read(best + ca)) shared_out = ca;
 }
 
 __global__ __launch_bounds__(256) void k_tree_reset(int32_t* __restrict__ comp, tree_key_t* __restrict__ best, uint32_t* __restrict__ live, int rounds,
@@ -137,93 +125,45 @@ __global__ void k_tree_take_counts(tree_key_t* out, const tree_key_t* __restrict
     }
 }
 
-template <int DIST>
-__global__ __launch_bounds__(TREE_THREADS) void k_tree_scan_slab(const double* __restrict__ vals, int64_t Lp, PcShard sh, const int32_t* __restrict__ comp,
-                                                                 tree_key_t* best, tree_key_t* out, int n, const uint32_t* __restrict__ live) {
+// (no barrier but the one that hands the chunk's place on: either domain is located ahead of the loads)
+template <int DIST, class Dom>
+__device__ __forceinline__ void pc_tree_scan_body(const double* __restrict__ vals, int64_t Lp, const Dom dom, const int32_t* __restrict__ comp,
+                                                  tree_key_t* best, tree_key_t* out, int n, const uint32_t* __restrict__ live) {
     if (*live == 0u) return;                           // (the whole grid)
-    __shared__ int k_first;
+    __shared__ typename Dom::Origin origin;
     const int lane = threadIdx.x & 63;
-    const int64_t i0 = (int64_t)blockIdx.x * TREE_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
-    if (threadIdx.x == 0) {
-        // the row of the chunk's first element: lbase[k] <= i0 < lbase[k + 1] (lbase[0] = 0 <= i0 < Lp = lbase[nown])
-        int lo = 0, hi = sh.nown;
-        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (sh.lbase[mid] <= i0) lo = mid; else hi = mid; }
-        k_first = lo;
-    }
+    const int64_t base = (int64_t)blockIdx.x * SLAB_CHUNK + (int64_t)threadIdx.x * 2;
+    pc_slab_locate(dom, origin);
     __syncthreads();
-    int k = k_first;
+    typename Dom::Cursor at = dom.start(origin);
     uint32_t bad = 0;
 #pragma unroll 1
-    for (int j = 0; j < TREE_ITERS; ++j) {             // (every lane takes every turn: the reductions below are the wave's)
-        const int64_t i = base + (int64_t)j * TREE_STRIDE;
+    for (int j = 0; j < SLAB_ITERS; ++j) {             // (every lane takes every turn: the reductions below are the wave's)
         double a, b;
-        const int have = pc_tree_load(vals, i, Lp, a, b);
+        const int64_t i = base + (int64_t)j * SLAB_STRIDE;
+        const int have = pc_slab_load(vals, i, Lp, a, b);
         tree_key_t key_a = PC_TREE_NONE, key_b = PC_TREE_NONE;
-        int ct_a = -1, ct_b = -1;
-        if (have > 0) {                                // (an element below Lp = lbase[nown]: the walk stops at k + 1 <= nown)
-            while (i >= sh.lbase[k + 1]) ++k;
-            pc_tree_element<DIST>(a, (int)(i - sh.lbase[k]), sh.owned[k], comp, best, key_a, ct_a, bad);
-        }
-        if (have > 1) {
-            while (i + 1 >= sh.lbase[k + 1]) ++k;
-            pc_tree_element<DIST>(b, (int)(i + 1 - sh.lbase[k]), sh.owned[k], comp, best, key_b, ct_b, bad);
-        }
-        if (ct_b >= 0 && ct_b == ct_a) { key_a = key_b < key_a ? key_b : key_a; ct_b = -1; }
-        else if (ct_b >= 0 && ct_a < 0) { key_a = key_b; ct_a = ct_b; ct_b = -1; }
-        pc_tree_lower_shared(best, ct_a, key_a, lane);
-        if (__any(ct_b >= 0)) pc_tree_lower_shared(best, ct_b, key_b, lane);      // (a lane whose two elements lie in two rows)
+        int c_a = -1, c_b = -1, ga, gb;
+        if (have > 0 && dom.live(at, i)) { dom.pair(at, i, ga, gb); pc_tree_element<DIST, Dom>(a, ga, gb, comp, best, key_a, c_a, bad); }
+        if (have > 1 && dom.live(at, i + 1)) { dom.pair(at, i + 1, ga, gb); pc_tree_element<DIST, Dom>(b, ga, gb, comp, best, key_b, c_b, bad); }
+        if (c_b >= 0 && c_b == c_a) { key_a = key_b < key_a ? key_b : key_a; c_b = -1; }
+        else if (c_b >= 0 && c_a < 0) { key_a = key_b; c_a = c_b; c_b = -1; }
+        pc_tree_lower_shared(best, c_a, key_a, lane);
+        if (__any(c_b >= 0)) pc_tree_lower_shared(best, c_b, key_b, lane);        // (a lane whose two elements lie in two rows)
+        dom.step(at);
     }
     if (bad) atomicAdd(out + n, (unsigned long long)bad);
 }
 
-// k_tree_scan_slab over a rows slab (PcRowsSlab: vals = f64[m][n] seen flat, Lp = m * n; pc_fill_rows_tree): the LIVE elements only.
-// The same key, domain check and violation count, the same early return.  A wave's 128 consecutive elements lie mostly in ONE row, so
-// here the side the lanes share is the QUERY genome's component -- whether the query is the pair's source or its target -- and that
-// side goes through the wave's reduction; the other genome's component is lowered at once.  (row, column) come from a PcRowsCursor.
-static_assert(TREE_CHUNK == 4096, "pc_rows_slab_span");
-template <int DIST> __device__ __forceinline__ void pc_tree_element_rows(double v, int q, int g, const int32_t* __restrict__ comp, tree_key_t* best,
-                                                                         tree_key_t& key, int& cq_out, uint32_t& bad) {
-    key = PC_TREE_NONE; cq_out = -1;
-    const int cq = comp[q], cg = comp[g];
-    if (cq == cg) return;
-    key = pc_tree_pair_key<DIST>(v, q < g ? q : g, q < g ? g : q, bad);
-    if (key == PC_TREE_NONE) return;
-    pc_tree_lower(best, cg, key);
-    if (key < pc_tree_read(best + cq)) cq_out = cq;
-}
-
 template <int DIST>
-__global__ __launch_bounds__(TREE_THREADS) void k_tree_scan_rows(const double* __restrict__ vals, int64_t Lp, PcRowsSlab dom, const int32_t* __restrict__ comp,
+__global__ __launch_bounds__(SLAB_THREADS) void k_tree_scan_slab(const double* __restrict__ vals, int64_t Lp, PcShard sh, const int32_t* __restrict__ comp,
                                                                  tree_key_t* best, tree_key_t* out, int n, const uint32_t* __restrict__ live) {
-    if (*live == 0u) return;                           // (the whole grid)
-    __shared__ int2 origin;
-    const int lane = threadIdx.x & 63;
-    const int64_t i0 = (int64_t)blockIdx.x * TREE_CHUNK, base = i0 + (int64_t)threadIdx.x * 2;
-    if (threadIdx.x == 0) origin = pc_rows_origin(i0, dom.n);
-    __syncthreads();
-    PcRowsCursor at;
-    at.start(origin, threadIdx.x * 2u, dom);
-    uint32_t bad = 0;
-#pragma unroll 1
-    for (int j = 0; j < TREE_ITERS; ++j) {             // (every lane takes every turn: the reductions below are the wave's)
-        const int64_t i = base + (int64_t)j * TREE_STRIDE;
-        double a, b;
-        const int have = pc_tree_load(vals, i, Lp, a, b);
-        tree_key_t key_a = PC_TREE_NONE, key_b = PC_TREE_NONE;
-        int cq_a = -1, cq_b = -1, q;
-        if (have > 0 && pc_rows_live(dom, at.row, at.col, q)) pc_tree_element_rows<DIST>(a, q, at.col, comp, best, key_a, cq_a, bad);
-        if (have > 1) {
-            int row1, col1;
-            at.next(dom, row1, col1);
-            if (pc_rows_live(dom, row1, col1, q)) pc_tree_element_rows<DIST>(b, q, col1, comp, best, key_b, cq_b, bad);
-        }
-        if (cq_b >= 0 && cq_b == cq_a) { key_a = key_b < key_a ? key_b : key_a; cq_b = -1; }
-        else if (cq_b >= 0 && cq_a < 0) { key_a = key_b; cq_a = cq_b; cq_b = -1; }
-        pc_tree_lower_shared(best, cq_a, key_a, lane);
-        if (__any(cq_b >= 0)) pc_tree_lower_shared(best, cq_b, key_b, lane);      // (a lane whose two elements lie in two rows)
-        at.advance(dom);
-    }
-    if (bad) atomicAdd(out + n, (unsigned long long)bad);
+    pc_tree_scan_body<DIST>(vals, Lp, PcTriDomain{sh}, comp, best, out, n, live);
+}
+template <int DIST>
+__global__ __launch_bounds__(SLAB_THREADS) void k_tree_scan_rows(const double* __restrict__ vals, int64_t Lp, PcRowsSlab dom, const int32_t* __restrict__ comp,
+                                                                 tree_key_t* best, tree_key_t* out, int n, const uint32_t* __restrict__ live) {
+    pc_tree_scan_body<DIST>(vals, Lp, PcRowsDomain{dom}, comp, best, out, n, live);
 }
 
 // list: [n + PC_TREE_TAIL], list[n - 1] keys in it
@@ -287,11 +227,6 @@ __global__ __launch_bounds__(256) void k_tree_flatten(int32_t* comp, const int32
     if (g == 0) out[n + 1] += 1ull;                    // a round that did work
 }
 
-static int tree_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
-    return PC_OK;
-}
 static dim3 tree_grid(int n) { return dim3((unsigned)((std::max(n, 1) + 255) / 256)); }
 
 int pc_tree_round_count(int n) {
@@ -305,54 +240,50 @@ int pc_launch_tree_reset(int32_t* comp, unsigned long long* best, uint32_t* live
                          int n, hipStream_t st) {
     if (n < 2) return PC_OK;
     hipLaunchKernelGGL(k_tree_reset, tree_grid(n), dim3(256), 0, st, comp, best, live, rounds, in, out, n);
-    return tree_check("k_tree_reset");
+    return pc_launch_check("k_tree_reset");
 }
 
 int pc_launch_tree_take_counts(unsigned long long* out, const unsigned long long* lists, int n_foreign, int n, hipStream_t st) {
     if (n_foreign <= 0 || n < 2) return PC_OK;
     hipLaunchKernelGGL(k_tree_take_counts, dim3(1), dim3(64), 0, st, out, lists, n_foreign, n);
-    return tree_check("k_tree_take_counts");
+    return pc_launch_check("k_tree_take_counts");
 }
 
-// sh: the slab's shard (owned / lbase on the device, nown targets, every one below n); comp, best: [n]; out: the list that takes the violations
-int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, const PcShard& sh, const int32_t* comp, unsigned long long* best,
+// dom: the slab's shard or rows domain, its tables on the device, every genome of its pairs below n; comp, best: [n]; out: the list
+// that takes the violations
+int pc_launch_tree_scan_slab(const double* vals, int64_t Lp, int as_distance, PcSlabDomain dom, const int32_t* comp, unsigned long long* best,
                              unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st) {
     if (Lp <= 0 || n < 2) return PC_OK;
-    const dim3 grid((unsigned)((Lp + TREE_CHUNK - 1) / TREE_CHUNK)), block(TREE_THREADS);
-    if (as_distance) hipLaunchKernelGGL((k_tree_scan_slab<1>), grid, block, 0, st, vals, Lp, sh, comp, best, out, n, live + r);
-    else hipLaunchKernelGGL((k_tree_scan_slab<0>), grid, block, 0, st, vals, Lp, sh, comp, best, out, n, live + r);
-    return tree_check("k_tree_scan_slab");
-}
-
-// dom: rows / is_query on the device, dom.n == n, Lp = m * n; comp, best: [n]; out: the list that takes the violations
-int pc_launch_tree_scan_rows(const double* vals, int64_t Lp, int as_distance, PcRowsSlab dom, const int32_t* comp, unsigned long long* best,
-                             unsigned long long* out, int n, const uint32_t* live, int r, hipStream_t st) {
-    if (Lp <= 0 || n < 2) return PC_OK;
-    if (dom.n != n || dom.m <= 0 || Lp != (int64_t)dom.m * dom.n) { pc_set_error("k_tree_scan_rows: a rows slab of %d x %d is not %lld values of %d genomes", dom.m, dom.n, (long long)Lp, n); return PC_ERR_ARG; }
-    dom.adv_rows = TREE_STRIDE / dom.n; dom.adv_cols = TREE_STRIDE % dom.n;
-    const dim3 grid((unsigned)((Lp + TREE_CHUNK - 1) / TREE_CHUNK)), block(TREE_THREADS);
-    if (as_distance) hipLaunchKernelGGL((k_tree_scan_rows<1>), grid, block, 0, st, vals, Lp, dom, comp, best, out, n, live + r);
-    else hipLaunchKernelGGL((k_tree_scan_rows<0>), grid, block, 0, st, vals, Lp, dom, comp, best, out, n, live + r);
-    return tree_check("k_tree_scan_rows");
+    const char* const what = dom.is_rows ? "k_tree_scan_rows" : "k_tree_scan_slab";
+    if (dom.is_rows && (dom.rows.n != n || dom.rows.m <= 0 || Lp != (int64_t)dom.rows.m * dom.rows.n)) { pc_set_error("%s: a rows slab of %d x %d is not %lld values of %d genomes", what, dom.rows.m, dom.rows.n, (long long)Lp, n); return PC_ERR_ARG; }
+    const int rc = pc_slab_domain_check(dom, Lp, what);
+    if (rc != PC_OK) return rc;
+    const dim3 grid((unsigned)pc_edge_chunks(Lp)), block(SLAB_THREADS);
+    pc_dispatch<0, 1>(as_distance ? 1 : 0, [&](auto dist) {
+        constexpr int DIST = decltype(dist)::value;
+        if (dom.is_rows) hipLaunchKernelGGL((k_tree_scan_rows<DIST>), grid, block, 0, st, vals, Lp, dom.rows, comp, best, out, n, live + r);
+        else hipLaunchKernelGGL((k_tree_scan_slab<DIST>), grid, block, 0, st, vals, Lp, dom.shard, comp, best, out, n, live + r);
+    });
+    return pc_launch_check(what);
 }
 
 int pc_launch_tree_scan_list(const unsigned long long* list, const int32_t* comp, unsigned long long* best, int n, const uint32_t* live, int r,
                              hipStream_t st) {
     if (n < 2) return PC_OK;
     hipLaunchKernelGGL(k_tree_scan_list, tree_grid(n - 1), dim3(256), 0, st, list, comp, best, n, live + r);
-    return tree_check("k_tree_scan_list");
+    return pc_launch_check("k_tree_scan_list");
 }
 
 int pc_launch_tree_hook(const int32_t* comp, int32_t* next, const unsigned long long* best, unsigned long long* out, int n, uint32_t* live, int r,
                         hipStream_t st) {
     if (n < 2) return PC_OK;
     hipLaunchKernelGGL(k_tree_hook, tree_grid(n), dim3(256), 0, st, comp, next, best, out, n, live + r);
-    return tree_check("k_tree_hook");
+    return pc_launch_check("k_tree_hook");
 }
 
 int pc_launch_tree_flatten(int32_t* comp, const int32_t* next, unsigned long long* best, unsigned long long* out, int n, const uint32_t* live, int r,
                            hipStream_t st) {
     if (n < 2) return PC_OK;
     hipLaunchKernelGGL(k_tree_flatten, tree_grid(n), dim3(256), 0, st, comp, next, best, out, n, live + r);
-    return tree_check("k_tree_flatten");
+    return pc_launch_check("k_tree_flatten");
 }

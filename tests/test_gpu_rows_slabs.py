@@ -193,7 +193,8 @@ def test_synth200_under_every_slab_cut(ctx, synth200_packed, metric):
 def test_workgroup_seams(ctx, n):
     """m rows of n values against one workgroup's span of each pass: the largest m with m * n <= span and the first above it (n = 65:
     4,095 and 4,160 values; n = 64: 4,032, 4,096 and all 64 rows; n = 129: 3,999 / 4,128 and, two spans, 8,127 / 8,256), whole and
-    cut into two slabs, so that pairs of two new genomes lie in different slabs and must be taken once."""
+    cut into two slabs, so that pairs of two new genomes lie in different slabs and must be taken once.  n = 65 runs its counts a second
+    time on the similarity form (sim >= 0.1, expected from the similarity fill)."""
     from phamclust_amd.hip import Context
     from phamclust_amd.synth import synth_packed
     spans = {Context.rows_pass_span(kind) for kind in PASSES}
@@ -206,21 +207,26 @@ def test_workgroup_seams(ctx, n):
             m = k * span // n
             counts.update(min(x, n) for x in (m - 1 if (k * span) % n == 0 else None, m, m + 1) if x is not None)      # (n = 63: all 63 rows, 3,969 values)
     assert counts and min(counts) >= 1
-    for m in sorted(counts):
-        new = sorted(np.random.default_rng(m).choice(n, size=m, replace=False).tolist()) if m < n else list(range(n))
-        if m == n:                                                          # every genome new: nothing stored
-            src, tgt, val = ctx.fill_rows_tree("jc", new)
-            want = dense.get("tree", list(range(n)))
-            assert np.array_equal(src, want.source) and np.array_equal(tgt, want.target) and same_bits(val, want.weight)
-            s, t, v, st = ctx.fill_rows_edges("jc", 0.9, new, want_stats=True)
-            want = dense.get("edges", list(range(n)), 0.9)
-            assert np.array_equal(s, want.source) and np.array_equal(t, want.target) and same_bits(v, want.weight) and st["n_slabs"] == 1
-            labels = ctx.fill_rows_components("jc", 0.9, new)
-            assert np.array_equal(labels, dense.get("components", list(range(n)), 0.9, True))
-            continue
-        grow_all(ctx, "jc", dense, new, 0.9, label=("seam", n, m), want_slabs=1)
-        half = (m + 1) // 2
-        grow_all(ctx, "jc", dense, new, 0.9, slab_bytes=8 * n * half, label=("seam, two slabs", n, m), want_slabs=2 if m > 1 else 1)
+    forms = [(dense, 0.9)]
+    if n == 65:     # once more as similarities: the passes' similarity instances meet a workgroup seam of a rows slab only here
+        forms.append((Dense(square_of(ctx.fill("jc", as_distance=False), n, False), False), 0.1))
+    for dense, thr in forms:
+        sim = {} if dense.as_distance else {"as_distance": False}
+        for m in sorted(counts):
+            new = sorted(np.random.default_rng(m).choice(n, size=m, replace=False).tolist()) if m < n else list(range(n))
+            if m == n:                                                      # every genome new: nothing stored
+                src, tgt, val = ctx.fill_rows_tree("jc", new, **sim)
+                want = dense.get("tree", list(range(n)))
+                assert np.array_equal(src, want.source) and np.array_equal(tgt, want.target) and same_bits(val, want.weight)
+                s, t, v, st = ctx.fill_rows_edges("jc", thr, new, want_stats=True, **sim)
+                want = dense.get("edges", list(range(n)), thr)
+                assert np.array_equal(s, want.source) and np.array_equal(t, want.target) and same_bits(v, want.weight) and st["n_slabs"] == 1
+                labels = ctx.fill_rows_components("jc", thr, new, **sim)
+                assert np.array_equal(labels, dense.get("components", list(range(n)), thr, True))
+                continue
+            grow_all(ctx, "jc", dense, new, thr, label=("seam", n, m), want_slabs=1)
+            half = (m + 1) // 2
+            grow_all(ctx, "jc", dense, new, thr, slab_bytes=8 * n * half, label=("seam, two slabs", n, m), want_slabs=2 if m > 1 else 1)
 
 
 # ---- 4: ties and contention ---------------------------------------------------------------------------------------
