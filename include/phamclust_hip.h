@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 162   /* 0.5.11: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree, pc_rows_pass_span */
+#define PC_VERSION 163   /* 0.5.12: pc_fill_rows_nearest, pc_nearest_rows_tile */
 
 typedef enum {
     PC_OK = 0,
@@ -390,7 +390,7 @@ int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
  * Outputs, loans, stats and the refusals' order are the triangular calls' (before upload, sharded context, PC_TREE_MAX_GENOMES, a NULL
  * out pointer, a NaN threshold, negative slab_bytes, missing residues); then rows (pc_fill_rows' PC_ERR_ARG), then the seeds.
  * pc_last_edge_times / pc_last_component_times / pc_last_tree_times / pc_last_tree_rounds report on these calls too (the edges' host
- * sort is added to ms_d2h).  Not built: a rows form of pc_fill_nearest, several GPUs.
+ * sort is added to ms_d2h).  Not built: several GPUs.
  */
 int pc_fill_rows_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
                        const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
@@ -403,6 +403,27 @@ int pc_fill_rows_tree(pc_ctx* ctx, int metric, int as_distance, const int32_t* r
 /* Test hook, host arithmetic: the values one workgroup of a rows pass covers (pass_kind 0: edge count / emit, 1: union, 2: tree scan;
  * anything else: 0) -- what a test of the passes' workgroup seams sizes its slabs by. */
 int pc_rows_pass_span(int pass_kind);
+
+/*
+ * The rows form of the nearest-neighbours fill: stored k-nearest lists grown by new genomes (PC_VERSION 163).  rows, the walk, the
+ * values and the index space as above.  seed_nbr / seed_val [N][k_seed], row-major in the UPLOADED collection's numbering, are the stored
+ * lists re-indexed: row g of an old genome its best old neighbours, best first; rows of query genomes are ignored.  With N_old = N -
+ * n_rows and kk = min(k, N - 1): k_seed >= min(kk, N_old - 1), else PC_ERR_ARG (a shorter stored list cannot decide kk neighbours);
+ * columns beyond kk (and beyond N_old - 1) are cut; NULL seeds only while N_old <= 1.  A seed entry that is out of range, names a query genome or the genome
+ * itself, or a row that does not ascend in (value, better first; then index): PC_ERR_ARG.  All refusals come before anything is launched,
+ * with the outputs nulled, and leave the context usable.  The stored lists replace the empty ones on the device; each slab of query rows
+ * goes through two passes (k_nn_qrows: a query genome's list from its row, every genome but itself a candidate; k_nn_qcols: the slab's
+ * rows as candidates of the old genomes' lists).  Exact: every old candidate outside a stored list is worse, in the total order, than
+ * every entry in it, so the best kk of {stored list} + {pairs with the new genomes} is the best kk of all N - 1.  *nbr / *val [N][*k_out]
+ * as pc_fill_nearest delivers them, equal to its result over the whole collection.  n_rows == 0: the seed re-laid to kk columns; n_rows
+ * == N: pc_fill_nearest; N <= 1 as there.  Refusals' order: pc_fill_nearest's, then rows, then the seed.  pc_last_nearest_times reports
+ * on this call too.  One GPU.
+ */
+int pc_fill_rows_nearest(pc_ctx* ctx, int metric, int as_distance, int k, const int32_t* rows, int n_rows,
+                         const int32_t* seed_nbr, const double* seed_val, int32_t k_seed, int64_t slab_bytes,
+                         const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats);
+/* Test hook, host arithmetic: the tile edge of that call's column pass (rows and columns of the slab a workgroup stages at a time). */
+int pc_nearest_rows_tile(void);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -72,6 +72,10 @@ _OPTIONS = (
                                                                      "the pairs of the genomes it lacks are filled, on one GPU, and the file written is "
                                                                      "the from-scratch run's, byte for byte; the adjacency file has no such route (it "
                                                                      "does not say which genomes it covered: matrix.edges_extend is the API for it)")),
+    (None, "-W", "--grow-nearest", dict(type=pathlib.Path, default=None, help="with --nearest K: the nearest_<metric>.tsv an earlier --nearest run (of at "
+                                                                             "least K neighbours) wrote over a SUBSET of these genomes: only the pairs "
+                                                                             "of the genomes it lacks are filled, on one GPU, and the file written is "
+                                                                             "the from-scratch run's, byte for byte")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -139,6 +143,11 @@ def parse_args(argv=None):
                 parser.error(f"--grow goes with exactly one of --tree and --components-only; it cannot be combined with {flag}")
         if args.gpus > 1:
             parser.error("--grow: growing a stored result is a one-GPU call; it cannot be combined with --gpus N")
+    if args.grow_nearest is not None:
+        if args.nearest is None:
+            parser.error("--grow-nearest FILE grows the stored lists of a --nearest K run; give --nearest K")
+        if args.gpus > 1:
+            parser.error("--grow-nearest: growing a stored result is a one-GPU call; it cannot be combined with --gpus N")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

@@ -205,6 +205,11 @@ int pc_launch_cc_merge(int32_t* parent, const int32_t* fparent, int n_foreign, i
 // targets [t0, t1) merged into the K slots of every genome they touch (the row pass, then the column pass); values back from the keys
 int pc_launch_nn_init(unsigned long long* key, int32_t* nbr, int64_t n, hipStream_t st);
 int pc_launch_nn_select(const double* vals, int64_t Lp, int t0, int t1, int as_distance, int K, unsigned long long* key, int32_t* nbr, hipStream_t st);
+int pc_launch_nn_select_rows(const double* vals, int64_t Lp, const PcRowsSlab& dom, int as_distance, int K, unsigned long long* key, int32_t* nbr,
+                             hipStream_t st);
+int pc_nn_seed_pack(const int32_t* seed_nbr, const double* seed_val, int k_seed, int ks, int N, int K, const uint8_t* is_query, int as_distance,
+                    unsigned long long* key, int32_t* idx, int* bad_g, int* bad_j);
+int pc_nn_rows_tile(void);
 int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st);
 // the lists of other devices merged into key / nbr [N][K] (pc_multi_fill_nearest): fkey / fnbr [n_foreign][N][K], in key space
 int pc_launch_nn_merge(unsigned long long* key, int32_t* nbr, const unsigned long long* fkey, const int32_t* fnbr, int n_foreign, int N, int K, hipStream_t st);

@@ -6,7 +6,7 @@
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
 // fills a PcSlabRun, calls the driver and copies the results out.  Host only.
-// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree (at the end of the file) grow a stored result by new genomes: the same
+// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest (at the end of the file) grow a stored result by new genomes: the same
 // descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
 // either slab's pair domain.
 //
@@ -445,11 +445,15 @@ int PcNearestFill::begin(pc_ctx* c, PcSlabRun& run) {
     if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes))) return abi_rc(rc);
     return pc_launch_nn_init(c->b_nn_key.as<unsigned long long>(), nn_nbr(c, run), (int64_t)n_ent, c->stream);
 }
-// the row pass, then the column pass; the slab's targets are the consecutive range that starts at its first owned one
-int PcNearestFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcShard& shard) {
-    const int t0 = c->h_owned[0], t1 = t0 + shard.nown;
+// the row pass, then the column pass: a triangular slab's targets are the consecutive range that starts at its first owned one; a rows
+// slab goes through the rows forms of the two passes (k_nn_qrows, k_nn_qcols)
+int PcNearestFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    unsigned long long* const key = c->b_nn_key.as<unsigned long long>();
+    if (dom.is_rows)
+        return slab_pass(c, run, c->last_nn_ms, [&](hipStream_t st) { return pc_launch_nn_select_rows(slab, Lp, dom.rows, run.as_distance, run.kk, key, nn_nbr(c, run), st); });
+    const int t0 = c->h_owned[0], t1 = t0 + dom.shard.nown;
     return slab_pass(c, run, c->last_nn_ms, [&](hipStream_t st) {
-        return pc_launch_nn_select(slab, Lp, t0, t1, run.as_distance, run.kk, c->b_nn_key.as<unsigned long long>(), nn_nbr(c, run), st);
+        return pc_launch_nn_select(slab, Lp, t0, t1, run.as_distance, run.kk, key, nn_nbr(c, run), st);
     });
 }
 int PcNearestFill::end(pc_ctx* c, PcSlabRun& run) {
@@ -635,10 +639,11 @@ extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_
     return PC_OK;
 }
 
-// ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree grow a STORED result.  The pairs of the call are
+// ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest grow a STORED result.  The pairs of the call are
 // those that touch a query genome (the new genomes of a grown collection): k query rows cost k N pairs, not N^2 / 2.  What is stored
 // stands for the pairs among the other genomes: the components fill takes their labelling as the initial parent[], the tree fill
-// their tree's keys as the resident forest (MST(A + B) = MST(MST(A) + B), the invariant the slabs already keep); a stored edge list
+// their tree's keys as the resident forest (MST(A + B) = MST(MST(A) + B), the invariant the slabs already keep), the nearest fill their
+// lists as the resident key[N][K] / nbr[N][K] (the best K of a list and new candidates is the best K of all); a stored edge list
 // needs nothing on the device -- the caller merges the two lists.  The same descriptions run: check -> begin -> seed -> the rows walk
 // -> end.  The walk cuts the query rows into consecutive ranges of at most max(1, slab_bytes / 8 / N) rows (0: by slab_max_pairs'
 // rule), fills each with the rows fill itself (pc_fill_rows_dev) into the context's slab buffer as f64[m][N], and hands it to the
@@ -788,5 +793,61 @@ extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const i
     return PC_OK;
 }
 
+// The stored lists are seed_nbr / seed_val [N][k_seed] in the uploaded collection's numbering, rows of query genomes ignored: the best
+// min(K, N_old - 1) old neighbours of every old genome, N_old = N - n_rows.  They replace the sentinel in the resident lists; the query
+// rows' pairs are merged into them by the one total order, so an old genome's list is the best kk of all its N - 1 candidates (every old
+// candidate outside the stored list is worse than every entry in it), and a query genome's list is built from its row alone.
+extern "C" int pc_fill_rows_nearest(pc_ctx* c, int metric, int as_distance, int k, const int32_t* rows, int n_rows, const int32_t* seed_nbr,
+                                    const double* seed_val, int32_t k_seed, int64_t slab_bytes, const int32_t** nbr, const double** val, int32_t* k_out,
+                                    int32_t* n_slabs, pc_stats* stats) {
+    if (nbr) *nbr = nullptr;
+    if (val) *val = nullptr;
+    if (k_out) *k_out = 0;
+    if (n_slabs) *n_slabs = 0;
+    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_fill_rows_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
+    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
+    int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, PcNearestFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+    const int N = c->dev.N, kk = run.kk, n_old = N - n_rows;
+    const int need = std::max(std::min(kk, n_old - 1), 0);                  // entries a stored list must hold; more (up to kk) are taken, the rest cut
+    if (k_seed < need) {
+        pc_set_error("%s: k_seed %d is below min(k, N_old - 1) = %d (%d old genomes): the stored lists cannot decide %d neighbours", run.who, (int)k_seed, need, n_old, kk);
+        return PC_ERR_ARG;
+    }
+    if (n_old > 1 && !(seed_nbr && seed_val)) { pc_set_error("%s: a seed array is NULL with %d old genomes", run.who, n_old); return PC_ERR_ARG; }
+    const int ks = std::min<int>(std::min<int>(k_seed, kk), std::max(n_old - 1, 0));
+    // packed before begin: the caller may hand back the arrays an earlier call lent out
+    std::vector<unsigned long long> keys; std::vector<int32_t> idx;
+    if (ks > 0) {
+        std::vector<uint8_t> is_query((size_t)N, 0);
+        for (int i = 0; i < n_rows; ++i) is_query[rows[i]] = 1;
+        keys.resize((size_t)N * kk); idx.resize((size_t)N * kk);
+        int bad_g = -1, bad_j = -1;
+        const int why = pc_nn_seed_pack(seed_nbr, seed_val, k_seed, ks, N, kk, is_query.data(), run.as_distance, keys.data(), idx.data(), &bad_g, &bad_j);
+        if (why) {
+            pc_set_error("%s: seed entry [%d][%d] = (%d, %.17g) %s", run.who, bad_g, bad_j, seed_nbr[(size_t)bad_g * k_seed + bad_j], seed_val[(size_t)bad_g * k_seed + bad_j],
+                         why == 1 ? "is no other old genome (out of range, a query genome, or the genome itself)"
+                                  : "does not come after the entry before it: a stored list ascends in (value, better first; then index)");
+            return PC_ERR_ARG;
+        }
+    }
+    rc = pc_rows_slab_fill<PcNearestFill>(c, run, rows, n_rows, [&]() -> int {
+        if (ks == 0) return PC_OK;
+        // the stored lists in place of the sentinel, through the pinned result image (end() rewrites it only after the stream has drained)
+        const size_t n_ent = nn_entries(c, run);
+        memcpy(c->h_nn.p, keys.data(), n_ent * 8);
+        memcpy((char*)c->h_nn.p + n_ent * 8, idx.data(), n_ent * 4);
+        PC_HIP(hipMemcpyAsync(c->b_nn_key.p, c->h_nn.p, n_ent * 8, hipMemcpyHostToDevice, c->stream));
+        PC_HIP(hipMemcpyAsync(nn_nbr(c, run), (const char*)c->h_nn.p + n_ent * 8, n_ent * 4, hipMemcpyHostToDevice, c->stream));
+        return PC_OK;
+    });
+    if (rc != PC_OK) return rc;
+    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
+    if (stats) *stats = run.sum;
+    return PC_OK;
+}
+
 // elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by
 extern "C" int pc_rows_pass_span(int pass_kind) { return pc_rows_slab_span(pass_kind); }
+// the tile edge of the nearest-neighbours rows form's column pass (rows and columns): what a test of its seams sizes its inputs by
+extern "C" int pc_nearest_rows_tile(void) { return pc_nn_rows_tile(); }

@@ -128,7 +128,7 @@ struct pc_ctx {
     // pc_fill_nearest: key[N][K] (order-preserving u64 of the value), then val[N][K] | nbr[N][K] (one D2H), and their pinned host image
     DevBuf b_nn_key, b_nn_out;
     PinnedBuf h_nn;                         // the neighbours and values lent out by pc_fill_nearest
-    float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest with stats (pc_last_nearest_times)
+    float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest / pc_fill_rows_nearest with stats (pc_last_nearest_times)
     // pc_fill_tree: comp[N] | next[N], best[N], two lists of N + PC_TREE_TAIL keys (the resident forest and the one a pass writes), the
     // rounds' live words; the keys' pinned host image and the pinned result val[N] | src[N] | tgt[N]
     DevBuf b_tree_comp, b_tree_best, b_tree_list, b_tree_live;
@@ -254,7 +254,7 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
 //   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device.  dom says which pairs
-//           its values are: the shard of a triangular slab, or -- edges, components and tree; nearest refuses it at compile time -- the
+//           its values are: the shard of a triangular slab, or the
 //           PcRowsSlab of one slab of a rows slab fill (pc_rows_slab_fill, pc_fill_slabs.hip: f64[m][N] of a range of query rows); begin
 //           and end are the triangular walk's
 //   end     labels / finish and the D2H copy; the result pointers and counts into the run
@@ -297,7 +297,7 @@ struct PcSlabRun {
     }
 PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill");
 PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill");
-PC_SLAB_FILL(PcNearestFill, PcShard, "nearest", "a nearest-neighbours fill");
+PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill");
 PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill");
 #undef PC_SLAB_FILL
 int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what);

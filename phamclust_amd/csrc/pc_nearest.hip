@@ -20,12 +20,24 @@
 //                devices, staged on the root as fkey / fnbr [n_foreign][N][K], go into the root's, one wave per genome.  A pair lies
 //                in exactly one stretch (its target's), so no real entry occurs twice; a foreign list may end in worst sentinels (its
 //                device need not have met K candidates of the genome), which are no candidates.
+//   k_nn_qrows / k_nn_qcols   the two passes of pc_fill_rows_nearest over a ROWS slab (PcRowsSlab: f64[m][n], row r the values of query
+//                genome rows[r] against every genome), which grow lists seeded from a stored result.  They are no flat passes -- a wave
+//                or a workgroup owns whole rows or whole columns of the slab, not a run of its elements -- so they do not go through
+//                pc_slab_pass.h; they take the PcRowsSlab as it is (adv_* unused).
+//                k_nn_qrows: one wave per slab row, q = rows[r]: the candidates (v[r][g], g) for every g != q, other query genomes
+//                included -- a query row lies in exactly one slab, so the list, begun empty, is complete after this one wave.
+//                k_nn_qcols: a workgroup owns 64 consecutive genomes (columns) and walks the slab's rows in tiles of 64, staged as
+//                keys into LDS (stride 65, one 512-byte run per row); each of its four waves holds 16 columns' lists in registers
+//                and reads a column of the tile lanes across rows, exactly as k_nn_cols; the candidate's index is rows[row].  A
+//                column that is itself a query genome is skipped whole (its list is k_nn_qrows'); rows >= m and columns >= n stage
+//                the worst sentinel and are no candidates.  Nothing is read beyond m * n values.
 // A genome's list lives one entry per lane of a wave (why K <= 64).  The K-th entry is "the bar": a ballot of `candidate beats the
 // bar` finds the few candidates that matter (after the warm-up about K ln(n / K) per genome); each of them is inserted at the
 // position popcount(ballot(entry comes before the candidate)), the lanes behind it taking their lower neighbour's entry.
 // Who writes what: the list of genome g is written by exactly one wave per launch -- in k_nn_rows the wave of target g, in k_nn_cols
-// the wave that owns source g -- and the launches are ordered on the stream.  No atomics, no flags, nothing one workgroup waits for
-// from another.  Nothing is read beyond Lp: an element lbase(t) + s is read only for s < t < t1; loads are 8 bytes wide.
+// the wave that owns source g; in k_nn_qrows the wave of query row g, in k_nn_qcols the wave that owns the old column g -- and the
+// launches are ordered on the stream.  No atomics, no flags, nothing one workgroup waits for from another.  Nothing is read beyond Lp:
+// an element lbase(t) + s is read only for s < t < t1, an element row * n + g of a rows slab only for row < m, g < n; loads are 8 bytes wide.
 #include "pc_pairs.h"
 
 #define NN_THREADS 256
@@ -153,6 +165,71 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_cols(const double* __restrict
     }
 }
 
+// query-row pass of a rows slab: wave w of workgroup b takes slab row b * NN_WAVES + w
+__global__ __launch_bounds__(NN_THREADS) void k_nn_qrows(const double* __restrict__ vals, PcRowsSlab dom, nn_key flip, int K,
+                                                         nn_key* __restrict__ key, int32_t* __restrict__ nbr) {
+    const int lane = threadIdx.x & 63;
+    const int r = (int)blockIdx.x * NN_WAVES + (int)(threadIdx.x >> 6);
+    if (r >= dom.m) return;                            // (the whole wave)
+    const int n = dom.n, q = dom.rows[r];
+    const double* __restrict__ row = vals + (size_t)r * n;
+    nn_key ek = NN_WORST_KEY; int ei = NN_WORST_IDX;   // a query genome's list begins empty: all its n - 1 >= K candidates are in this row
+    for (int base = 0; base < n; base += 128) {        // two independent 512-byte loads in flight
+        const int g0 = base + lane, g1 = base + 64 + lane;
+        const bool i0 = g0 < n, i1 = g1 < n;
+        const double v0 = i0 ? row[g0] : 0.0, v1 = i1 ? row[g1] : 0.0;
+        nn_take(ek, ei, nn_key_of(v0, flip), g0, i0 && g0 != q, K, lane);
+        if (base + 64 < n) nn_take(ek, ei, nn_key_of(v1, flip), g1, i1 && g1 != q, K, lane);
+    }
+    const size_t at = (size_t)q * K + lane;
+    if (lane < K) { key[at] = ek; nbr[at] = ei; }
+}
+
+// old-column pass of a rows slab: workgroup b takes the genomes [64 b, 64 b + 64) as columns
+__global__ __launch_bounds__(NN_THREADS) void k_nn_qcols(const double* __restrict__ vals, PcRowsSlab dom, nn_key flip, int K,
+                                                         nn_key* __restrict__ key, int32_t* __restrict__ nbr) {
+    __shared__ nn_key tile[NN_TILE * NN_LD];           // [row of the tile][column of the block], 33,280 bytes
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int m = dom.m, n = dom.n;
+    const int cb = (int)blockIdx.x * NN_TILE;          // first column of the block
+    nn_key lk[NN_SRC_PER_WAVE]; int li[NN_SRC_PER_WAVE];
+    unsigned skip = 0;                                 // bit q: the wave's column q is beyond n or a query genome (wave-uniform)
+#pragma unroll
+    for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+        const int g = cb + wv * NN_SRC_PER_WAVE + q;
+        const bool live = g < n && !dom.is_query[g];
+        if (!live) skip |= 1u << q;
+        lk[q] = NN_WORST_KEY; li[q] = NN_WORST_IDX;
+        if (live && lane < K) { lk[q] = key[(size_t)g * K + lane]; li[q] = nbr[(size_t)g * K + lane]; }
+    }
+    skip = (unsigned)__builtin_amdgcn_readfirstlane((int)skip);
+    for (int rb = 0; rb < m; rb += NN_TILE) {
+        // stage: row i of the tile = slab row rb + i, lanes across the block's columns; only elements with row < m, column < n exist
+#pragma unroll
+        for (int i = 0; i < NN_TILE / NN_WAVES; ++i) {  // (sixteen independent 512-byte loads in flight per wave)
+            const int tr = wv + i * NN_WAVES, row = rb + tr, g = cb + lane;
+            nn_key k = NN_WORST_KEY;
+            if (row < m && g < n) k = nn_key_of(vals[(size_t)row * n + g], flip);
+            tile[tr * NN_LD + lane] = k;
+        }
+        __syncthreads();
+        const int row = rb + lane;                     // this lane's candidate of every column of the wave: the query genome of its row
+        const bool have = row < m;
+        const int ci = have ? dom.rows[row] : NN_WORST_IDX;
+#pragma unroll
+        for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+            if ((skip >> q) & 1u) continue;            // (wave-uniform)
+            nn_take(lk[q], li[q], tile[lane * NN_LD + wv * NN_SRC_PER_WAVE + q], ci, have, K, lane);
+        }
+        __syncthreads();                               // the tile is rewritten by the next round
+    }
+#pragma unroll
+    for (int q = 0; q < NN_SRC_PER_WAVE; ++q) {
+        const int g = cb + wv * NN_SRC_PER_WAVE + q;
+        if (!((skip >> q) & 1u) && lane < K) { key[(size_t)g * K + lane] = lk[q]; nbr[(size_t)g * K + lane] = li[q]; }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_nn_finish(const nn_key* __restrict__ key, double* __restrict__ val, int64_t n, nn_key flip) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) val[i] = nn_value_of(key[i], flip);
@@ -203,6 +280,48 @@ int pc_launch_nn_select(const double* vals, int64_t Lp, int t0, int t1, int as_d
     hipLaunchKernelGGL(k_nn_cols, dim3((unsigned)((t1 - 1 + NN_TILE - 1) / NN_TILE)), dim3(NN_THREADS), 0, st, vals, t0, t1, flip, K, key, nbr);   // (Lp > 0: t1 >= 2)
     return nn_check("k_nn_cols");
 }
+
+// vals: one filled slab of a rows slab fill, f64[dom.m][dom.n] (Lp = m * n); key / nbr: [n][K], 1 <= K <= min(64, n - 1).  The lists
+// of the slab's query genomes are written whole; those of the other genomes take the slab's rows as candidates.
+int pc_launch_nn_select_rows(const double* vals, int64_t Lp, const PcRowsSlab& dom, int as_distance, int K, unsigned long long* key, int32_t* nbr,
+                             hipStream_t st) {
+    if (K < 1 || K > 64 || dom.m < 1 || dom.n < 2 || K > dom.n - 1 || dom.m > dom.n || Lp != (int64_t)dom.m * dom.n || !dom.rows || !dom.is_query) {
+        pc_set_error("pc_launch_nn_select_rows: %d rows of %d genomes with %lld values, K = %d", dom.m, dom.n, (long long)Lp, K);
+        return PC_ERR_ARG;
+    }
+    const nn_key flip = as_distance ? 0ull : ~0ull;
+    hipLaunchKernelGGL(k_nn_qrows, dim3((unsigned)((dom.m + NN_WAVES - 1) / NN_WAVES)), dim3(NN_THREADS), 0, st, vals, dom, flip, K, key, nbr);
+    int rc = nn_check("k_nn_qrows");
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(k_nn_qcols, dim3((unsigned)((dom.n + NN_TILE - 1) / NN_TILE)), dim3(NN_THREADS), 0, st, vals, dom, flip, K, key, nbr);
+    return nn_check("k_nn_qcols");
+}
+// The seed of pc_fill_rows_nearest, checked and packed on the host: seed_nbr / seed_val [N][k_seed], of which the first ks columns of
+// every row g with !is_query[g] go into key / idx [N][K] (ks <= K); everything else is the sentinel.  The transform is nn_key_of's, in
+// plain integer arithmetic.  Returns 0, or 1 (an entry that is out of range, a query genome or g itself) / 2 (a row that does not
+// ascend in (key, index)) with the entry in *bad_g, *bad_j; nothing on the device is touched.
+int pc_nn_seed_pack(const int32_t* seed_nbr, const double* seed_val, int k_seed, int ks, int N, int K, const uint8_t* is_query, int as_distance,
+                    unsigned long long* key, int32_t* idx, int* bad_g, int* bad_j) {
+    const nn_key flip = as_distance ? 0ull : ~0ull;
+    for (int g = 0; g < N; ++g) {
+        nn_key* const kr = key + (size_t)g * K; int32_t* const ir = idx + (size_t)g * K;
+        for (int j = 0; j < K; ++j) { kr[j] = NN_WORST_KEY; ir[j] = NN_WORST_IDX; }
+        if (is_query[g]) continue;
+        for (int j = 0; j < ks; ++j) {
+            const int32_t h = seed_nbr[(size_t)g * k_seed + j];
+            nn_key u = 0;
+            __builtin_memcpy(&u, &seed_val[(size_t)g * k_seed + j], 8);
+            const nn_key kj = (u ^ ((u >> 63) ? ~0ull : (1ull << 63))) ^ flip;
+            *bad_g = g; *bad_j = j;
+            if (h < 0 || h >= N || h == g || is_query[h]) return 1;
+            if (j > 0 && !(kr[j - 1] < kj || (kr[j - 1] == kj && ir[j - 1] < h))) return 2;
+            kr[j] = kj; ir[j] = h;
+        }
+    }
+    return 0;
+}
+// the column pass's tile edge (pc_nearest_rows_tile)
+int pc_nn_rows_tile(void) { return NN_TILE; }
 
 int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st) {
     if (n <= 0) return PC_OK;

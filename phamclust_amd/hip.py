@@ -77,7 +77,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_fill_nearest", "pc_last_nearest_times", "pc_multi_fill_edges", "pc_multi_fill_components", "pc_multi_fill_nearest",
            "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan", "pc_fill_tree", "pc_multi_fill_tree", "pc_last_tree_times",
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
-           "pc_rows_pass_span"]
+           "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -168,6 +168,10 @@ def load():
                                     ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_rows_pass_span.argtypes = [ctypes.c_int]
+    L.pc_fill_rows_nearest.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _f64p, ctypes.c_int32, ctypes.c_int64,
+                                       ctypes.POINTER(_i32p), ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(PcStats)]
+    L.pc_nearest_rows_tile.argtypes = []
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -665,7 +669,7 @@ class Context(_SlabFills):
 
     NEAREST_MAX_K = 64                    # PC_NEAREST_MAX_K: a genome's list lives one entry per lane of a wave
 
-    # -- the rows forms of fill_edges / fill_components / fill_tree: a stored result grown by new genomes (one GPU) -----------------------
+    # -- the rows forms of fill_edges / fill_components / fill_tree / fill_nearest: a stored result grown by new genomes (one GPU) -----------------------
     ROWS_PASSES = ("edges", "components", "tree")
 
     @staticmethod
@@ -758,6 +762,44 @@ class Context(_SlabFills):
         if not want_stats:
             return tuple(out)
         return (*out, self._slab_stats("tree", stats, n_edges=int(n.value), n_slabs=int(nsl.value), **self._tree_rounds()))
+
+    @staticmethod
+    def nearest_rows_tile():
+        """The tile edge of :meth:`fill_rows_nearest`'s column pass (``pc_nearest_rows_tile``; host arithmetic, no GPU): rows and
+        columns of the slab a workgroup stages at a time -- what a test of the pass's seams sizes its inputs by."""
+        return int(load().pc_nearest_rows_tile())
+
+    def fill_rows_nearest(self, metric, k, rows, seed=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """:meth:`fill_nearest`'s lists of the whole collection from the stored lists of the other genomes: ``seed = (nbr, val)``,
+        two ``[N, k_seed]`` arrays in the uploaded collection's numbering -- row g of an old genome its best old neighbours, best
+        first (rows of the query genomes are ignored) -- replaces the empty lists, and the pairs that touch a query genome of
+        ``rows`` are merged into them by the one total order: ``len(rows) * N`` pairs filled instead of ``N (N - 1) / 2``, and
+        the result is :meth:`fill_nearest`'s, element for element.  With ``N_old = N - len(rows)`` and ``kk = min(k, N - 1)`` the
+        library refuses ``k_seed < min(kk, N_old - 1)``, no seed while ``N_old > 1``, and a seed entry that is out of range, a
+        query genome, the genome itself or out of order; columns beyond ``kk`` are cut.  Returns ``(nbr, val)``; ``want_stats``
+        adds :meth:`fill_nearest`'s stats (``n_slabs``: the ranges of rows walked).  One GPU."""
+        rows, prow, n_rows = self._rows_arg(rows)
+        n = self.n_genomes
+        s_nbr = s_val = None
+        k_seed = 0
+        if seed is not None:
+            s_nbr = np.ascontiguousarray(seed[0], dtype=np.int32)
+            s_val = np.ascontiguousarray(seed[1], dtype=np.float64)
+            if s_nbr.ndim != 2 or s_nbr.shape != s_val.shape or s_nbr.shape[0] != n:
+                raise ValueError(f"fill_rows_nearest: the seed must be two ({n}, k_seed) arrays, not {s_nbr.shape} and {s_val.shape}")
+            k_seed = int(s_nbr.shape[1])
+        pn, pv = _i32p(), _f64p()
+        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        stats = self._rows_fill("nearest", metric, int(bool(as_distance)), int(k), prow, n_rows,
+                                _ptr(s_nbr, _i32p) if k_seed and n else None, _ptr(s_val, _f64p) if k_seed and n else None, k_seed, int(slab_bytes),
+                                ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl))
+        if n and kk.value and pn and pv:
+            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
+        else:
+            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
+        if not want_stats:
+            return nbr, val
+        return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

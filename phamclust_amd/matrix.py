@@ -1135,6 +1135,45 @@ class NearestNeighbors:
         pair, first = pair[keep], first[keep]
         return SparseEdges(self.nodes, pair % max(n, 1), pair // max(n, 1), self.weights.reshape(-1)[first], is_distance=self.is_distance)
 
+    def extended(self, nodes, rows, values, k=None):
+        """These lists grown to ``nodes``: the host statement of ``neighbors_extend`` (arguments as ``SparseEdges.extended``:
+        ``values[i]`` holds the weights of node ``rows[i]`` against all of ``nodes``), equal to ``from_dense`` of the grown matrix cut
+        after ``k`` (default: this result's k).  An old node's stored list is the best of its old candidates, and every old
+        candidate outside it is worse than every entry in it, so the best k of {stored list} + {its pairs with the new nodes} is the
+        best k of all; a new node's row holds all of its candidates.  The old nodes keep their relative order, so re-indexing
+        changes no comparison.  ``k`` above this result's k is a ``ValueError`` unless the stored lists are complete (k = N_old - 1)."""
+        old_at, rows = _grown_positions(self.nodes, nodes, rows, "NearestNeighbors.extended")
+        n, n_old = len(nodes), len(self.nodes)
+        k = self.k if k is None else int(k)
+        if k > self.k and self.k < n_old - 1:
+            raise ValueError(f"NearestNeighbors.extended: the stored lists hold {self.k} of {n_old - 1} old neighbours and cannot decide {k}")
+        if k < 1 and n > 1:
+            raise ValueError("k must be at least 1")
+        kk = max(min(k, n - 1), 0)
+        values = np.asarray(values, dtype=np.float64).reshape(len(rows), n)
+        if np.isnan(values).any():
+            raise TypeError("cannot rank neighbours of a node with unset edges")
+        sign = 1.0 if self.is_distance else -1.0
+        indices = np.empty((n, kk), dtype=np.int32)
+        weights = np.empty((n, kk), dtype=np.float64)
+        for g, at in enumerate(old_at.tolist()):
+            others = np.concatenate([old_at[self.indices[g]], rows])
+            row = np.concatenate([self.weights[g], values[:, at]])
+            order = np.lexsort((others, sign * row))[:kk]
+            indices[at], weights[at] = others[order], row[order]
+        for i, q in enumerate(rows.tolist()):
+            others = np.concatenate([np.arange(q), np.arange(q + 1, n)])
+            row = values[i, others]
+            order = np.lexsort((others, sign * row))[:kk]
+            indices[q], weights[q] = others[order], row[order]
+        return NearestNeighbors(nodes, indices, weights, is_distance=self.is_distance)
+
+    def without(self, names):
+        """Refused: a list that named a removed genome needs its (k+1)-th entry to stay k long, and only a fill knows it
+        (``neighbors_de_novo`` over the remaining genomes)."""
+        raise ValueError("NearestNeighbors.without: a list that named a removed genome needs its next-best entry, which only a fill knows; "
+                         "removing genomes needs a fill of the remaining ones (neighbors_de_novo)")
+
 
 def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     """Each genome's ``k`` nearest neighbours in ``matrix_de_novo(genomes, func, cpus, as_distance)`` as a
@@ -1331,7 +1370,7 @@ def tree_de_novo(genomes, func, as_distance=True, slab_bytes=0):
 
 
 # ---------------------------------------------------------------------------------------
-# Growing a stored sparse result: new genomes against an edge list, a partition, a tree
+# Growing a stored sparse result: new genomes against an edge list, a partition, a tree, k-nearest lists
 # ---------------------------------------------------------------------------------------
 def _extend_plan(stored_nodes, genomes, caller):
     """What ``edges_extend`` / ``components_extend`` / ``tree_extend`` check of their arguments, as ``matrix_extend`` does: distinct
@@ -1509,6 +1548,123 @@ def tree_extend(tree, genomes, func, verify=4, slab_bytes=0):
     logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} tree edges in {stats['n_slabs']} slab(s): "
                   f"guard+fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds {stats.get('ms_rounds', 0.0):.3f} ms)")
     return SingleLinkageTree(names, src, tgt, weight, is_distance=as_distance)
+
+
+def _guard_neighbors(names, metric, checked, values, old_at, indices, weights, is_distance):
+    """For every verified old genome (``checked``: positions among the genomes; ``values``: their refilled rows) the best of its
+    refilled row, restricted to the old genomes, must equal its stored list -- ``indices`` (positions among the genomes) and
+    ``weights`` [N_old, k] -- in indices and value bits."""
+    k = indices.shape[1]
+    slot = {int(g): i for i, g in enumerate(old_at.tolist())}
+    for i, q in enumerate(checked):
+        others = old_at[old_at != q]
+        row = np.ascontiguousarray(values[i, others], dtype=np.float64)
+        order = np.lexsort((others, row if is_distance else -row))[:k]
+        want_idx, want_w = others[order], row[order]
+        have_idx, have_w = indices[slot[q]], np.ascontiguousarray(weights[slot[q]], dtype=np.float64)
+        bad = np.flatnonzero((want_idx != have_idx) | (want_w.view(np.uint64) != have_w.view(np.uint64)))
+        if bad.shape[0]:
+            j = int(bad[0])
+            raise ValueError(f"pair ({names[q]}, {names[int(have_idx[j])]}): the nearest-neighbours list holds it at place {j + 1} with {float(have_w[j])!r}, the "
+                             f"{metric} fill gives ({names[int(want_idx[j])]}, {float(want_w[j])!r}) there: it was not filled with this metric from these "
+                             f"genomes in this order")
+
+
+def neighbors_extend(neighbors, genomes, func, k=None, verify=4, slab_bytes=0):
+    """New genomes against stored k-nearest lists: the :class:`NearestNeighbors` over all of ``genomes`` that
+    ``neighbors_de_novo(genomes, func, k, neighbors.is_distance)`` would return, element for element, computing only the pairs that
+    touch a genome ``neighbors`` lacks (``Context.fill_rows_nearest``: the stored lists seed the resident ones).  ``k`` defaults to
+    ``neighbors.k``; ``k > neighbors.k`` is a ``ValueError`` unless the stored lists are complete (``neighbors.k == N_old - 1``): a
+    shorter list cannot decide more neighbours.  Arguments, refusals and routes as ``tree_extend``.  The guard: for each verified old
+    genome, the best ``neighbors.k`` of its refilled row, restricted to the old genomes, must equal its stored list in indices and
+    value bits.  Removing genomes is no such call: ``NearestNeighbors.without`` says why."""
+    names, old_at, new_idx = _extend_plan(neighbors.nodes, genomes, "neighbors_extend")
+    as_distance, n_old = neighbors.is_distance, int(old_at.shape[0])
+    if k is None:
+        k = neighbors.k
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NEAREST_MAX_K:
+        raise ValueError(f"neighbors_extend: k must be an integer in 1..{NEAREST_MAX_K}, not {k!r}")
+    k = int(k)
+    if n_old and k > neighbors.k and neighbors.k < n_old - 1:
+        raise ValueError(f"neighbors_extend: the stored lists hold {neighbors.k} of {n_old - 1} old neighbours and cannot decide {k}: fill from scratch "
+                         "(neighbors_de_novo)")
+    if n_old == 0:
+        return neighbors_de_novo(genomes, func, k, as_distance=as_distance, slab_bytes=slab_bytes)
+    indices = old_at[neighbors.indices].reshape(n_old, neighbors.k)
+    if not new_idx:
+        kk = min(k, neighbors.k)
+        return NearestNeighbors(names, indices[:, :kk], neighbors.weights[:, :kk], is_distance=as_distance)
+    ctx, metric, record = _extend_upload(genomes, func, "neighbors_extend")
+    import time
+    t0 = time.perf_counter()
+    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
+    _guard_neighbors(names, metric, checked, values, old_at, indices, neighbors.weights, as_distance)
+    seed_nbr = np.zeros((len(names), neighbors.k), dtype=np.int32)
+    seed_val = np.zeros((len(names), neighbors.k), dtype=np.float64)
+    seed_nbr[old_at], seed_val[old_at] = indices, neighbors.weights
+    nbr, val, stats = ctx.fill_rows_nearest(metric, k, new_idx, seed=(seed_nbr, seed_val), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
+    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, the {stats['k']} nearest of each in {stats['n_slabs']} slab(s): "
+                  f"guard+fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection {stats.get('ms_select', 0.0):.3f} ms)")
+    return NearestNeighbors(names, nbr, val, is_distance=as_distance)
+
+
+def nearest_to_file(found, filepath):
+    """``nearest_<metric>.tsv``: one ``source<TAB>target<TAB>similarity`` line per neighbour of a distance result, sources in node
+    order, targets nearest first; the weights inverted as for the adjacency file, "%.6f"."""
+    with open(filepath, "w") as handle:
+        handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in found.inverted())
+    return filepath
+
+
+def nearest_from_file(filepath, names):
+    """The distance :class:`NearestNeighbors` a ``nearest_<metric>.tsv`` holds, bit for bit: its nodes are the names that occur as
+    sources in the file, in the order of ``names`` (the genomes in fill order; ``KeyError`` for a name they lack), and a similarity
+    comes back as ``tree_from_file`` decodes it.  ``ValueError`` for a line that is no neighbour, sources whose lines are not together
+    or come in another order than ``names``, an unequal number of lines per source, a count other than min(K, n - 1) (more than
+    n - 1 lines for n sources, or none), or a target that is no source, the source itself, or listed twice."""
+    index = {name: k for k, name in enumerate(names)}
+    sources, lists = [], []
+    with open(filepath, "r") as handle:
+        for number, line in enumerate(handle, start=1):
+            fields = line.rstrip("\n").split("\t")
+            if len(fields) != 3:
+                raise ValueError(f"{filepath}:{number}: expected source<TAB>target<TAB>similarity")
+            for name in fields[:2]:
+                if name not in index:
+                    raise KeyError(f"{filepath}:{number}: '{name}' is not among the genomes")
+            try:
+                k = int(np.rint(float(fields[2]) * 1.0e6))
+            except (ValueError, OverflowError):
+                raise ValueError(f"{filepath}:{number}: '{fields[2]}' is no similarity") from None
+            if not 0 <= k <= 1000000:
+                raise ValueError(f"{filepath}:{number}: similarity {fields[2]} is outside [0, 1]")
+            s = index[fields[0]]
+            if not sources or sources[-1] != s:
+                if sources and s <= sources[-1]:
+                    raise ValueError(f"{filepath}:{number}: source '{fields[0]}' comes against the genomes' order (or its lines are not together): "
+                                     "the file was written for another order")
+                sources.append(s)
+                lists.append([])
+            lists[-1].append((index[fields[1]], (1000000 - k) / 1000000.0))
+    n = len(sources)
+    count = len(lists[0]) if lists else 0
+    uneven = next((g for g, one in zip(sources, lists) if len(one) != count), None)
+    if uneven is not None:
+        raise ValueError(f"{filepath}: '{names[uneven]}' has {len(lists[sources.index(uneven)])} lines, '{names[sources[0]]}' has {count}: every source "
+                         "lists the same number of neighbours")
+    if n and not 1 <= count <= n - 1:
+        raise ValueError(f"{filepath}: {count} neighbours per source for {n} sources is no min(K, n - 1)")
+    at = {g: k for k, g in enumerate(sources)}
+    for g, one in zip(sources, lists):
+        targets = [t for t, _ in one]
+        bad = next((t for t in targets if t not in at or t == g), None)
+        if bad is not None or len(set(targets)) != len(targets):
+            raise ValueError(f"{filepath}: the neighbours of '{names[g]}' must be distinct other sources of the file"
+                             + (f" ('{names[bad]}' is not)" if bad is not None else ""))
+    indices = np.asarray([[at[t] for t, _ in one] for one in lists], dtype=np.int32).reshape(n, count)
+    weights = np.asarray([[w for _, w in one] for one in lists], dtype=np.float64).reshape(n, count)
+    return NearestNeighbors([names[g] for g in sources], indices, weights, is_distance=True)
 
 
 def tree_to_file(tree, filepath):

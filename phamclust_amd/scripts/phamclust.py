@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, neighbors_de_novo, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -122,6 +122,7 @@ class _Run:
         self.genomes, self.by_name, self.cache, self.stage, self.fills = [], {}, None, None, None
         self.rank, self.world = 0, 1          # this process's place in the job (one process per GPU)
         self.extend = None                    # --extend FILE: a distance matrix over a subset of the genomes
+        self.grow_nearest = None              # --grow-nearest FILE: a nearest_<metric>.tsv over a subset of the genomes
         self.grow = None                      # --grow FILE: a tree_<metric>.tsv / components_<metric>.tsv over a subset of the genomes
 
     @staticmethod
@@ -277,7 +278,12 @@ class _Run:
         Distances are filled and inverted, as for the adjacency file.  No matrix, no threshold, nothing cached or clustered."""
         self.banner(2, f"{self.metric} nearest neighbours (nearest-neighbours fill)")
         t0 = time.perf_counter()
-        found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True)
+        if self.grow_nearest is not None:
+            names = [g.name for g in self.genomes]
+            found = self.grown(lambda: nearest_from_file(self.grow_nearest, names),
+                               lambda old: neighbors_extend(old, self.genomes, METRICS[self.metric], k=k), t0, flag="--grow-nearest", path=self.grow_nearest)
+        else:
+            found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True)
         st = _matrix.LAST_FILL
         log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {found.k} nearest of each of {len(found):,} genomes from {st.get('n_slabs', 1)} slab(s) "
                  f"on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, "
@@ -286,8 +292,7 @@ class _Run:
         if self.metric in _metrics.PARITY_NOTE:
             log.info(f"parity: {_metrics.parity_note(self.metric)}")
         target = self.outdir / f"nearest_{self.metric}.tsv"
-        with open(target, "w") as handle:
-            handle.writelines(f"{source}\t{other}\t{weight:.6f}\n" for source, other, weight in found.inverted())
+        nearest_to_file(found, target)
         log.info(f"wrote {target.name}")
         return found
 
@@ -316,14 +321,14 @@ class _Run:
         log.info(f"wrote {target.name}")
         return found
 
-    def grown(self, read, extend, t0):
-        """Stage 2 under --grow: the stored tree or components are read back, held against a refill of a few old genomes and grown by
-        the rows of the genomes they lack (tree_extend / components_extend)."""
+    def grown(self, read, extend, t0, flag="--grow", path=None):
+        """Stage 2 under --grow / --grow-nearest: the stored tree, components or nearest-neighbour lists are read back, held against a
+        refill of a few old genomes and grown by the rows of the genomes they lack (tree_extend / components_extend / neighbors_extend)."""
         try:
             old = read()
             found = extend(old)
         except (ValueError, KeyError, OSError) as exc:
-            log.error(f"--grow {self.grow}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
+            log.error(f"{flag} {self.grow if path is None else path}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
             print("growing the stored result failed - check log for details")
             sys.exit(1)
         st, n = _matrix.LAST_FILL, len(found.nodes)
@@ -492,7 +497,7 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, grow=None, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -502,7 +507,11 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     ``nearest``: stop after a nearest-neighbours fill of that many neighbours per genome and write only ``nearest_<metric>.tsv``;
     ``tree``: stop after a tree fill and write only ``tree_<metric>.tsv``, the single-linkage dendrogram's edges in merge order;
     ``grow``: with ``tree``, the ``tree_<metric>.tsv`` -- with ``components_only`` and an ``edge_thresh``, the ``components_<metric>.tsv`` --
-    an earlier run wrote over a subset of the genomes (``--grow``): only the pairs of the genomes it lacks are filled, on one GPU."""
+    an earlier run wrote over a subset of the genomes (``--grow``): only the pairs of the genomes it lacks are filled, on one GPU;
+    ``grow_nearest``: with ``nearest``, the ``nearest_<metric>.tsv`` of an earlier run over a subset of the genomes (``--grow-nearest``),
+    grown the same way."""
+    if grow_nearest is not None and (nearest is None or grow is not None):
+        raise ValueError("grow_nearest goes with nearest, and not with grow")
     if grow is not None:
         if adjacency_only or no_matrix or nearest is not None or extend is not None or tree == bool(components_only):
             raise ValueError("grow goes with exactly one of tree and components_only, and with nothing else")
@@ -544,12 +553,15 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["tree"] = "only (single-linkage dendrogram)"
     if grow is not None:
         settings["grow"] = grow
+    if grow_nearest is not None:
+        settings["grow"] = grow_nearest
     log.info("--- 0: settings ---")
     for key, value in settings.items():
         log.info(f"{key:<11}{value}")
     run = _Run(outdir, metric, colors, midpoint)
     run.extend = extend
     run.grow = grow
+    run.grow_nearest = grow_nearest
     run.rank, run.world = distributed.ensure_process_group()      # (0, 1) unless started by torch.distributed.run
     _mark("torch_import_and_process_group")
     run.read(infile, is_genome_dir)
@@ -633,6 +645,8 @@ def gpus_plan(args, route, packed):
     --extend's rows fill is a one-GPU call.  --adjacency-only, --components-only, --nearest and --tree spread over the GPUs of this process
     (pc_multi_fill_edges / _components / _nearest / _tree) under the same estimate as the dense fill; one process per GPU has no route for
     them, so under PHAMCLUST_MULTI=launcher they stay on one GPU."""
+    if getattr(args, "grow_nearest", None) is not None:
+        return 1, "one", "--grow-nearest fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
     if getattr(args, "grow", None) is not None:
         return 1, "one", "--grow fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
     if args.extend is not None:
@@ -729,7 +743,7 @@ def _run(args, argv):
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
-                  nearest=args.nearest, tree=args.tree, grow=args.grow)
+                  nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")

@@ -15,6 +15,17 @@ and, alternated with it call by call on the same context, the only route the com
   ratio      dense wall / call wall
 The two results are compared once per configuration (indices and values, exactly).  The output is what profiles/nearest_fill.txt
 records.
+
+``--rows`` times the rows form instead (pc_fill_rows_nearest: stored lists grown by new genomes): jc on synth(20000,5000) and peq on
+synth(5000,5000) at k = 16, with 5 / 50 / 500 new genomes (``--new``), spread evenly over the collection.  The stored lists of the old
+genomes come from one dense fill and a host selection restricted to them (not timed).  Per configuration, call by call alternated with
+``Context.fill_nearest`` from scratch at the same N and k -- what a user without the rows form must run -- ``--steps`` calls after
+``--warmup``:
+  fill / select / finish / wall   as above, of Context.fill_rows_nearest(borrow=True); select is the two rows passes' own time
+  scratch                         host clock around Context.fill_nearest(borrow=True)
+  ratio                           scratch wall / grown wall
+The grown lists are compared with the from-scratch ones once per configuration (exactly).  The output is what
+profiles/rows_nearest_fill.txt records.
 """
 
 import argparse
@@ -27,6 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM_PEAK = 8.0e12
 CONFIGS = (("jc", 20000, 16), ("jc", 20000, 64), ("peq", 5000, 16))
+ROWS_CONFIGS = (("jc", 20000, 16), ("peq", 5000, 16))
 
 
 def spread(xs):
@@ -57,6 +69,71 @@ def dense_route(ctx, metric, n, k):
     return nbr, val, t1 - t0, t2 - t1
 
 
+def stored_lists(square, new, k):
+    """The k best old neighbours of every old genome from the square matrix (diagonal inf), as [n, k] seed arrays in the grown
+    numbering: the lists a fill of the old genomes alone would have stored."""
+    import numpy as np
+    n = square.shape[0]
+    is_new = np.zeros(n, dtype=bool)
+    is_new[new] = True
+    old = np.flatnonzero(~is_new)
+    ks = min(k, old.shape[0] - 1)
+    nbr = np.zeros((n, ks), dtype=np.int32)
+    val = np.zeros((n, ks), dtype=np.float64)
+    for g in old.tolist():
+        row = square[g, old]
+        bar = np.partition(row, ks - 1)[ks - 1]
+        cand = np.flatnonzero(row <= bar)
+        order = cand[np.lexsort((old[cand], row[cand]))][:ks]
+        nbr[g] = old[order]
+        val[g] = row[order]
+    return nbr, val
+
+
+def rows_mode(a):
+    import numpy as np
+    from scipy.spatial.distance import squareform
+    from phamclust_amd import hip
+    from phamclust_amd.synth import synth_packed
+    configs = [(c.split(":")[0], int(c.split(":")[1]), int(c.split(":")[2])) for c in a.configs.split(",")] if a.configs else ROWS_CONFIGS
+    counts = [int(x) for x in a.new.split(",")]
+    print(f"rows form of the nearest-neighbours fill against the fill from scratch: library version {hip.load().pc_version()}, {a.steps} calls "
+          f"after {a.warmup} warm-up, ms")
+    ctx = hip.Context(int(os.environ.get("PHAMCLUST_DEVICE", "0")))
+    for metric, n, k in configs:
+        ctx.upload(synth_packed(n, a.phams), residues=metric in hip.NEEDS_RESIDUES)
+        square = squareform(np.asarray(ctx.fill(metric, borrow=True)))
+        np.fill_diagonal(square, np.inf)
+        for m in counts:
+            new = np.unique(np.linspace(0, n - 1, m).astype(np.int64))
+            seed = stored_lists(square, new, k)
+            print(f"\n{metric} synth({n},{a.phams}) k = {k}, {new.shape[0]} new genomes: {new.shape[0] * n:,} values filled instead of {n * (n - 1) // 2:,} pairs")
+            got = {key: [] for key in ("fill", "select", "finish", "wall", "scratch", "scratch_select")}
+            same = None
+            for step in range(a.warmup + a.steps):
+                t0 = time.perf_counter()
+                nbr, val, st = ctx.fill_rows_nearest(metric, k, new, seed=seed, want_stats=True, borrow=True)
+                wall = time.perf_counter() - t0
+                nbr, val = np.array(nbr), np.array(val)
+                t0 = time.perf_counter()
+                w_nbr, w_val, w_st = ctx.fill_nearest(metric, k, want_stats=True, borrow=True)
+                scratch = time.perf_counter() - t0
+                if same is None:
+                    same = bool(np.array_equal(nbr, w_nbr) and np.array_equal(val.view(np.uint64), np.asarray(w_val).view(np.uint64)))
+                if step >= a.warmup:
+                    for key, x in (("fill", st["ms_total"]), ("select", st["ms_select"]), ("finish", st["ms_finish"]), ("wall", wall * 1e3),
+                                   ("scratch", scratch * 1e3), ("scratch_select", w_st["ms_select"])):
+                        got[key].append(x)
+            print(f"  {st['n_slabs']} slab(s); grown and from-scratch lists agree: {same}")
+            for key, title in (("fill", "rows fill (device)"), ("select", "ms_select (device)"), ("finish", "finish (device)"), ("wall", "grown call wall"),
+                               ("scratch", "from-scratch call wall"), ("scratch_select", "  its ms_select")):
+                print(f"    {title:<24}{spread(got[key])}")
+            print(f"    ratio scratch / grown   min {min(got['scratch']) / min(got['wall']):.1f}x   median "
+                  f"{statistics.median(got['scratch']) / statistics.median(got['wall']):.1f}x")
+        del square
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--phams", type=int, default=5000)
@@ -64,7 +141,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--slabs", type=int, default=0, help="also time the call cut into this many slabs (slab_bytes = dense bytes / this)")
     ap.add_argument("--configs", default=None, help="comma-separated metric:N:k triples instead of the default three")
+    ap.add_argument("--rows", action="store_true", help="time the rows form (pc_fill_rows_nearest) against the fill from scratch instead")
+    ap.add_argument("--new", default="5,50,500", help="with --rows: comma-separated counts of new genomes")
     a = ap.parse_args()
+    if a.rows:
+        return rows_mode(a)
     import numpy as np
     from phamclust_amd import hip
     from phamclust_amd.synth import synth_packed
