@@ -4,8 +4,8 @@
 // pc_last_nearest_times, and pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds.
 // Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill: begin, slab, end, and what several
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
-// multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point nulls its outputs,
-// fills a PcSlabRun, calls the driver and copies the results out.  Host only.
+// multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
+// own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
 // pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest (at the end of the file) grow a stored result by new genomes: the same
 // descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
 // either slab's pair domain.
@@ -325,18 +325,8 @@ int PcEdgesFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& 
 
 extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
                              const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    const int rc = pc_slab_fill<PcEdgesFill>(c, run);
-    if (rc != PC_OK) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcEdgesFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return pc_slab_fill<PcEdgesFill>(c, run); });
 }
 
 extern "C" int pc_last_edge_times(const pc_ctx* c, float* ms_compact, float* ms_d2h) {
@@ -411,17 +401,9 @@ int PcComponentsFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabR
 
 extern "C" int pc_fill_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
                                   const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (labels) *labels = nullptr;
-    if (n_components) *n_components = 0;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
-    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
-    const int rc = pc_slab_fill<PcComponentsFill>(c, run);
-    if (rc != PC_OK) return rc;
-    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict; run.threshold = threshold;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcComponentsFill>(run, {labels, n_components, n_edges, n_slabs}, stats, [&] { return pc_slab_fill<PcComponentsFill>(c, run); });
 }
 
 extern "C" int pc_last_component_times(const pc_ctx* c, float* ms_union, float* ms_labels) {
@@ -492,17 +474,8 @@ int PcNearestFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>
 
 extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, int64_t slab_bytes,
                                const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats) {
-    if (nbr) *nbr = nullptr;
-    if (val) *val = nullptr;
-    if (k_out) *k_out = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
-    const int rc = pc_slab_fill<PcNearestFill>(c, run);
-    if (rc != PC_OK) return rc;
-    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcNearestFill>(run, {nbr, val, k_out, n_slabs}, stats, [&] { return pc_slab_fill<PcNearestFill>(c, run); });
 }
 
 extern "C" int pc_last_nearest_times(const pc_ctx* c, float* ms_select, float* ms_finish) {
@@ -614,18 +587,8 @@ int PcTreeFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& r
 
 extern "C" int pc_fill_tree(pc_ctx* c, int metric, int as_distance, int64_t slab_bytes,
                             const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_fill_tree"; run.metric = metric; run.as_distance = as_distance;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    const int rc = pc_slab_fill<PcTreeFill>(c, run);
-    if (rc != PC_OK) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_fill_tree"; run.metric = metric; run.as_distance = as_distance; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcTreeFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return pc_slab_fill<PcTreeFill>(c, run); });
 }
 
 extern "C" int pc_last_tree_times(const pc_ctx* c, float* ms_rounds, float* ms_finish) {
@@ -684,167 +647,141 @@ template <class Fill> static int rows_walk(pc_ctx* c, PcSlabRun& run, const int3
     return PC_OK;
 }
 
-// seed(): the stored result onto the device, after begin has sized and initialised the state (N > 1 only)
-template <class Fill, class Seed> static int pc_rows_slab_fill(pc_ctx* c, PcSlabRun& run, const int32_t* rows, int n_rows, Seed seed) {
+// A rows form on one context: the refusals in the order of the public calls (pc_slab_check's, the rows argument, the seed), then begin,
+// the packed seed onto the device once begin has sized and initialised the state (N > 1 only), the rows walk, end.
+template <class Fill> static int pc_rows_slab_fill(pc_ctx* c, PcSlabRun& run, const int32_t* rows, int n_rows, typename Fill::Seed seed) {
     int rc = PC_OK;
+    if ((rc = pc_slab_check(c, run, Fill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows)) || (rc = seed.pack(c, run, rows, n_rows))) return rc;
     PC_ON_DEVICE(c);
     PcRange range(Fill::range);
     run.rows_form = true; run.n_query = n_rows;
     if ((rc = Fill::begin(c, run))) return rc;
     if (c->dev.N > 1) {
-        if ((rc = seed())) return rc;
+        if ((rc = seed.install(c, run))) return rc;
         if (n_rows > 0 && (rc = rows_walk<Fill>(c, run, rows, n_rows))) return rc;
     }
     return Fill::end(c, run);
 }
 
-extern "C" int pc_fill_rows_edges(pc_ctx* c, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
-                                  const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_fill_rows_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    int rc = PC_OK;
-    if ((rc = pc_slab_check(c, run, PcEdgesFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
-    if ((rc = pc_rows_slab_fill<PcEdgesFill>(c, run, rows, n_rows, [] { return (int)PC_OK; }))) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
+// ---- the seeds (PcNoSeed: pc_host.h) ----
+int PcLabelSeed::pack(const pc_ctx* c, const PcSlabRun& run, const int32_t*, int) {
+    if (!labels) return PC_OK;
+    const int N = c->dev.N;
+    packed.resize((size_t)N);
+    std::copy(labels, labels + N, packed.begin());
+    for (int g = 0; g < N; ++g)
+        if (packed[g] < 0 || packed[g] > g || packed[packed[g]] != packed[g]) {
+            pc_set_error("%s: seed_labels[%d] = %d is not the smallest member of a component (0 <= label <= genome, a label labels itself)", run.who, g, packed[g]);
+            return PC_ERR_ARG;
+        }
+    return PC_OK;
+}
+// parent[g] = the stored label, through the pinned labels image (end() rewrites it only after the stream has drained)
+int PcLabelSeed::install(pc_ctx* c, PcSlabRun&) const {
+    if (packed.empty()) return PC_OK;
+    memcpy(c->h_cc_labels.p, packed.data(), packed.size() * 4);
+    PC_HIP(hipMemcpyAsync(c->b_cc_parent.p, c->h_cc_labels.p, packed.size() * 4, hipMemcpyHostToDevice, c->stream));
     return PC_OK;
 }
 
-extern "C" int pc_fill_rows_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, const int32_t* rows, int n_rows,
-                                       const int32_t* seed_labels, int64_t slab_bytes, const int32_t** labels, int32_t* n_components, int64_t* n_edges,
-                                       int32_t* n_slabs, pc_stats* stats) {
-    if (labels) *labels = nullptr;
-    if (n_components) *n_components = 0;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_fill_rows_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
-    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
-    int rc = PC_OK;
-    if ((rc = pc_slab_check(c, run, PcComponentsFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+int PcTreeSeed::pack(const pc_ctx* c, const PcSlabRun& run, const int32_t*, int) {
     const int N = c->dev.N;
-    std::vector<int32_t> seed;                                              // (a copy: the caller may hand back the labels an earlier call lent out)
-    if (seed_labels) {
-        seed.assign(seed_labels, seed_labels + N);
-        for (int g = 0; g < N; ++g)
-            if (seed[g] < 0 || seed[g] > g || seed[seed[g]] != seed[g]) {
-                pc_set_error("%s: seed_labels[%d] = %d is not the smallest member of a component (0 <= label <= genome, a label labels itself)", run.who, g, seed[g]);
-                return PC_ERR_ARG;
-            }
-    }
-    rc = pc_rows_slab_fill<PcComponentsFill>(c, run, rows, n_rows, [&]() -> int {
-        if (seed.empty()) return PC_OK;
-        // parent[g] = the stored label, through the pinned labels image (end() rewrites it only after the stream has drained)
-        memcpy(c->h_cc_labels.p, seed.data(), (size_t)N * 4);
-        PC_HIP(hipMemcpyAsync(c->b_cc_parent.p, c->h_cc_labels.p, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        return PC_OK;
-    });
-    if (rc != PC_OK) return rc;
-    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
-    return PC_OK;
-}
-
-extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const int32_t* rows, int n_rows, const int32_t* seed_src, const int32_t* seed_tgt,
-                                 const double* seed_val, int32_t n_seed, int64_t slab_bytes, const int32_t** src, const int32_t** tgt, const double** val,
-                                 int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_fill_rows_tree"; run.metric = metric; run.as_distance = as_distance;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    int rc = PC_OK;
-    if ((rc = pc_slab_check(c, run, PcTreeFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
-    const int N = c->dev.N;
-    if (n_seed < 0 || n_seed > std::max(N - 1, 0)) { pc_set_error("%s: %d seed edges for %d genomes (a forest holds at most N - 1)", run.who, n_seed, N); return PC_ERR_ARG; }
-    if (n_seed > 0 && !(seed_src && seed_tgt && seed_val)) { pc_set_error("%s: a seed array is NULL", run.who); return PC_ERR_ARG; }
-    std::vector<unsigned long long> keys((size_t)n_seed);                   // (packed before begin: the caller may hand back the edges an earlier call lent out)
-    for (int i = 0; i < n_seed; ++i) {
-        const double v = seed_val[i], k = __builtin_rint(v * 1.0e6);
+    if (n < 0 || n > std::max(N - 1, 0)) { pc_set_error("%s: %d seed edges for %d genomes (a forest holds at most N - 1)", run.who, n, N); return PC_ERR_ARG; }
+    if (n > 0 && !(src && tgt && val)) { pc_set_error("%s: a seed array is NULL", run.who); return PC_ERR_ARG; }
+    keys.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const double v = val[i], k = __builtin_rint(v * 1.0e6);
         const bool millionth = k >= 0.0 && k <= 1.0e6 && k / 1000000.0 == v;
         const int micro = millionth ? (run.as_distance ? (int)k : PC_TREE_MICRO_MAX - (int)k) : -1;
-        keys[i] = seed_tgt[i] < N ? pc_tree_key(micro, seed_src[i], seed_tgt[i]) : PC_TREE_NONE;
+        keys[i] = tgt[i] < N ? pc_tree_key(micro, src[i], tgt[i]) : PC_TREE_NONE;
         if (keys[i] == PC_TREE_NONE) {
             pc_set_error("%s: seed edge %d (%d, %d, %.17g) is no key: source < target < %d and a value that is a millionth in [0, 1]", run.who, i,
-                         seed_src[i], seed_tgt[i], v, N);
+                         src[i], tgt[i], v, N);
             return PC_ERR_ARG;
         }
     }
-    rc = pc_rows_slab_fill<PcTreeFill>(c, run, rows, n_rows, [&]() -> int {
-        if (n_seed == 0) return PC_OK;
-        // the stored tree as the resident forest in place of the empty one, through the pinned key image (end() rewrites it after the stream has drained)
-        unsigned long long* const h = c->h_tree_keys.as<unsigned long long>();
-        memcpy(h, keys.data(), (size_t)n_seed * 8);
-        h[N - 1] = (unsigned long long)n_seed; h[N] = 0ull; h[N + 1] = 0ull;
-        PC_HIP(hipMemcpyAsync(tree_list(c, 0), h, tree_list_words(c) * 8, hipMemcpyHostToDevice, c->stream));
-        if (n_rows > 0) return PC_OK;
-        // no query row: one pass over the list alone leaves the tree of the seed edges (a seed that is no forest comes out short, and end() says so)
-        return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, nullptr, 0, nullptr, nullptr, 0, st); });
-    });
-    if (rc != PC_OK) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
     return PC_OK;
+}
+// the stored tree as the resident forest in place of the empty one, through the pinned key image (end() rewrites it after the stream has drained)
+int PcTreeSeed::install(pc_ctx* c, PcSlabRun& run) const {
+    if (keys.empty()) return PC_OK;
+    const int N = c->dev.N;
+    unsigned long long* const h = c->h_tree_keys.as<unsigned long long>();
+    memcpy(h, keys.data(), keys.size() * 8);
+    h[N - 1] = (unsigned long long)keys.size(); h[N] = 0ull; h[N + 1] = 0ull;
+    PC_HIP(hipMemcpyAsync(tree_list(c, 0), h, tree_list_words(c) * 8, hipMemcpyHostToDevice, c->stream));
+    if (run.n_query > 0) return PC_OK;
+    // no query row: one pass over the list alone leaves the tree of the seed edges (a seed that is no forest comes out short, and end() says so)
+    return slab_pass(c, run, c->last_tree_ms, [&](hipStream_t st) { return tree_pass(c, run, nullptr, 0, nullptr, nullptr, 0, st); });
 }
 
 // The stored lists are seed_nbr / seed_val [N][k_seed] in the uploaded collection's numbering, rows of query genomes ignored: the best
 // min(K, N_old - 1) old neighbours of every old genome, N_old = N - n_rows.  They replace the sentinel in the resident lists; the query
 // rows' pairs are merged into them by the one total order, so an old genome's list is the best kk of all its N - 1 candidates (every old
 // candidate outside the stored list is worse than every entry in it), and a query genome's list is built from its row alone.
-extern "C" int pc_fill_rows_nearest(pc_ctx* c, int metric, int as_distance, int k, const int32_t* rows, int n_rows, const int32_t* seed_nbr,
-                                    const double* seed_val, int32_t k_seed, int64_t slab_bytes, const int32_t** nbr, const double** val, int32_t* k_out,
-                                    int32_t* n_slabs, pc_stats* stats) {
-    if (nbr) *nbr = nullptr;
-    if (val) *val = nullptr;
-    if (k_out) *k_out = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_fill_rows_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
-    int rc = PC_OK;
-    if ((rc = pc_slab_check(c, run, PcNearestFill::what)) || (rc = rows_arg_check(c, run.who, rows, n_rows))) return rc;
+int PcNearestSeed::pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows) {
     const int N = c->dev.N, kk = run.kk, n_old = N - n_rows;
     const int need = std::max(std::min(kk, n_old - 1), 0);                  // entries a stored list must hold; more (up to kk) are taken, the rest cut
     if (k_seed < need) {
         pc_set_error("%s: k_seed %d is below min(k, N_old - 1) = %d (%d old genomes): the stored lists cannot decide %d neighbours", run.who, (int)k_seed, need, n_old, kk);
         return PC_ERR_ARG;
     }
-    if (n_old > 1 && !(seed_nbr && seed_val)) { pc_set_error("%s: a seed array is NULL with %d old genomes", run.who, n_old); return PC_ERR_ARG; }
-    const int ks = std::min<int>(std::min<int>(k_seed, kk), std::max(n_old - 1, 0));
-    // packed before begin: the caller may hand back the arrays an earlier call lent out
-    std::vector<unsigned long long> keys; std::vector<int32_t> idx;
-    if (ks > 0) {
-        std::vector<uint8_t> is_query((size_t)N, 0);
-        for (int i = 0; i < n_rows; ++i) is_query[rows[i]] = 1;
-        keys.resize((size_t)N * kk); idx.resize((size_t)N * kk);
-        int bad_g = -1, bad_j = -1;
-        const int why = pc_nn_seed_pack(seed_nbr, seed_val, k_seed, ks, N, kk, is_query.data(), run.as_distance, keys.data(), idx.data(), &bad_g, &bad_j);
-        if (why) {
-            pc_set_error("%s: seed entry [%d][%d] = (%d, %.17g) %s", run.who, bad_g, bad_j, seed_nbr[(size_t)bad_g * k_seed + bad_j], seed_val[(size_t)bad_g * k_seed + bad_j],
-                         why == 1 ? "is no other old genome (out of range, a query genome, or the genome itself)"
-                                  : "does not come after the entry before it: a stored list ascends in (value, better first; then index)");
-            return PC_ERR_ARG;
-        }
+    if (n_old > 1 && !(nbr && val)) { pc_set_error("%s: a seed array is NULL with %d old genomes", run.who, n_old); return PC_ERR_ARG; }
+    ks = std::min<int>(std::min<int>(k_seed, kk), std::max(n_old - 1, 0));
+    if (ks == 0) return PC_OK;
+    std::vector<uint8_t> is_query((size_t)N, 0);
+    for (int i = 0; i < n_rows; ++i) is_query[rows[i]] = 1;
+    keys.resize((size_t)N * kk); idx.resize((size_t)N * kk);
+    int bad_g = -1, bad_j = -1;
+    const int why = pc_nn_seed_pack(nbr, val, k_seed, ks, N, kk, is_query.data(), run.as_distance, keys.data(), idx.data(), &bad_g, &bad_j);
+    if (why) {
+        pc_set_error("%s: seed entry [%d][%d] = (%d, %.17g) %s", run.who, bad_g, bad_j, nbr[(size_t)bad_g * k_seed + bad_j], val[(size_t)bad_g * k_seed + bad_j],
+                     why == 1 ? "is no other old genome (out of range, a query genome, or the genome itself)"
+                              : "does not come after the entry before it: a stored list ascends in (value, better first; then index)");
+        return PC_ERR_ARG;
     }
-    rc = pc_rows_slab_fill<PcNearestFill>(c, run, rows, n_rows, [&]() -> int {
-        if (ks == 0) return PC_OK;
-        // the stored lists in place of the sentinel, through the pinned result image (end() rewrites it only after the stream has drained)
-        const size_t n_ent = nn_entries(c, run);
-        memcpy(c->h_nn.p, keys.data(), n_ent * 8);
-        memcpy((char*)c->h_nn.p + n_ent * 8, idx.data(), n_ent * 4);
-        PC_HIP(hipMemcpyAsync(c->b_nn_key.p, c->h_nn.p, n_ent * 8, hipMemcpyHostToDevice, c->stream));
-        PC_HIP(hipMemcpyAsync(nn_nbr(c, run), (const char*)c->h_nn.p + n_ent * 8, n_ent * 4, hipMemcpyHostToDevice, c->stream));
-        return PC_OK;
-    });
-    if (rc != PC_OK) return rc;
-    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
-    if (stats) *stats = run.sum;
     return PC_OK;
+}
+// the stored lists in place of the sentinel, through the pinned result image (end() rewrites it only after the stream has drained)
+int PcNearestSeed::install(pc_ctx* c, PcSlabRun& run) const {
+    if (ks == 0) return PC_OK;
+    const size_t n_ent = nn_entries(c, run);
+    memcpy(c->h_nn.p, keys.data(), n_ent * 8);
+    memcpy((char*)c->h_nn.p + n_ent * 8, idx.data(), n_ent * 4);
+    PC_HIP(hipMemcpyAsync(c->b_nn_key.p, c->h_nn.p, n_ent * 8, hipMemcpyHostToDevice, c->stream));
+    PC_HIP(hipMemcpyAsync(nn_nbr(c, run), (const char*)c->h_nn.p + n_ent * 8, n_ent * 4, hipMemcpyHostToDevice, c->stream));
+    return PC_OK;
+}
+
+extern "C" int pc_fill_rows_edges(pc_ctx* c, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
+                                  const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcEdgesFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return pc_rows_slab_fill<PcEdgesFill>(c, run, rows, n_rows, {}); });
+}
+
+extern "C" int pc_fill_rows_components(pc_ctx* c, int metric, int as_distance, double threshold, int strict, const int32_t* rows, int n_rows,
+                                       const int32_t* seed_labels, int64_t slab_bytes, const int32_t** labels, int32_t* n_components, int64_t* n_edges,
+                                       int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict; run.threshold = threshold;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcComponentsFill>(run, {labels, n_components, n_edges, n_slabs}, stats,
+                                          [&] { return pc_rows_slab_fill<PcComponentsFill>(c, run, rows, n_rows, {seed_labels}); });
+}
+
+extern "C" int pc_fill_rows_tree(pc_ctx* c, int metric, int as_distance, const int32_t* rows, int n_rows, const int32_t* seed_src, const int32_t* seed_tgt,
+                                 const double* seed_val, int32_t n_seed, int64_t slab_bytes, const int32_t** src, const int32_t** tgt, const double** val,
+                                 int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_tree"; run.metric = metric; run.as_distance = as_distance; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcTreeFill>(run, {src, tgt, val, n_edges, n_slabs}, stats,
+                                    [&] { return pc_rows_slab_fill<PcTreeFill>(c, run, rows, n_rows, {seed_src, seed_tgt, seed_val, n_seed}); });
+}
+
+extern "C" int pc_fill_rows_nearest(pc_ctx* c, int metric, int as_distance, int k, const int32_t* rows, int n_rows, const int32_t* seed_nbr,
+                                    const double* seed_val, int32_t k_seed, int64_t slab_bytes, const int32_t** nbr, const double** val, int32_t* k_out,
+                                    int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcNearestFill>(run, {nbr, val, k_out, n_slabs}, stats,
+                                       [&] { return pc_rows_slab_fill<PcNearestFill>(c, run, rows, n_rows, {seed_nbr, seed_val, k_seed}); });
 }
 
 // elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by

@@ -245,12 +245,19 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 }
 
 // A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree, and pc_multi_fill_* over several devices) is ONE description of the
-// fill -- a struct of static functions, declared here and defined next to the launchers of its kernels in pc_fill_slabs.hip -- handed as
-// a template argument to the drivers:
+// fill -- a struct of static functions, declared here and defined in pc_fill_slabs.hip (the launchers of its kernels live in pc_edges.hip,
+// pc_components.hip, pc_nearest.hip and pc_tree.hip) -- handed as a template argument to the drivers:
 //   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
 //   pc_slab_stretch<Fill>   the walk over the targets [ta, tb): the slab cut, each slab filled and handed to Fill::slab
 //   multi_slab_fill<Fill>   (pc_multi.hip) begin -> walk(its stretch) -> ship on every device, then merge -> end on the root
+//   pc_rows_slab_fill<Fill> (pc_fill_slabs.hip) a rows form: check -> rows -> Seed::pack -> begin -> Seed::install -> walk the query rows -> end
+// and every extern "C" entry point is its signature, the fields of the run that are its own, and pc_slab_call<Fill> around one of them.
 // What a description says:
+//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut), which can be
+//           cleared, say whether all are there, and take their values from a finished run
+//   Seed    what a stored result is to the fill (the rows forms): the caller's seed arguments; pack() checks them and packs them into host
+//           memory the call owns, BEFORE begin (the caller may hand back arrays an earlier call lent out, which begin rewrites);
+//           install() puts the packed seed in place of the initial state on the device, after begin (N > 1 only)
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
 //   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device.  dom says which pairs
@@ -285,9 +292,54 @@ struct PcSlabRun {
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
 };
-#define PC_SLAB_FILL(Name, Dom, tag, text)                                                                                              \
+// The output shapes and the seeds are hidden, and pc_slab_call is static: however their members are inlined, the library's list of
+// dynamic symbols stays what it was before they had names.
+#pragma GCC visibility push(hidden)
+// The three output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
+template <class Count> struct PcEdgeOut {
+    const int32_t **src, **tgt; const double** val; Count* n_edges; int32_t* n_slabs;
+    bool all() const { return src && tgt && val && n_edges && n_slabs; }
+    void clear() const { if (src) *src = nullptr; if (tgt) *tgt = nullptr; if (val) *val = nullptr; if (n_edges) *n_edges = 0; if (n_slabs) *n_slabs = 0; }
+    void take(const PcSlabRun& run) const { *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (Count)run.n_edges; *n_slabs = run.n_slabs; }
+};
+struct PcLabelOut {
+    const int32_t** labels; int32_t* n_components; int64_t* n_edges; int32_t* n_slabs;
+    bool all() const { return labels && n_components && n_edges && n_slabs; }
+    void clear() const { if (labels) *labels = nullptr; if (n_components) *n_components = 0; if (n_edges) *n_edges = 0; if (n_slabs) *n_slabs = 0; }
+    void take(const PcSlabRun& run) const { *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs; }
+};
+struct PcListOut {
+    const int32_t** nbr; const double** val; int32_t* k; int32_t* n_slabs;
+    bool all() const { return nbr && val && k && n_slabs; }
+    void clear() const { if (nbr) *nbr = nullptr; if (val) *val = nullptr; if (k) *k = 0; if (n_slabs) *n_slabs = 0; }
+    void take(const PcSlabRun& run) const { *nbr = run.nbr; *val = run.val; *k = run.kk; *n_slabs = run.n_slabs; }
+};
+// The seeds: the caller's arguments first (an entry point brace-initialises them), then what pack() made of them.
+struct PcNoSeed {                           // edges: a stored list needs nothing on the device, the caller merges the two lists
+    int pack(const pc_ctx*, const PcSlabRun&, const int32_t*, int) { return PC_OK; }
+    int install(pc_ctx*, PcSlabRun&) const { return PC_OK; }
+};
+struct PcLabelSeed {                        // components: the stored labelling, int32[N] or NULL, as the initial parent[]
+    const int32_t* labels; std::vector<int32_t> packed;
+    int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
+    int install(pc_ctx* c, PcSlabRun& run) const;
+};
+struct PcTreeSeed {                         // tree: the stored tree's n edges, as keys, the resident forest
+    const int32_t *src, *tgt; const double* val; int32_t n; std::vector<unsigned long long> keys;
+    int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
+    int install(pc_ctx* c, PcSlabRun& run) const;
+};
+struct PcNearestSeed {                      // nearest: the stored lists [N][k_seed], as key[N][kk] / idx[N][kk] (none: ks == 0), the resident lists
+    const int32_t* nbr; const double* val; int32_t k_seed; int ks = 0; std::vector<unsigned long long> keys; std::vector<int32_t> idx;
+    int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
+    int install(pc_ctx* c, PcSlabRun& run) const;
+};
+#pragma GCC visibility pop
+#define PC_SLAB_FILL(Name, Dom, tag, text, KIND, OUT, SEED)                                                                             \
     struct Name {                                                                                                                       \
         static constexpr const char *what = text, *who = "pc_fill_" tag, *range = "pc:fill_" tag, *multi_range = "pc:multi_fill_" tag; \
+        static constexpr PcSlabKind kind = KIND;                                                                                        \
+        using Out = OUT; using Seed = SEED;                                                                                             \
         static int begin(pc_ctx* c, PcSlabRun& run);                                                                                    \
         static int slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const Dom& dom);                                     \
         static int end(pc_ctx* c, PcSlabRun& run);                                                                                      \
@@ -295,11 +347,23 @@ struct PcSlabRun {
         static int ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int n_foreign);                                 \
         static int merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float* ms_exchange); \
     }
-PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill");
-PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill");
-PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill");
-PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill");
+PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill", PC_SLAB_EDGES, PcEdgeOut<int64_t>, PcNoSeed);
+PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill", PC_SLAB_COMPONENTS, PcLabelOut, PcLabelSeed);
+PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill", PC_SLAB_NEAREST, PcListOut, PcNearestSeed);
+PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill", PC_SLAB_TREE, PcEdgeOut<int32_t>, PcTreeSeed);
 #undef PC_SLAB_FILL
+// What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into
+// the run (whose call fields the entry point has set), drive(), and on PC_OK the results into the outputs and the run's own stats
+// into stats[0] (several devices: the root's; multi_slab_fill writes the others').
+template <class Fill, class Drive> static int pc_slab_call(PcSlabRun& run, const typename Fill::Out& out, pc_stats* stats, Drive drive) {
+    out.clear();
+    run.kind = Fill::kind; run.outputs = out.all(); run.timed = stats != nullptr;
+    const int rc = drive();
+    if (rc != PC_OK) return rc;
+    out.take(run);
+    if (stats) stats[0] = run.sum;
+    return PC_OK;
+}
 int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what);
 template <class Fill> int pc_slab_fill(pc_ctx* c, PcSlabRun& run);
 template <class Fill> int pc_slab_stretch(pc_ctx* c, PcSlabRun& run, int ta, int tb);

@@ -249,7 +249,8 @@ int slab_prepare(pc_multi* m, PcSlabRun& run, const char* what, bool& single) {
     return pc_stretch_plan(cost.data(), N, world, m->stretches.data());
 }
 
-// The call `run` over the devices of m; on PC_OK the run holds the results (the root's) and stats[r], when asked for, device r's fills.
+// The call `run` over the devices of m; on PC_OK the run holds the results and the stats of the root (pc_slab_call delivers them, the
+// stats as stats[0]) and stats[r], when asked for, the fills of device r > 0.
 template <class Fill> int multi_slab_fill(pc_multi* m, PcSlabRun& run, pc_stats* stats) {
     int rc = PC_OK;
     bool single = false;
@@ -259,9 +260,7 @@ template <class Fill> int multi_slab_fill(pc_multi* m, PcSlabRun& run, pc_stats*
     if (single) {                                                           // the single-context call, under its own name
         if (stats) for (int r = 1; r < world; ++r) memset(&stats[r], 0, sizeof(pc_stats));
         run.who = Fill::who;
-        if ((rc = pc_slab_fill<Fill>(root, run))) return rc;
-        if (stats) stats[0] = run.sum;
-        return PC_OK;
+        return pc_slab_fill<Fill>(root, run);
     }
     PcRange range(Fill::multi_range);
     // a slice of the root's staging buffer for every device that ships: the non-root devices with a stretch, in rank order
@@ -306,67 +305,34 @@ template <class Fill> int multi_slab_fill(pc_multi* m, PcSlabRun& run, pc_stats*
     }
     run = runs[0];
     run.n_slabs = (int32_t)slabs;
-    if (stats) for (int r = 0; r < world; ++r) stats[r] = runs[r].sum;
+    if (stats) for (int r = 1; r < world; ++r) stats[r] = runs[r].sum;
     return PC_OK;
 }
 }  // namespace
 
 extern "C" int pc_multi_fill_edges(pc_multi* m, int metric, int as_distance, double threshold, int64_t slab_bytes,
                                    const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_EDGES; run.who = "pc_multi_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    const int rc = multi_slab_fill<PcEdgesFill>(m, run, stats);
-    if (rc != PC_OK) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_multi_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcEdgesFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return multi_slab_fill<PcEdgesFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_fill_components(pc_multi* m, int metric, int as_distance, double threshold, int strict, int64_t slab_bytes,
                                         const int32_t** labels, int32_t* n_components, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (labels) *labels = nullptr;
-    if (n_components) *n_components = 0;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_COMPONENTS; run.who = "pc_multi_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict;
-    run.threshold = threshold; run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = labels && n_components && n_edges && n_slabs;
-    const int rc = multi_slab_fill<PcComponentsFill>(m, run, stats);
-    if (rc != PC_OK) return rc;
-    *labels = run.labels; *n_components = run.n_components; *n_edges = run.n_edges; *n_slabs = run.n_slabs;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_multi_fill_components"; run.metric = metric; run.as_distance = as_distance; run.strict = strict; run.threshold = threshold;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcComponentsFill>(run, {labels, n_components, n_edges, n_slabs}, stats, [&] { return multi_slab_fill<PcComponentsFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, int k, int64_t slab_bytes,
                                      const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats) {
-    if (nbr) *nbr = nullptr;
-    if (val) *val = nullptr;
-    if (k_out) *k_out = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_NEAREST; run.who = "pc_multi_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = nbr && val && k_out && n_slabs;
-    const int rc = multi_slab_fill<PcNearestFill>(m, run, stats);
-    if (rc != PC_OK) return rc;
-    *nbr = run.nbr; *val = run.val; *k_out = run.kk; *n_slabs = run.n_slabs;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_multi_fill_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcNearestFill>(run, {nbr, val, k_out, n_slabs}, stats, [&] { return multi_slab_fill<PcNearestFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int64_t slab_bytes,
                                   const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
-    if (src) *src = nullptr;
-    if (tgt) *tgt = nullptr;
-    if (val) *val = nullptr;
-    if (n_edges) *n_edges = 0;
-    if (n_slabs) *n_slabs = 0;
-    PcSlabRun run; run.kind = PC_SLAB_TREE; run.who = "pc_multi_fill_tree"; run.metric = metric; run.as_distance = as_distance;
-    run.slab_bytes = slab_bytes; run.timed = stats != nullptr; run.outputs = src && tgt && val && n_edges && n_slabs;
-    const int rc = multi_slab_fill<PcTreeFill>(m, run, stats);
-    if (rc != PC_OK) return rc;
-    *src = run.src; *tgt = run.tgt; *val = run.val; *n_edges = (int32_t)run.n_edges; *n_slabs = run.n_slabs;
-    return PC_OK;
+    PcSlabRun run; run.who = "pc_multi_fill_tree"; run.metric = metric; run.as_distance = as_distance; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcTreeFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return multi_slab_fill<PcTreeFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds) {

@@ -304,10 +304,49 @@ class _SlabFills:
     (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
     dict of such a fill)."""
 
-    def _slab_fill(self, kind, metric, *args):
+    def _slab_call(self, symbol, metric, *args):
         stats = self._before_slab_fill(metric)
-        self._check(getattr(self._lib, self._SLAB_CALL + kind)(self._h, METRIC_IDS[metric], *args, stats))
+        self._check(getattr(self._lib, symbol)(self._h, METRIC_IDS[metric], *args, stats))
         return stats
+
+    # One decoder per result shape, for the whole form and the rows form alike: the call ``prefix + kind`` with ``args`` (what the call
+    # takes between the metric and its output cells), the output cells as arrays or loans, and with ``want_stats`` the stats dict.
+    def _fill_edge_arrays(self, kind, prefix, metric, args, want_stats, borrow):
+        """``(src, tgt, val)`` of an edge list (``"edges"``: a 64-bit count; ``"tree"``: a 32-bit one, and the round counts)."""
+        ps, pt, pv = _i32p(), _i32p(), _f64p()
+        n, nsl = (ctypes.c_int32 if kind == "tree" else ctypes.c_int64)(0), ctypes.c_int32(0)
+        stats = self._slab_call(prefix + kind, metric, *args, ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
+               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
+        if not want_stats:
+            return tuple(out)
+        own = self._tree_rounds() if kind == "tree" else {}
+        return (*out, self._slab_stats(kind, stats, n_edges=int(n.value), n_slabs=int(nsl.value), **own))
+
+    def _fill_labels(self, prefix, metric, args, want_stats, borrow):
+        """``labels`` of a components fill."""
+        pl = _i32p()
+        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._slab_call(prefix + "components", metric, *args, ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl))
+        n = self.n_genomes
+        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
+        if not want_stats:
+            return labels
+        return labels, self._slab_stats("components", stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+
+    def _fill_lists(self, prefix, metric, args, want_stats, borrow):
+        """``(nbr, val)`` of a nearest-neighbours fill."""
+        pn, pv = _i32p(), _f64p()
+        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
+        stats = self._slab_call(prefix + "nearest", metric, *args, ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl))
+        n = self.n_genomes
+        if n and kk.value and pn and pv:
+            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
+        else:
+            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
+        if not want_stats:
+            return nbr, val
+        return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
 
     def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
@@ -320,15 +359,7 @@ class _SlabFills:
         contiguous stretch of targets, and the lists are laid end to end in the root's page-locked memory.  The stats are summed
         over the devices and carry the route's own entries (``per_device``, ``stretches``, ``ms_exchange``, ``ms_merge``,
         ``n_devices``, ``peer_access``) in place of the two times."""
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
-        stats = self._slab_fill("edges", metric, int(bool(as_distance)), float(threshold), int(slab_bytes),
-                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        return (*out, self._slab_stats("edges", stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
+        return self._fill_edge_arrays("edges", self._SLAB_CALL, metric, (int(bool(as_distance)), float(threshold), int(slab_bytes)), want_stats, borrow)
 
     def fill_components(self, metric, threshold, as_distance=True, strict=True, slab_bytes=0, want_stats=False, borrow=False):
         """The connected components of the graph whose edges are the pairs that pass ``threshold`` -- ``d < threshold`` for a
@@ -342,15 +373,7 @@ class _SlabFills:
         On a :class:`MultiContext`: the same canonical ``labels`` -- every device builds the forest of its stretch of targets, the
         root unites them (``k_cc_merge``) and labels; ``n_edges`` counts over all devices, and the stats carry the route's own
         entries (as for :meth:`fill_edges`) in place of the two times."""
-        pl = _i32p()
-        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        stats = self._slab_fill("components", metric, int(bool(as_distance)), float(threshold), int(bool(strict)), int(slab_bytes),
-                                ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl))
-        n = self.n_genomes
-        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
-        if not want_stats:
-            return labels
-        return labels, self._slab_stats("components", stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+        return self._fill_labels(self._SLAB_CALL, metric, (int(bool(as_distance)), float(threshold), int(bool(strict)), int(slab_bytes)), want_stats, borrow)
 
     def fill_nearest(self, metric, k, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """Each genome's ``kk = min(k, N - 1)`` nearest neighbours as ``(nbr, val)``: int32[N, kk] genome indices and float64[N, kk]
@@ -364,18 +387,7 @@ class _SlabFills:
         On a :class:`MultiContext`: the same ``(nbr, val)`` -- the k smallest of one total order, so the lists the devices build
         over their stretches of targets merge by that order on the root (``k_nn_merge``); the stats carry the route's own entries
         (as for :meth:`fill_edges`) in place of the two times."""
-        pn, pv = _i32p(), _f64p()
-        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        stats = self._slab_fill("nearest", metric, int(bool(as_distance)), int(k), int(slab_bytes),
-                                ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl))
-        n = self.n_genomes
-        if n and kk.value and pn and pv:
-            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
-        else:
-            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
-        if not want_stats:
-            return nbr, val
-        return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
+        return self._fill_lists(self._SLAB_CALL, metric, (int(bool(as_distance)), int(k), int(slab_bytes)), want_stats, borrow)
 
     def fill_tree(self, metric, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The single-linkage dendrogram as the ``N - 1`` edges ``(src, tgt, val)`` -- int32, int32, float64, ``src < tgt`` -- of the
@@ -392,15 +404,7 @@ class _SlabFills:
         On a :class:`MultiContext`: the same arrays -- every device builds the forest of its stretch of targets, the root merges
         the forests by rounds over the lists alone; the stats carry the route's own entries (as for :meth:`fill_edges`) in place of
         the two times."""
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        stats = self._slab_fill("tree", metric, int(bool(as_distance)), int(slab_bytes),
-                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        return (*out, self._slab_stats("tree", stats, n_edges=int(n.value), n_slabs=int(nsl.value), **self._tree_rounds()))
+        return self._fill_edge_arrays("tree", self._SLAB_CALL, metric, (int(bool(as_distance)), int(slab_bytes)), want_stats, borrow)
 
 
 class Context(_SlabFills):
@@ -687,15 +691,17 @@ class Context(_SlabFills):
         per = max(1, int(slab_bytes) // 8 // max(int(n), 1))
         return (int(n_rows) + per - 1) // per if int(n) > 1 else 0
 
-    def _rows_fill(self, kind, metric, *args):
-        stats = self._before_slab_fill(metric)
-        self._check(getattr(self._lib, "pc_fill_rows_" + kind)(self._h, METRIC_IDS[metric], *args, stats))
-        return stats
+    _ROWS_CALL = "pc_fill_rows_"
 
     @staticmethod
     def _rows_arg(rows):
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
         return rows, _ptr(rows if rows.size else np.zeros(1, dtype=np.int32), _i32p), int(rows.shape[0])
+
+    @staticmethod
+    def _seed_ptr(arr, typ):
+        """A seed array for the library: NULL for none and for an empty one."""
+        return _ptr(arr, typ) if arr is not None and arr.size else None
 
     def fill_rows_edges(self, metric, threshold, rows, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The pairs that touch a query genome of ``rows`` (distinct indices, strictly ascending: the new genomes of a grown
@@ -705,15 +711,8 @@ class Context(_SlabFills):
         the rows into slabs of ``max(1, slab_bytes // 8 // N)`` (0 = automatic).  Copies, or loans with ``borrow``; ``want_stats`` as
         :meth:`fill_edges`."""
         rows, prow, n_rows = self._rows_arg(rows)
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int64(0), ctypes.c_int32(0)
-        stats = self._rows_fill("edges", metric, int(bool(as_distance)), float(threshold), prow, n_rows, int(slab_bytes),
-                                ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        return (*out, self._slab_stats("edges", stats, n_edges=int(n.value), n_slabs=int(nsl.value)))
+        return self._fill_edge_arrays("edges", self._ROWS_CALL, metric, (int(bool(as_distance)), float(threshold), prow, n_rows, int(slab_bytes)),
+                                      want_stats, borrow)
 
     def fill_rows_components(self, metric, threshold, rows, seed_labels=None, as_distance=True, strict=True, slab_bytes=0, want_stats=False,
                              borrow=False):
@@ -727,16 +726,8 @@ class Context(_SlabFills):
             seed = np.ascontiguousarray(seed_labels, dtype=np.int32).reshape(-1)
             if seed.shape[0] != self.n_genomes:
                 raise ValueError(f"fill_rows_components: seed_labels holds {seed.shape[0]} entries for {self.n_genomes} genomes")
-        pl = _i32p()
-        nc, ne, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        stats = self._rows_fill("components", metric, int(bool(as_distance)), float(threshold), int(bool(strict)), prow, n_rows,
-                                _ptr(seed, _i32p) if seed is not None and seed.size else None, int(slab_bytes),
-                                ctypes.byref(pl), ctypes.byref(nc), ctypes.byref(ne), ctypes.byref(nsl))
-        n = self.n_genomes
-        labels = self._lend(pl, (n,), borrow) if n and pl else np.empty(0, dtype=np.int32)
-        if not want_stats:
-            return labels
-        return labels, self._slab_stats("components", stats, n_components=int(nc.value), n_edges=int(ne.value), n_slabs=int(nsl.value))
+        return self._fill_labels(self._ROWS_CALL, metric, (int(bool(as_distance)), float(threshold), int(bool(strict)), prow, n_rows,
+                                                           self._seed_ptr(seed, _i32p), int(slab_bytes)), want_stats, borrow)
 
     def fill_rows_tree(self, metric, rows, seed=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """:meth:`fill_tree`'s tree of the whole collection from the stored tree of the other genomes: ``seed = (src, tgt, val)``, its
@@ -751,17 +742,9 @@ class Context(_SlabFills):
         s_val = np.ascontiguousarray(seed[2], dtype=np.float64).reshape(-1)
         if not s_src.shape == s_tgt.shape == s_val.shape:
             raise ValueError("fill_rows_tree: the seed's source, target and value arrays differ in length")
-        n_seed = int(s_src.shape[0])
-        ps, pt, pv = _i32p(), _i32p(), _f64p()
-        n, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        stats = self._rows_fill("tree", metric, int(bool(as_distance)), prow, n_rows,
-                                _ptr(s_src, _i32p) if n_seed else None, _ptr(s_tgt, _i32p) if n_seed else None, _ptr(s_val, _f64p) if n_seed else None,
-                                n_seed, int(slab_bytes), ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
-        out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
-               for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
-        if not want_stats:
-            return tuple(out)
-        return (*out, self._slab_stats("tree", stats, n_edges=int(n.value), n_slabs=int(nsl.value), **self._tree_rounds()))
+        args = (int(bool(as_distance)), prow, n_rows, self._seed_ptr(s_src, _i32p), self._seed_ptr(s_tgt, _i32p), self._seed_ptr(s_val, _f64p),
+                int(s_src.shape[0]), int(slab_bytes))
+        return self._fill_edge_arrays("tree", self._ROWS_CALL, metric, args, want_stats, borrow)
 
     @staticmethod
     def nearest_rows_tile():
@@ -788,18 +771,8 @@ class Context(_SlabFills):
             if s_nbr.ndim != 2 or s_nbr.shape != s_val.shape or s_nbr.shape[0] != n:
                 raise ValueError(f"fill_rows_nearest: the seed must be two ({n}, k_seed) arrays, not {s_nbr.shape} and {s_val.shape}")
             k_seed = int(s_nbr.shape[1])
-        pn, pv = _i32p(), _f64p()
-        kk, nsl = ctypes.c_int32(0), ctypes.c_int32(0)
-        stats = self._rows_fill("nearest", metric, int(bool(as_distance)), int(k), prow, n_rows,
-                                _ptr(s_nbr, _i32p) if k_seed and n else None, _ptr(s_val, _f64p) if k_seed and n else None, k_seed, int(slab_bytes),
-                                ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(kk), ctypes.byref(nsl))
-        if n and kk.value and pn and pv:
-            nbr, val = self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow)
-        else:
-            nbr, val = np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64)
-        if not want_stats:
-            return nbr, val
-        return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
+        args = (int(bool(as_distance)), int(k), prow, n_rows, self._seed_ptr(s_nbr, _i32p), self._seed_ptr(s_val, _f64p), k_seed, int(slab_bytes))
+        return self._fill_lists(self._ROWS_CALL, metric, args, want_stats, borrow)
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()
@@ -1120,7 +1093,7 @@ class MultiContext(_SlabFills):
         return bounds
 
     def _before_slab_fill(self, metric):
-        """What the three calls share ahead of the library call: the residues on demand, earlier loans ended, a stats array."""
+        """What the four calls share ahead of the library call: the residues on demand, earlier loans ended, a stats array."""
         if self._packed is not None and metric in NEEDS_RESIDUES and not self._residues:     # (before an upload the library refuses the call itself)
             s = self._struct(self._packed)
             self._check(self._lib.pc_multi_upload_residues(self._h, ctypes.byref(s)))

@@ -841,8 +841,8 @@ class SparseEdges:
 
 
 def _slab_fill_context():
-    """(context, devices used) of an edge-list, components or nearest-neighbours fill: the ``MultiContext`` over the devices
-    ``in_process_devices()`` names when there are several -- the three fills spread over them, a stretch of targets per device --
+    """(context, devices used) of an edge-list, components, nearest-neighbours or tree fill: the ``MultiContext`` over the devices
+    ``in_process_devices()`` names when there are several -- the four fills spread over them, a stretch of targets per device --
     else the one-GPU context (of the one device named, or the default device)."""
     devices = in_process_devices()
     if devices and len(devices) > 1:
@@ -857,14 +857,12 @@ def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
     has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  With ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` naming more than one
     device the fill is spread over them from this process (``MultiContext.fill_edges``: a contiguous stretch of targets per device,
     the same edges); under a launcher (``WORLD_SIZE`` > 1) it raises."""
-    ctx, metric, names, record = upload_for_fills(genomes, func, "edges_de_novo", several=True,
-                                                  advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), threshold)")
-    import time
-    t0 = time.perf_counter()
-    src, tgt, val, stats = ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_fill(stats, metric, names, record, t0)
-    logging.debug(f"{len(names)} genomes -> {stats['n_edges']} of {record['genome_pairs']} edges in {stats['n_slabs']} slab(s) on {record['n_gpus']} "
-                  f"device(s): fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    names, (src, tgt, val) = _de_novo_route(genomes, func, "edges_de_novo",
+        lambda ctx, metric: ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: (
+            f"{len(genomes)} genomes -> {stats['n_edges']} of {record['genome_pairs']} edges in {stats['n_slabs']} slab(s) on {record['n_gpus']} "
+            f"device(s): fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)"),
+        advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), threshold)")
     return SparseEdges(names, src, tgt, val, is_distance=as_distance, threshold=threshold)
 
 
@@ -942,14 +940,12 @@ def components_de_novo(genomes, func, threshold, as_distance=True, strict=True, 
     ``METRICS`` callables (no CPU route: ``SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)`` serves another
     callable).  Several devices as ``edges_de_novo`` (``MultiContext.fill_components``: the same labels); under a launcher
     (``WORLD_SIZE`` > 1) it raises."""
-    ctx, metric, names, record = upload_for_fills(genomes, func, "components_de_novo", several=True,
-                                                  advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)")
-    import time
-    t0 = time.perf_counter()
-    labels, stats = ctx.fill_components(metric, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_fill(stats, metric, names, record, t0)
-    logging.debug(f"{len(names)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {record['genome_pairs']} pairs in "
-                  f"{stats['n_slabs']} slab(s) on {record['n_gpus']} device(s): fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+    names, (labels,) = _de_novo_route(genomes, func, "components_de_novo",
+        lambda ctx, metric: ctx.fill_components(metric, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: (
+            f"{len(genomes)} genomes -> {stats['n_components']} components from {stats['n_edges']} of {record['genome_pairs']} pairs in "
+            f"{stats['n_slabs']} slab(s) on {record['n_gpus']} device(s): fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)"),
+        advice="for another callable: SparseEdges.from_dense(matrix_de_novo(...), 2.0).components(threshold)")
     return Components(names, labels)
 
 
@@ -958,7 +954,7 @@ def upload_for_fills(genomes, func, caller, several=False, advice="the dense rou
     six ``METRICS``, a launcher), then ONE pack and ONE upload.  Returns ``(context, metric name, genome names, record)`` -- the
     record holds ``pack_s``, ``upload_s``, ``n_gpus`` and the collection's ``genome_pairs`` for ``LAST_FILL`` -- and the caller runs as
     many fills as it needs.  ``several``: the caller's fill also runs over several devices (``edges_de_novo``, ``components_de_novo``,
-    ``neighbors_de_novo``), so the context is ``_slab_fill_context()``'s; the groups and rows routes leave it off and stay on one GPU.
+    ``neighbors_de_novo``, ``tree_de_novo``), so the context is ``_slab_fill_context()``'s; the groups and rows routes leave it off and stay on one GPU.
     ``advice``: what the refusal of a generic callable tells its reader to use instead.  The caller runs as many fills
     on the context as it needs (``submatrices_de_novo``: a groups fill; ``hierarchical_clustering_de_novo``: a components fill, then
     a groups fill; ``phamclust --no-matrix``: two and three of them)."""
@@ -984,15 +980,25 @@ def upload_for_fills(genomes, func, caller, several=False, advice="the dense rou
     return ctx, metric, [g.name for g in genomes], dict(pack_s=t1 - t0, upload_s=t2 - t1, genome_pairs=packed.n_pairs, n_gpus=n_gpus)
 
 
-def _record_fill(stats, metric, names, record, t0):
-    """``LAST_FILL`` after the one fill of a route behind ``upload_for_fills(..., several=True)``, begun at ``t0``: its stats, the
-    collection and the upload's record.  Returns ``fill_s``."""
+def _fill_done(stats, metric, names, record, t0, log, **own):
+    """After the one fill of a ``*_de_novo`` / ``*_extend`` route, begun at ``t0``: ``LAST_FILL`` -- the fill's stats, the collection, the
+    upload's record and the route's ``own`` entries -- and the route's log line, ``log(stats, record, fill_s)``."""
     import time
     fill_s = time.perf_counter() - t0
     LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(names), genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"], rank=0,
-                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
-    return fill_s
+    LAST_FILL.update(stats, metric=metric, n_genomes=len(names), rank=0, pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s, **own)
+    logging.debug(log(stats, record, fill_s))
+
+
+def _de_novo_route(genomes, func, caller, fill, log, advice="the dense route, matrix_de_novo, serves another callable"):
+    """The frame the four ``*_de_novo`` routes share: ``upload_for_fills`` over the devices at hand (``advice``: its refusal's), the clock,
+    ``fill(ctx, metric)`` -> ``(*arrays, stats)``, ``LAST_FILL`` and the log line (``_fill_done``).  Returns ``(names, arrays)``."""
+    ctx, metric, names, record = upload_for_fills(genomes, func, caller, several=True, advice=advice)
+    import time
+    t0 = time.perf_counter()
+    *arrays, stats = fill(ctx, metric)
+    _fill_done(stats, metric, names, record, t0, log, genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"])
+    return names, arrays
 
 
 def _group_indices(names, index, groups):
@@ -1184,14 +1190,11 @@ def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
     refusal comes before the first GPU call."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NEAREST_MAX_K:
         raise ValueError(f"neighbors_de_novo: k must be an integer in 1..{NEAREST_MAX_K}, not {k!r}")
-    ctx, metric, names, record = upload_for_fills(genomes, func, "neighbors_de_novo", several=True)
-    import time
-    t0 = time.perf_counter()
-    nbr, val, stats = ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_fill(stats, metric, names, record, t0)
-    logging.debug(f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in {stats['n_slabs']} "
-                  f"slab(s) on {record['n_gpus']} device(s): fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection "
-                  f"{stats.get('ms_select', 0.0):.3f} ms)")
+    names, (nbr, val) = _de_novo_route(genomes, func, "neighbors_de_novo",
+        lambda ctx, metric: ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in "
+                                      f"{stats['n_slabs']} slab(s) on {record['n_gpus']} device(s): fill+select+D2H {fill_s:.3f} s (kernels "
+                                      f"{stats['ms_total']:.3f} ms, selection {stats.get('ms_select', 0.0):.3f} ms)")
     return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 
@@ -1357,15 +1360,12 @@ def tree_de_novo(genomes, func, as_distance=True, slab_bytes=0):
     ``SingleLinkageTree.from_dense(matrix_de_novo(...))`` serves another callable).  Several devices as ``edges_de_novo``
     (``MultiContext.fill_tree``: the same tree); under a launcher (``WORLD_SIZE`` > 1) it raises.  Every refusal comes before the
     first GPU call."""
-    ctx, metric, names, record = upload_for_fills(genomes, func, "tree_de_novo", several=True,
-                                                  advice="for another callable: SingleLinkageTree.from_dense(matrix_de_novo(...))")
-    import time
-    t0 = time.perf_counter()
-    src, tgt, val, stats = ctx.fill_tree(metric, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_fill(stats, metric, names, record, t0)
-    logging.debug(f"{len(genomes)} genomes -> {stats['n_edges']} tree edges from {record['genome_pairs']} pairs in {stats['n_slabs']} slab(s) on "
-                  f"{record['n_gpus']} device(s): fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds "
-                  f"{stats.get('ms_rounds', 0.0):.3f} ms)")
+    names, (src, tgt, val) = _de_novo_route(genomes, func, "tree_de_novo",
+        lambda ctx, metric: ctx.fill_tree(metric, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: f"{len(genomes)} genomes -> {stats['n_edges']} tree edges from {record['genome_pairs']} pairs in "
+                                      f"{stats['n_slabs']} slab(s) on {record['n_gpus']} device(s): fill+rounds+D2H {fill_s:.3f} s (kernels "
+                                      f"{stats['ms_total']:.3f} ms, rounds {stats.get('ms_rounds', 0.0):.3f} ms)",
+        advice="for another callable: SingleLinkageTree.from_dense(matrix_de_novo(...))")
     return SingleLinkageTree(names, src, tgt, val, is_distance=as_distance)
 
 
@@ -1391,14 +1391,6 @@ def _extend_plan(stored_nodes, genomes, caller):
     new_idx = [k for k, name in enumerate(names) if name not in stored]
     old_at, _ = _grown_positions(stored_nodes, names, new_idx, caller)
     return names, old_at, new_idx
-
-
-def _extend_upload(genomes, func, caller):
-    """The one pack and upload of an ``*_extend`` call on one GPU (``upload_for_fills``: its refusals -- a callable outside ``METRICS``,
-    a launcher -- come before any GPU call).  Returns (context, metric, record)."""
-    ctx, metric, _, record = upload_for_fills(genomes, func, caller, advice="for another callable: the extended() statement of the stored result "
-                                                                            "takes any rows of values")
-    return ctx, metric, record
 
 
 def _guard_rows(ctx, metric, as_distance, old_at, verify):
@@ -1441,14 +1433,22 @@ def merge_edge_lists(first, second):
     return tuple(out)
 
 
-def _record_extend(stats, metric, names, record, n_rows, t0):
-    """``LAST_FILL`` after an ``*_extend`` call, as ``matrix_extend`` fills it.  Returns ``fill_s``."""
+def _extend_fill(plan, genomes, func, caller, as_distance, verify, guard, fill, log):
+    """What the four ``*_extend`` routes share once some genomes are stored and some are new: the one pack and upload on one GPU
+    (``upload_for_fills``: its refusals -- a callable outside ``METRICS``, a launcher -- come before any GPU call), the clock,
+    ``_guard_rows``, the kind's ``guard(metric, checked, values)``, the rows fill ``fill(ctx, metric)`` -> ``(*arrays, stats)``,
+    ``LAST_FILL`` and the log line (``_fill_done``).  Returns the arrays.  The early returns stay with the routes, in one order: every genome
+    new -> de novo, nothing new -> the stored result re-laid without a GPU call."""
+    names, old_at, new_idx = plan
+    ctx, metric, _, record = upload_for_fills(genomes, func, caller, advice="for another callable: the extended() statement of the stored result "
+                                                                            "takes any rows of values")
     import time
-    fill_s = time.perf_counter() - t0
-    LAST_FILL.clear()
-    LAST_FILL.update(stats, metric=metric, n_genomes=len(names), genome_pairs=int(stats["n_pairs"]), rows=n_rows, n_gpus=1, rank=0,
-                     pack_s=record["pack_s"], upload_s=record["upload_s"], fill_s=fill_s)
-    return fill_s
+    t0 = time.perf_counter()
+    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
+    guard(metric, checked, values)
+    *arrays, stats = fill(ctx, metric)
+    _fill_done(stats, metric, names, record, t0, log, genome_pairs=int(stats["n_pairs"]), rows=len(new_idx), n_gpus=1)
+    return arrays
 
 
 def edges_extend(edges, genomes, func, verify=4, slab_bytes=0):
@@ -1463,30 +1463,31 @@ def edges_extend(edges, genomes, func, verify=4, slab_bytes=0):
     launcher (``WORLD_SIZE`` > 1) raise before any GPU call (``SparseEdges.extended`` serves another callable)."""
     if edges.threshold is None:
         raise ValueError("edges_extend: the stored list carries no threshold, so which new pairs belong to it is undefined")
-    names, old_at, new_idx = _extend_plan(edges.nodes, genomes, "edges_extend")
+    plan = names, old_at, new_idx = _extend_plan(edges.nodes, genomes, "edges_extend")
     as_distance, threshold = edges.is_distance, edges.threshold
     if old_at.shape[0] == 0:
         return edges_de_novo(genomes, func, threshold, as_distance=as_distance, slab_bytes=slab_bytes)
     src, tgt, weight = old_at[edges.source], old_at[edges.target], edges.weight
     if not new_idx:
         return SparseEdges(names, src, tgt, weight, is_distance=as_distance, threshold=threshold)
-    ctx, metric, record = _extend_upload(genomes, func, "edges_extend")
-    import time
-    t0 = time.perf_counter()
-    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
-    _guard_edges(names, metric, checked, values, src, tgt, weight, "edge list")
-    stored = set(zip(src.tolist(), tgt.tolist()))
-    for i, q in enumerate(checked):
-        w = values[i, old_at]
-        for g in old_at[(w <= threshold) if as_distance else (w >= threshold)].tolist():
-            if g != q and (min(q, g), max(q, g)) not in stored:
-                raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
-                                 f"{threshold!r}, and the edge list lacks it: it was not filled with this metric from these genomes in this order")
-    n_src, n_tgt, n_val, stats = ctx.fill_rows_edges(metric, threshold, new_idx, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    src, tgt, weight = merge_edge_lists((src, tgt, weight), (n_src, n_tgt, n_val))
-    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
-    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} new edges in {stats['n_slabs']} slab(s): "
-                  f"guard+fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+
+    def guard(metric, checked, values):
+        _guard_edges(names, metric, checked, values, src, tgt, weight, "edge list")
+        stored = set(zip(src.tolist(), tgt.tolist()))
+        for i, q in enumerate(checked):
+            w = values[i, old_at]
+            for g in old_at[(w <= threshold) if as_distance else (w >= threshold)].tolist():
+                if g != q and (min(q, g), max(q, g)) not in stored:
+                    raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
+                                     f"{threshold!r}, and the edge list lacks it: it was not filled with this metric from these genomes in this order")
+
+    def fill(ctx, metric):
+        n_src, n_tgt, n_val, stats = ctx.fill_rows_edges(metric, threshold, new_idx, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+        return (*merge_edge_lists((src, tgt, weight), (n_src, n_tgt, n_val)), stats)
+
+    src, tgt, weight = _extend_fill(plan, genomes, func, "edges_extend", as_distance, verify, guard, fill,
+        lambda stats, record, fill_s: f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} new edges in "
+                                      f"{stats['n_slabs']} slab(s): guard+fill+compact+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
     return SparseEdges(names, src, tgt, weight, is_distance=as_distance, threshold=threshold)
 
 
@@ -1495,33 +1496,32 @@ def components_extend(components, genomes, func, threshold, strict=True, verify=
     func, threshold, as_distance, strict)`` would return, computing only the pairs that touch a genome ``components`` lacks
     (``Context.fill_rows_components``: the stored labels seed the forest).  Arguments, refusals and routes as ``edges_extend``.  The
     guard: a verified old genome and every old genome it passes the threshold with must share a stored label."""
-    names, old_at, new_idx = _extend_plan(components.nodes, genomes, "components_extend")
+    plan = names, old_at, new_idx = _extend_plan(components.nodes, genomes, "components_extend")
     if old_at.shape[0] == 0:
         return components_de_novo(genomes, func, threshold, as_distance=as_distance, strict=strict, slab_bytes=slab_bytes)
     seed = np.arange(len(names), dtype=np.int32)
     seed[old_at] = old_at[components.labels]
     if not new_idx:
         return Components(names, seed)
-    ctx, metric, record = _extend_upload(genomes, func, "components_extend")
-    import time
-    t0 = time.perf_counter()
-    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
-    for i, q in enumerate(checked):
-        w = values[i, old_at]
-        if as_distance:
-            passing = w < threshold if strict else w <= threshold
-        else:
-            passing = w > threshold if strict else w >= threshold
-        for g in old_at[passing].tolist():
-            if g != q and seed[g] != seed[q]:
-                raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
-                                 f"{threshold!r}, and the stored components keep the two apart: they were not filled with this metric and threshold "
-                                 f"from these genomes")
-    labels, stats = ctx.fill_rows_components(metric, threshold, new_idx, seed_labels=seed, as_distance=as_distance, strict=strict,
-                                             slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
-    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_components']} components in {stats['n_slabs']} "
-                  f"slab(s): guard+fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
+
+    def guard(metric, checked, values):
+        for i, q in enumerate(checked):
+            w = values[i, old_at]
+            if as_distance:
+                passing = w < threshold if strict else w <= threshold
+            else:
+                passing = w > threshold if strict else w >= threshold
+            for g in old_at[passing].tolist():
+                if g != q and seed[g] != seed[q]:
+                    raise ValueError(f"pair ({names[min(q, g)]}, {names[max(q, g)]}): the {metric} fill gives {float(values[i, g])!r}, within the threshold "
+                                     f"{threshold!r}, and the stored components keep the two apart: they were not filled with this metric and threshold "
+                                     f"from these genomes")
+
+    (labels,) = _extend_fill(plan, genomes, func, "components_extend", as_distance, verify, guard,
+        lambda ctx, metric: ctx.fill_rows_components(metric, threshold, new_idx, seed_labels=seed, as_distance=as_distance, strict=strict,
+                                                     slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_components']} components in "
+                                      f"{stats['n_slabs']} slab(s): guard+fill+union+labels {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)")
     return Components(names, labels)
 
 
@@ -1531,22 +1531,19 @@ def tree_extend(tree, genomes, func, verify=4, slab_bytes=0):
     ``tree`` lacks (``Context.fill_rows_tree``: the stored edges seed the resident forest; MST(A + B) = MST(MST(A) + B)).  Arguments,
     refusals and routes as ``edges_extend``.  The guard: every stored edge that touches a verified old genome must carry exactly the
     refilled value.  Removing genomes is no such call: ``SingleLinkageTree.without`` says why."""
-    names, old_at, new_idx = _extend_plan(tree.nodes, genomes, "tree_extend")
+    plan = names, old_at, new_idx = _extend_plan(tree.nodes, genomes, "tree_extend")
     as_distance = tree.is_distance
     if old_at.shape[0] == 0:
         return tree_de_novo(genomes, func, as_distance=as_distance, slab_bytes=slab_bytes)
     src, tgt, weight = old_at[tree.source], old_at[tree.target], tree.weight
     if not new_idx:
         return SingleLinkageTree(names, src, tgt, weight, is_distance=as_distance)
-    ctx, metric, record = _extend_upload(genomes, func, "tree_extend")
-    import time
-    t0 = time.perf_counter()
-    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
-    _guard_edges(names, metric, checked, values, src, tgt, weight, "tree")
-    src, tgt, weight, stats = ctx.fill_rows_tree(metric, new_idx, seed=(src, tgt, weight), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
-    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} tree edges in {stats['n_slabs']} slab(s): "
-                  f"guard+fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds {stats.get('ms_rounds', 0.0):.3f} ms)")
+    src, tgt, weight = _extend_fill(plan, genomes, func, "tree_extend", as_distance, verify,
+        lambda metric, checked, values: _guard_edges(names, metric, checked, values, src, tgt, weight, "tree"),
+        lambda ctx, metric: ctx.fill_rows_tree(metric, new_idx, seed=(src, tgt, weight), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
+        lambda stats, record, fill_s: (
+            f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, {stats['n_edges']} tree edges in {stats['n_slabs']} slab(s): "
+            f"guard+fill+rounds+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, rounds {stats.get('ms_rounds', 0.0):.3f} ms)"))
     return SingleLinkageTree(names, src, tgt, weight, is_distance=as_distance)
 
 
@@ -1578,7 +1575,7 @@ def neighbors_extend(neighbors, genomes, func, k=None, verify=4, slab_bytes=0):
     shorter list cannot decide more neighbours.  Arguments, refusals and routes as ``tree_extend``.  The guard: for each verified old
     genome, the best ``neighbors.k`` of its refilled row, restricted to the old genomes, must equal its stored list in indices and
     value bits.  Removing genomes is no such call: ``NearestNeighbors.without`` says why."""
-    names, old_at, new_idx = _extend_plan(neighbors.nodes, genomes, "neighbors_extend")
+    plan = names, old_at, new_idx = _extend_plan(neighbors.nodes, genomes, "neighbors_extend")
     as_distance, n_old = neighbors.is_distance, int(old_at.shape[0])
     if k is None:
         k = neighbors.k
@@ -1592,20 +1589,19 @@ def neighbors_extend(neighbors, genomes, func, k=None, verify=4, slab_bytes=0):
         return neighbors_de_novo(genomes, func, k, as_distance=as_distance, slab_bytes=slab_bytes)
     indices = old_at[neighbors.indices].reshape(n_old, neighbors.k)
     if not new_idx:
-        kk = min(k, neighbors.k)
-        return NearestNeighbors(names, indices[:, :kk], neighbors.weights[:, :kk], is_distance=as_distance)
-    ctx, metric, record = _extend_upload(genomes, func, "neighbors_extend")
-    import time
-    t0 = time.perf_counter()
-    checked, values = _guard_rows(ctx, metric, as_distance, old_at, verify)
-    _guard_neighbors(names, metric, checked, values, old_at, indices, neighbors.weights, as_distance)
-    seed_nbr = np.zeros((len(names), neighbors.k), dtype=np.int32)
-    seed_val = np.zeros((len(names), neighbors.k), dtype=np.float64)
-    seed_nbr[old_at], seed_val[old_at] = indices, neighbors.weights
-    nbr, val, stats = ctx.fill_rows_nearest(metric, k, new_idx, seed=(seed_nbr, seed_val), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
-    fill_s = _record_extend(stats, metric, names, record, len(new_idx), t0)
-    logging.debug(f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, the {stats['k']} nearest of each in {stats['n_slabs']} slab(s): "
-                  f"guard+fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection {stats.get('ms_select', 0.0):.3f} ms)")
+        return NearestNeighbors(names, indices[:, :min(k, neighbors.k)], neighbors.weights[:, :min(k, neighbors.k)], is_distance=as_distance)
+
+    def fill(ctx, metric):
+        seed_nbr = np.zeros((len(names), neighbors.k), dtype=np.int32)
+        seed_val = np.zeros((len(names), neighbors.k), dtype=np.float64)
+        seed_nbr[old_at], seed_val[old_at] = indices, neighbors.weights
+        return ctx.fill_rows_nearest(metric, k, new_idx, seed=(seed_nbr, seed_val), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+
+    nbr, val = _extend_fill(plan, genomes, func, "neighbors_extend", as_distance, verify,
+        lambda metric, checked, values: _guard_neighbors(names, metric, checked, values, old_at, indices, neighbors.weights, as_distance), fill,
+        lambda stats, record, fill_s: (
+            f"{len(new_idx)} new of {len(names)} genomes -> {stats['n_pairs']} pairs, the {stats['k']} nearest of each in {stats['n_slabs']} slab(s): "
+            f"guard+fill+select+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, selection {stats.get('ms_select', 0.0):.3f} ms)"))
     return NearestNeighbors(names, nbr, val, is_distance=as_distance)
 
 
