@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 163   /* 0.5.12: pc_fill_rows_nearest, pc_nearest_rows_tile */
+#define PC_VERSION 164   /* 0.5.13: pc_fill_between, pc_multi_fill_between, pc_last_between_times, pc_between_max_groups, pc_between_segment */
 
 typedef enum {
     PC_OK = 0,
@@ -360,6 +360,44 @@ uint64_t pc_tree_key(int32_t micro, int32_t s, int32_t t);
 int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
 
 /*
+ * Between-groups fill: for a partition of the N genomes into n_groups groups -- group[g] in [0, n_groups) is genome g's -- the
+ * n_groups x n_groups table of the count, sum, minimum and maximum of the pair values between every two groups, and within each group
+ * on the diagonal: the minimum is the single-linkage, the maximum the complete-linkage and sum / count the average-linkage distance of
+ * two clusters (what the reference's dataset heatmap in cluster order shows, matrix.py / scripts/phamclust.py:433, above its 1,500
+ * genome cap); the diagonal holds each group's diameter and mean.  A value enters as its millionths, micro = rint(v * 1e6), of the
+ * DISTANCE as filled: every delivered value is round(x, 6), so sum[a][b] is an integer and lo / hi are integers, and the table is
+ * exact: it depends neither on the slab cut, nor on the number of devices, nor on the order of any atomic.  The pass checks what that
+ * relies on -- 0 <= micro <= 10^6 and micro / 10^6 == v, bit for bit -- and counts violations: PC_ERR_DATA; such a value is added
+ * nowhere.  as_distance == 0 delivers the SIMILARITY table, which is the distance table inverted -- sum' = count * 10^6 - sum, lo' =
+ * 10^6 - hi, hi' = 10^6 - lo, by the fold -- i.e. the table of the matrix SymMatrix.invert() (matrix.py:236-247: round(1 - d, 6), the
+ * complement of a millionth) makes of the distance matrix, as every similarity the pipeline writes is made.  It is deliberately not
+ * the table of a similarity FILL's values: that fill rounds s where the distance fill rounds 1 - s, and at a decimal tie both round
+ * up (one pair in 19,900 under af on the synth200 fixture), so its millionths are not always the complements.
+ * Same walk as pc_fill_edges (the slab cut, slab_bytes, 0 = automatic).  Each filled slab goes through ONE pass, k_between_rows: a
+ * workgroup takes one target row of the slab, or one segment of pc_between_segment() elements of a long row, accumulates over the
+ * sources' groups in a table of n_groups entries in LDS and adds what it touched into one row of the accumulator that stays on the
+ * device (sum u64, cnt u64, lo u32, hi u32 per entry).  After the last slab k_between_fold makes the square symmetric, then ONE D2H copy.
+ * *sum, *count (int64), *lo, *hi (int32; millionths): [n_groups][n_groups], row-major, symmetric, in page-locked memory the context owns
+ * (pc_fill_borrow's loan rule).  An entry no pair fell into -- the diagonal of a one-genome group, every entry of an empty group --
+ * reads count = 0, sum = 0, lo = INT32_MAX, hi = -1.  Off the diagonal count[a][b] = n_a n_b, on it n_a (n_a - 1) / 2.  N <= 1: PC_OK,
+ * nothing runs on the device, every entry empty.  *n_slabs and stats as pc_fill_edges gives them.
+ * PC_ERR_ARG: bad metric, group NULL, n_groups < 1, a label outside [0, n_groups) (the message names the genome), negative slab_bytes,
+ * a NULL out pointer.  PC_ERR_LIMIT: n_groups above PC_BETWEEN_MAX_GROUPS (the LDS table of the pass: 16 bytes per group, 32 KB at the
+ * limit, four workgroups of 256 threads per compute unit).  PC_ERR_STATE: before upload, on a sharded context (world != 1: several
+ * GPUs share the walk through pc_multi_fill_between), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill, and a
+ * slab value that is no millionth in [0, 1].  On a refusal the four pointers are NULL and *n_slabs is 0.  The caller's unsharded state
+ * is back in force when the call returns, whatever it returns.  Runs on the context's own stream and returns with everything finished.
+ */
+#define PC_BETWEEN_MAX_GROUPS 2048
+int pc_fill_between(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                    const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook, of the last pc_fill_between call: *ms_reduce the passes summed over its slabs, *ms_finish the fold (HIP events; 0
+ * unless the call was given stats); either pointer may be NULL. */
+int pc_last_between_times(const pc_ctx* ctx, float* ms_reduce, float* ms_finish);
+int pc_between_max_groups(void);    /* PC_BETWEEN_MAX_GROUPS */
+int pc_between_segment(void);       /* elements of a slab row one workgroup of the pass takes (a longer row is split at multiples of it) */
+
+/*
  * The rows forms of the edge-list, components and tree fills: a STORED result grown by new genomes.  rows[n_rows] are the query genomes
  * -- the new ones -- under pc_fill_rows' contract (strictly ascending indices of the uploaded collection, which holds old and new
  * genomes in fill order); the pairs of the call are those that touch a query genome, each once (a pair of two query genomes in the row
@@ -524,6 +562,12 @@ int pc_multi_fill_nearest(pc_multi* m, int metric, int as_distance, int k, int64
  * does.  pc_multi_last_slab_times: the slowest device's copy and the root's merge rounds. */
 int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int64_t slab_bytes,
                        const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats);
+/* pc_fill_between over the devices of `m`, on the same terms and with the same deal.  Every device accumulates over its stretch of
+ * targets and ships its raw accumulator once, 24 n_groups^2 + 8 bytes, into a staging slice on the root; ONE launch of k_between_merge
+ * adds sums and counts and takes the extremes (a pair lies in exactly one stretch: nothing is counted twice), then the root folds as
+ * the single-context call does.  pc_multi_last_slab_times: the slowest device's copy and the root's merge. */
+int pc_multi_fill_between(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                          const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
 int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds /* pc_multi_devices(m) + 1 entries */);
 int pc_multi_last_slab_times(const pc_multi* m, float* ms_exchange, float* ms_merge);
 /* The stretch deal itself, host arithmetic only (no GPU, no context; exported for tests as pc_chunk_plan is): bounds[world + 1] with

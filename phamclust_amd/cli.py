@@ -76,6 +76,12 @@ _OPTIONS = (
                                                                              "least K neighbours) wrote over a SUBSET of these genomes: only the pairs "
                                                                              "of the genomes it lacks are filled, on one GPU, and the file written is "
                                                                              "the from-scratch run's, byte for byte")),
+    (None, "-B", "--cluster-table", dict(action="store_true", help="after clustering, one between-groups fill over the final clusters (the "
+                                                                   "multi-genome clusters in output order, then the singletons): writes "
+                                                                   "cluster_table_<metric>.tsv (count, mean, min, max similarity of every two "
+                                                                   "clusters), cluster_<metric>_similarities.tsv (their mean similarity as a "
+                                                                   "square) and, for at most 1500 clusters, cluster_<metric>_heatmap.{html,svg}; "
+                                                                   "with the dense route or --no-matrix, and with --gpus N")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -148,6 +154,11 @@ def parse_args(argv=None):
             parser.error("--grow-nearest FILE grows the stored lists of a --nearest K run; give --nearest K")
         if args.gpus > 1:
             parser.error("--grow-nearest: growing a stored result is a one-GPU call; it cannot be combined with --gpus N")
+    if args.cluster_table:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--tree", args.tree),
+                            ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
+            if given:
+                parser.error(f"--cluster-table reads the final clusters of the whole pipeline; it cannot be combined with {flag}")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

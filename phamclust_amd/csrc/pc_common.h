@@ -241,6 +241,27 @@ int pc_launch_tree_hook(const int32_t* comp, int32_t* next, const unsigned long 
                         hipStream_t st);
 int pc_launch_tree_flatten(int32_t* comp, const int32_t* next, unsigned long long* best, unsigned long long* out, int n, const uint32_t* live, int r,
                            hipStream_t st);
+// between-groups table of a filled slab (pc_between.hip).  The accumulator of G groups is one allocation of pc_between_bytes(G):
+// sum u64[G][G] | cnt u64[G][G] | lo u32[G][G] | hi u32[G][G] | the 8-byte count of values that are no millionth in [0, 1].  Entry
+// [group[t]][group[s]] takes pair (s, t); an empty accumulator is all zero but lo = ~0.  The folded result has the same layout with
+// i64 / i64 / i32 / i32 arrays, symmetric.
+#define PC_BETWEEN_SEGMENT 4096                    // elements of a slab row one workgroup of k_between_rows takes
+struct PcBetweenAcc { unsigned long long *sum, *cnt; uint32_t *lo, *hi; unsigned long long* bad; };
+static inline size_t pc_between_bytes(int G) { return (size_t)G * (size_t)G * 24 + 8; }
+__host__ __device__ static inline PcBetweenAcc pc_between_view(void* base, int G) {
+    const size_t gg = (size_t)G * (size_t)G;
+    unsigned long long* const sum = (unsigned long long*)base;
+    uint32_t* const lo = (uint32_t*)(sum + 2 * gg);
+    return PcBetweenAcc{sum, sum + gg, lo, lo + gg, (unsigned long long*)(lo + 2 * gg)};
+}
+int pc_launch_between_init(void* acc, int G, hipStream_t st);
+// one slab: vals f64[Lp] in the shard's layout, max_row its longest row; group: [N] on the device, every label in [0, G)
+int pc_launch_between_rows(const double* vals, int64_t Lp, const PcShard& sh, int64_t max_row, const int32_t* group, int G, void* acc, hipStream_t st);
+// the accumulators of other devices added into acc: staged[n_foreign] of pc_between_bytes(G) each
+int pc_launch_between_merge(void* acc, const void* staged, int n_foreign, int G, hipStream_t st);
+// the square made symmetric into out (the result layout), empty entries as lo = INT32_MAX, hi = -1; invert: the accumulator holds
+// distances and out takes the similarity table, every millionth's complement
+int pc_launch_between_fold(const void* acc, void* out, int G, int invert, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

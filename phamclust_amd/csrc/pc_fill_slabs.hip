@@ -1,8 +1,9 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
-// pc_last_nearest_times, and pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds.
-// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill: begin, slab, end, and what several
+// pc_last_nearest_times, pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds, and
+// pc_fill_between (the count, sum, minimum and maximum of the pair values between every two groups of a partition) with pc_last_between_times.
+// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill, PcBetweenFill: begin, slab, end, and what several
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
 // own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
@@ -15,6 +16,7 @@
 // shard-local layout), filled by fill_impl into the context's slab buffer and handed to the description's slab().  Slabs come in
 // ascending target order; one slab is resident at a time.
 #include <chrono>
+#include <climits>
 
 #include "pc_host.h"
 
@@ -44,6 +46,17 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         if (run.k < 1) { pc_set_error("%s: k %d", who, run.k); return PC_ERR_ARG; }
         if (run.k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, run.k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
         run.kk = std::max(std::min(run.k, c->dev.N - 1), 0);
+    }
+    if (run.kind == PC_SLAB_BETWEEN) {
+        if (!run.group) { pc_set_error("%s: group is NULL", who); return PC_ERR_ARG; }
+        if (run.n_groups < 1) { pc_set_error("%s: n_groups %d", who, run.n_groups); return PC_ERR_ARG; }
+        if (run.n_groups > PC_BETWEEN_MAX_GROUPS) {
+            pc_set_error("%s: n_groups %d is above PC_BETWEEN_MAX_GROUPS = %d", who, run.n_groups, PC_BETWEEN_MAX_GROUPS); return PC_ERR_LIMIT;
+        }
+        for (int g = 0; g < c->dev.N; ++g)
+            if (run.group[g] < 0 || run.group[g] >= run.n_groups) {
+                pc_set_error("%s: genome %d has label %d, outside [0, %d)", who, g, run.group[g], run.n_groups); return PC_ERR_ARG;
+            }
     }
     if (run.kind == PC_SLAB_TREE && c->dev.N > PC_TREE_MAX_GENOMES) {
         pc_set_error("%s: %d genomes are above PC_TREE_MAX_GENOMES = %d", who, c->dev.N, PC_TREE_MAX_GENOMES);
@@ -152,10 +165,12 @@ template int pc_slab_fill<PcEdgesFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_fill<PcComponentsFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_fill<PcNearestFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_fill<PcTreeFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_fill<PcBetweenFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_stretch<PcEdgesFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcComponentsFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcNearestFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcTreeFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_stretch<PcBetweenFill>(pc_ctx*, PcSlabRun&, int, int);
 
 // ---- what the descriptions share ----
 // begin, ahead of anything of the fill's own: the run and the fill's two times (last_ms) reset, the loan of an earlier call ended (its
@@ -601,6 +616,85 @@ extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_
     if (launched_rounds) *launched_rounds = c->last_tree_rounds[1];
     return PC_OK;
 }
+
+// ---- between-groups fill: for a partition of the genomes into G groups the G x G table of the count, sum, minimum and maximum of the
+// pair values between every two groups, in millionths -- what the reference's dataset heatmap in cluster order shows (matrix.py,
+// scripts/phamclust.py:433) and what single, complete and average linkage between clusters are.  Each filled slab goes through ONE pass,
+// k_between_rows (pc_between.hip), over an accumulator that stays on the device from the first slab to the last; nothing is read back
+// per slab.  After the last slab: k_between_fold, then one D2H of the four arrays and the 8-byte violation count behind them.  The walk
+// always fills distances (the entry points set as_distance = 1 and keep what the caller asked for in bt_invert): a similarity table is
+// the distance table inverted by the fold, as SymMatrix.invert() inverts a matrix.
+int PcBetweenFill::begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N, G = run.n_groups;
+    const size_t bytes = pc_between_bytes(G);
+    if ((rc = slab_begin(c, run, c->last_bt_ms)) || (rc = c->h_bt.ensure(bytes))) return rc;
+    if (N <= 1) return PC_OK;
+    if ((rc = slab_size(c, run))) return rc;
+    if ((rc = c->b_bt_acc.ensure(bytes)) || (rc = c->b_bt_out.ensure(bytes))) return abi_rc(rc);
+    if ((rc = upload_raw(c->b_bt_group, run.group, (size_t)N * 4))) return rc;
+    return pc_launch_between_init(c->b_bt_acc.p, G, c->stream);
+}
+// (there is no rows form: a rows slab is refused)
+int PcBetweenFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    if (dom.is_rows) { pc_set_error("%s: a between-groups fill has no rows form", run.who); return PC_ERR_ARG; }
+    const int64_t max_row = c->h_owned.empty() ? 0 : (int64_t)c->h_owned.back();      // (ascending targets, row t holds t values)
+    return slab_pass(c, run, c->last_bt_ms, [&](hipStream_t st) {
+        return pc_launch_between_rows(slab, Lp, dom.shard, max_row, c->b_bt_group.as<int32_t>(), run.n_groups, c->b_bt_acc.p, st);
+    });
+}
+int PcBetweenFill::end(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int G = run.n_groups;
+    const size_t gg = (size_t)G * (size_t)G;
+    const PcBetweenAcc h = pc_between_view(c->h_bt.p, G);
+    run.bt_sum = (const int64_t*)h.sum; run.bt_cnt = (const int64_t*)h.cnt; run.bt_lo = (const int32_t*)h.lo; run.bt_hi = (const int32_t*)h.hi;
+    if (c->dev.N <= 1) {                                                    // no pair: every entry empty
+        memset(h.sum, 0, gg * 16);
+        for (size_t i = 0; i < gg; ++i) { ((int32_t*)h.lo)[i] = INT32_MAX; ((int32_t*)h.hi)[i] = -1; }
+        return PC_OK;
+    }
+    if ((rc = slab_finish(c, run, c->last_bt_ms, c->h_bt.p, c->b_bt_out.p, pc_between_bytes(G), [&](hipStream_t st) {
+            return pc_launch_between_fold(c->b_bt_acc.p, c->b_bt_out.p, G, run.bt_invert, st);
+        }))) return rc;
+    if (*h.bad) {
+        pc_set_error("%s: %llu values of the fill are no millionth in [0, 1]: the table is not defined on them", run.who, *h.bad);
+        return PC_ERR_DATA;
+    }
+    return PC_OK;
+}
+// Several devices: a device ships its raw accumulator, 24 G^2 + 8 bytes, and the root adds the staged ones into its own in one launch
+// (k_between_merge) before it folds: a pair lies in exactly one stretch, so nothing is counted twice.
+size_t PcBetweenFill::ship_bytes(const pc_ctx*, const PcSlabRun& run) { return pc_between_bytes(run.n_groups); }
+int PcBetweenFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int) {
+    int rc = PC_OK;
+    const size_t bytes = pc_between_bytes(run.n_groups);
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, (char*)stage + (size_t)slot * bytes, c->b_bt_acc.p, bytes))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
+    return PC_OK;
+}
+int PcBetweenFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if ((rc = pc_launch_between_merge(root->b_bt_acc.p, stage, n_foreign, runs[0].n_groups, root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
+    return PC_OK;
+}
+
+extern "C" int pc_fill_between(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                               const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_between"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcBetweenFill>(run, {sum, count, lo, hi, n_slabs}, stats, [&] { return pc_slab_fill<PcBetweenFill>(c, run); });
+}
+
+extern "C" int pc_last_between_times(const pc_ctx* c, float* ms_reduce, float* ms_finish) {
+    return last_times(c, "pc_last_between_times", c ? c->last_bt_ms : nullptr, ms_reduce, ms_finish);
+}
+extern "C" int pc_between_max_groups(void) { return PC_BETWEEN_MAX_GROUPS; }
+extern "C" int pc_between_segment(void) { return PC_BETWEEN_SEGMENT; }
 
 // ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest grow a STORED result.  The pairs of the call are
 // those that touch a query genome (the new genomes of a grown collection): k query rows cost k N pairs, not N^2 / 2.  What is stored

@@ -136,6 +136,10 @@ struct pc_ctx {
     int tree_cur = 0;                       // which of the two lists is the resident forest
     float last_tree_ms[2] = {0.f, 0.f};     // rounds (with stats), finish of the last pc_fill_tree (pc_last_tree_times)
     int32_t last_tree_rounds[2] = {0, 0};   // ... its rounds that did work, and those enqueued (pc_last_tree_rounds)
+    // pc_fill_between: group[N], the resident accumulator and the folded table (pc_between_bytes(G) each: pc_common.h), the table's pinned host image
+    DevBuf b_bt_group, b_bt_acc, b_bt_out;
+    PinnedBuf h_bt;                         // the four arrays lent out by pc_fill_between
+    float last_bt_ms[2] = {0.f, 0.f};       // passes, fold of the last pc_fill_between with stats (pc_last_between_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -244,23 +248,23 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
-// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree, and pc_multi_fill_* over several devices) is ONE description of the
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree / pc_fill_between, and pc_multi_fill_* over several devices) is ONE description of the
 // fill -- a struct of static functions, declared here and defined in pc_fill_slabs.hip (the launchers of its kernels live in pc_edges.hip,
-// pc_components.hip, pc_nearest.hip and pc_tree.hip) -- handed as a template argument to the drivers:
+// pc_components.hip, pc_nearest.hip, pc_tree.hip and pc_between.hip) -- handed as a template argument to the drivers:
 //   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
 //   pc_slab_stretch<Fill>   the walk over the targets [ta, tb): the slab cut, each slab filled and handed to Fill::slab
 //   multi_slab_fill<Fill>   (pc_multi.hip) begin -> walk(its stretch) -> ship on every device, then merge -> end on the root
 //   pc_rows_slab_fill<Fill> (pc_fill_slabs.hip) a rows form: check -> rows -> Seed::pack -> begin -> Seed::install -> walk the query rows -> end
 // and every extern "C" entry point is its signature, the fields of the run that are its own, and pc_slab_call<Fill> around one of them.
 // What a description says:
-//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut), which can be
+//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut / PcTableOut), which can be
 //           cleared, say whether all are there, and take their values from a finished run
 //   Seed    what a stored result is to the fill (the rows forms): the caller's seed arguments; pack() checks them and packs them into host
 //           memory the call owns, BEFORE begin (the caller may hand back arrays an earlier call lent out, which begin rewrites);
 //           install() puts the packed seed in place of the initial state on the device, after begin (N > 1 only)
 //   begin   the earlier loan ends, the pinned result and the device state are sized, the state initialised (k_cc_init / k_nn_init),
 //           the slab size decided (before the call allocates anything of its own, as the automatic size reads the free HBM)
-//   slab    what is done with one filled slab (compact and append / union / select); the state stays on the device.  dom says which pairs
+//   slab    what is done with one filled slab (compact and append / union / select / accumulate); the state stays on the device.  dom says which pairs
 //           its values are: the shard of a triangular slab, or the
 //           PcRowsSlab of one slab of a rows slab fill (pc_rows_slab_fill, pc_fill_slabs.hip: f64[m][N] of a range of query rows); begin
 //           and end are the triangular walk's
@@ -269,13 +273,16 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //           nothing travels between devices), and how the root takes the others' state in before its end
 // For N <= 1 begin and the walk do nothing on the device.  PcSlabRun is the call as its entry point was given it (pc_slab_check
 // refuses in the public calls' order, folds the metric, normalises the flags and settles kk), its working state, and its results.
-enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE };
+enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE, PC_SLAB_BETWEEN };
 struct PcSlabRun {
     PcSlabKind kind = PC_SLAB_EDGES;
     const char* who = "";                   // the entry point, for the message texts
     bool outputs = false;                   // every output pointer was there
     int metric = 0, as_distance = 0, strict = 0, k = 0;
     double threshold = 0.0;                 // (nearest: none, stays 0)
+    const int32_t* group = nullptr;         // between: the caller's labels, host memory, [N]
+    int n_groups = 0;                       // ... and their range
+    bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold inverts
     int64_t slab_bytes = 0;
     bool timed = false;                     // the caller asked for stats: events around the passes over a slab
     int kk = 0;                             // nearest: min(k, N - 1), at least 0 (pc_slab_check)
@@ -288,6 +295,8 @@ struct PcSlabRun {
     const double* val = nullptr;            // edges: the values; nearest: val[N][kk]
     int64_t n_edges = 0;                    // edges: in the pinned arrays so far; components: pairs that passed (before end: on the other devices)
     int32_t n_components = 0;
+    const int64_t *bt_sum = nullptr, *bt_cnt = nullptr;     // between: the four [n_groups][n_groups] arrays
+    const int32_t *bt_lo = nullptr, *bt_hi = nullptr;
     int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
@@ -295,7 +304,7 @@ struct PcSlabRun {
 // The output shapes and the seeds are hidden, and pc_slab_call is static: however their members are inlined, the library's list of
 // dynamic symbols stays what it was before they had names.
 #pragma GCC visibility push(hidden)
-// The three output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
+// The four output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
 template <class Count> struct PcEdgeOut {
     const int32_t **src, **tgt; const double** val; Count* n_edges; int32_t* n_slabs;
     bool all() const { return src && tgt && val && n_edges && n_slabs; }
@@ -313,6 +322,12 @@ struct PcListOut {
     bool all() const { return nbr && val && k && n_slabs; }
     void clear() const { if (nbr) *nbr = nullptr; if (val) *val = nullptr; if (k) *k = 0; if (n_slabs) *n_slabs = 0; }
     void take(const PcSlabRun& run) const { *nbr = run.nbr; *val = run.val; *k = run.kk; *n_slabs = run.n_slabs; }
+};
+struct PcTableOut {
+    const int64_t **sum, **count; const int32_t **lo, **hi; int32_t* n_slabs;
+    bool all() const { return sum && count && lo && hi && n_slabs; }
+    void clear() const { if (sum) *sum = nullptr; if (count) *count = nullptr; if (lo) *lo = nullptr; if (hi) *hi = nullptr; if (n_slabs) *n_slabs = 0; }
+    void take(const PcSlabRun& run) const { *sum = run.bt_sum; *count = run.bt_cnt; *lo = run.bt_lo; *hi = run.bt_hi; *n_slabs = run.n_slabs; }
 };
 // The seeds: the caller's arguments first (an entry point brace-initialises them), then what pack() made of them.
 struct PcNoSeed {                           // edges: a stored list needs nothing on the device, the caller merges the two lists
@@ -351,6 +366,7 @@ PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill", PC_SLAB_ED
 PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill", PC_SLAB_COMPONENTS, PcLabelOut, PcLabelSeed);
 PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill", PC_SLAB_NEAREST, PcListOut, PcNearestSeed);
 PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill", PC_SLAB_TREE, PcEdgeOut<int32_t>, PcTreeSeed);
+PC_SLAB_FILL(PcBetweenFill, PcSlabDomain, "between", "a between-groups fill", PC_SLAB_BETWEEN, PcTableOut, PcNoSeed);
 #undef PC_SLAB_FILL
 // What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into
 // the run (whose call fields the entry point has set), drive(), and on PC_OK the results into the outputs and the run's own stats

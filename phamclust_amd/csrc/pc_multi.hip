@@ -15,7 +15,7 @@
 // partition by itself), and ONE exchange -- every device copies its shard to the root's gather buffer, device to device (peer
 // copies: xGMI between the GPUs of a node) -- before the root permutes the shards into condensed order and delivers them to the
 // host.  The reference spreads the same pair list over `cpus` worker processes (matrix.py:471-493).
-// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest / _tree, at the end of this file) deal contiguous
+// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest / _tree / _between, at the end of this file) deal contiguous
 // stretches of targets instead, one per device, and merge the devices' small per-genome state on the root.
 // ---------------------------------------------------------------------------------------------------------------------
 struct pc_multi {
@@ -211,7 +211,7 @@ extern "C" int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Edge, component, nearest and tree fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
+// Edge, component, nearest, tree and between-groups fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
 // (pc_host.h, pc_fill_slabs.hip).  Each device runs the description's begin and the walk over ONE contiguous stretch of targets with
 // the call's state on its own device, and ships that state to the root; the state merges exactly -- lists by their total order,
 // forests by uniting g with its foreign parent, edge lists over ascending stretches by concatenation -- so the root's end delivers
@@ -333,6 +333,13 @@ extern "C" int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int6
                                   const int32_t** src, const int32_t** tgt, const double** val, int32_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     PcSlabRun run; run.who = "pc_multi_fill_tree"; run.metric = metric; run.as_distance = as_distance; run.slab_bytes = slab_bytes;
     return pc_slab_call<PcTreeFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return multi_slab_fill<PcTreeFill>(m, run, stats); });
+}
+
+extern "C" int pc_multi_fill_between(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                                     const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_multi_fill_between"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcBetweenFill>(run, {sum, count, lo, hi, n_slabs}, stats, [&] { return multi_slab_fill<PcBetweenFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds) {

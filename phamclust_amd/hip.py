@@ -77,7 +77,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_fill_nearest", "pc_last_nearest_times", "pc_multi_fill_edges", "pc_multi_fill_components", "pc_multi_fill_nearest",
            "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan", "pc_fill_tree", "pc_multi_fill_tree", "pc_last_tree_times",
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
-           "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile"]
+           "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
+           "pc_between_max_groups", "pc_between_segment"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -172,6 +173,11 @@ def load():
                                        ctypes.POINTER(_i32p), ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(PcStats)]
     L.pc_nearest_rows_tile.argtypes = []
+    L.pc_fill_between.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i64p), ctypes.POINTER(_i64p),
+                                  ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_between_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_between_max_groups.argtypes = []
+    L.pc_between_segment.argtypes = []
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -202,6 +208,7 @@ def load():
     L.pc_multi_fill_components.argtypes = L.pc_fill_components.argtypes
     L.pc_multi_fill_nearest.argtypes = L.pc_fill_nearest.argtypes
     L.pc_multi_fill_tree.argtypes = L.pc_fill_tree.argtypes
+    L.pc_multi_fill_between.argtypes = L.pc_fill_between.argtypes
     L.pc_multi_last_stretches.argtypes = [vp, _i32p]
     L.pc_multi_last_slab_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_stretch_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_int, _i32p]
@@ -299,7 +306,7 @@ class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
 
 
 class _SlabFills:
-    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` -- the fills that deliver no dense matrix -- once for :class:`Context`
+    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` / ``fill_between`` -- the fills that deliver no dense matrix -- once for :class:`Context`
     and :class:`MultiContext`.  The class supplies ``_SLAB_CALL`` (the prefix of the library's symbols), ``_before_slab_fill(metric)``
     (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
     dict of such a fill)."""
@@ -347,6 +354,43 @@ class _SlabFills:
         if not want_stats:
             return nbr, val
         return nbr, val, self._slab_stats("nearest", stats, k=int(kk.value), n_slabs=int(nsl.value))
+
+    def _fill_table(self, prefix, metric, args, n_groups, want_stats, borrow):
+        """``(sum, count, lo, hi)`` of a between-groups fill."""
+        ps, pc, pl, ph = _i64p(), _i64p(), _i32p(), _i32p()
+        nsl = ctypes.c_int32(0)
+        stats = self._slab_call(prefix + "between", metric, *args, ctypes.byref(ps), ctypes.byref(pc), ctypes.byref(pl), ctypes.byref(ph), ctypes.byref(nsl))
+        out = tuple(self._lend(ptr, (n_groups, n_groups), borrow) for ptr in (ps, pc, pl, ph))
+        if not want_stats:
+            return out
+        return (*out, self._slab_stats("between", stats, n_groups=int(n_groups), n_slabs=int(nsl.value)))
+
+    def fill_between(self, metric, group, n_groups=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """For a partition of the genomes -- ``group[g]`` in ``[0, n_groups)`` is genome g's group; ``n_groups`` defaults to the largest
+        label + 1 -- the table of the pair values between every two groups, and within each group on the diagonal, as ``(sum, count,
+        lo, hi)``: int64, int64, int32, int32 arrays ``[G, G]``, symmetric, in MILLIONTHS of the whole distance fill's values; with
+        ``as_distance=False`` the similarity table, which is that table inverted (``GroupLinkage.inverted``: every millionth's
+        complement, what ``SymMatrix.invert`` makes of the distance matrix -- at a decimal tie not what a similarity fill rounds to).  ``lo`` is the single-linkage, ``hi`` the complete-linkage and ``sum / count`` the
+        average-linkage value of two groups (``matrix.GroupLinkage`` reads them); integers, so the table is exact whatever the slab
+        cut or the number of devices.  An entry no pair fell into reads ``count = 0, sum = 0, lo = 2**31 - 1, hi = -1``.  The dense
+        matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time; 0 = automatic) held, as by :meth:`fill_edges`.
+        ``n_groups`` above ``Context.BETWEEN_MAX_GROUPS`` and a label out of range are refused by the library.  The arrays are copies;
+        ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s terms.  ``want_stats`` adds the
+        fills' summed stats with ``n_groups``, ``n_slabs``, ``ms_reduce`` and ``ms_finish``.
+
+        On a :class:`MultiContext`: the same arrays -- every device accumulates over its stretch of targets, the root adds the
+        accumulators (``k_between_merge``) and folds; the stats carry the route's own entries (as for :meth:`fill_edges`) in place of
+        the two times."""
+        if group is None:
+            raise ValueError("fill_between: group is None")
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        if group.shape[0] != self.n_genomes:
+            raise ValueError(f"fill_between: group holds {group.shape[0]} labels for {self.n_genomes} genomes")
+        if n_groups is None:
+            n_groups = int(group.max()) + 1 if group.size else 1
+        n_groups = int(n_groups)
+        pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
+        return self._fill_table(self._SLAB_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, int(slab_bytes)), n_groups, want_stats, borrow)
 
     def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
@@ -636,8 +680,15 @@ class Context(_SlabFills):
     # -- fill_edges / fill_components / fill_nearest / fill_tree (_SlabFills): what this class supplies ----------------------------------
     _SLAB_CALL = "pc_fill_"
     _SLAB_TIMES = {"edges": ("pc_last_edge_times", "ms_compact", "ms_d2h"), "components": ("pc_last_component_times", "ms_union", "ms_labels"),
-                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish")}
+                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish"), "between": ("pc_last_between_times", "ms_reduce", "ms_finish")}
     TREE_MAX_GENOMES = 1 << 22            # PC_TREE_MAX_GENOMES: a genome index takes 22 bits of a tree key
+    BETWEEN_MAX_GROUPS = 2048             # PC_BETWEEN_MAX_GROUPS: the pass keeps one entry per group in LDS
+
+    @staticmethod
+    def between_segment():
+        """Elements of a slab row one workgroup of the between-groups pass takes (``pc_between_segment``; host arithmetic, no GPU): what
+        a test of the pass's segment seams sizes its inputs by."""
+        return int(load().pc_between_segment())
 
     def _tree_rounds(self):
         """``live_rounds`` / ``launched_rounds`` of the last tree fill (``pc_last_tree_rounds``)."""

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, SparseEdges, SymMatrix, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupLinkage, SparseEdges, SymMatrix, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -452,6 +452,46 @@ class _Run:
         for suffix in ("svg", "html"):
             draw_heatmap(cluster, colors=self.colors, midpoint=self.midpoint, filename=root / f"{self.metric}_heatmap.{suffix}")
 
+    # 4b, --cluster-table
+    def cluster_table(self, groups, clu_distance):
+        """One between-groups fill over the final clusters -- ``groups``: the multi-genome clusters in output order, then the singletons,
+        as lists of names -- into the staging directory: ``cluster_table_<metric>.tsv`` (the long form, similarities),
+        ``cluster_<metric>_similarities.tsv`` (the mean similarity of every two clusters as a square over ``cluster_1 .. cluster_k`` and
+        the singletons' names; the diagonal a cluster's own mean) and, for at most 1,500 clusters, the heatmap of that square.  On the
+        --no-matrix route the fill runs on the upload that route holds; else on one of its own, over the devices of this process."""
+        self.banner("4b", f"{self.metric} cluster table (between-groups fill)")
+        t0 = time.perf_counter()
+        if len(groups) > _matrix.BETWEEN_MAX_GROUPS:
+            log.warning(f"--cluster-table: {len(groups):,} clusters and singletons are above the fill's {_matrix.BETWEEN_MAX_GROUPS:,} groups: "
+                        f"no cluster table is written")
+            return None
+        multi = sum(1 for group in groups if len(group) > 1)
+        names = [f"cluster_{k + 1}" if k < multi else group[0] for k, group in enumerate(groups)]
+        if self.fills is not None:
+            ctx, metric, genome_names = self.fills
+            index = {name: k for k, name in enumerate(genome_names)}
+            label = np.zeros(len(genome_names), dtype=np.int32)
+            for k, group in enumerate(groups):
+                label[[index[name] for name in group]] = k
+            *arrays, st = ctx.fill_between(metric, label, len(groups), as_distance=True, want_stats=True)
+            table = GroupLinkage(groups, *arrays, is_distance=True)
+        else:
+            table = between_de_novo(self.genomes, METRICS[self.metric], groups, as_distance=True)
+            st = _matrix.LAST_FILL
+        log.info(f"{len(groups):,} clusters and singletons -> {len(groups) * (len(groups) + 1) // 2:,} entries from {st.get('n_slabs', 1)} slab(s) on "
+                 f"{_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (kernels {st.get('ms_total', 0.0):.3f} ms, reduction "
+                 f"{st.get('ms_reduce', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
+        table = table.inverted()
+        between_to_file(table, names, self.stage / f"cluster_table_{self.metric}.tsv")
+        square = table.to_symmatrix(names, "mean")
+        matrix_to_squareform(square, self.stage / f"cluster_{self.metric}_similarities.tsv")
+        if len(groups) > 1500:
+            log.info("cluster table too large for a heatmap")
+        else:
+            for suffix in ("html", "svg"):
+                draw_heatmap(square, colors=self.colors, midpoint=1.0 - clu_distance, filename=self.stage / f"cluster_{self.metric}_heatmap.{suffix}")
+        return table
+
     # 5 + 6
     def finish(self, matrix, multi, single, clu_distance, rm_tmp):
         self.banner(5, "dataset outputs")
@@ -497,7 +537,7 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, grow=None, grow_nearest=None, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -509,7 +549,10 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     ``grow``: with ``tree``, the ``tree_<metric>.tsv`` -- with ``components_only`` and an ``edge_thresh``, the ``components_<metric>.tsv`` --
     an earlier run wrote over a subset of the genomes (``--grow``): only the pairs of the genomes it lacks are filled, on one GPU;
     ``grow_nearest``: with ``nearest``, the ``nearest_<metric>.tsv`` of an earlier run over a subset of the genomes (``--grow-nearest``),
-    grown the same way."""
+    grown the same way; ``cluster_table``: after the clustering, one between-groups fill over the final clusters and its three outputs
+    (``--cluster-table``; with the whole pipeline only, on either route)."""
+    if cluster_table and (adjacency_only or components_only or tree or nearest is not None or extend is not None):
+        raise ValueError("cluster_table cannot be combined with adjacency_only, components_only, tree, nearest or extend")
     if grow_nearest is not None and (nearest is None or grow is not None):
         raise ValueError("grow_nearest goes with nearest, and not with grow")
     if grow is not None:
@@ -551,6 +594,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["nearest"] = f"only, {nearest} neighbours per genome"
     if tree:
         settings["tree"] = "only (single-linkage dendrogram)"
+    if cluster_table:
+        settings["clusters"] = "with their table (--cluster-table: a between-groups fill)"
     if grow is not None:
         settings["grow"] = grow
     if grow_nearest is not None:
@@ -593,6 +638,9 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         run.tree()
         run.banner(3, "done (--tree: no clustering)")
         return
+    if cluster_table and run.world > 1:
+        log.error("--cluster-table is a one-process call: run it in one process, not under a launcher")
+        sys.exit(1)
     matrix = None
     if no_matrix:
         if run.world > 1:
@@ -604,6 +652,7 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         if matrix is None:                    # ranks other than 0 are done once their shard is gathered
             return
         multi, single = run.clusters(matrix, (nr_distance, nr_linkage), (clu_distance, clu_linkage))
+    final_groups = [list(m.nodes) for m in multi] + [list(m.nodes) for m in single]
     run.banner(4, "sub-clusters")
     run.stage = run._dir(run.cache / "03_clusters")
     for number, cluster in enumerate(multi, start=1):
@@ -614,6 +663,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         for one in single:
             name = one.nodes[0]
             run.by_name[name].save(lone / f"{name}.faa")
+    if cluster_table:
+        run.cluster_table(final_groups, clu_distance)
     if no_matrix:
         run.finish_no_matrix(rm_tmp)
     else:
@@ -652,6 +703,8 @@ def gpus_plan(args, route, packed):
     if args.extend is not None:
         # (pc_fill_rows refuses a sharded context): the matrix stage stays in this process, on one GPU
         return 1, "one", "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
+    if route == "launcher" and getattr(args, "cluster_table", False):
+        return 1, "one", "--cluster-table fills the clusters' table from one process: the matrix stage stays on one GPU"
     if route == "launcher":
         for attr, flag, what in SLAB_FILL_FLAGS:
             if getattr(args, attr) not in (None, False):
@@ -743,7 +796,7 @@ def _run(args, argv):
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
-                  nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest)
+                  nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
