@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 164   /* 0.5.13: pc_fill_between, pc_multi_fill_between, pc_last_between_times, pc_between_max_groups, pc_between_segment */
+#define PC_VERSION 165   /* 0.5.14: pc_fill_affinity, pc_multi_fill_affinity, pc_last_affinity_times, pc_affinity_block, pc_affinity_bytes */
 
 typedef enum {
     PC_OK = 0,
@@ -398,6 +398,39 @@ int pc_between_max_groups(void);    /* PC_BETWEEN_MAX_GROUPS */
 int pc_between_segment(void);       /* elements of a slab row one workgroup of the pass takes (a longer row is split at multiples of it) */
 
 /*
+ * Affinity fill (PC_VERSION 165): how every genome relates to every group of a partition.  group / n_groups, the checks, the millionths
+ * and the walk are pc_fill_between's.  For genome g and group b the table holds the sum, minimum and maximum of the millionths of
+ * d(g, x) over x in b, x != g; the count is not stored, it is size[b] - [group[g] == b].  The table, N x n_groups entries of 16 bytes
+ * (pc_affinity_bytes), stays on the device from the first slab to the last; each filled slab goes through two passes (k_aff_rows:
+ * entry [t][group[s]], a workgroup per target row; k_aff_cols: entry [s][group[t]], a wave per block of pc_affinity_block() sources
+ * and range of groups), every entry written by exactly one wave per launch, no global atomics on the table.  After the last slab
+ * k_aff_finish writes what a caller needs per genome, and ONE D2H copy delivers it:
+ *   *own_sum (int64), *own_lo, *own_hi (int32): [N], the genome's entry for its own group (a medoid is the member with the smallest
+ *       own_sum; own_sum / (size - 1) is the a of a silhouette)
+ *   *near_group (int32): [3][N], the OTHER non-empty group that is nearest by 0: the smallest mean (sum_b * size_c against sum_c * size_b
+ *       in 64-bit integers), 1: the smallest minimum, 2: the smallest maximum; ties go to the smaller group index; -1 where no other
+ *       non-empty group exists
+ *   *near_sum (int64), *near_lo, *near_hi (int32): [N], the value that made it nearest -- the sum of group near_group[0][g], the minimum
+ *       of group near_group[1][g], the maximum of group near_group[2][g]; 0 / INT32_MAX / -1 where there is none
+ *   *tab_sum (int64), *tab_lo, *tab_hi (int32): with want_table != 0 the whole table, [N][n_groups] row-major; else NULL
+ * An entry no pair falls into reads sum 0, lo INT32_MAX, hi -1.  as_distance == 0 delivers the statement of the inverted matrix (see
+ * pc_fill_between): the nearest groups are chosen on the distances and are the same, every reported value is complemented -- sum' =
+ * count * 10^6 - sum, table and own entries lo' = 10^6 - hi, hi' = 10^6 - lo, near_lo' = 10^6 - near_lo, near_hi' = 10^6 - near_hi.
+ * All arrays lie in page-locked memory the context owns (pc_fill_borrow's loan rule).  N <= 1: PC_OK, nothing runs on the device.
+ * Refusals as pc_fill_between's, and PC_ERR_LIMIT when the table (with want_table: and its converted copy) takes more than half of the
+ * HBM that is free when the call begins; the message carries both numbers.  There is no rows form.
+ */
+int pc_fill_affinity(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, int want_table, int64_t slab_bytes,
+                     const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                     const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                     const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook, of the last pc_fill_affinity call: the row passes and the column passes summed over its slabs, and the finish (HIP
+ * events; 0 unless the call was given stats); any pointer may be NULL. */
+int pc_last_affinity_times(const pc_ctx* ctx, float* ms_rows, float* ms_cols, float* ms_finish);
+int pc_affinity_block(void);        /* consecutive sources one wave of the column pass takes */
+int64_t pc_affinity_bytes(int64_t n, int64_t n_groups);   /* the resident table: 16 n n_groups + 8; -1: not representable */
+
+/*
  * The rows forms of the edge-list, components and tree fills: a STORED result grown by new genomes.  rows[n_rows] are the query genomes
  * -- the new ones -- under pc_fill_rows' contract (strictly ascending indices of the uploaded collection, which holds old and new
  * genomes in fill order); the pairs of the call are those that touch a query genome, each once (a pair of two query genomes in the row
@@ -568,6 +601,13 @@ int pc_multi_fill_tree(pc_multi* m, int metric, int as_distance, int64_t slab_by
  * the single-context call does.  pc_multi_last_slab_times: the slowest device's copy and the root's merge. */
 int pc_multi_fill_between(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
                           const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
+/* pc_fill_affinity over the devices of `m`, on the same terms and with the same deal.  Every device fills its table over its stretch of
+ * targets and ships it once, 16 N n_groups + 8 bytes, into a staging slice on the root; ONE launch of k_aff_merge combines them entry by
+ * entry (a pair lies in exactly one stretch), then the root finishes. */
+int pc_multi_fill_affinity(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int want_table, int64_t slab_bytes,
+                           const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                           const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                           const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats);
 int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds /* pc_multi_devices(m) + 1 entries */);
 int pc_multi_last_slab_times(const pc_multi* m, float* ms_exchange, float* ms_merge);
 /* The stretch deal itself, host arithmetic only (no GPU, no context; exported for tests as pc_chunk_plan is): bounds[world + 1] with

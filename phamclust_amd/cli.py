@@ -82,6 +82,12 @@ _OPTIONS = (
                                                                    "clusters), cluster_<metric>_similarities.tsv (their mean similarity as a "
                                                                    "square) and, for at most 1500 clusters, cluster_<metric>_heatmap.{html,svg}; "
                                                                    "with the dense route or --no-matrix, and with --gpus N")),
+    (None, "-F", "--cluster-fit", dict(action="store_true", help="after clustering, one affinity fill over the final clusters (as "
+                                                                 "--cluster-table takes them): writes cluster_fit_<metric>.tsv (per genome: its "
+                                                                 "cluster, mean similarity to it, the nearest other cluster and that mean, its "
+                                                                 "silhouette, whether it is the cluster's medoid) and "
+                                                                 "cluster_fit_<metric>_summary.tsv (per cluster: size, medoid, mean silhouette, "
+                                                                 "largest own distance); with the dense route or --no-matrix, and with --gpus N")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -159,6 +165,11 @@ def parse_args(argv=None):
                             ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
             if given:
                 parser.error(f"--cluster-table reads the final clusters of the whole pipeline; it cannot be combined with {flag}")
+    if args.cluster_fit:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--tree", args.tree),
+                            ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
+            if given:
+                parser.error(f"--cluster-fit reads the final clusters of the whole pipeline; it cannot be combined with {flag}")
     if args.no_matrix:
         for flag, given in (("--extend", args.extend is not None), ("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only)):
             if given:

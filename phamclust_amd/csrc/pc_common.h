@@ -262,6 +262,46 @@ int pc_launch_between_merge(void* acc, const void* staged, int n_foreign, int G,
 // the square made symmetric into out (the result layout), empty entries as lo = INT32_MAX, hi = -1; invert: the accumulator holds
 // distances and out takes the similarity table, every millionth's complement
 int pc_launch_between_fold(const void* acc, void* out, int G, int invert, hipStream_t st);
+// genome x group table of a filled slab (pc_affinity.hip).  The resident table of N genomes and G groups is one allocation of
+// pc_affinity_table_bytes(N, G): PcAffinityEntry[N][G] | the 8-byte count of values that are no millionth in [0, 1].  Entry [g][b]
+// takes the pairs of g with the members of b; an empty entry is (0, ~0, 0).  The result (PcAffinityOut over one allocation of
+// pc_affinity_out_bytes) is the violation count, the O(N) arrays and, when wanted, the converted table behind them.
+#define PC_AFFINITY_BLOCK 64                       // consecutive sources one wave of k_aff_cols takes, a lane each
+struct PcAffinityEntry { unsigned long long sum; uint32_t lo, hi; };
+static_assert(sizeof(PcAffinityEntry) == 16, "16 bytes per entry");
+static inline size_t pc_affinity_table_bytes(int N, int G) { return (size_t)N * (size_t)G * sizeof(PcAffinityEntry) + 8; }
+struct PcAffinityOut {
+    unsigned long long* bad;
+    long long *own_sum, *near_sum;                  // [N]
+    int32_t *own_lo, *own_hi, *near_group, *near_lo, *near_hi;   // [N]; near_group: [3][N], by mean, by minimum, by maximum
+    long long* tab_sum; int32_t *tab_lo, *tab_hi;   // [N][G], or NULL: the table was not asked for
+};
+static inline size_t pc_affinity_head_bytes(int N) { return ((size_t)8 + (size_t)N * 44 + 7) & ~(size_t)7; }
+static inline size_t pc_affinity_out_bytes(int N, int G, int want_table) {
+    return pc_affinity_head_bytes(N) + (want_table ? (size_t)N * (size_t)G * 16 : 0);
+}
+static inline PcAffinityOut pc_affinity_out_view(void* base, int N, int G, int want_table) {
+    const size_t n = (size_t)N, ng = n * (size_t)G;
+    PcAffinityOut o{};
+    o.bad = (unsigned long long*)base;
+    o.own_sum = (long long*)(o.bad + 1); o.near_sum = o.own_sum + n;
+    o.own_lo = (int32_t*)(o.near_sum + n); o.own_hi = o.own_lo + n; o.near_group = o.own_hi + n; o.near_lo = o.near_group + 3 * n; o.near_hi = o.near_lo + n;
+    if (want_table) {
+        o.tab_sum = (long long*)((char*)base + pc_affinity_head_bytes(N));
+        o.tab_lo = (int32_t*)(o.tab_sum + ng); o.tab_hi = o.tab_lo + ng;
+    }
+    return o;
+}
+int pc_launch_affinity_init(void* tab, int N, int G, hipStream_t st);
+// one slab of the consecutive targets [t0, t0 + sh.nown): vals f64[Lp] in the shard's layout; group / member / goff on the device, every
+// label in [0, G); grange: [n_ranges + 1] group ranges of the column pass, ascending from 0 to G
+int pc_launch_affinity_rows(const double* vals, int64_t Lp, const PcShard& sh, int t0, int N, const int32_t* group, int G, void* tab, hipStream_t st);
+int pc_launch_affinity_cols(const double* vals, int64_t Lp, const PcShard& sh, int t0, int N, const int32_t* member, const int32_t* goff,
+                            const int32_t* grange, int n_ranges, int G, void* tab, hipStream_t st);
+// the tables of other devices combined into tab: staged[n_foreign] of pc_affinity_table_bytes(N, G) each
+int pc_launch_affinity_merge(void* tab, const void* staged, int n_foreign, int N, int G, hipStream_t st);
+// the result into out (pc_affinity_out_bytes); invert: the table holds distances and out takes the similarity statement
+int pc_launch_affinity_finish(const void* tab, const int32_t* group, const int32_t* goff, int N, int G, int invert, void* out, int want_table, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

@@ -2,8 +2,9 @@
 // pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
 // pc_last_nearest_times, pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds, and
-// pc_fill_between (the count, sum, minimum and maximum of the pair values between every two groups of a partition) with pc_last_between_times.
-// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill, PcBetweenFill: begin, slab, end, and what several
+// pc_fill_between (the count, sum, minimum and maximum of the pair values between every two groups of a partition) with pc_last_between_times,
+// pc_fill_affinity (the sum, minimum and maximum of every genome's pair values to every group) with pc_last_affinity_times.
+// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill, PcBetweenFill, PcAffinityFill: begin, slab, end, and what several
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
 // own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
@@ -47,7 +48,7 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         if (run.k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, run.k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
         run.kk = std::max(std::min(run.k, c->dev.N - 1), 0);
     }
-    if (run.kind == PC_SLAB_BETWEEN) {
+    if (run.kind == PC_SLAB_BETWEEN || run.kind == PC_SLAB_AFFINITY) {
         if (!run.group) { pc_set_error("%s: group is NULL", who); return PC_ERR_ARG; }
         if (run.n_groups < 1) { pc_set_error("%s: n_groups %d", who, run.n_groups); return PC_ERR_ARG; }
         if (run.n_groups > PC_BETWEEN_MAX_GROUPS) {
@@ -171,6 +172,8 @@ template int pc_slab_stretch<PcComponentsFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcNearestFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcTreeFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcBetweenFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_fill<PcAffinityFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_stretch<PcAffinityFill>(pc_ctx*, PcSlabRun&, int, int);
 
 // ---- what the descriptions share ----
 // begin, ahead of anything of the fill's own: the run and the fill's two times (last_ms) reset, the loan of an earlier call ended (its
@@ -695,6 +698,153 @@ extern "C" int pc_last_between_times(const pc_ctx* c, float* ms_reduce, float* m
 }
 extern "C" int pc_between_max_groups(void) { return PC_BETWEEN_MAX_GROUPS; }
 extern "C" int pc_between_segment(void) { return PC_BETWEEN_SEGMENT; }
+
+// ---- affinity fill: for a partition of the genomes into G groups the N x G table of the sum, minimum and maximum of the pair values
+// between every genome and every group, in millionths -- the column a medoid is read from (SymMatrix.medoid, matrix.py:80-104, over a
+// group's own column), the two entries a silhouette is made of, and the group a genome is nearest to by average, single or complete
+// linkage.  Each filled slab goes through TWO passes, k_aff_rows and k_aff_cols (pc_affinity.hip), over a table that stays on the
+// device from the first slab to the last; nothing is read back per slab.  After the last slab: k_aff_finish, then one D2H of the O(N)
+// arrays (and of the whole table only when the caller asked for it).  The walk always fills distances, as the between-groups fill's.
+// What the table may take of the device: half of the HBM that is free when the call begins (the fill's own grow-only buffers counted as
+// free); the automatic slab size is read after the table is in place.
+extern "C" int pc_affinity_block(void) { return PC_AFFINITY_BLOCK; }
+extern "C" int64_t pc_affinity_bytes(int64_t n, int64_t n_groups) {
+    if (n < 0 || n_groups < 0 || (n && n_groups > (INT64_MAX - 8) / 16 / n)) return -1;
+    return n * n_groups * 16 + 8;
+}
+// the column pass's group ranges: about `want` of them, cut where the running member count passes equal shares (no range empty)
+static void affinity_ranges(const std::vector<int32_t>& goff, int G, int N, int want, std::vector<int32_t>& bounds) {
+    const int R = std::max(1, std::min(G, want));
+    bounds.assign(1, 0);
+    for (int r = 1; r < R; ++r) {
+        const int64_t share = (int64_t)N * r / R;
+        int a = (int)(std::lower_bound(goff.begin(), goff.begin() + G, (int32_t)share) - goff.begin());
+        a = std::max(a, bounds.back() + 1);
+        if (a >= G) break;
+        bounds.push_back(a);
+    }
+    bounds.push_back(G);
+}
+int PcAffinityFill::begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N, G = run.n_groups, want = run.want_table ? 1 : 0;
+    const size_t out_bytes = pc_affinity_out_bytes(std::max(N, 1), G, want);
+    c->last_af_ms[2] = 0.f;
+    if ((rc = slab_begin(c, run, c->last_af_ms))) return rc;
+    if (N <= 1) return c->h_af.ensure(out_bytes);
+    const size_t tab_bytes = pc_affinity_table_bytes(N, G), need = tab_bytes + (want ? out_bytes : 0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
+    const size_t may = (free_b + c->b_af_tab.cap + c->b_af_out.cap) / 2;
+    if (need > may) {
+        pc_set_error("%s: the table of %d genomes x %d groups takes %zu bytes on the device (pc_affinity_bytes%s), above the %zu it may take (half of the free HBM)",
+                     run.who, N, G, need, want ? " and its copy for want_table" : "", may);
+        return PC_ERR_LIMIT;
+    }
+    if ((rc = c->h_af.ensure(out_bytes))) return rc;
+    if ((rc = c->b_af_tab.ensure(tab_bytes)) || (rc = c->b_af_out.ensure(out_bytes))) return abi_rc(rc);
+    if ((rc = slab_size(c, run))) return rc;
+    // member: the genomes sorted by (group, index); goff: each group's run
+    std::vector<int32_t> goff((size_t)G + 1, 0), member((size_t)N), bounds;
+    for (int g = 0; g < N; ++g) ++goff[(size_t)run.group[g] + 1];
+    for (int b = 0; b < G; ++b) goff[(size_t)b + 1] += goff[b];
+    { std::vector<int32_t> at(goff.begin(), goff.end() - 1); for (int g = 0; g < N; ++g) member[(size_t)at[run.group[g]]++] = g; }
+    const int blocks = (N + PC_AFFINITY_BLOCK - 1) / PC_AFFINITY_BLOCK;
+    affinity_ranges(goff, G, N, (16 * c->n_cu + blocks - 1) / blocks, bounds);      // about sixteen waves per compute unit over the whole grid
+    c->af_ranges = (int)bounds.size() - 1;
+    if ((rc = upload_raw(c->b_af_group, run.group, (size_t)N * 4)) || (rc = upload_vec(c->b_af_member, member)) || (rc = upload_vec(c->b_af_goff, goff)) ||
+        (rc = upload_vec(c->b_af_range, bounds))) return rc;
+    return pc_launch_affinity_init(c->b_af_tab.p, N, G, c->stream);
+}
+// the two passes' times of the pending slab: events 0, 1 and 4
+static int affinity_add_pass_times(pc_ctx* c, const PcSlabRun& run) {
+    if (!run.timed || !run.pending) return PC_OK;
+    float x = 0.f, y = 0.f;
+    PC_HIP(hipEventElapsedTime(&x, c->ev_slab[0], c->ev_slab[1]));
+    PC_HIP(hipEventElapsedTime(&y, c->ev_slab[1], c->ev_slab[4]));
+    c->last_af_ms[0] += x; c->last_af_ms[2] += y;
+    return PC_OK;
+}
+// (there is no rows form: a rows slab is refused)
+int PcAffinityFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    if (dom.is_rows) { pc_set_error("%s: an affinity fill has no rows form", run.who); return PC_ERR_ARG; }
+    if (c->h_owned.empty() || c->h_owned.back() - c->h_owned.front() + 1 != dom.shard.nown) { pc_set_error("%s: a slab of targets that are not consecutive", run.who); return PC_ERR_ARG; }
+    int rc = PC_OK;
+    hipStream_t st = c->stream;
+    const int N = c->dev.N, G = run.n_groups, t0 = c->h_owned.front();
+    if ((rc = affinity_add_pass_times(c, run))) return rc;                  // (the walk has waited for the slab before: its events can be read)
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[0], st));
+    if ((rc = pc_launch_affinity_rows(slab, Lp, dom.shard, t0, N, c->b_af_group.as<int32_t>(), G, c->b_af_tab.p, st))) return rc;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[1], st));
+    if ((rc = pc_launch_affinity_cols(slab, Lp, dom.shard, t0, N, c->b_af_member.as<int32_t>(), c->b_af_goff.as<int32_t>(), c->b_af_range.as<int32_t>(),
+                                      c->af_ranges, G, c->b_af_tab.p, st))) return rc;
+    if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[4], st));
+    run.pending = true;
+    return mark_work(c, st);
+}
+int PcAffinityFill::end(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N, G = run.n_groups, want = run.want_table ? 1 : 0;
+    const PcAffinityOut h = pc_affinity_out_view(c->h_af.p, std::max(N, 1), G, want);
+    run.af_own_sum = (const int64_t*)h.own_sum; run.af_own_lo = h.own_lo; run.af_own_hi = h.own_hi; run.af_near_group = h.near_group;
+    run.af_near_sum = (const int64_t*)h.near_sum; run.af_near_lo = h.near_lo; run.af_near_hi = h.near_hi;
+    run.af_tab_sum = (const int64_t*)h.tab_sum; run.af_tab_lo = h.tab_lo; run.af_tab_hi = h.tab_hi;
+    if (N <= 1) {                                                           // no pair: every entry empty, no other group
+        if (N == 1) {
+            h.own_sum[0] = h.near_sum[0] = 0; h.own_lo[0] = h.near_lo[0] = INT32_MAX; h.own_hi[0] = h.near_hi[0] = -1;
+            h.near_group[0] = h.near_group[1] = h.near_group[2] = -1;
+            for (int b = 0; want && b < G; ++b) { h.tab_sum[b] = 0; h.tab_lo[b] = INT32_MAX; h.tab_hi[b] = -1; }
+        }
+        return PC_OK;
+    }
+    const bool cols_pending = run.timed && run.pending;
+    if ((rc = slab_finish(c, run, c->last_af_ms, c->h_af.p, c->b_af_out.p, pc_affinity_out_bytes(N, G, want), [&](hipStream_t st) {
+            return pc_launch_affinity_finish(c->b_af_tab.p, c->b_af_group.as<int32_t>(), c->b_af_goff.as<int32_t>(), N, G, run.bt_invert, c->b_af_out.p, want, st);
+        }))) return rc;
+    if (cols_pending) { float y = 0.f; PC_HIP(hipEventElapsedTime(&y, c->ev_slab[1], c->ev_slab[4])); c->last_af_ms[2] += y; }
+    if (*h.bad) {
+        pc_set_error("%s: %llu values of the fill are no millionth in [0, 1]: the table is not defined on them", run.who, *h.bad);
+        return PC_ERR_DATA;
+    }
+    return PC_OK;
+}
+// Several devices: a device ships its raw table, 16 N G + 8 bytes, and the root combines the staged ones into its own in one launch
+// (k_aff_merge) before it finishes: a pair lies in exactly one stretch, so nothing is counted twice.
+size_t PcAffinityFill::ship_bytes(const pc_ctx* root, const PcSlabRun& run) { return pc_affinity_table_bytes(root->dev.N, run.n_groups); }
+int PcAffinityFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int) {
+    int rc = PC_OK;
+    const size_t bytes = pc_affinity_table_bytes(c->dev.N, run.n_groups);
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, (char*)stage + (size_t)slot * bytes, c->b_af_tab.p, bytes))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
+    return PC_OK;
+}
+int PcAffinityFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if ((rc = pc_launch_affinity_merge(root->b_af_tab.p, stage, n_foreign, root->dev.N, runs[0].n_groups, root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
+    return PC_OK;
+}
+
+extern "C" int pc_fill_affinity(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, int want_table, int64_t slab_bytes,
+                                const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                                const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                                const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_affinity"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.want_table = want_table != 0; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcAffinityFill>(run, {own_sum, own_lo, own_hi, near_group, near_sum, near_lo, near_hi, tab_sum, tab_lo, tab_hi, n_slabs}, stats,
+                                        [&] { return pc_slab_fill<PcAffinityFill>(c, run); });
+}
+
+extern "C" int pc_last_affinity_times(const pc_ctx* c, float* ms_rows, float* ms_cols, float* ms_finish) {
+    if (!c) { pc_set_error("pc_last_affinity_times: NULL context"); return PC_ERR_ARG; }
+    if (ms_rows) *ms_rows = c->last_af_ms[0];
+    if (ms_cols) *ms_cols = c->last_af_ms[2];
+    if (ms_finish) *ms_finish = c->last_af_ms[1];
+    return PC_OK;
+}
 
 // ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest grow a STORED result.  The pairs of the call are
 // those that touch a query genome (the new genomes of a grown collection): k query rows cost k N pairs, not N^2 / 2.  What is stored

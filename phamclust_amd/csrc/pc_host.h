@@ -140,6 +140,12 @@ struct pc_ctx {
     DevBuf b_bt_group, b_bt_acc, b_bt_out;
     PinnedBuf h_bt;                         // the four arrays lent out by pc_fill_between
     float last_bt_ms[2] = {0.f, 0.f};       // passes, fold of the last pc_fill_between with stats (pc_last_between_times)
+    // pc_fill_affinity: group[N], member[N] (the genomes sorted by (group, index)), goff[G + 1], the column pass's group ranges, the resident
+    // table (pc_affinity_table_bytes) and the result (pc_affinity_out_bytes: pc_common.h), the result's pinned host image
+    DevBuf b_af_group, b_af_member, b_af_goff, b_af_range, b_af_tab, b_af_out;
+    PinnedBuf h_af;                         // the arrays lent out by pc_fill_affinity
+    int af_ranges = 0;                      // group ranges of the column pass (b_af_range holds af_ranges + 1 bounds)
+    float last_af_ms[3] = {0.f, 0.f, 0.f};  // row passes, finish, column passes of the last pc_fill_affinity with stats (pc_last_affinity_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -248,16 +254,16 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
-// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree / pc_fill_between, and pc_multi_fill_* over several devices) is ONE description of the
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree / pc_fill_between / pc_fill_affinity, and pc_multi_fill_* over several devices) is ONE description of the
 // fill -- a struct of static functions, declared here and defined in pc_fill_slabs.hip (the launchers of its kernels live in pc_edges.hip,
-// pc_components.hip, pc_nearest.hip, pc_tree.hip and pc_between.hip) -- handed as a template argument to the drivers:
+// pc_components.hip, pc_nearest.hip, pc_tree.hip, pc_between.hip and pc_affinity.hip) -- handed as a template argument to the drivers:
 //   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
 //   pc_slab_stretch<Fill>   the walk over the targets [ta, tb): the slab cut, each slab filled and handed to Fill::slab
 //   multi_slab_fill<Fill>   (pc_multi.hip) begin -> walk(its stretch) -> ship on every device, then merge -> end on the root
 //   pc_rows_slab_fill<Fill> (pc_fill_slabs.hip) a rows form: check -> rows -> Seed::pack -> begin -> Seed::install -> walk the query rows -> end
 // and every extern "C" entry point is its signature, the fields of the run that are its own, and pc_slab_call<Fill> around one of them.
 // What a description says:
-//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut / PcTableOut), which can be
+//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut / PcTableOut / PcGenomeTableOut), which can be
 //           cleared, say whether all are there, and take their values from a finished run
 //   Seed    what a stored result is to the fill (the rows forms): the caller's seed arguments; pack() checks them and packs them into host
 //           memory the call owns, BEFORE begin (the caller may hand back arrays an earlier call lent out, which begin rewrites);
@@ -273,16 +279,17 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //           nothing travels between devices), and how the root takes the others' state in before its end
 // For N <= 1 begin and the walk do nothing on the device.  PcSlabRun is the call as its entry point was given it (pc_slab_check
 // refuses in the public calls' order, folds the metric, normalises the flags and settles kk), its working state, and its results.
-enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE, PC_SLAB_BETWEEN };
+enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE, PC_SLAB_BETWEEN, PC_SLAB_AFFINITY };
 struct PcSlabRun {
     PcSlabKind kind = PC_SLAB_EDGES;
     const char* who = "";                   // the entry point, for the message texts
     bool outputs = false;                   // every output pointer was there
     int metric = 0, as_distance = 0, strict = 0, k = 0;
     double threshold = 0.0;                 // (nearest: none, stays 0)
-    const int32_t* group = nullptr;         // between: the caller's labels, host memory, [N]
+    const int32_t* group = nullptr;         // between, affinity: the caller's labels, host memory, [N]
     int n_groups = 0;                       // ... and their range
-    bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold inverts
+    bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold / finish inverts
+    bool want_table = false;                // affinity: the whole [N][n_groups] table is delivered beside the O(N) arrays
     int64_t slab_bytes = 0;
     bool timed = false;                     // the caller asked for stats: events around the passes over a slab
     int kk = 0;                             // nearest: min(k, N - 1), at least 0 (pc_slab_check)
@@ -297,6 +304,9 @@ struct PcSlabRun {
     int32_t n_components = 0;
     const int64_t *bt_sum = nullptr, *bt_cnt = nullptr;     // between: the four [n_groups][n_groups] arrays
     const int32_t *bt_lo = nullptr, *bt_hi = nullptr;
+    const int64_t *af_own_sum = nullptr, *af_near_sum = nullptr, *af_tab_sum = nullptr;      // affinity: [N] / [N] / [N][n_groups] or NULL
+    const int32_t *af_own_lo = nullptr, *af_own_hi = nullptr, *af_near_group = nullptr, *af_near_lo = nullptr, *af_near_hi = nullptr;
+    const int32_t *af_tab_lo = nullptr, *af_tab_hi = nullptr;
     int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
@@ -304,7 +314,7 @@ struct PcSlabRun {
 // The output shapes and the seeds are hidden, and pc_slab_call is static: however their members are inlined, the library's list of
 // dynamic symbols stays what it was before they had names.
 #pragma GCC visibility push(hidden)
-// The four output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
+// The five output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
 template <class Count> struct PcEdgeOut {
     const int32_t **src, **tgt; const double** val; Count* n_edges; int32_t* n_slabs;
     bool all() const { return src && tgt && val && n_edges && n_slabs; }
@@ -328,6 +338,21 @@ struct PcTableOut {
     bool all() const { return sum && count && lo && hi && n_slabs; }
     void clear() const { if (sum) *sum = nullptr; if (count) *count = nullptr; if (lo) *lo = nullptr; if (hi) *hi = nullptr; if (n_slabs) *n_slabs = 0; }
     void take(const PcSlabRun& run) const { *sum = run.bt_sum; *count = run.bt_cnt; *lo = run.bt_lo; *hi = run.bt_hi; *n_slabs = run.n_slabs; }
+};
+struct PcGenomeTableOut {
+    const int64_t** own_sum; const int32_t **own_lo, **own_hi, **near_group; const int64_t** near_sum; const int32_t **near_lo, **near_hi;
+    const int64_t** tab_sum; const int32_t **tab_lo, **tab_hi; int32_t* n_slabs;
+    bool all() const { return own_sum && own_lo && own_hi && near_group && near_sum && near_lo && near_hi && tab_sum && tab_lo && tab_hi && n_slabs; }
+    void clear() const {
+        if (own_sum) *own_sum = nullptr; if (own_lo) *own_lo = nullptr; if (own_hi) *own_hi = nullptr; if (near_group) *near_group = nullptr;
+        if (near_sum) *near_sum = nullptr; if (near_lo) *near_lo = nullptr; if (near_hi) *near_hi = nullptr;
+        if (tab_sum) *tab_sum = nullptr; if (tab_lo) *tab_lo = nullptr; if (tab_hi) *tab_hi = nullptr; if (n_slabs) *n_slabs = 0;
+    }
+    void take(const PcSlabRun& run) const {
+        *own_sum = run.af_own_sum; *own_lo = run.af_own_lo; *own_hi = run.af_own_hi; *near_group = run.af_near_group;
+        *near_sum = run.af_near_sum; *near_lo = run.af_near_lo; *near_hi = run.af_near_hi;
+        *tab_sum = run.af_tab_sum; *tab_lo = run.af_tab_lo; *tab_hi = run.af_tab_hi; *n_slabs = run.n_slabs;
+    }
 };
 // The seeds: the caller's arguments first (an entry point brace-initialises them), then what pack() made of them.
 struct PcNoSeed {                           // edges: a stored list needs nothing on the device, the caller merges the two lists
@@ -367,6 +392,7 @@ PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill", 
 PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill", PC_SLAB_NEAREST, PcListOut, PcNearestSeed);
 PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill", PC_SLAB_TREE, PcEdgeOut<int32_t>, PcTreeSeed);
 PC_SLAB_FILL(PcBetweenFill, PcSlabDomain, "between", "a between-groups fill", PC_SLAB_BETWEEN, PcTableOut, PcNoSeed);
+PC_SLAB_FILL(PcAffinityFill, PcSlabDomain, "affinity", "an affinity fill", PC_SLAB_AFFINITY, PcGenomeTableOut, PcNoSeed);
 #undef PC_SLAB_FILL
 // What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into
 // the run (whose call fields the entry point has set), drive(), and on PC_OK the results into the outputs and the run's own stats

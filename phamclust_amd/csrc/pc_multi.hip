@@ -15,7 +15,7 @@
 // partition by itself), and ONE exchange -- every device copies its shard to the root's gather buffer, device to device (peer
 // copies: xGMI between the GPUs of a node) -- before the root permutes the shards into condensed order and delivers them to the
 // host.  The reference spreads the same pair list over `cpus` worker processes (matrix.py:471-493).
-// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest / _tree / _between, at the end of this file) deal contiguous
+// The fills that deliver no dense matrix (pc_multi_fill_edges / _components / _nearest / _tree / _between / _affinity, at the end of this file) deal contiguous
 // stretches of targets instead, one per device, and merge the devices' small per-genome state on the root.
 // ---------------------------------------------------------------------------------------------------------------------
 struct pc_multi {
@@ -211,7 +211,7 @@ extern "C" int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Edge, component, nearest, tree and between-groups fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
+// Edge, component, nearest, tree, between-groups and affinity fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
 // (pc_host.h, pc_fill_slabs.hip).  Each device runs the description's begin and the walk over ONE contiguous stretch of targets with
 // the call's state on its own device, and ships that state to the root; the state merges exactly -- lists by their total order,
 // forests by uniting g with its foreign parent, edge lists over ascending stretches by concatenation -- so the root's end delivers
@@ -340,6 +340,16 @@ extern "C" int pc_multi_fill_between(pc_multi* m, int metric, int as_distance, c
     PcSlabRun run; run.who = "pc_multi_fill_between"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
     run.slab_bytes = slab_bytes;
     return pc_slab_call<PcBetweenFill>(run, {sum, count, lo, hi, n_slabs}, stats, [&] { return multi_slab_fill<PcBetweenFill>(m, run, stats); });
+}
+
+extern "C" int pc_multi_fill_affinity(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int want_table, int64_t slab_bytes,
+                                      const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                                      const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                                      const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_multi_fill_affinity"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.want_table = want_table != 0; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcAffinityFill>(run, {own_sum, own_lo, own_hi, near_group, near_sum, near_lo, near_hi, tab_sum, tab_lo, tab_hi, n_slabs}, stats,
+                                        [&] { return multi_slab_fill<PcAffinityFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds) {

@@ -78,7 +78,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_multi_last_stretches", "pc_multi_last_slab_times", "pc_stretch_plan", "pc_fill_tree", "pc_multi_fill_tree", "pc_last_tree_times",
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
-           "pc_between_max_groups", "pc_between_segment"]
+           "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
+           "pc_affinity_block", "pc_affinity_bytes"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -178,6 +179,14 @@ def load():
     L.pc_last_between_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_between_max_groups.argtypes = []
     L.pc_between_segment.argtypes = []
+    L.pc_fill_affinity.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                   ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                   ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                   ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_affinity_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_affinity_block.argtypes = []
+    L.pc_affinity_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    L.pc_affinity_bytes.restype = ctypes.c_int64
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -209,6 +218,7 @@ def load():
     L.pc_multi_fill_nearest.argtypes = L.pc_fill_nearest.argtypes
     L.pc_multi_fill_tree.argtypes = L.pc_fill_tree.argtypes
     L.pc_multi_fill_between.argtypes = L.pc_fill_between.argtypes
+    L.pc_multi_fill_affinity.argtypes = L.pc_fill_affinity.argtypes
     L.pc_multi_last_stretches.argtypes = [vp, _i32p]
     L.pc_multi_last_slab_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_stretch_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_int, _i32p]
@@ -306,7 +316,7 @@ class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
 
 
 class _SlabFills:
-    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` / ``fill_between`` -- the fills that deliver no dense matrix -- once for :class:`Context`
+    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` / ``fill_between`` / ``fill_affinity`` -- the fills that deliver no dense matrix -- once for :class:`Context`
     and :class:`MultiContext`.  The class supplies ``_SLAB_CALL`` (the prefix of the library's symbols), ``_before_slab_fill(metric)``
     (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
     dict of such a fill)."""
@@ -391,6 +401,60 @@ class _SlabFills:
         n_groups = int(n_groups)
         pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
         return self._fill_table(self._SLAB_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, int(slab_bytes)), n_groups, want_stats, borrow)
+
+    def fill_affinity(self, metric, group, n_groups=None, as_distance=True, slab_bytes=0, want_table=False, want_stats=False, borrow=False):
+        """How every genome relates to every group of a partition (``group`` / ``n_groups`` as :meth:`fill_between` takes them), in
+        MILLIONTHS of the whole distance fill's values and without the dense matrix.  Returns a dict of arrays: ``own_sum`` (int64),
+        ``own_lo``, ``own_hi`` (int32) ``[N]`` -- sum, minimum and maximum of a genome's values to the OTHER members of its own group;
+        ``near_group`` (int32 ``[3, N]``) -- the other non-empty group nearest by 0: smallest mean, 1: smallest minimum, 2: smallest
+        maximum (ties to the smaller index, -1: none) -- with ``near_sum`` (int64), ``near_lo``, ``near_hi`` (int32) ``[N]``, the value
+        that made it nearest; and ``table``: None, or with ``want_table=True`` the whole ``(sum, lo, hi)`` of ``[N, G]`` arrays.  The
+        count of entry ``[g, b]`` is ``size[b] - (group[g] == b)``; an entry no pair falls into reads ``0, 2**31 - 1, -1``.  The N x G
+        table stays on the device (:meth:`affinity_bytes`; refused above half of the free HBM); only the O(N) arrays cross PCIe unless
+        the table is asked for.  ``as_distance=False``: the statement of the inverted matrix -- the same nearest groups, every value
+        complemented (``matrix.GroupAffinity.inverted``).  Integers, so the result is exact whatever the slab cut or the number of
+        devices.  ``borrow`` as for :meth:`fill_between`; ``want_stats`` adds ``stats`` to the dict: the fills' summed stats with
+        ``n_groups``, ``n_slabs``, ``ms_rows``, ``ms_cols`` and ``ms_finish`` (a :class:`MultiContext`: the route's own entries)."""
+        if group is None:
+            raise ValueError("fill_affinity: group is None")
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        if group.shape[0] != self.n_genomes:
+            raise ValueError(f"fill_affinity: group holds {group.shape[0]} labels for {self.n_genomes} genomes")
+        if n_groups is None:
+            n_groups = int(group.max()) + 1 if group.size else 1
+        n_groups, n = int(n_groups), self.n_genomes
+        pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
+        cells = [t() for t in (_i64p, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p, _i64p, _i32p, _i32p)]
+        nsl = ctypes.c_int32(0)
+        stats = self._slab_call(self._SLAB_CALL + "affinity", metric, int(bool(as_distance)), pgroup, n_groups, int(bool(want_table)), int(slab_bytes),
+                                *(ctypes.byref(c) for c in cells), ctypes.byref(nsl))
+        names = ("own_sum", "own_lo", "own_hi", "near_group", "near_sum", "near_lo", "near_hi")
+        dtypes = (np.int64, np.int32, np.int32, np.int32, np.int64, np.int32, np.int32)
+        out = {}
+        for name, cell, dtype in zip(names, cells, dtypes):
+            shape = (3, n) if name == "near_group" else (n,)
+            out[name] = self._lend(cell, shape, borrow) if n and cell else np.empty(shape, dtype=dtype)
+        out["table"] = None
+        if want_table:
+            out["table"] = tuple(self._lend(cell, (n, n_groups), borrow) if n and cell else np.empty((n, n_groups), dtype=dtype)
+                                 for cell, dtype in zip(cells[7:], (np.int64, np.int32, np.int32)))
+        if want_stats:
+            out["stats"] = self._slab_stats("affinity", stats, n_groups=n_groups, n_slabs=int(nsl.value))
+        return out
+
+    @staticmethod
+    def affinity_block():
+        """Consecutive sources one wave of the affinity fill's column pass takes (``pc_affinity_block``; host arithmetic, no GPU)."""
+        return int(load().pc_affinity_block())
+
+    @staticmethod
+    def affinity_bytes(n, n_groups):
+        """Bytes of the table an affinity fill of ``n`` genomes in ``n_groups`` groups keeps on the device (``pc_affinity_bytes``: 16 per
+        entry and an 8-byte counter; host arithmetic, no GPU)."""
+        b = int(load().pc_affinity_bytes(int(n), int(n_groups)))
+        if b < 0:
+            raise ValueError(f"affinity_bytes: {n} genomes x {n_groups} groups")
+        return b
 
     def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
@@ -680,7 +744,8 @@ class Context(_SlabFills):
     # -- fill_edges / fill_components / fill_nearest / fill_tree (_SlabFills): what this class supplies ----------------------------------
     _SLAB_CALL = "pc_fill_"
     _SLAB_TIMES = {"edges": ("pc_last_edge_times", "ms_compact", "ms_d2h"), "components": ("pc_last_component_times", "ms_union", "ms_labels"),
-                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish"), "between": ("pc_last_between_times", "ms_reduce", "ms_finish")}
+                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish"), "between": ("pc_last_between_times", "ms_reduce", "ms_finish"),
+                   "affinity": ("pc_last_affinity_times", "ms_rows", "ms_cols", "ms_finish")}
     TREE_MAX_GENOMES = 1 << 22            # PC_TREE_MAX_GENOMES: a genome index takes 22 bits of a tree key
     BETWEEN_MAX_GROUPS = 2048             # PC_BETWEEN_MAX_GROUPS: the pass keeps one entry per group in LDS
 
@@ -716,11 +781,11 @@ class Context(_SlabFills):
         return PcStats()
 
     def _slab_stats(self, kind, stats, **own):
-        """The stats dict of such a fill: the fills' summed stats, the call's counts and the kind's two times."""
-        call, first, second = self._SLAB_TIMES[kind]
-        a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
-        self._check(getattr(self._lib, call)(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return dict(stats.as_dict(), **own, **{first: float(a.value), second: float(b.value)})
+        """The stats dict of such a fill: the fills' summed stats, the call's counts and the kind's two times (affinity: three)."""
+        call, *names = self._SLAB_TIMES[kind]
+        times = [ctypes.c_float(0.0) for _ in names]
+        self._check(getattr(self._lib, call)(self._h, *(ctypes.byref(t) for t in times)))
+        return dict(stats.as_dict(), **own, **{name: float(t.value) for name, t in zip(names, times)})
 
     NEAREST_MAX_K = 64                    # PC_NEAREST_MAX_K: a genome's list lives one entry per lane of a wave
 

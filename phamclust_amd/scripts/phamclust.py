@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, GroupLinkage, SparseEdges, SymMatrix, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -492,6 +492,60 @@ class _Run:
                 draw_heatmap(square, colors=self.colors, midpoint=1.0 - clu_distance, filename=self.stage / f"cluster_{self.metric}_heatmap.{suffix}")
         return table
 
+    # 4c, --cluster-fit
+    def cluster_fit(self, groups):
+        """One affinity fill over the final clusters (``groups`` as ``cluster_table`` takes them) into the staging directory:
+        ``cluster_fit_<metric>.tsv``, one line per genome in cluster order -- its cluster, its mean similarity to its own cluster, the
+        nearest other cluster by mean and that mean, its silhouette, whether it is its cluster's medoid -- and
+        ``cluster_fit_<metric>_summary.tsv``, one line per cluster: size, medoid, mean silhouette, largest own distance.  The fill runs
+        where ``cluster_table``'s does; the numbers are exact integers on every route, so the files are the same on all of them."""
+        self.banner("4c", f"{self.metric} cluster fit (affinity fill)")
+        t0 = time.perf_counter()
+        if len(groups) > _matrix.BETWEEN_MAX_GROUPS:
+            log.warning(f"--cluster-fit: {len(groups):,} clusters and singletons are above the fill's {_matrix.BETWEEN_MAX_GROUPS:,} groups: "
+                        f"no cluster fit is written")
+            return None
+        multi = sum(1 for group in groups if len(group) > 1)
+        names = [f"cluster_{k + 1}" if k < multi else group[0] for k, group in enumerate(groups)]
+        if self.fills is not None:
+            ctx, metric, genome_names = self.fills
+            index = {name: k for k, name in enumerate(genome_names)}
+            label = np.zeros(len(genome_names), dtype=np.int32)
+            for k, group in enumerate(groups):
+                label[[index[name] for name in group]] = k
+            found = ctx.fill_affinity(metric, label, len(groups), as_distance=True, want_stats=True)
+            st = found.pop("stats")
+            found.pop("table")
+            fit = GroupAffinity(genome_names, groups, **found, is_distance=True)
+        else:
+            fit = affinity_de_novo(self.genomes, METRICS[self.metric], groups, as_distance=True)
+            st = _matrix.LAST_FILL
+        log.info(f"{len(fit):,} genomes x {len(groups):,} clusters and singletons from {st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in "
+                 f"{time.perf_counter() - t0:.3f} s (kernels {st.get('ms_total', 0.0):.3f} ms, row passes {st.get('ms_rows', 0.0):.3f} ms, column passes "
+                 f"{st.get('ms_cols', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
+        at = {name: k for k, name in enumerate(fit.nodes)}
+        silhouette, medoids, by_group = fit.silhouette(), fit.medoids(), fit.silhouette_by_group()
+        similar = fit.inverted()                                            # (similarities from the integers, as every output of the run)
+        near, near_mean = fit.nearest_group("mean"), similar.nearest_value("mean")
+
+        def text(value):
+            return "nan" if value != value else repr(float(value))
+
+        with open(self.stage / f"cluster_fit_{self.metric}.tsv", "w") as handle:
+            handle.write("genome\tcluster\town_similarity\tnearest_cluster\tnearest_similarity\tsilhouette\tmedoid\n")
+            for b, group in enumerate(groups):
+                for name in group:
+                    k = at[name]
+                    handle.write(f"{name}\t{names[b]}\t{text(similar.own_mean(name))}\t{names[near[k]] if near[k] >= 0 else 'none'}\t{text(near_mean[k])}\t"
+                                 f"{text(silhouette[k])}\t{int(medoids[b] == name)}\n")
+        with open(self.stage / f"cluster_fit_{self.metric}_summary.tsv", "w") as handle:
+            handle.write("cluster\tsize\tmedoid\tmean_silhouette\tlargest_own_distance\n")
+            for b, group in enumerate(groups):
+                worst = max(int(fit.own_hi[at[name]]) for name in group)
+                handle.write(f"{names[b]}\t{len(group)}\t{medoids[b]}\t{text(by_group[b])}\t{'nan' if worst < 0 else f'{worst / 1.0e6:.6f}'}\n")
+        log.info(f"mean silhouette of the {len(groups):,} clusters and singletons: {text(fit.silhouette_mean())}")
+        return fit
+
     # 5 + 6
     def finish(self, matrix, multi, single, clu_distance, rm_tmp):
         self.banner(5, "dataset outputs")
@@ -537,7 +591,7 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, grow_nearest=None, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -550,7 +604,10 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     an earlier run wrote over a subset of the genomes (``--grow``): only the pairs of the genomes it lacks are filled, on one GPU;
     ``grow_nearest``: with ``nearest``, the ``nearest_<metric>.tsv`` of an earlier run over a subset of the genomes (``--grow-nearest``),
     grown the same way; ``cluster_table``: after the clustering, one between-groups fill over the final clusters and its three outputs
-    (``--cluster-table``; with the whole pipeline only, on either route)."""
+    (``--cluster-table``; with the whole pipeline only, on either route); ``cluster_fit``: after the clustering, one affinity fill over the
+    final clusters and its two files (``--cluster-fit``; on the same terms)."""
+    if cluster_fit and (adjacency_only or components_only or tree or nearest is not None or extend is not None):
+        raise ValueError("cluster_fit cannot be combined with adjacency_only, components_only, tree, nearest or extend")
     if cluster_table and (adjacency_only or components_only or tree or nearest is not None or extend is not None):
         raise ValueError("cluster_table cannot be combined with adjacency_only, components_only, tree, nearest or extend")
     if grow_nearest is not None and (nearest is None or grow is not None):
@@ -596,6 +653,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["tree"] = "only (single-linkage dendrogram)"
     if cluster_table:
         settings["clusters"] = "with their table (--cluster-table: a between-groups fill)"
+    if cluster_fit:
+        settings["cluster fit"] = "written (--cluster-fit: an affinity fill)"
     if grow is not None:
         settings["grow"] = grow
     if grow_nearest is not None:
@@ -641,6 +700,9 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     if cluster_table and run.world > 1:
         log.error("--cluster-table is a one-process call: run it in one process, not under a launcher")
         sys.exit(1)
+    if cluster_fit and run.world > 1:
+        log.error("--cluster-fit is a one-process call: run it in one process, not under a launcher")
+        sys.exit(1)
     matrix = None
     if no_matrix:
         if run.world > 1:
@@ -665,6 +727,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             run.by_name[name].save(lone / f"{name}.faa")
     if cluster_table:
         run.cluster_table(final_groups, clu_distance)
+    if cluster_fit:
+        run.cluster_fit(final_groups)
     if no_matrix:
         run.finish_no_matrix(rm_tmp)
     else:
@@ -705,6 +769,8 @@ def gpus_plan(args, route, packed):
         return 1, "one", "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
     if route == "launcher" and getattr(args, "cluster_table", False):
         return 1, "one", "--cluster-table fills the clusters' table from one process: the matrix stage stays on one GPU"
+    if route == "launcher" and getattr(args, "cluster_fit", False):
+        return 1, "one", "--cluster-fit fills the genomes' affinity to the clusters from one process: the matrix stage stays on one GPU"
     if route == "launcher":
         for attr, flag, what in SLAB_FILL_FLAGS:
             if getattr(args, attr) not in (None, False):
@@ -796,7 +862,8 @@ def _run(args, argv):
                   no_sub=args.no_sub, colors=_colors(args.heatmap_colors), midpoint=round(args.heatmap_midpoint, 6),
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
-                  nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table)
+                  nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
+                  cluster_fit=args.cluster_fit)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
