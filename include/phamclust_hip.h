@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 165   /* 0.5.14: pc_fill_affinity, pc_multi_fill_affinity, pc_last_affinity_times, pc_affinity_block, pc_affinity_bytes */
+#define PC_VERSION 166   /* 0.5.15: pc_hook_slab_values, pc_affinity_ranges (test hooks); an affinity fill's refusal counts each value once */
 
 typedef enum {
     PC_OK = 0,
@@ -90,6 +90,17 @@ const char* pc_last_error(void);
 /* 1 in a library compiled with -DPC_TEST_HOOKS (libphamclust_hip_hooks.so: fault injection for the tests, see the knob table
  * at the end of this header), 0 in the release library. */
 int pc_test_hooks(void);
+/* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 166): values, the whole triangle of the uploaded collection as
+ * n_pairs = N (N - 1) / 2 doubles in the slab walk's own order -- target-major: element t (t - 1) / 2 + s is the pair (s, t), s < t --
+ * stands for "the slab as filled" in every triangular slab walk of the process from now on: pc_fill_edges, _components, _nearest, _tree,
+ * _between, _affinity and their pc_multi_ forms.  The fill still runs (the uploaded collection only sets N); each slab is then overwritten
+ * with its stretch of the triangle by one host-to-device copy on the walk's stream, in whichever direction the fill ran: between and
+ * affinity always fill distances and invert at the end, the other four fill the direction asked for.  The pointer is stored process-wide,
+ * not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets or clears it
+ * between calls only.  A walk that finds n_pairs != N (N - 1) / 2 refuses with PC_ERR_ARG.  The rows walk (pc_fill_rows_edges,
+ * _components, _tree, _nearest) takes no injection: deliberately out of scope.  PC_ERR_ARG: values with a negative n_pairs.
+ * In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
+int pc_hook_slab_values(const double* values, int64_t n_pairs);
 
 /* One context per GPU.  device_id is the HIP device ordinal. */
 int pc_ctx_create(pc_ctx** out, int device_id);
@@ -330,7 +341,9 @@ int pc_last_nearest_times(const pc_ctx* ctx, float* ms_select, float* ms_finish)
  * 20 + 22 + 22 bits, hence PC_TREE_MAX_GENOMES.  ~0 is no key (its value field is above 10^6).  One unsigned 64-bit minimum is the
  * minimum of the total order, and a forest is an array of keys.  pc_tree_key packs a key and pc_tree_key_parts unpacks one (PC_ERR_ARG
  * for a word that is no key: micro > 10^6 or s >= t; host arithmetic, no GPU, exported for tests as pc_chunk_plan is).  The pass over a
- * slab checks what the key relies on -- 0 <= k <= 10^6 and k / 10^6 == v, bit for bit -- and counts violations: PC_ERR_DATA.
+ * slab checks what the key relies on -- 0 <= k <= 10^6 and k / 10^6 == v (bit for bit; -0.0 is the millionth 0) -- and counts violations: PC_ERR_DATA.  The count
+ * in the message is one of SIGHTINGS, not of values: every Boruvka round scans the slab again and sees only the pairs whose ends lie in
+ * different components, so a refused value is counted once per round that met it (at least once, unless its ends were joined before).
  * Same walk as pc_fill_edges: the same slab cut (pc_chunk_plan over count[t] = t, slab_bytes / 8 pairs, <= 2^31-1; 0 = automatic),
  * each slab filled as a shard into the resident slab buffer.  MST(A + B) = MST(MST(A) + B): a forest of at most N - 1 keys stays on
  * the device across the slabs, and per slab Boruvka rounds run over that forest and the slab (ceil(log2 N) rounds are enqueued; a
@@ -367,7 +380,7 @@ int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
  * genome cap); the diagonal holds each group's diameter and mean.  A value enters as its millionths, micro = rint(v * 1e6), of the
  * DISTANCE as filled: every delivered value is round(x, 6), so sum[a][b] is an integer and lo / hi are integers, and the table is
  * exact: it depends neither on the slab cut, nor on the number of devices, nor on the order of any atomic.  The pass checks what that
- * relies on -- 0 <= micro <= 10^6 and micro / 10^6 == v, bit for bit -- and counts violations: PC_ERR_DATA; such a value is added
+ * relies on -- 0 <= micro <= 10^6 and micro / 10^6 == v (bit for bit; -0.0 is the millionth 0) -- and counts violations: PC_ERR_DATA; such a value is added
  * nowhere.  as_distance == 0 delivers the SIMILARITY table, which is the distance table inverted -- sum' = count * 10^6 - sum, lo' =
  * 10^6 - hi, hi' = 10^6 - lo, by the fold -- i.e. the table of the matrix SymMatrix.invert() (matrix.py:236-247: round(1 - d, 6), the
  * complement of a millionth) makes of the distance matrix, as every similarity the pipeline writes is made.  It is deliberately not
@@ -417,6 +430,8 @@ int pc_between_segment(void);       /* elements of a slab row one workgroup of t
  * pc_fill_between): the nearest groups are chosen on the distances and are the same, every reported value is complemented -- sum' =
  * count * 10^6 - sum, table and own entries lo' = 10^6 - hi, hi' = 10^6 - lo, near_lo' = 10^6 - near_lo, near_hi' = 10^6 - near_hi.
  * All arrays lie in page-locked memory the context owns (pc_fill_borrow's loan rule).  N <= 1: PC_OK, nothing runs on the device.
+ * The two passes each see every element of a slab and each leave a value that is no millionth in [0, 1] out; the row pass alone counts
+ * it, so the count in the PC_ERR_DATA message is the number of such values, as pc_fill_between's is.
  * Refusals as pc_fill_between's, and PC_ERR_LIMIT when the table (with want_table: and its converted copy) takes more than half of the
  * HBM that is free when the call begins; the message carries both numbers.  There is no rows form.
  */
@@ -429,6 +444,12 @@ int pc_fill_affinity(pc_ctx* ctx, int metric, int as_distance, const int32_t* gr
 int pc_last_affinity_times(const pc_ctx* ctx, float* ms_rows, float* ms_cols, float* ms_finish);
 int pc_affinity_block(void);        /* consecutive sources one wave of the column pass takes */
 int64_t pc_affinity_bytes(int64_t n, int64_t n_groups);   /* the resident table: 16 n n_groups + 8; -1: not representable */
+/* Test hook, host arithmetic (PC_VERSION 166): the column pass's cut of the groups into ranges, as the fill makes it from the device's
+ * compute-unit count (want = ceil(16 n_cu / ceil(N / pc_affinity_block()))).  goff[n_groups + 1]: each group's run among the genomes
+ * sorted by (group, index), goff[0] = 0 ascending to goff[n_groups] = N.  Writes the range starts followed by n_groups into
+ * bounds_out[cap] and returns the number of ranges R <= max(1, min(n_groups, want)): R + 1 bounds, strictly ascending (no range is
+ * empty of groups).  cap == 0: only the count.  PC_ERR_ARG: a NULL pointer, n_groups < 1, goff that is no such array, cap too small. */
+int pc_affinity_ranges(const int32_t* goff, int n_groups, int n, int want, int32_t* bounds_out, int cap);
 
 /*
  * The rows forms of the edge-list, components and tree fills: a STORED result grown by new genomes.  rows[n_rows] are the query genomes
@@ -764,6 +785,7 @@ int pc_round6_probe(pc_ctx* ctx, const double* in, double* out, int64_t n);
  *     PC_PIPE=0|n               strip-mined launches: never pipelined (one row per wave) / always, the passes of a row over n <= 8 waves (default: by the launch's size)
  *   only in libphamclust_hip_hooks.so (compiled with -DPC_TEST_HOOKS; pc_test_hooks() == 1)
  *     PC_FAKE_OOM_ABOVE=n       device allocations above n bytes made while a fill is planning fail (fault injection)
+ *     pc_hook_slab_values()     (a call, not a variable) the value triangle that stands for every filled slab of the triangular slab walks
  * The Python package adds PHAMCLUST_DEVICE, PHAMCLUST_DIST_BACKEND, PHAMCLUST_DIST_MODE, PHAMCLUST_DIST_TIMEOUT_S, PHAMCLUST_LAUNCH_COST_S,
  * PHAMCLUST_FORCE_GPUS, PHAMCLUST_NO_TORCH and PHAMCLUST_NATIVE_VARIANT.
  */

@@ -30,7 +30,9 @@
 // of target t; entry (s, a) of k_aff_cols to the wave whose source block holds s and whose group range holds a.  The two passes are
 // separate launches on the fill's stream, so the read-modify-write of an entry is never concurrent with another.
 // What is atomic and why.  In LDS: ds atomics in k_aff_rows -- the lanes of a workgroup hit the same entry whenever two sources share a
-// group.  In HBM: only the violation count (a relaxed agent-scope add, once per wave that found any); the table needs none, as above.
+// group.  In HBM: only the violation count (a relaxed agent-scope add, once per wave of k_aff_rows that found any); the table needs none,
+// as above.  Both passes see every element of a slab and both leave a refused value out, but only the row pass counts it: the count is
+// the number of refused VALUES.
 // Progress: no workgroup waits for another; no flag is spun on.  The loops are a row's (bounded by its length), the table's (G), a
 // group's member run and two binary searches over it.
 // What is read: a row pass reads [lbase[k], lbase[k + 1]) of its row; a column pass reads lbase[k] + s for s < min(t, the row's
@@ -48,7 +50,7 @@ static_assert((size_t)PC_BETWEEN_MAX_GROUPS * 16 <= 65536, "the LDS table of the
 // one value as its contribution: false (and one violation) when it is no millionth in [0, 1] (bt_micro of pc_between.hip)
 __device__ __forceinline__ bool af_micro(double v, uint32_t& micro, uint32_t& bad) {
     const double k = __builtin_rint(v * 1.0e6);
-    if (!(k >= 0.0 && k <= 1.0e6) || __double_as_longlong(pc_div_million(k)) != __double_as_longlong(v)) { ++bad; return false; }
+    if (!(k >= 0.0 && k <= 1.0e6) || pc_div_million(k) != v) { ++bad; return false; }
     micro = (uint32_t)k;
     return true;
 }
@@ -127,7 +129,7 @@ __device__ __forceinline__ int af_lower(const int32_t* __restrict__ member, int 
 // column pass: wave (blockIdx.y * AF_WAVES + wave) of source block blockIdx.x takes the groups [grange[u], grange[u + 1])
 __global__ __launch_bounds__(AF_THREADS) void k_aff_cols(const double* __restrict__ vals, PcShard sh, int t0, int t1, const int32_t* __restrict__ member,
                                                         const int32_t* __restrict__ goff, const int32_t* __restrict__ grange, int n_ranges, int G,
-                                                        PcAffinityEntry* __restrict__ tab, unsigned long long* __restrict__ n_bad) {
+                                                        PcAffinityEntry* __restrict__ tab, unsigned long long* __restrict__ /* n_bad: the row pass's */) {
     const int lane = threadIdx.x & 63;
     const int u = (int)blockIdx.y * AF_WAVES + (int)(threadIdx.x >> 6);
     if (u >= n_ranges) return;                         // (the whole wave)
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(AF_THREADS) void k_aff_cols(const double* __restric
     const int t_first = max(t0, sb + 1);               // the block's first target: above its first source, inside the slab
     if (t_first >= t1) return;                         // (the whole wave)
     const int a0 = grange[u], a1 = grange[u + 1];
-    uint32_t bad = 0;
+    uint32_t bad = 0;                                  // (not reported: the row pass has seen every element of the slab and counted it once)
     for (int a = a0; a < a1; ++a) {
         const int g0 = goff[a], g1 = goff[a + 1];
         const int j0 = af_lower(member, g0, g1, t_first), j1 = af_lower(member, j0, g1, t1);
@@ -163,7 +165,6 @@ __global__ __launch_bounds__(AF_THREADS) void k_aff_cols(const double* __restric
         }
         if (lo != ~0u) af_entry_add(tab + (size_t)s * (size_t)G + a, sum, lo, hi);       // (s < some t < t1 <= N: a row of the table)
     }
-    if (bad) (void)__hip_atomic_fetch_add(n_bad, (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // staged: n_foreign tables of `bytes` each

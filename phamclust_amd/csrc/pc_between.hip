@@ -29,8 +29,9 @@
 // k_between_fold run as launches of their own, after the passes: plain loads and stores, every thread its own entries.
 // Progress: no workgroup ever waits for another; no flag is spun on; nothing sleeps.  The loops are the segment's (bounded by
 // PC_BETWEEN_SEGMENT), the table's (bounded by G) and the wave reduction (six steps).
-// The pass checks what the integers rely on, as pc_tree_pair_key does -- micro lies in [0, 10^6] and pc_div_million(micro) == v bit for
-// bit -- and counts what fails it in the accumulator's violation word (such a value is added nowhere): the host answers a non-zero
+// The pass checks what the integers rely on, as pc_tree_pair_key does -- micro lies in [0, 10^6] and pc_div_million(micro) == v (an f64
+// compare, which is one of bits for everything but the two zeros: -0.0 is a zero, and pc_div_million(-0.0) is +0.0) -- and counts what
+// fails it in the accumulator's violation word (such a value is added nowhere): the host answers a non-zero
 // count with PC_ERR_DATA.
 #include <climits>
 
@@ -46,7 +47,7 @@ static_assert((size_t)PC_BETWEEN_MAX_GROUPS * 16 <= 65536, "the LDS table of the
 // one value as its contribution: false (and one violation) when it is no millionth in [0, 1]
 __device__ __forceinline__ bool bt_micro(double v, uint32_t& micro, uint32_t& bad) {
     const double k = __builtin_rint(v * 1.0e6);
-    if (!(k >= 0.0 && k <= 1.0e6) || __double_as_longlong(pc_div_million(k)) != __double_as_longlong(v)) { ++bad; return false; }
+    if (!(k >= 0.0 && k <= 1.0e6) || pc_div_million(k) != v) { ++bad; return false; }
     micro = (uint32_t)k;
     return true;
 }

@@ -66,6 +66,27 @@ PlanningScope::PlanningScope() {}
 PlanningScope::~PlanningScope() {}
 #endif
 
+// Value injection (pc_hook_slab_values): the triangle a test sets stands for "the slab as filled" in every triangular slab walk of the
+// process (slab_walk, pc_fill_slabs.hip; the rows walk takes none) until it is cleared.  The caller keeps the memory alive.  Set between
+// calls only: the walks of a several-device fill read it from their own threads.  Compiled only under -DPC_TEST_HOOKS; the release library
+// stores nothing and its getter answers NULL.
+#ifdef PC_TEST_HOOKS
+static const double* g_slab_values = nullptr;
+static int64_t g_slab_n_pairs = 0;
+const double* pc_hooked_slab_values(int64_t* n_pairs) { *n_pairs = g_slab_n_pairs; return g_slab_values; }
+extern "C" int pc_hook_slab_values(const double* values, int64_t n_pairs) {
+    if (values && n_pairs < 0) { pc_set_error("pc_hook_slab_values: n_pairs %lld", (long long)n_pairs); return PC_ERR_ARG; }
+    g_slab_values = values; g_slab_n_pairs = values ? n_pairs : 0;
+    return PC_OK;
+}
+#else
+const double* pc_hooked_slab_values(int64_t* n_pairs) { *n_pairs = 0; return nullptr; }
+extern "C" int pc_hook_slab_values(const double*, int64_t) {
+    pc_set_error("pc_hook_slab_values: this library carries no test hooks (libphamclust_hip_hooks.so does)");
+    return PC_ERR_STATE;
+}
+#endif
+
 int DevBuf::ensure(size_t bytes) {
     if (bytes <= cap) return PC_OK;
     if (p) { (void)hipFree(p); p = nullptr; cap = 0; }

@@ -134,6 +134,16 @@ template <class Hook> static int slab_walk(pc_ctx* c, const std::vector<int32_t>
         pc_stats one; memset(&one, 0, sizeof(one));
         if ((rc = fill_impl(c, metric, as_distance, slab, 0, st, sum ? &one : nullptr))) return rc;
         if (sum) pc_stats_add(*sum, one);
+        // test-hooks build only (the release getter answers NULL): the injected triangle stands for the slab as filled
+        int64_t hooked_pairs = 0;
+        if (const double* const hooked = pc_hooked_slab_values(&hooked_pairs)) {
+            if (hooked_pairs != pairs_below(c->dev.N)) {
+                pc_set_error("slab walk: pc_hook_slab_values holds %lld values, the triangle of %d genomes has %lld", (long long)hooked_pairs, c->dev.N,
+                             (long long)pairs_below(c->dev.N));
+                return PC_ERR_ARG;
+            }
+            PC_HIP(hipMemcpyAsync(slab, hooked + pairs_below(t0), (size_t)Lp * 8, hipMemcpyHostToDevice, st));
+        }
         if ((rc = hook(slab, Lp, c->shard))) return rc;
     }
     return PC_OK;
@@ -724,6 +734,18 @@ static void affinity_ranges(const std::vector<int32_t>& goff, int G, int N, int 
         bounds.push_back(a);
     }
     bounds.push_back(G);
+}
+// (test hook, host arithmetic: that cut for a caller's goff[G + 1], goff[0] = 0 ascending to N)
+extern "C" int pc_affinity_ranges(const int32_t* goff, int G, int N, int want, int32_t* bounds_out, int cap) {
+    if (!goff || G < 1 || N < 0 || cap < 0 || (cap > 0 && !bounds_out)) { pc_set_error("pc_affinity_ranges: bad argument"); return PC_ERR_ARG; }
+    if (goff[0] != 0 || goff[G] != N) { pc_set_error("pc_affinity_ranges: goff runs from %d to %d, not from 0 to %d", goff[0], goff[G], N); return PC_ERR_ARG; }
+    for (int b = 0; b < G; ++b)
+        if (goff[b + 1] < goff[b]) { pc_set_error("pc_affinity_ranges: goff descends at group %d", b); return PC_ERR_ARG; }
+    std::vector<int32_t> bounds;
+    affinity_ranges(std::vector<int32_t>(goff, goff + G + 1), G, N, want, bounds);
+    if (cap > 0 && (size_t)cap < bounds.size()) { pc_set_error("pc_affinity_ranges: %zu bounds, room for %d", bounds.size(), cap); return PC_ERR_ARG; }
+    if (cap > 0) memcpy(bounds_out, bounds.data(), bounds.size() * 4);
+    return (int)bounds.size() - 1;
 }
 int PcAffinityFill::begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;

@@ -24,6 +24,9 @@ struct PcRange {
 constexpr int PC_ERR_NOMEM_INTERNAL = -100;
 // marks the planning stage of a fill: the test-hooks build refuses device allocations above PC_FAKE_OOM_ABOVE inside it (pc_ctx.hip)
 struct PlanningScope { PlanningScope(); ~PlanningScope(); };
+// the value triangle pc_hook_slab_values set (target-major, *n_pairs doubles), or NULL: always NULL in the release library (pc_ctx.hip).
+// slab_walk overwrites every slab it has filled with its part of the triangle.  (Not part of the exported set.)
+__attribute__((visibility("hidden"))) const double* pc_hooked_slab_values(int64_t* n_pairs);
 // Grow-only device buffer that owns its memory: freed when it goes out of scope, on whichever device is current then (the
 // context's destruction runs under its device guard).  Move-only, so that a std::vector of them can grow.
 struct DevBuf {

@@ -81,9 +81,10 @@ __device__ __forceinline__ void pc_tree_lower_shared(tree_key_t* best, int c, tr
 }
 
 // the key of pair (s, t) with value v, or none (and one violation) when v is not a millionth in [0, 1]
+// (an f64 compare: of bits for everything but the two zeros -- -0.0 is the millionth 0, and pc_div_million(-0.0) is +0.0)
 template <int DIST> __device__ __forceinline__ tree_key_t pc_tree_pair_key(double v, int s, int t, uint32_t& bad) {
     const double k = __builtin_rint(v * 1.0e6);
-    if (!(k >= 0.0 && k <= 1.0e6) || __double_as_longlong(pc_div_million(k)) != __double_as_longlong(v)) { ++bad; return PC_TREE_NONE; }
+    if (!(k >= 0.0 && k <= 1.0e6) || pc_div_million(k) != v) { ++bad; return PC_TREE_NONE; }
     const int ki = (int)k;
     return pc_tree_key_of(DIST ? ki : PC_TREE_MICRO_MAX - ki, s, t);
 }

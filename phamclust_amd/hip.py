@@ -79,7 +79,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
-           "pc_affinity_block", "pc_affinity_bytes"]
+           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -187,6 +187,8 @@ def load():
     L.pc_affinity_block.argtypes = []
     L.pc_affinity_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     L.pc_affinity_bytes.restype = ctypes.c_int64
+    L.pc_affinity_ranges.argtypes = [_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int]
+    L.pc_hook_slab_values.argtypes = [_f64p, ctypes.c_int64]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -230,6 +232,50 @@ def load():
 
 def _ptr(arr, typ):
     return arr.ctypes.data_as(typ)
+
+
+# -- test hook: the values of the triangular slab walks (libphamclust_hip_hooks.so only) -------------------------------------------
+_slab_values = None                     # the array the library holds a pointer to: kept alive here until it is replaced or cleared
+
+
+def set_slab_values(values):
+    """``pc_hook_slab_values``: ``values`` -- float64, C-contiguous, the whole triangle target-major (:func:`triangle_of`) -- stands
+    for every slab that ``fill_edges`` / ``_components`` / ``_nearest`` / ``_tree`` / ``_between`` / ``_affinity`` of any context of
+    this process fills from now on; ``None`` clears it.  The array is referenced, not copied: do not write to it while it is set.  Only
+    the test-hooks twin (``PHAMCLUST_NATIVE_VARIANT=hooks``) takes it; the release library refuses, and so does this."""
+    global _slab_values
+    lib = load()
+    if values is None:
+        rc = lib.pc_hook_slab_values(None, 0)
+    else:
+        if not (isinstance(values, np.ndarray) and values.dtype == np.float64 and values.ndim == 1 and values.flags.c_contiguous):
+            raise ValueError("set_slab_values: a one-dimensional C-contiguous float64 array, or None")
+        rc = lib.pc_hook_slab_values(_ptr(values, _f64p), int(values.shape[0]))
+    if rc != 0:
+        raise HipLibraryError(f"libphamclust_hip: status {rc}: {lib.pc_last_error().decode()}")
+    _slab_values = values
+
+
+def triangle_of(square):
+    """The triangle the slab walks fill, from a symmetric ``N x N`` array: target-major, element ``t (t - 1) / 2 + s`` the pair
+    ``(s, t)``, ``s < t`` -- the strict lower triangle row by row."""
+    square = np.asarray(square)
+    if square.ndim != 2 or square.shape[0] != square.shape[1]:
+        raise ValueError(f"triangle_of: a square array, not {square.shape}")
+    t, s = np.tril_indices(square.shape[0], k=-1)
+    return np.ascontiguousarray(square[t, s])
+
+
+def square_of(triangle, n, diagonal=0.0):
+    """The symmetric ``n x n`` array of a target-major triangle (:func:`triangle_of`'s inverse), ``diagonal`` on the diagonal."""
+    triangle = np.asarray(triangle)
+    if triangle.shape != (int(n) * (int(n) - 1) // 2,):
+        raise ValueError(f"square_of: {triangle.shape} values for {n} genomes")
+    out = np.full((int(n), int(n)), diagonal, dtype=triangle.dtype)
+    t, s = np.tril_indices(int(n), k=-1)
+    out[t, s] = triangle
+    out[s, t] = triangle
+    return out
 
 
 class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
@@ -455,6 +501,19 @@ class _SlabFills:
         if b < 0:
             raise ValueError(f"affinity_bytes: {n} genomes x {n_groups} groups")
         return b
+
+    @staticmethod
+    def affinity_ranges(goff, n, want):
+        """The group ranges of the affinity fill's column pass as host arithmetic (``pc_affinity_ranges``; no GPU): range starts +
+        [G] for ``goff`` (int32 ``[G + 1]``, each group's run among the genomes sorted by group) of ``n`` genomes and about ``want``
+        ranges -- a fill asks for ``ceil(16 * CUs / ceil(n / affinity_block()))``."""
+        goff = np.ascontiguousarray(goff, dtype=np.int32).reshape(-1)
+        bounds = np.zeros(goff.shape[0] + 1, dtype=np.int32)
+        lib = load()
+        r = lib.pc_affinity_ranges(_ptr(goff, _i32p), int(goff.shape[0]) - 1, int(n), int(want), _ptr(bounds, _i32p), int(bounds.shape[0]))
+        if r < 0:
+            raise ValueError(lib.pc_last_error().decode())
+        return bounds[:r + 1].copy()
 
     def fill_edges(self, metric, threshold, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
         """The pairs (s, t), s < t, whose value passes ``threshold`` -- ``d <= threshold`` for a distance fill, ``sim >= threshold``
