@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 166   /* 0.5.15: pc_hook_slab_values, pc_affinity_ranges (test hooks); an affinity fill's refusal counts each value once */
+#define PC_VERSION 167   /* 0.5.16: pc_hook_rows_values (test hook of the rows walk) */
 
 typedef enum {
     PC_OK = 0,
@@ -98,9 +98,19 @@ int pc_test_hooks(void);
  * affinity always fill distances and invert at the end, the other four fill the direction asked for.  The pointer is stored process-wide,
  * not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets or clears it
  * between calls only.  A walk that finds n_pairs != N (N - 1) / 2 refuses with PC_ERR_ARG.  The rows walk (pc_fill_rows_edges,
- * _components, _tree, _nearest) takes no injection: deliberately out of scope.  PC_ERR_ARG: values with a negative n_pairs.
+ * _components, _tree, _nearest) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
  * In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
 int pc_hook_slab_values(const double* values, int64_t n_pairs);
+/* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 167): values, f64[n_rows][n], row k the values of the call's query
+ * genome rows[k] to every genome, stands for "the slab as filled" in every rows walk of the process from now on: pc_fill_rows_edges,
+ * _components, _tree, _nearest.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
+ * values + r0 * n, m * n doubles, by one host-to-device copy on the walk's stream -- EVERY element of it: the diagonal [k][rows[k]] and
+ * both copies of a pair of two query genomes are the caller's too, so a test decides what the elements hold that no pass may read.
+ * pc_fill_rows, pc_fill_rows_dev and the triangular walk do not read it; the two hooks are independent.  The pointer is stored
+ * process-wide, not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets
+ * or clears it between calls only.  A walk whose n_rows or N is not the hook's refuses with PC_ERR_ARG.  PC_ERR_ARG: values with a
+ * negative n_rows or n.  In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
+int pc_hook_rows_values(const double* values, int32_t n_rows, int32_t n);
 
 /* One context per GPU.  device_id is the HIP device ordinal. */
 int pc_ctx_create(pc_ctx** out, int device_id);
@@ -786,6 +796,7 @@ int pc_round6_probe(pc_ctx* ctx, const double* in, double* out, int64_t n);
  *   only in libphamclust_hip_hooks.so (compiled with -DPC_TEST_HOOKS; pc_test_hooks() == 1)
  *     PC_FAKE_OOM_ABOVE=n       device allocations above n bytes made while a fill is planning fail (fault injection)
  *     pc_hook_slab_values()     (a call, not a variable) the value triangle that stands for every filled slab of the triangular slab walks
+ *     pc_hook_rows_values()     (a call, not a variable) the rows that stand for every filled slab of the rows walk (the four rows forms)
  * The Python package adds PHAMCLUST_DEVICE, PHAMCLUST_DIST_BACKEND, PHAMCLUST_DIST_MODE, PHAMCLUST_DIST_TIMEOUT_S, PHAMCLUST_LAUNCH_COST_S,
  * PHAMCLUST_FORCE_GPUS, PHAMCLUST_NO_TORCH and PHAMCLUST_NATIVE_VARIANT.
  */

@@ -67,22 +67,37 @@ PlanningScope::~PlanningScope() {}
 #endif
 
 // Value injection (pc_hook_slab_values): the triangle a test sets stands for "the slab as filled" in every triangular slab walk of the
-// process (slab_walk, pc_fill_slabs.hip; the rows walk takes none) until it is cleared.  The caller keeps the memory alive.  Set between
-// calls only: the walks of a several-device fill read it from their own threads.  Compiled only under -DPC_TEST_HOOKS; the release library
-// stores nothing and its getter answers NULL.
+// process (slab_walk, pc_fill_slabs.hip) until it is cleared.  pc_hook_rows_values is its twin for the rows walk (rows_walk, the four rows
+// forms): f64[n_rows][n], row k the values of the call's query genome rows[k], every element of every rows slab -- the diagonal and both
+// copies of a pair of two query genomes included.  The two are independent: neither walk reads the other's.  The caller keeps the memory
+// alive.  Set between calls only: the walks of a several-device fill read it from their own threads.  Compiled only under -DPC_TEST_HOOKS;
+// the release library stores nothing and its getters answer NULL.
 #ifdef PC_TEST_HOOKS
 static const double* g_slab_values = nullptr;
 static int64_t g_slab_n_pairs = 0;
+static const double* g_rows_values = nullptr;
+static int32_t g_rows_n_rows = 0, g_rows_n = 0;
 const double* pc_hooked_slab_values(int64_t* n_pairs) { *n_pairs = g_slab_n_pairs; return g_slab_values; }
+const double* pc_hooked_rows_values(int32_t* n_rows, int32_t* n) { *n_rows = g_rows_n_rows; *n = g_rows_n; return g_rows_values; }
 extern "C" int pc_hook_slab_values(const double* values, int64_t n_pairs) {
     if (values && n_pairs < 0) { pc_set_error("pc_hook_slab_values: n_pairs %lld", (long long)n_pairs); return PC_ERR_ARG; }
     g_slab_values = values; g_slab_n_pairs = values ? n_pairs : 0;
     return PC_OK;
 }
+extern "C" int pc_hook_rows_values(const double* values, int32_t n_rows, int32_t n) {
+    if (values && (n_rows < 0 || n < 0)) { pc_set_error("pc_hook_rows_values: n_rows %d, n %d", (int)n_rows, (int)n); return PC_ERR_ARG; }
+    g_rows_values = values; g_rows_n_rows = values ? n_rows : 0; g_rows_n = values ? n : 0;
+    return PC_OK;
+}
 #else
 const double* pc_hooked_slab_values(int64_t* n_pairs) { *n_pairs = 0; return nullptr; }
+const double* pc_hooked_rows_values(int32_t* n_rows, int32_t* n) { *n_rows = 0; *n = 0; return nullptr; }
 extern "C" int pc_hook_slab_values(const double*, int64_t) {
     pc_set_error("pc_hook_slab_values: this library carries no test hooks (libphamclust_hip_hooks.so does)");
+    return PC_ERR_STATE;
+}
+extern "C" int pc_hook_rows_values(const double*, int32_t, int32_t) {
+    pc_set_error("pc_hook_rows_values: this library carries no test hooks (libphamclust_hip_hooks.so does)");
     return PC_ERR_STATE;
 }
 #endif

@@ -906,6 +906,16 @@ template <class Fill> static int rows_walk(pc_ctx* c, PcSlabRun& run, const int3
         // (the rows fill waits for the pass the slab before it left running before it rewrites the slab and its own tables)
         if ((rc = pc_fill_rows_dev(c, run.metric, run.as_distance, rows + r0, m, slab, st, run.timed ? &one : nullptr))) return rc;
         if (run.timed) pc_stats_add(run.sum, one);
+        // test-hooks build only (the release getter answers NULL): the injected rows stand for the slab as filled, every element of it
+        int32_t hooked_rows = 0, hooked_n = 0;
+        if (const double* const hooked = pc_hooked_rows_values(&hooked_rows, &hooked_n)) {
+            if (hooked_rows != n_rows || hooked_n != N) {
+                pc_set_error("rows walk: pc_hook_rows_values holds %d rows of %d values, the call has %d query rows of %d genomes", (int)hooked_rows,
+                             (int)hooked_n, n_rows, N);
+                return PC_ERR_ARG;
+            }
+            PC_HIP(hipMemcpyAsync(slab, hooked + (size_t)r0 * N, (size_t)m * N * 8, hipMemcpyHostToDevice, st));
+        }
         const PcRowsSlab dom{m, N, c->b_rq_rows.as<int32_t>() + r0, c->b_rq_query.as<uint8_t>(), 0, 0};
         if ((rc = Fill::slab(c, run, slab, (int64_t)m * N, dom))) return rc;
         ++run.n_slabs;

@@ -27,6 +27,9 @@ struct PlanningScope { PlanningScope(); ~PlanningScope(); };
 // the value triangle pc_hook_slab_values set (target-major, *n_pairs doubles), or NULL: always NULL in the release library (pc_ctx.hip).
 // slab_walk overwrites every slab it has filled with its part of the triangle.  (Not part of the exported set.)
 __attribute__((visibility("hidden"))) const double* pc_hooked_slab_values(int64_t* n_pairs);
+// the rows pc_hook_rows_values set (f64[*n_rows][*n], row k for the call's rows[k]), or NULL: always NULL in the release library.
+// rows_walk overwrites every rows slab it has filled with its rows of them.  (Not part of the exported set.)
+__attribute__((visibility("hidden"))) const double* pc_hooked_rows_values(int32_t* n_rows, int32_t* n);
 // Grow-only device buffer that owns its memory: freed when it goes out of scope, on whichever device is current then (the
 // context's destruction runs under its device guard).  Move-only, so that a std::vector of them can grow.
 struct DevBuf {

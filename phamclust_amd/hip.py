@@ -79,7 +79,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
-           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values"]
+           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -189,6 +189,7 @@ def load():
     L.pc_affinity_bytes.restype = ctypes.c_int64
     L.pc_affinity_ranges.argtypes = [_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int]
     L.pc_hook_slab_values.argtypes = [_f64p, ctypes.c_int64]
+    L.pc_hook_rows_values.argtypes = [_f64p, ctypes.c_int32, ctypes.c_int32]
     L.pc_plan_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PcStats)]
     L.pc_align_slice_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_reduce_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
@@ -254,6 +255,30 @@ def set_slab_values(values):
     if rc != 0:
         raise HipLibraryError(f"libphamclust_hip: status {rc}: {lib.pc_last_error().decode()}")
     _slab_values = values
+
+
+# -- test hook: the values of the rows walk (libphamclust_hip_hooks.so only) --------------------------------------------------------
+_rows_values = None                     # the array the library holds a pointer to: kept alive here until it is replaced or cleared
+
+
+def set_rows_values(values):
+    """``pc_hook_rows_values``: ``values`` -- float64, C-contiguous, ``[n_rows, N]``, row k the values of the call's query genome
+    ``rows[k]`` -- stands for every slab that ``fill_rows_edges`` / ``_components`` / ``_tree`` / ``_nearest`` of any context of this
+    process fills from now on, every element of it: the diagonal ``[k, rows[k]]`` and both copies of a pair of two query genomes are
+    the caller's too.  ``None`` clears it.  Independent of :func:`set_slab_values`.  The array is referenced, not copied: do not write
+    to it while it is set.  Only the test-hooks twin (``PHAMCLUST_NATIVE_VARIANT=hooks``) takes it; the release library refuses, and
+    so does this."""
+    global _rows_values
+    lib = load()
+    if values is None:
+        rc = lib.pc_hook_rows_values(None, 0, 0)
+    else:
+        if not (isinstance(values, np.ndarray) and values.dtype == np.float64 and values.ndim == 2 and values.flags.c_contiguous):
+            raise ValueError("set_rows_values: a two-dimensional C-contiguous float64 array, or None")
+        rc = lib.pc_hook_rows_values(_ptr(values, _f64p), int(values.shape[0]), int(values.shape[1]))
+    if rc != 0:
+        raise HipLibraryError(f"libphamclust_hip: status {rc}: {lib.pc_last_error().decode()}")
+    _rows_values = values
 
 
 def triangle_of(square):
