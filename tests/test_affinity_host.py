@@ -249,8 +249,8 @@ def test_affinity_de_novo_refuses_before_any_gpu_call(monkeypatch, small_genomes
 
     def no_gpu(*args, **kwargs):
         raise AssertionError("a GPU call was reached")
-    monkeypatch.setattr(matrix, "get_context", no_gpu)
-    monkeypatch.setattr(matrix, "get_multi_context", no_gpu)
+    monkeypatch.setattr("phamclust_amd.routes.get_context", no_gpu)
+    monkeypatch.setattr("phamclust_amd.routes.get_multi_context", no_gpu)
     names = [g.name for g in small_genomes]
     with pytest.raises(ValueError, match="METRICS"):
         matrix.affinity_de_novo(small_genomes, lambda a, b: 0.5, [names])

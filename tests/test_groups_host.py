@@ -102,8 +102,8 @@ def test_submatrices_de_novo_refuses_before_any_gpu_call(monkeypatch, small_geno
 
     def no_gpu(*args, **kwargs):
         raise AssertionError("a refusal must come before any GPU call")
-    monkeypatch.setattr(M, "get_context", no_gpu)
-    monkeypatch.setattr(M, "_packed_of", no_gpu)
+    monkeypatch.setattr("phamclust_amd.routes.get_context", no_gpu)
+    monkeypatch.setattr("phamclust_amd.routes._packed_of", no_gpu)
     with pytest.raises(ValueError, match="METRICS"):
         M.submatrices_de_novo(small_genomes, lambda s, t, as_distance=True: 0.0, [names[:3]])
     with pytest.raises(KeyError, match="no such genome"):

@@ -296,7 +296,7 @@ def test_phamclust_checks_grow_nearest_before_any_gpu_call(monkeypatch):
         raise AssertionError("a refusal came after the run had begun")
 
     monkeypatch.setattr(script, "_Run", reached)
-    monkeypatch.setattr(M, "upload_for_fills", reached)
+    monkeypatch.setattr("phamclust_amd.routes.upload_for_fills", reached)
     assert list(inspect.signature(script.phamclust).parameters)[-2:] == ["grow_nearest", "nearest"]     # (an older test pins nearest as the last one)
     assert inspect.signature(script.phamclust).parameters["grow_nearest"].default is None
     base = (None, None, False, "jc", 0.0, "complete", 0.5, "average", 0.3, "single", 1, False, None, 0.5, 1, False, False)

@@ -164,8 +164,8 @@ def test_de_novo_calls_choose_the_multi_context(monkeypatch):
     named: the one-GPU context; under a launcher they raise as before (tests/test_edges_host.py and its siblings pin the message)."""
     from phamclust_amd import matrix as M
     made = []
-    monkeypatch.setattr(M, "get_multi_context", lambda ids: made.append(("multi", list(ids))) or "multi")
-    monkeypatch.setattr(M, "get_context", lambda device=None: made.append(("one", device)) or "one")
+    monkeypatch.setattr("phamclust_amd.routes.get_multi_context", lambda ids: made.append(("multi", list(ids))) or "multi")
+    monkeypatch.setattr("phamclust_amd.routes.get_context", lambda device=None: made.append(("one", device)) or "one")
     for key in ("WORLD_SIZE", "PHAMCLUST_GPUS", "PHAMCLUST_GPU_IDS"):
         monkeypatch.delenv(key, raising=False)
     assert M._slab_fill_context() == ("one", 1)
