@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 167   /* 0.5.16: pc_hook_rows_values (test hook of the rows walk) */
+#define PC_VERSION 168   /* 0.5.17: pc_fill_rows_affinity (new genomes against stored clusters) */
 
 typedef enum {
     PC_OK = 0,
@@ -98,12 +98,12 @@ int pc_test_hooks(void);
  * affinity always fill distances and invert at the end, the other four fill the direction asked for.  The pointer is stored process-wide,
  * not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets or clears it
  * between calls only.  A walk that finds n_pairs != N (N - 1) / 2 refuses with PC_ERR_ARG.  The rows walk (pc_fill_rows_edges,
- * _components, _tree, _nearest) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
+ * _components, _tree, _nearest, _affinity) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
  * In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
 int pc_hook_slab_values(const double* values, int64_t n_pairs);
 /* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 167): values, f64[n_rows][n], row k the values of the call's query
  * genome rows[k] to every genome, stands for "the slab as filled" in every rows walk of the process from now on: pc_fill_rows_edges,
- * _components, _tree, _nearest.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
+ * _components, _tree, _nearest, _affinity.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
  * values + r0 * n, m * n doubles, by one host-to-device copy on the walk's stream -- EVERY element of it: the diagonal [k][rows[k]] and
  * both copies of a pair of two query genomes are the caller's too, so a test decides what the elements hold that no pass may read.
  * pc_fill_rows, pc_fill_rows_dev and the triangular walk do not read it; the two hooks are independent.  The pointer is stored
@@ -443,13 +443,14 @@ int pc_between_segment(void);       /* elements of a slab row one workgroup of t
  * The two passes each see every element of a slab and each leave a value that is no millionth in [0, 1] out; the row pass alone counts
  * it, so the count in the PC_ERR_DATA message is the number of such values, as pc_fill_between's is.
  * Refusals as pc_fill_between's, and PC_ERR_LIMIT when the table (with want_table: and its converted copy) takes more than half of the
- * HBM that is free when the call begins; the message carries both numbers.  There is no rows form.
+ * HBM that is free when the call begins; the message carries both numbers.  The rows form is pc_fill_rows_affinity, below; this call
+ * keeps refusing a label of -1.
  */
 int pc_fill_affinity(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, int want_table, int64_t slab_bytes,
                      const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
                      const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
                      const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats);
-/* Test / tuning hook, of the last pc_fill_affinity call: the row passes and the column passes summed over its slabs, and the finish (HIP
+/* Test / tuning hook, of the last pc_fill_affinity or pc_fill_rows_affinity call: the row passes and the column passes summed over its slabs, and the finish (HIP
  * events; 0 unless the call was given stats); any pointer may be NULL. */
 int pc_last_affinity_times(const pc_ctx* ctx, float* ms_rows, float* ms_cols, float* ms_finish);
 int pc_affinity_block(void);        /* consecutive sources one wave of the column pass takes */
@@ -526,6 +527,48 @@ int pc_fill_rows_nearest(pc_ctx* ctx, int metric, int as_distance, int k, const 
                          const int32_t** nbr, const double** val, int32_t* k_out, int32_t* n_slabs, pc_stats* stats);
 /* Test hook, host arithmetic: the tile edge of that call's column pass (rows and columns of the slab a workgroup stages at a time). */
 int pc_nearest_rows_tile(void);
+
+/*
+ * The rows form of the affinity fill (PC_VERSION 168): new genomes placed against stored clusters.  rows[n_rows] -- pc_fill_rows' contract,
+ * the rows walk and its slabs (f64[m][N], slab_bytes) as above -- are the QUERY genomes; group[N] / n_groups is the partition, and here,
+ * and only here, group[g] may be -1: a member of no group (a new genome not yet placed).  Values enter as millionths of the DISTANCE
+ * under pc_fill_affinity's rule; as_distance == 0 complements every reported value by its formulas; the nearest groups are chosen on
+ * distances.  The definition everything is held to:
+ *   Row table.  Query k is q = rows[k].  Entry [k][b] holds the sum, minimum and maximum of the millionths of d(q, x) over all x != q
+ *       with group[x] == b -- x may itself be a query.  Its count is not stored: size[b] - [group[q] == b], size[b] the genomes
+ *       labelled b, queries included.  An entry no pair falls into reads 0 / INT32_MAX / -1.
+ *   Per query, [n_rows], as pc_fill_affinity states it per genome: *own_sum / *own_lo / *own_hi (empty when group[q] == -1);
+ *       *near_group [3][n_rows], the nearest group b != group[q] with a non-zero count by the smallest mean (64-bit integers), minimum
+ *       and maximum, ties to the smaller index, -1: none -- an unlabelled query has no own group, so every non-empty group is a
+ *       candidate; *near_sum / *near_lo / *near_hi; with want_table *tab_sum / *tab_lo / *tab_hi [n_rows][n_groups], else NULL.
+ *   Own-group gain, with want_gain, [N] (else NULL): for a genome g that is NOT a query and has group[g] >= 0, the sum, minimum and
+ *       maximum of the millionths of d(g, x) over the query genomes x with group[x] == group[g]; empty for a query, for an unlabelled
+ *       genome and where no such x exists.  It is what the queries add to g's own entry: with own_old from an affinity fill of the
+ *       collection without the queries, own_old (+) gain -- sums added, the smaller lo, the larger hi -- is own of pc_fill_affinity
+ *       over the whole collection, so stored own sums, the medoids and the a-term of every silhouette grow exactly.  (as_distance ==
+ *       0: complemented over its count, the queries labelled group[g].)  The nearest-other-group columns of OLD genomes cannot grow
+ *       without the stored N x n_groups table: not built.
+ * Consequence: with every genome labelled, query k's row and per-query outputs equal entry rows[k] of pc_fill_affinity's on the same
+ * group, integer for integer, for any subset of rows and any slab cut.
+ * On the device: n_rows x n_groups entries and the gain's N, 16 bytes each, stay resident (refused with PC_ERR_LIMIT above half of the
+ * free HBM, with want_table counting the table's converted copy); each slab of query rows goes through k_aff_qrows (a workgroup per
+ * query row; a query's row lies in one slab and is written once) and, with want_gain, k_aff_qcols (a lane per column, one writer per
+ * genome and launch); after the last slab k_aff_qfinish and ONE D2H copy.  Every entry has one writer per launch; no global atomics
+ * but the violation count.  A value that is no millionth in [0, 1] is left out and counted once per PAIR (a pair of two labelled
+ * queries stands in two rows: the row of the smaller counts it); columns of unlabelled genomes and the diagonal are never read.
+ * PC_ERR_DATA carries the count.
+ * All arrays lie in page-locked memory the context owns (pc_fill_borrow's loan rule).  n_rows == 0 and N <= 1: PC_OK, nothing runs on
+ * the device, every entry empty; n_rows == N is allowed.  Refusals in pc_fill_affinity's order -- the label check admits -1 and names
+ * the genome otherwise -- then rows (pc_fill_rows' PC_ERR_ARG); all before anything is launched, with the outputs nulled, and the
+ * context stays usable.  One GPU: a sharded context is refused (PC_ERR_STATE).  pc_last_affinity_times reports on this call too (rows:
+ * k_aff_qrows, cols: k_aff_qcols).
+ */
+int pc_fill_rows_affinity(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                          int want_table, int want_gain, int64_t slab_bytes,
+                          const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                          const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                          const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi,
+                          const int64_t** gain_sum, const int32_t** gain_lo, const int32_t** gain_hi, int32_t* n_slabs, pc_stats* stats);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

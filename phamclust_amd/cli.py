@@ -88,6 +88,12 @@ _OPTIONS = (
                                                                  "silhouette, whether it is the cluster's medoid) and "
                                                                  "cluster_fit_<metric>_summary.tsv (per cluster: size, medoid, mean silhouette, "
                                                                  "largest own distance); with the dense route or --no-matrix, and with --gpus N")),
+    (None, "-P", "--place", dict(type=pathlib.Path, default=None, help="stop after the matrix stage and write only placement_<metric>.tsv: FILE is the "
+                                                                      "cluster_fit_<metric>.tsv of an earlier --cluster-fit run over a SUBSET of "
+                                                                      "these genomes; the genomes it lacks are placed against its clusters -- per new "
+                                                                      "genome the nearest cluster by mean, by nearest and by farthest member, with the "
+                                                                      "three similarities and the clusters' sizes -- filling only the new genomes' "
+                                                                      "pairs, on one GPU; no matrix, no clustering")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -160,6 +166,14 @@ def parse_args(argv=None):
             parser.error("--grow-nearest FILE grows the stored lists of a --nearest K run; give --nearest K")
         if args.gpus > 1:
             parser.error("--grow-nearest: growing a stored result is a one-GPU call; it cannot be combined with --gpus N")
+    if args.place is not None:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--no-matrix", args.no_matrix),
+                            ("--nearest", args.nearest is not None), ("--tree", args.tree), ("--extend", args.extend is not None),
+                            ("--grow", args.grow is not None), ("--cluster-table", args.cluster_table), ("--cluster-fit", args.cluster_fit)):
+            if given:
+                parser.error(f"--place stops after a placement of its own; it cannot be combined with {flag}")
+        if args.gpus > 1:
+            parser.error("--place: placing new genomes is a one-GPU call; it cannot be combined with --gpus N")
     if args.cluster_table:
         for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--tree", args.tree),
                             ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):

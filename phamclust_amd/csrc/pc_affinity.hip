@@ -37,6 +37,22 @@
 // group's member run and two binary searches over it.
 // What is read: a row pass reads [lbase[k], lbase[k + 1]) of its row; a column pass reads lbase[k] + s for s < min(t, the row's
 // length); nothing beyond Lp.
+//
+// The rows form (pc_fill_rows_affinity): n_rows query genomes against the groups, over ROWS slabs (PcRowsSlab: f64[m][N], row r the values
+// of query genome rows[r] to every genome).  A label may be -1 here: a member of no group.  The resident state is T[n_rows][G] (row k the
+// query rows[k]) | gain[N] | the violation count (pc_common.h).
+//   k_aff_qrows    T[k][group[s]] over every column s != q with a label: a workgroup per row of the slab, the LDS table and the wave
+//                  reduction of k_aff_rows (af_lds_add).  The diagonal and the columns of unlabelled genomes are not read.
+//   k_aff_qcols    gain[g] (want_gain only): what the slab's query genomes add to the own entry of an old labelled genome g.  A lane per
+//                  column, a row's group wave-uniform, the value loaded only where a lane of the wave matches (ballot).
+//   k_aff_qfinish  a wave per query row through k_aff_finish's body (af_finish_row) with a row indirection and an own group that may be
+//                  -1; behind them a thread per genome converts gain[].
+// Who writes what.  A query's row lies in exactly one slab: row r0 + r of T is written once, whole, by the workgroup of slab row r (plain
+// stores, no read-modify-write).  gain[g] has one writer per launch -- the lane of column g -- and the slabs' launches follow each other
+// on one stream.  What is atomic: ds atomics in LDS as in k_aff_rows; in HBM the violation count alone.  A refused value is left out by
+// both passes and counted by the row pass once per PAIR: a pair of two labelled query genomes stands in two rows that both read it, and
+// the row of the smaller counts it (PcRowsDomain::live's rule).  Progress: no workgroup waits for another; the loops are a row's N
+// columns, the slab's m rows, the table's G.  What is read: row r of the slab at columns below N; nothing beyond m * N.
 #include <climits>
 
 #include "pc_slab_pass.h"
@@ -68,6 +84,30 @@ __global__ __launch_bounds__(256) void k_aff_init(PcAffinityEntry* __restrict__ 
     if (i == 0) *(unsigned long long*)(tab + n_entries) = 0ull;
 }
 
+// One wave's step of a row pass (k_aff_rows, k_aff_qrows): lane's millionths m into entry b of the workgroup's LDS table, b == -1: this lane
+// adds nothing.  Called by the whole wave.  A wave whose live lanes all name one group reduces by shuffles and one lane adds; otherwise a
+// ds atomic per live lane.
+__device__ __forceinline__ void af_lds_add(int b, uint32_t m, int lane, unsigned long long* t_sum, uint32_t* t_lo, uint32_t* t_hi) {
+    const unsigned long long live = __ballot(b >= 0);
+    if (live == 0ull) return;                          // (the whole wave)
+    const int leader = __ffsll((long long)live) - 1;
+    const int lb = __shfl(b, leader);
+    if (!__any(b >= 0 && b != lb)) {
+        // one group for the whole wave: reduce, one lane adds
+        unsigned long long sum = b >= 0 ? m : 0ull;
+        uint32_t lo = b >= 0 ? m : ~0u, hi = b >= 0 ? m : 0u;
+#pragma unroll
+        for (int off = 32; off; off >>= 1) {
+            sum += __shfl_xor(sum, off);
+            const uint32_t ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
+            lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
+        }
+        if (lane == leader) { atomicAdd(t_sum + lb, sum); atomicMin(t_lo + lb, lo); atomicMax(t_hi + lb, hi); }
+    } else if (b >= 0) {
+        atomicAdd(t_sum + b, (unsigned long long)m); atomicMin(t_lo + b, m); atomicMax(t_hi + b, m);
+    }
+}
+
 // row pass: workgroup k takes target t0 + k
 __global__ __launch_bounds__(AF_THREADS) void k_aff_rows(const double* __restrict__ vals, PcShard sh, int t0, const int32_t* __restrict__ group, int G,
                                                         PcAffinityEntry* __restrict__ tab, unsigned long long* __restrict__ n_bad) {
@@ -91,24 +131,7 @@ __global__ __launch_bounds__(AF_THREADS) void k_aff_rows(const double* __restric
         int b = -1;
         if (s < len && af_micro(row[s], m, bad)) b = group[s];
         if ((unsigned)b >= (unsigned)G && b != -1) { ++bad; b = -1; }  // (the host has checked the labels: never)
-        const unsigned long long live = __ballot(b >= 0);
-        if (live == 0ull) continue;                    // (the whole wave)
-        const int leader = __ffsll((long long)live) - 1;
-        const int lb = __shfl(b, leader);
-        if (!__any(b >= 0 && b != lb)) {
-            // one group for the whole wave: reduce, one lane adds
-            unsigned long long sum = b >= 0 ? m : 0ull;
-            uint32_t lo = b >= 0 ? m : ~0u, hi = b >= 0 ? m : 0u;
-#pragma unroll
-            for (int off = 32; off; off >>= 1) {
-                sum += __shfl_xor(sum, off);
-                const uint32_t ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
-                lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
-            }
-            if (lane == leader) { atomicAdd(t_sum + lb, sum); atomicMin(t_lo + lb, lo); atomicMax(t_hi + lb, hi); }
-        } else if (b >= 0) {
-            atomicAdd(t_sum + b, (unsigned long long)m); atomicMin(t_lo + b, m); atomicMax(t_hi + b, m);
-        }
+        af_lds_add(b, m, lane, t_sum, t_lo, t_hi);
     }
     __syncthreads();
     PcAffinityEntry* const out = tab + (size_t)t * (size_t)G;
@@ -167,6 +190,68 @@ __global__ __launch_bounds__(AF_THREADS) void k_aff_cols(const double* __restric
     }
 }
 
+// rows form, row pass: workgroup r takes row r of the rows slab -- query genome q = rows[r], table row r0 + r of the call (r0: the slab's
+// first query row).  Every column s != q with a label is a pair of this row, whether s is a query genome or not; column q (the diagonal)
+// and the columns of unlabelled genomes are not read.  The row is written whole by plain stores: a query's row lies in one slab.
+// A refused value is left out and counted once per PAIR: a pair of two query genomes stands in two rows, and where both rows read it
+// (both labelled) the row of the smaller counts it, as PcRowsDomain::live takes such a pair.
+__global__ __launch_bounds__(AF_THREADS) void k_aff_qrows(const double* __restrict__ vals, PcRowsSlab dom, int r0, const int32_t* __restrict__ group, int G,
+                                                         PcAffinityEntry* __restrict__ tab, unsigned long long* __restrict__ n_bad) {
+    extern __shared__ unsigned long long af_table[];
+    unsigned long long* const t_sum = af_table;
+    uint32_t* const t_lo = (uint32_t*)(af_table + G);
+    uint32_t* const t_hi = t_lo + G;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int n = dom.n, q = dom.rows[r];
+    const bool q_labelled = group[q] >= 0;
+    for (int b = tid; b < G; b += AF_THREADS) { t_sum[b] = 0ull; t_lo[b] = ~0u; t_hi[b] = 0u; }
+    __syncthreads();
+    const double* __restrict__ row = vals + (size_t)r * (size_t)n;
+    uint32_t bad = 0;
+#pragma unroll 1
+    for (int base = 0; base < n; base += AF_THREADS) {                // (workgroup-uniform: the reduction is the wave's)
+        const int s = base + tid;
+        uint32_t m = 0;
+        int b = -1;
+        if (s < n && s != q) {
+            const int bs = group[s];
+            uint32_t refused = 0;
+            if (bs >= 0) {
+                if (af_micro(row[s], m, refused)) b = bs;
+                else if (!(s < q && q_labelled && dom.is_query[s])) ++bad;      // (else row s reads the pair at column q, and counts it)
+            }
+        }
+        if (b >= G) { ++bad; b = -1; }                 // (the host has checked the labels: never)
+        af_lds_add(b, m, lane, t_sum, t_lo, t_hi);
+    }
+    __syncthreads();
+    PcAffinityEntry* const out = tab + (size_t)(r0 + r) * (size_t)G;
+    for (int b = tid; b < G; b += AF_THREADS) out[b] = PcAffinityEntry{t_sum[b], t_lo[b], t_hi[b]};
+    if (bad) (void)__hip_atomic_fetch_add(n_bad, (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// rows form, column pass (want_gain only): lane = column g, a wave 64 consecutive columns; what the slab's query genomes add to the own
+// entry of an OLD labelled genome g -- the values of (g, x) over the query genomes x of the slab with group[x] == group[g].  A row's
+// group is wave-uniform; its value is loaded only where some lane of the wave matches.  A lane keeps (sum, lo, hi) in registers and adds
+// them into gain[g] once per slab: one writer per g and launch, slabs are successive launches on one stream.  Refused values are left
+// out and not counted: the row pass has read the same elements.
+__global__ __launch_bounds__(AF_THREADS) void k_aff_qcols(const double* __restrict__ vals, PcRowsSlab dom, const int32_t* __restrict__ group,
+                                                         PcAffinityEntry* __restrict__ gain) {
+    const int n = dom.n, g = (int)blockIdx.x * AF_THREADS + (int)threadIdx.x;
+    const int mine = g < n && !dom.is_query[g] ? group[g] : -1;      // (-1: a query genome, an unlabelled one, or no column)
+    if (!__any(mine >= 0)) return;                     // (the whole wave)
+    unsigned long long sum = 0ull;
+    uint32_t lo = ~0u, hi = 0u, bad = 0;               // (bad: not reported)
+    for (int r = 0; r < dom.m; ++r) {
+        const int gq = group[dom.rows[r]];             // (wave-uniform)
+        const bool match = gq >= 0 && mine == gq;
+        if (!__any(match)) continue;                   // (the whole wave)
+        uint32_t m = 0;
+        if (match && af_micro(vals[(size_t)r * (size_t)n + g], m, bad)) { sum += m; lo = m < lo ? m : lo; hi = m > hi ? m : hi; }
+    }
+    if (lo != ~0u) af_entry_add(gain + g, sum, lo, hi);
+}
+
 // staged: n_foreign tables of `bytes` each
 __global__ __launch_bounds__(256) void k_aff_merge(PcAffinityEntry* __restrict__ tab, const char* __restrict__ staged, size_t bytes, int n_foreign, size_t n_entries) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -191,15 +276,11 @@ __device__ __forceinline__ bool af_mean_less(unsigned long long sum_a, unsigned 
     return l < r || (l == r && a < b);
 }
 
-// wave w of workgroup b takes genome b * AF_WAVES + w
-__global__ __launch_bounds__(AF_THREADS) void k_aff_finish(const PcAffinityEntry* __restrict__ tab, const int32_t* __restrict__ group, const int32_t* __restrict__ goff,
-                                                          int N, int G, int invert, PcAffinityOut out) {
-    const int lane = threadIdx.x & 63;
-    const int g = (int)blockIdx.x * AF_WAVES + (int)(threadIdx.x >> 6);
-    if (g == 0 && threadIdx.x == 0) *out.bad = *(const unsigned long long*)(tab + (size_t)N * (size_t)G);
-    if (g >= N) return;                                // (the whole wave)
-    const int own = group[g];
-    const PcAffinityEntry* const row = tab + (size_t)g * (size_t)G;
+// The finish of ONE table row by one wave, shared by k_aff_finish (row g of the N x G table, own = group[g]) and k_aff_qfinish (row k of
+// the n_rows x G table, own = the query genome's label or -1: it has no own group, its own entry is empty and every non-empty group is
+// a candidate).  g: the row, and the place in the O(rows) arrays; N: their length (near_group is [3][N]).
+__device__ __forceinline__ void af_finish_row(const PcAffinityEntry* __restrict__ row, int own, const int32_t* __restrict__ goff, int g, int N, int G, int invert,
+                                              const PcAffinityOut& out, int lane) {
     // per lane, over its groups in ascending order: the best by each criterion (strictly better only: ties stay with the smaller index)
     unsigned long long m_sum = 0ull, m_size = 1ull;
     int m_idx = INT32_MAX;
@@ -247,6 +328,49 @@ __global__ __launch_bounds__(AF_THREADS) void k_aff_finish(const PcAffinityEntry
     out.near_sum[g] = none ? 0ll : (long long)(invert ? m_size * 1000000ull - m_sum : m_sum);
     out.near_lo[g] = none ? INT32_MAX : (int32_t)(invert ? 1000000u - v_lo : v_lo);
     out.near_hi[g] = none ? -1 : (int32_t)(invert ? 1000000u - v_hi : v_hi);
+    if (own < 0) { out.own_sum[g] = 0ll; out.own_lo[g] = INT32_MAX; out.own_hi[g] = -1; }      // (the rows form's unlabelled query only)
+}
+
+// wave w of workgroup b takes genome b * AF_WAVES + w
+__global__ __launch_bounds__(AF_THREADS) void k_aff_finish(const PcAffinityEntry* __restrict__ tab, const int32_t* __restrict__ group, const int32_t* __restrict__ goff,
+                                                          int N, int G, int invert, PcAffinityOut out) {
+    const int lane = threadIdx.x & 63;
+    const int g = (int)blockIdx.x * AF_WAVES + (int)(threadIdx.x >> 6);
+    if (g == 0 && threadIdx.x == 0) *out.bad = *(const unsigned long long*)(tab + (size_t)N * (size_t)G);
+    if (g >= N) return;                                // (the whole wave)
+    af_finish_row(tab + (size_t)g * (size_t)G, group[g], goff, g, N, G, invert, out, lane);
+}
+
+// rows form.  Workgroups [0, ceil(n_rows / AF_WAVES)): wave w of workgroup b takes query row k = b * AF_WAVES + w -- row k of the table,
+// own group that of genome rows[k].  goff counts the LABELLED genomes of each group, queries included.  The workgroups behind them
+// (want_gain only: gout.sum != NULL) take AF_THREADS genomes each, a thread a genome: gain[g] converted (an empty entry as 0 / INT32_MAX /
+// -1) and, for a similarity statement, complemented over its count, qcount[group[g]] -- the query genomes of g's group (from the host).
+// tab: PcAffinityEntry[n_rows][G] | gain[N] | the violation count.
+__global__ __launch_bounds__(AF_THREADS) void k_aff_qfinish(const PcAffinityEntry* __restrict__ tab, const int32_t* __restrict__ rows, const int32_t* __restrict__ group,
+                                                           const int32_t* __restrict__ goff, const int32_t* __restrict__ qcount, int n_rows, int N, int G,
+                                                           int invert, PcAffinityOut out, PcAffinityGainOut gout) {
+    const int row_blocks = (n_rows + AF_WAVES - 1) / AF_WAVES;
+    const PcAffinityEntry* const gain = tab + (size_t)n_rows * (size_t)G;
+    if ((int)blockIdx.x >= row_blocks) {
+        const int g = ((int)blockIdx.x - row_blocks) * AF_THREADS + (int)threadIdx.x;
+        if (g >= N) return;
+        const PcAffinityEntry e = gain[g];
+        const bool empty = e.lo == ~0u;                // (else g is an old labelled genome: the column pass adds nowhere else)
+        unsigned long long sum = e.sum;
+        uint32_t lo = e.lo, hi = e.hi;
+        if (invert && !empty) {
+            sum = (unsigned long long)qcount[group[g]] * 1000000ull - sum;
+            const uint32_t l = 1000000u - hi;
+            hi = 1000000u - lo; lo = l;
+        }
+        gout.sum[g] = (long long)sum; gout.lo[g] = empty ? INT32_MAX : (int32_t)lo; gout.hi[g] = empty ? -1 : (int32_t)hi;
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * AF_WAVES + (int)(threadIdx.x >> 6);
+    if (k == 0 && threadIdx.x == 0) *out.bad = *(const unsigned long long*)(gain + N);
+    if (k >= n_rows) return;                           // (the whole wave)
+    af_finish_row(tab + (size_t)k * (size_t)G, group[rows[k]], goff, k, n_rows, G, invert, out, lane);
 }
 
 static bool affinity_shape_ok(int N, int G, const char* what) {
@@ -311,4 +435,49 @@ int pc_launch_affinity_finish(const void* tab, const int32_t* group, const int32
     hipLaunchKernelGGL(k_aff_finish, dim3((unsigned)((N + AF_WAVES - 1) / AF_WAVES)), dim3(AF_THREADS), 0, st, (const PcAffinityEntry*)tab, group, goff, N, G,
                        invert ? 1 : 0, pc_affinity_out_view(out, N, G, want_table));
     return pc_launch_check("k_aff_finish");
+}
+
+// ---- the rows form ----
+static bool affinity_rows_shape_ok(int n_rows, int N, int G, const char* what) {
+    if (N >= 1 && n_rows >= 1 && n_rows <= N && G >= 1 && G <= PC_BETWEEN_MAX_GROUPS) return true;
+    pc_set_error("%s: %d query rows of %d genomes in %d groups (1 .. PC_BETWEEN_MAX_GROUPS = %d)", what, n_rows, N, G, PC_BETWEEN_MAX_GROUPS);
+    return false;
+}
+
+int pc_launch_affinity_rows_init(void* state, int n_rows, int N, int G, hipStream_t st) {
+    if (!affinity_rows_shape_ok(n_rows, N, G, "k_aff_init")) return PC_ERR_ARG;
+    const size_t n_entries = pc_affinity_rows_entries(n_rows, N, G);
+    dim3 grid;
+    int rc = affinity_grid(n_entries, "k_aff_init", grid);
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(k_aff_init, grid, dim3(256), 0, st, (PcAffinityEntry*)state, n_entries);
+    return pc_launch_check("k_aff_init");
+}
+
+int pc_launch_affinity_rows_slab(const double* vals, int64_t Lp, const PcRowsSlab& dom, int r0, int n_rows, const int32_t* group, int G, void* state,
+                                 int want_gain, hipEvent_t between, hipStream_t st) {
+    const int N = dom.n, m = dom.m;
+    if (!affinity_rows_shape_ok(n_rows, N, G, "k_aff_qrows")) return PC_ERR_ARG;
+    if (m < 1 || r0 < 0 || (int64_t)r0 + m > n_rows || Lp != (int64_t)m * N) {
+        pc_set_error("k_aff_qrows: a slab of %d x %d at query row %d of %d is not %lld values", m, N, r0, n_rows, (long long)Lp);
+        return PC_ERR_ARG;
+    }
+    PcAffinityEntry* const tab = (PcAffinityEntry*)state;
+    PcAffinityEntry* const gain = tab + (size_t)n_rows * (size_t)G;
+    hipLaunchKernelGGL(k_aff_qrows, dim3((unsigned)m), dim3(AF_THREADS), (size_t)G * 16, st, vals, dom, r0, group, G, tab, (unsigned long long*)(gain + N));
+    int rc = pc_launch_check("k_aff_qrows");
+    if (rc != PC_OK) return rc;
+    if (between) PC_HIP(hipEventRecord(between, st));
+    if (!want_gain) return PC_OK;
+    hipLaunchKernelGGL(k_aff_qcols, dim3((unsigned)((N + AF_THREADS - 1) / AF_THREADS)), dim3(AF_THREADS), 0, st, vals, dom, group, gain);
+    return pc_launch_check("k_aff_qcols");
+}
+
+int pc_launch_affinity_rows_finish(const void* state, const int32_t* rows, const int32_t* group, const int32_t* goff, const int32_t* qcount, int n_rows, int N,
+                                   int G, int invert, void* out, int want_table, int want_gain, hipStream_t st) {
+    if (!affinity_rows_shape_ok(n_rows, N, G, "k_aff_qfinish")) return PC_ERR_ARG;
+    const unsigned blocks = (unsigned)((n_rows + AF_WAVES - 1) / AF_WAVES) + (want_gain ? (unsigned)((N + AF_THREADS - 1) / AF_THREADS) : 0u);
+    hipLaunchKernelGGL(k_aff_qfinish, dim3(blocks), dim3(AF_THREADS), 0, st, (const PcAffinityEntry*)state, rows, group, goff, qcount, n_rows, N, G,
+                       invert ? 1 : 0, pc_affinity_out_view(out, n_rows, G, want_table), pc_affinity_gain_view(out, n_rows, N, G, want_table, want_gain));
+    return pc_launch_check("k_aff_qfinish");
 }

@@ -302,6 +302,34 @@ int pc_launch_affinity_cols(const double* vals, int64_t Lp, const PcShard& sh, i
 int pc_launch_affinity_merge(void* tab, const void* staged, int n_foreign, int N, int G, hipStream_t st);
 // the result into out (pc_affinity_out_bytes); invert: the table holds distances and out takes the similarity statement
 int pc_launch_affinity_finish(const void* tab, const int32_t* group, const int32_t* goff, int N, int G, int invert, void* out, int want_table, hipStream_t st);
+// The rows form (pc_fill_rows_affinity): n_rows query genomes against the groups.  The resident state is one allocation of
+// pc_affinity_rows_state_bytes: PcAffinityEntry[n_rows][G] (row k the query rows[k]) | PcAffinityEntry gain[N] (what the queries add to an
+// old genome's own entry; used with want_gain only) | the 8-byte violation count.  The result is PcAffinityOut over n_rows rows
+// (pc_affinity_out_bytes(n_rows, G, want_table)) with, want_gain only, PcAffinityGainOut over N genomes behind it (16 N bytes).
+struct PcAffinityGainOut { long long* sum; int32_t *lo, *hi; };      // [N]; all NULL: the gain was not asked for
+static inline size_t pc_affinity_rows_entries(int n_rows, int N, int G) { return (size_t)n_rows * (size_t)G + (size_t)N; }
+static inline size_t pc_affinity_rows_state_bytes(int n_rows, int N, int G) { return pc_affinity_rows_entries(n_rows, N, G) * sizeof(PcAffinityEntry) + 8; }
+static inline size_t pc_affinity_rows_out_bytes(int n_rows, int N, int G, int want_table, int want_gain) {
+    return pc_affinity_out_bytes(n_rows, G, want_table) + (want_gain ? (size_t)N * 16 : 0);
+}
+static inline PcAffinityGainOut pc_affinity_gain_view(void* base, int n_rows, int N, int G, int want_table, int want_gain) {
+    PcAffinityGainOut o{};
+    if (want_gain) {
+        o.sum = (long long*)((char*)base + pc_affinity_out_bytes(n_rows, G, want_table));
+        o.lo = (int32_t*)(o.sum + (size_t)N); o.hi = o.lo + (size_t)N;
+    }
+    return o;
+}
+// every entry of the state empty, the count 0
+int pc_launch_affinity_rows_init(void* state, int n_rows, int N, int G, hipStream_t st);
+// one rows slab (dom: f64[m][N] at vals, query rows r0 .. r0 + m of the call): k_aff_qrows, and with want_gain k_aff_qcols behind it; group on
+// the device, every label in [-1, G).  *between, when not NULL, is recorded between the two launches
+int pc_launch_affinity_rows_slab(const double* vals, int64_t Lp, const PcRowsSlab& dom, int r0, int n_rows, const int32_t* group, int G, void* state,
+                                 int want_gain, hipEvent_t between, hipStream_t st);
+// the result into out (pc_affinity_rows_out_bytes); rows[n_rows], goff[G + 1] (the labelled genomes of each group) and qcount[G] (the
+// query genomes among them) on the device
+int pc_launch_affinity_rows_finish(const void* state, const int32_t* rows, const int32_t* group, const int32_t* goff, const int32_t* qcount, int n_rows, int N,
+                                   int G, int invert, void* out, int want_table, int want_gain, hipStream_t st);
 // residue bytes -> codes on the device (pc_plan.hip): gene k's raw bytes [seq_off[k], seq_off[k+1]) go through the LUT to
 // codes + gene_off[k], padded with PC_PADCODE to a multiple of 16
 struct PcLut { uint8_t v[256]; };

@@ -8,7 +8,7 @@
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
 // own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
-// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest (at the end of the file) grow a stored result by new genomes: the same
+// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest / pc_fill_rows_affinity (at the end of the file) grow a stored result by new genomes: the same
 // descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
 // either slab's pair domain.
 //
@@ -54,9 +54,10 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         if (run.n_groups > PC_BETWEEN_MAX_GROUPS) {
             pc_set_error("%s: n_groups %d is above PC_BETWEEN_MAX_GROUPS = %d", who, run.n_groups, PC_BETWEEN_MAX_GROUPS); return PC_ERR_LIMIT;
         }
+        const int lowest = run.allow_unlabelled ? -1 : 0;                  // (pc_fill_rows_affinity alone: -1 is a member of no group)
         for (int g = 0; g < c->dev.N; ++g)
-            if (run.group[g] < 0 || run.group[g] >= run.n_groups) {
-                pc_set_error("%s: genome %d has label %d, outside [0, %d)", who, g, run.group[g], run.n_groups); return PC_ERR_ARG;
+            if (run.group[g] < lowest || run.group[g] >= run.n_groups) {
+                pc_set_error("%s: genome %d has label %d, outside [%d, %d)", who, g, run.group[g], lowest, run.n_groups); return PC_ERR_ARG;
             }
     }
     if (run.kind == PC_SLAB_TREE && c->dev.N > PC_TREE_MAX_GENOMES) {
@@ -747,7 +748,37 @@ extern "C" int pc_affinity_ranges(const int32_t* goff, int G, int N, int want, i
     if (cap > 0) memcpy(bounds_out, bounds.data(), bounds.size() * 4);
     return (int)bounds.size() - 1;
 }
+// The rows form's begin: the state is n_query x G entries and the gain's N (pc_affinity_rows_state_bytes), goff counts the LABELLED genomes
+// of each group (queries included: the count of entry [k][b] is size[b] - [group[rows[k]] == b]), qcount the query genomes among them
+// (the count of a gain entry).  No query row, or N <= 1: nothing on the device.
+static int affinity_rows_begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N, G = run.n_groups, nq = run.n_query, want = run.want_table ? 1 : 0, gain = run.want_gain ? 1 : 0;
+    const size_t out_bytes = std::max<size_t>(pc_affinity_rows_out_bytes(nq, std::max(N, 0), G, want, gain), 16);
+    c->last_af_ms[2] = 0.f;
+    if ((rc = slab_begin(c, run, c->last_af_ms))) return rc;
+    if (N <= 1 || nq == 0) return c->h_af.ensure(out_bytes);
+    const size_t state_bytes = pc_affinity_rows_state_bytes(nq, N, G), need = state_bytes + (want ? out_bytes : 0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
+    const size_t may = (free_b + c->b_af_tab.cap + c->b_af_out.cap) / 2;
+    if (need > may) {
+        pc_set_error("%s: the table of %d query rows x %d groups and the gain of %d genomes take %zu bytes on the device (16 n_rows n_groups + 16 N + 8%s), above the %zu they may take (half of the free HBM)",
+                     run.who, nq, G, N, need, want ? " and the table's copy for want_table" : "", may);
+        return PC_ERR_LIMIT;
+    }
+    if ((rc = c->h_af.ensure(out_bytes))) return rc;
+    if ((rc = c->b_af_tab.ensure(state_bytes)) || (rc = c->b_af_out.ensure(out_bytes))) return abi_rc(rc);
+    if ((rc = slab_size(c, run))) return rc;
+    std::vector<int32_t> goff((size_t)G + 1, 0), qcount((size_t)G, 0);
+    for (int g = 0; g < N; ++g) if (run.group[g] >= 0) ++goff[(size_t)run.group[g] + 1];
+    for (int b = 0; b < G; ++b) goff[(size_t)b + 1] += goff[b];
+    for (int k = 0; k < nq; ++k) if (run.group[run.query[k]] >= 0) ++qcount[run.group[run.query[k]]];
+    if ((rc = upload_raw(c->b_af_group, run.group, (size_t)N * 4)) || (rc = upload_vec(c->b_af_goff, goff)) || (rc = upload_vec(c->b_af_qcount, qcount))) return rc;
+    return pc_launch_affinity_rows_init(c->b_af_tab.p, nq, N, G, c->stream);
+}
 int PcAffinityFill::begin(pc_ctx* c, PcSlabRun& run) {
+    if (run.rows_form) return affinity_rows_begin(c, run);
     int rc = PC_OK;
     const int N = c->dev.N, G = run.n_groups, want = run.want_table ? 1 : 0;
     const size_t out_bytes = pc_affinity_out_bytes(std::max(N, 1), G, want);
@@ -787,9 +818,21 @@ static int affinity_add_pass_times(pc_ctx* c, const PcSlabRun& run) {
     c->last_af_ms[0] += x; c->last_af_ms[2] += y;
     return PC_OK;
 }
-// (there is no rows form: a rows slab is refused)
+// A rows slab (pc_fill_rows_affinity) goes through the rows form's two passes: k_aff_qrows, and with want_gain k_aff_qcols.
 int PcAffinityFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
-    if (dom.is_rows) { pc_set_error("%s: an affinity fill has no rows form", run.who); return PC_ERR_ARG; }
+    if (dom.is_rows != run.rows_form) { pc_set_error("%s: a slab of the other pair domain", run.who); return PC_ERR_ARG; }
+    if (dom.is_rows) {
+        int rc = PC_OK;
+        hipStream_t st = c->stream;
+        const int r0 = (int)(dom.rows.rows - c->b_rq_rows.as<int32_t>());     // (the rows walk hands the slab's stretch of the call's rows)
+        if ((rc = affinity_add_pass_times(c, run))) return rc;
+        if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[0], st));
+        if ((rc = pc_launch_affinity_rows_slab(slab, Lp, dom.rows, r0, run.n_query, c->b_af_group.as<int32_t>(), run.n_groups, c->b_af_tab.p, run.want_gain,
+                                               run.timed ? c->ev_slab[1] : nullptr, st))) return rc;
+        if (run.timed) PC_HIP(hipEventRecord(c->ev_slab[4], st));
+        run.pending = true;
+        return mark_work(c, st);
+    }
     if (c->h_owned.empty() || c->h_owned.back() - c->h_owned.front() + 1 != dom.shard.nown) { pc_set_error("%s: a slab of targets that are not consecutive", run.who); return PC_ERR_ARG; }
     int rc = PC_OK;
     hipStream_t st = c->stream;
@@ -804,7 +847,39 @@ int PcAffinityFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t 
     run.pending = true;
     return mark_work(c, st);
 }
+// The rows form's end: k_aff_qfinish, ONE D2H of the per-query arrays (and the table, and the gain, where asked for).
+static int affinity_rows_end(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = std::max(c->dev.N, 0), G = run.n_groups, nq = run.n_query, want = run.want_table ? 1 : 0, gain = run.want_gain ? 1 : 0;
+    const PcAffinityOut h = pc_affinity_out_view(c->h_af.p, nq, G, want);
+    const PcAffinityGainOut hg = pc_affinity_gain_view(c->h_af.p, nq, N, G, want, gain);
+    run.af_own_sum = (const int64_t*)h.own_sum; run.af_own_lo = h.own_lo; run.af_own_hi = h.own_hi; run.af_near_group = h.near_group;
+    run.af_near_sum = (const int64_t*)h.near_sum; run.af_near_lo = h.near_lo; run.af_near_hi = h.near_hi;
+    run.af_tab_sum = (const int64_t*)h.tab_sum; run.af_tab_lo = h.tab_lo; run.af_tab_hi = h.tab_hi;
+    run.af_gain_sum = (const int64_t*)hg.sum; run.af_gain_lo = hg.lo; run.af_gain_hi = hg.hi;
+    if (N <= 1 || nq == 0) {                                                // no pair of the call: every entry empty, no group near
+        for (int k = 0; k < nq; ++k) {
+            h.own_sum[k] = h.near_sum[k] = 0; h.own_lo[k] = h.near_lo[k] = INT32_MAX; h.own_hi[k] = h.near_hi[k] = -1;
+            for (int i = 0; i < 3; ++i) h.near_group[(size_t)i * nq + k] = -1;
+            for (int b = 0; want && b < G; ++b) { h.tab_sum[(size_t)k * G + b] = 0; h.tab_lo[(size_t)k * G + b] = INT32_MAX; h.tab_hi[(size_t)k * G + b] = -1; }
+        }
+        for (int g = 0; gain && g < N; ++g) { hg.sum[g] = 0; hg.lo[g] = INT32_MAX; hg.hi[g] = -1; }
+        return PC_OK;
+    }
+    const bool cols_pending = run.timed && run.pending;
+    if ((rc = slab_finish(c, run, c->last_af_ms, c->h_af.p, c->b_af_out.p, pc_affinity_rows_out_bytes(nq, N, G, want, gain), [&](hipStream_t st) {
+            return pc_launch_affinity_rows_finish(c->b_af_tab.p, c->b_rq_rows.as<int32_t>(), c->b_af_group.as<int32_t>(), c->b_af_goff.as<int32_t>(),
+                                                  c->b_af_qcount.as<int32_t>(), nq, N, G, run.bt_invert, c->b_af_out.p, want, gain, st);
+        }))) return rc;
+    if (cols_pending) { float y = 0.f; PC_HIP(hipEventElapsedTime(&y, c->ev_slab[1], c->ev_slab[4])); c->last_af_ms[2] += y; }
+    if (*h.bad) {
+        pc_set_error("%s: %llu pairs of the call hold values that are no millionth in [0, 1]: the table is not defined on them", run.who, *h.bad);
+        return PC_ERR_DATA;
+    }
+    return PC_OK;
+}
 int PcAffinityFill::end(pc_ctx* c, PcSlabRun& run) {
+    if (run.rows_form) return affinity_rows_end(c, run);
     int rc = PC_OK;
     const int N = c->dev.N, G = run.n_groups, want = run.want_table ? 1 : 0;
     const PcAffinityOut h = pc_affinity_out_view(c->h_af.p, std::max(N, 1), G, want);
@@ -1058,6 +1133,20 @@ extern "C" int pc_fill_rows_nearest(pc_ctx* c, int metric, int as_distance, int 
     PcSlabRun run; run.who = "pc_fill_rows_nearest"; run.metric = metric; run.as_distance = as_distance; run.k = k; run.slab_bytes = slab_bytes;
     return pc_slab_call<PcNearestFill>(run, {nbr, val, k_out, n_slabs}, stats,
                                        [&] { return pc_rows_slab_fill<PcNearestFill>(c, run, rows, n_rows, {seed_nbr, seed_val, k_seed}); });
+}
+
+// The rows form of the affinity fill: nothing stored is needed on the device (PcNoSeed) -- the stored partition is `group` itself; what
+// the queries add to the stored own entries is delivered (want_gain) and combined by the caller.  The walk fills distances, as the whole form's.
+extern "C" int pc_fill_rows_affinity(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                                     int want_table, int want_gain, int64_t slab_bytes,
+                                     const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
+                                     const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
+                                     const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi,
+                                     const int64_t** gain_sum, const int32_t** gain_lo, const int32_t** gain_hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_affinity"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.allow_unlabelled = true; run.query = rows; run.want_table = want_table != 0; run.want_gain = want_gain != 0; run.slab_bytes = slab_bytes;
+    const PcPlacementOut out{{own_sum, own_lo, own_hi, near_group, near_sum, near_lo, near_hi, tab_sum, tab_lo, tab_hi, n_slabs}, gain_sum, gain_lo, gain_hi};
+    return pc_slab_call<PcAffinityFill, PcPlacementOut>(run, out, stats, [&] { return pc_rows_slab_fill<PcAffinityFill>(c, run, rows, n_rows, {}); });
 }
 
 // elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by

@@ -148,10 +148,12 @@ struct pc_ctx {
     float last_bt_ms[2] = {0.f, 0.f};       // passes, fold of the last pc_fill_between with stats (pc_last_between_times)
     // pc_fill_affinity: group[N], member[N] (the genomes sorted by (group, index)), goff[G + 1], the column pass's group ranges, the resident
     // table (pc_affinity_table_bytes) and the result (pc_affinity_out_bytes: pc_common.h), the result's pinned host image
-    DevBuf b_af_group, b_af_member, b_af_goff, b_af_range, b_af_tab, b_af_out;
+    // pc_fill_rows_affinity: the same buffers -- group[N] (-1: in no group), goff over the labelled genomes, the resident state in b_af_tab
+    // (pc_affinity_rows_state_bytes), the result in b_af_out / h_af (pc_affinity_rows_out_bytes) -- and qcount[G], the query genomes of each group
+    DevBuf b_af_group, b_af_member, b_af_goff, b_af_range, b_af_tab, b_af_out, b_af_qcount;
     PinnedBuf h_af;                         // the arrays lent out by pc_fill_affinity
     int af_ranges = 0;                      // group ranges of the column pass (b_af_range holds af_ranges + 1 bounds)
-    float last_af_ms[3] = {0.f, 0.f, 0.f};  // row passes, finish, column passes of the last pc_fill_affinity with stats (pc_last_affinity_times)
+    float last_af_ms[3] = {0.f, 0.f, 0.f};  // row passes, finish, column passes of the last pc_fill_affinity / pc_fill_rows_affinity with stats (pc_last_affinity_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -296,6 +298,9 @@ struct PcSlabRun {
     int n_groups = 0;                       // ... and their range
     bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold / finish inverts
     bool want_table = false;                // affinity: the whole [N][n_groups] table is delivered beside the O(N) arrays
+    bool allow_unlabelled = false;          // affinity, rows form: a label may be -1, a member of no group
+    bool want_gain = false;                 // affinity, rows form: what the queries add to the old genomes' own entries is delivered, [N]
+    const int32_t* query = nullptr;         // affinity, rows form: the caller's rows[n_query], host memory (begin counts the queries of each group)
     int64_t slab_bytes = 0;
     bool timed = false;                     // the caller asked for stats: events around the passes over a slab
     int kk = 0;                             // nearest: min(k, N - 1), at least 0 (pc_slab_check)
@@ -313,6 +318,8 @@ struct PcSlabRun {
     const int64_t *af_own_sum = nullptr, *af_near_sum = nullptr, *af_tab_sum = nullptr;      // affinity: [N] / [N] / [N][n_groups] or NULL
     const int32_t *af_own_lo = nullptr, *af_own_hi = nullptr, *af_near_group = nullptr, *af_near_lo = nullptr, *af_near_hi = nullptr;
     const int32_t *af_tab_lo = nullptr, *af_tab_hi = nullptr;
+    const int64_t* af_gain_sum = nullptr;   // affinity, rows form with want_gain: [N], else NULL
+    const int32_t *af_gain_lo = nullptr, *af_gain_hi = nullptr;
     int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
@@ -320,7 +327,7 @@ struct PcSlabRun {
 // The output shapes and the seeds are hidden, and pc_slab_call is static: however their members are inlined, the library's list of
 // dynamic symbols stays what it was before they had names.
 #pragma GCC visibility push(hidden)
-// The five output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
+// The output shapes.  An edge list's count is as wide as its entry point declares it: int64_t (edges), int32_t (tree).
 template <class Count> struct PcEdgeOut {
     const int32_t **src, **tgt; const double** val; Count* n_edges; int32_t* n_slabs;
     bool all() const { return src && tgt && val && n_edges && n_slabs; }
@@ -359,6 +366,12 @@ struct PcGenomeTableOut {
         *near_sum = run.af_near_sum; *near_lo = run.af_near_lo; *near_hi = run.af_near_hi;
         *tab_sum = run.af_tab_sum; *tab_lo = run.af_tab_lo; *tab_hi = run.af_tab_hi; *n_slabs = run.n_slabs;
     }
+};
+struct PcPlacementOut {                     // the rows form of the affinity fill: the per-query arrays, and the gain of the old genomes
+    PcGenomeTableOut rows; const int64_t** gain_sum; const int32_t **gain_lo, **gain_hi;
+    bool all() const { return rows.all() && gain_sum && gain_lo && gain_hi; }
+    void clear() const { rows.clear(); if (gain_sum) *gain_sum = nullptr; if (gain_lo) *gain_lo = nullptr; if (gain_hi) *gain_hi = nullptr; }
+    void take(const PcSlabRun& run) const { rows.take(run); *gain_sum = run.af_gain_sum; *gain_lo = run.af_gain_lo; *gain_hi = run.af_gain_hi; }
 };
 // The seeds: the caller's arguments first (an entry point brace-initialises them), then what pack() made of them.
 struct PcNoSeed {                           // edges: a stored list needs nothing on the device, the caller merges the two lists
@@ -403,7 +416,7 @@ PC_SLAB_FILL(PcAffinityFill, PcSlabDomain, "affinity", "an affinity fill", PC_SL
 // What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into
 // the run (whose call fields the entry point has set), drive(), and on PC_OK the results into the outputs and the run's own stats
 // into stats[0] (several devices: the root's; multi_slab_fill writes the others').
-template <class Fill, class Drive> static int pc_slab_call(PcSlabRun& run, const typename Fill::Out& out, pc_stats* stats, Drive drive) {
+template <class Fill, class Out = typename Fill::Out, class Drive> static int pc_slab_call(PcSlabRun& run, const Out& out, pc_stats* stats, Drive drive) {
     out.clear();
     run.kind = Fill::kind; run.outputs = out.all(); run.timed = stats != nullptr;
     const int rc = drive();

@@ -79,7 +79,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
-           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values"]
+           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -183,6 +183,11 @@ def load():
                                    ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                    ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                    ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_affinity.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                        ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                        ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                        ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                        ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_affinity_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_affinity_block.argtypes = []
     L.pc_affinity_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -973,6 +978,53 @@ class Context(_SlabFills):
             k_seed = int(s_nbr.shape[1])
         args = (int(bool(as_distance)), int(k), prow, n_rows, self._seed_ptr(s_nbr, _i32p), self._seed_ptr(s_val, _f64p), k_seed, int(slab_bytes))
         return self._fill_lists(self._ROWS_CALL, metric, args, want_stats, borrow)
+
+    def fill_rows_affinity(self, metric, group, rows, n_groups=None, as_distance=True, slab_bytes=0, want_table=False, want_gain=False,
+                           want_stats=False, borrow=False):
+        """New genomes placed against the groups of a stored partition: :meth:`fill_affinity`'s statement for the query genomes of
+        ``rows`` alone -- ``len(rows) * N`` pairs filled instead of ``N (N - 1) / 2``.  ``group[g]`` in ``[0, n_groups)`` is genome
+        g's group or -1: a member of no group (here only; ``n_groups`` defaults to the largest label + 1, at least 1).  Returns a dict
+        of arrays over the QUERIES, in the order of ``rows``: ``own_sum`` (int64), ``own_lo``, ``own_hi`` (int32) ``[n_rows]`` -- empty
+        for an unlabelled query; ``near_group`` (int32 ``[3, n_rows]``), ``near_sum``, ``near_lo``, ``near_hi`` as :meth:`fill_affinity`
+        gives them per genome (an unlabelled query has no own group: every non-empty group is a candidate); ``table``: None, or with
+        ``want_table`` the ``(sum, lo, hi)`` of ``[n_rows, G]`` arrays, entry ``[k, b]`` counting ``size[b] - (group[rows[k]] == b)``
+        pairs, ``size`` over the labelled genomes, queries included; ``gain``: None, or with ``want_gain`` the ``(sum, lo, hi)`` of
+        ``[N]`` arrays -- for an old labelled genome what the queries of its own group add to its own entry (``stored own + gain`` is
+        the own entry of :meth:`fill_affinity` over the whole collection), empty elsewhere.  With every genome labelled, query k's
+        entries equal entry ``rows[k]`` of :meth:`fill_affinity`'s, integer for integer.  ``as_distance``, ``slab_bytes`` (ranges of
+        ``max(1, slab_bytes // 8 // N)`` rows), ``borrow`` and ``want_stats`` (``stats``: with ``n_groups``, ``n_slabs``, ``ms_rows``,
+        ``ms_cols``, ``ms_finish``) as there.  One GPU."""
+        if group is None:
+            raise ValueError("fill_rows_affinity: group is None")
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        n = self.n_genomes
+        if group.shape[0] != n:
+            raise ValueError(f"fill_rows_affinity: group holds {group.shape[0]} labels for {n} genomes")
+        if n_groups is None:
+            n_groups = max(int(group.max()) + 1, 1) if group.size else 1
+        n_groups = int(n_groups)
+        rows, prow, n_rows = self._rows_arg(rows)
+        pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
+        cells = [t() for t in (_i64p, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i64p, _i32p, _i32p)]
+        nsl = ctypes.c_int32(0)
+        stats = self._slab_call(self._ROWS_CALL + "affinity", metric, int(bool(as_distance)), pgroup, n_groups, prow, n_rows, int(bool(want_table)),
+                                int(bool(want_gain)), int(slab_bytes), *(ctypes.byref(c) for c in cells), ctypes.byref(nsl))
+        names = ("own_sum", "own_lo", "own_hi", "near_group", "near_sum", "near_lo", "near_hi")
+        dtypes = (np.int64, np.int32, np.int32, np.int32, np.int64, np.int32, np.int32)
+        triple = (np.int64, np.int32, np.int32)
+        out = {}
+        for name, cell, dtype in zip(names, cells, dtypes):
+            shape = (3, n_rows) if name == "near_group" else (n_rows,)
+            out[name] = self._lend(cell, shape, borrow) if n_rows and cell else np.empty(shape, dtype=dtype)
+        out["table"] = out["gain"] = None
+        if want_table:
+            out["table"] = tuple(self._lend(cell, (n_rows, n_groups), borrow) if n_rows and cell else np.empty((n_rows, n_groups), dtype=dtype)
+                                 for cell, dtype in zip(cells[7:10], triple))
+        if want_gain:
+            out["gain"] = tuple(self._lend(cell, (n,), borrow) if n and cell else np.empty((n,), dtype=dtype) for cell, dtype in zip(cells[10:], triple))
+        if want_stats:
+            out["stats"] = self._slab_stats("affinity", stats, n_groups=n_groups, n_slabs=int(nsl.value))
+        return out
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -34,6 +34,8 @@ from phamclust_amd.results.linkage import (BETWEEN_MAX_GROUPS, MILLION, _EMPTY_H
                                            between_from_file, between_to_file)
 from phamclust_amd.results.affinity import (AFFINITY_KINDS, _AFFINITY_COLUMNS, GroupAffinity, affinity_de_novo, affinity_from_file,  # noqa: F401
                                             affinity_to_file)
+from phamclust_amd.results.placement import (GroupPlacement, GrownOwn, _PLACEMENT_COLUMNS, own_similarity_text, placement_de_novo,  # noqa: F401
+                                             placement_from_file, placement_report, placement_to_file, stored_fit_from_file)
 
 
 def _outside_in_index_iterator(num_indices):

@@ -122,10 +122,11 @@ def _fill_done(stats, metric, names, record, t0, log, **own):
     logging.debug(log(stats, record, fill_s))
 
 
-def _de_novo_route(genomes, func, caller, fill, log, advice="the dense route, matrix_de_novo, serves another callable"):
-    """The frame the four ``*_de_novo`` routes share: ``upload_for_fills`` over the devices at hand (``advice``: its refusal's), the clock,
-    ``fill(ctx, metric)`` -> ``(*arrays, stats)``, ``LAST_FILL`` and the log line (``_fill_done``).  Returns ``(names, arrays)``."""
-    ctx, metric, names, record = upload_for_fills(genomes, func, caller, several=True, advice=advice)
+def _de_novo_route(genomes, func, caller, fill, log, advice="the dense route, matrix_de_novo, serves another callable", several=True):
+    """The frame the ``*_de_novo`` routes share: ``upload_for_fills`` over the devices at hand (``advice``: its refusal's; ``several=False``: a
+    one-GPU fill, ``placement_de_novo``'s), the clock, ``fill(ctx, metric)`` -> ``(*arrays, stats)``, ``LAST_FILL`` and the log line
+    (``_fill_done``).  Returns ``(names, arrays)``."""
+    ctx, metric, names, record = upload_for_fills(genomes, func, caller, several=several, advice=advice)
     t0 = time.perf_counter()
     *arrays, stats = fill(ctx, metric)
     _fill_done(stats, metric, names, record, t0, log, genome_pairs=record["genome_pairs"], n_gpus=record["n_gpus"])

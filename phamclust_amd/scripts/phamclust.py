@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -293,6 +293,52 @@ class _Run:
             log.info(f"parity: {_metrics.parity_note(self.metric)}")
         target = self.outdir / f"nearest_{self.metric}.tsv"
         nearest_to_file(found, target)
+        log.info(f"wrote {target.name}")
+        return found
+
+    # 2, --place
+    def place(self, path, verify=4):
+        """Stage 2 as a placement: ``path`` is the ``cluster_fit_<metric>.tsv`` of an earlier run over a subset of the genomes; the genomes
+        it lacks are placed against its clusters by ONE rows form of the affinity fill, and only ``placement_<metric>.tsv`` is written
+        (``placement_report``).  The new genomes stay in no cluster, so the own entry of an old genome is over old members only:
+        ``verify`` old genomes ride along as queries and their own-similarity text must be the file's, byte for byte -- the guard against
+        a stale file, another metric or changed genomes."""
+        self.banner(2, f"{self.metric} placement of new genomes (rows form of the affinity fill)")
+        t0 = time.perf_counter()
+        names = [g.name for g in self.genomes]
+        try:
+            clusters, groups, own = stored_fit_from_file(path)
+            there = set(names)
+            missing = next((name for group in groups for name in group if name not in there), None)
+            if missing is not None:
+                raise KeyError(f"genome '{missing}' of the file is not among the genomes of the input")
+            if len(groups) > _matrix.BETWEEN_MAX_GROUPS:
+                raise ValueError(f"{len(groups):,} clusters are above the fill's {_matrix.BETWEEN_MAX_GROUPS:,} groups")
+            new = [name for name in names if name not in own]
+            old = [name for name in names if name in own]
+            several = {name for group in groups if len(group) > 1 for name in group}        # (a genome alone in its cluster has no own similarity to hold)
+            pool = [name for name in old if name in several] or old
+            n_verify = max(0, min(int(verify), len(pool)))
+            checked = sorted({pool[(i * len(pool)) // n_verify] for i in range(n_verify)}, key=names.index)
+            found = placement_de_novo(self.genomes, METRICS[self.metric], groups, queries=new + checked, as_distance=True)
+            for name in checked:
+                if own_similarity_text(found, name) != own[name]:
+                    raise ValueError(f"genome '{name}': the file holds the own similarity {own[name]}, the {self.metric} fill gives "
+                                     f"{own_similarity_text(found, name)}: the file was not written with this metric from these genomes")
+        except (ValueError, KeyError, OSError) as exc:
+            log.error(f"--place {path}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
+            print("placing the new genomes failed - check log for details")
+            sys.exit(1)
+        st = _matrix.LAST_FILL
+        log.info(f"placed {len(new):,} new genomes against {len(groups):,} clusters of {len(old):,} genomes ({len(checked)} of them verified): "
+                 f"{st.get('genome_pairs', 0):,} pairs filled instead of {len(names) * (len(names) - 1) // 2:,} in {time.perf_counter() - t0:.3f} s "
+                 f"(pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, fill+passes+D2H {st.get('fill_s', 0.0):.3f}; kernels "
+                 f"{st.get('ms_total', 0.0):.3f} ms, row passes {st.get('ms_rows', 0.0):.3f} ms, finish {st.get('ms_finish', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        target = self.outdir / f"placement_{self.metric}.tsv"
+        with open(target, "w") as handle:
+            handle.write("\n".join(placement_report(found, clusters, new)) + "\n")
         log.info(f"wrote {target.name}")
         return found
 
@@ -591,7 +637,7 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, grow_nearest=None, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -605,7 +651,11 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     ``grow_nearest``: with ``nearest``, the ``nearest_<metric>.tsv`` of an earlier run over a subset of the genomes (``--grow-nearest``),
     grown the same way; ``cluster_table``: after the clustering, one between-groups fill over the final clusters and its three outputs
     (``--cluster-table``; with the whole pipeline only, on either route); ``cluster_fit``: after the clustering, one affinity fill over the
-    final clusters and its two files (``--cluster-fit``; on the same terms)."""
+    final clusters and its two files (``--cluster-fit``; on the same terms); ``place``: stop after placing the genomes that a
+    ``cluster_fit_<metric>.tsv`` of an earlier run lacks against its clusters, and write only ``placement_<metric>.tsv`` (``--place``)."""
+    if place is not None and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
+                              grow_nearest is not None or cluster_table or cluster_fit):
+        raise ValueError("place cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, cluster_table or cluster_fit")
     if cluster_fit and (adjacency_only or components_only or tree or nearest is not None or extend is not None):
         raise ValueError("cluster_fit cannot be combined with adjacency_only, components_only, tree, nearest or extend")
     if cluster_table and (adjacency_only or components_only or tree or nearest is not None or extend is not None):
@@ -655,6 +705,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["clusters"] = "with their table (--cluster-table: a between-groups fill)"
     if cluster_fit:
         settings["cluster fit"] = "written (--cluster-fit: an affinity fill)"
+    if place is not None:
+        settings["place"] = f"only, against the clusters of {place}"
     if grow is not None:
         settings["grow"] = grow
     if grow_nearest is not None:
@@ -689,6 +741,13 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             sys.exit(1)
         run.nearest(nearest)
         run.banner(3, "done (--nearest: no clustering)")
+        return
+    if place is not None:
+        if run.world > 1:
+            log.error("--place is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.place(place)
+        run.banner(3, "done (--place: no clustering)")
         return
     if tree:
         if run.world > 1:
@@ -762,6 +821,8 @@ def gpus_plan(args, route, packed):
     them, so under PHAMCLUST_MULTI=launcher they stay on one GPU."""
     if getattr(args, "grow_nearest", None) is not None:
         return 1, "one", "--grow-nearest fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
+    if getattr(args, "place", None) is not None:
+        return 1, "one", "--place fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
     if getattr(args, "grow", None) is not None:
         return 1, "one", "--grow fills only the pairs of the new genomes, which is a one-GPU call: the matrix stage stays on one GPU"
     if args.extend is not None:
@@ -863,7 +924,7 @@ def _run(args, argv):
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
-                  cluster_fit=args.cluster_fit)
+                  cluster_fit=args.cluster_fit, place=args.place)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
