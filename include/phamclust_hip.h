@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 168   /* 0.5.17: pc_fill_rows_affinity (new genomes against stored clusters) */
+#define PC_VERSION 169   /* 0.5.18: pc_fill_rows_between (a stored between-groups table grown by new genomes) */
 
 typedef enum {
     PC_OK = 0,
@@ -98,12 +98,12 @@ int pc_test_hooks(void);
  * affinity always fill distances and invert at the end, the other four fill the direction asked for.  The pointer is stored process-wide,
  * not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets or clears it
  * between calls only.  A walk that finds n_pairs != N (N - 1) / 2 refuses with PC_ERR_ARG.  The rows walk (pc_fill_rows_edges,
- * _components, _tree, _nearest, _affinity) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
+ * _components, _tree, _nearest, _affinity, _between) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
  * In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
 int pc_hook_slab_values(const double* values, int64_t n_pairs);
 /* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 167): values, f64[n_rows][n], row k the values of the call's query
  * genome rows[k] to every genome, stands for "the slab as filled" in every rows walk of the process from now on: pc_fill_rows_edges,
- * _components, _tree, _nearest, _affinity.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
+ * _components, _tree, _nearest, _affinity, _between.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
  * values + r0 * n, m * n doubles, by one host-to-device copy on the walk's stream -- EVERY element of it: the diagonal [k][rows[k]] and
  * both copies of a pair of two query genomes are the caller's too, so a test decides what the elements hold that no pass may read.
  * pc_fill_rows, pc_fill_rows_dev and the triangular walk do not read it; the two hooks are independent.  The pointer is stored
@@ -410,11 +410,12 @@ int pc_tree_key_parts(uint64_t key, int32_t* micro, int32_t* s, int32_t* t);
  * GPUs share the walk through pc_multi_fill_between), aai / peq before pc_upload_residues.  PC_ERR_DATA: as for a whole fill, and a
  * slab value that is no millionth in [0, 1].  On a refusal the four pointers are NULL and *n_slabs is 0.  The caller's unsharded state
  * is back in force when the call returns, whatever it returns.  Runs on the context's own stream and returns with everything finished.
+ * The rows form is pc_fill_rows_between, below; this call keeps refusing a label of -1.
  */
 #define PC_BETWEEN_MAX_GROUPS 2048
 int pc_fill_between(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
                     const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
-/* Test / tuning hook, of the last pc_fill_between call: *ms_reduce the passes summed over its slabs, *ms_finish the fold (HIP events; 0
+/* Test / tuning hook, of the last pc_fill_between or pc_fill_rows_between call: *ms_reduce the passes summed over its slabs, *ms_finish the fold (HIP events; 0
  * unless the call was given stats); either pointer may be NULL. */
 int pc_last_between_times(const pc_ctx* ctx, float* ms_reduce, float* ms_finish);
 int pc_between_max_groups(void);    /* PC_BETWEEN_MAX_GROUPS */
@@ -569,6 +570,41 @@ int pc_fill_rows_affinity(pc_ctx* ctx, int metric, int as_distance, const int32_
                           const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
                           const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi,
                           const int64_t** gain_sum, const int32_t** gain_lo, const int32_t** gain_hi, int32_t* n_slabs, pc_stats* stats);
+
+/*
+ * The rows form of the between-groups fill (PC_VERSION 169): a stored table grown by new genomes.  rows[n_rows] -- pc_fill_rows'
+ * contract, the rows walk and its slabs (f64[m][N], slab_bytes) as above -- are the QUERY genomes (the new ones); group[N] / n_groups
+ * is the partition of the grown collection, and group[g] may be -1, for a query or an old genome: a member of no group, in no pair of
+ * the table.  The pairs of the call are those with a query genome at one end and both ends labelled; a pair of two queries is taken
+ * once.  Values enter as millionths of the DISTANCE under pc_fill_between's rule, as_distance == 0 inverts in the fold.
+ *   The seed: seed_sum / seed_count (int64) and seed_lo / seed_hi (int32), [n_groups][n_groups] in the result layout and IN THE CALL'S
+ *       DIRECTION -- what pc_fill_between delivers for the same labels over the genomes that are no query rows; all four NULL: no seed.
+ *       Counts and sums add, minima and maxima only move outward, everything is an integer: seed (+) the pairs of the call IS the
+ *       table of the grown collection.  The seed is checked on the host before any GPU work, PC_ERR_ARG naming the entry: not
+ *       symmetric; emptiness inconsistent (count 0 goes with sum 0, lo INT32_MAX, hi -1, and a full entry has none of those); lo > hi or
+ *       either outside [0, 10^6]; sum outside [count lo, count hi]; a count that is not the partition's own -- with old[b] the genomes
+ *       labelled b that are no query rows, count[a][b] must be old[a] old[b], and old[a] (old[a] - 1) / 2 on the diagonal: every pair
+ *       of a fill is counted, so a table of another partition or genome set fails here.  Some but not all of the four: PC_ERR_ARG.
+ * Contract: (a) every genome labelled and the seed pc_fill_between's over the non-query genomes with the same labels -> the result is
+ * pc_fill_between over the whole collection, integer for integer, for any slab cut and both directions; (b) no seed and rows = all
+ * genomes -> pc_fill_between itself; (c) no seed -> the table over exactly the pairs with at least one labelled query end and both
+ * ends labelled.
+ * On the device: the seed, complemented to distances where as_distance == 0, replaces the empty accumulator (entries a <= b; the fold
+ * adds the two orientations); each slab of query rows goes through ONE pass, k_between_qrows -- grid (rows of the slab, segments of
+ * pc_between_segment() elements of a row), a workgroup per segment of one row, the same LDS table, wave reduction and relaxed
+ * agent-scope atomics without a return value as k_between_rows; the value of an element that is no pair of the call (the diagonal, the
+ * second copy of a pair of two queries, a column of an unlabelled genome, the row of an unlabelled query) is never looked at, so a
+ * refused value is counted once per PAIR (PC_ERR_DATA carries the count) -- then k_between_fold as it is and ONE D2H copy.
+ * Outputs, *n_slabs, stats and pc_last_between_times as pc_fill_between's.  n_rows == 0: the seed comes back unchanged (without one:
+ * every entry empty).  N <= 1: every entry empty, and a seed must be all empty.  n_rows == N is allowed.  Refusals in
+ * pc_fill_between's order -- the label check admits -1 -- then rows (pc_fill_rows' PC_ERR_ARG), then the seed; all before anything
+ * is launched, with the outputs nulled, and the context stays usable.  One GPU: a sharded context is refused (PC_ERR_STATE); there is
+ * no pc_multi_* form, n_groups stays within PC_BETWEEN_MAX_GROUPS, and genomes cannot be REMOVED from a stored table (a minimum cannot
+ * be un-taken).
+ */
+int pc_fill_rows_between(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                         const int64_t* seed_sum, const int64_t* seed_count, const int32_t* seed_lo, const int32_t* seed_hi, int64_t slab_bytes,
+                         const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
 
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */

@@ -94,6 +94,14 @@ _OPTIONS = (
                                                                       "genome the nearest cluster by mean, by nearest and by farthest member, with the "
                                                                       "three similarities and the clusters' sizes -- filling only the new genomes' "
                                                                       "pairs, on one GPU; no matrix, no clustering")),
+    (None, "-b", "--grow-table", dict(type=pathlib.Path, default=None, help="with --place FIT: FILE is the cluster_table_<metric>.tsv of the run that "
+                                                                           "wrote FIT; after the placement every new genome joins its nearest cluster by "
+                                                                           "mean and the stored table is grown by the new genomes' pairs alone (exact: "
+                                                                           "counts and sums add, extremes only move outward); writes "
+                                                                           "cluster_table_<metric>.tsv beside placement_<metric>.tsv")),
+    (None, "-j", "--join-min", dict(type=float, default=None, help="with --grow-table: a new genome whose nearest mean similarity lies below SIM "
+                                                                   "joins no cluster and becomes a singleton group of its own, appended after "
+                                                                   "the stored groups in genome order")),
     (None, "-e", "--edge-thresh", dict(type=float, default=None, help="with --adjacency-only: keep the pairs of at least this similarity "
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
@@ -174,6 +182,13 @@ def parse_args(argv=None):
                 parser.error(f"--place stops after a placement of its own; it cannot be combined with {flag}")
         if args.gpus > 1:
             parser.error("--place: placing new genomes is a one-GPU call; it cannot be combined with --gpus N")
+    if args.grow_table is not None and args.place is None:
+        parser.error("--grow-table FILE grows the cluster table of the run that wrote the --place FIT file; give --place FIT")
+    if args.join_min is not None:
+        if args.grow_table is None:
+            parser.error("--join-min SIM decides which new genomes join a cluster of --grow-table FILE; give --grow-table FILE")
+        if not 0.0 <= args.join_min <= 1.0:              # (also refuses NaN)
+            parser.error("--join-min is a similarity in [0, 1]")
     if args.cluster_table:
         for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--tree", args.tree),
                             ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):

@@ -257,6 +257,8 @@ __host__ __device__ static inline PcBetweenAcc pc_between_view(void* base, int G
 int pc_launch_between_init(void* acc, int G, hipStream_t st);
 // one slab: vals f64[Lp] in the shard's layout, max_row its longest row; group: [N] on the device, every label in [0, G)
 int pc_launch_between_rows(const double* vals, int64_t Lp, const PcShard& sh, int64_t max_row, const int32_t* group, int G, void* acc, hipStream_t st);
+// one rows slab (dom: f64[m][n] at vals): the live elements of every query row with a label; group: [N] on the device, every label in [-1, G)
+int pc_launch_between_qrows(const double* vals, int64_t Lp, const PcRowsSlab& dom, const int32_t* group, int G, void* acc, hipStream_t st);
 // the accumulators of other devices added into acc: staged[n_foreign] of pc_between_bytes(G) each
 int pc_launch_between_merge(void* acc, const void* staged, int n_foreign, int G, hipStream_t st);
 // the square made symmetric into out (the result layout), empty entries as lo = INT32_MAX, hi = -1; invert: the accumulator holds

@@ -8,7 +8,7 @@
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
 // own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
-// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest / pc_fill_rows_affinity (at the end of the file) grow a stored result by new genomes: the same
+// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest / pc_fill_rows_affinity / pc_fill_rows_between (at the end of the file) grow a stored result by new genomes: the same
 // descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
 // either slab's pair domain.
 //
@@ -54,7 +54,7 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         if (run.n_groups > PC_BETWEEN_MAX_GROUPS) {
             pc_set_error("%s: n_groups %d is above PC_BETWEEN_MAX_GROUPS = %d", who, run.n_groups, PC_BETWEEN_MAX_GROUPS); return PC_ERR_LIMIT;
         }
-        const int lowest = run.allow_unlabelled ? -1 : 0;                  // (pc_fill_rows_affinity alone: -1 is a member of no group)
+        const int lowest = run.allow_unlabelled ? -1 : 0;                  // (the rows forms alone: -1 is a member of no group)
         for (int g = 0; g < c->dev.N; ++g)
             if (run.group[g] < lowest || run.group[g] >= run.n_groups) {
                 pc_set_error("%s: genome %d has label %d, outside [%d, %d)", who, g, run.group[g], lowest, run.n_groups); return PC_ERR_ARG;
@@ -637,7 +637,8 @@ extern "C" int pc_last_tree_rounds(const pc_ctx* c, int32_t* live_rounds, int32_
 // k_between_rows (pc_between.hip), over an accumulator that stays on the device from the first slab to the last; nothing is read back
 // per slab.  After the last slab: k_between_fold, then one D2H of the four arrays and the 8-byte violation count behind them.  The walk
 // always fills distances (the entry points set as_distance = 1 and keep what the caller asked for in bt_invert): a similarity table is
-// the distance table inverted by the fold, as SymMatrix.invert() inverts a matrix.
+// the distance table inverted by the fold, as SymMatrix.invert() inverts a matrix.  The rows form, pc_fill_rows_between, seeds the accumulator
+// with a stored table (PcBetweenSeed, with the seeds below) and passes the new genomes' rows through k_between_qrows: begin and end are these.
 int PcBetweenFill::begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
     const int N = c->dev.N, G = run.n_groups;
@@ -649,9 +650,13 @@ int PcBetweenFill::begin(pc_ctx* c, PcSlabRun& run) {
     if ((rc = upload_raw(c->b_bt_group, run.group, (size_t)N * 4))) return rc;
     return pc_launch_between_init(c->b_bt_acc.p, G, c->stream);
 }
-// (there is no rows form: a rows slab is refused)
+// A rows slab (pc_fill_rows_between) goes through the rows form of the pass, k_between_qrows, into the same accumulator.
 int PcBetweenFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
-    if (dom.is_rows) { pc_set_error("%s: a between-groups fill has no rows form", run.who); return PC_ERR_ARG; }
+    if (dom.is_rows != run.rows_form) { pc_set_error("%s: a slab of the other pair domain", run.who); return PC_ERR_ARG; }
+    if (dom.is_rows)
+        return slab_pass(c, run, c->last_bt_ms, [&](hipStream_t st) {
+            return pc_launch_between_qrows(slab, Lp, dom.rows, c->b_bt_group.as<int32_t>(), run.n_groups, c->b_bt_acc.p, st);
+        });
     const int64_t max_row = c->h_owned.empty() ? 0 : (int64_t)c->h_owned.back();      // (ascending targets, row t holds t values)
     return slab_pass(c, run, c->last_bt_ms, [&](hipStream_t st) {
         return pc_launch_between_rows(slab, Lp, dom.shard, max_row, c->b_bt_group.as<int32_t>(), run.n_groups, c->b_bt_acc.p, st);
@@ -1104,6 +1109,67 @@ int PcNearestSeed::install(pc_ctx* c, PcSlabRun& run) const {
     return PC_OK;
 }
 
+// The stored table is the caller's four [G][G] arrays in the result layout and the call's direction.  pack holds every entry to what a
+// fill of `group` over the genomes that are no query rows delivers -- symmetric, empty or full consistently, 0 <= lo <= hi <= 10^6,
+// count lo <= sum <= count hi, and the count the partition's own: old[a] old[b] pairs between two groups, old[a] (old[a] - 1) / 2
+// within one, old[] counting the labelled genomes that are no query -- and packs it as the raw accumulator's image: distances (a
+// similarity seed is complemented: the walk fills distances and the fold inverts back), entries a <= b, the rest empty, so that the
+// fold returns the seed when no row follows.
+int PcBetweenSeed::pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows) {
+    const int given = (sum != nullptr) + (count != nullptr) + (lo != nullptr) + (hi != nullptr);
+    if (given == 0) return PC_OK;
+    if (given != 4) { pc_set_error("%s: %d of the four seed arrays are given (all of seed_sum, seed_count, seed_lo, seed_hi, or none)", run.who, given); return PC_ERR_ARG; }
+    const int N = c->dev.N, G = run.n_groups;
+    const size_t gg = (size_t)G * (size_t)G;
+    std::vector<uint8_t> is_query((size_t)std::max(N, 1), 0);
+    for (int k = 0; k < n_rows; ++k) is_query[rows[k]] = 1;
+    std::vector<int64_t> old((size_t)G, 0);
+    for (int g = 0; g < N; ++g) if (run.group[g] >= 0 && !is_query[g]) ++old[run.group[g]];
+    image.assign(pc_between_bytes(G) / 8, 0ull);
+    const PcBetweenAcc img = pc_between_view(image.data(), G);
+    for (size_t i = 0; i < gg; ++i) img.lo[i] = ~0u;
+    for (int a = 0; a < G; ++a)
+        for (int b = a; b < G; ++b) {
+            const size_t at = (size_t)a * G + b, mirror = (size_t)b * G + a;
+            const int64_t s = sum[at], n = count[at];
+            const int32_t l = lo[at], h = hi[at];
+            const char* why = nullptr;
+            if (sum[mirror] != s || count[mirror] != n || lo[mirror] != l || hi[mirror] != h) why = "is not symmetric";
+            else if (n < 0 || (n == 0) != (s == 0 && l == INT32_MAX && h == -1) || (n != 0 && (l == INT32_MAX || h == -1)))
+                why = "is neither empty (count 0, sum 0, lo INT32_MAX, hi -1) nor full";
+            else if (n && (l < 0 || h > 1000000 || l > h)) why = "does not hold 0 <= lo <= hi <= 10^6";
+            if (why) {
+                pc_set_error("%s: seed entry [%d][%d] (count %lld, sum %lld, lo %d, hi %d) %s", run.who, a, b, (long long)n, (long long)s, (int)l, (int)h, why);
+                return PC_ERR_ARG;
+            }
+            const int64_t want = a == b ? old[a] * (old[a] - 1) / 2 : old[a] * old[b];
+            if (n != want) {
+                pc_set_error("%s: seed entry [%d][%d] counts %lld pairs, the partition has %lld there (%lld and %lld genomes that are no query rows): "
+                             "the stored table is of another partition or another genome set", run.who, a, b, (long long)n, (long long)want,
+                             (long long)old[a], (long long)old[b]);
+                return PC_ERR_ARG;
+            }
+            if (!n) continue;
+            if ((__int128)s < (__int128)n * l || (__int128)s > (__int128)n * h) {
+                pc_set_error("%s: seed entry [%d][%d] (count %lld, sum %lld, lo %d, hi %d) holds a sum outside [count lo, count hi]", run.who, a, b, (long long)n,
+                             (long long)s, (int)l, (int)h);
+                return PC_ERR_ARG;
+            }
+            img.cnt[at] = (unsigned long long)n;
+            if (run.bt_invert) { img.sum[at] = (unsigned long long)(n * 1000000 - s); img.lo[at] = (uint32_t)(1000000 - h); img.hi[at] = (uint32_t)(1000000 - l); }
+            else { img.sum[at] = (unsigned long long)s; img.lo[at] = (uint32_t)l; img.hi[at] = (uint32_t)h; }
+        }
+    return PC_OK;
+}
+// the stored table in place of the empty accumulator, through the pinned result image (end() rewrites it only after the stream has drained)
+int PcBetweenSeed::install(pc_ctx* c, PcSlabRun& run) const {
+    if (image.empty()) return PC_OK;
+    const size_t bytes = pc_between_bytes(run.n_groups);
+    memcpy(c->h_bt.p, image.data(), bytes);
+    PC_HIP(hipMemcpyAsync(c->b_bt_acc.p, c->h_bt.p, bytes, hipMemcpyHostToDevice, c->stream));
+    return PC_OK;
+}
+
 extern "C" int pc_fill_rows_edges(pc_ctx* c, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
                                   const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     PcSlabRun run; run.who = "pc_fill_rows_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
@@ -1147,6 +1213,18 @@ extern "C" int pc_fill_rows_affinity(pc_ctx* c, int metric, int as_distance, con
     run.allow_unlabelled = true; run.query = rows; run.want_table = want_table != 0; run.want_gain = want_gain != 0; run.slab_bytes = slab_bytes;
     const PcPlacementOut out{{own_sum, own_lo, own_hi, near_group, near_sum, near_lo, near_hi, tab_sum, tab_lo, tab_hi, n_slabs}, gain_sum, gain_lo, gain_hi};
     return pc_slab_call<PcAffinityFill, PcPlacementOut>(run, out, stats, [&] { return pc_rows_slab_fill<PcAffinityFill>(c, run, rows, n_rows, {}); });
+}
+
+// The rows form of the between-groups fill: the stored table (PcBetweenSeed) and the pairs that have a query genome at one end are the
+// table of the grown collection, integer for integer -- counts and sums add, extremes only move outward.  Without a seed: the table over
+// those pairs alone.  A label may be -1 (a member of no group: in no pair).  The walk fills distances, as the whole form's.
+extern "C" int pc_fill_rows_between(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                                    const int64_t* seed_sum, const int64_t* seed_count, const int32_t* seed_lo, const int32_t* seed_hi, int64_t slab_bytes,
+                                    const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_between"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.allow_unlabelled = true; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcBetweenFill>(run, {sum, count, lo, hi, n_slabs}, stats,
+                                       [&] { return pc_rows_slab_fill<PcBetweenFill>(c, run, rows, n_rows, {seed_sum, seed_count, seed_lo, seed_hi}); });
 }
 
 // elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by

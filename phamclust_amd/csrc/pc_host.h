@@ -145,7 +145,7 @@ struct pc_ctx {
     // pc_fill_between: group[N], the resident accumulator and the folded table (pc_between_bytes(G) each: pc_common.h), the table's pinned host image
     DevBuf b_bt_group, b_bt_acc, b_bt_out;
     PinnedBuf h_bt;                         // the four arrays lent out by pc_fill_between
-    float last_bt_ms[2] = {0.f, 0.f};       // passes, fold of the last pc_fill_between with stats (pc_last_between_times)
+    float last_bt_ms[2] = {0.f, 0.f};       // passes, fold of the last pc_fill_between / pc_fill_rows_between with stats (pc_last_between_times)
     // pc_fill_affinity: group[N], member[N] (the genomes sorted by (group, index)), goff[G + 1], the column pass's group ranges, the resident
     // table (pc_affinity_table_bytes) and the result (pc_affinity_out_bytes: pc_common.h), the result's pinned host image
     // pc_fill_rows_affinity: the same buffers -- group[N] (-1: in no group), goff over the labelled genomes, the resident state in b_af_tab
@@ -298,7 +298,7 @@ struct PcSlabRun {
     int n_groups = 0;                       // ... and their range
     bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold / finish inverts
     bool want_table = false;                // affinity: the whole [N][n_groups] table is delivered beside the O(N) arrays
-    bool allow_unlabelled = false;          // affinity, rows form: a label may be -1, a member of no group
+    bool allow_unlabelled = false;          // between and affinity, rows forms: a label may be -1, a member of no group
     bool want_gain = false;                 // affinity, rows form: what the queries add to the old genomes' own entries is delivered, [N]
     const int32_t* query = nullptr;         // affinity, rows form: the caller's rows[n_query], host memory (begin counts the queries of each group)
     int64_t slab_bytes = 0;
@@ -393,6 +393,12 @@ struct PcNearestSeed {                      // nearest: the stored lists [N][k_s
     int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
     int install(pc_ctx* c, PcSlabRun& run) const;
 };
+struct PcBetweenSeed {                      // between: the stored table, four [G][G] arrays in the result layout and the call's direction (all NULL:
+    const int64_t *sum, *count; const int32_t *lo, *hi;     // none), as the raw accumulator's image (pc_between_bytes; empty: no seed)
+    std::vector<unsigned long long> image;
+    int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
+    int install(pc_ctx* c, PcSlabRun& run) const;
+};
 #pragma GCC visibility pop
 #define PC_SLAB_FILL(Name, Dom, tag, text, KIND, OUT, SEED)                                                                             \
     struct Name {                                                                                                                       \
@@ -410,7 +416,7 @@ PC_SLAB_FILL(PcEdgesFill, PcSlabDomain, "edges", "an edge-list fill", PC_SLAB_ED
 PC_SLAB_FILL(PcComponentsFill, PcSlabDomain, "components", "a components fill", PC_SLAB_COMPONENTS, PcLabelOut, PcLabelSeed);
 PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill", PC_SLAB_NEAREST, PcListOut, PcNearestSeed);
 PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill", PC_SLAB_TREE, PcEdgeOut<int32_t>, PcTreeSeed);
-PC_SLAB_FILL(PcBetweenFill, PcSlabDomain, "between", "a between-groups fill", PC_SLAB_BETWEEN, PcTableOut, PcNoSeed);
+PC_SLAB_FILL(PcBetweenFill, PcSlabDomain, "between", "a between-groups fill", PC_SLAB_BETWEEN, PcTableOut, PcBetweenSeed);
 PC_SLAB_FILL(PcAffinityFill, PcSlabDomain, "affinity", "an affinity fill", PC_SLAB_AFFINITY, PcGenomeTableOut, PcNoSeed);
 #undef PC_SLAB_FILL
 // What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into

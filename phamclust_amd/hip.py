@@ -79,7 +79,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_last_tree_rounds", "pc_tree_key", "pc_tree_key_parts", "pc_fill_rows_edges", "pc_fill_rows_components", "pc_fill_rows_tree",
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
-           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity"]
+           "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity",
+           "pc_fill_rows_between"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 
 _lib = None
@@ -188,6 +189,9 @@ def load():
                                         ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                         ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                         ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_between.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i64p, _i64p, _i32p, _i32p, ctypes.c_int64,
+                                       ctypes.POINTER(_i64p), ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_affinity_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_affinity_block.argtypes = []
     L.pc_affinity_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -1025,6 +1029,42 @@ class Context(_SlabFills):
         if want_stats:
             out["stats"] = self._slab_stats("affinity", stats, n_groups=n_groups, n_slabs=int(nsl.value))
         return out
+
+    def fill_rows_between(self, metric, group, rows, n_groups=None, seed=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """A stored between-groups table grown by new genomes: :meth:`fill_between`'s ``(sum, count, lo, hi)`` of the whole collection
+        from ``seed`` -- the 4-tuple :meth:`fill_between` gave for the same labels over the genomes that are NOT in ``rows``, in this
+        call's direction -- and the pairs that have a query genome of ``rows`` at one end: ``len(rows) * N`` pairs filled instead of
+        ``N (N - 1) / 2``, and the result is the whole fill's, integer for integer.  ``group[g]`` in ``[0, n_groups)`` or -1: a member
+        of no group, in no pair (``n_groups`` defaults to the largest label + 1, at least 1).  ``seed=None``: the table over the pairs
+        with a query end alone.  The library refuses a seed that is not symmetric, not consistent, or whose counts are not the
+        partition's own (``old[a] * old[b]``; ``old[a] * (old[a] - 1) / 2`` on the diagonal; ``old`` the labelled genomes outside
+        ``rows``), naming the entry.  ``as_distance``, ``slab_bytes`` (ranges of ``max(1, slab_bytes // 8 // N)`` rows), ``borrow``
+        and ``want_stats`` as :meth:`fill_between`.  One GPU."""
+        if group is None:
+            raise ValueError("fill_rows_between: group is None")
+        if rows is None:
+            raise ValueError("fill_rows_between: rows is None")
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        if group.shape[0] != self.n_genomes:
+            raise ValueError(f"fill_rows_between: group holds {group.shape[0]} labels for {self.n_genomes} genomes")
+        if n_groups is None:
+            n_groups = max(int(group.max()) + 1, 1) if group.size else 1
+        n_groups = int(n_groups)
+        if n_groups < 1:
+            raise ValueError(f"fill_rows_between: n_groups {n_groups}")
+        pseed = (None, None, None, None)
+        if seed is not None:
+            if len(seed) != 4 or any(part is None for part in seed):
+                raise ValueError("fill_rows_between: seed is the 4-tuple (sum, count, lo, hi) or None")
+            seed = [np.ascontiguousarray(part, dtype=dtype) for part, dtype in zip(seed, (np.int64, np.int64, np.int32, np.int32))]
+            for name, part in zip(("sum", "count", "lo", "hi"), seed):
+                if part.shape != (n_groups, n_groups):
+                    raise ValueError(f"fill_rows_between: seed {name} must be {n_groups} x {n_groups} for {n_groups} groups, not {part.shape}")
+            pseed = tuple(_ptr(part, typ) for part, typ in zip(seed, (_i64p, _i64p, _i32p, _i32p)))
+        rows, prow, n_rows = self._rows_arg(rows)
+        pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
+        return self._fill_table(self._ROWS_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, prow, n_rows, *pseed, int(slab_bytes)), n_groups,
+                                want_stats, borrow)
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -1,12 +1,14 @@
 """The table between the groups of a partition: count, sum, minimum and maximum of the pair values of every two groups.
 
-Owns ``GroupLinkage``, its route ``between_de_novo`` and its file (``between_to_file`` / ``between_from_file``); ``MILLION`` and
+Owns ``GroupLinkage``, its routes ``between_de_novo`` and ``between_extend`` (a stored table grown by new genomes) and its file (``between_to_file`` / ``between_from_file``); ``MILLION`` and
 the empty entry's ``_EMPTY_LO`` / ``_EMPTY_HI`` are shared with the affinity result."""
+
+import logging
 
 import numpy as np
 
 from phamclust_amd.symmatrix import _square_matrix
-from phamclust_amd.routes import _de_novo_route, _partition_labels
+from phamclust_amd.routes import LAST_FILL, _de_novo_route, _partition_labels
 
 BETWEEN_MAX_GROUPS = 2048   # PC_BETWEEN_MAX_GROUPS of the C-ABI: the groups a between-groups fill takes at most
 MILLION = 1000000
@@ -133,6 +135,98 @@ class GroupLinkage:
         lo = np.where(full, MILLION - self.hi.astype(np.int64), _EMPTY_LO).astype(np.int32)
         hi = np.where(full, MILLION - self.lo.astype(np.int64), _EMPTY_HI).astype(np.int32)
         return GroupLinkage(self.groups, self.cnt * MILLION - self.sum, self.cnt, lo, hi, is_distance=not self.is_distance)
+
+    def padded(self, n_groups):
+        """The four arrays with empty entries appended up to ``n_groups`` groups (at least this table's)."""
+        g = len(self)
+        if n_groups < g:
+            raise ValueError(f"GroupLinkage.padded: {n_groups} groups are fewer than this table's {g}")
+        out = []
+        for arr, empty in ((self.sum, 0), (self.cnt, 0), (self.lo, _EMPTY_LO), (self.hi, _EMPTY_HI)):
+            wide = np.full((n_groups, n_groups), empty, dtype=arr.dtype)
+            wide[:g, :g] = arr
+            out.append(wide)
+        return tuple(out)
+
+    def _grown_members(self, groups, who):
+        """``groups`` as a grown partition of this table's: group i of the table a subset of group i, more groups may follow.  Returns the
+        set of stored members.  ValueError for fewer groups, a genome in two groups, a stored member that is missing or moved."""
+        groups = [list(group) for group in groups]
+        if len(groups) < len(self):
+            raise ValueError(f"{who}: {len(groups)} groups are fewer than the stored table's {len(self)}")
+        where = {}
+        for a, group in enumerate(groups):
+            for name in group:
+                if name in where:
+                    raise ValueError(f"{who}: '{name}' is in groups {where[name]} and {a}")
+                where[name] = a
+        stored = set()
+        for a, group in enumerate(self.groups):
+            for name in group:
+                if name not in where:
+                    raise ValueError(f"{who}: stored member '{name}' of group {a} is missing from the grown partition (a stored table cannot "
+                                     "lose a genome: a minimum cannot be un-taken)")
+                if where[name] != a:
+                    raise ValueError(f"{who}: stored member '{name}' of group {a} moved to group {where[name]}")
+                if name in stored:
+                    raise ValueError(f"{who}: stored member '{name}' is listed twice")
+                stored.add(name)
+        return stored
+
+    def extended(self, matrix, groups):
+        """This table grown to ``groups``, a partition of (some of) the nodes of ``matrix`` -- any dense ``SymMatrix`` over the grown
+        collection, of this table's direction: group i of this table must be a subset of ``groups[i]``, and more groups may follow.  The
+        new genomes are the members of ``groups`` this table does not hold; the result is the stored integers plus the NEW genomes' rows
+        of ``matrix`` alone -- counts and sums add, extremes only move outward -- and equals ``GroupLinkage.from_dense(matrix, groups)``.
+        ValueError for a stored member that is missing or moved, for another direction, and for a new genome's weight that is unset or
+        no millionth."""
+        groups = [list(group) for group in groups]
+        if bool(matrix.is_distance) != self.is_distance:
+            raise ValueError("GroupLinkage.extended: the matrix holds " + ("distances" if matrix.is_distance else "similarities") +
+                             ", the stored table " + ("distances" if self.is_distance else "similarities"))
+        stored = self._grown_members(groups, "GroupLinkage.extended")
+        g, n = len(groups), matrix._data.shape[0]
+        label = np.full(n, -1, dtype=np.int64)
+        is_new = np.zeros(n, dtype=bool)
+        for a, group in enumerate(groups):
+            for name in group:
+                if name not in matrix:
+                    raise KeyError(f"node '{name}' not in matrix")
+                label[matrix._slot[name]] = a
+                is_new[matrix._slot[name]] = name not in stored
+        total, count, lo, hi = (arr.astype(np.int64) for arr in self.padded(g))
+        rows = np.flatnonzero(is_new)
+        if rows.shape[0]:
+            block = matrix._data[rows, :]
+            cols = np.arange(n)
+            # a new genome's row takes the pairs to every labelled genome but itself; a pair of two new genomes is the smaller slot's
+            live = (label[None, :] >= 0) & (cols[None, :] != rows[:, None]) & ((cols[None, :] > rows[:, None]) | ~is_new[None, :])
+            values = block[live]
+            micro = np.rint(values * 1.0e6)
+            if not (micro >= 0.0).all() or not (micro <= 1.0e6).all() or not np.array_equal(micro / 1.0e6, values):
+                raise ValueError("GroupLinkage.extended: a weight of a new genome is unset or no millionth in [0, 1]")
+            micro = micro.astype(np.int64)
+            a = np.broadcast_to(label[rows][:, None], live.shape)[live]
+            b = np.broadcast_to(label[None, :], live.shape)[live]
+            first, second = np.minimum(a, b), np.maximum(a, b)
+            flat = first * g + second
+            add_count = np.bincount(flat, minlength=g * g).astype(np.int64)
+            add_total = np.zeros(g * g, dtype=np.int64)
+            np.add.at(add_total, flat, micro)
+            add_lo = np.full(g * g, _EMPTY_LO, dtype=np.int64)
+            add_hi = np.full(g * g, _EMPTY_HI, dtype=np.int64)
+            np.minimum.at(add_lo, flat, micro)
+            np.maximum.at(add_hi, flat, micro)
+            upper = np.triu(np.ones((g, g), dtype=bool))
+
+            def both(square):                                              # entries a <= b were written: mirror them
+                square = square.reshape(g, g)
+                return np.where(upper, square, square.T)
+            count += both(add_count)
+            total += both(add_total)
+            lo = np.minimum(lo, both(add_lo))
+            hi = np.maximum(hi, both(add_hi))
+        return GroupLinkage(groups, total, count, lo.astype(np.int32), hi.astype(np.int32), is_distance=self.is_distance)
 
     @classmethod
     def from_dense(cls, matrix, groups):
@@ -267,3 +361,86 @@ def between_de_novo(genomes, func, groups, as_distance=True, slab_bytes=0):
                                       f"{stats.get('ms_reduce', 0.0):.3f} ms)",
         advice="for another callable: GroupLinkage.from_dense(matrix_de_novo(...), groups)")
     return GroupLinkage([[names[i] for i in idx] for idx in members], *arrays, is_distance=as_distance)
+
+
+BETWEEN_VERIFY_ALONE = 256   # the smallest old group is verified alone, beyond ``verify``, up to this many members
+
+
+def _verify_rows(stored_members, verify):
+    """The query rows of ``between_extend``'s verification: the whole member lists (index lists) of old groups, smallest group first,
+    for as long as the running total stays within ``verify`` rows; if even the smallest does not fit, that group alone when it has at
+    most ``BETWEEN_VERIFY_ALONE`` members.  Returns ``(group indices verified, rows ascending)``; both empty: nothing to verify with."""
+    order = sorted((len(idx), a) for a, idx in enumerate(stored_members) if idx)
+    taken, total = [], 0
+    for size, a in order:
+        if total + size > verify:
+            break
+        taken.append(a)
+        total += size
+    if not taken and order and order[0][0] <= BETWEEN_VERIFY_ALONE:
+        taken = [order[0][1]]
+    return taken, sorted(i for a in taken for i in stored_members[a])
+
+
+def between_extend(stored, genomes, func, groups, verify=8, slab_bytes=0):
+    """``GroupLinkage.from_dense(matrix_de_novo(genomes, func, cpus), groups)`` in ``stored``'s direction, from the STORED table and the
+    pairs of the new genomes alone: ``stored`` is the :class:`GroupLinkage` of an earlier collection (``between_de_novo``, or
+    ``between_from_file`` with its member lists), ``groups`` the grown partition of ``genomes`` -- group i of ``stored`` a subset of
+    group i, more groups may follow (the stored table is padded with empty entries for them) -- and the new genomes are those in
+    ``groups`` but not in ``stored.groups``.  ``Context.fill_rows_between`` fills ``len(new) * N`` pairs instead of ``N (N - 1) / 2``
+    and the result is the whole fill's, integer for integer.  The verification is exact: before the growing call ONE seedless call
+    with the new genomes labelled -1 refills whole old groups, smallest first, within ``verify`` rows (``_verify_rows``; 0: none), and
+    all G entries of every verified group must be the stored ones -- ValueError naming the two groups and both values otherwise.  Every
+    refusal comes before the first GPU call: no partition of ``genomes``, more than ``BETWEEN_MAX_GROUPS`` groups, a stored member absent
+    or moved, stored counts that are not the partition's, a launcher (``WORLD_SIZE`` > 1), a callable outside ``METRICS`` (for such a
+    callable: ``GroupLinkage.extended`` over any dense matrix).  One GPU; not built: several GPUs, the launcher route, more groups,
+    removing genomes."""
+    if not isinstance(stored, GroupLinkage):
+        raise ValueError("between_extend: stored must be a GroupLinkage")
+    names = [g.name for g in genomes]
+    members, label = _partition_labels(names, groups, "between_extend", BETWEEN_MAX_GROUPS)
+    grown = [[names[i] for i in idx] for idx in members]
+    stored._grown_members(grown, "between_extend")
+    index = {name: k for k, name in enumerate(names)}
+    stored_members = [sorted(index[name] for name in group) for group in stored.groups] + [[] for _ in range(len(members) - len(stored))]
+    old = np.array([len(idx) for idx in stored_members], dtype=np.int64)
+    seed = stored.padded(len(members))
+    want = np.outer(old, old)
+    np.fill_diagonal(want, old * (old - 1) // 2)
+    if not np.array_equal(seed[1], want):
+        a, b = (int(x) for x in np.argwhere(seed[1] != want)[0])
+        raise ValueError(f"between_extend: the stored table counts {int(seed[1][a, b])} pairs between groups {a} and {b}, their {int(old[a])} and "
+                         f"{int(old[b])} stored members make {int(want[a, b])}: the table is of another partition or another genome set")
+    is_old = np.zeros(len(names), dtype=bool)
+    for idx in stored_members:
+        is_old[idx] = True
+    new_idx = np.flatnonzero(~is_old).astype(np.int32)
+    if new_idx.shape[0] == 0:                                              # nothing new: the stored table re-laid, no GPU call
+        return GroupLinkage(grown, *seed, is_distance=stored.is_distance)
+    checked, rows = _verify_rows(stored_members, max(0, int(verify)))
+    if int(verify) > 0 and not checked and old.sum():
+        logging.warning(f"between_extend: the smallest stored group has more than {BETWEEN_VERIFY_ALONE} members and verify is {int(verify)}: "
+                        "the stored table is not verified")
+
+    def fill(ctx, metric):
+        if int(verify) > 0 and checked:
+            masked = label.copy()
+            masked[new_idx] = -1
+            found = ctx.fill_rows_between(metric, masked, rows, len(members), as_distance=stored.is_distance, slab_bytes=slab_bytes)
+            for a in checked:
+                for arr, ref, what in zip(found, seed, ("sum", "count", "lo", "hi")):
+                    if not np.array_equal(arr[a], ref[a]):
+                        b = int(np.flatnonzero(arr[a] != ref[a])[0])
+                        raise ValueError(f"between_extend: groups {a} and {b}: the stored table holds {what} {int(ref[a, b])}, the {metric} fill gives "
+                                         f"{int(arr[a, b])}: the file was not written with this metric from these genomes")
+        return ctx.fill_rows_between(metric, label, new_idx, len(members), seed=seed, as_distance=stored.is_distance, slab_bytes=slab_bytes,
+                                     want_stats=True)
+
+    _, arrays = _de_novo_route(genomes, func, "between_extend", fill,
+        lambda stats, record, fill_s: f"{len(genomes)} genomes in {len(members)} groups, {new_idx.shape[0]} of them new ({len(rows)} old verified) -> "
+                                      f"{len(members) * (len(members) + 1) // 2} entries from {int(stats['n_pairs'])} pairs in {stats['n_slabs']} slab(s): "
+                                      f"fill+reduce+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, reduction "
+                                      f"{stats.get('ms_reduce', 0.0):.3f} ms)",
+        advice="for another callable: GroupLinkage.extended over any dense matrix", several=False)
+    LAST_FILL.update(rows=int(new_idx.shape[0]), verified_rows=len(rows))
+    return GroupLinkage(grown, *arrays, is_distance=stored.is_distance)

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_extend, between_from_file, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -342,6 +342,54 @@ class _Run:
         log.info(f"wrote {target.name}")
         return found
 
+    # 2, --place --grow-table
+    def grow_table(self, fit_path, table_path, found, join_min=None):
+        """After ``place``: the stored ``cluster_table_<metric>.tsv`` at ``table_path`` -- of the run that wrote ``fit_path`` -- grown by the
+        new genomes.  Every new genome joins its ``assigned("mean")`` cluster of ``found``; with ``join_min`` a genome whose nearest mean
+        similarity lies below it (and one no cluster is near) becomes a singleton group, appended after the stored groups in genome order
+        and named by the genome.  ``between_extend`` fills only the new genomes' pairs and verifies whole old clusters against the file;
+        writes ``cluster_table_<metric>.tsv`` into the output directory.  A failure is logged and exits 1 without writing the table."""
+        self.banner("2b", f"{self.metric} cluster table grown by the placed genomes (rows form of the between-groups fill)")
+        t0 = time.perf_counter()
+        names = [g.name for g in self.genomes]
+        try:
+            clusters, fit_groups, own = stored_fit_from_file(fit_path)
+            at = {cluster: k for k, cluster in enumerate(clusters)}
+            table_names, _ = between_from_file(table_path, None, is_distance=False)
+            stranger = next((name for name in table_names if name not in at), None)
+            if stranger is not None:
+                raise ValueError(f"group '{stranger}' of the table is no cluster of {fit_path}")
+            if len(table_names) != len(clusters):
+                raise ValueError(f"the table holds {len(table_names)} groups, {fit_path} {len(clusters)} clusters")
+            table_names, stored = between_from_file(table_path, [fit_groups[at[name]] for name in table_names], is_distance=False)
+            new = [name for name in names if name not in own]
+            joined = found.assigned("mean", min_similarity=join_min)
+            groups = [list(group) for group in stored.groups]
+            singles = []
+            for name in new:
+                k = joined.get(name)
+                if k is None:
+                    singles.append(name)
+                else:
+                    groups[table_names.index(clusters[k])].append(name)
+            taken = next((name for name in singles if name in at), None)
+            if taken is not None:
+                raise ValueError(f"new genome '{taken}' would name a singleton group, and the table has a group of that name")
+            table = between_extend(stored, self.genomes, METRICS[self.metric], groups + [[name] for name in singles])
+        except (ValueError, KeyError, OSError, RuntimeError) as exc:
+            log.error(f"--grow-table {table_path}: {exc.args[0] if isinstance(exc, KeyError) and exc.args else exc}")
+            print("growing the cluster table failed - check log for details")
+            sys.exit(1)
+        st = _matrix.LAST_FILL
+        log.info(f"grew the table of {len(stored):,} clusters by {len(new):,} genomes ({len(new) - len(singles):,} joined a cluster, {len(singles):,} "
+                 f"became singletons; {st.get('verified_rows', 0)} old genomes verified): {int(st.get('n_pairs', 0)):,} pairs filled instead of "
+                 f"{len(names) * (len(names) - 1) // 2:,} in {time.perf_counter() - t0:.3f} s (kernels {st.get('ms_total', 0.0):.3f} ms, pass "
+                 f"{st.get('ms_reduce', 0.0):.3f} ms, fold {st.get('ms_finish', 0.0):.3f} ms)")
+        target = self.outdir / f"cluster_table_{self.metric}.tsv"
+        between_to_file(table, table_names + singles, target)
+        log.info(f"wrote {target.name}")
+        return table
+
     # 2, --tree
     def tree(self):
         """Stage 2 as a tree fill: the single-linkage dendrogram, and only ``tree_<metric>.tsv`` is written: one
@@ -637,7 +685,8 @@ class _Run:
 
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
-              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_nearest=None, nearest=None):
+              components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_table=None, join_min=None,
+              grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -652,7 +701,14 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     grown the same way; ``cluster_table``: after the clustering, one between-groups fill over the final clusters and its three outputs
     (``--cluster-table``; with the whole pipeline only, on either route); ``cluster_fit``: after the clustering, one affinity fill over the
     final clusters and its two files (``--cluster-fit``; on the same terms); ``place``: stop after placing the genomes that a
-    ``cluster_fit_<metric>.tsv`` of an earlier run lacks against its clusters, and write only ``placement_<metric>.tsv`` (``--place``)."""
+    ``cluster_fit_<metric>.tsv`` of an earlier run lacks against its clusters, and write only ``placement_<metric>.tsv`` (``--place``);
+    ``grow_table``: with ``place``, the ``cluster_table_<metric>.tsv`` of the run that wrote that file: every new genome joins its nearest
+    cluster by mean -- with ``join_min``, a similarity, only when that mean reaches it, else it becomes a singleton group -- and the
+    table is grown by the new genomes' pairs alone (``--grow-table``, ``--join-min``)."""
+    if grow_table is not None and place is None:
+        raise ValueError("grow_table goes with place")
+    if join_min is not None and grow_table is None:
+        raise ValueError("join_min goes with grow_table")
     if place is not None and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
                               grow_nearest is not None or cluster_table or cluster_fit):
         raise ValueError("place cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, cluster_table or cluster_fit")
@@ -707,6 +763,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["cluster fit"] = "written (--cluster-fit: an affinity fill)"
     if place is not None:
         settings["place"] = f"only, against the clusters of {place}"
+    if grow_table is not None:
+        settings["table"] = f"{grow_table}, grown by the placed genomes" + ("" if join_min is None else f" (joining at similarity >= {join_min})")
     if grow is not None:
         settings["grow"] = grow
     if grow_nearest is not None:
@@ -746,7 +804,9 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         if run.world > 1:
             log.error("--place is a one-GPU call: run it in one process, not under a launcher")
             sys.exit(1)
-        run.place(place)
+        found = run.place(place)
+        if grow_table is not None:
+            run.grow_table(place, grow_table, found, join_min)
         run.banner(3, "done (--place: no clustering)")
         return
     if tree:
@@ -924,7 +984,7 @@ def _run(args, argv):
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
-                  cluster_fit=args.cluster_fit, place=args.place)
+                  cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
