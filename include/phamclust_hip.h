@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 169   /* 0.5.18: pc_fill_rows_between (a stored between-groups table grown by new genomes) */
+#define PC_VERSION 170   /* 0.5.19: pc_fill_hist / pc_multi_fill_hist / pc_fill_rows_hist (the exact histogram of all pair values) */
 
 typedef enum {
     PC_OK = 0,
@@ -93,17 +93,17 @@ int pc_test_hooks(void);
 /* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 166): values, the whole triangle of the uploaded collection as
  * n_pairs = N (N - 1) / 2 doubles in the slab walk's own order -- target-major: element t (t - 1) / 2 + s is the pair (s, t), s < t --
  * stands for "the slab as filled" in every triangular slab walk of the process from now on: pc_fill_edges, _components, _nearest, _tree,
- * _between, _affinity and their pc_multi_ forms.  The fill still runs (the uploaded collection only sets N); each slab is then overwritten
- * with its stretch of the triangle by one host-to-device copy on the walk's stream, in whichever direction the fill ran: between and
+ * _between, _affinity, _hist and their pc_multi_ forms.  The fill still runs (the uploaded collection only sets N); each slab is then overwritten
+ * with its stretch of the triangle by one host-to-device copy on the walk's stream, in whichever direction the fill ran: between, hist and
  * affinity always fill distances and invert at the end, the other four fill the direction asked for.  The pointer is stored process-wide,
  * not the values: the caller keeps the memory alive and unchanged until it clears the hook with values == NULL, and sets or clears it
  * between calls only.  A walk that finds n_pairs != N (N - 1) / 2 refuses with PC_ERR_ARG.  The rows walk (pc_fill_rows_edges,
- * _components, _tree, _nearest, _affinity, _between) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
+ * _components, _tree, _nearest, _affinity, _between, _hist) does not read it: pc_hook_rows_values is its hook.  PC_ERR_ARG: values with a negative n_pairs.
  * In the release library: PC_ERR_STATE and an error text, with a pointer and with NULL alike; nothing is stored. */
 int pc_hook_slab_values(const double* values, int64_t n_pairs);
 /* Test hook, only in effect in libphamclust_hip_hooks.so (PC_VERSION 167): values, f64[n_rows][n], row k the values of the call's query
  * genome rows[k] to every genome, stands for "the slab as filled" in every rows walk of the process from now on: pc_fill_rows_edges,
- * _components, _tree, _nearest, _affinity, _between.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
+ * _components, _tree, _nearest, _affinity, _between, _hist.  The rows fill still runs; each slab of m rows starting at query row r0 is then overwritten with
  * values + r0 * n, m * n doubles, by one host-to-device copy on the walk's stream -- EVERY element of it: the diagonal [k][rows[k]] and
  * both copies of a pair of two query genomes are the caller's too, so a test decides what the elements hold that no pass may read.
  * pc_fill_rows, pc_fill_rows_dev and the triangular walk do not read it; the two hooks are independent.  The pointer is stored
@@ -606,6 +606,52 @@ int pc_fill_rows_between(pc_ctx* ctx, int metric, int as_distance, const int32_t
                          const int64_t* seed_sum, const int64_t* seed_count, const int32_t* seed_lo, const int32_t* seed_hi, int64_t slab_bytes,
                          const int64_t** sum, const int64_t** count, const int32_t** lo, const int32_t** hi, int32_t* n_slabs, pc_stats* stats);
 
+/*
+ * Distribution fill (PC_VERSION 170): the exact histogram of every pair value of the collection, without the dense matrix.  A delivered
+ * value is round(x, 6), one of the pc_hist_bins() = 10^6 + 1 millionths in [0, 1] (checked per value under pc_fill_between's rule: -0.0
+ * is the millionth 0, anything else that is no millionth in [0, 1] is counted and enters no bin), so the whole distribution is one
+ * integer array, 8 MB whatever N is.  From it follow, exactly and for every threshold at once: the count of pairs within a threshold
+ * (pc_fill_edges' *n_edges), every quantile, minimum and maximum, mean, variance and skewness.
+ *   group / n_groups   NULL: one class.  int32[N], every label in [0, n_groups) (no cap on n_groups: labels are only compared): two
+ *                      classes, class 0 the pairs whose genomes share a label ("within"), class 1 the others ("between").
+ *   *hist              int64[*n_classes][pc_hist_bins()], the context's pinned memory, lent under pc_fill_borrow's rule; bin k of a class
+ *                      counts its pairs of millionth k.  *n_pairs is the sum of all bins, N (N - 1) / 2; with a partition class 0 sums
+ *                      to the sum over the groups of n_c (n_c - 1) / 2.
+ * The slabs are always filled as DISTANCES; as_distance == 0 delivers the histogram of the inverted matrix, every class reversed (bin k
+ * <-> 10^6 - k), as pc_fill_between inverts its table -- deliberately not the histogram of a similarity fill's values (at a decimal tie
+ * 1 - d and d both round up).
+ * Same walk as pc_fill_edges (the slab cut, slab_bytes, 0 = automatic).  Each filled slab goes through ONE pass, k_hist_pass: a workgroup
+ * takes a chunk of 4,096 elements and counts the keys class << 20 | millionth in an open-addressing table in LDS -- pc_hist_table_slots()
+ * slots; the first slot of a key is (key * 2654435761 mod 2^32) >> (32 - log2 slots), then linear probing over at most pc_hist_probes()
+ * slots; an insert that finds them all held by other keys adds to the global bin directly -- after the wave's most frequent keys were
+ * added by one lane each; at the end of the chunk every occupied slot is ONE relaxed agent-scope 64-bit add into the resident state,
+ * u64[classes][bins] and the violation count, which stays on the device from the first slab to the last.  After the last slab
+ * k_hist_finish (the reversal), then ONE D2H copy.  The moments are the caller's: it has the whole array.
+ * Refusals in pc_fill_between's order and wording (without its cap on n_groups); PC_ERR_DATA: values that are no millionth in [0, 1],
+ * with their count; the context stays usable.  N <= 1: PC_OK, nothing runs on the device, every bin zero.
+ */
+int pc_fill_hist(pc_ctx* ctx, int metric, int as_distance, const int32_t* group /* i32[N] or NULL */, int n_groups, int64_t slab_bytes,
+                 const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs, pc_stats* stats);
+/* Test / tuning hook, of the last pc_fill_hist or pc_fill_rows_hist call: *ms_pass the passes summed over its slabs, *ms_finish the finish (HIP events; 0
+ * without stats). */
+int pc_last_hist_times(const pc_ctx* ctx, float* ms_pass, float* ms_finish);
+int pc_hist_bins(void);             /* 1000001 */
+int pc_hist_table_slots(void);      /* slots of the pass's LDS table (a power of two) */
+int pc_hist_probes(void);           /* slots an insert tries before it adds to the global bin */
+/*
+ * The rows form of the distribution fill (PC_VERSION 170): a stored histogram grown by new genomes.  rows[n_rows] -- pc_fill_rows'
+ * contract -- are the query genomes; the pairs of the call are those that touch one, each once (a pair of two queries in the smaller
+ * one's row; the diagonal and the second copy are never looked at: neither counted nor refused).  seed_hist, int64[n_classes][bins] in the
+ * call's DIRECTION or NULL, is what pc_fill_hist delivers for the same labels over the genomes that are no query rows; the result is seed
+ * + rows, which is pc_fill_hist over the whole collection, bin for bin, for any slab cut and both directions.  Refused (PC_ERR_ARG): a
+ * seed with a negative bin, a seed whose total is not N_old (N_old - 1) / 2, with a partition a seed whose class 0 is not the old
+ * genomes' within count -- necessary checks, not sufficient ones: a histogram cannot name its pairs.  A label of -1 is refused here too.
+ * Refusals in pc_fill_hist's order, then rows, then the seed.  One GPU: a sharded context is refused; there is no pc_multi_* form.
+ */
+int pc_fill_rows_hist(pc_ctx* ctx, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                      const int64_t* seed_hist /* i64[n_classes][bins] or NULL */, int64_t slab_bytes,
+                      const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs, pc_stats* stats);
+
 /* Root only: permute `world` gathered shards (f64[world * pc_shard_stride()], device)
  * into scipy condensed order (device f64[N(N-1)/2]). */
 int pc_assemble_dev(pc_ctx* ctx, const void* gathered_dev, int world, void* out_condensed_dev, void* stream);
@@ -718,6 +764,11 @@ int pc_multi_fill_affinity(pc_multi* m, int metric, int as_distance, const int32
                            const int64_t** own_sum, const int32_t** own_lo, const int32_t** own_hi, const int32_t** near_group,
                            const int64_t** near_sum, const int32_t** near_lo, const int32_t** near_hi,
                            const int64_t** tab_sum, const int32_t** tab_lo, const int32_t** tab_hi, int32_t* n_slabs, pc_stats* stats);
+/* pc_fill_hist over the devices of `m`, on the same terms and with the same deal.  Every device counts over its stretch of targets and
+ * ships its raw state once, 8 (n_classes bins + 1) bytes, into a staging slice on the root; ONE launch of k_hist_merge adds them word by
+ * word (a pair lies in exactly one stretch), then the root finishes.  The result is the same for any number of devices. */
+int pc_multi_fill_hist(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                       const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs, pc_stats* stats);
 int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds /* pc_multi_devices(m) + 1 entries */);
 int pc_multi_last_slab_times(const pc_multi* m, float* ms_exchange, float* ms_merge);
 /* The stretch deal itself, host arithmetic only (no GPU, no context; exported for tests as pc_chunk_plan is): bounds[world + 1] with

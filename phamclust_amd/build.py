@@ -26,13 +26,14 @@ NW_FLAGS = []
 # kernels (choosers, launch classes, launch shapes; what it shares with the kernels is pc_nw_geometry.h): they hold no device code, so the
 # library's .hip_fatbin comes from the kernel units alone.  Those are, by family (internal header pc_pairs.h): pc_set_popc (popcount tiles), pc_sparse (sparse
 # tiles and their entry lists), pc_sparse_col (the column kernel), pc_walk (the shared-pham walker over both pair domains), pc_util
-# (scan, gather, shard assembly, test probes), pc_edges (the edge-list compaction of pc_fill_edges), pc_components (the union-find of pc_fill_components), pc_nearest (the k-best selection of pc_fill_nearest), pc_tree (the Boruvka rounds of pc_fill_tree), pc_between (the group table of pc_fill_between), pc_affinity (the genome x group table of pc_fill_affinity) -- pc_edges, pc_components and pc_tree share what a pass over a filled slab is (pc_slab_pass.h); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
+# (scan, gather, shard assembly, test probes), pc_edges (the edge-list compaction of pc_fill_edges), pc_components (the union-find of pc_fill_components), pc_nearest (the k-best selection of pc_fill_nearest), pc_tree (the Boruvka rounds of pc_fill_tree), pc_between (the group table of pc_fill_between), pc_affinity (the genome x group table of pc_fill_affinity), pc_hist (the value histogram of pc_fill_hist) -- pc_edges, pc_components, pc_tree and pc_hist share what a pass over a filled slab is (pc_slab_pass.h); then pc_plan (alignment planning) and the alignment kernels pc_nw*.
 HIP_UNITS = [("pc_ctx.hip", "pc_ctx.o", []), ("pc_upload.hip", "pc_upload.o", []), ("pc_align.hip", "pc_align.o", []),
              ("pc_fill.hip", "pc_fill.o", []), ("pc_fill_slabs.hip", "pc_fill_slabs.o", []), ("pc_multi.hip", "pc_multi.o", []),
              ("pc_set_popc.hip", "pc_set_popc.o", []), ("pc_sparse.hip", "pc_sparse.o", []), ("pc_sparse_col.hip", "pc_sparse_col.o", []),
              ("pc_set_shape.hip", "pc_set_shape.o", []), ("pc_walk.hip", "pc_walk.o", []), ("pc_util.hip", "pc_util.o", []),
              ("pc_edges.hip", "pc_edges.o", []), ("pc_components.hip", "pc_components.o", []), ("pc_nearest.hip", "pc_nearest.o", []),
              ("pc_tree.hip", "pc_tree.o", []), ("pc_between.hip", "pc_between.o", []), ("pc_affinity.hip", "pc_affinity.o", []),
+             ("pc_hist.hip", "pc_hist.o", []),
              ("pc_plan.hip", "pc_plan.o", []), ("pc_nw_shape.hip", "pc_nw_shape.o", []),
              ("pc_nw.hip", "pc_nw.o", NW_FLAGS),
              ("pc_nw_rules.hip", "pc_nw_r23.o", NW_FLAGS + ["-DPC_RULE_A=2", "-DPC_RULE_B=3"]),

@@ -88,6 +88,17 @@ _OPTIONS = (
                                                                  "silhouette, whether it is the cluster's medoid) and "
                                                                  "cluster_fit_<metric>_summary.tsv (per cluster: size, medoid, mean silhouette, "
                                                                  "largest own distance); with the dense route or --no-matrix, and with --gpus N")),
+    (None, "-H", "--distribution-only", dict(action="store_true", help="stop after the matrix stage and write only pairwise_<metric>_distribution.tsv (the "
+                                                                       "exact histogram of all pair similarities: value<TAB>count per occupied "
+                                                                       "millionth) and pairwise_<metric>_distribution_summary.tsv (n, min, max, mean, "
+                                                                       "std, skew, quartiles, and how many pairs pass --nr-thresh, --clu-thresh, "
+                                                                       "--sub-thresh and --edge-thresh), from a distribution fill: no matrix, no "
+                                                                       "threshold, no clustering; with --gpus N the devices of this process share the fill")),
+    (None, "-U", "--distribution", dict(action="store_true", help="after clustering, the distribution of the pair similarities split by the final "
+                                                                  "clusters: writes pairwise_<metric>_distribution.tsv (value<TAB>within<TAB>between) "
+                                                                  "and pairwise_<metric>_distribution_summary.tsv, which also says how --clu-thresh "
+                                                                  "separates the clusters and which threshold would separate them best; with the "
+                                                                  "dense route or --no-matrix")),
     (None, "-P", "--place", dict(type=pathlib.Path, default=None, help="stop after the matrix stage and write only placement_<metric>.tsv: FILE is the "
                                                                       "cluster_fit_<metric>.tsv of an earlier --cluster-fit run over a SUBSET of "
                                                                       "these genomes; the genomes it lacks are placed against its clusters -- per new "
@@ -136,7 +147,7 @@ def build_parser():
 def parse_args(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.edge_thresh is not None and not (args.adjacency_only or args.components_only):
+    if args.edge_thresh is not None and not (args.adjacency_only or args.components_only or args.distribution_only):
         parser.error("--edge-thresh selects the edges of --adjacency-only or --components-only; without one of them there is nothing to select")
     if args.edge_thresh is not None and not 0.0 <= args.edge_thresh <= 1.0:          # (also refuses NaN)
         parser.error("--edge-thresh is a similarity in [0, 1]")
@@ -158,6 +169,18 @@ def parse_args(argv=None):
                             ("--nearest", args.nearest is not None), ("--extend", args.extend is not None)):
             if given:
                 parser.error(f"--tree stops after a tree fill of its own; it cannot be combined with {flag}")
+    if args.distribution_only:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--no-matrix", args.no_matrix),
+                            ("--nearest", args.nearest is not None), ("--tree", args.tree), ("--extend", args.extend is not None),
+                            ("--grow", args.grow is not None), ("--place", args.place is not None), ("--cluster-table", args.cluster_table),
+                            ("--cluster-fit", args.cluster_fit), ("--distribution", args.distribution)):
+            if given:
+                parser.error(f"--distribution-only stops after a distribution fill of its own; it cannot be combined with {flag}")
+    if args.distribution:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--tree", args.tree),
+                            ("--nearest", args.nearest is not None), ("--extend", args.extend is not None), ("--place", args.place is not None)):
+            if given:
+                parser.error(f"--distribution reads the final clusters of the whole pipeline; it cannot be combined with {flag}")
     if args.grow is not None:
         if not (args.tree or args.components_only):
             parser.error("--grow FILE grows a stored tree (--tree) or stored components (--components-only --edge-thresh SIM); give one of them")

@@ -264,6 +264,19 @@ int pc_launch_between_merge(void* acc, const void* staged, int n_foreign, int G,
 // the square made symmetric into out (the result layout), empty entries as lo = INT32_MAX, hi = -1; invert: the accumulator holds
 // distances and out takes the similarity table, every millionth's complement
 int pc_launch_between_fold(const void* acc, void* out, int G, int invert, hipStream_t st);
+// histogram of a filled slab's pair values (pc_hist.hip).  The state of `classes` classes (1: no partition; 2: within, between) is one
+// allocation of pc_hist_bytes(classes): u64 hist[classes][PC_HIST_BINS] | the 8-byte count of values that are no millionth in [0, 1].
+// Bin k of a class counts its pairs of micro k; an empty state is all zero.  The finished result has the same layout, i64.
+#define PC_HIST_BINS 1000001
+static inline size_t pc_hist_bytes(int classes) { return ((size_t)classes * PC_HIST_BINS + 1) * 8; }
+int pc_hist_table_slot_count(void);                // slots of the pass's LDS table
+int pc_hist_probe_bound(void);                     // slots an insert tries before it goes to the global bin
+// one slab (either pair domain); group: [N] on the device, every label compared only, or NULL (classes == 1)
+int pc_launch_hist_pass(const double* vals, int64_t Lp, PcSlabDomain dom, const int32_t* group, int classes, void* state, hipStream_t st);
+// the states of other devices added into state: staged[n_foreign] of pc_hist_bytes(classes) each
+int pc_launch_hist_merge(void* state, const void* staged, int n_foreign, int classes, hipStream_t st);
+// the state into out (the result layout); invert: the state holds distances and out takes the similarity histogram, every class reversed
+int pc_launch_hist_finish(const void* state, void* out, int classes, int invert, hipStream_t st);
 // genome x group table of a filled slab (pc_affinity.hip).  The resident table of N genomes and G groups is one allocation of
 // pc_affinity_table_bytes(N, G): PcAffinityEntry[N][G] | the 8-byte count of values that are no millionth in [0, 1].  Entry [g][b]
 // takes the pairs of g with the members of b; an empty entry is (0, ~0, 0).  The result (PcAffinityOut over one allocation of

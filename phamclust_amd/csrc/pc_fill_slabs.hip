@@ -3,12 +3,13 @@
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
 // pc_last_nearest_times, pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds, and
 // pc_fill_between (the count, sum, minimum and maximum of the pair values between every two groups of a partition) with pc_last_between_times,
-// pc_fill_affinity (the sum, minimum and maximum of every genome's pair values to every group) with pc_last_affinity_times.
-// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill, PcBetweenFill, PcAffinityFill: begin, slab, end, and what several
+// pc_fill_affinity (the sum, minimum and maximum of every genome's pair values to every group) with pc_last_affinity_times,
+// pc_fill_hist (the exact histogram of all pair values, split by a partition into within and between) with pc_last_hist_times.
+// Each fill is described once (PcEdgesFill, PcComponentsFill, PcNearestFill, PcTreeFill, PcBetweenFill, PcAffinityFill, PcHistFill: begin, slab, end, and what several
 // devices ship and merge; declared in pc_host.h) and run by one driver, pc_slab_fill<Fill>: check -> begin -> walk [0, N) -> end.
 // multi_slab_fill<Fill> (pc_multi.hip) runs the same description on a stretch of targets per device.  An entry point sets the call's
 // own fields of a PcSlabRun and hands a driver to pc_slab_call<Fill> (pc_host.h), which clears and delivers the outputs.  Host only.
-// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest / pc_fill_rows_affinity / pc_fill_rows_between (at the end of the file) grow a stored result by new genomes: the same
+// pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest / pc_fill_rows_affinity / pc_fill_rows_between / pc_fill_rows_hist (at the end of the file) grow a stored result by new genomes: the same
 // descriptions, seeded, over a walk of the new genomes' rows instead of the triangle (pc_rows_slab_fill<Fill>, rows_walk): slab() takes
 // either slab's pair domain.
 //
@@ -58,6 +59,13 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
         for (int g = 0; g < c->dev.N; ++g)
             if (run.group[g] < lowest || run.group[g] >= run.n_groups) {
                 pc_set_error("%s: genome %d has label %d, outside [%d, %d)", who, g, run.group[g], lowest, run.n_groups); return PC_ERR_ARG;
+            }
+    }
+    if (run.kind == PC_SLAB_HIST && run.group) {                            // (no cap on n_groups: the labels are only compared)
+        if (run.n_groups < 1) { pc_set_error("%s: n_groups %d", who, run.n_groups); return PC_ERR_ARG; }
+        for (int g = 0; g < c->dev.N; ++g)
+            if (run.group[g] < 0 || run.group[g] >= run.n_groups) {
+                pc_set_error("%s: genome %d has label %d, outside [%d, %d)", who, g, run.group[g], 0, run.n_groups); return PC_ERR_ARG;
             }
     }
     if (run.kind == PC_SLAB_TREE && c->dev.N > PC_TREE_MAX_GENOMES) {
@@ -185,6 +193,8 @@ template int pc_slab_stretch<PcTreeFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_stretch<PcBetweenFill>(pc_ctx*, PcSlabRun&, int, int);
 template int pc_slab_fill<PcAffinityFill>(pc_ctx*, PcSlabRun&);
 template int pc_slab_stretch<PcAffinityFill>(pc_ctx*, PcSlabRun&, int, int);
+template int pc_slab_fill<PcHistFill>(pc_ctx*, PcSlabRun&);
+template int pc_slab_stretch<PcHistFill>(pc_ctx*, PcSlabRun&, int, int);
 
 // ---- what the descriptions share ----
 // begin, ahead of anything of the fill's own: the run and the fill's two times (last_ms) reset, the loan of an earlier call ended (its
@@ -948,6 +958,87 @@ extern "C" int pc_last_affinity_times(const pc_ctx* c, float* ms_rows, float* ms
     return PC_OK;
 }
 
+// ---- distribution fill: the exact histogram of every pair value -- a delivered value is one of the 10^6 + 1 millionths in [0, 1], so
+// the whole distribution is pc_hist_bins() integer bins, whatever N is: the count of pairs within ANY threshold (pc_fill_edges' n_edges at
+// every threshold at once), every quantile, and the mean, deviation and skewness SymMatrix.statistics takes from the dense matrix
+// (matrix.py:132-153).  With a partition two such arrays: class 0 the pairs inside a group, class 1 those between two.  Each filled slab
+// goes through ONE pass, k_hist_pass (pc_hist.hip), over a state that stays on the device from the first slab to the last; nothing is
+// read back per slab.  After the last slab: k_hist_finish, then one D2H of the bins and the 8-byte violation count behind them.  The walk
+// always fills distances, as the between-groups fill's: a similarity histogram is the distance histogram reversed by the finish.  The
+// rows form, pc_fill_rows_hist, seeds the state with a stored histogram (PcHistSeed, with the seeds below) and passes the new genomes'
+// rows through the rows form of the same pass body: begin and end are these.
+int PcHistFill::begin(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int N = c->dev.N, classes = run.group ? 2 : 1;
+    const size_t bytes = pc_hist_bytes(classes);
+    run.hist_classes = classes; run.hist_pairs = 0;
+    if ((rc = slab_begin(c, run, c->last_hist_ms)) || (rc = c->h_hist.ensure(bytes))) return rc;
+    if (N <= 1) return PC_OK;
+    if ((rc = slab_size(c, run))) return rc;
+    if ((rc = c->b_hist_state.ensure(bytes)) || (rc = c->b_hist_out.ensure(bytes))) return abi_rc(rc);
+    if (run.group && (rc = upload_raw(c->b_hist_group, run.group, (size_t)N * 4))) return rc;
+    PC_HIP(hipMemsetAsync(c->b_hist_state.p, 0, bytes, c->stream));
+    return PC_OK;
+}
+int PcHistFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    if (dom.is_rows != run.rows_form) { pc_set_error("%s: a slab of the other pair domain", run.who); return PC_ERR_ARG; }
+    return slab_pass(c, run, c->last_hist_ms, [&](hipStream_t st) {
+        return pc_launch_hist_pass(slab, Lp, dom, run.group ? c->b_hist_group.as<int32_t>() : nullptr, run.hist_classes, c->b_hist_state.p, st);
+    });
+}
+int PcHistFill::end(pc_ctx* c, PcSlabRun& run) {
+    int rc = PC_OK;
+    const int classes = run.hist_classes;
+    const size_t words = pc_hist_bytes(classes) / 8;
+    int64_t* const h = c->h_hist.as<int64_t>();
+    run.hist = h; run.hist_pairs = 0;
+    if (c->dev.N <= 1) { memset(h, 0, words * 8); return PC_OK; }            // no pair: every bin zero
+    if ((rc = slab_finish(c, run, c->last_hist_ms, h, c->b_hist_out.p, words * 8, [&](hipStream_t st) {
+            return pc_launch_hist_finish(c->b_hist_state.p, c->b_hist_out.p, classes, run.bt_invert, st);
+        }))) return rc;
+    if (h[words - 1]) {
+        pc_set_error("%s: %llu values of the fill are no millionth in [0, 1]: the histogram is not defined on them", run.who, (unsigned long long)h[words - 1]);
+        return PC_ERR_DATA;
+    }
+    int64_t total = 0;
+    for (size_t i = 0; i + 1 < words; ++i) total += h[i];
+    run.hist_pairs = total;
+    return PC_OK;
+}
+// Several devices: a device ships its raw state, pc_hist_bytes(classes), and the root adds the staged ones into its own in one launch
+// (k_hist_merge) before it finishes: a pair lies in exactly one stretch, so nothing is counted twice.
+size_t PcHistFill::ship_bytes(const pc_ctx*, const PcSlabRun& run) { return pc_hist_bytes(run.group ? 2 : 1); }
+int PcHistFill::ship(pc_ctx* c, pc_ctx* root, PcSlabRun& run, void* stage, int slot, int) {
+    int rc = PC_OK;
+    const size_t bytes = pc_hist_bytes(run.hist_classes);
+    PC_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = pc_ship(c, root, (char*)stage + (size_t)slot * bytes, c->b_hist_state.p, bytes))) return rc;
+    PC_HIP(hipEventRecord(c->ev[1], c->stream));
+    return PC_OK;
+}
+int PcHistFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& runs, const void* stage, int n_foreign, float*) {
+    int rc = PC_OK;
+    pc_ctx* root = ctx[0];
+    PC_HIP(hipEventRecord(root->ev[0], root->stream));
+    if ((rc = pc_launch_hist_merge(root->b_hist_state.p, stage, n_foreign, runs[0].hist_classes, root->stream))) return rc;
+    PC_HIP(hipEventRecord(root->ev[1], root->stream));
+    return PC_OK;
+}
+
+extern "C" int pc_fill_hist(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                            const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_hist"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcHistFill>(run, {hist, n_classes, n_pairs, n_slabs}, stats, [&] { return pc_slab_fill<PcHistFill>(c, run); });
+}
+
+extern "C" int pc_last_hist_times(const pc_ctx* c, float* ms_pass, float* ms_finish) {
+    return last_times(c, "pc_last_hist_times", c ? c->last_hist_ms : nullptr, ms_pass, ms_finish);
+}
+extern "C" int pc_hist_bins(void) { return PC_HIST_BINS; }
+extern "C" int pc_hist_table_slots(void) { return pc_hist_table_slot_count(); }
+extern "C" int pc_hist_probes(void) { return pc_hist_probe_bound(); }
+
 // ---- the rows forms: pc_fill_rows_edges / pc_fill_rows_components / pc_fill_rows_tree / pc_fill_rows_nearest grow a STORED result.  The pairs of the call are
 // those that touch a query genome (the new genomes of a grown collection): k query rows cost k N pairs, not N^2 / 2.  What is stored
 // stands for the pairs among the other genomes: the components fill takes their labelling as the initial parent[], the tree fill
@@ -1170,6 +1261,55 @@ int PcBetweenSeed::install(pc_ctx* c, PcSlabRun& run) const {
     return PC_OK;
 }
 
+// A stored histogram as the state's bins: i64[classes][PC_HIST_BINS] in the call's direction (a similarity seed is reversed: the walk
+// fills distances and the finish reverses back).  It must be the histogram of the pairs among the genomes that are no query rows: no
+// bin negative, the total their N_old (N_old - 1) / 2 pairs, and with a partition class 0 the pairs inside their groups.  (Necessary,
+// not sufficient: a histogram cannot name its pairs.)
+int PcHistSeed::pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows) {
+    if (!hist) return PC_OK;
+    const int N = c->dev.N, classes = run.group ? 2 : 1;
+    const size_t words = pc_hist_bytes(classes) / 8;
+    int64_t total[2] = {0, 0};
+    for (int cl = 0; cl < classes; ++cl)
+        for (size_t k = 0; k < PC_HIST_BINS; ++k) {
+            const int64_t x = hist[(size_t)cl * PC_HIST_BINS + k];
+            if (x < 0) { pc_set_error("%s: seed bin [%d][%zu] is negative (%lld)", run.who, cl, k, (long long)x); return PC_ERR_ARG; }
+            total[cl] += x;
+        }
+    std::vector<uint8_t> is_query((size_t)std::max(N, 1), 0);
+    for (int k = 0; k < n_rows; ++k) is_query[rows[k]] = 1;
+    const int64_t n_old = (int64_t)N - n_rows, want = n_old * (n_old - 1) / 2;
+    if (total[0] + total[1] != want) {
+        pc_set_error("%s: the seed counts %lld pairs, the %lld genomes that are no query rows have %lld: the stored histogram is of another genome set",
+                     run.who, (long long)(total[0] + total[1]), (long long)n_old, (long long)want);
+        return PC_ERR_ARG;
+    }
+    if (run.group) {
+        std::vector<int64_t> old((size_t)run.n_groups, 0);
+        for (int g = 0; g < N; ++g) if (!is_query[g]) ++old[run.group[g]];
+        int64_t within = 0;
+        for (int64_t n : old) within += n * (n - 1) / 2;
+        if (total[0] != within) {
+            pc_set_error("%s: class 0 of the seed counts %lld pairs, the partition has %lld inside its groups over the genomes that are no query rows: "
+                         "the stored histogram is of another partition or another genome set", run.who, (long long)total[0], (long long)within);
+            return PC_ERR_ARG;
+        }
+    }
+    image.assign(words, 0ull);
+    for (int cl = 0; cl < classes; ++cl)
+        for (size_t k = 0; k < PC_HIST_BINS; ++k)
+            image[(size_t)cl * PC_HIST_BINS + (run.bt_invert ? PC_HIST_BINS - 1 - k : k)] = (unsigned long long)hist[(size_t)cl * PC_HIST_BINS + k];
+    return PC_OK;
+}
+// the stored histogram in place of the empty state, through the pinned result image (end() rewrites it only after the stream has drained)
+int PcHistSeed::install(pc_ctx* c, PcSlabRun& run) const {
+    if (image.empty()) return PC_OK;
+    const size_t bytes = pc_hist_bytes(run.hist_classes);
+    memcpy(c->h_hist.p, image.data(), bytes);
+    PC_HIP(hipMemcpyAsync(c->b_hist_state.p, c->h_hist.p, bytes, hipMemcpyHostToDevice, c->stream));
+    return PC_OK;
+}
+
 extern "C" int pc_fill_rows_edges(pc_ctx* c, int metric, int as_distance, double threshold, const int32_t* rows, int n_rows, int64_t slab_bytes,
                                   const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     PcSlabRun run; run.who = "pc_fill_rows_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
@@ -1225,6 +1365,17 @@ extern "C" int pc_fill_rows_between(pc_ctx* c, int metric, int as_distance, cons
     run.allow_unlabelled = true; run.slab_bytes = slab_bytes;
     return pc_slab_call<PcBetweenFill>(run, {sum, count, lo, hi, n_slabs}, stats,
                                        [&] { return pc_rows_slab_fill<PcBetweenFill>(c, run, rows, n_rows, {seed_sum, seed_count, seed_lo, seed_hi}); });
+}
+
+// The rows form of the distribution fill: the stored histogram (PcHistSeed) and the pairs that have a query genome at one end, each once,
+// are the histogram of the grown collection, bin for bin -- counts add.  Without a seed: the histogram over those pairs alone.  Every
+// genome is labelled (this form keeps to full partitions: a label of -1 is refused).  The walk fills distances, as the whole form's.
+extern "C" int pc_fill_rows_hist(pc_ctx* c, int metric, int as_distance, const int32_t* group, int n_groups, const int32_t* rows, int n_rows,
+                                 const int64_t* seed_hist, int64_t slab_bytes, const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs,
+                                 pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_rows_hist"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcHistFill>(run, {hist, n_classes, n_pairs, n_slabs}, stats, [&] { return pc_rows_slab_fill<PcHistFill>(c, run, rows, n_rows, {seed_hist}); });
 }
 
 // elements one workgroup of a slab pass covers (0: edge count / emit, 1: union, 2: tree scan): what a test of the passes' seams sizes its slabs by

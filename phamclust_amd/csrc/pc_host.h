@@ -154,6 +154,11 @@ struct pc_ctx {
     PinnedBuf h_af;                         // the arrays lent out by pc_fill_affinity
     int af_ranges = 0;                      // group ranges of the column pass (b_af_range holds af_ranges + 1 bounds)
     float last_af_ms[3] = {0.f, 0.f, 0.f};  // row passes, finish, column passes of the last pc_fill_affinity / pc_fill_rows_affinity with stats (pc_last_affinity_times)
+    // pc_fill_hist: group[N] (a partition only), the resident state and the finished result (pc_hist_bytes(classes) each: pc_common.h), the
+    // result's pinned host image
+    DevBuf b_hist_group, b_hist_state, b_hist_out;
+    PinnedBuf h_hist;                       // the histogram lent out by pc_fill_hist
+    float last_hist_ms[2] = {0.f, 0.f};     // passes, finish of the last pc_fill_hist / pc_fill_rows_hist with stats (pc_last_hist_times)
     PinnedBuf h_plan;                       // u32 [ncls+1] task offsets, then from word 1000 the u64 totals
     // what the last alignment plan (stage_plan) left in the work buffers, for the stages that follow it
     struct PlanState {
@@ -262,16 +267,16 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
     sum.n_distinct_alignments += one.n_distinct_alignments; sum.n_distinct_cells += one.n_distinct_cells;
 }
 
-// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree / pc_fill_between / pc_fill_affinity, and pc_multi_fill_* over several devices) is ONE description of the
+// A slab fill (pc_fill_edges / pc_fill_components / pc_fill_nearest / pc_fill_tree / pc_fill_between / pc_fill_affinity / pc_fill_hist, and pc_multi_fill_* over several devices) is ONE description of the
 // fill -- a struct of static functions, declared here and defined in pc_fill_slabs.hip (the launchers of its kernels live in pc_edges.hip,
-// pc_components.hip, pc_nearest.hip, pc_tree.hip, pc_between.hip and pc_affinity.hip) -- handed as a template argument to the drivers:
+// pc_components.hip, pc_nearest.hip, pc_tree.hip, pc_between.hip, pc_affinity.hip and pc_hist.hip) -- handed as a template argument to the drivers:
 //   pc_slab_fill<Fill>      one context: check -> begin -> walk [0, N) -> end
 //   pc_slab_stretch<Fill>   the walk over the targets [ta, tb): the slab cut, each slab filled and handed to Fill::slab
 //   multi_slab_fill<Fill>   (pc_multi.hip) begin -> walk(its stretch) -> ship on every device, then merge -> end on the root
 //   pc_rows_slab_fill<Fill> (pc_fill_slabs.hip) a rows form: check -> rows -> Seed::pack -> begin -> Seed::install -> walk the query rows -> end
 // and every extern "C" entry point is its signature, the fields of the run that are its own, and pc_slab_call<Fill> around one of them.
 // What a description says:
-//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut / PcTableOut / PcGenomeTableOut), which can be
+//   kind, Out   its PcSlabKind, and its output shape: the caller's output pointers (PcEdgeOut / PcLabelOut / PcListOut / PcTableOut / PcGenomeTableOut / PcHistOut), which can be
 //           cleared, say whether all are there, and take their values from a finished run
 //   Seed    what a stored result is to the fill (the rows forms): the caller's seed arguments; pack() checks them and packs them into host
 //           memory the call owns, BEFORE begin (the caller may hand back arrays an earlier call lent out, which begin rewrites);
@@ -287,14 +292,14 @@ static void pc_stats_add(pc_stats& sum, const pc_stats& one) {
 //           nothing travels between devices), and how the root takes the others' state in before its end
 // For N <= 1 begin and the walk do nothing on the device.  PcSlabRun is the call as its entry point was given it (pc_slab_check
 // refuses in the public calls' order, folds the metric, normalises the flags and settles kk), its working state, and its results.
-enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE, PC_SLAB_BETWEEN, PC_SLAB_AFFINITY };
+enum PcSlabKind { PC_SLAB_EDGES, PC_SLAB_COMPONENTS, PC_SLAB_NEAREST, PC_SLAB_TREE, PC_SLAB_BETWEEN, PC_SLAB_AFFINITY, PC_SLAB_HIST };
 struct PcSlabRun {
     PcSlabKind kind = PC_SLAB_EDGES;
     const char* who = "";                   // the entry point, for the message texts
     bool outputs = false;                   // every output pointer was there
     int metric = 0, as_distance = 0, strict = 0, k = 0;
     double threshold = 0.0;                 // (nearest: none, stays 0)
-    const int32_t* group = nullptr;         // between, affinity: the caller's labels, host memory, [N]
+    const int32_t* group = nullptr;         // between, affinity: the caller's labels, host memory, [N]; hist: the same, or NULL (no partition)
     int n_groups = 0;                       // ... and their range
     bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold / finish inverts
     bool want_table = false;                // affinity: the whole [N][n_groups] table is delivered beside the O(N) arrays
@@ -320,6 +325,9 @@ struct PcSlabRun {
     const int32_t *af_tab_lo = nullptr, *af_tab_hi = nullptr;
     const int64_t* af_gain_sum = nullptr;   // affinity, rows form with want_gain: [N], else NULL
     const int32_t *af_gain_lo = nullptr, *af_gain_hi = nullptr;
+    const int64_t* hist = nullptr;          // hist: [hist_classes][PC_HIST_BINS]
+    int32_t hist_classes = 0;               // ... 1 without a partition, 2 with one (class 0 within, class 1 between)
+    int64_t hist_pairs = 0;                 // ... the sum of all bins
     int32_t tree_launched = 0;              // tree: rounds enqueued so far (the live ones are counted on the device)
     bool rows_form = false;                 // a rows slab fill (pc_fill_rows_*): edges come row-major, end() sorts them by (target, source)
     int32_t n_query = 0;                    // ... its query rows (all slabs)
@@ -367,6 +375,12 @@ struct PcGenomeTableOut {
         *tab_sum = run.af_tab_sum; *tab_lo = run.af_tab_lo; *tab_hi = run.af_tab_hi; *n_slabs = run.n_slabs;
     }
 };
+struct PcHistOut {
+    const int64_t** hist; int32_t* n_classes; int64_t* n_pairs; int32_t* n_slabs;
+    bool all() const { return hist && n_classes && n_pairs && n_slabs; }
+    void clear() const { if (hist) *hist = nullptr; if (n_classes) *n_classes = 0; if (n_pairs) *n_pairs = 0; if (n_slabs) *n_slabs = 0; }
+    void take(const PcSlabRun& run) const { *hist = run.hist; *n_classes = run.hist_classes; *n_pairs = run.hist_pairs; *n_slabs = run.n_slabs; }
+};
 struct PcPlacementOut {                     // the rows form of the affinity fill: the per-query arrays, and the gain of the old genomes
     PcGenomeTableOut rows; const int64_t** gain_sum; const int32_t **gain_lo, **gain_hi;
     bool all() const { return rows.all() && gain_sum && gain_lo && gain_hi; }
@@ -399,6 +413,12 @@ struct PcBetweenSeed {                      // between: the stored table, four [
     int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
     int install(pc_ctx* c, PcSlabRun& run) const;
 };
+struct PcHistSeed {                         // hist: the stored histogram, i64[classes][PC_HIST_BINS] in the call's direction (NULL: none), as the
+    const int64_t* hist;                    // raw state's bins (distances; empty: no seed)
+    std::vector<unsigned long long> image;
+    int pack(const pc_ctx* c, const PcSlabRun& run, const int32_t* rows, int n_rows);
+    int install(pc_ctx* c, PcSlabRun& run) const;
+};
 #pragma GCC visibility pop
 #define PC_SLAB_FILL(Name, Dom, tag, text, KIND, OUT, SEED)                                                                             \
     struct Name {                                                                                                                       \
@@ -418,6 +438,7 @@ PC_SLAB_FILL(PcNearestFill, PcSlabDomain, "nearest", "a nearest-neighbours fill"
 PC_SLAB_FILL(PcTreeFill, PcSlabDomain, "tree", "a tree fill", PC_SLAB_TREE, PcEdgeOut<int32_t>, PcTreeSeed);
 PC_SLAB_FILL(PcBetweenFill, PcSlabDomain, "between", "a between-groups fill", PC_SLAB_BETWEEN, PcTableOut, PcBetweenSeed);
 PC_SLAB_FILL(PcAffinityFill, PcSlabDomain, "affinity", "an affinity fill", PC_SLAB_AFFINITY, PcGenomeTableOut, PcNoSeed);
+PC_SLAB_FILL(PcHistFill, PcSlabDomain, "hist", "a distribution fill", PC_SLAB_HIST, PcHistOut, PcHistSeed);
 #undef PC_SLAB_FILL
 // What every entry point of these fills does around its driver: the outputs cleared before anything else, kind / outputs / timed into
 // the run (whose call fields the entry point has set), drive(), and on PC_OK the results into the outputs and the run's own stats

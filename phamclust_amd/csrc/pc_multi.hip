@@ -211,7 +211,7 @@ extern "C" int pc_multi_fill_borrow(pc_multi* m, int metric, int as_distance, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Edge, component, nearest, tree, between-groups and affinity fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
+// Edge, component, nearest, tree, between-groups, affinity and distribution fills over the devices of a pc_multi: one driver, multi_slab_fill<Fill>, over the fill's description
 // (pc_host.h, pc_fill_slabs.hip).  Each device runs the description's begin and the walk over ONE contiguous stretch of targets with
 // the call's state on its own device, and ships that state to the root; the state merges exactly -- lists by their total order,
 // forests by uniting g with its foreign parent, edge lists over ascending stretches by concatenation -- so the root's end delivers
@@ -350,6 +350,13 @@ extern "C" int pc_multi_fill_affinity(pc_multi* m, int metric, int as_distance, 
     run.want_table = want_table != 0; run.slab_bytes = slab_bytes;
     return pc_slab_call<PcAffinityFill>(run, {own_sum, own_lo, own_hi, near_group, near_sum, near_lo, near_hi, tab_sum, tab_lo, tab_hi, n_slabs}, stats,
                                         [&] { return multi_slab_fill<PcAffinityFill>(m, run, stats); });
+}
+
+extern "C" int pc_multi_fill_hist(pc_multi* m, int metric, int as_distance, const int32_t* group, int n_groups, int64_t slab_bytes,
+                                  const int64_t** hist, int32_t* n_classes, int64_t* n_pairs, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_multi_fill_hist"; run.metric = metric; run.as_distance = 1; run.bt_invert = !as_distance; run.group = group; run.n_groups = n_groups;
+    run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcHistFill>(run, {hist, n_classes, n_pairs, n_slabs}, stats, [&] { return multi_slab_fill<PcHistFill>(m, run, stats); });
 }
 
 extern "C" int pc_multi_last_stretches(const pc_multi* m, int32_t* bounds) {

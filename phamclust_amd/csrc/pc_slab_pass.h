@@ -1,5 +1,5 @@
-// pc_slab_pass.h -- what a pass over a filled slab is, for the three units that hold one (pc_edges: count and emit, pc_components:
-// union, pc_tree: the scan).  A pass sees the slab as one flat f64[Lp] cut into chunks of SLAB_CHUNK elements, one workgroup each; a
+// pc_slab_pass.h -- what a pass over a filled slab is, for the four units that hold one (pc_edges: count and emit, pc_components:
+// union, pc_tree: the scan, pc_hist: the histogram).  A pass sees the slab as one flat f64[Lp] cut into chunks of SLAB_CHUNK elements, one workgroup each; a
 // thread takes two consecutive elements (one 16-byte load) per iteration.  Which PAIR an element is, and whether it is one at all, is
 // the DOMAIN's business -- every pass body is a template over it, written once:
 //   PcTriDomain    a triangular slab, the shard layout a fill writes with condensed = 0: the values of pairs (s, owned[k]),

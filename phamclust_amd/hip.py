@@ -80,8 +80,10 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_rows_pass_span", "pc_fill_rows_nearest", "pc_nearest_rows_tile", "pc_fill_between", "pc_multi_fill_between", "pc_last_between_times",
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
            "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity",
-           "pc_fill_rows_between"]
+           "pc_fill_rows_between", "pc_fill_hist", "pc_multi_fill_hist", "pc_fill_rows_hist", "pc_last_hist_times", "pc_hist_bins",
+           "pc_hist_table_slots", "pc_hist_probes"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
+HIST_BINS = 1000001                     # pc_hist_bins(): the millionths in [0, 1]
 
 _lib = None
 
@@ -192,6 +194,14 @@ def load():
     L.pc_fill_rows_between.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i64p, _i64p, _i32p, _i32p, ctypes.c_int64,
                                        ctypes.POINTER(_i64p), ctypes.POINTER(_i64p), ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_hist.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i64p), ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_rows_hist.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i64p, ctypes.c_int64, ctypes.POINTER(_i64p),
+                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_last_hist_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pc_hist_bins.argtypes = []
+    L.pc_hist_table_slots.argtypes = []
+    L.pc_hist_probes.argtypes = []
     L.pc_last_affinity_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_affinity_block.argtypes = []
     L.pc_affinity_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -231,6 +241,7 @@ def load():
     L.pc_multi_fill_tree.argtypes = L.pc_fill_tree.argtypes
     L.pc_multi_fill_between.argtypes = L.pc_fill_between.argtypes
     L.pc_multi_fill_affinity.argtypes = L.pc_fill_affinity.argtypes
+    L.pc_multi_fill_hist.argtypes = L.pc_fill_hist.argtypes
     L.pc_multi_last_stretches.argtypes = [vp, _i32p]
     L.pc_multi_last_slab_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_stretch_plan.argtypes = [_u64p, ctypes.c_int, ctypes.c_int, _i32p]
@@ -250,7 +261,7 @@ _slab_values = None                     # the array the library holds a pointer 
 
 def set_slab_values(values):
     """``pc_hook_slab_values``: ``values`` -- float64, C-contiguous, the whole triangle target-major (:func:`triangle_of`) -- stands
-    for every slab that ``fill_edges`` / ``_components`` / ``_nearest`` / ``_tree`` / ``_between`` / ``_affinity`` of any context of
+    for every slab that ``fill_edges`` / ``_components`` / ``_nearest`` / ``_tree`` / ``_between`` / ``_affinity`` / ``_hist`` of any context of
     this process fills from now on; ``None`` clears it.  The array is referenced, not copied: do not write to it while it is set.  Only
     the test-hooks twin (``PHAMCLUST_NATIVE_VARIANT=hooks``) takes it; the release library refuses, and so does this."""
     global _slab_values
@@ -272,7 +283,7 @@ _rows_values = None                     # the array the library holds a pointer 
 
 def set_rows_values(values):
     """``pc_hook_rows_values``: ``values`` -- float64, C-contiguous, ``[n_rows, N]``, row k the values of the call's query genome
-    ``rows[k]`` -- stands for every slab that ``fill_rows_edges`` / ``_components`` / ``_tree`` / ``_nearest`` of any context of this
+    ``rows[k]`` -- stands for every slab that ``fill_rows_edges`` / ``_components`` / ``_tree`` / ``_nearest`` / ``_affinity`` / ``_between`` / ``_hist`` of any context of this
     process fills from now on, every element of it: the diagonal ``[k, rows[k]]`` and both copies of a pair of two query genomes are
     the caller's too.  ``None`` clears it.  Independent of :func:`set_slab_values`.  The array is referenced, not copied: do not write
     to it while it is set.  Only the test-hooks twin (``PHAMCLUST_NATIVE_VARIANT=hooks``) takes it; the release library refuses, and
@@ -396,7 +407,7 @@ class BorrowedArray(np.lib.mixins.NDArrayOperatorsMixin):
 
 
 class _SlabFills:
-    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` / ``fill_between`` / ``fill_affinity`` -- the fills that deliver no dense matrix -- once for :class:`Context`
+    """``fill_edges`` / ``fill_components`` / ``fill_nearest`` / ``fill_tree`` / ``fill_between`` / ``fill_affinity`` / ``fill_hist`` -- the fills that deliver no dense matrix -- once for :class:`Context`
     and :class:`MultiContext`.  The class supplies ``_SLAB_CALL`` (the prefix of the library's symbols), ``_before_slab_fill(metric)``
     (the residues on demand, earlier loans ended; returns the call's stats object) and ``_slab_stats(kind, stats, **own)`` (the stats
     dict of such a fill)."""
@@ -481,6 +492,60 @@ class _SlabFills:
         n_groups = int(n_groups)
         pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
         return self._fill_table(self._SLAB_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, int(slab_bytes)), n_groups, want_stats, borrow)
+
+    def _fill_hist(self, prefix, metric, args, want_stats, borrow):
+        """``hist`` of a distribution fill: int64 ``[n_classes, HIST_BINS]``."""
+        ph = _i64p()
+        ncl, npairs, nsl = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        stats = self._slab_call(prefix + "hist", metric, *args, ctypes.byref(ph), ctypes.byref(ncl), ctypes.byref(npairs), ctypes.byref(nsl))
+        hist = self._lend(ph, (int(ncl.value), HIST_BINS), borrow)
+        if not want_stats:
+            return hist
+        return hist, self._slab_stats("hist", stats, n_classes=int(ncl.value), hist_pairs=int(npairs.value), n_slabs=int(nsl.value))
+
+    def _hist_group(self, who, group, n_groups):
+        """``(group array or None, its pointer or NULL, n_groups)`` of a distribution fill."""
+        if group is None:
+            return None, None, 0
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        if group.shape[0] != self.n_genomes:
+            raise ValueError(f"{who}: group holds {group.shape[0]} labels for {self.n_genomes} genomes")
+        if n_groups is None:
+            n_groups = int(group.max()) + 1 if group.size else 1
+        return group, _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p), int(n_groups)
+
+    def fill_hist(self, metric, group=None, n_groups=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """The exact histogram of every pair value, without the dense matrix: int64 ``[n_classes, HIST_BINS]``, bin k the pairs whose
+        value is k millionths (every delivered value is ``round(x, 6)``: the histogram IS the distribution).  ``group=None``: one
+        class.  ``group[g]`` in ``[0, n_groups)`` (``n_groups`` defaults to the largest label + 1; no cap): two classes, row 0 the
+        pairs inside a group, row 1 the pairs between two.  The bins sum to ``N (N - 1) / 2``.  ``as_distance=False``: the histogram
+        of the inverted matrix, every row reversed (as :meth:`fill_between` inverts; at a decimal tie not a similarity fill's
+        values).  ``matrix.PairDistribution`` reads the array: counts within any threshold, quantiles, exact moments.  The dense
+        matrix is neither delivered nor (beyond ``slab_bytes`` of HBM at a time; 0 = automatic) held, as by :meth:`fill_edges`.
+        The array is a copy; ``borrow=True`` lends the context's page-locked memory instead, on ``fill(borrow=True)``'s terms.
+        ``want_stats`` adds the fills' summed stats with ``n_classes``, ``hist_pairs`` (the sum of all bins), ``n_slabs``, ``ms_pass`` and ``ms_finish``.
+
+        On a :class:`MultiContext`: the same array -- every device counts over its stretch of targets, the root adds the shipped
+        histograms (``k_hist_merge``) and finishes; the stats carry the route's own entries in place of the two times."""
+        group, pgroup, n_groups = self._hist_group("fill_hist", group, n_groups)
+        return self._fill_hist(self._SLAB_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, int(slab_bytes)), want_stats, borrow)
+
+    @staticmethod
+    def hist_table_slots():
+        """Slots of the LDS table a workgroup of the distribution pass counts its chunk in (``pc_hist_table_slots``; no GPU)."""
+        return int(load().pc_hist_table_slots())
+
+    @staticmethod
+    def hist_probes():
+        """Slots an insert into that table tries before it adds to the global bin (``pc_hist_probes``; no GPU)."""
+        return int(load().pc_hist_probes())
+
+    @staticmethod
+    def hist_slot(key):
+        """The first slot of ``key = cls << 20 | micro`` in that table: the top bits of ``key * 2654435761 mod 2**32`` (the hash the
+        C header documents; host arithmetic for the tests that build probe runs)."""
+        slots = _SlabFills.hist_table_slots()
+        return ((int(key) * 2654435761) & 0xFFFFFFFF) >> (32 - (slots.bit_length() - 1))
 
     def fill_affinity(self, metric, group, n_groups=None, as_distance=True, slab_bytes=0, want_table=False, want_stats=False, borrow=False):
         """How every genome relates to every group of a partition (``group`` / ``n_groups`` as :meth:`fill_between` takes them), in
@@ -837,7 +902,7 @@ class Context(_SlabFills):
     # -- fill_edges / fill_components / fill_nearest / fill_tree (_SlabFills): what this class supplies ----------------------------------
     _SLAB_CALL = "pc_fill_"
     _SLAB_TIMES = {"edges": ("pc_last_edge_times", "ms_compact", "ms_d2h"), "components": ("pc_last_component_times", "ms_union", "ms_labels"),
-                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish"), "between": ("pc_last_between_times", "ms_reduce", "ms_finish"),
+                   "nearest": ("pc_last_nearest_times", "ms_select", "ms_finish"), "tree": ("pc_last_tree_times", "ms_rounds", "ms_finish"), "between": ("pc_last_between_times", "ms_reduce", "ms_finish"), "hist": ("pc_last_hist_times", "ms_pass", "ms_finish"),
                    "affinity": ("pc_last_affinity_times", "ms_rows", "ms_cols", "ms_finish")}
     TREE_MAX_GENOMES = 1 << 22            # PC_TREE_MAX_GENOMES: a genome index takes 22 bits of a tree key
     BETWEEN_MAX_GROUPS = 2048             # PC_BETWEEN_MAX_GROUPS: the pass keeps one entry per group in LDS
@@ -1065,6 +1130,28 @@ class Context(_SlabFills):
         pgroup = _ptr(group if group.size else np.zeros(1, dtype=np.int32), _i32p)
         return self._fill_table(self._ROWS_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, prow, n_rows, *pseed, int(slab_bytes)), n_groups,
                                 want_stats, borrow)
+
+    def fill_rows_hist(self, metric, rows, group=None, n_groups=None, seed=None, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """A stored histogram grown by new genomes: :meth:`fill_hist`'s array of the whole collection from ``seed`` -- the array
+        :meth:`fill_hist` gave for the same labels over the genomes that are NOT in ``rows``, in this call's direction -- and the pairs
+        that have a query genome of ``rows`` at one end, each once: ``len(rows) * N`` pairs filled instead of ``N (N - 1) / 2``, and
+        the result is the whole fill's, bin for bin.  ``seed=None``: the histogram over the pairs with a query end alone.  The library
+        refuses a seed with a negative bin, one whose total is not the old genomes' pair count and, with a partition, one whose row 0
+        is not their within count (necessary, not sufficient: a histogram cannot name its pairs).  ``group`` as :meth:`fill_hist`
+        (every genome labelled).  ``as_distance``, ``slab_bytes`` (ranges of ``max(1, slab_bytes // 8 // N)`` rows), ``borrow`` and
+        ``want_stats`` as :meth:`fill_hist`.  One GPU."""
+        if rows is None:
+            raise ValueError("fill_rows_hist: rows is None")
+        group, pgroup, n_groups = self._hist_group("fill_rows_hist", group, n_groups)
+        pseed = None
+        if seed is not None:
+            classes = 1 if group is None else 2
+            seed = np.ascontiguousarray(seed, dtype=np.int64)
+            if seed.shape != (classes, HIST_BINS):
+                raise ValueError(f"fill_rows_hist: seed must be {classes} x {HIST_BINS}, not {seed.shape}")
+            pseed = _ptr(seed, _i64p)
+        rows, prow, n_rows = self._rows_arg(rows)
+        return self._fill_hist(self._ROWS_CALL, metric, (int(bool(as_distance)), pgroup, n_groups, prow, n_rows, pseed, int(slab_bytes)), want_stats, borrow)
 
     def fill_rows_dev(self, metric, as_distance, rows, out_ptr, stream=None, want_stats=True):
         stats = PcStats()

@@ -30,6 +30,8 @@ from phamclust_amd.results.components import (Components, components_de_novo, co
 from phamclust_amd.results.neighbors import (NEAREST_MAX_K, NearestNeighbors, _guard_neighbors, nearest_from_file, nearest_to_file,  # noqa: F401
                                              neighbors_de_novo, neighbors_extend)
 from phamclust_amd.results.tree import SingleLinkageTree, _kruskal, tree_de_novo, tree_extend, tree_from_file, tree_to_file  # noqa: F401
+from phamclust_amd.results.distribution import (HIST_BINS, PairDistribution, distribution_de_novo, distribution_extend,  # noqa: F401
+                                                distribution_from_file, distribution_to_file)
 from phamclust_amd.results.linkage import (BETWEEN_MAX_GROUPS, MILLION, _EMPTY_HI, _EMPTY_LO, GroupLinkage, between_de_novo,  # noqa: F401
                                            between_extend, between_from_file, between_to_file)
 from phamclust_amd.results.affinity import (AFFINITY_KINDS, _AFFINITY_COLUMNS, GroupAffinity, affinity_de_novo, affinity_from_file,  # noqa: F401

@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_extend, between_from_file, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, PairDistribution, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_extend, between_from_file, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, distribution_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -640,6 +640,69 @@ class _Run:
         log.info(f"mean silhouette of the {len(groups):,} clusters and singletons: {text(fit.silhouette_mean())}")
         return fit
 
+    def _distribution_files(self, found, folder, thresholds, clu_similarity=None):
+        """The two files of a distribution -- ``found``, similarities -- into ``folder``: the non-empty bins, and the summary, one
+        ``statistic<TAB>value`` line each: n, min, max, mean, std, skew (``SymMatrix.statistics``' forms, from exact integers), the
+        quartiles, the pairs that pass each of ``thresholds`` (name, similarity) and, for a split distribution, how ``clu_similarity``
+        separates the clusters and the threshold that would separate them best."""
+        found.to_file(folder / f"pairwise_{self.metric}_distribution.tsv")
+        rows = [("n", f"{found.n_pairs}")]
+        if found.n_pairs:
+            mean, std, skew = found.statistics
+            rows += [("min", f"{found.min:.6f}"), ("max", f"{found.max:.6f}"), ("mean", repr(mean)), ("std", repr(std)), ("skew", repr(skew)),
+                     ("q25", f"{found.quantile(0.25):.6f}"), ("median", f"{found.median:.6f}"), ("q75", f"{found.quantile(0.75):.6f}")]
+        rows += [(f"pairs_at_{name}_{value:.6f}", f"{found.count_within(value)}") for name, value in thresholds]
+        if found.partitioned:
+            rows += [("within_pairs", f"{found.within.n_pairs}"), ("between_pairs", f"{found.between.n_pairs}")]
+            beyond, inside = found.separation(clu_similarity)
+            rows += [(f"within_beyond_clu_thresh_{clu_similarity:.6f}", f"{beyond}"), (f"between_inside_clu_thresh_{clu_similarity:.6f}", f"{inside}")]
+            best, beyond, inside = found.best_separation()
+            rows += [("best_separation", f"{best:.6f}"), ("best_separation_within_beyond", f"{beyond}"), ("best_separation_between_inside", f"{inside}")]
+        with open(folder / f"pairwise_{self.metric}_distribution_summary.tsv", "w") as handle:
+            handle.writelines(f"{key}\t{value}\n" for key, value in rows)
+        log.info(f"wrote pairwise_{self.metric}_distribution.tsv ({found.micro.shape[0]:,} occupied bins) and pairwise_{self.metric}_distribution_summary.tsv")
+
+    # 2, --distribution-only
+    def distribution(self, thresholds):
+        """Stage 2 as a distribution fill: the exact histogram of all pair values, and only its two files are written.  Distances are
+        filled and inverted, as for the adjacency file.  No matrix, no threshold, nothing cached or clustered."""
+        self.banner(2, f"{self.metric} pair distribution (distribution fill)")
+        t0 = time.perf_counter()
+        found = distribution_de_novo(self.genomes, METRICS[self.metric], as_distance=True)
+        st = _matrix.LAST_FILL
+        log.info(f"{st.get('genome_pairs', 0):,} pairs -> {found.micro.shape[0]:,} occupied bins from {st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in "
+                 f"{time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, fill+count+D2H "
+                 f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, passes {st.get('ms_pass', 0.0):.3f} ms, finish "
+                 f"{st.get('ms_finish', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        self._distribution_files(found.inverted(), self.outdir, thresholds)
+        return found
+
+    # 4d, --distribution
+    def cluster_distribution(self, groups, matrix, thresholds, clu_distance):
+        """The distribution split by the final clusters (``groups`` as ``cluster_table`` takes them) into the staging directory.  On
+        the dense route it is read off the matrix the run holds (``PairDistribution.from_dense``); on the --no-matrix route one
+        distribution fill runs on the upload that route holds.  Integers either way: the files are the same on both."""
+        self.banner("4d", f"{self.metric} pair distribution within and between the clusters")
+        t0 = time.perf_counter()
+        if matrix is not None:
+            found = PairDistribution.from_dense(matrix, groups)
+            how = "the dense matrix"
+        else:
+            ctx, metric, genome_names = self.fills
+            index = {name: k for k, name in enumerate(genome_names)}
+            label = np.zeros(len(genome_names), dtype=np.int32)
+            for k, group in enumerate(groups):
+                label[[index[name] for name in group]] = k
+            hist, st = ctx.fill_hist(metric, label, len(groups), as_distance=True, want_stats=True)
+            found = PairDistribution.from_hist(hist, is_distance=True, nodes=genome_names)
+            how = f"{st.get('n_slabs', 1)} slab(s) of a distribution fill (passes {st.get('ms_pass', 0.0):.3f} ms)"
+        log.info(f"{found.n_pairs:,} pairs, {found.within.n_pairs:,} of them inside the {len(groups):,} clusters and singletons, from {how} in "
+                 f"{time.perf_counter() - t0:.3f} s")
+        self._distribution_files(found.inverted(), self.stage, thresholds, clu_similarity=round(1.0 - clu_distance, 6))
+        return found
+
     # 5 + 6
     def finish(self, matrix, multi, single, clu_distance, rm_tmp):
         self.banner(5, "dataset outputs")
@@ -686,7 +749,7 @@ class _Run:
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
               components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_table=None, join_min=None,
-              grow_nearest=None, nearest=None):
+              distribution_only=False, distribution=False, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -704,7 +767,16 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     ``cluster_fit_<metric>.tsv`` of an earlier run lacks against its clusters, and write only ``placement_<metric>.tsv`` (``--place``);
     ``grow_table``: with ``place``, the ``cluster_table_<metric>.tsv`` of the run that wrote that file: every new genome joins its nearest
     cluster by mean -- with ``join_min``, a similarity, only when that mean reaches it, else it becomes a singleton group -- and the
-    table is grown by the new genomes' pairs alone (``--grow-table``, ``--join-min``)."""
+    table is grown by the new genomes' pairs alone (``--grow-table``, ``--join-min``); ``distribution_only``: stop after a distribution fill and
+    write only the histogram of all pair similarities and its summary (``--distribution-only``; ``edge_thresh`` then adds a line to the
+    summary); ``distribution``: after the clustering, the same two files split by the final clusters (``--distribution``; with the whole
+    pipeline only, on either route)."""
+    if distribution_only and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
+                              place is not None or cluster_table or cluster_fit or distribution):
+        raise ValueError("distribution_only cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, "
+                         "cluster_table, cluster_fit or distribution")
+    if distribution and (adjacency_only or components_only or tree or nearest is not None or extend is not None or place is not None):
+        raise ValueError("distribution cannot be combined with adjacency_only, components_only, tree, nearest, extend or place")
     if grow_table is not None and place is None:
         raise ValueError("grow_table goes with place")
     if join_min is not None and grow_table is None:
@@ -738,7 +810,7 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         raise ValueError("adjacency_only cannot be combined with extend")
     if components_only and (adjacency_only or extend is not None):
         raise ValueError("components_only cannot be combined with adjacency_only or extend")
-    if edge_thresh is not None and not (adjacency_only or components_only):
+    if edge_thresh is not None and not (adjacency_only or components_only or distribution_only):
         raise ValueError("edge_thresh selects the edges of adjacency_only or components_only")
     if nr_distance >= clu_distance:          # pre-grouping must be tighter than clustering, else switch it off
         nr_distance = 0.0
@@ -757,6 +829,10 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["nearest"] = f"only, {nearest} neighbours per genome"
     if tree:
         settings["tree"] = "only (single-linkage dendrogram)"
+    if distribution_only:
+        settings["histogram"] = "only (--distribution-only: the distribution of all pair similarities)"
+    if distribution:
+        settings["histogram"] = "written, within and between the clusters (--distribution)"
     if cluster_table:
         settings["clusters"] = "with their table (--cluster-table: a between-groups fill)"
     if cluster_fit:
@@ -816,6 +892,18 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         run.tree()
         run.banner(3, "done (--tree: no clustering)")
         return
+    as_similarity = lambda distance: round(1.0 - distance, 6)          # noqa: E731
+    thresholds = [("nr_thresh", as_similarity(nr_distance)), ("clu_thresh", as_similarity(clu_distance)), ("sub_thresh", as_similarity(sub_distance))]
+    if distribution_only:
+        if run.world > 1:
+            log.error("--distribution-only is a one-process call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.distribution(thresholds + ([] if edge_thresh is None else [("edge_thresh", edge_thresh)]))
+        run.banner(3, "done (--distribution-only: no clustering)")
+        return
+    if distribution and run.world > 1:
+        log.error("--distribution is a one-process call: run it in one process, not under a launcher")
+        sys.exit(1)
     if cluster_table and run.world > 1:
         log.error("--cluster-table is a one-process call: run it in one process, not under a launcher")
         sys.exit(1)
@@ -848,6 +936,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         run.cluster_table(final_groups, clu_distance)
     if cluster_fit:
         run.cluster_fit(final_groups)
+    if distribution:
+        run.cluster_distribution(final_groups, matrix, thresholds, clu_distance)
     if no_matrix:
         run.finish_no_matrix(rm_tmp)
     else:
@@ -869,7 +959,8 @@ def _colors(text):
 
 
 SLAB_FILL_FLAGS = (("adjacency_only", "--adjacency-only", "fills an edge list"), ("components_only", "--components-only", "fills component labels"),
-                   ("nearest", "--nearest", "fills nearest-neighbour lists"), ("tree", "--tree", "fills the single-linkage tree"))
+                   ("nearest", "--nearest", "fills nearest-neighbour lists"), ("tree", "--tree", "fills the single-linkage tree"),
+                   ("distribution_only", "--distribution-only", "fills the pair distribution"))
 
 
 def gpus_plan(args, route, packed):
@@ -890,6 +981,8 @@ def gpus_plan(args, route, packed):
         return 1, "one", "--extend fills only the new genomes' rows, which is a one-GPU call: the matrix stage stays on one GPU"
     if route == "launcher" and getattr(args, "cluster_table", False):
         return 1, "one", "--cluster-table fills the clusters' table from one process: the matrix stage stays on one GPU"
+    if route == "launcher" and getattr(args, "distribution", False):
+        return 1, "one", "--distribution reads the clusters' pair distribution from one process: the matrix stage stays on one GPU"
     if route == "launcher" and getattr(args, "cluster_fit", False):
         return 1, "one", "--cluster-fit fills the genomes' affinity to the clusters from one process: the matrix stage stays on one GPU"
     if route == "launcher":
@@ -984,7 +1077,8 @@ def _run(args, argv):
                   cpus=args.threads, rm_tmp=args.remove_tmp, debug=args.debug, extend=args.extend,
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
-                  cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min)
+                  cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min,
+                  distribution_only=args.distribution_only, distribution=args.distribution)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
