@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 170   /* 0.5.19: pc_fill_hist / pc_multi_fill_hist / pc_fill_rows_hist (the exact histogram of all pair values) */
+#define PC_VERSION 171   /* 0.5.20: pc_fill_pairs / pc_fill_pairs_dev (the values of any listed pairs, oriented as written) */
 
 typedef enum {
     PC_OK = 0,
@@ -246,6 +246,37 @@ int pc_fill_groups_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* 
  * group_off[0] != 0 or a decreasing group_off. */
 int64_t pc_group_pair_offsets(const int64_t* group_off, int n_groups, int64_t* pair_off);
 int64_t pc_group_tiles(const int64_t* group_off, int n_groups, int32_t* tile_row, int32_t* tile_col, int64_t cap);
+
+/*
+ * Pair-list fill (PC_VERSION 171): the values of the pairs the caller names, in one call.  This is the reference's most basic interface,
+ * METRICS[metric](source, target) (cli.py:30-35, metrics.py:26-253), for a whole list: entry k is the pair with source genome src[k]
+ * and target genome tgt[k], and out[k] = METRICS[metric](genomes[src[k]], genomes[tgt[k]], as_distance), in the caller's order.  Every
+ * other fill fixes its pair domain by shape (the triangle, whole rows, whole blocks); here the domain is the list: the edges of an
+ * adjacency file under another metric, k-nearest lists rescored, a random sample of a collection too large to fill, a spot check.
+ * The list is ORIENTED: src[k] is the `source` whatever the index order.  With src[k] < tgt[k] the value is the whole fill's cell, bit
+ * for bit; with src[k] > tgt[k] it is the reference's value for the arguments in that order, which differs under aai / aai_ppos / peq
+ * where a tie in gene counts makes the source the anchor (metrics.py:208-209) -- no other fill computes that orientation; the four set
+ * metrics are symmetric.  src[k] == tgt[k] gives the diagonal, 1.0 - as_distance (matrix.py:467-468).  A pair may be listed any number
+ * of times, in either orientation; every entry gets its own value.
+ * The library sorts the list on the device by (target, source) and walks blocks of pc_pair_block() = 256 sorted slots, one plan (per
+ * chunk) merging the duplicate sequence pairs of everything listed.  The six metrics and PC_AAI_PPOS.  gcs / jc / pocp / af always run
+ * on the pairs walker: no selector, and pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill.  aai / peq are cut
+ * into successive ranges of blocks under the rule of pc_set_plan_budget, the 8 bytes per slot of the per-pair count / offset arrays
+ * counting against the budget as in a groups fill; same values whatever the cut.  stats: n_pairs = the entries with src != tgt;
+ * n_alignments, n_cells, n_residue_bytes summed over the entries (an entry listed twice counts twice); n_distinct_* per plan; n_chunks,
+ * n_tasks and the times as for a groups fill (ms_total includes the sort; under gcs / jc / pocp / af ms_plan is the sort and ms_reduce the
+ * walker alone); pc_last_plan_tasks covers this call too.
+ * The context's state and the metric are checked first, as in every fill; then n_pairs == 0: PC_OK, nothing written.  PC_ERR_ARG, nothing launched and out untouched: bad metric; n_pairs < 0; a NULL pointer with
+ * n_pairs > 0; an index outside [0, N) (the message names the entry).  PC_ERR_LIMIT: n_pairs > 2^31-1.  PC_ERR_STATE: before upload, on a
+ * sharded context (world != 1), aai / peq before pc_upload_residues.  PC_ERR_DATA: an empty translation under aai / peq, anywhere in
+ * the collection, as a whole fill.  pc_fill_pairs delivers into host memory f64[n_pairs]; pc_fill_pairs_dev leaves the result in HBM
+ * (out_dev: device f64[n_pairs]; stream as for pc_fill_dev; src and tgt are host memory in both forms, copied before the call returns).
+ */
+int pc_fill_pairs(pc_ctx* ctx, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                  double* out_host, pc_stats* stats);
+int pc_fill_pairs_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                      void* out_dev, void* stream, pc_stats* stats);
+int pc_pair_block(void);     /* slots per block of a pair-list fill (256): host arithmetic, for tests */
 
 /*
  * Edge-list fill: the pairs within a threshold, without the dense matrix.  The reference knows this form of its result twice --

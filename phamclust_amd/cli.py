@@ -117,6 +117,13 @@ _OPTIONS = (
                                                                       "(default: every non-zero similarity, what the pipeline's file holds); with "
                                                                       "--components-only: join genomes of distance below 1 - this similarity "
                                                                       "(default 0.0: any non-zero similarity joins)")),
+    (None, "-L", "--pairs", dict(type=pathlib.Path, default=None, help="stop after the matrix stage and write only pairwise_<metric>_pairs.tsv: FILE names "
+                                                                      "one pair per line, two tab-separated genome names (further columns are ignored, "
+                                                                      "so an adjacency file of any metric is valid input); the file written holds "
+                                                                      "source<TAB>target<TAB>similarity in FILE's order, each pair oriented as written, "
+                                                                      "from one pair-list fill on one GPU; nothing else is computed")),
+    (None, "-f", "--prefilter", dict(action="store_true", help="with --adjacency-only -m peq --edge-thresh SIM: fill the af edge list at SIM first (peq "
+                                                               "never exceeds af) and align only its pairs; the same file byte for byte, on one GPU")),
     (None, "-t", "--threads", dict(type=int, default=CPUS, help="accepted for compatibility; the six metrics run on the GPU (see --gpus)")),
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),
@@ -228,4 +235,23 @@ def parse_args(argv=None):
                 parser.error(f"--no-matrix runs the whole pipeline without the dense matrix; it cannot be combined with {flag}")
         if args.gpus > 1:
             parser.error("--no-matrix: the components and groups fills are one-GPU calls; it cannot be combined with --gpus N")
+    if args.pairs is not None:
+        for flag, given in (("--adjacency-only", args.adjacency_only), ("--components-only", args.components_only), ("--no-matrix", args.no_matrix),
+                            ("--nearest", args.nearest is not None), ("--tree", args.tree), ("--distribution-only", args.distribution_only),
+                            ("--distribution", args.distribution), ("--extend", args.extend is not None), ("--grow", args.grow is not None),
+                            ("--place", args.place is not None), ("--cluster-table", args.cluster_table), ("--cluster-fit", args.cluster_fit),
+                            ("--prefilter", args.prefilter)):
+            if given:
+                parser.error(f"--pairs stops after a pair-list fill of its own; it cannot be combined with {flag}")
+        if args.gpus > 1:
+            parser.error("--pairs: the pair-list fill is a one-GPU call; it cannot be combined with --gpus N")
+    if args.prefilter:
+        if not args.adjacency_only:
+            parser.error("--prefilter bounds the edge list of --adjacency-only; give --adjacency-only -m peq --edge-thresh SIM")
+        if args.metric != "peq":
+            parser.error(f"--prefilter is the af bound of peq; it serves no other metric (-m {args.metric})")
+        if args.edge_thresh is None:
+            parser.error("--prefilter needs --edge-thresh SIM: without a threshold every pair that shares a pham is a candidate")
+        if args.gpus > 1:
+            parser.error("--prefilter: the pair-list fill is a one-GPU call; it cannot be combined with --gpus N")
     return args

@@ -287,34 +287,39 @@ static int count_per_target(pc_ctx* c, int condensed, hipStream_t st, std::vecto
 // Which walk a stage launches, over which slots: the owned targets [k0, k1) of the context's shard (k_walk; slot arrays indexed
 // by the shard-local pair index), or -- rows != NULL -- the query rows [k0, k1) of a rows fill (k_walk_rows; slot arrays
 // [k1 - k0][N], filled for that range alone), or -- groups != NULL -- the row blocks [k0, k1) of a groups fill (k_walk_groups; slot
-// arrays hold that range's slots, first slot block_slot[k0]).
-static int walk_domain(pc_ctx* c, int mode, const PcRows* rows, const PcGroupsHost* groups, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
-    if (rows) return pc_launch_walk_rows(mode, c->dev, *rows, k0, k1, a, st);
-    if (groups) {
-        PcGroups sub = groups->dev;
-        sub.slot_base = groups->block_slot[k0];
-        return pc_launch_walk_groups(mode, c->dev, sub, groups->block_tile[k0], groups->block_tile[k1], a, st);
+// arrays hold that range's slots, first slot block_slot[k0]), or -- dom.pairs -- the blocks [k0, k1) of a pair-list fill (k_walk_pairs;
+// slot arrays hold that range's slots, first slot k0 * PC_PAIR_BLOCK).
+static int walk_domain(pc_ctx* c, int mode, const PcUnitDomain& dom, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
+    if (dom.rows) return pc_launch_walk_rows(mode, c->dev, *dom.rows, k0, k1, a, st);
+    if (dom.groups) {
+        PcGroups sub = dom.groups->dev;
+        sub.slot_base = dom.groups->block_slot[k0];
+        return pc_launch_walk_groups(mode, c->dev, sub, dom.groups->block_tile[k0], dom.groups->block_tile[k1], a, st);
+    }
+    if (dom.pairs) {
+        PcPairs sub = dom.pairs->dev;
+        sub.slot_base = (int64_t)k0 * PC_PAIR_BLOCK;
+        return pc_launch_walk_pairs(mode, c->dev, sub, k0, k1, a, st);
     }
     PcShard sub = c->shard;
     sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
     return pc_launch_walk(mode, c->dev, sub, a, st);
 }
 
-// PLAN of the owned targets (or query rows, or row blocks of a groups fill) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
+// PLAN of the owned targets (or the units of dom) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
 // sorted by launch class.  Leaves its results in the context's work buffers and c->plan; two small read-backs.
-static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A, const PcRows* rows = nullptr,
-                      const PcGroupsHost* groups = nullptr) {
+static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0, int k1, uint64_t A, const PcUnitDomain& dom = PcUnitDomain{}) {
     int rc = PC_OK;
     PcRange range("pc:plan");
     PlanningScope planning;
     const PcDev& d = c->dev;
     pc_ctx::PlanState& P = c->plan;
     P.valid = false; P.ppos = ppos; P.condensed = condensed; P.A = (int64_t)A; P.n_distinct = 0; P.ntasks = 0; P.tb.assign(c->nlc + 1, 0);
-    P.k0 = k0; P.k1 = k1; P.whole = !rows && !groups && c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
+    P.k0 = k0; P.k1 = k1; P.whole = !dom.any() && c->world == 1 && condensed == 1 && k0 == 0 && k1 == c->shard.nown;
     memset(&P.st, 0, sizeof(P.st));
     pc_stats& local = P.st;
-    const int64_t base = (rows || groups) ? 0 : c->h_lbase[k0];
-    const int64_t Lc = rows ? (int64_t)(k1 - k0) * d.N : groups ? groups->block_slot[k1] - groups->block_slot[k0] : c->h_lbase[k1] - base;
+    const int64_t base = dom.any() ? 0 : c->h_lbase[k0];
+    const int64_t Lc = dom.any() ? dom.slots(k0, k1, d.N) : c->h_lbase[k1] - base;
     local.n_pairs = Lc;
     local.n_alignments = (int64_t)A;
     if (A > (uint64_t)PC_PLAN_MAX_ALIGNMENTS) {
@@ -346,7 +351,7 @@ static int stage_plan(pc_ctx* c, int ppos, int condensed, hipStream_t st, int k0
         const int64_t tmp_elems = (int64_t)(c->b_scan_tmp.cap / 4);
         // 2 ENUM: one sort key per alignment slot; 3 sort; 4 distinct alignments, aliases, buckets (pc_plan.hip)
         a.key = c->b_key0.as<unsigned long long>(); a.val = c->b_val0.as<uint32_t>();
-        if ((rc = walk_domain(c, PCW_ENUM, rows, groups, k0, k1, a, st))) return rc;
+        if ((rc = walk_domain(c, PCW_ENUM, dom, k0, k1, a, st))) return rc;
         if ((rc = pc_sort_pairs(c->b_sort_tmp.p, c->b_sort_tmp.cap, c->b_key0.as<unsigned long long>(), c->b_key1.as<unsigned long long>(),
                                 c->b_val0.as<uint32_t>(), c->b_val1.as<uint32_t>(), An, key_bits, st))) return rc;
         if ((rc = pc_launch_mark_heads(c->b_key1.as<unsigned long long>(), c->b_flags.as<uint32_t>(), An, st))) return rc;
@@ -421,15 +426,14 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
 }
 
 // REDUCE: best match per anchor gene through the aliases, fp64 epilogue (metrics.py:204-232, 247-253), over the plan's targets
-static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcRows* rows = nullptr,
-                        const PcGroupsHost* groups = nullptr) {
+static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcUnitDomain& dom = PcUnitDomain{}) {
     PcRange range("pc:reduce");
     pc_ctx::PlanState& P = c->plan;
     if (!P.valid) { pc_set_error("reduce: no plan (pc_plan_dev first)"); return PC_ERR_STATE; }
     PcWalkArgs a; memset(&a, 0, sizeof(a));
     a.off = c->b_off.as<uint32_t>(); a.alias = c->b_alias.as<uint32_t>(); a.res = res; a.out = out;
     a.as_distance = as_distance ? 1 : 0; a.condensed = P.condensed;
-    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, rows, groups, P.k0, P.k1, a, st);
+    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, dom, P.k0, P.k1, a, st);
 }
 
 // a finished chunk: its plan's counts, and its tasks per launch class for pc_last_plan_tasks
@@ -444,14 +448,14 @@ static void set_last_plan_tasks(pc_ctx* c, const std::vector<uint32_t>& per_clas
     c->last_plan_tasks_valid = true;
 }
 
-// One plan -> align -> reduce over the owned targets (or query rows, or row blocks) [k0, k1) holding A alignments, and its counts added
+// One plan -> align -> reduce over the owned targets (or the units of dom) [k0, k1) holding A alignments, and its counts added
 // to `local`.  events: ev[1] and ev[2] are recorded between the stages (ev[3] after them always); ms != NULL: the step is waited for and its
 // three stage times, the first counted from `from`, are added to ms[0..2].
 static int chunk_step(pc_ctx* c, int metric, int ppos, int as_distance, int condensed, double* out, hipStream_t st, int k0, int k1, uint64_t A,
-                      const PcRows* rows, const PcGroupsHost* groups, pc_stats& local, bool events, hipEvent_t from, float* ms) {
-    int rc = stage_plan(c, ppos, condensed, st, k0, k1, A, rows, groups);
+                      const PcUnitDomain& dom, pc_stats& local, bool events, hipEvent_t from, float* ms) {
+    int rc = stage_plan(c, ppos, condensed, st, k0, k1, A, dom);
     if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
-    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, rows, groups); }
+    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, dom); }
     if (rc != PC_OK) return rc;
     PC_HIP(hipEventRecord(c->ev[3], st));
     add_plan_stats(c, local);
@@ -490,7 +494,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
     local.n_chunks = 0;
     if (A <= max_aln) {
         // (its stage times are read by fill_impl: ev[0] .. ev[3])
-        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, 0, nown, A, nullptr, nullptr, local, true, nullptr, nullptr);
+        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, 0, nown, A, PcUnitDomain{}, local, true, nullptr, nullptr);
         if (rc == PC_OK) {
             local.n_chunks = 1;
             c->last_plan_tasks_valid = true;
@@ -511,7 +515,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
         uint64_t run = per_owned[k]; int k1 = k + 1;
         while (k1 < nown && run + per_owned[k1] <= max_aln) { run += per_owned[k1]; ++k1; }
         if (timed) PC_HIP(hipEventRecord(c->ev[4], st));
-        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, k, k1, run, nullptr, nullptr, local, timed, c->ev[4], timed ? ms : nullptr);
+        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, k, k1, run, PcUnitDomain{}, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller chunk, not an error
             if ((rc = release_for_retry(c, st, false))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run) / 2, 1);
@@ -528,20 +532,21 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
 }
 
 // aai / peq over a domain that is cut into UNITS -- the query rows of a rows fill (pc_fill_rows*), the row blocks of TS positions of a
-// groups fill (pc_fill_groups*): COUNT over every unit (totals, alignments per unit: aln_t), then plan -> align -> reduce over successive
+// groups fill (pc_fill_groups*), the blocks of PC_PAIR_BLOCK slots of a pair-list fill (pc_fill_pairs*): COUNT over every unit (totals, alignments per unit: aln_t), then plan -> align -> reduce over successive
 // ranges of units.  The ranges follow pc_chunk_plan over the units' costs under the budget a whole fill has (pc_set_plan_budget /
 // PC_PLAN_BYTES, 2^31-2 alignments per plan, a failed allocation halves the range); a unit costs its alignments plus its slots of na /
 // off (8 bytes each, stated in alignments), so a request of many units never holds more than a range's worth of slot arrays.  A range of
-// units is a range of slots: N per query row; for row blocks block_slot[] says where (and a range of the tile list, block_tile[]).  One
+// units is a range of slots: N per query row; for row blocks block_slot[] says where (and a range of the tile list, block_tile[]); a
+// block of a pair list holds PC_PAIR_BLOCK consecutive slots.  One
 // plan per range merges the duplicate sequence pairs of everything the range touches.  `out` is the whole result; the reduce of a range
 // writes its cells (a rows fill: also the mirror cells of pairs of two queries).  Values do not depend on the cut: every pair's
 // alignments stay in one range.
-static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out,
+static int fill_units_aligned(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out,
                               hipStream_t st, pc_stats& local, bool timed) {
     int rc = PC_OK;
     const PcDev& d = c->dev;
-    const int U = rows ? rows->nrows : groups->nblocks;
-    auto slots = [&](int k0, int k1) { return rows ? (int64_t)(k1 - k0) * d.N : groups->block_slot[k1] - groups->block_slot[k0]; };
+    const int U = dom.units();
+    auto slots = [&](int k0, int k1) { return dom.slots(k0, k1, d.N); };
     if ((rc = fill_check_residues(c, "fill", metric))) return rc;
     if (d.G > 0 && c->min_gene_len == 0) {
         pc_set_error("fill: an empty translation cannot be aligned (aai/peq); the reference fails on it too"); return PC_ERR_DATA;
@@ -558,7 +563,7 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
         PC_HIP(hipMemsetAsync(c->b_aln_t.p, 0, (size_t)U * 8, st));
         PcWalkArgs a; memset(&a, 0, sizeof(a));
         a.totals = c->b_totals.as<unsigned long long>(); a.aln_t = c->b_aln_t.as<unsigned long long>();
-        if ((rc = walk_domain(c, PCW_COUNT, rows, groups, 0, U, a, st))) return rc;
+        if ((rc = walk_domain(c, PCW_COUNT, dom, 0, U, a, st))) return rc;
         uint64_t* h_tot = (uint64_t*)(c->h_plan.as<uint32_t>() + 1000);
         PC_HIP(hipMemcpyAsync(h_tot, c->b_totals.p, 24, hipMemcpyDeviceToHost, st));
         PC_HIP(hipMemcpyAsync(own.data(), c->b_aln_t.p, (size_t)U * 8, hipMemcpyDeviceToHost, st));
@@ -595,9 +600,9 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
             PC_HIP(hipMemsetAsync(c->b_na.p, 0, (Lc + 1) * 4, st));
             PcWalkArgs a; memset(&a, 0, sizeof(a));
             a.na = c->b_na.as<uint32_t>(); a.totals = c->b_totals.as<unsigned long long>() + 5;
-            rc = walk_domain(c, PCW_COUNT, rows, groups, k, k1, a, st);
+            rc = walk_domain(c, PCW_COUNT, dom, k, k1, a, st);
         }
-        if (rc == PC_OK) rc = chunk_step(c, metric, ppos, as_distance, 0, out, st, k, k1, run, rows, groups, local, timed, c->ev[4], timed ? ms : nullptr);
+        if (rc == PC_OK) rc = chunk_step(c, metric, ppos, as_distance, 0, out, st, k, k1, run, dom, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller range, not an error
             if ((rc = release_for_retry(c, st, true))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run + run_slot_cost) / 2, 1);
@@ -613,15 +618,15 @@ static int fill_units_aligned(pc_ctx* c, const PcRows* rows, const PcGroupsHost*
     return PC_OK;
 }
 
-// a rows fill (the units are the query rows) or a groups fill (the row blocks of TS positions), every metric: the set metrics always run
-// on the domain's walker, all units in one launch (no selector: pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill)
-int fill_units(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out, hipStream_t st,
-               pc_stats& local, bool timed) {
-    if (metric >= PC_AAI) return fill_units_aligned(c, rows, groups, metric, ppos, as_distance, out, st, local, timed);
+// a rows fill (the units are the query rows), a groups fill (the row blocks of TS positions) or a pair-list fill (the blocks of
+// PC_PAIR_BLOCK slots), every metric: the set metrics always run on the domain's walker, all units in one launch (no selector:
+// pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill)
+int fill_units(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
+    if (metric >= PC_AAI) return fill_units_aligned(c, dom, metric, ppos, as_distance, out, st, local, timed);
     PcWalkArgs a; memset(&a, 0, sizeof(a));
     a.out = out; a.as_distance = as_distance;
     const int mode = metric == PC_GCS ? PCW_GCS : metric == PC_JC ? PCW_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
-    return walk_domain(c, mode, rows, groups, 0, rows ? rows->nrows : groups->nblocks, a, st);
+    return walk_domain(c, mode, dom, 0, dom.units(), a, st);
 }
 
 // ---- alignment-sliced multi-GPU route (aai / peq): every rank plans the whole (unsharded) fill -- milliseconds --, aligns

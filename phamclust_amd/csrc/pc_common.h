@@ -97,6 +97,18 @@ struct PcGroups {
     int64_t slot_base;                // first slot the na / off arrays of this launch hold (a range of row blocks is a range of slots)
 };
 
+// Pair domain of a pair-list fill: L slots, the caller's list sorted by (target, source) on the device (k_walk_pairs).  Slot i is the
+// ORIENTED pair with source genome src[i] and target genome tgt[i] -- whatever their index order -- and its value goes to out[at[i]],
+// the entry's position in the caller's list.  src[i] == tgt[i] is the diagonal: a dead slot, no alignment and no visit.
+#define PC_PAIR_BLOCK 256     // slots per workgroup of k_walk_pairs: the unit a pair-list fill is cut by
+struct PcPairs {
+    int64_t L;                        // slots
+    const int32_t* src;               // [L] source genome
+    const int32_t* tgt;               // [L] target genome
+    const uint32_t* at;               // [L] the caller's index of the entry
+    int64_t slot_base;                // first slot the na / off arrays of this launch hold (a range of blocks is a range of slots)
+};
+
 // One wave task of the alignment kernels: column gene + a range of its bucket.
 struct PcTask { int32_t gene, begin, end, pad; };   // pad: launch class of the task (planning only)
 
@@ -118,7 +130,7 @@ struct PcTaskPlan {
 
 // walker modes (pc_walk.hip)
 enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5,
-       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows / k_walk_groups only (whole fills count gcs / jc on the tile kernels)
+       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows / k_walk_groups / k_walk_pairs only (whole fills count gcs / jc on the tile kernels)
 enum { PCW_SPARSE_GCS = 10, PCW_SPARSE_JC = 11 };   // k_sparse_tile64 only: shared-pham counts, one direction
 
 struct PcWalkArgs {
@@ -127,10 +139,11 @@ struct PcWalkArgs {
     unsigned long long* totals;       // [0] alignments [1] cells [2] residue bytes (as the reference would run them)
     unsigned long long* cost_t;       // [N] or NULL: DP cells per target genome (input of the cost-balanced deal)
     unsigned long long* aln_t;        // [N] or NULL: alignments per target genome (where a fill that exceeds its memory budget is cut);
-                                      //   k_walk_rows: [nrows], alignments per query row (aln_row); k_walk_groups: per row block of positions
+                                      //   k_walk_rows: [nrows], alignments per query row (aln_row); k_walk_groups: per row block of positions;
+                                      //   k_walk_pairs: per block of PC_PAIR_BLOCK slots
     // ENUM: alignment slot k of a pair = off[pair] + its position in the reference's loop order
     const uint32_t* off;              // [Lp] exclusive scan of na   (k_walk_rows: na / off are [rows of the range][N], slot (k - kb) * N + g;
-                                      //   k_walk_groups: the range's slots, slot - slot_base)
+                                      //   k_walk_groups, k_walk_pairs: the range's slots, slot - slot_base)
     unsigned long long* key;          // [A] (column sequence rank << ubits) | row sequence rank
     uint32_t* val;                    // [A] k
     // AAI / PEQ
@@ -175,6 +188,12 @@ int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs
 int pc_launch_walk_rows(int mode, const PcDev& d, const PcRows& rw, int kb, int ke, const PcWalkArgs& a, hipStream_t st);
 // the walker over the tiles [tb, te) of a groups fill; a.out is the whole f64[L], a.condensed is not read
 int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t tb, int64_t te, const PcWalkArgs& a, hipStream_t st);
+// the walker over the blocks [bb, be) of PC_PAIR_BLOCK slots of a pair-list fill; a.out is the whole f64[L] in the caller's order,
+// a.aln_t is per block, a.condensed is not read
+int pc_launch_walk_pairs(int mode, const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcWalkArgs& a, hipStream_t st);
+// a pair list's sort: key[i] = tgt[i] << 32 | src[i], val[i] = i before pc_sort_pairs; src / tgt back out of the sorted keys after it
+int pc_launch_pair_keys(const int32_t* src, const int32_t* tgt, unsigned long long* key, uint32_t* val, int64_t n, hipStream_t st);
+int pc_launch_pair_split(const unsigned long long* key, int32_t* src, int32_t* tgt, int64_t n, hipStream_t st);
 int pc_launch_sparse(int mode, const PcDev& d, const PcShard& sh, double* out, int as_distance, int condensed, hipStream_t st, pc_set_shape* shape_out = nullptr);   // pocp / af
 int pc_launch_pair_entries(const int32_t* pham, const int32_t* len, const int32_t* cnt, uint2* pair_len, uint2* pair_cnt, int64_t n, hipStream_t st);
 int pc_launch_sp_build(int N, const uint32_t* ent_off, const int32_t* pham, const int32_t* len, const int32_t* cnt, const int32_t* dense, int W2,

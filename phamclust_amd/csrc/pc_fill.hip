@@ -1,6 +1,6 @@
 // pc_fill.hip -- the fill entry points of libphamclust_hip.so over the whole matrix or shard (pc_fill, pc_fill_borrow, pc_fill_dev,
-// pc_fill_shard_dev, pc_assemble_dev) and over the rows and groups domains (pc_fill_rows, pc_fill_rows_dev, pc_fill_groups,
-// pc_fill_groups_dev): the frame they share, and pick_set_kernel, which gathers the selector's inputs from the context (the selector itself:
+// pc_fill_shard_dev, pc_assemble_dev) and over the rows, groups and pairs domains (pc_fill_rows, pc_fill_rows_dev, pc_fill_groups,
+// pc_fill_groups_dev, pc_fill_pairs, pc_fill_pairs_dev): the frame they share, and pick_set_kernel, which gathers the selector's inputs from the context (the selector itself:
 // pc_set_shape.hip).  The slab walks pc_fill_edges / pc_fill_components: pc_fill_slabs.hip.
 #include "pc_host.h"
 
@@ -157,11 +157,11 @@ extern "C" int pc_fill_shard_dev(pc_ctx* c, int metric, int as_distance, void* s
 }
 
 // ---- the domain fills: pairs of a domain other than the shard's -- the query rows of a rows fill, the within-group pairs of a groups
-// fill -- on an unsharded context.  Their entry points open with fill_check, validate the domain, and hand the rest to fill_domain: the
+// fill, the listed pairs of a pair-list fill -- on an unsharded context.  Their entry points open with fill_check, validate the domain, and hand the rest to fill_domain: the
 // residues check, the wait for whatever may still read the domain's device tables (upload_tables rewrites them by blocking copies and
-// leaves the device view in *rows / *groups), fill_units, the close.  local: zeroed but for n_pairs.
+// leaves the device view in what dom points to), fill_units, the close.  local: zeroed but for n_pairs.
 template <class Tables>
-static int fill_domain(pc_ctx* c, const char* who, const char* const* range_names, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos,
+static int fill_domain(pc_ctx* c, const char* who, const char* const* range_names, const PcUnitDomain& dom, int metric, int ppos,
                        int as_distance, void* out_dev, void* stream, pc_stats& local, pc_stats* stats, Tables upload_tables) {
     int rc = PC_OK;
     if ((rc = fill_check_residues(c, who, metric))) return rc;
@@ -171,7 +171,7 @@ static int fill_domain(pc_ctx* c, const char* who, const char* const* range_name
     if ((rc = wait_last_work(c, st, false))) return rc;
     if ((rc = upload_tables())) return rc;
     PC_HIP(hipEventRecord(c->ev[0], st));
-    rc = fill_units(c, rows, groups, metric, ppos, as_distance ? 1 : 0, (double*)out_dev, st, local, stats != nullptr);
+    rc = fill_units(c, dom, metric, ppos, as_distance ? 1 : 0, (double*)out_dev, st, local, stats != nullptr);
     return fill_close(c, metric, st, rc, local, stats, false);
 }
 
@@ -191,7 +191,8 @@ extern "C" int pc_fill_rows_dev(pc_ctx* c, int metric, int as_distance, const in
     local.n_pairs = (int64_t)n_rows * (N - 1) - (int64_t)n_rows * (n_rows - 1) / 2;
     static const char* const fill_names[] = {"pc:fill_rows:gcs", "pc:fill_rows:jc", "pc:fill_rows:pocp", "pc:fill_rows:af", "pc:fill_rows:aai", "pc:fill_rows:peq"};
     PcRows rw{};
-    return fill_domain(c, "pc_fill_rows", fill_names, &rw, nullptr, metric, ppos, as_distance, out_dev, stream, local, stats, [&]() -> int {
+    PcUnitDomain dom; dom.rows = &rw;
+    return fill_domain(c, "pc_fill_rows", fill_names, dom, metric, ppos, as_distance, out_dev, stream, local, stats, [&]() -> int {
         std::vector<int32_t> h_rows(rows, rows + n_rows), h_row_of((size_t)N, -1);
         for (int k = 0; k < n_rows; ++k) h_row_of[rows[k]] = k;
         int rc = PC_OK;
@@ -291,7 +292,8 @@ extern "C" int pc_fill_groups_dev(pc_ctx* c, int metric, int as_distance, const 
     local.n_pairs = L;
     static const char* const fill_names[] = {"pc:fill_groups:gcs", "pc:fill_groups:jc", "pc:fill_groups:pocp", "pc:fill_groups:af", "pc:fill_groups:aai", "pc:fill_groups:peq"};
     PcGroupsHost gh;
-    return fill_domain(c, "pc_fill_groups", fill_names, nullptr, &gh, metric, ppos, as_distance, out_dev, stream, local, stats, [&]() -> int {
+    PcUnitDomain dom; dom.groups = &gh;
+    return fill_domain(c, "pc_fill_groups", fill_names, dom, metric, ppos, as_distance, out_dev, stream, local, stats, [&]() -> int {
         // the per-position tables and the tile list
         std::vector<int32_t> h_genome(members, members + M), h_end((size_t)M), h_trow, h_tcol;
         std::vector<int64_t> h_rowbase((size_t)M + 1);
@@ -326,6 +328,95 @@ extern "C" int pc_fill_groups(pc_ctx* c, int metric, int as_distance, const int3
     if (L > 0 && group_off[n_groups] > 0x7fffffffLL) { pc_set_error("pc_fill_groups: %lld members exceed 2^31-1", (long long)group_off[n_groups]); return PC_ERR_ARG; }
     return fill_to_host(c, L, out_host, true,
                         [&](void* out_dev, void* st) { return pc_fill_groups_dev(c, metric, as_distance, members, group_off, n_groups, out_dev, st, stats); });
+}
+
+// ---- pair-list fill: the pairs the caller names, METRICS[metric](genomes[src[k]], genomes[tgt[k]]) for every entry k, f64[n_pairs] in the
+// caller's order.  The list is oriented (src is the reference's `source`), may repeat a pair and may hold the diagonal (src == tgt: 1 -
+// as_distance).  It is sorted on the device by (target, source) with the caller's index as the value; the walker then runs over blocks of
+// PC_PAIR_BLOCK sorted slots (k_walk_pairs) and scatters each value to its entry.
+extern "C" int pc_pair_block(void) { return PC_PAIR_BLOCK; }
+
+// What both forms check before anything is allocated or launched, in one pass over the list; *n_live: the entries with src != tgt.
+// Returns PC_OK with *n_live = -1 when there is nothing to do (n_pairs == 0).
+static int pairs_check(const pc_ctx* c, int* metric, int* ppos, const int32_t* src, const int32_t* tgt, int64_t n_pairs, const void* out, int64_t* n_live) {
+    int rc = PC_OK;
+    *n_live = -1;
+    if ((rc = fill_check(c, "pc_fill_pairs", "a pair-list fill", metric, ppos))) return rc;
+    if (n_pairs < 0) { pc_set_error("pc_fill_pairs: n_pairs %lld", (long long)n_pairs); return PC_ERR_ARG; }
+    if (n_pairs == 0) return PC_OK;
+    if (n_pairs > 0x7fffffffLL) { pc_set_error("pc_fill_pairs: %lld pairs exceed the 2^31-1 one call takes", (long long)n_pairs); return PC_ERR_LIMIT; }
+    if (!src || !tgt || !out) { pc_set_error("pc_fill_pairs: %s is NULL", !src ? "src" : !tgt ? "tgt" : "out"); return PC_ERR_ARG; }
+    const int N = c->dev.N;
+    int64_t live = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        if (src[k] < 0 || src[k] >= N || tgt[k] < 0 || tgt[k] >= N) {
+            pc_set_error("pc_fill_pairs: entry %lld is (%d, %d); genome indices lie in [0, %d)", (long long)k, src[k], tgt[k], N); return PC_ERR_ARG;
+        }
+        live += src[k] != tgt[k];
+    }
+    if ((rc = fill_check_residues(c, "pc_fill_pairs", *metric))) return rc;
+    *n_live = live;
+    return PC_OK;
+}
+
+// the checked list (L > 0 entries, n_live of them off the diagonal) onto the device, sorted, and filled
+static int fill_pairs_run(pc_ctx* c, int metric, int ppos, int as_distance, const int32_t* src, const int32_t* tgt, int64_t L, int64_t n_live,
+                          void* out_dev, void* stream, pc_stats* stats) {
+    int rc = PC_OK;
+    PC_ON_DEVICE(c);
+    static const char* const fill_names[] = {"pc:fill_pairs:gcs", "pc:fill_pairs:jc", "pc:fill_pairs:pocp", "pc:fill_pairs:af", "pc:fill_pairs:aai", "pc:fill_pairs:peq"};
+    PcRange range(fill_names[metric]);
+    hipStream_t st = (hipStream_t)stream;
+    pc_stats local; memset(&local, 0, sizeof(local));
+    local.n_pairs = n_live;
+    if ((rc = wait_last_work(c, st, false))) return rc;
+    int key_bits = 33;
+    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < c->dev.N) ++key_bits;
+    const size_t sort_bytes = pc_sort_temp_bytes(L, key_bits);
+    if ((rc = upload_raw(c->b_pr_src, src, (size_t)L * 4)) || (rc = upload_raw(c->b_pr_tgt, tgt, (size_t)L * 4))) return rc;
+    if ((rc = c->b_pr_at.ensure((size_t)L * 4)) || (rc = c->b_key0.ensure((size_t)L * 8)) || (rc = c->b_key1.ensure((size_t)L * 8)) ||
+        (rc = c->b_val0.ensure((size_t)L * 4)) || (rc = c->b_sort_tmp.ensure(std::max<size_t>(sort_bytes, 16)))) return abi_rc(rc);
+    PC_HIP(hipEventRecord(c->ev[0], st));
+    // the sort: (target << 32 | source, entry) -> slots; the plan buffers it borrows are free until the first plan of the fill
+    if ((rc = pc_launch_pair_keys(c->b_pr_src.as<int32_t>(), c->b_pr_tgt.as<int32_t>(), c->b_key0.as<unsigned long long>(), c->b_val0.as<uint32_t>(), L, st)) ||
+        (rc = pc_sort_pairs(c->b_sort_tmp.p, c->b_sort_tmp.cap, c->b_key0.as<unsigned long long>(), c->b_key1.as<unsigned long long>(),
+                            c->b_val0.as<uint32_t>(), c->b_pr_at.as<uint32_t>(), L, key_bits, st)) ||
+        (rc = pc_launch_pair_split(c->b_key1.as<unsigned long long>(), c->b_pr_src.as<int32_t>(), c->b_pr_tgt.as<int32_t>(), L, st))) {
+        (void)mark_work(c, st); return rc;
+    }
+    const bool split_times = stats && metric < PC_AAI;                     // a set metric: ms_plan is the sort, ms_reduce the walker alone
+    if (split_times) PC_HIP(hipEventRecord(c->ev[1], st));
+    PcPairsHost ph;
+    ph.dev = PcPairs{L, c->b_pr_src.as<int32_t>(), c->b_pr_tgt.as<int32_t>(), c->b_pr_at.as<uint32_t>(), 0};
+    ph.nblocks = (int)((L + PC_PAIR_BLOCK - 1) / PC_PAIR_BLOCK);
+    PcUnitDomain dom; dom.pairs = &ph;
+    rc = fill_units(c, dom, metric, ppos, as_distance ? 1 : 0, (double*)out_dev, st, local, stats != nullptr);
+    if (rc != PC_OK && metric < PC_AAI) (void)mark_work(c, st);            // (the sort is in flight; the aligned routes are marked by the close)
+    rc = fill_close(c, metric, st, rc, local, stats, false);
+    if (rc == PC_OK && split_times) {                                      // (the close has waited for ev[3])
+        PC_HIP(hipEventElapsedTime(&stats->ms_plan, c->ev[0], c->ev[1]));
+        PC_HIP(hipEventElapsedTime(&stats->ms_reduce, c->ev[1], c->ev[3]));
+    }
+    return rc;
+}
+
+extern "C" int pc_fill_pairs_dev(pc_ctx* c, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                                 void* out_dev, void* stream, pc_stats* stats) {
+    int ppos = 0, rc = PC_OK;
+    int64_t n_live = 0;
+    if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out_dev, &n_live))) return rc;
+    if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
+    return fill_pairs_run(c, metric, ppos, as_distance, src, tgt, n_pairs, n_live, out_dev, stream, stats);
+}
+
+extern "C" int pc_fill_pairs(pc_ctx* c, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                             double* out_host, pc_stats* stats) {
+    int ppos = 0, rc = PC_OK;
+    int64_t n_live = 0;
+    if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out_host, &n_live))) return rc;
+    if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
+    return fill_to_host(c, n_pairs, out_host, true,
+                        [&](void* out_dev, void* st) { return fill_pairs_run(c, metric, ppos, as_distance, src, tgt, n_pairs, n_live, out_dev, st, stats); });
 }
 
 extern "C" int pc_assemble_dev(pc_ctx* c, const void* gathered_dev, int world, void* out_condensed_dev, void* stream) {

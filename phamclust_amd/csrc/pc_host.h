@@ -121,6 +121,7 @@ struct pc_ctx {
     DevBuf b_tasks, b_tasks_sorted, b_bucket_row, b_bucket_dest, b_res, b_totals, b_plan, b_scratch, b_out, b_lut, b_slice_begin, b_aln_t;
     DevBuf b_rows, b_row_of;                // the domain of the last rows fill (PcRows: the query genomes, and every genome's position among them)
     DevBuf b_grp_genome, b_grp_end, b_grp_rowbase, b_grp_trow, b_grp_tcol;   // the domain of the last groups fill (PcGroups)
+    DevBuf b_pr_src, b_pr_tgt, b_pr_at;     // the domain of the last pair-list fill (PcPairs): the caller's list as uploaded, then sorted
     // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
     DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
     DevBuf b_rq_rows, b_rq_query;           // a rows slab fill: every query row of the call, ascending, and is_query[N] (PcRowsSlab)
@@ -241,6 +242,26 @@ struct PcGroupsHost {
     int nblocks = 0;                        // row blocks = ceil(M / TS)
     std::vector<int64_t> block_tile;        // [nblocks+1] first tile of row block a; [nblocks] = T
     std::vector<int64_t> block_slot;        // [nblocks+1] first slot of row block a = pos_rowbase[a * TS]; [nblocks] = L
+};
+
+// A pair-list fill's domain as the host sees it: the device view and its blocks of PC_PAIR_BLOCK slots.
+struct PcPairsHost {
+    PcPairs dev{};
+    int nblocks = 0;                        // ceil(L / PC_PAIR_BLOCK); block k holds the slots [k * PC_PAIR_BLOCK, min((k + 1) * PC_PAIR_BLOCK, L))
+};
+// The domain of a fill that is cut into UNITS (fill_units): exactly one of the three is set -- the query rows of a rows fill, the row
+// blocks of a groups fill, the blocks of slots of a pair-list fill.  None set: the owned targets of the context's shard (a whole fill).
+struct PcUnitDomain {
+    const PcRows* rows = nullptr;
+    const PcGroupsHost* groups = nullptr;
+    const PcPairsHost* pairs = nullptr;
+    bool any() const { return rows || groups || pairs; }
+    int units() const { return rows ? rows->nrows : groups ? groups->nblocks : pairs ? pairs->nblocks : 0; }
+    int64_t slots(int k0, int k1, int N) const {              // a range of units is a range of slots
+        if (rows) return (int64_t)(k1 - k0) * N;
+        if (groups) return groups->block_slot[k1] - groups->block_slot[k0];
+        return std::min<int64_t>((int64_t)k1 * PC_PAIR_BLOCK, pairs->dev.L) - (int64_t)k0 * PC_PAIR_BLOCK;
+    }
 };
 
 // What every fill entry point checks of its context and its metric before anything of its own.  `who` names the caller in the message
@@ -470,7 +491,7 @@ int pc_count_target_costs(pc_ctx* c);
 int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st, pc_stats* stats);
 // aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
 int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);
-// a rows fill (rows != NULL; out: f64[rows->nrows][N]) or a groups fill (groups != NULL; out: f64[L]) once its domain tables are on the
-// device: the set metrics in one launch of the domain's walker, aai / peq chunked over ranges of query rows / of row blocks (pc_align.hip)
-int fill_units(pc_ctx* c, const PcRows* rows, const PcGroupsHost* groups, int metric, int ppos, int as_distance, double* out, hipStream_t st,
-               pc_stats& local, bool timed);
+// a rows fill (dom.rows; out: f64[rows->nrows][N]), a groups fill (dom.groups; out: f64[L]) or a pair-list fill (dom.pairs; out: f64[L]
+// in the caller's order) once its domain tables are on the device: the set metrics in one launch of the domain's walker, aai / peq
+// chunked over ranges of query rows / of row blocks / of blocks of slots (pc_align.hip)
+int fill_units(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);

@@ -1,7 +1,8 @@
-// pc_walk.hip -- the shared-pham walker over its three pair domains: k_walk (whole fills: pocp / af, alignment counting and planning,
-// the best-match reduce of aai / peq), k_walk_rows (rows fills: the same and gcs / jc) and k_walk_groups (groups fills: as the rows
-// walker, over the within-group pairs of a family of groups).  One core -- the visit of a shared pham, the visits of a bitmap word,
-// the value epilogue, the COUNT totals -- serves all three kernels, so each rule of the reference is stated once.
+// pc_walk.hip -- the shared-pham walker over its four pair domains: k_walk (whole fills: pocp / af, alignment counting and planning,
+// the best-match reduce of aai / peq), k_walk_rows (rows fills: the same and gcs / jc), k_walk_groups (groups fills: as the rows
+// walker, over the within-group pairs of a family of groups) and k_walk_pairs (pair-list fills: as the rows walker, over a flat list
+// of oriented pairs).  One core -- the visit of a shared pham, the visits of a bitmap word, the value epilogue, the COUNT totals --
+// serves all four kernels, so each rule of the reference is stated once.
 //
 // Reference semantics restated here (metrics.py of the reference unless named):
 //   metrics.py:83-115, 118-157   pocp / af: sums over shared phams of gene counts / lengths     (pc_visit, pc_walk_value)
@@ -9,6 +10,7 @@
 //   metrics.py:247-253           peq = round(af, 6) * round(aai, 6), then round(., 6)            (pc_walk_value)
 //   matrix.py:169-213, 467-486   the rows domain: source = min, target = max, the diagonal      (k_walk_rows)
 //   matrix.py:155-167, 479-486   the groups domain: a sub-matrix's pairs, source = the smaller index (k_walk_groups)
+//   metrics.py:26-253            the pairs domain: METRICS[metric](source, target) as called        (k_walk_pairs)
 #include "pc_pairs.h"
 
 #define WCH 32         // bitmap words staged per chunk (17 KB of LDS per workgroup: nine workgroups per CU hide the staging latency)
@@ -468,5 +470,118 @@ int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("k_walk_groups launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// The walker over a PAIRS domain (pc_fill_pairs): a flat list of pairs the caller names, the reference's most basic interface,
+// METRICS[metric](source, target), for many pairs in one call.  The host sorts the list on the device by (target, source)
+// (k_pair_keys -> pc_sort_pairs -> k_pair_split), so slot i holds source src[i], target tgt[i] and the caller's position at[i]:
+// neighbouring lanes mostly share their target row, and entries listed twice sit side by side.
+//
+// The list is ORIENTED: src[i] is the reference's `source` and tgt[i] its `target` whatever their index order.  pc_visit decides
+// the anchor from the two entries it is handed (fewer genes, tie -> source) and pc_walk_value reads per-genome sums only, so the two
+// genomes pass through as given: with src < tgt the value is the whole fill's cell bit for bit, with src > tgt (aai, aai_ppos, peq)
+// it is the other orientation, which no other fill computes.  src == tgt is the diagonal, 1 - as_distance (matrix.py:467-468): a
+// dead slot, no visit, no alignment.
+//
+// A workgroup takes PC_PAIR_BLOCK consecutive slots, one lane per slot.  A list has no tile to amortise an LDS stage over: each
+// lane reads the words of its two rows straight from the bitmap (in a sorted wave the target's word is mostly one address for all
+// lanes; a source row is one 128-byte line per 16 words).  The two-step scan of the other walkers holds: which of up to WCH words
+// intersect goes into one 32-bit mask, the visits follow, so a wave stays together through the word loop.  Slot arrays (na, off)
+// hold the launch's slots, slot - slot_base; COUNT adds a workgroup's alignments into aln_t[block] (where a pair-list fill is cut);
+// ENUM emits k_walk's keys.  GCS / JC count in the word scan, as in k_walk_rows.
+// ---------------------------------------------------------------------------------
+static_assert(PC_PAIR_BLOCK == 256, "k_walk_pairs runs one lane per slot of a block");
+template <int MODE>
+__global__ __launch_bounds__(256) void k_walk_pairs(PcDev d, PcPairs pr, int64_t bb, PcWalkArgs a) {
+    constexpr bool SETS = MODE == PCW_GCS || MODE == PCW_JC;                        // shared-pham counts: no visit
+    constexpr bool SLOTS = MODE == PCW_ENUM || MODE == PCW_AAI || MODE == PCW_PEQ;  // walks the pair's alignment slots
+    __shared__ unsigned long long red[3];
+    const int64_t block = bb + blockIdx.x;
+    const int64_t slot = block * PC_PAIR_BLOCK + threadIdx.x;
+    const bool in = slot < pr.L;
+    const int s = in ? pr.src[slot] : 0, t = in ? pr.tgt[slot] : 0;                 // (a lane past the list scans genome 0 against itself, and visits nothing)
+    const bool ok = in && s != t;
+    PcPairAcc acc; acc.reset();
+    if (ok && SLOTS) acc.k = a.off[slot - pr.slot_base];
+    unsigned long long cells = 0, rbytes = 0;
+    if (MODE == PCW_COUNT) { if (threadIdx.x < 3) red[threadIdx.x] = 0; __syncthreads(); }
+
+    const uint64_t* const ps = d.bitmap + (int64_t)s * d.Wstride;
+    const uint64_t* const pt = d.bitmap + (int64_t)t * d.Wstride;
+    const uint32_t* const rps = d.rankpre + (int64_t)s * d.Wb;
+    const uint32_t* const rpt = d.rankpre + (int64_t)t * d.Wb;
+    for (int w0 = 0; w0 < d.Wb; w0 += WCH) {
+        const int wn = min(WCH, d.Wb - w0);
+        uint32_t nz = 0u;
+        for (int i = 0; i < wn; ++i) {
+            const uint64_t both = ps[w0 + i] & pt[w0 + i];
+            if (SETS) acc.k += (uint32_t)__popcll(both);
+            else nz |= (both != 0 ? 1u : 0u) << i;
+        }
+        if constexpr (!SETS) {
+            uint32_t todo = ok ? nz : 0u;
+            while (todo) {
+                const int w = w0 + __ffs((int)todo) - 1;
+                todo &= todo - 1;
+                pc_walk_word<MODE>(d, a, acc, ps[w], pt[w], rps[w], rpt[w], cells, rbytes);
+            }
+        }
+    }
+
+    if (MODE == PCW_COUNT) {
+        const uint32_t n = ok ? acc.k : 0u;
+        if (ok && a.na) a.na[slot - pr.slot_base] = n;
+        pc_walk_totals(red, a.totals, n, cells, rbytes);
+        if (a.aln_t && threadIdx.x == 0 && red[0]) atomicAdd(&a.aln_t[block], red[0]);        // (red[] is final behind the barrier of pc_walk_totals)
+        return;
+    }
+    if (MODE == PCW_ENUM) return;
+    if (!in) return;
+    a.out[pr.at[slot]] = ok ? pc_walk_value<MODE>(d, acc, s, t, a.as_distance) : (a.as_distance ? 0.0 : 1.0);
+}
+
+int pc_launch_walk_pairs(int mode, const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcWalkArgs& a, hipStream_t st) {
+    const int64_t nb = (pr.L + PC_PAIR_BLOCK - 1) / PC_PAIR_BLOCK;
+    if (bb < 0 || bb > be || be > nb || be - bb > 0x7fffffffLL) { pc_set_error("pc_launch_walk_pairs: blocks [%lld, %lld) of %lld", (long long)bb, (long long)be, (long long)nb); return PC_ERR_ARG; }
+    if (be == bb || d.N < 1) return PC_OK;
+    dim3 grid((unsigned)(be - bb)), block(PC_PAIR_BLOCK);
+    if (!pc_dispatch<PCW_GCS, PCW_JC, PCW_POCP, PCW_AF, PCW_COUNT, PCW_ENUM, PCW_AAI, PCW_PEQ>(
+            mode, [&](auto m) { hipLaunchKernelGGL(k_walk_pairs<decltype(m)::value>, grid, block, 0, st, d, pr, bb, a); })) {
+        pc_set_error("pc_launch_walk_pairs: bad mode %d", mode); return PC_ERR_ARG;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_walk_pairs launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+// The sort of a pair list, around pc_sort_pairs: entry i -> key tgt << 32 | src, value i; and the sorted keys back into src / tgt.
+__global__ __launch_bounds__(256) void k_pair_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt, unsigned long long* __restrict__ key,
+                                                   uint32_t* __restrict__ val, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    key[i] = ((unsigned long long)(uint32_t)tgt[i] << 32) | (unsigned long long)(uint32_t)src[i];
+    val[i] = (uint32_t)i;
+}
+__global__ __launch_bounds__(256) void k_pair_split(const unsigned long long* __restrict__ key, int32_t* __restrict__ src, int32_t* __restrict__ tgt, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = key[i];
+    src[i] = (int32_t)(uint32_t)(k & 0xffffffffull);
+    tgt[i] = (int32_t)(uint32_t)(k >> 32);
+}
+int pc_launch_pair_keys(const int32_t* src, const int32_t* tgt, unsigned long long* key, uint32_t* val, int64_t n, hipStream_t st) {
+    if (n <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, tgt, key, val, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_pair_keys launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+int pc_launch_pair_split(const unsigned long long* key, int32_t* src, int32_t* tgt, int64_t n, hipStream_t st) {
+    if (n <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_pair_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key, src, tgt, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_pair_split launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
     return PC_OK;
 }

@@ -81,7 +81,7 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
            "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity",
            "pc_fill_rows_between", "pc_fill_hist", "pc_multi_fill_hist", "pc_fill_rows_hist", "pc_last_hist_times", "pc_hist_bins",
-           "pc_hist_table_slots", "pc_hist_probes"]
+           "pc_hist_table_slots", "pc_hist_probes", "pc_fill_pairs", "pc_fill_pairs_dev", "pc_pair_block"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 HIST_BINS = 1000001                     # pc_hist_bins(): the millionths in [0, 1]
 
@@ -147,6 +147,9 @@ def load():
     L.pc_group_pair_offsets.restype = ctypes.c_int64
     L.pc_group_tiles.argtypes = [_i64p, ctypes.c_int, _i32p, _i32p, ctypes.c_int64]
     L.pc_group_tiles.restype = ctypes.c_int64
+    L.pc_fill_pairs.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, _f64p, ctypes.POINTER(PcStats)]
+    L.pc_fill_pairs_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, vp, vp, ctypes.POINTER(PcStats)]
+    L.pc_pair_block.restype = ctypes.c_int
     L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                 ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_last_edge_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
@@ -886,6 +889,44 @@ class Context(_SlabFills):
         self._check(self._lib.pc_fill_groups_dev(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(members if members.size else np.zeros(1, np.int32), _i32p),
                                                  _ptr(off, _i64p), len(off) - 1, ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0),
                                                  ctypes.byref(stats) if want_stats else None))
+        return stats.as_dict() if want_stats else None
+
+    @staticmethod
+    def _pair_arrays(src, tgt):
+        """``src`` / ``tgt`` (genome indices) as the C-ABI's two int32 arrays of one length."""
+        src, tgt = np.asarray(src).reshape(-1), np.asarray(tgt).reshape(-1)
+        if src.shape[0] != tgt.shape[0]:
+            raise ValueError(f"fill_pairs: {src.shape[0]} sources and {tgt.shape[0]} targets")
+        for name, arr in (("src", src), ("tgt", tgt)):                 # before the cast: an index beyond 32 bits must not wrap into range
+            if arr.size and (arr.dtype.kind not in "iu" or int(arr.min()) < -2 ** 31 or int(arr.max()) >= 2 ** 31):
+                raise ValueError(f"fill_pairs: {name} must hold integer genome indices that fit 32 bits")
+        return np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(tgt, dtype=np.int32)
+
+    def fill_pairs(self, metric, src, tgt, as_distance=True, want_stats=False):
+        """The pairs ``(src[k], tgt[k])`` in one call -> a float64 array in the caller's order: ``out[k]`` is the reference's
+        ``METRICS[metric](genomes[src[k]], genomes[tgt[k]])``, ORIENTED as written (with ``src[k] < tgt[k]`` the whole fill's cell;
+        reversed, under aai / peq, the other orientation), ``src[k] == tgt[k]`` the diagonal.  A pair may be listed any number of times."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        src, tgt = self._pair_arrays(src, tgt)
+        out = np.empty(src.shape[0], dtype=np.float64)
+        one = np.zeros(1, np.int32)
+        self._check(self._lib.pc_fill_pairs(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(src if src.size else one, _i32p),
+                                            _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), _ptr(out if out.size else np.zeros(1), _f64p),
+                                            ctypes.byref(stats)))
+        return (out, stats.as_dict()) if want_stats else out
+
+    def fill_pairs_dev(self, metric, as_distance, src, tgt, out_ptr, stream=None, want_stats=True):
+        """The same, left in HBM at ``out_ptr`` as one float64 vector in the caller's order (``src`` / ``tgt`` are host arrays)."""
+        stats = PcStats()
+        if metric in NEEDS_RESIDUES:
+            self.ensure_residues()
+        src, tgt = self._pair_arrays(src, tgt)
+        one = np.zeros(1, np.int32)
+        self._check(self._lib.pc_fill_pairs_dev(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(src if src.size else one, _i32p),
+                                                _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), ctypes.c_void_p(out_ptr),
+                                                ctypes.c_void_p(stream or 0), ctypes.byref(stats) if want_stats else None))
         return stats.as_dict() if want_stats else None
 
     EDGE_MAX_PAIRS = 2 ** 31 - 1          # pairs one slab of an edge-list fill may hold (u32 counts and offsets on the device)

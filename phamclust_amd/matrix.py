@@ -25,6 +25,7 @@ from phamclust_amd.routes import (LAST_FILL, _CONTEXTS, _de_novo_route, _extend_
                                   get_multi_context, in_process_devices, upload_for_fills)
 from phamclust_amd.results._common import _grown_positions, _live_row_pairs, _positions_without  # noqa: F401
 from phamclust_amd.results.edges import SparseEdges, _guard_edges, edges_de_novo, edges_extend, merge_edge_lists  # noqa: F401
+from phamclust_amd.results.pairs import pairs_de_novo  # noqa: F401
 from phamclust_amd.results.components import (Components, components_de_novo, components_extend, components_from_file,  # noqa: F401
                                               components_to_file)
 from phamclust_amd.results.neighbors import (NEAREST_MAX_K, NearestNeighbors, _guard_neighbors, nearest_from_file, nearest_to_file,  # noqa: F401

@@ -6,6 +6,8 @@ the reference's source genome (anchor on ties, metrics.py:208-209).  No CPU fall
 
 Bulk use goes through ``matrix_de_novo`` (it recognises these callables and fills the
 whole matrix in one device pass); calling them in a Python loop is correct but slow.
+The values of many NAMED pairs, each oriented as written, come from ``matrix.pairs_de_novo``
+(one upload, one pair-list fill).
 """
 
 from phamclust_amd.genome import Genome

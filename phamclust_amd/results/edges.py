@@ -112,6 +112,24 @@ class SparseEdges:
         return SparseEdges([self.nodes[k] for k in keep_at.tolist()], new_at[self.source[keep]], new_at[self.target[keep]], self.weight[keep],
                            is_distance=self.is_distance, threshold=self.threshold)
 
+    def rescored(self, genomes, func, as_distance=None):
+        """The same edges in the same order with their weights from another metric: ``func`` over every listed pair, each with its
+        ``source`` node as the reference's source, by ONE pair-list fill (``pairs_de_novo``).  ``genomes`` must hold every node of the
+        list (``KeyError`` otherwise; it may hold more); with the nodes in the genomes' relative order -- as every list a fill
+        delivers has them -- the weights are the cells of ``matrix_de_novo(genomes, func, ...)``.  ``as_distance``: the direction of
+        the new weights (``None``: the list's own).  The result carries no threshold: what passed under one metric is no threshold
+        set under another."""
+        from phamclust_amd.results.pairs import pairs_de_novo
+        as_distance = self.is_distance if as_distance is None else bool(as_distance)
+        index = {g.name: k for k, g in enumerate(genomes)}
+        stranger = next((node for node in self.nodes if node not in index), None)
+        if stranger is not None:
+            raise KeyError(f"SparseEdges.rescored: node '{stranger}' is not among the genomes")
+        at = np.fromiter((index[node] for node in self.nodes), dtype=np.int64, count=len(self.nodes))
+        pairs = np.stack([at[self.source], at[self.target]], axis=1) if len(self) else np.empty((0, 2), dtype=np.int64)
+        weight = pairs_de_novo(genomes, func, pairs, as_distance=as_distance)
+        return SparseEdges(self.nodes, self.source, self.target, weight, is_distance=as_distance, threshold=None)
+
     def inverted(self):
         """distance <-> similarity: every weight becomes round(1 - w, 6), as ``SymMatrix.invert`` does (matrix.py:236-247)."""
         return SparseEdges(self.nodes, self.source, self.target, np.round(1.0 - self.weight, 6), is_distance=not self.is_distance,
@@ -127,13 +145,54 @@ class SparseEdges:
         return _square_matrix(self.nodes, data, self.is_distance)
 
 
-def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0):
+PREFILTER_SLACK = 2e-6      # how far below the request the af candidates of a prefiltered peq edge list are taken (see edges_de_novo)
+
+
+def _prefiltered_peq_edges(ctx, threshold, as_distance, slab_bytes):
+    """The peq edge list within ``threshold`` behind its af bound, on an uploaded context: ``(src, tgt, val, stats)``.
+
+    peq = round(round(af, 6) * round(aai, 6), 6) (metrics.py:247-253) and round(aai, 6) <= 1.0, so a pair's delivered peq similarity
+    never exceeds its delivered af similarity ``a``, and its delivered peq distance is never below round(1 - a, 6).  A pair that passes
+    a similarity request ``sim >= threshold`` therefore has ``a >= threshold``; one that passes a distance request ``d <= threshold``
+    has round(1 - a, 6) <= threshold, so ``a >= 1 - threshold - 0.5e-6``.  The candidates are the af SIMILARITY edges at the request's
+    similarity bound less ``PREFILTER_SLACK`` (four times the half-millionth of the rounding, and far above the error of the
+    subtraction): a superset of every passing pair, in the edge list's own order.  The peq values of the candidates alone come from
+    one pair-list fill, and the request's own predicate over those delivered values cuts the list: the plain fill's, element for
+    element."""
+    bound = ((1.0 - threshold) if as_distance else threshold) - PREFILTER_SLACK
+    c_src, c_tgt, _, af_stats = ctx.fill_edges("af", bound, as_distance=False, slab_bytes=slab_bytes, want_stats=True, borrow=True)
+    src, tgt = np.array(c_src, dtype=np.int32), np.array(c_tgt, dtype=np.int32)       # out of the loan before the next call
+    val, stats = ctx.fill_pairs("peq", src, tgt, as_distance=as_distance, want_stats=True)
+    keep = _passes(val, threshold, as_distance)
+    stats.update(n_edges=int(keep.sum()), n_slabs=int(af_stats["n_slabs"]), n_candidates=int(src.shape[0]), af_ms_total=float(af_stats["ms_total"]),
+                 af_ms_d2h=float(af_stats.get("ms_d2h", 0.0)))
+    return src[keep], tgt[keep], val[keep], stats
+
+
+def edges_de_novo(genomes, func, threshold, as_distance=True, slab_bytes=0, prefilter=False):
     """The edges of ``matrix_de_novo(genomes, func, cpus, as_distance)`` within ``threshold`` as a :class:`SparseEdges`, filled
     on the GPU by ``Context.fill_edges``: the dense matrix is never delivered, and beyond ``slab_bytes`` of HBM (0: automatic)
     never held.  ``func`` must be one of the six ``METRICS`` callables: there is no CPU route for this call (a generic callable
     has ``matrix_de_novo`` and ``SparseEdges.from_dense``).  With ``PHAMCLUST_GPUS`` / ``PHAMCLUST_GPU_IDS`` naming more than one
     device the fill is spread over them from this process (``MultiContext.fill_edges``: a contiguous stretch of targets per device,
-    the same edges); under a launcher (``WORLD_SIZE`` > 1) it raises."""
+    the same edges); under a launcher (``WORLD_SIZE`` > 1) it raises.
+
+    ``prefilter=True`` (peq only; any other metric raises ``ValueError`` before any GPU call): the same list, element for element,
+    in three steps on one GPU -- the af edge list at a bound no passing pair can miss (``_prefiltered_peq_edges`` has the proof),
+    the peq values of those candidates alone by a pair-list fill, the request's predicate over them -- so no pair outside the af
+    list is ever aligned.  What it saves depends on the threshold: much at a tight one, little at the clustering threshold."""
+    if prefilter:
+        from phamclust_amd.routes import _metric_name
+        if _metric_name(func) != "peq":
+            raise ValueError("edges_de_novo: prefilter=True is the af bound of peq and serves no other metric "
+                             f"(func is {_metric_name(func) or 'no METRICS callable'})")
+        names, (src, tgt, val) = _de_novo_route(genomes, func, "edges_de_novo",
+            lambda ctx, metric: _prefiltered_peq_edges(ctx, threshold, as_distance, slab_bytes),
+            lambda stats, record, fill_s: (
+                f"{len(genomes)} genomes -> {stats['n_edges']} of {stats['n_candidates']} af candidates of {record['genome_pairs']} edges on one "
+                f"device: af edges + peq pairs + D2H {fill_s:.3f} s (peq kernels {stats['ms_total']:.3f} ms, {stats['n_alignments']} alignments)"),
+            several=False)
+        return SparseEdges(names, src, tgt, val, is_distance=as_distance, threshold=threshold)
     names, (src, tgt, val) = _de_novo_route(genomes, func, "edges_de_novo",
         lambda ctx, metric: ctx.fill_edges(metric, threshold, as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
         lambda stats, record, fill_s: (

@@ -99,6 +99,23 @@ def load_genomes(filepath):
         return sorted(load_genomes_from_tsv(filepath), key=lambda g: g.name)
 
 
+def read_pairs_file(filepath):
+    """The pairs a ``--pairs`` file names: the first two tab-separated columns of every line, as (source name, target name) in file
+    order.  Further columns are ignored, so an adjacency file of any metric is valid input; an empty line is skipped; a line with
+    one column raises ``ValueError`` naming it."""
+    pairs = []
+    with open(filepath) as handle:
+        for number, line in enumerate(handle, start=1):
+            line = line.rstrip("\r\n")
+            if not line:
+                continue
+            fields = line.split("\t")
+            if len(fields) < 2 or not fields[0] or not fields[1]:
+                raise ValueError(f"{filepath}, line {number}: expected two tab-separated genome names, got {line!r}")
+            pairs.append((fields[0], fields[1]))
+    return pairs
+
+
 def _hash_genomes(genomes):
     """md5 of the concatenated FASTA text, genomes in the order given (the cache key)."""
     md5 = hashlib.md5()
@@ -223,16 +240,20 @@ class _Run:
         return matrix
 
     # 2, --adjacency-only
-    def adjacency(self, similarity):
+    def adjacency(self, similarity, prefilter=False):
         """Stage 2 as an edge-list fill: the pairs of similarity >= ``similarity`` (None: every non-zero one) straight into
         ``pairwise_<metric>_adjacency.tsv`` -- the file ``finish`` writes from the dense matrix (name order instead of cluster
-        order), without the dense matrix: nothing is cached, nothing is clustered."""
+        order), without the dense matrix: nothing is cached, nothing is clustered.  ``prefilter`` (peq, with a threshold): the same
+        list behind its af bound (``edges_de_novo(..., prefilter=True)``)."""
         self.banner(2, f"{self.metric} adjacency (edge-list fill)")
         t0 = time.perf_counter()
         distance = 0.999999 if similarity is None else round(1.0 - similarity, 6)       # 6-place values: d <= 0.999999 is sim > 0
-        edges = edges_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True)
+        edges = edges_de_novo(self.genomes, METRICS[self.metric], distance, as_distance=True, prefilter=prefilter)
         st = _matrix.LAST_FILL
         pairs = st.get("genome_pairs", 0)
+        if prefilter:
+            log.info(f"--prefilter: {st.get('n_candidates', 0):,} of {pairs:,} pairs are af candidates; {st.get('n_alignments', 0):,} alignments "
+                     f"({st.get('n_distinct_alignments', 0):,} distinct) behind them")
         log.info(f"{len(edges):,} of {pairs:,} pairs ({100.0 * len(edges) / max(pairs, 1):.1f} %) within distance {distance:.6f} from "
                  f"{st.get('n_slabs', 1)} slab(s) on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload "
                  f"{st.get('upload_s', 0.0):.3f}, fill+compact+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, "
@@ -243,6 +264,27 @@ class _Run:
         edges_to_adjacency(edges.inverted(), target, skip_zero=True)
         log.info(f"wrote {target.name}")
         return edges
+
+    # 2, --pairs
+    def pairs(self, listing):
+        """Stage 2 as a pair-list fill: the pairs ``listing`` names (``read_pairs_file``), each oriented as written, into
+        ``pairwise_<metric>_pairs.tsv`` as ``source<TAB>target<TAB>similarity`` in the listing's order.  Nothing else is computed."""
+        self.banner(2, f"{self.metric} of the listed pairs (pair-list fill)")
+        t0 = time.perf_counter()
+        named = read_pairs_file(listing)
+        values = _matrix.pairs_de_novo(self.genomes, METRICS[self.metric], named, as_distance=False)
+        st = _matrix.LAST_FILL
+        log.info(f"{len(named):,} listed pairs ({st.get('n_pairs', 0):,} off the diagonal) of {len(self.genomes):,} genomes on 1 GPU in "
+                 f"{time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, sort+fill+D2H "
+                 f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms)")
+        if self.metric in _metrics.PARITY_NOTE:
+            log.info(f"parity: {_metrics.parity_note(self.metric)}")
+        target = self.outdir / f"pairwise_{self.metric}_pairs.tsv"
+        with open(target, "w") as handle:
+            for (source, other), value in zip(named, values.tolist()):
+                handle.write(f"{source}\t{other}\t{value:.6f}\n")
+        log.info(f"wrote {target.name}")
+        return values
 
     # 2, --components-only
     def components(self, similarity):
@@ -749,7 +791,7 @@ class _Run:
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
               components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_table=None, join_min=None,
-              distribution_only=False, distribution=False, grow_nearest=None, nearest=None):
+              distribution_only=False, distribution=False, pairs=None, prefilter=False, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -770,7 +812,15 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     table is grown by the new genomes' pairs alone (``--grow-table``, ``--join-min``); ``distribution_only``: stop after a distribution fill and
     write only the histogram of all pair similarities and its summary (``--distribution-only``; ``edge_thresh`` then adds a line to the
     summary); ``distribution``: after the clustering, the same two files split by the final clusters (``--distribution``; with the whole
-    pipeline only, on either route)."""
+    pipeline only, on either route); ``pairs``: stop after a pair-list fill of the pairs that file names and write only
+    ``pairwise_<metric>_pairs.tsv`` (``--pairs``); ``prefilter``: with ``adjacency_only``, peq and an ``edge_thresh``, the same adjacency
+    file from the af edge list's pairs alone (``--prefilter``)."""
+    if pairs is not None and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
+                              place is not None or cluster_table or cluster_fit or distribution or distribution_only or prefilter):
+        raise ValueError("pairs cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, cluster_table, "
+                         "cluster_fit, distribution, distribution_only or prefilter")
+    if prefilter and not (adjacency_only and metric == "peq" and edge_thresh is not None):
+        raise ValueError("prefilter goes with adjacency_only, the peq metric and an edge_thresh")
     if distribution_only and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
                               place is not None or cluster_table or cluster_fit or distribution):
         raise ValueError("distribution_only cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, "
@@ -820,7 +870,9 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     if extend is not None:
         settings["extend"] = extend
     if adjacency_only:
-        settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}")
+        settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}") + (" (--prefilter: behind the af bound)" if prefilter else "")
+    if pairs is not None:
+        settings["pairs"] = f"only, the pairs listed in {pairs}"
     if no_matrix:
         settings["matrix"] = "none (--no-matrix: components and groups fills)"
     if components_only:
@@ -859,8 +911,15 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         if run.world > 1:
             log.error("--adjacency-only is a one-GPU call: run it in one process, not under a launcher")
             sys.exit(1)
-        run.adjacency(edge_thresh)
+        run.adjacency(edge_thresh, prefilter=prefilter)
         run.banner(3, "done (--adjacency-only: no clustering)")
+        return
+    if pairs is not None:
+        if run.world > 1:
+            log.error("--pairs is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        run.pairs(pairs)
+        run.banner(3, "done (--pairs: no clustering)")
         return
     if components_only:
         if run.world > 1:
@@ -1078,7 +1137,7 @@ def _run(args, argv):
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
                   cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min,
-                  distribution_only=args.distribution_only, distribution=args.distribution)
+                  distribution_only=args.distribution_only, distribution=args.distribution, pairs=args.pairs, prefilter=args.prefilter)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
