@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 171   /* 0.5.20: pc_fill_pairs / pc_fill_pairs_dev (the values of any listed pairs, oriented as written) */
+#define PC_VERSION 172   /* 0.5.21: pc_fill_edges_bars (an edge list under a bar per genome), pc_nearest_of_pairs (k-nearest lists of a pair list) */
 
 typedef enum {
     PC_OK = 0,
@@ -307,6 +307,19 @@ int pc_fill_edges(pc_ctx* ctx, int metric, int as_distance, double threshold, in
 /* Test / tuning hook: HIP-event milliseconds of the last pc_fill_edges call that was given stats, summed over its slabs:
  * *ms_compact count + scan + emit, *ms_d2h the copy of the edges to the host; either pointer may be NULL. */
 int pc_last_edge_times(const pc_ctx* ctx, float* ms_compact, float* ms_d2h);
+/*
+ * The edge-list fill under a bar per genome (PC_VERSION 172): pc_fill_edges with the predicate pass(v, bar[s]) || pass(v, bar[t]) in
+ * place of pass(v, threshold) -- pass is pc_fill_edges' plain f64 compare, v <= bar on a distance fill, v >= bar on a similarity fill,
+ * on the delivered, already round(x, 6) value of the pair (s, t), s < t.  bar: f64[N] in host memory, read during the call only.  It is
+ * the candidate pass of a k-nearest search (bar[g] = the worst value genome g still takes): a pair is delivered when either end takes
+ * it.  An infinite bar is legal and admits every pair of its genome or none of them on its own account.  With every bar equal to thr
+ * the result is pc_fill_edges(thr)'s, element for element.  The walk, the slab cut, the order (t, then s), the loan rule, the values,
+ * stats, *n_slabs and pc_last_edge_times are pc_fill_edges'; so are its refusals, with "a NaN bar, naming the genome" and "bar is NULL"
+ * (both PC_ERR_ARG, checked where pc_fill_edges checks its threshold) in the NaN threshold's place.  One context; there is no
+ * pc_multi_ form and no rows form.
+ */
+int pc_fill_edges_bars(pc_ctx* ctx, int metric, int as_distance, const double* bar /* f64[N], host */, int64_t slab_bytes,
+                       const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats);
 
 /*
  * Components fill: the single-linkage clusters at a threshold, without the dense matrix and without an edge list.  labels[g] is
@@ -363,6 +376,27 @@ int pc_fill_nearest(pc_ctx* ctx, int metric, int as_distance, int k, int64_t sla
 /* Test / tuning hook: HIP-event milliseconds of the last pc_fill_nearest call that was given stats: *ms_select the row and column
  * passes summed over its slabs, *ms_finish the finishing pass; either pointer may be NULL. */
 int pc_last_nearest_times(const pc_ctx* ctx, float* ms_select, float* ms_finish);
+/*
+ * K-nearest lists of a pair list (PC_VERSION 172): what pc_fill_nearest delivers of the whole triangle, of the pairs the caller lists.
+ * src / tgt / val: n_pairs entries in host memory, entry e the pair {src[e], tgt[e]} with the value val[e]; in any order and either
+ * orientation; the diagonal (src[e] == tgt[e]) is refused, and the caller promises that no pair is listed twice (in either
+ * orientation: it would be two candidates).  Every pair is a candidate of BOTH its ends.  Let kk = min(k, N - 1).  count[g] is the
+ * number of listed pairs that touch genome g; row g of nbr[N][kk] / val_out[N][kk] (row-major) lists the best min(kk, count[g]) of them
+ * -- the other end and the value, bit for bit as given -- in pc_fill_nearest's total order: the better value first (the smaller with
+ * as_distance != 0, else the larger; a plain f64 compare), among equal values the smaller genome index.  Slots beyond count[g] hold
+ * nbr = -1 and val = NaN.  A list that holds the whole triangle gives pc_fill_nearest's result.
+ * *nbr, *val_out and *count point into page-locked memory the context owns (pc_fill_nearest's loan: valid until the next fill, upload
+ * or call of this kind on the context, or its destruction); *k_out = kk.  The context supplies N and the work buffers only: neither the
+ * sets nor the residues are read, and the shard in force does not matter.  On the device: the 2 n_pairs directed entries (owner << 32 |
+ * other, position) are sorted, and one wave per genome selects from its run; no atomics, the result is canonical.
+ * PC_OK also for n_pairs == 0 (every count 0, every slot padded) and N <= 1 (*k_out = 0).  In this order -- PC_ERR_STATE: before
+ * upload.  PC_ERR_ARG: k < 1.  PC_ERR_LIMIT: k > PC_NEAREST_MAX_K.  PC_ERR_ARG: a NULL out pointer, n_pairs < 0.  PC_ERR_LIMIT:
+ * n_pairs > 2^30 (the directed entries number 2 n_pairs and their sort value has 32 bits).  PC_ERR_ARG: src, tgt or val NULL with
+ * n_pairs > 0; an entry with an index outside [0, N) or on the diagonal, naming it.  On a refusal *nbr, *val_out and *count are NULL and
+ * *k_out is 0; the inputs are never written.  Runs on the context's own stream and returns with everything finished.
+ */
+int pc_nearest_of_pairs(pc_ctx* ctx, const int32_t* src, const int32_t* tgt, const double* val, int64_t n_pairs, int as_distance, int k,
+                        const int32_t** nbr, const double** val_out, const int32_t** count /* i32[N] */, int32_t* k_out);
 
 /*
  * Tree fill: the single-linkage dendrogram, without the dense matrix and without a threshold -- the one delivery form that answers

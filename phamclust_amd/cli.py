@@ -124,6 +124,11 @@ _OPTIONS = (
                                                                       "from one pair-list fill on one GPU; nothing else is computed")),
     (None, "-f", "--prefilter", dict(action="store_true", help="with --adjacency-only -m peq --edge-thresh SIM: fill the af edge list at SIM first (peq "
                                                                "never exceeds af) and align only its pairs; the same file byte for byte, on one GPU")),
+    (None, "-a", "--af-bound", dict(action="store_true", help="with --nearest K -m peq: seed every genome's list from its K nearest by af, then align "
+                                                              "only the pairs whose af similarity can still reach the K-th value of either "
+                                                              "genome (peq never exceeds af); the same file byte for byte, on one GPU; falls "
+                                                              "back to the plain fill when more than half the pairs remain candidates; it "
+                                                              "pays for small K and loses where K reaches the size of the clusters (README)")),
     (None, "-t", "--threads", dict(type=int, default=CPUS, help="accepted for compatibility; the six metrics run on the GPU (see --gpus)")),
     (None, "-D", "--device", dict(type=int, default=None, help="HIP device ordinal of a single-GPU run (default: PHAMCLUST_DEVICE, else 0); "
                                                                "with --gpus N the ranks take devices 0..N-1")),
@@ -254,4 +259,13 @@ def parse_args(argv=None):
             parser.error("--prefilter needs --edge-thresh SIM: without a threshold every pair that shares a pham is a candidate")
         if args.gpus > 1:
             parser.error("--prefilter: the pair-list fill is a one-GPU call; it cannot be combined with --gpus N")
+    if args.af_bound:
+        if args.nearest is None:
+            parser.error("--af-bound bounds the alignments of --nearest K; give --nearest K -m peq")
+        if args.metric != "peq":
+            parser.error(f"--af-bound is the af bound of peq; it serves no other metric (-m {args.metric})")
+        if args.grow_nearest is not None:
+            parser.error("--af-bound fills the lists from scratch; it cannot be combined with --grow-nearest")
+        if args.gpus > 1:
+            parser.error("--af-bound: the pair-list fill is a one-GPU call; it cannot be combined with --gpus N")
     return args

@@ -211,6 +211,10 @@ int64_t pc_edge_chunks(int64_t Lp);
 int pc_launch_edge_count(const double* vals, int64_t Lp, int as_distance, double thr, PcSlabDomain dom, uint32_t* counts, hipStream_t st);
 int pc_launch_edge_emit(const double* vals, int64_t Lp, int as_distance, double thr, PcSlabDomain dom, const uint32_t* offs,
                         int32_t* src, int32_t* tgt, double* val, hipStream_t st);
+// pc_fill_edges_bars: the predicate is pass(v, bar[s]) || pass(v, bar[t]); bar f64[N] on the device; a triangular slab (its shard) only
+int pc_launch_edge_count_bars(const double* vals, int64_t Lp, int as_distance, const double* bar, const PcShard& sh, uint32_t* counts, hipStream_t st);
+int pc_launch_edge_emit_bars(const double* vals, int64_t Lp, int as_distance, const double* bar, const PcShard& sh, const uint32_t* offs,
+                             int32_t* src, int32_t* tgt, double* val, hipStream_t st);
 int pc_rows_slab_span(int pass);                   // elements one workgroup of a slab pass covers (0: edges, 1: union, 2: tree scan; else 0)
 // connected components of a filled slab's passing pairs (pc_components.hip): parent[g] = g and the pair counter zeroed; one slab's
 // passing pairs hooked into parent[] (strict: < / > instead of <= / >=) and counted into *n_pass; labels[g] = root of g
@@ -230,6 +234,13 @@ int pc_nn_seed_pack(const int32_t* seed_nbr, const double* seed_val, int k_seed,
                     unsigned long long* key, int32_t* idx, int* bad_g, int* bad_j);
 int pc_nn_rows_tile(void);
 int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, int as_distance, hipStream_t st);
+// k-nearest lists of a pair list (pc_nearest_of_pairs): src / tgt / val [L] on the device, L <= 2^30.  dkey / dpos [2 L]: every pair
+// from both ends, key = owner << 32 | other, the pair's position behind it; after the caller's sort (skey / spos) start[N + 1] takes where
+// each owner's run begins, and one wave per owner selects: key / nbr [N][K] best first, slots beyond count[g] = the run's length padded
+// (nbr -1, the key of a quiet NaN: k_nn_finish then delivers NaN)
+int pc_launch_nn_pair_entries(const int32_t* src, const int32_t* tgt, unsigned long long* dkey, uint32_t* dpos, int64_t L, hipStream_t st);
+int pc_launch_nn_of_pairs(const unsigned long long* skey, const uint32_t* spos, const double* val, int64_t L, int N, int as_distance, int K,
+                          uint32_t* start, unsigned long long* key, int32_t* nbr, int32_t* count, hipStream_t st);
 // the lists of other devices merged into key / nbr [N][K] (pc_multi_fill_nearest): fkey / fnbr [n_foreign][N][K], in key space
 int pc_launch_nn_merge(unsigned long long* key, int32_t* nbr, const unsigned long long* fkey, const int32_t* fnbr, int n_foreign, int N, int K, hipStream_t st);
 // single-linkage tree of a filled slab (pc_tree.hip).  A pair's place in the total order is one word (the C-ABI header states it):

@@ -1,7 +1,7 @@
 // pc_fill_slabs.hip -- the fills of libphamclust_hip.so that walk the matrix slab by slab and deliver what a threshold leaves of it:
-// pc_fill_edges (the passing pairs as an edge list) and pc_fill_components (their connected components), with pc_last_edge_times and
+// pc_fill_edges (the passing pairs as an edge list; pc_fill_edges_bars: under a bar per genome) and pc_fill_components (their connected components), with pc_last_edge_times and
 // pc_last_component_times -- and, on the same walk without a threshold, pc_fill_nearest (every genome's k best neighbours) with
-// pc_last_nearest_times, pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds, and
+// pc_last_nearest_times (beside it pc_nearest_of_pairs, the same lists from a caller's pair list: no walk), pc_fill_tree (the single-linkage dendrogram as N - 1 edges) with pc_last_tree_times / pc_last_tree_rounds, and
 // pc_fill_between (the count, sum, minimum and maximum of the pair values between every two groups of a partition) with pc_last_between_times,
 // pc_fill_affinity (the sum, minimum and maximum of every genome's pair values to every group) with pc_last_affinity_times,
 // pc_fill_hist (the exact histogram of all pair values, split by a partition into within and between) with pc_last_hist_times.
@@ -74,6 +74,11 @@ int pc_slab_check(const pc_ctx* c, PcSlabRun& run, const char* what) {
     }
     if (!run.outputs) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
     if (run.threshold != run.threshold) { pc_set_error("%s: the threshold is NaN", who); return PC_ERR_ARG; }
+    if (run.by_bars) {
+        if (!run.bars) { pc_set_error("%s: bar is NULL", who); return PC_ERR_ARG; }
+        for (int g = 0; g < c->dev.N; ++g)
+            if (run.bars[g] != run.bars[g]) { pc_set_error("%s: the bar of genome %d is NaN", who, g); return PC_ERR_ARG; }
+    }
     if (run.slab_bytes < 0) { pc_set_error("%s: slab_bytes %lld", who, (long long)run.slab_bytes); return PC_ERR_ARG; }
     if ((rc = fill_check_residues(c, who, run.metric))) return rc;
     run.as_distance = run.as_distance ? 1 : 0; run.strict = run.strict ? 1 : 0;
@@ -258,7 +263,9 @@ static int last_times(const pc_ctx* c, const char* who, const float* last_ms, fl
 int PcEdgesFill::begin(pc_ctx* c, PcSlabRun& run) {
     int rc = PC_OK;
     if ((rc = slab_begin(c, run, c->last_edge_ms)) || (rc = c->h_edge_src.ensure(16)) || (rc = c->h_edge_tgt.ensure(16)) || (rc = c->h_edge_val.ensure(16))) return rc;
-    return c->dev.N <= 1 ? (int)PC_OK : slab_size(c, run);
+    if (c->dev.N <= 1) return PC_OK;
+    if ((rc = slab_size(c, run))) return rc;
+    return run.by_bars ? upload_raw(c->b_edge_bars, run.bars, (size_t)c->dev.N * 8) : (int)PC_OK;     // (resident for the call)
 }
 // compact: count -> scan (n + 1 elements: the total falls out) -> read the total back -> emit; count(cnt, st) and emit(off, st) launch
 // the two passes
@@ -307,6 +314,16 @@ template <class Count, class Emit> static int edges_slab(pc_ctx* c, PcSlabRun& r
     return PC_OK;
 }
 int PcEdgesFill::slab(pc_ctx* c, PcSlabRun& run, const double* slab, int64_t Lp, const PcSlabDomain& dom) {
+    if (run.by_bars) {                                                      // (the triangular walk alone: no rows form takes bars)
+        if (dom.is_rows) { pc_set_error("%s: a bar per genome over a rows slab", run.who); return PC_ERR_ARG; }
+        const double* const bar = c->b_edge_bars.as<double>();
+        return edges_slab(c, run, Lp,
+            [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count_bars(slab, Lp, run.as_distance, bar, dom.shard, cnt, st); },
+            [&](const uint32_t* off, hipStream_t st) {
+                return pc_launch_edge_emit_bars(slab, Lp, run.as_distance, bar, dom.shard, off, c->b_edge_src.as<int32_t>(), c->b_edge_tgt.as<int32_t>(),
+                                                c->b_edge_val.as<double>(), st);
+            });
+    }
     return edges_slab(c, run, Lp,
         [&](uint32_t* cnt, hipStream_t st) { return pc_launch_edge_count(slab, Lp, run.as_distance, run.threshold, dom, cnt, st); },
         [&](const uint32_t* off, hipStream_t st) {
@@ -365,6 +382,14 @@ int PcEdgesFill::merge(const std::vector<pc_ctx*>& ctx, std::vector<PcSlabRun>& 
 extern "C" int pc_fill_edges(pc_ctx* c, int metric, int as_distance, double threshold, int64_t slab_bytes,
                              const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
     PcSlabRun run; run.who = "pc_fill_edges"; run.metric = metric; run.as_distance = as_distance; run.threshold = threshold; run.slab_bytes = slab_bytes;
+    return pc_slab_call<PcEdgesFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return pc_slab_fill<PcEdgesFill>(c, run); });
+}
+
+// the same fill with a bar per genome (host memory, f64[N]) in the threshold's place
+extern "C" int pc_fill_edges_bars(pc_ctx* c, int metric, int as_distance, const double* bar, int64_t slab_bytes,
+                                  const int32_t** src, const int32_t** tgt, const double** val, int64_t* n_edges, int32_t* n_slabs, pc_stats* stats) {
+    PcSlabRun run; run.who = "pc_fill_edges_bars"; run.metric = metric; run.as_distance = as_distance; run.by_bars = true; run.bars = bar;
+    run.slab_bytes = slab_bytes;
     return pc_slab_call<PcEdgesFill>(run, {src, tgt, val, n_edges, n_slabs}, stats, [&] { return pc_slab_fill<PcEdgesFill>(c, run); });
 }
 
@@ -519,6 +544,76 @@ extern "C" int pc_fill_nearest(pc_ctx* c, int metric, int as_distance, int k, in
 
 extern "C" int pc_last_nearest_times(const pc_ctx* c, float* ms_select, float* ms_finish) {
     return last_times(c, "pc_last_nearest_times", c ? c->last_nn_ms : nullptr, ms_select, ms_finish);
+}
+
+// ---- k-nearest lists of a pair list: no fill and no walk -- the caller's (src, tgt, val)[L] go up once, every pair becomes two directed
+// entries (owner << 32 | other, position), one sort makes an owner's entries a run, and one wave per owner selects (pc_nearest.hip:
+// k_nn_pair_entries, k_nn_run_starts, k_nn_pairs), then k_nn_finish and ONE D2H of val[N][kk] | nbr[N][kk] | count[N] into h_nn.  The
+// context gives N and the buffers; neither the sets nor the residues are read.
+#define PC_NEAREST_PAIRS_MAX ((int64_t)1 << 30)
+
+extern "C" int pc_nearest_of_pairs(pc_ctx* c, const int32_t* src, const int32_t* tgt, const double* val, int64_t n_pairs, int as_distance, int k,
+                                   const int32_t** nbr, const double** val_out, const int32_t** count, int32_t* k_out) {
+    const char* const who = "pc_nearest_of_pairs";
+    if (nbr) *nbr = nullptr; if (val_out) *val_out = nullptr; if (count) *count = nullptr; if (k_out) *k_out = 0;
+    if (!c || !c->uploaded) { pc_set_error("%s: upload first", who); return PC_ERR_STATE; }
+    if (k < 1) { pc_set_error("%s: k %d", who, k); return PC_ERR_ARG; }
+    if (k > PC_NEAREST_MAX_K) { pc_set_error("%s: k %d is above PC_NEAREST_MAX_K = %d", who, k, PC_NEAREST_MAX_K); return PC_ERR_LIMIT; }
+    if (!nbr || !val_out || !count || !k_out) { pc_set_error("%s: an output pointer is NULL", who); return PC_ERR_ARG; }
+    if (n_pairs < 0) { pc_set_error("%s: n_pairs %lld", who, (long long)n_pairs); return PC_ERR_ARG; }
+    if (n_pairs > PC_NEAREST_PAIRS_MAX) {
+        pc_set_error("%s: %lld pairs exceed the 2^30 one call takes (its 2 n_pairs directed entries are sorted with 32-bit values)", who, (long long)n_pairs);
+        return PC_ERR_LIMIT;
+    }
+    if (n_pairs > 0 && (!src || !tgt || !val)) { pc_set_error("%s: %s is NULL", who, !src ? "src" : !tgt ? "tgt" : "val"); return PC_ERR_ARG; }
+    const int N = c->dev.N;
+    const int64_t L = n_pairs;
+    for (int64_t e = 0; e < L; ++e) {
+        if (src[e] < 0 || src[e] >= N || tgt[e] < 0 || tgt[e] >= N) {
+            pc_set_error("%s: entry %lld is (%d, %d); genome indices lie in [0, %d)", who, (long long)e, src[e], tgt[e], N); return PC_ERR_ARG;
+        }
+        if (src[e] == tgt[e]) { pc_set_error("%s: entry %lld is the diagonal (%d, %d): a genome is no neighbour of itself", who, (long long)e, src[e], tgt[e]); return PC_ERR_ARG; }
+    }
+    int rc = PC_OK;
+    PC_ON_DEVICE(c);
+    PcRange range("pc:nearest_of_pairs");
+    hipStream_t st = c->stream;
+    const int kk = std::max(std::min(k, N - 1), 0);
+    const size_t n_ent = (size_t)std::max(N, 0) * kk, val_bytes = n_ent * 8, out_bytes = val_bytes + n_ent * 4 + (size_t)std::max(N, 0) * 4;
+    if ((rc = wait_last_work(c, st, false)) || (rc = c->h_nn.ensure(std::max<size_t>(out_bytes, 16)))) return rc;
+    *val_out = c->h_nn.as<double>(); *nbr = (const int32_t*)((const char*)c->h_nn.p + val_bytes); *count = *nbr + n_ent; *k_out = kk;
+    if (N < 1) return PC_OK;
+    int32_t* const h_count = (int32_t*)((char*)c->h_nn.p + val_bytes + n_ent * 4);
+    if (kk == 0) { h_count[0] = 0; return PC_OK; }                         // (N == 1: no pair can be listed)
+    int key_bits = 33;
+    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < N) ++key_bits;
+    rc = [&]() -> int {
+        int rc = PC_OK;
+        if ((rc = c->b_nn_key.ensure(n_ent * 8)) || (rc = c->b_nn_out.ensure(out_bytes)) || (rc = c->b_np_start.ensure((size_t)(N + 1) * 4)) ||
+            (rc = c->b_key0.ensure(std::max<size_t>((size_t)L * 16, 16))) || (rc = c->b_key1.ensure(std::max<size_t>((size_t)L * 16, 16))) ||
+            (rc = c->b_val0.ensure(std::max<size_t>((size_t)L * 8, 16))) || (rc = c->b_val1.ensure(std::max<size_t>((size_t)L * 8, 16))) ||
+            (rc = c->b_sort_tmp.ensure(std::max<size_t>(pc_sort_temp_bytes(2 * L, key_bits), 16)))) return abi_rc(rc);
+        if ((rc = upload_raw(c->b_pr_src, src, (size_t)L * 4)) || (rc = upload_raw(c->b_pr_tgt, tgt, (size_t)L * 4)) ||
+            (rc = upload_raw(c->b_np_val, val, (size_t)L * 8))) return rc;
+        unsigned long long* const key = c->b_nn_key.as<unsigned long long>();
+        double* const d_val = c->b_nn_out.as<double>();
+        int32_t* const d_nbr = (int32_t*)((char*)c->b_nn_out.p + val_bytes); int32_t* const d_count = d_nbr + n_ent;
+        if ((rc = pc_launch_nn_pair_entries(c->b_pr_src.as<int32_t>(), c->b_pr_tgt.as<int32_t>(), c->b_key0.as<unsigned long long>(), c->b_val0.as<uint32_t>(), L, st)) ||
+            (rc = pc_sort_pairs(c->b_sort_tmp.p, c->b_sort_tmp.cap, c->b_key0.as<unsigned long long>(), c->b_key1.as<unsigned long long>(),
+                                c->b_val0.as<uint32_t>(), c->b_val1.as<uint32_t>(), 2 * L, key_bits, st)) ||
+            (rc = pc_launch_nn_of_pairs(c->b_key1.as<unsigned long long>(), c->b_val1.as<uint32_t>(), c->b_np_val.as<double>(), L, N, as_distance ? 1 : 0, kk,
+                                        c->b_np_start.as<uint32_t>(), key, d_nbr, d_count, st)) ||
+            (rc = pc_launch_nn_finish(key, d_val, (int64_t)n_ent, as_distance ? 1 : 0, st))) return rc;
+        PC_HIP(hipMemcpyAsync(c->h_nn.p, c->b_nn_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        PC_HIP(hipStreamSynchronize(st));
+        c->busy = false;
+        return PC_OK;
+    }();
+    if (rc != PC_OK) {
+        (void)hipStreamSynchronize(st);                                     // (nothing of a refused call stays in flight over the buffers)
+        *nbr = nullptr; *val_out = nullptr; *count = nullptr; *k_out = 0;
+    }
+    return rc;
 }
 
 // ---- tree fill: the single-linkage dendrogram as the N - 1 edges of the minimum spanning tree under the one total order (value, better

@@ -124,6 +124,7 @@ struct pc_ctx {
     DevBuf b_pr_src, b_pr_tgt, b_pr_at;     // the domain of the last pair-list fill (PcPairs): the caller's list as uploaded, then sorted
     // pc_fill_edges: the resident slab (shard layout) and its shard tables, chunk counts / offsets, one slab's edges
     DevBuf b_edge_slab, b_edge_owned, b_edge_lbase, b_edge_cnt, b_edge_off, b_edge_src, b_edge_tgt, b_edge_val;
+    DevBuf b_edge_bars;                     // pc_fill_edges_bars: bar[N], resident for the call
     DevBuf b_rq_rows, b_rq_query;           // a rows slab fill: every query row of the call, ascending, and is_query[N] (PcRowsSlab)
     PinnedBuf h_edge_src, h_edge_tgt, h_edge_val;   // the edge list lent out by pc_fill_edges (grown by copying: pinned_grow_keep)
     hipEvent_t ev_slab[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the passes over a slab, of whichever of the three fills runs: created by the first one that is asked for stats
@@ -134,6 +135,7 @@ struct pc_ctx {
     float last_cc_ms[2] = {0.f, 0.f};       // union passes, labels pass of the last pc_fill_components with stats (pc_last_component_times)
     // pc_fill_nearest: key[N][K] (order-preserving u64 of the value), then val[N][K] | nbr[N][K] (one D2H), and their pinned host image
     DevBuf b_nn_key, b_nn_out;
+    DevBuf b_np_val, b_np_start;            // pc_nearest_of_pairs: the caller's val[L]; start[N + 1] of the owners' runs (its result: val[N][kk] | nbr[N][kk] | count[N] in b_nn_out / h_nn)
     PinnedBuf h_nn;                         // the neighbours and values lent out by pc_fill_nearest
     float last_nn_ms[2] = {0.f, 0.f};       // row + column passes, finishing pass of the last pc_fill_nearest / pc_fill_rows_nearest with stats (pc_last_nearest_times)
     // pc_fill_tree: comp[N] | next[N], best[N], two lists of N + PC_TREE_TAIL keys (the resident forest and the one a pass writes), the
@@ -320,6 +322,8 @@ struct PcSlabRun {
     bool outputs = false;                   // every output pointer was there
     int metric = 0, as_distance = 0, strict = 0, k = 0;
     double threshold = 0.0;                 // (nearest: none, stays 0)
+    bool by_bars = false;                   // edges: pc_fill_edges_bars -- the predicate is pass(v, bars[s]) || pass(v, bars[t]), the threshold is not read
+    const double* bars = nullptr;           // ... the caller's bar[N], host memory
     const int32_t* group = nullptr;         // between, affinity: the caller's labels, host memory, [N]; hist: the same, or NULL (no partition)
     int n_groups = 0;                       // ... and their range
     bool bt_invert = false;                 // ... a similarity table was asked for: the slabs are filled as distances, the fold / finish inverts

@@ -31,6 +31,8 @@
 //                and reads a column of the tile lanes across rows, exactly as k_nn_cols; the candidate's index is rows[row].  A
 //                column that is itself a query genome is skipped whole (its list is k_nn_qrows'); rows >= m and columns >= n stage
 //                the worst sentinel and are no candidates.  Nothing is read beyond m * n values.
+//   k_nn_pair_entries / k_nn_run_starts / k_nn_pairs   pc_nearest_of_pairs: the same lists from a PAIR LIST instead of a slab (their section
+//                below): a wave per genome over the sorted run of its pairs, through the same wave step.
 // A genome's list lives one entry per lane of a wave (why K <= 64).  The K-th entry is "the bar": a ballot of `candidate beats the
 // bar` finds the few candidates that matter (after the warm-up about K ln(n / K) per genome); each of them is inserted at the
 // position popcount(ballot(entry comes before the candidate)), the lanes behind it taking their lower neighbour's entry.
@@ -254,6 +256,64 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_merge(nn_key* __restrict__ ke
     if (lane < K) { key[at] = ek; nbr[at] = ei; }
 }
 
+// ---- pc_nearest_of_pairs: the lists of a PAIR LIST (src / tgt / val [L], any order, no pair twice, no diagonal), every pair a
+// candidate of both its ends.
+//   k_nn_pair_entries  the 2 L directed entries: entry d < L is pair d seen from its source (owner src[d], other tgt[d]), entry L + d
+//                      the same pair from its target; key = owner << 32 | other, value = the pair's position d
+//   (pc_sort_pairs by the key: an owner's entries become one run)
+//   k_nn_run_starts    start[g], g = 0 .. N: the first sorted entry whose owner is >= g, by binary search (start[N] = 2 L); owners
+//                      without a pair get an empty run
+//   k_nn_pairs         one wave per owner walks its run 64 entries a step through nn_take -- the candidate is (key of val[position],
+//                      other) -- and writes the list, count[g] = the run's length, and the padding behind it
+// The run is in index order within equal values already; nn_take compares (key, index) all the same.  The list of g is written by the
+// wave of g alone; nothing is read beyond 2 L entries or beyond val[L].
+#define NN_PAD_IDX (-1)
+#define NN_QUIET_NAN 0x7ff8000000000000ll
+
+__global__ __launch_bounds__(256) void k_nn_pair_entries(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt, nn_key* __restrict__ dkey,
+                                                         uint32_t* __restrict__ dpos, int64_t L) {
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d >= 2 * L) return;
+    const int64_t p = d < L ? d : d - L;
+    const uint32_t s = (uint32_t)src[p], t = (uint32_t)tgt[p];
+    dkey[d] = d < L ? ((nn_key)s << 32) | t : ((nn_key)t << 32) | s;
+    dpos[d] = (uint32_t)p;
+}
+
+__global__ __launch_bounds__(256) void k_nn_run_starts(const nn_key* __restrict__ skey, int64_t n, int N, uint32_t* __restrict__ start) {
+    const int g = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (g > N) return;
+    const nn_key bound = (nn_key)(uint32_t)g << 32;
+    int64_t lo = 0, hi = n;                            // the first entry with skey >= bound lies in [lo, hi]
+    while (lo < hi) { const int64_t mid = lo + (hi - lo) / 2; if (skey[mid] < bound) lo = mid + 1; else hi = mid; }
+    start[g] = (uint32_t)lo;
+}
+
+// wave w of workgroup b takes owner b * NN_WAVES + w
+__global__ __launch_bounds__(NN_THREADS) void k_nn_pairs(const nn_key* __restrict__ skey, const uint32_t* __restrict__ spos, const double* __restrict__ val,
+                                                         const uint32_t* __restrict__ start, int N, nn_key flip, int K, nn_key* __restrict__ key,
+                                                         int32_t* __restrict__ nbr, int32_t* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int g = (int)blockIdx.x * NN_WAVES + (int)(threadIdx.x >> 6);
+    if (g >= N) return;                                // (the whole wave)
+    const uint32_t d0 = start[g], d1 = start[g + 1];
+    nn_key ek = NN_WORST_KEY; int ei = NN_WORST_IDX;
+    for (uint32_t base = d0; base < d1; base += 64) {  // (2 L <= 2^31: base + 64 does not wrap)
+        const uint32_t d = base + (uint32_t)lane;
+        const bool have = d < d1;
+        nn_key ck = NN_WORST_KEY; int ci = NN_WORST_IDX;
+        if (have) { ci = (int)(uint32_t)skey[d]; ck = nn_key_of(val[spos[d]], flip); }
+        nn_take(ek, ei, ck, ci, have, K, lane);
+    }
+    const uint32_t n = d1 - d0;
+    if (lane == 0) count[g] = (int32_t)n;
+    if (lane < K) {
+        const bool pad = (uint32_t)lane >= n;
+        key[(size_t)g * K + lane] = pad ? nn_key_of(__longlong_as_double(NN_QUIET_NAN), flip) : ek;
+        nbr[(size_t)g * K + lane] = pad ? NN_PAD_IDX : ei;
+    }
+}
+
 static int nn_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("%s launch: %s", what, hipGetErrorString(e)); return PC_ERR_HIP; }
@@ -327,6 +387,27 @@ int pc_launch_nn_finish(const unsigned long long* key, double* val, int64_t n, i
     if (n <= 0) return PC_OK;
     hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key, val, n, as_distance ? 0ull : ~0ull);
     return nn_check("k_nn_finish");
+}
+
+// dkey / dpos: [2 L]
+int pc_launch_nn_pair_entries(const int32_t* src, const int32_t* tgt, unsigned long long* dkey, uint32_t* dpos, int64_t L, hipStream_t st) {
+    if (L <= 0) return PC_OK;
+    hipLaunchKernelGGL(k_nn_pair_entries, dim3((unsigned)((2 * L + 255) / 256)), dim3(256), 0, st, src, tgt, dkey, dpos, L);
+    return nn_check("k_nn_pair_entries");
+}
+// skey / spos: the 2 L sorted entries; val: [L]; start: [N + 1]; key / nbr: [N][K], count: [N], 1 <= K <= 64, N >= 1
+int pc_launch_nn_of_pairs(const unsigned long long* skey, const uint32_t* spos, const double* val, int64_t L, int N, int as_distance, int K,
+                          uint32_t* start, unsigned long long* key, int32_t* nbr, int32_t* count, hipStream_t st) {
+    if (K < 1 || K > 64 || N < 1 || L < 0 || L > ((int64_t)1 << 30)) {
+        pc_set_error("pc_launch_nn_of_pairs: %lld pairs of %d genomes, K = %d", (long long)L, N, K);
+        return PC_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_nn_run_starts, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, st, skey, 2 * L, N, start);
+    int rc = nn_check("k_nn_run_starts");
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(k_nn_pairs, dim3((unsigned)((N + NN_WAVES - 1) / NN_WAVES)), dim3(NN_THREADS), 0, st, skey, spos, val, start, N,
+                       as_distance ? 0ull : ~0ull, K, key, nbr, count);
+    return nn_check("k_nn_pairs");
 }
 
 // key / nbr: [N][K]; fkey / fnbr: [n_foreign][N][K], 1 <= K <= 64

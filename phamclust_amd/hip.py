@@ -81,7 +81,8 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_between_max_groups", "pc_between_segment", "pc_fill_affinity", "pc_multi_fill_affinity", "pc_last_affinity_times",
            "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity",
            "pc_fill_rows_between", "pc_fill_hist", "pc_multi_fill_hist", "pc_fill_rows_hist", "pc_last_hist_times", "pc_hist_bins",
-           "pc_hist_table_slots", "pc_hist_probes", "pc_fill_pairs", "pc_fill_pairs_dev", "pc_pair_block"]
+           "pc_hist_table_slots", "pc_hist_probes", "pc_fill_pairs", "pc_fill_pairs_dev", "pc_pair_block",
+           "pc_fill_edges_bars", "pc_nearest_of_pairs"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
 HIST_BINS = 1000001                     # pc_hist_bins(): the millionths in [0, 1]
 
@@ -152,6 +153,10 @@ def load():
     L.pc_pair_block.restype = ctypes.c_int
     L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                 ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_fill_edges_bars.argtypes = [vp, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
+                                     ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
+    L.pc_nearest_of_pairs.argtypes = [vp, _i32p, _i32p, _f64p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_i32p), ctypes.POINTER(_f64p),
+                                      ctypes.POINTER(_i32p), ctypes.POINTER(ctypes.c_int32)]
     L.pc_last_edge_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pc_fill_components.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_i32p),
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
@@ -422,11 +427,12 @@ class _SlabFills:
 
     # One decoder per result shape, for the whole form and the rows form alike: the call ``prefix + kind`` with ``args`` (what the call
     # takes between the metric and its output cells), the output cells as arrays or loans, and with ``want_stats`` the stats dict.
-    def _fill_edge_arrays(self, kind, prefix, metric, args, want_stats, borrow):
-        """``(src, tgt, val)`` of an edge list (``"edges"``: a 64-bit count; ``"tree"``: a 32-bit one, and the round counts)."""
+    def _fill_edge_arrays(self, kind, prefix, metric, args, want_stats, borrow, symbol=None):
+        """``(src, tgt, val)`` of an edge list (``"edges"``: a 64-bit count; ``"tree"``: a 32-bit one, and the round counts);
+        ``symbol``: the call, where it is not ``prefix + kind``."""
         ps, pt, pv = _i32p(), _i32p(), _f64p()
         n, nsl = (ctypes.c_int32 if kind == "tree" else ctypes.c_int64)(0), ctypes.c_int32(0)
-        stats = self._slab_call(prefix + kind, metric, *args, ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
+        stats = self._slab_call(symbol or prefix + kind, metric, *args, ctypes.byref(ps), ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n), ctypes.byref(nsl))
         out = [self._lend(ptr, (n.value,), borrow) if n.value and ptr else np.empty(0, dtype=dtype)
                for ptr, dtype in ((ps, np.int32), (pt, np.int32), (pv, np.float64))]
         if not want_stats:
@@ -928,6 +934,43 @@ class Context(_SlabFills):
                                                 _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), ctypes.c_void_p(out_ptr),
                                                 ctypes.c_void_p(stream or 0), ctypes.byref(stats) if want_stats else None))
         return stats.as_dict() if want_stats else None
+
+    def fill_edges_bars(self, metric, bars, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):
+        """:meth:`fill_edges` with a bar per genome in the threshold's place: the pairs (s, t), s < t, whose value passes ``bars[s]``
+        OR ``bars[t]`` -- ``d <= bar`` for a distance fill, ``sim >= bar`` for a similarity fill -- as ``(src, tgt, val)`` in
+        :meth:`fill_edges`' order, with its values, loan rule and stats.  ``bars``: N floats; ``+-inf`` is legal, NaN is refused by the
+        library, naming the genome.  With all bars equal it is ``fill_edges`` at that threshold, element for element.  One GPU."""
+        bars = np.ascontiguousarray(np.asarray(bars, dtype=np.float64).reshape(-1))
+        if bars.shape[0] != self.n_genomes:
+            raise ValueError(f"fill_edges_bars: {bars.shape[0]} bars for {self.n_genomes} genomes")
+        return self._fill_edge_arrays("edges", "pc_fill_", metric, (int(bool(as_distance)), _ptr(bars if bars.size else np.zeros(1), _f64p), int(slab_bytes)),
+                                      want_stats, borrow, symbol="pc_fill_edges_bars")
+
+    NEAREST_PAIRS_MAX = 2 ** 30           # pairs one nearest_of_pairs call takes (2 entries each, sorted with 32-bit values)
+
+    def nearest_of_pairs(self, src, tgt, val, k, as_distance=True, borrow=False):
+        """K-nearest lists of a pair list: ``(nbr, val, count)`` -- int32[N, kk], float64[N, kk], int32[N], ``kk = min(k, N - 1)``.
+        Every listed pair ``{src[e], tgt[e]}`` with value ``val[e]`` is a candidate of both its ends; ``count[g]`` is how many touch
+        genome g, and row g lists the best ``min(kk, count[g])`` of them in :meth:`fill_nearest`'s total order (better value first,
+        then the smaller index), the slots behind them ``-1`` / NaN.  The list may come in any order; a diagonal entry is refused,
+        and the caller promises that no pair is listed twice.  ``SparseEdges.nearest`` states the same on the host.  The context
+        gives N only; nothing is filled.  The arrays are copies; ``borrow=True`` lends the context's page-locked memory."""
+        src, tgt = self._pair_arrays(src, tgt)
+        val = np.ascontiguousarray(np.asarray(val, dtype=np.float64).reshape(-1))
+        if val.shape[0] != src.shape[0]:
+            raise ValueError(f"nearest_of_pairs: {src.shape[0]} pairs and {val.shape[0]} values")
+        self._invalidate_loans()
+        pn, pv, pc = _i32p(), _f64p(), _i32p()
+        kk = ctypes.c_int32(0)
+        one = np.zeros(1, np.int32)
+        self._check(self._lib.pc_nearest_of_pairs(self._h, _ptr(src if src.size else one, _i32p), _ptr(tgt if tgt.size else one, _i32p),
+                                                  _ptr(val if val.size else np.zeros(1), _f64p), int(src.shape[0]), int(bool(as_distance)), int(k),
+                                                  ctypes.byref(pn), ctypes.byref(pv), ctypes.byref(pc), ctypes.byref(kk)))
+        n = self.n_genomes
+        count = self._lend(pc, (n,), borrow) if n and pc else np.zeros(n, dtype=np.int32)
+        if n and kk.value and pn and pv:
+            return self._lend(pn, (n, kk.value), borrow), self._lend(pv, (n, kk.value), borrow), count
+        return np.empty((n, 0), dtype=np.int32), np.empty((n, 0), dtype=np.float64), count
 
     EDGE_MAX_PAIRS = 2 ** 31 - 1          # pairs one slab of an edge-list fill may hold (u32 counts and offsets on the device)
 

@@ -78,6 +78,31 @@ class SparseEdges:
         ranked = other[np.argsort(w if self.is_distance else -w, kind="stable")]
         return [self.nodes[j] for j in ranked]
 
+    def nearest(self, k):
+        """K-nearest lists of this edge list, every edge a candidate of both its ends: ``(indices, weights, count)`` -- int32[N, kk],
+        float64[N, kk], int32[N], ``kk = min(k, N - 1)``.  ``count[g]`` is the number of edges that touch node g; row g lists the
+        best ``min(kk, count[g])`` of them in the total order of ``NearestNeighbors`` (the better weight first, equal weights in node
+        order), and the slots behind them hold ``-1`` and NaN.  A list that holds every pair gives ``NearestNeighbors.from_dense``.
+        Host arithmetic (one ``np.lexsort`` over the 2 E directed edges): the statement ``Context.nearest_of_pairs`` is held to, and
+        the CPU route of a held list."""
+        if isinstance(k, bool) or int(k) < 1:
+            raise ValueError("k must be at least 1")
+        n, e = len(self.nodes), len(self)
+        kk = max(min(int(k), n - 1), 0)
+        owner = np.concatenate([self.source, self.target]).astype(np.int64)
+        other = np.concatenate([self.target, self.source]).astype(np.int64)
+        w = np.concatenate([self.weight, self.weight])
+        order = np.lexsort((other, w if self.is_distance else -w, owner))
+        owner, other, w = owner[order], other[order], w[order]
+        count = np.bincount(owner, minlength=n).astype(np.int32) if n else np.zeros(0, dtype=np.int32)
+        place = np.arange(2 * e, dtype=np.int64) - np.searchsorted(owner, owner)     # an entry's place in its owner's run
+        keep = place < kk
+        indices = np.full((n, kk), -1, dtype=np.int32)
+        weights = np.full((n, kk), np.nan, dtype=np.float64)
+        indices[owner[keep], place[keep]] = other[keep]
+        weights[owner[keep], place[keep]] = w[keep]
+        return indices, weights, count
+
     def components(self, threshold=None, strict=True):
         """Connected components of the graph over ``nodes`` whose edges are this list's pairs within ``threshold`` -- ``weight <
         threshold`` on distances, ``> threshold`` on similarities; ``<=`` / ``>=`` with ``strict=False``; ``None``: every pair

@@ -7,7 +7,7 @@ import numpy as np
 
 from phamclust_amd.routes import _de_novo_route, _extend_fill, _extend_plan
 from phamclust_amd.results._common import _grown_positions, _similarity_lines, _similarity_lines_to_file
-from phamclust_amd.results.edges import SparseEdges
+from phamclust_amd.results.edges import PREFILTER_SLACK, SparseEdges
 
 NEAREST_MAX_K = 64     # PC_NEAREST_MAX_K of the C-ABI: the k a nearest-neighbours fill takes at most
 
@@ -133,15 +133,112 @@ class NearestNeighbors:
                          "removing genomes needs a fill of the remaining ones (neighbors_de_novo)")
 
 
-def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0):
+NEAREST_PAIRS_MAX = 2 ** 30     # pairs one Context.nearest_of_pairs call takes
+
+
+def _bounded_peq_nearest(ctx, k, as_distance, slab_bytes):
+    """The peq k-nearest lists behind their af bound, on an uploaded context: ``(nbr, val, stats)``, the lists of
+    ``ctx.fill_nearest("peq", k)`` element for element.  ``kk = min(k, N - 1)``; "better" and the total order are the fill's.
+
+    peq = round(round(af, 6) * round(aai, 6), 6) (metrics.py:247-253) and round(aai, 6) <= 1.0, so a pair's delivered peq similarity
+    never exceeds its delivered af similarity ``a``, and its delivered peq distance is never below round(1 - a, 6)
+    (``_prefiltered_peq_edges``).  The nearest fill has no threshold to hold that against; it has one per genome:
+
+    1. Seed.  ``fill_nearest("af", kk)`` as similarities; the seed pairs are every {g, h} with h in g's af list, oriented
+       source < target, each once: at most N kk pairs.
+    2. Bars.  The peq values of the seed pairs (one pair-list fill) become k-nearest lists (``nearest_of_pairs``: a pair is a
+       candidate of both its ends).  Every genome has at least kk entries -- its own af list holds kk pairs that contain it -- and
+       ``bar[g]`` is the kk-th value of g's list.  The list is made of true pairs of g, so g's true kk-th best is as good or better.
+    3. Candidates.  Any h in g's true top kk has a delivered peq value at least as good as ``bar[g]``.  On similarities
+       peq <= a, so ``a >= bar[g]``; on distances d_peq >= round(1 - a, 6), so round(1 - a, 6) <= bar[g] and
+       ``a >= (1 - bar[g]) - PREFILTER_SLACK`` (the slack covers the half-millionth of the rounding and the subtraction's error, as
+       for the edge list; the delivered af DISTANCE is no bound, it can lie a millionth above round(1 - a, 6)).  The candidates are
+       the pairs (s < t) whose af similarity reaches ``simbar[s]`` or ``simbar[t]`` -- non-strictly, since equal values order by
+       index -- which is ``fill_edges_bars("af", simbar)``: they contain every true top-kk pair of every genome.
+    4. Result.  The peq values of the candidates (one pair-list fill), then ``nearest_of_pairs`` over that list ALONE: each genome's
+       true top kk are all in it and everything else in it is a true pair that ranks behind them, so the best kk of the list are the
+       best kk of all, in the same total order.  The seed pairs are not merged in (most are candidates again; one list holds no pair
+       twice).
+    5. Fallback.  More candidates than half the triangle (or than one ``nearest_of_pairs`` call takes): they are dropped and the plain
+       ``fill_nearest("peq", k)`` runs -- the same result by definition.
+
+    ``stats``: the last peq call's, with ``k``, ``n_slabs`` (the candidate pass's, or the plain fill's), ``n_seed_pairs``,
+    ``n_candidates``, ``n_alignments`` (every peq call of the route), ``fallback``, ``af_ms_total`` (both af fills), ``af_ms_d2h`` (the candidates' copy to the host), ``ms_total`` (every
+    fill of the route), ``n_list_bytes`` (what the pair lists moved over PCIe: 16 bytes per edge down, 8 up and 8 down per pair value, 16 up per listed pair) and ``step_s`` (host seconds of the seed af
+    fill, the seed peq values, the seed lists, the candidate pass, the final peq values, the final lists or the fallback)."""
+    import time
+    n = ctx.n_genomes
+    total = n * (n - 1) // 2
+    kk = max(min(int(k), n - 1), 0)
+    route = dict(n_seed_pairs=0, n_candidates=0, fallback=0, af_ms_total=0.0, af_ms_d2h=0.0, n_list_bytes=0)
+    if kk == 0:                                                         # (N == 1: nothing to bound)
+        nbr, val, stats = ctx.fill_nearest("peq", int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+        return nbr, val, dict(stats, **route, step_s=[0.0] * 6)
+    clock = [time.perf_counter()]
+    a_nbr, _, af_stats = ctx.fill_nearest("af", kk, as_distance=False, slab_bytes=slab_bytes, want_stats=True)
+    g, h = np.repeat(np.arange(n, dtype=np.int64), kk), np.asarray(a_nbr, dtype=np.int64).reshape(-1)
+    pair = np.unique(np.maximum(g, h) * n + np.minimum(g, h))
+    s_src, s_tgt = (pair % n).astype(np.int32), (pair // n).astype(np.int32)
+    clock.append(time.perf_counter())
+    s_val, seed_stats = ctx.fill_pairs("peq", s_src, s_tgt, as_distance=as_distance, want_stats=True)
+    clock.append(time.perf_counter())
+    _, l_val, l_count = ctx.nearest_of_pairs(s_src, s_tgt, s_val, kk, as_distance=as_distance)
+    if int(l_count.min()) < kk:
+        raise RuntimeError(f"bounded nearest fill: a genome has {int(l_count.min())} seed pairs, below k = {kk}: the af lists are not what fill_nearest delivers")
+    bar = np.ascontiguousarray(l_val[:, kk - 1])
+    simbar = ((1.0 - bar) - PREFILTER_SLACK) if as_distance else bar
+    clock.append(time.perf_counter())
+    c_src, c_tgt, _, cand_stats = ctx.fill_edges_bars("af", simbar, as_distance=False, slab_bytes=slab_bytes, want_stats=True)
+    clock.append(time.perf_counter())
+    n_cand = int(c_src.shape[0])
+    route.update(n_seed_pairs=int(pair.shape[0]), n_candidates=n_cand, af_ms_total=float(af_stats["ms_total"]) + float(cand_stats["ms_total"]),
+                 af_ms_d2h=float(cand_stats.get("ms_d2h", 0.0)), n_list_bytes=int(pair.shape[0]) * 32 + n_cand * 16)
+    if 2 * n_cand > total or n_cand > NEAREST_PAIRS_MAX:
+        nbr, val, stats = ctx.fill_nearest("peq", int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True)
+        clock += [clock[-1], time.perf_counter()]
+        route.update(fallback=1)
+    else:
+        c_val, stats = ctx.fill_pairs("peq", c_src, c_tgt, as_distance=as_distance, want_stats=True)
+        clock.append(time.perf_counter())
+        nbr, val, count = ctx.nearest_of_pairs(c_src, c_tgt, c_val, kk, as_distance=as_distance)
+        clock.append(time.perf_counter())
+        if int(count.min()) < kk:
+            raise RuntimeError(f"bounded nearest fill: a genome has {int(count.min())} candidates, below k = {kk}: the af bound does not hold on this collection")
+        route.update(n_list_bytes=route["n_list_bytes"] + n_cand * 32)
+        stats = dict(stats, k=kk, n_slabs=int(cand_stats["n_slabs"]))
+    stats = dict(stats, **route, n_alignments=int(stats["n_alignments"]) + int(seed_stats["n_alignments"]),
+                 ms_total=float(stats["ms_total"]) + float(seed_stats["ms_total"]) + route["af_ms_total"],
+                 step_s=[b - a for a, b in zip(clock, clock[1:])])
+    return nbr, val, stats
+
+
+def neighbors_de_novo(genomes, func, k, as_distance=True, slab_bytes=0, bound=False):
     """Each genome's ``k`` nearest neighbours in ``matrix_de_novo(genomes, func, cpus, as_distance)`` as a
     :class:`NearestNeighbors`, filled on the GPU by ``Context.fill_nearest``: the dense matrix is never delivered, and beyond
     ``slab_bytes`` of HBM (0: automatic) never held; N * k entries cross PCIe.  ``func`` must be one of the six ``METRICS``
     callables (no CPU route: ``NearestNeighbors.from_dense(matrix_de_novo(...), k)`` serves another callable).  Several devices as
     ``edges_de_novo`` (``MultiContext.fill_nearest``: the same lists); under a launcher (``WORLD_SIZE`` > 1) it raises.  Every
-    refusal comes before the first GPU call."""
+    refusal comes before the first GPU call.
+
+    ``bound=True`` (peq only; any other metric raises ``ValueError`` before any GPU call): the same lists, element for element, on one
+    GPU behind the af bound of peq -- each genome's own k-th best value so far is its bar, and only pairs whose af similarity can
+    reach the bar of either end are aligned (``_bounded_peq_nearest`` has the rule and its proof).  What it saves depends on the
+    collection and on k; when more than half the pairs stay candidates it falls back to the plain fill."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NEAREST_MAX_K:
         raise ValueError(f"neighbors_de_novo: k must be an integer in 1..{NEAREST_MAX_K}, not {k!r}")
+    if bound:
+        from phamclust_amd.routes import _metric_name
+        if _metric_name(func) != "peq":
+            raise ValueError("neighbors_de_novo: bound=True is the af bound of peq and serves no other metric "
+                             f"(func is {_metric_name(func) or 'no METRICS callable'})")
+        names, (nbr, val) = _de_novo_route(genomes, func, "neighbors_de_novo",
+            lambda ctx, metric: _bounded_peq_nearest(ctx, int(k), as_distance, slab_bytes),
+            lambda stats, record, fill_s: (
+                f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {stats['n_candidates']} af candidates of {record['genome_pairs']} "
+                f"pairs on one device ({stats['n_seed_pairs']} seed pairs{', fell back to the plain fill' if stats['fallback'] else ''}): "
+                f"af fills + peq pairs + select + D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms, {stats['n_alignments']} alignments)"),
+            several=False)
+        return NearestNeighbors(names, nbr, val, is_distance=as_distance)
     names, (nbr, val) = _de_novo_route(genomes, func, "neighbors_de_novo",
         lambda ctx, metric: ctx.fill_nearest(metric, int(k), as_distance=as_distance, slab_bytes=slab_bytes, want_stats=True),
         lambda stats, record, fill_s: f"{len(genomes)} genomes -> {stats['k']} nearest neighbours each from {record['genome_pairs']} pairs in "

@@ -314,10 +314,11 @@ class _Run:
         return found
 
     # 2, --nearest
-    def nearest(self, k):
+    def nearest(self, k, bound=False):
         """Stage 2 as a nearest-neighbours fill: each genome's ``k`` closest genomes, and only ``nearest_<metric>.tsv`` is written:
         ``source<TAB>target<TAB>similarity``, sources in genome order, targets nearest first (equally near ones in genome order).
-        Distances are filled and inverted, as for the adjacency file.  No matrix, no threshold, nothing cached or clustered."""
+        Distances are filled and inverted, as for the adjacency file.  No matrix, no threshold, nothing cached or clustered.
+        ``bound`` (peq): the same lists behind the af bound (``neighbors_de_novo(..., bound=True)``)."""
         self.banner(2, f"{self.metric} nearest neighbours (nearest-neighbours fill)")
         t0 = time.perf_counter()
         if self.grow_nearest is not None:
@@ -325,8 +326,13 @@ class _Run:
             found = self.grown(lambda: nearest_from_file(self.grow_nearest, names),
                                lambda old: neighbors_extend(old, self.genomes, METRICS[self.metric], k=k), t0, flag="--grow-nearest", path=self.grow_nearest)
         else:
-            found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True)
+            found = neighbors_de_novo(self.genomes, METRICS[self.metric], k, as_distance=True, bound=bound)
         st = _matrix.LAST_FILL
+        if bound:
+            pairs = st.get("genome_pairs", 0)
+            log.info(f"--af-bound: {st.get('n_candidates', 0):,} of {pairs:,} pairs are af candidates ({st.get('n_seed_pairs', 0):,} seed pairs)"
+                     f"{'; more than half: fell back to the plain fill' if st.get('fallback') else ''}; {st.get('n_alignments', 0):,} alignments against "
+                     f"{pairs:,} pairs x the mean a plain fill aligns")
         log.info(f"{st.get('genome_pairs', 0):,} pairs -> the {found.k} nearest of each of {len(found):,} genomes from {st.get('n_slabs', 1)} slab(s) "
                  f"on {_gpus_text(st)} in {time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, "
                  f"fill+select+D2H {st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms, selection "
@@ -791,7 +797,7 @@ class _Run:
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
               components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_table=None, join_min=None,
-              distribution_only=False, distribution=False, pairs=None, prefilter=False, grow_nearest=None, nearest=None):
+              distribution_only=False, distribution=False, pairs=None, prefilter=False, nearest_bound=False, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -814,13 +820,16 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     summary); ``distribution``: after the clustering, the same two files split by the final clusters (``--distribution``; with the whole
     pipeline only, on either route); ``pairs``: stop after a pair-list fill of the pairs that file names and write only
     ``pairwise_<metric>_pairs.tsv`` (``--pairs``); ``prefilter``: with ``adjacency_only``, peq and an ``edge_thresh``, the same adjacency
-    file from the af edge list's pairs alone (``--prefilter``)."""
+    file from the af edge list's pairs alone (``--prefilter``); ``nearest_bound``: with ``nearest`` and peq, the same lists from the
+    pairs the af bound leaves open (``--af-bound``)."""
     if pairs is not None and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
                               place is not None or cluster_table or cluster_fit or distribution or distribution_only or prefilter):
         raise ValueError("pairs cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, cluster_table, "
                          "cluster_fit, distribution, distribution_only or prefilter")
     if prefilter and not (adjacency_only and metric == "peq" and edge_thresh is not None):
         raise ValueError("prefilter goes with adjacency_only, the peq metric and an edge_thresh")
+    if nearest_bound and not (nearest is not None and metric == "peq" and grow_nearest is None):
+        raise ValueError("nearest_bound goes with nearest and the peq metric, and not with grow_nearest")
     if distribution_only and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
                               place is not None or cluster_table or cluster_fit or distribution):
         raise ValueError("distribution_only cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, "
@@ -878,7 +887,7 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     if components_only:
         settings["components"] = f"only, joined at similarity > {0.0 if edge_thresh is None else edge_thresh}"
     if nearest is not None:
-        settings["nearest"] = f"only, {nearest} neighbours per genome"
+        settings["nearest"] = f"only, {nearest} neighbours per genome" + (" (--af-bound: behind the af bound)" if nearest_bound else "")
     if tree:
         settings["tree"] = "only (single-linkage dendrogram)"
     if distribution_only:
@@ -932,7 +941,7 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         if run.world > 1:
             log.error("--nearest is a one-GPU call: run it in one process, not under a launcher")
             sys.exit(1)
-        run.nearest(nearest)
+        run.nearest(nearest, bound=nearest_bound)
         run.banner(3, "done (--nearest: no clustering)")
         return
     if place is not None:
@@ -1137,7 +1146,7 @@ def _run(args, argv):
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
                   cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min,
-                  distribution_only=args.distribution_only, distribution=args.distribution, pairs=args.pairs, prefilter=args.prefilter)
+                  distribution_only=args.distribution_only, distribution=args.distribution, pairs=args.pairs, prefilter=args.prefilter, nearest_bound=args.af_bound)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
