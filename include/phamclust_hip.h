@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PC_VERSION 172   /* 0.5.21: pc_fill_edges_bars (an edge list under a bar per genome), pc_nearest_of_pairs (k-nearest lists of a pair list) */
+#define PC_VERSION 173   /* 0.5.22: pc_fill_joint, pc_fill_joint_dev, pc_fill_pairs_joint, pc_fill_pairs_joint_dev (all six metrics of a pair from one alignment pass) */
 
 typedef enum {
     PC_OK = 0,
@@ -277,6 +277,37 @@ int pc_fill_pairs(pc_ctx* ctx, int metric, int as_distance, const int32_t* src, 
 int pc_fill_pairs_dev(pc_ctx* ctx, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
                       void* out_dev, void* stream, pc_stats* stats);
 int pc_pair_block(void);     /* slots per block of a pair-list fill (256): host arithmetic, for tests */
+
+/*
+ * Joint fill (PC_VERSION 173): up to six metrics of every pair from ONE plan and ONE alignment pass.  peq is
+ * round(round(af, 6) * round(aai, 6), 6) (metrics.py:247-253): a peq fill computes af and aai of every pair on its way, and its walk
+ * visits every shared pham, which is all that gcs, jc and pocp read.  A caller who wants several metrics of a collection -- why are
+ * two genomes far apart under peq: few shared genes (af) or diverged ones (aai)? -- ran the fills one after another, and the aai fill
+ * ran the peq fill's alignments again, bit for bit.  Here the reduce walk of the peq fill (k_walk / k_walk_pairs in their joint mode)
+ * stores every metric asked for, each finished by the single-metric fill's own expression: every value equals pc_fill's / pc_fill_pairs'
+ * of that metric bit for bit, for both as_distance values.
+ * metrics: bit m set = metric m of the enum pc_metric is wanted: PC_GCS ... PC_PEQ, bits 0-5.  out[m] must be non-NULL for every set bit; for a
+ * clear bit out[m] is not read and nothing behind it is touched.  pc_fill_joint / pc_fill_joint_dev: the whole triangle, every array
+ * the condensed f64[N (N - 1) / 2] of pc_fill (host) / pc_fill_dev (HBM; stream as there).  pc_fill_pairs_joint / _dev: the listed
+ * pairs under pc_fill_pairs' contract -- oriented, in the caller's order, repeats allowed, src[k] == tgt[k] the diagonal 1.0 -
+ * as_distance in every array -- every array f64[n_pairs].  The host forms stage through the context's output buffer, sized for the
+ * arrays asked for.
+ * The plan is cut into chunks by pc_set_plan_budget's rule exactly as the peq fill's (same chunks; each chunk's walk writes all the
+ * arrays for its targets / blocks).  stats are the peq fill's: n_alignments, n_distinct_alignments, n_cells, n_tasks, n_align_launches
+ * and n_chunks equal those of pc_fill(PC_PEQ) / pc_fill_pairs(PC_PEQ) on the same context, budget and list; ms_reduce is the joint
+ * walk; pc_last_plan_tasks covers these calls too.
+ * Refused before anything is launched, the context staying usable -- PC_ERR_STATE: before upload; on a sharded context (world != 1).
+ * PC_ERR_ARG: an empty set; a bit above 5 (PC_AAI_PPOS is another alignment pass and no part of this); a set with neither PC_AAI nor
+ * PC_PEQ (gcs / jc / pocp / af alone share no alignment pass: four millisecond fills, pc_fill); out NULL, or out[m] NULL for a set
+ * bit.  Then the list's checks as pc_fill_pairs makes them (the pair-list forms); PC_ERR_STATE before pc_upload_residues; PC_ERR_DATA:
+ * an empty translation, as a peq fill.  No rows, groups, slab, borrow or multi-GPU form.
+ */
+int pc_fill_joint(pc_ctx* ctx, uint32_t metrics, int as_distance, double* const out_condensed[6], pc_stats* stats);
+int pc_fill_joint_dev(pc_ctx* ctx, uint32_t metrics, int as_distance, void* const out_dev[6], void* stream, pc_stats* stats);
+int pc_fill_pairs_joint(pc_ctx* ctx, uint32_t metrics, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                        double* const out[6], pc_stats* stats);
+int pc_fill_pairs_joint_dev(pc_ctx* ctx, uint32_t metrics, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                            void* const out_dev[6], void* stream, pc_stats* stats);
 
 /*
  * Edge-list fill: the pairs within a threshold, without the dense matrix.  The reference knows this form of its result twice --

@@ -2,6 +2,7 @@
 (cli.py:10-117), declared here as a table so that the defaults are inspectable (``DEFAULTS``)."""
 
 import argparse
+import os
 import pathlib
 from multiprocessing import cpu_count
 
@@ -122,6 +123,11 @@ _OPTIONS = (
                                                                       "so an adjacency file of any metric is valid input); the file written holds "
                                                                       "source<TAB>target<TAB>similarity in FILE's order, each pair oriented as written, "
                                                                       "from one pair-list fill on one GPU; nothing else is computed")),
+    (None, "-O", "--also", dict(type=str, default=None, help="METRIC[,METRIC...]: further metrics beside -m's, off the same alignment pass (one joint "
+                                                             "fill serves aai and peq together, and af / pocp / gcs / jc with them).  On the "
+                                                             "dense route on one GPU: each metric's matrix is cached as -m's is and written as "
+                                                             "pairwise_<metric>_similarities.tsv in the node order of -m's file; the clustering "
+                                                             "runs on -m's matrix alone.  With --pairs FILE: one pairwise_<metric>_pairs.tsv per metric")),
     (None, "-f", "--prefilter", dict(action="store_true", help="with --adjacency-only -m peq --edge-thresh SIM: fill the af edge list at SIM first (peq "
                                                                "never exceeds af) and align only its pairs; the same file byte for byte, on one GPU")),
     (None, "-a", "--af-bound", dict(action="store_true", help="with --nearest K -m peq: seed every genome's list from its K nearest by af, then align "
@@ -259,6 +265,26 @@ def parse_args(argv=None):
             parser.error("--prefilter needs --edge-thresh SIM: without a threshold every pair that shares a pham is a candidate")
         if args.gpus > 1:
             parser.error("--prefilter: the pair-list fill is a one-GPU call; it cannot be combined with --gpus N")
+    if args.also is not None:
+        names = [name.strip() for name in args.also.split(",")]
+        for name in names:
+            if name not in METRICS:
+                parser.error(f"--also names metrics among {', '.join(METRICS)}, separated by commas; '{name}' is none of them")
+            if name == args.metric:
+                parser.error(f"--also names metrics BESIDE -m's; '{name}' is -m's own")
+            if names.count(name) > 1:
+                parser.error(f"--also names every metric once; '{name}' is listed twice")
+        for flag, given in (("--extend", args.extend is not None), ("--no-matrix", args.no_matrix), ("--adjacency-only", args.adjacency_only),
+                            ("--components-only", args.components_only), ("--nearest", args.nearest is not None), ("--tree", args.tree),
+                            ("--distribution-only", args.distribution_only), ("--place", args.place is not None), ("--grow", args.grow is not None),
+                            ("--grow-nearest", args.grow_nearest is not None), ("--prefilter", args.prefilter), ("--af-bound", args.af_bound)):
+            if given:
+                parser.error(f"--also fills further metrics on the dense route or with --pairs; it cannot be combined with {flag}")
+        if args.gpus > 1:
+            parser.error("--also: the joint fill is a one-GPU call; it cannot be combined with --gpus N")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--also: the joint fill is a one-GPU call; it cannot be combined with a launcher job (WORLD_SIZE > 1)")
+        args.also = names
     if args.af_bound:
         if args.nearest is None:
             parser.error("--af-bound bounds the alignments of --nearest K; give --nearest K -m peq")

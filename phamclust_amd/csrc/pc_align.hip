@@ -7,7 +7,7 @@
 //   3 read-back      alignment total + task range per kernel variant (a few words)
 //   4 ENUM walk      (row gene, result slot) scattered into the column gene's bucket
 //   5 K4 launches    one per kernel variant present, wave tasks of <= 64 row sequences
-//   6 REDUCE walk    best match per anchor gene, fp64 weighted mean, af, round -> out
+//   6 REDUCE walk    best match per anchor gene, fp64 weighted mean, af, round -> out (a joint fill: -> one array per metric asked for)
 // Bucketing by column gene is what lets a wave build one substitution profile and stream
 // many row sequences through it; results are written pair-major so step 6 reads them
 // contiguously and in the canonical order (pham id, anchor gene, other gene).
@@ -289,6 +289,16 @@ static int count_per_target(pc_ctx* c, int condensed, hipStream_t st, std::vecto
 // [k1 - k0][N], filled for that range alone), or -- groups != NULL -- the row blocks [k0, k1) of a groups fill (k_walk_groups; slot
 // arrays hold that range's slots, first slot block_slot[k0]), or -- dom.pairs -- the blocks [k0, k1) of a pair-list fill (k_walk_pairs;
 // slot arrays hold that range's slots, first slot k0 * PC_PAIR_BLOCK).
+static PcPairs pairs_from(const PcPairsHost& ph, int k0) {
+    PcPairs sub = ph.dev;
+    sub.slot_base = (int64_t)k0 * PC_PAIR_BLOCK;
+    return sub;
+}
+static PcShard shard_range(const pc_ctx* c, int k0, int k1) {
+    PcShard sub = c->shard;
+    sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
+    return sub;
+}
 static int walk_domain(pc_ctx* c, int mode, const PcUnitDomain& dom, int k0, int k1, const PcWalkArgs& a, hipStream_t st) {
     if (dom.rows) return pc_launch_walk_rows(mode, c->dev, *dom.rows, k0, k1, a, st);
     if (dom.groups) {
@@ -296,14 +306,14 @@ static int walk_domain(pc_ctx* c, int mode, const PcUnitDomain& dom, int k0, int
         sub.slot_base = dom.groups->block_slot[k0];
         return pc_launch_walk_groups(mode, c->dev, sub, dom.groups->block_tile[k0], dom.groups->block_tile[k1], a, st);
     }
-    if (dom.pairs) {
-        PcPairs sub = dom.pairs->dev;
-        sub.slot_base = (int64_t)k0 * PC_PAIR_BLOCK;
-        return pc_launch_walk_pairs(mode, c->dev, sub, k0, k1, a, st);
-    }
-    PcShard sub = c->shard;
-    sub.nown = k1 - k0; sub.owned = c->shard.owned + k0; sub.lbase = c->shard.lbase + k0; sub.ident = c->shard.ident && k0 == 0;
-    return pc_launch_walk(mode, c->dev, sub, a, st);
+    if (dom.pairs) return pc_launch_walk_pairs(mode, c->dev, pairs_from(*dom.pairs, k0), k0, k1, a, st);
+    return pc_launch_walk(mode, c->dev, shard_range(c, k0, k1), a, st);
+}
+// ... and the JOINT walk, which exists over the shard's targets and over the blocks of a pair list
+static int walk_domain_joint(pc_ctx* c, const PcUnitDomain& dom, int k0, int k1, const PcJointArgs& a, hipStream_t st) {
+    if (dom.rows || dom.groups) { pc_set_error("reduce: no joint walk over a rows or groups domain"); return PC_ERR_ARG; }
+    if (dom.pairs) return pc_launch_walk_pairs_joint(c->dev, pairs_from(*dom.pairs, k0), k0, k1, a, st);
+    return pc_launch_walk_joint(c->dev, shard_range(c, k0, k1), a, st);
 }
 
 // PLAN of the owned targets (or the units of dom) [k0, k1) holding A alignments (b_na is filled): scan, ENUM, sort, distinct alignments, tasks
@@ -425,15 +435,19 @@ static int stage_align(pc_ctx* c, int slice_rank, int slice_world, uint2* res, h
     return run_align_classes(c, task_list, tb.data(), c->cls_max_lb.data(), res, st, stats, P.ppos);
 }
 
-// REDUCE: best match per anchor gene through the aliases, fp64 epilogue (metrics.py:204-232, 247-253), over the plan's targets
-static int stage_reduce(pc_ctx* c, int metric, int as_distance, const uint2* res, double* out, hipStream_t st, const PcUnitDomain& dom = PcUnitDomain{}) {
+// REDUCE: best match per anchor gene through the aliases, fp64 epilogue (metrics.py:204-232, 247-253), over the plan's targets: o's one
+// metric into its array, or its joint set, each metric into its own, in one walk
+static int stage_reduce(pc_ctx* c, const PcFillOut& o, int as_distance, const uint2* res, hipStream_t st, const PcUnitDomain& dom = PcUnitDomain{}) {
     PcRange range("pc:reduce");
     pc_ctx::PlanState& P = c->plan;
     if (!P.valid) { pc_set_error("reduce: no plan (pc_plan_dev first)"); return PC_ERR_STATE; }
-    PcWalkArgs a; memset(&a, 0, sizeof(a));
-    a.off = c->b_off.as<uint32_t>(); a.alias = c->b_alias.as<uint32_t>(); a.res = res; a.out = out;
+    PcJointArgs a; memset(&a, 0, sizeof(a));
+    a.off = c->b_off.as<uint32_t>(); a.alias = c->b_alias.as<uint32_t>(); a.res = res; a.out = o.out;
     a.as_distance = as_distance ? 1 : 0; a.condensed = P.condensed;
-    return walk_domain(c, metric == PC_AAI ? PCW_AAI : PCW_PEQ, dom, P.k0, P.k1, a, st);
+    if (!o.mask) return walk_domain(c, o.metric == PC_AAI ? PCW_AAI : PCW_PEQ, dom, P.k0, P.k1, a, st);
+    a.mask = o.mask;
+    for (int m = 0; m < 6; ++m) a.jout[m] = o.joint[m];
+    return walk_domain_joint(c, dom, P.k0, P.k1, a, st);
 }
 
 // a finished chunk: its plan's counts, and its tasks per launch class for pc_last_plan_tasks
@@ -451,11 +465,11 @@ static void set_last_plan_tasks(pc_ctx* c, const std::vector<uint32_t>& per_clas
 // One plan -> align -> reduce over the owned targets (or the units of dom) [k0, k1) holding A alignments, and its counts added
 // to `local`.  events: ev[1] and ev[2] are recorded between the stages (ev[3] after them always); ms != NULL: the step is waited for and its
 // three stage times, the first counted from `from`, are added to ms[0..2].
-static int chunk_step(pc_ctx* c, int metric, int ppos, int as_distance, int condensed, double* out, hipStream_t st, int k0, int k1, uint64_t A,
+static int chunk_step(pc_ctx* c, const PcFillOut& o, int ppos, int as_distance, int condensed, hipStream_t st, int k0, int k1, uint64_t A,
                       const PcUnitDomain& dom, pc_stats& local, bool events, hipEvent_t from, float* ms) {
     int rc = stage_plan(c, ppos, condensed, st, k0, k1, A, dom);
     if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[1], st)); rc = stage_align(c, 0, 1, c->b_res.as<uint2>(), st, &local); }
-    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, metric, as_distance, c->b_res.as<uint2>(), out, st, dom); }
+    if (rc == PC_OK) { if (events) PC_HIP(hipEventRecord(c->ev[2], st)); rc = stage_reduce(c, o, as_distance, c->b_res.as<uint2>(), st, dom); }
     if (rc != PC_OK) return rc;
     PC_HIP(hipEventRecord(c->ev[3], st));
     add_plan_stats(c, local);
@@ -476,10 +490,10 @@ static int release_for_retry(pc_ctx* c, hipStream_t st, bool slots) {
     return PC_OK;
 }
 
-// aai / peq: COUNT once, then plan -> align -> reduce -- in one piece when the plan fits the budget, else chunk by chunk
-int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed) {
+// aai / peq / a joint set: COUNT once, then plan -> align -> reduce -- in one piece when the plan fits the budget, else chunk by chunk
+int fill_aligned(pc_ctx* c, const PcFillOut& o, int ppos, int as_distance, int condensed, hipStream_t st, pc_stats& local, bool timed) {
     int rc = PC_OK;
-    if ((rc = fill_check_residues(c, "fill", metric))) return rc;
+    if ((rc = fill_check_residues(c, "fill", o.metric))) return rc;
     uint64_t tot[3] = {0, 0, 0};
     c->last_plan_tasks_valid = false;
     c->last_plan_tasks.assign(c->nlc, 0);
@@ -494,7 +508,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
     local.n_chunks = 0;
     if (A <= max_aln) {
         // (its stage times are read by fill_impl: ev[0] .. ev[3])
-        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, 0, nown, A, PcUnitDomain{}, local, true, nullptr, nullptr);
+        rc = chunk_step(c, o, ppos, as_distance, condensed, st, 0, nown, A, PcUnitDomain{}, local, true, nullptr, nullptr);
         if (rc == PC_OK) {
             local.n_chunks = 1;
             c->last_plan_tasks_valid = true;
@@ -515,7 +529,7 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
         uint64_t run = per_owned[k]; int k1 = k + 1;
         while (k1 < nown && run + per_owned[k1] <= max_aln) { run += per_owned[k1]; ++k1; }
         if (timed) PC_HIP(hipEventRecord(c->ev[4], st));
-        rc = chunk_step(c, metric, ppos, as_distance, condensed, out, st, k, k1, run, PcUnitDomain{}, local, timed, c->ev[4], timed ? ms : nullptr);
+        rc = chunk_step(c, o, ppos, as_distance, condensed, st, k, k1, run, PcUnitDomain{}, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller chunk, not an error
             if ((rc = release_for_retry(c, st, false))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run) / 2, 1);
@@ -541,13 +555,13 @@ int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, 
 // plan per range merges the duplicate sequence pairs of everything the range touches.  `out` is the whole result; the reduce of a range
 // writes its cells (a rows fill: also the mirror cells of pairs of two queries).  Values do not depend on the cut: every pair's
 // alignments stay in one range.
-static int fill_units_aligned(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out,
+static int fill_units_aligned(pc_ctx* c, const PcUnitDomain& dom, const PcFillOut& o, int ppos, int as_distance,
                               hipStream_t st, pc_stats& local, bool timed) {
     int rc = PC_OK;
     const PcDev& d = c->dev;
     const int U = dom.units();
     auto slots = [&](int k0, int k1) { return dom.slots(k0, k1, d.N); };
-    if ((rc = fill_check_residues(c, "fill", metric))) return rc;
+    if ((rc = fill_check_residues(c, "fill", o.metric))) return rc;
     if (d.G > 0 && c->min_gene_len == 0) {
         pc_set_error("fill: an empty translation cannot be aligned (aai/peq); the reference fails on it too"); return PC_ERR_DATA;
     }
@@ -602,7 +616,7 @@ static int fill_units_aligned(pc_ctx* c, const PcUnitDomain& dom, int metric, in
             a.na = c->b_na.as<uint32_t>(); a.totals = c->b_totals.as<unsigned long long>() + 5;
             rc = walk_domain(c, PCW_COUNT, dom, k, k1, a, st);
         }
-        if (rc == PC_OK) rc = chunk_step(c, metric, ppos, as_distance, 0, out, st, k, k1, run, dom, local, timed, c->ev[4], timed ? ms : nullptr);
+        if (rc == PC_OK) rc = chunk_step(c, o, ppos, as_distance, 0, st, k, k1, run, dom, local, timed, c->ev[4], timed ? ms : nullptr);
         if (rc == PC_ERR_NOMEM_INTERNAL && max_aln > 1 && k1 - k > 1) {                 // a retry with a smaller range, not an error
             if ((rc = release_for_retry(c, st, true))) return rc;
             max_aln = std::max<uint64_t>(std::min(max_aln, run + run_slot_cost) / 2, 1);
@@ -621,10 +635,11 @@ static int fill_units_aligned(pc_ctx* c, const PcUnitDomain& dom, int metric, in
 // a rows fill (the units are the query rows), a groups fill (the row blocks of TS positions) or a pair-list fill (the blocks of
 // PC_PAIR_BLOCK slots), every metric: the set metrics always run on the domain's walker, all units in one launch (no selector:
 // pc_last_set_kernel / pc_last_set_launch keep reporting the last whole fill)
-int fill_units(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed) {
-    if (metric >= PC_AAI) return fill_units_aligned(c, dom, metric, ppos, as_distance, out, st, local, timed);
+int fill_units(pc_ctx* c, const PcUnitDomain& dom, const PcFillOut& o, int ppos, int as_distance, hipStream_t st, pc_stats& local, bool timed) {
+    const int metric = o.metric;
+    if (o.mask || metric >= PC_AAI) return fill_units_aligned(c, dom, o, ppos, as_distance, st, local, timed);
     PcWalkArgs a; memset(&a, 0, sizeof(a));
-    a.out = out; a.as_distance = as_distance;
+    a.out = o.out; a.as_distance = as_distance;
     const int mode = metric == PC_GCS ? PCW_GCS : metric == PC_JC ? PCW_JC : metric == PC_POCP ? PCW_POCP : PCW_AF;
     return walk_domain(c, mode, dom, 0, dom.units(), a, st);
 }
@@ -708,7 +723,7 @@ extern "C" int pc_reduce_dev(pc_ctx* c, int metric, int as_distance, const void*
     PC_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     int rc = wait_last_work(c, st, true); if (rc != PC_OK) return rc;
-    rc = stage_reduce(c, metric, as_distance, (const uint2*)res_dev, (double*)out_condensed_dev, st);
+    rc = stage_reduce(c, PcFillOut(metric, (double*)out_condensed_dev), as_distance, (const uint2*)res_dev, st);
     int rc2 = mark_work(c, st);
     return rc != PC_OK ? abi_rc(rc) : rc2;
 }

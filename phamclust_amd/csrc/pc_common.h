@@ -130,7 +130,8 @@ struct PcTaskPlan {
 
 // walker modes (pc_walk.hip)
 enum { PCW_POCP = 0, PCW_AF = 1, PCW_COUNT = 2, PCW_ENUM = 3, PCW_AAI = 4, PCW_PEQ = 5,
-       PCW_GCS = 6, PCW_JC = 7 };                   // the last two: k_walk_rows / k_walk_groups / k_walk_pairs only (whole fills count gcs / jc on the tile kernels)
+       PCW_GCS = 6, PCW_JC = 7,                     // these two: k_walk_rows / k_walk_groups / k_walk_pairs only (whole fills count gcs / jc on the tile kernels)
+       PCW_JOINT = 8 };                             // k_walk (condensed) / k_walk_pairs only: PEQ's walk, up to six metrics of the pair out of it (PcJointArgs)
 enum { PCW_SPARSE_GCS = 10, PCW_SPARSE_JC = 11 };   // k_sparse_tile64 only: shared-pham counts, one direction
 
 struct PcWalkArgs {
@@ -153,6 +154,14 @@ struct PcWalkArgs {
     double* out;
     int as_distance;
     int condensed;                    // 1: scipy condensed index, 0: shard-local index
+};
+
+// JOINT: the walk arguments of PEQ (out is not read) and, beside them, where each metric of the launch's set goes: metric m of the
+// enum pc_metric (PC_GCS ... PC_PEQ) is written iff bit m of mask is set, to jout[m] -- at the index a.out would be written at.  Only
+// the joint instantiations take this struct: the other kernels' parameters stay PcWalkArgs as it is.
+struct PcJointArgs : PcWalkArgs {
+    double* jout[6];
+    uint32_t mask;
 };
 
 const char* pc_hip_err(hipError_t e);
@@ -191,6 +200,9 @@ int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t 
 // the walker over the blocks [bb, be) of PC_PAIR_BLOCK slots of a pair-list fill; a.out is the whole f64[L] in the caller's order,
 // a.aln_t is per block, a.condensed is not read
 int pc_launch_walk_pairs(int mode, const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcWalkArgs& a, hipStream_t st);
+// the JOINT walks: k_walk over the shard's pairs (condensed output only) and k_walk_pairs over the blocks [bb, be) of a pair list
+int pc_launch_walk_joint(const PcDev& d, const PcShard& sh, const PcJointArgs& a, hipStream_t st);
+int pc_launch_walk_pairs_joint(const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcJointArgs& a, hipStream_t st);
 // a pair list's sort: key[i] = tgt[i] << 32 | src[i], val[i] = i before pc_sort_pairs; src / tgt back out of the sorted keys after it
 int pc_launch_pair_keys(const int32_t* src, const int32_t* tgt, unsigned long long* key, uint32_t* val, int64_t n, hipStream_t st);
 int pc_launch_pair_split(const unsigned long long* key, int32_t* src, int32_t* tgt, int64_t n, hipStream_t st);

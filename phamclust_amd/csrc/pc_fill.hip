@@ -1,6 +1,7 @@
 // pc_fill.hip -- the fill entry points of libphamclust_hip.so over the whole matrix or shard (pc_fill, pc_fill_borrow, pc_fill_dev,
 // pc_fill_shard_dev, pc_assemble_dev) and over the rows, groups and pairs domains (pc_fill_rows, pc_fill_rows_dev, pc_fill_groups,
-// pc_fill_groups_dev, pc_fill_pairs, pc_fill_pairs_dev): the frame they share, and pick_set_kernel, which gathers the selector's inputs from the context (the selector itself:
+// pc_fill_groups_dev, pc_fill_pairs, pc_fill_pairs_dev), and the joint fills (pc_fill_joint, pc_fill_joint_dev, pc_fill_pairs_joint,
+// pc_fill_pairs_joint_dev: several metrics off one alignment pass): the frame they share, and pick_set_kernel, which gathers the selector's inputs from the context (the selector itself:
 // pc_set_shape.hip).  The slab walks pc_fill_edges / pc_fill_components: pc_fill_slabs.hip.
 #include "pc_host.h"
 
@@ -100,7 +101,7 @@ int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed
             a.out = out; a.as_distance = as_distance; a.condensed = condensed;
             rc = pc_launch_walk(mode, d, c->shard, a, st, shp);
         }
-    } else rc = fill_aligned(c, metric, ppos, as_distance, out, condensed, st, local, stats != nullptr);
+    } else rc = fill_aligned(c, PcFillOut(metric, out), ppos, as_distance, condensed, st, local, stats != nullptr);
     return fill_close(c, metric, st, rc, local, stats, true);
 }
 
@@ -171,7 +172,7 @@ static int fill_domain(pc_ctx* c, const char* who, const char* const* range_name
     if ((rc = wait_last_work(c, st, false))) return rc;
     if ((rc = upload_tables())) return rc;
     PC_HIP(hipEventRecord(c->ev[0], st));
-    rc = fill_units(c, dom, metric, ppos, as_distance ? 1 : 0, (double*)out_dev, st, local, stats != nullptr);
+    rc = fill_units(c, dom, PcFillOut(metric, (double*)out_dev), ppos, as_distance ? 1 : 0, st, local, stats != nullptr);
     return fill_close(c, metric, st, rc, local, stats, false);
 }
 
@@ -359,13 +360,14 @@ static int pairs_check(const pc_ctx* c, int* metric, int* ppos, const int32_t* s
     return PC_OK;
 }
 
-// the checked list (L > 0 entries, n_live of them off the diagonal) onto the device, sorted, and filled
-static int fill_pairs_run(pc_ctx* c, int metric, int ppos, int as_distance, const int32_t* src, const int32_t* tgt, int64_t L, int64_t n_live,
-                          void* out_dev, void* stream, pc_stats* stats) {
+// the checked list (L > 0 entries, n_live of them off the diagonal) onto the device, sorted, and filled: o's one metric, or its joint set
+static int fill_pairs_run(pc_ctx* c, const PcFillOut& o, int ppos, int as_distance, const int32_t* src, const int32_t* tgt, int64_t L, int64_t n_live,
+                          void* stream, pc_stats* stats) {
     int rc = PC_OK;
     PC_ON_DEVICE(c);
     static const char* const fill_names[] = {"pc:fill_pairs:gcs", "pc:fill_pairs:jc", "pc:fill_pairs:pocp", "pc:fill_pairs:af", "pc:fill_pairs:aai", "pc:fill_pairs:peq"};
-    PcRange range(fill_names[metric]);
+    const int metric = o.metric;
+    PcRange range(o.mask ? "pc:fill_pairs:joint" : fill_names[metric]);
     hipStream_t st = (hipStream_t)stream;
     pc_stats local; memset(&local, 0, sizeof(local));
     local.n_pairs = n_live;
@@ -390,7 +392,7 @@ static int fill_pairs_run(pc_ctx* c, int metric, int ppos, int as_distance, cons
     ph.dev = PcPairs{L, c->b_pr_src.as<int32_t>(), c->b_pr_tgt.as<int32_t>(), c->b_pr_at.as<uint32_t>(), 0};
     ph.nblocks = (int)((L + PC_PAIR_BLOCK - 1) / PC_PAIR_BLOCK);
     PcUnitDomain dom; dom.pairs = &ph;
-    rc = fill_units(c, dom, metric, ppos, as_distance ? 1 : 0, (double*)out_dev, st, local, stats != nullptr);
+    rc = fill_units(c, dom, o, ppos, as_distance ? 1 : 0, st, local, stats != nullptr);
     if (rc != PC_OK && metric < PC_AAI) (void)mark_work(c, st);            // (the sort is in flight; the aligned routes are marked by the close)
     rc = fill_close(c, metric, st, rc, local, stats, false);
     if (rc == PC_OK && split_times) {                                      // (the close has waited for ev[3])
@@ -406,7 +408,7 @@ extern "C" int pc_fill_pairs_dev(pc_ctx* c, int metric, int as_distance, const i
     int64_t n_live = 0;
     if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out_dev, &n_live))) return rc;
     if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
-    return fill_pairs_run(c, metric, ppos, as_distance, src, tgt, n_pairs, n_live, out_dev, stream, stats);
+    return fill_pairs_run(c, PcFillOut(metric, (double*)out_dev), ppos, as_distance, src, tgt, n_pairs, n_live, stream, stats);
 }
 
 extern "C" int pc_fill_pairs(pc_ctx* c, int metric, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
@@ -416,8 +418,95 @@ extern "C" int pc_fill_pairs(pc_ctx* c, int metric, int as_distance, const int32
     if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out_host, &n_live))) return rc;
     if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
     return fill_to_host(c, n_pairs, out_host, true,
-                        [&](void* out_dev, void* st) { return fill_pairs_run(c, metric, ppos, as_distance, src, tgt, n_pairs, n_live, out_dev, st, stats); });
+                        [&](void* out_dev, void* st) { return fill_pairs_run(c, PcFillOut(metric, (double*)out_dev), ppos, as_distance, src, tgt, n_pairs, n_live, st, stats); });
 }
+
+// ---- joint fills: up to six metrics of every pair off ONE plan and ONE alignment pass.  peq = round(round(af, 6) * round(aai, 6), 6)
+// computes af and aai on its way, and its walk visits every shared pham, which is all gcs, jc and pocp read: the PCW_JOINT walk
+// (pc_walk.hip) is the peq fill's reduce with one store per metric asked for.  COUNT, plan, align, the chunking and the stats are the
+// peq fill's own (fill_aligned / fill_units over a PcFillOut with a mask); every value is the single-metric fill's, bit for bit.
+
+// What both domains check of a joint call before anything of their own: the context as every fill (an unsharded one), then the set
+static int joint_check(const pc_ctx* c, const char* who, uint32_t metrics, void* const out[6]) {
+    int metric = PC_PEQ, rc = PC_OK;
+    if ((rc = fill_check(c, who, "a joint fill", &metric, nullptr))) return rc;
+    if (!metrics) { pc_set_error("%s: the metric set is empty", who); return PC_ERR_ARG; }
+    if (metrics & ~PC_JOINT_ALL) {
+        pc_set_error("%s: metric set 0x%x has a bit above PC_PEQ (aai_ppos is another alignment pass: pc_fill)", who, metrics); return PC_ERR_ARG;
+    }
+    if (!(metrics & (1u << PC_AAI | 1u << PC_PEQ))) {
+        pc_set_error("%s: metric set 0x%x holds neither aai nor peq; gcs / jc / pocp / af alone are four millisecond fills and share no alignment pass (pc_fill)", who, metrics);
+        return PC_ERR_ARG;
+    }
+    if (!out) { pc_set_error("%s: out is NULL", who); return PC_ERR_ARG; }
+    static const char* const names[] = {"gcs", "jc", "pocp", "af", "aai", "peq"};
+    for (int m = 0; m < 6; ++m)
+        if ((metrics >> m & 1u) && !out[m]) { pc_set_error("%s: out[%d] (%s) is NULL", who, m, names[m]); return PC_ERR_ARG; }
+    return PC_OK;
+}
+
+// The host forms: b_out sized for the set's arrays of n doubles each, the device form run into them on the context's stream, each
+// array copied to its caller's, the stream drained.  wait: as fill_to_host.
+template <class Fill> static int joint_to_host(pc_ctx* c, uint32_t metrics, int64_t n, double* const host[6], bool wait, Fill fill_dev) {
+    PC_ON_DEVICE(c);
+    int rc = PC_OK;
+    if (wait && (rc = wait_last_work(c, c->stream, false))) return rc;
+    const int64_t each = std::max<int64_t>(n, 1);
+    if ((rc = c->b_out.ensure((size_t)__builtin_popcount(metrics) * each * 8))) return abi_rc(rc);
+    void* dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int k = 0;
+    for (int m = 0; m < 6; ++m) if (metrics >> m & 1u) dev[m] = c->b_out.as<double>() + each * k++;
+    if ((rc = fill_dev(dev, c->stream))) return rc;
+    for (int m = 0; m < 6 && n > 0; ++m) if (dev[m]) PC_HIP(hipMemcpyAsync(host[m], dev[m], n * 8, hipMemcpyDeviceToHost, c->stream));
+    PC_HIP(hipStreamSynchronize(c->stream));
+    c->busy = false;
+    return PC_OK;
+}
+
+extern "C" int pc_fill_joint_dev(pc_ctx* c, uint32_t metrics, int as_distance, void* const out_dev[6], void* stream, pc_stats* stats) {
+    int rc = PC_OK;
+    if ((rc = joint_check(c, "pc_fill_joint", metrics, out_dev))) return rc;
+    if ((rc = fill_check_residues(c, "pc_fill_joint", PC_PEQ))) return rc;
+    PC_ON_DEVICE(c);
+    PcRange range("pc:fill:joint");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = wait_last_work(c, st, true))) return rc;
+    pc_stats local; memset(&local, 0, sizeof(local));
+    local.n_pairs = c->shard_pairs;
+    PC_HIP(hipEventRecord(c->ev[0], st));
+    rc = fill_aligned(c, PcFillOut(metrics, out_dev), 0, as_distance ? 1 : 0, 1, st, local, stats != nullptr);
+    return fill_close(c, PC_PEQ, st, rc, local, stats, true);
+}
+
+extern "C" int pc_fill_joint(pc_ctx* c, uint32_t metrics, int as_distance, double* const out_condensed[6], pc_stats* stats) {
+    int rc = PC_OK;
+    if ((rc = joint_check(c, "pc_fill_joint", metrics, (void* const*)out_condensed))) return rc;
+    return joint_to_host(c, metrics, (int64_t)c->dev.N * (c->dev.N - 1) / 2, out_condensed, false,
+                         [&](void* const* out_dev, void* st) { return pc_fill_joint_dev(c, metrics, as_distance, out_dev, st, stats); });
+}
+
+extern "C" int pc_fill_pairs_joint_dev(pc_ctx* c, uint32_t metrics, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                                       void* const out_dev[6], void* stream, pc_stats* stats) {
+    int metric = PC_PEQ, ppos = 0, rc = PC_OK;
+    int64_t n_live = 0;
+    if ((rc = joint_check(c, "pc_fill_pairs_joint", metrics, out_dev))) return rc;
+    if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out_dev, &n_live))) return rc;
+    if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
+    return fill_pairs_run(c, PcFillOut(metrics, out_dev), 0, as_distance, src, tgt, n_pairs, n_live, stream, stats);
+}
+
+extern "C" int pc_fill_pairs_joint(pc_ctx* c, uint32_t metrics, int as_distance, const int32_t* src, const int32_t* tgt, int64_t n_pairs,
+                                   double* const out[6], pc_stats* stats) {
+    int metric = PC_PEQ, ppos = 0, rc = PC_OK;
+    int64_t n_live = 0;
+    if ((rc = joint_check(c, "pc_fill_pairs_joint", metrics, (void* const*)out))) return rc;
+    if ((rc = pairs_check(c, &metric, &ppos, src, tgt, n_pairs, out, &n_live))) return rc;
+    if (n_live < 0) { if (stats) memset(stats, 0, sizeof(*stats)); return PC_OK; }
+    return joint_to_host(c, metrics, n_pairs, out, true, [&](void* const* out_dev, void* st) {
+        return fill_pairs_run(c, PcFillOut(metrics, out_dev), 0, as_distance, src, tgt, n_pairs, n_live, st, stats);
+    });
+}
+
 
 extern "C" int pc_assemble_dev(pc_ctx* c, const void* gathered_dev, int world, void* out_condensed_dev, void* stream) {
     if (!c || !c->uploaded) { pc_set_error("pc_assemble_dev: upload first"); return PC_ERR_STATE; }

@@ -491,11 +491,24 @@ static int pc_ship(pc_ctx* c, pc_ctx* root, void* dst, const void* src, size_t b
 // be unsharded (rank 0 of 1 in force) and idle; no deal is installed or left behind.
 int pc_count_target_costs(pc_ctx* c);
 
+// What a fill delivers: one metric into one array, or -- mask != 0, a JOINT fill (pc_fill_joint*, pc_fill_pairs_joint*) -- metric m of
+// every set bit m of mask into joint[m], all off one plan and one alignment pass.  A joint fill plans, aligns and is accounted as the
+// peq fill it walks as, so its `metric` is PC_PEQ wherever a stage asks for one.
+struct PcFillOut {
+    int metric; double* out;
+    uint32_t mask; double* joint[6];
+    PcFillOut(int metric_, double* out_) : metric(metric_), out(out_), mask(0), joint{} {}
+    PcFillOut(uint32_t mask_, void* const joint_[6]) : metric(PC_PEQ), out(nullptr), mask(mask_), joint{} {
+        for (int m = 0; m < 6; ++m) joint[m] = (mask >> m & 1u) ? (double*)joint_[m] : nullptr;
+    }
+};
+#define PC_JOINT_ALL 0x3fu                  // bits PC_GCS ... PC_PEQ
+
 // the whole fill of the shard in force into out (pc_fill.hip): what pc_fill_dev / pc_fill_shard_dev run, and every slab of a slab walk
 int fill_impl(pc_ctx* c, int metric, int as_distance, double* out, int condensed, hipStream_t st, pc_stats* stats);
-// aai / peq: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
-int fill_aligned(pc_ctx* c, int metric, int ppos, int as_distance, double* out, int condensed, hipStream_t st, pc_stats& local, bool timed);
+// aai / peq / a joint set: COUNT, then plan -> align -> reduce, in one piece or in chunks (pc_align.hip)
+int fill_aligned(pc_ctx* c, const PcFillOut& o, int ppos, int as_distance, int condensed, hipStream_t st, pc_stats& local, bool timed);
 // a rows fill (dom.rows; out: f64[rows->nrows][N]), a groups fill (dom.groups; out: f64[L]) or a pair-list fill (dom.pairs; out: f64[L]
 // in the caller's order) once its domain tables are on the device: the set metrics in one launch of the domain's walker, aai / peq
-// chunked over ranges of query rows / of row blocks / of blocks of slots (pc_align.hip)
-int fill_units(pc_ctx* c, const PcUnitDomain& dom, int metric, int ppos, int as_distance, double* out, hipStream_t st, pc_stats& local, bool timed);
+// chunked over ranges of query rows / of row blocks / of blocks of slots (pc_align.hip).  A joint set: a pair-list fill only
+int fill_units(pc_ctx* c, const PcUnitDomain& dom, const PcFillOut& o, int ppos, int as_distance, hipStream_t st, pc_stats& local, bool timed);

@@ -2,7 +2,8 @@
 // the best-match reduce of aai / peq), k_walk_rows (rows fills: the same and gcs / jc), k_walk_groups (groups fills: as the rows
 // walker, over the within-group pairs of a family of groups) and k_walk_pairs (pair-list fills: as the rows walker, over a flat list
 // of oriented pairs).  One core -- the visit of a shared pham, the visits of a bitmap word, the value epilogue, the COUNT totals --
-// serves all four kernels, so each rule of the reference is stated once.
+// serves all four kernels, so each rule of the reference is stated once.  k_walk and k_walk_pairs also run in a JOINT mode: PEQ's walk
+// over the alignment results, with up to six metrics of the pair out of its visits (pc_walk_joint_values: one store per metric asked for).
 //
 // Reference semantics restated here (metrics.py of the reference unless named):
 //   metrics.py:83-115, 118-157   pocp / af: sums over shared phams of gene counts / lengths     (pc_visit, pc_walk_value)
@@ -25,11 +26,26 @@ struct PcPairAcc {
     int any;               // shared set non-empty
     __device__ __forceinline__ void reset() { k = 0; cons = 0; num = 0.0; den = 0; any = 0; }
 };
+// JOINT walks as PEQ does (k the slot cursor, cons the conserved length) and keeps beside it what the other metrics read of the same visits
+struct PcJointAcc : PcPairAcc {
+    uint32_t shared;       // |S n T|: the visits (GCS / JC)
+    int64_t genes;         // conserved gene count (POCP)
+    __device__ __forceinline__ void reset() { PcPairAcc::reset(); shared = 0; genes = 0; }
+};
+// What a mode accumulates in and is launched with: JOINT's own, every other mode's as before.  (Specialisations, not a condition on
+// MODE: a kernel's signature names PcWalkModeTypes<MODE> and nothing else, so its mangled name does not depend on the modes' enum.)
+template <int MODE> struct PcWalkModeTypes { using Acc = PcPairAcc; using Args = PcWalkArgs; };
+template <> struct PcWalkModeTypes<PCW_JOINT> { using Acc = PcJointAcc; using Args = PcJointArgs; };
+template <int MODE> using PcAccOf = typename PcWalkModeTypes<MODE>::Acc;
+template <int MODE> using PcArgsOf = typename PcWalkModeTypes<MODE>::Args;
+// the modes that walk a pair's alignment slots from a.off on
+__host__ __device__ constexpr bool pc_walks_slots(int mode) { return mode == PCW_ENUM || mode == PCW_AAI || mode == PCW_PEQ || mode == PCW_JOINT; }
 
 template <int MODE>
-__device__ __forceinline__ void pc_visit(const PcDev& d, const PcWalkArgs& a, PcPairAcc& p, uint32_t es, uint32_t et,
+__device__ __forceinline__ void pc_visit(const PcDev& d, const PcWalkArgs& a, PcAccOf<MODE>& p, uint32_t es, uint32_t et,
                                          unsigned long long& cells, unsigned long long& rbytes) {
     p.any = 1;
+    if constexpr (MODE == PCW_JOINT) { ++p.shared; p.genes += d.ent_cnt[es] + d.ent_cnt[et]; }   // GCS / JC's count, POCP's sum (metrics.py:102-103)
     if (MODE == PCW_POCP) { p.cons += d.ent_cnt[es] + d.ent_cnt[et]; return; }          // metrics.py:102-103
     if (MODE == PCW_AF) { p.cons += d.ent_len[es] + d.ent_len[et]; return; }            // metrics.py:135-147
     const int cs = d.ent_cnt[es], ct = d.ent_cnt[et];
@@ -53,8 +69,8 @@ __device__ __forceinline__ void pc_visit(const PcDev& d, const PcWalkArgs& a, Pc
                 a.val[k] = k;
             }
         }
-    } else {                                                                              // AAI / PEQ
-        if (MODE == PCW_PEQ) p.cons += d.ent_len[es] + d.ent_len[et];
+    } else {                                                                              // AAI / PEQ / JOINT
+        if (MODE == PCW_PEQ || MODE == PCW_JOINT) p.cons += d.ent_len[es] + d.ent_len[et];
         for (int ia = 0; ia < ca; ++ia) {
             double best = -1.0; uint32_t best_len = 0;
             for (int ib = 0; ib < cb; ++ib) {
@@ -71,7 +87,7 @@ __device__ __forceinline__ void pc_visit(const PcDev& d, const PcWalkArgs& a, Pc
 // The visits of one bitmap word's shared bits, in ascending order.  sw / tw: the source's and the target's word, by value; bs / bt:
 // the entry index of the first set bit of either (rankpre).
 template <int MODE>
-__device__ __forceinline__ void pc_walk_word(const PcDev& d, const PcWalkArgs& a, PcPairAcc& acc, uint64_t sw, uint64_t tw, uint32_t bs, uint32_t bt,
+__device__ __forceinline__ void pc_walk_word(const PcDev& d, const PcWalkArgs& a, PcAccOf<MODE>& acc, uint64_t sw, uint64_t tw, uint32_t bs, uint32_t bt,
                                              unsigned long long& cells, unsigned long long& rbytes) {
     uint64_t x = sw & tw;
     while (x) {
@@ -94,6 +110,26 @@ __device__ __forceinline__ double pc_walk_value(const PcDev& d, const PcPairAcc&
     if (MODE == PCW_AAI) return pc_finish(aai, as_distance);
     if (MODE == PCW_AF) return pc_finish(af, as_distance);
     return pc_finish(pc_round6(af) * pc_round6(aai), as_distance);                                                    // metrics.py:247-253
+}
+
+// JOINT's epilogue: every metric of the launch's set to element `at` of its own array.  Each value is pc_walk_value of that metric's
+// own mode over that mode's view of the sums (k = |S n T| for GCS / JC, cons = the gene count for POCP, PEQ's own for AF / AAI / PEQ):
+// the expressions of the single-metric fills, called, so the values are theirs bit for bit.
+__device__ __forceinline__ void pc_walk_joint_values(const PcDev& d, const PcJointArgs& a, const PcJointAcc& acc, int s, int t, int64_t at) {
+    PcPairAcc v = acc;
+    if (a.mask & (1u << PC_AF)) a.jout[PC_AF][at] = pc_walk_value<PCW_AF>(d, v, s, t, a.as_distance);
+    if (a.mask & (1u << PC_AAI)) a.jout[PC_AAI][at] = pc_walk_value<PCW_AAI>(d, v, s, t, a.as_distance);
+    if (a.mask & (1u << PC_PEQ)) a.jout[PC_PEQ][at] = pc_walk_value<PCW_PEQ>(d, v, s, t, a.as_distance);
+    v.cons = acc.genes;
+    if (a.mask & (1u << PC_POCP)) a.jout[PC_POCP][at] = pc_walk_value<PCW_POCP>(d, v, s, t, a.as_distance);
+    v.k = acc.shared;
+    if (a.mask & (1u << PC_GCS)) a.jout[PC_GCS][at] = pc_walk_value<PCW_GCS>(d, v, s, t, a.as_distance);
+    if (a.mask & (1u << PC_JC)) a.jout[PC_JC][at] = pc_walk_value<PCW_JC>(d, v, s, t, a.as_distance);
+}
+// ... and a pair list's diagonal entry: 1 - as_distance in every array of the set (matrix.py:467-468)
+__device__ __forceinline__ void pc_walk_joint_diagonal(const PcJointArgs& a, int64_t at) {
+#pragma unroll
+    for (int m = 0; m < 6; ++m) if (a.mask & (1u << m)) a.jout[m][at] = a.as_distance ? 0.0 : 1.0;
 }
 
 // COUNT's tail: the workgroup's alignments, DP cells and residue bytes -> totals[0..2] (wave shuffle, LDS atomics, one global atomic each)
@@ -122,7 +158,7 @@ __device__ __forceinline__ void pc_stage_tile(const PcDev& d, const PcShard& sh,
 }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcWalkArgs a) {
+__global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcArgsOf<MODE> a) {
     __shared__ uint64_t rs[TS][WCH + 1];
     __shared__ uint64_t rt[TS][WCH + 1];
     __shared__ unsigned long long red[3];
@@ -133,7 +169,7 @@ __global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcWalkArgs a)
     if (s0 >= sh.owned[klast]) return;
     const int f = threadIdx.x & 31, q = threadIdx.x >> 5;
     const int cond = a.condensed;
-    PcPairAcc acc[4];
+    PcAccOf<MODE> acc[4];
     int ss[4], kk[4], tt[4]; bool ok[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -143,7 +179,7 @@ __global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcWalkArgs a)
         tt[m] = ok[m] ? sh.owned[kk[m]] : 0;
         ok[m] = ok[m] && ss[m] < tt[m];
         acc[m].reset();
-        if (ok[m] && (MODE == PCW_ENUM || MODE == PCW_AAI || MODE == PCW_PEQ)) acc[m].k = a.off[sh.lbase[kk[m]] + ss[m]];
+        if (ok[m] && pc_walks_slots(MODE)) acc[m].k = a.off[sh.lbase[kk[m]] + ss[m]];
     }
     unsigned long long cells = 0, rbytes = 0;
     if (MODE == PCW_COUNT) { if (threadIdx.x < 3) red[threadIdx.x] = 0; }
@@ -199,7 +235,9 @@ __global__ __launch_bounds__(256) void k_walk(PcDev d, PcShard sh, PcWalkArgs a)
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         if (!ok[m]) continue;
-        a.out[pc_out_index(d, sh, ss[m], tt[m], kk[m], cond)] = pc_walk_value<MODE>(d, acc[m], ss[m], tt[m], a.as_distance);
+        const int64_t at = pc_out_index(d, sh, ss[m], tt[m], kk[m], cond);
+        if constexpr (MODE == PCW_JOINT) pc_walk_joint_values(d, a, acc[m], ss[m], tt[m], at);
+        else a.out[at] = pc_walk_value<MODE>(d, acc[m], ss[m], tt[m], a.as_distance);
     }
 }
 
@@ -212,6 +250,17 @@ int pc_launch_walk(int mode, const PcDev& d, const PcShard& sh, const PcWalkArgs
     if (!pc_dispatch<PCW_POCP, PCW_AF, PCW_COUNT, PCW_ENUM, PCW_AAI, PCW_PEQ>(mode, [&](auto m) { hipLaunchKernelGGL(k_walk<decltype(m)::value>, grid, block, 0, st, d, sh, a); })) {
         pc_set_error("pc_launch_walk: bad mode %d", mode); return PC_ERR_ARG;
     }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_walk launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+// k_walk<PCW_JOINT>: the condensed triangle of the shard's pairs, every array of the set at pc_out_index(..., cond = 1)
+int pc_launch_walk_joint(const PcDev& d, const PcShard& sh, const PcJointArgs& a, hipStream_t st) {
+    if (!a.condensed) { pc_set_error("pc_launch_walk_joint: condensed output only"); return PC_ERR_ARG; }
+    if (sh.nown <= 0 || d.N <= 1) return PC_OK;
+    dim3 grid(pc_tile_grid((d.N + TS - 1) / TS, (sh.nown + TS - 1) / TS)), block(256);        // (the walker's grid: pc_set_shape_of(K_WALKER))
+    hipLaunchKernelGGL(k_walk<PCW_JOINT>, grid, block, 0, st, d, sh, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("k_walk launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
     return PC_OK;
@@ -494,16 +543,16 @@ int pc_launch_walk_groups(int mode, const PcDev& d, const PcGroups& gr, int64_t 
 // ---------------------------------------------------------------------------------
 static_assert(PC_PAIR_BLOCK == 256, "k_walk_pairs runs one lane per slot of a block");
 template <int MODE>
-__global__ __launch_bounds__(256) void k_walk_pairs(PcDev d, PcPairs pr, int64_t bb, PcWalkArgs a) {
+__global__ __launch_bounds__(256) void k_walk_pairs(PcDev d, PcPairs pr, int64_t bb, PcArgsOf<MODE> a) {
     constexpr bool SETS = MODE == PCW_GCS || MODE == PCW_JC;                        // shared-pham counts: no visit
-    constexpr bool SLOTS = MODE == PCW_ENUM || MODE == PCW_AAI || MODE == PCW_PEQ;  // walks the pair's alignment slots
+    constexpr bool SLOTS = pc_walks_slots(MODE);                                    // walks the pair's alignment slots
     __shared__ unsigned long long red[3];
     const int64_t block = bb + blockIdx.x;
     const int64_t slot = block * PC_PAIR_BLOCK + threadIdx.x;
     const bool in = slot < pr.L;
     const int s = in ? pr.src[slot] : 0, t = in ? pr.tgt[slot] : 0;                 // (a lane past the list scans genome 0 against itself, and visits nothing)
     const bool ok = in && s != t;
-    PcPairAcc acc; acc.reset();
+    PcAccOf<MODE> acc; acc.reset();
     if (ok && SLOTS) acc.k = a.off[slot - pr.slot_base];
     unsigned long long cells = 0, rbytes = 0;
     if (MODE == PCW_COUNT) { if (threadIdx.x < 3) red[threadIdx.x] = 0; __syncthreads(); }
@@ -539,7 +588,10 @@ __global__ __launch_bounds__(256) void k_walk_pairs(PcDev d, PcPairs pr, int64_t
     }
     if (MODE == PCW_ENUM) return;
     if (!in) return;
-    a.out[pr.at[slot]] = ok ? pc_walk_value<MODE>(d, acc, s, t, a.as_distance) : (a.as_distance ? 0.0 : 1.0);
+    if constexpr (MODE == PCW_JOINT) {
+        if (ok) pc_walk_joint_values(d, a, acc, s, t, pr.at[slot]);
+        else pc_walk_joint_diagonal(a, pr.at[slot]);
+    } else a.out[pr.at[slot]] = ok ? pc_walk_value<MODE>(d, acc, s, t, a.as_distance) : (a.as_distance ? 0.0 : 1.0);
 }
 
 int pc_launch_walk_pairs(int mode, const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcWalkArgs& a, hipStream_t st) {
@@ -551,6 +603,17 @@ int pc_launch_walk_pairs(int mode, const PcDev& d, const PcPairs& pr, int64_t bb
             mode, [&](auto m) { hipLaunchKernelGGL(k_walk_pairs<decltype(m)::value>, grid, block, 0, st, d, pr, bb, a); })) {
         pc_set_error("pc_launch_walk_pairs: bad mode %d", mode); return PC_ERR_ARG;
     }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { pc_set_error("k_walk_pairs launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
+    return PC_OK;
+}
+
+int pc_launch_walk_pairs_joint(const PcDev& d, const PcPairs& pr, int64_t bb, int64_t be, const PcJointArgs& a, hipStream_t st) {
+    const int64_t nb = (pr.L + PC_PAIR_BLOCK - 1) / PC_PAIR_BLOCK;
+    if (bb < 0 || bb > be || be > nb || be - bb > 0x7fffffffLL) { pc_set_error("pc_launch_walk_pairs_joint: blocks [%lld, %lld) of %lld", (long long)bb, (long long)be, (long long)nb); return PC_ERR_ARG; }
+    if (be == bb || d.N < 1) return PC_OK;
+    dim3 grid((unsigned)(be - bb)), block(PC_PAIR_BLOCK);
+    hipLaunchKernelGGL(k_walk_pairs<PCW_JOINT>, grid, block, 0, st, d, pr, bb, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pc_set_error("k_walk_pairs launch: %s", hipGetErrorString(e)); return PC_ERR_HIP; }
     return PC_OK;

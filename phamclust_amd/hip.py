@@ -82,8 +82,31 @@ EXPORTS = ["pc_version", "pc_test_hooks", "pc_last_error", "pc_ctx_create", "pc_
            "pc_affinity_block", "pc_affinity_bytes", "pc_affinity_ranges", "pc_hook_slab_values", "pc_hook_rows_values", "pc_fill_rows_affinity",
            "pc_fill_rows_between", "pc_fill_hist", "pc_multi_fill_hist", "pc_fill_rows_hist", "pc_last_hist_times", "pc_hist_bins",
            "pc_hist_table_slots", "pc_hist_probes", "pc_fill_pairs", "pc_fill_pairs_dev", "pc_pair_block",
-           "pc_fill_edges_bars", "pc_nearest_of_pairs"]
+           "pc_fill_edges_bars", "pc_nearest_of_pairs",
+           "pc_fill_joint", "pc_fill_joint_dev", "pc_fill_pairs_joint", "pc_fill_pairs_joint_dev"]
 NEEDS_RESIDUES = ("aai", "peq", "aai_ppos")
+JOINT_METRICS = ("gcs", "jc", "pocp", "af", "aai", "peq")      # a joint fill's metrics, by bit of its mask (pc_metric 0 ... 5)
+
+
+def joint_mask(metrics):
+    """The C-ABI's metric set of a joint fill: bit ``METRIC_IDS[name]`` for every name of ``metrics``.  Refused here, as the library
+    would refuse the mask: an empty set, an unknown name or ``aai_ppos`` (another alignment pass), a name listed twice, and a set with
+    neither ``aai`` nor ``peq`` (the set metrics alone share no alignment pass: four millisecond fills)."""
+    if isinstance(metrics, str):
+        metrics = (metrics,)
+    names = list(metrics)
+    if not names:
+        raise ValueError("joint fill: the metric set is empty")
+    mask = 0
+    for name in names:
+        if name not in JOINT_METRICS:
+            raise ValueError(f"joint fill: unknown metric {name!r} (one of {', '.join(JOINT_METRICS)})")
+        if mask >> METRIC_IDS[name] & 1:
+            raise ValueError(f"joint fill: metric {name!r} is listed twice")
+        mask |= 1 << METRIC_IDS[name]
+    if not mask & (1 << METRIC_IDS["aai"] | 1 << METRIC_IDS["peq"]):
+        raise ValueError("joint fill: the set holds neither aai nor peq; gcs / jc / pocp / af alone are four millisecond fills (fill)")
+    return mask
 HIST_BINS = 1000001                     # pc_hist_bins(): the millionths in [0, 1]
 
 _lib = None
@@ -151,6 +174,10 @@ def load():
     L.pc_fill_pairs.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, _f64p, ctypes.POINTER(PcStats)]
     L.pc_fill_pairs_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, vp, vp, ctypes.POINTER(PcStats)]
     L.pc_pair_block.restype = ctypes.c_int
+    L.pc_fill_joint.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(PcStats)]
+    L.pc_fill_joint_dev.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(vp), vp, ctypes.POINTER(PcStats)]
+    L.pc_fill_pairs_joint.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, ctypes.POINTER(vp), ctypes.POINTER(PcStats)]
+    L.pc_fill_pairs_joint_dev.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, _i32p, _i32p, ctypes.c_int64, ctypes.POINTER(vp), vp, ctypes.POINTER(PcStats)]
     L.pc_fill_edges.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
                                 ctypes.POINTER(_f64p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PcStats)]
     L.pc_fill_edges_bars.argtypes = [vp, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_int64, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),
@@ -933,6 +960,70 @@ class Context(_SlabFills):
         self._check(self._lib.pc_fill_pairs_dev(self._h, METRIC_IDS[metric], int(bool(as_distance)), _ptr(src if src.size else one, _i32p),
                                                 _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), ctypes.c_void_p(out_ptr),
                                                 ctypes.c_void_p(stream or 0), ctypes.byref(stats) if want_stats else None))
+        return stats.as_dict() if want_stats else None
+
+    # -- joint fills: several metrics of every pair off one plan and one alignment pass ---------------------------------------------
+    @staticmethod
+    def _joint_pointers(mask, pointer_of):
+        """The C-ABI's ``out[6]``: ``pointer_of(name)`` for every metric of the mask, NULL elsewhere."""
+        out = (ctypes.c_void_p * 6)()
+        for m, name in enumerate(JOINT_METRICS):
+            if mask >> m & 1:
+                out[m] = pointer_of(name)
+        return out
+
+    def _joint_host(self, mask, n):
+        arrays = {name: np.empty(n, dtype=np.float64) for m, name in enumerate(JOINT_METRICS) if mask >> m & 1}
+        spare = np.zeros(1)                                            # (an empty array still hands the library a pointer)
+        return arrays, self._joint_pointers(mask, lambda name: (arrays[name] if n else spare).ctypes.data)
+
+    def fill_joint(self, metrics, as_distance=True, want_stats=False):
+        """Several metrics of the whole matrix off ONE plan and ONE alignment pass -> ``{name: condensed f64 vector}``, every array what
+        :meth:`fill` of that metric returns, bit for bit.  ``metrics``: names among gcs, jc, pocp, af, aai, peq, at least one of aai /
+        peq among them (:func:`joint_mask`).  The stats are the peq fill's."""
+        mask = joint_mask(metrics)
+        stats = PcStats()
+        self.ensure_residues()
+        self._invalidate_loans()
+        arrays, out = self._joint_host(mask, max(self.n_pairs, 0))
+        self._check(self._lib.pc_fill_joint(self._h, mask, int(bool(as_distance)), out, ctypes.byref(stats)))
+        return (arrays, stats.as_dict()) if want_stats else arrays
+
+    def fill_joint_dev(self, metrics, as_distance, out_ptrs, stream=None, want_stats=True):
+        """The same, left in HBM: ``out_ptrs`` maps every metric name of the set to the device address of its condensed vector."""
+        mask = joint_mask(metrics)
+        stats = PcStats()
+        self.ensure_residues()
+        out = self._joint_pointers(mask, lambda name: int(out_ptrs[name]))
+        self._check(self._lib.pc_fill_joint_dev(self._h, mask, int(bool(as_distance)), out, ctypes.c_void_p(stream or 0),
+                                                ctypes.byref(stats) if want_stats else None))
+        return stats.as_dict() if want_stats else None
+
+    def fill_pairs_joint(self, metrics, src, tgt, as_distance=True, want_stats=False):
+        """Several metrics of the pairs ``(src[k], tgt[k])`` off one plan and one alignment pass -> ``{name: f64[L]}`` in the caller's
+        order, every array what :meth:`fill_pairs` of that metric returns, bit for bit (oriented as written; repeats allowed;
+        ``src[k] == tgt[k]`` the diagonal in every array)."""
+        mask = joint_mask(metrics)
+        stats = PcStats()
+        self.ensure_residues()
+        src, tgt = self._pair_arrays(src, tgt)
+        arrays, out = self._joint_host(mask, int(src.shape[0]))
+        one = np.zeros(1, np.int32)
+        self._check(self._lib.pc_fill_pairs_joint(self._h, mask, int(bool(as_distance)), _ptr(src if src.size else one, _i32p),
+                                                  _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), out, ctypes.byref(stats)))
+        return (arrays, stats.as_dict()) if want_stats else arrays
+
+    def fill_pairs_joint_dev(self, metrics, as_distance, src, tgt, out_ptrs, stream=None, want_stats=True):
+        """The same, left in HBM: ``out_ptrs`` maps every metric name of the set to the device address of its ``f64[L]``."""
+        mask = joint_mask(metrics)
+        stats = PcStats()
+        self.ensure_residues()
+        src, tgt = self._pair_arrays(src, tgt)
+        out = self._joint_pointers(mask, lambda name: int(out_ptrs[name]))
+        one = np.zeros(1, np.int32)
+        self._check(self._lib.pc_fill_pairs_joint_dev(self._h, mask, int(bool(as_distance)), _ptr(src if src.size else one, _i32p),
+                                                      _ptr(tgt if tgt.size else one, _i32p), int(src.shape[0]), out,
+                                                      ctypes.c_void_p(stream or 0), ctypes.byref(stats) if want_stats else None))
         return stats.as_dict() if want_stats else None
 
     def fill_edges_bars(self, metric, bars, as_distance=True, slab_bytes=0, want_stats=False, borrow=False):

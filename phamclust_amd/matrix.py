@@ -7,7 +7,7 @@ of the six ``METRICS`` callables the whole N x N fill runs on the GPU through
 per-pair loop with the reference's semantics.  There is no CPU fallback for the six
 metrics: a missing library or a failing call raises.
 
-Owns the routes whose results are ``SymMatrix``es (``matrix_de_novo``, ``matrix_extend``, ``submatrices_de_novo``) and the text
+Owns the routes whose results are ``SymMatrix``es (``matrix_de_novo``, ``matrices_de_novo``, ``matrix_extend``, ``submatrices_de_novo``) and the text
 I/O of the dense matrix with its C formatter (``_text_lib``; ``edges_to_adjacency`` writes the same bytes through it, so it
 lives here).  ``SymMatrix`` itself is symmatrix.py's, what the accelerated routes share is routes.py's, and every result that
 is no dense matrix has a module under results/ -- all of their names stay readable from here.
@@ -21,11 +21,11 @@ import numpy as np
 
 from phamclust_amd.symmatrix import SymMatrix, _get_tree_order, _square_matrix  # noqa: F401
 from phamclust_amd.routes import (LAST_FILL, _CONTEXTS, _de_novo_route, _extend_fill, _extend_plan, _fill_done, _group_indices,  # noqa: F401
-                                  _guard_rows, _metric_name, _name_index, _packed_of, _slab_fill_context, default_device, get_context,
-                                  get_multi_context, in_process_devices, upload_for_fills)
+                                  _guard_rows, _joint_upload, _metric_name, _metric_names, _name_index, _packed_of, _slab_fill_context,
+                                  default_device, get_context, get_multi_context, in_process_devices, upload_for_fills)
 from phamclust_amd.results._common import _grown_positions, _live_row_pairs, _positions_without  # noqa: F401
 from phamclust_amd.results.edges import SparseEdges, _guard_edges, edges_de_novo, edges_extend, merge_edge_lists  # noqa: F401
-from phamclust_amd.results.pairs import pairs_de_novo  # noqa: F401
+from phamclust_amd.results.pairs import pairs_de_novo, pairs_joint_de_novo  # noqa: F401
 from phamclust_amd.results.components import (Components, components_de_novo, components_extend, components_from_file,  # noqa: F401
                                               components_to_file)
 from phamclust_amd.results.neighbors import (NEAREST_MAX_K, NearestNeighbors, _guard_neighbors, nearest_from_file, nearest_to_file,  # noqa: F401
@@ -130,6 +130,32 @@ def matrix_de_novo(genomes, func, cpus, as_distance=True):
         logging.debug(f"finished {', '.join(genomes[i].name for i in rows)}")
     del runner
     return matrix
+
+
+def matrices_de_novo(genomes, funcs, cpus, as_distance=True):
+    """``{metric name: matrix_de_novo(genomes, func, cpus, as_distance) for func in funcs}`` off ONE pack, ONE upload and -- when aai or
+    peq is among ``funcs`` -- ONE joint fill (``Context.fill_joint``): one plan and one alignment pass deliver every metric asked for,
+    where ``matrix_de_novo`` per metric aligns again for each of aai and peq.  Every matrix equals ``matrix_de_novo``'s cell for cell,
+    bit for bit.  With only set metrics among ``funcs`` (gcs / jc / pocp / af) there is no alignment pass to share: one upload, then the
+    single fills.  ``funcs`` are ``METRICS`` callables, each at most once; ``cpus`` is accepted for signature compatibility.  One GPU, as
+    ``submatrices_de_novo``: under a launcher (``WORLD_SIZE`` > 1) it raises.  Every refusal -- an empty list, a callable outside
+    ``METRICS``, a callable listed twice, a launcher -- comes before the first GPU call.  ``LAST_FILL`` reports the joint fill (``fills``
+    = 1, ``metrics``) or, without one, the sums over the single fills."""
+    ctx, metrics, joint, names, record = _joint_upload(genomes, funcs, "matrices_de_novo")
+    t0 = time.perf_counter()
+    if joint:
+        arrays, stats = ctx.fill_joint(metrics, as_distance=as_distance, want_stats=True)
+    else:
+        arrays, stats = {}, None
+        for name in metrics:
+            arrays[name], one = ctx.fill(name, as_distance=as_distance, want_stats=True)
+            stats = one if stats is None else dict(stats, ms_total=stats["ms_total"] + one["ms_total"], ms_reduce=stats["ms_reduce"] + one["ms_reduce"])
+    _fill_done(stats, "+".join(metrics), names, record, t0,
+               lambda stats, record, fill_s: f"{len(names)} genomes -> {record['genome_pairs']} edges x {len(metrics)} metrics ({', '.join(metrics)}) "
+                                             f"on one device: {'one joint fill' if joint else 'single fills'}+D2H {fill_s:.3f} s "
+                                             f"(kernels {stats['ms_total']:.3f} ms)",
+               genome_pairs=record["genome_pairs"], n_gpus=1, metrics=tuple(metrics), fills=1 if joint else len(metrics))
+    return {name: SymMatrix.from_condensed(names, arrays[name], is_distance=as_distance) for name in metrics}
 
 
 def _row_adjacency(source, targets, func, distance):

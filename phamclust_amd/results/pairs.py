@@ -1,6 +1,6 @@
 """The pair list: the values of the pairs a caller names, without the dense matrix.
 
-Owns ``pairs_de_novo``, the bulk form of the reference's most basic interface -- ``METRICS[metric](source, target)`` per pair
+Owns ``pairs_de_novo`` (and ``pairs_joint_de_novo``, several metrics of the same list off one alignment pass), the bulk form of the reference's most basic interface -- ``METRICS[metric](source, target)`` per pair
 (cli.py:30-35) -- over ``Context.fill_pairs``: one pack, one upload, one call for any number of listed pairs, each oriented as
 written.  ``SparseEdges.rescored`` and the ``prefilter`` of ``edges_de_novo`` (results/edges.py) are built on the same call."""
 
@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from phamclust_amd.routes import _fill_done, _name_index, upload_for_fills
+from phamclust_amd.routes import _fill_done, _joint_upload, _name_index, upload_for_fills
 
 
 def _pair_indices(names, index, pairs, caller):
@@ -59,3 +59,29 @@ def pairs_de_novo(genomes, func, pairs, as_distance=True):
                                              f"{record['genome_pairs']} on one device: sort+fill+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)",
                genome_pairs=int(stats["n_pairs"]), listed=int(src.shape[0]), n_gpus=1)
     return values
+
+
+def pairs_joint_de_novo(genomes, funcs, pairs, as_distance=True):
+    """``{metric name: pairs_de_novo(genomes, func, pairs, as_distance) for func in funcs}`` off ONE pack, ONE upload and -- when aai or
+    peq is among ``funcs`` -- ONE joint pair-list fill (``Context.fill_pairs_joint``): one plan and one alignment pass for every metric
+    asked for.  ``pairs_de_novo``'s contract for names and indices, orientation (every entry as written, under every metric), repeats
+    and the diagonal; every array equals ``pairs_de_novo``'s bit for bit.  With only set metrics among ``funcs`` there is no alignment
+    pass to share: one upload, then the single fills.  ``funcs`` are ``METRICS`` callables, each at most once.  One GPU; every refusal
+    -- ``pairs_de_novo``'s, an empty list, a callable outside ``METRICS``, a callable listed twice -- comes before the first GPU call."""
+    names = [g.name for g in genomes]
+    src, tgt = _pair_indices(names, _name_index(names), pairs, "pairs_joint_de_novo")
+    ctx, metrics, joint, names, record = _joint_upload(genomes, funcs, "pairs_joint_de_novo")
+    t0 = time.perf_counter()
+    if joint:
+        arrays, stats = ctx.fill_pairs_joint(metrics, src, tgt, as_distance=as_distance, want_stats=True)
+    else:
+        arrays, stats = {}, None
+        for name in metrics:
+            arrays[name], one = ctx.fill_pairs(name, src, tgt, as_distance=as_distance, want_stats=True)
+            stats = one if stats is None else dict(stats, ms_total=stats["ms_total"] + one["ms_total"], ms_reduce=stats["ms_reduce"] + one["ms_reduce"])
+    _fill_done(stats, "+".join(metrics), names, record, t0,
+               lambda stats, record, fill_s: f"{len(names)} genomes, {src.shape[0]} listed pairs ({stats['n_pairs']} off the diagonal) of "
+                                             f"{record['genome_pairs']} x {len(metrics)} metrics ({', '.join(metrics)}) on one device: "
+                                             f"sort+{'one joint fill' if joint else 'single fills'}+D2H {fill_s:.3f} s (kernels {stats['ms_total']:.3f} ms)",
+               genome_pairs=int(stats["n_pairs"]), listed=int(src.shape[0]), n_gpus=1, metrics=tuple(metrics), fills=1 if joint else len(metrics))
+    return {name: arrays[name] for name in metrics}

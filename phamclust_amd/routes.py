@@ -63,6 +63,33 @@ def _metric_name(func):
     return metrics.ACCELERATED.get(func)
 
 
+def _metric_names(funcs, caller):
+    """The metric names of ``funcs``, callables of ``METRICS``, in their order -- what the joint routes (``matrices_de_novo``,
+    ``pairs_joint_de_novo``) check before any GPU call: ValueError for an empty list, a callable outside the six, a callable listed twice."""
+    funcs = list(funcs)
+    if not funcs:
+        raise ValueError(f"{caller}: funcs is empty; name at least one of the six METRICS callables")
+    names = []
+    for k, func in enumerate(funcs):
+        name = _metric_name(func)
+        if name is None:
+            raise ValueError(f"{caller}: funcs[{k}] is none of the six METRICS callables -- a joint fill runs on the GPU only and has no CPU route")
+        if name in names:
+            raise ValueError(f"{caller}: metric '{name}' is listed twice")
+        names.append(name)
+    return names
+
+
+def _joint_upload(genomes, funcs, caller):
+    """``upload_for_fills`` for the metrics of ``funcs`` (checked by ``_metric_names`` first): the residues go along when aai or peq is
+    among them.  Returns ``(context, metric names, whether one joint fill serves them, genome names, record)``."""
+    funcs = list(funcs)
+    metrics = _metric_names(funcs, caller)
+    aligned = [k for k, name in enumerate(metrics) if name in ("aai", "peq")]
+    ctx, _, names, record = upload_for_fills(genomes, funcs[aligned[0] if aligned else 0], caller, advice="a joint fill has no CPU route")
+    return ctx, metrics, bool(aligned), names, record
+
+
 LAST_FILL = {}          # what the last accelerated matrix_de_novo did: the pipeline's log line reads it
 
 

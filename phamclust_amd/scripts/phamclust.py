@@ -26,7 +26,7 @@ from phamclust_amd.cli import METRICS, parse_args
 from phamclust_amd.clustering import cluster_by_component, hierarchical_clustering
 from phamclust_amd.genome import Genome
 from phamclust_amd.heatmap import CSS_COLORS, draw_heatmap
-from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, PairDistribution, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_extend, between_from_file, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, distribution_de_novo, edges_de_novo, edges_to_adjacency, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
+from phamclust_amd.matrix import Components, GroupAffinity, GroupLinkage, PairDistribution, SparseEdges, SymMatrix, affinity_de_novo, between_de_novo, between_extend, between_from_file, between_to_file, components_de_novo, components_extend, components_from_file, components_to_file, distribution_de_novo, edges_de_novo, edges_to_adjacency, matrices_de_novo, matrix_de_novo, matrix_extend, matrix_from_squareform, matrix_to_adjacency, matrix_to_squareform, nearest_from_file, nearest_to_file, neighbors_de_novo, neighbors_extend, own_similarity_text, placement_de_novo, placement_report, stored_fit_from_file, tree_de_novo, tree_extend, tree_from_file, tree_to_file, upload_for_fills
 from phamclust_amd.pack import load_tsv_genomes, packed_behind
 from phamclust_amd import startup
 
@@ -141,6 +141,8 @@ class _Run:
         self.extend = None                    # --extend FILE: a distance matrix over a subset of the genomes
         self.grow_nearest = None              # --grow-nearest FILE: a nearest_<metric>.tsv over a subset of the genomes
         self.grow = None                      # --grow FILE: a tree_<metric>.tsv / components_<metric>.tsv over a subset of the genomes
+        self.also = []                        # --also: further metrics beside -m's, off the same joint fill
+        self.also_matrices = {}               # ... their distance matrices, once stage 2 has run (distances_also)
 
     @staticmethod
     def _dir(path, fresh=False):
@@ -239,6 +241,54 @@ class _Run:
             sys.exit(1)
         return matrix
 
+    # 2, --also
+    def distances_also(self, cpus):
+        """Stage 2 with ``--also``: the distance matrices of -m's metric and of the ``--also`` metrics.  Those with a cache file under
+        ``02_distmats/`` are read; the rest come from ONE ``matrices_de_novo`` call -- one pack, one upload, one joint fill when aai or peq
+        is among them -- and each is cached as ``<metric>_distance_matrix.tsv``, the file a ``-m <metric>`` run caches.  Returns -m's matrix,
+        on which the pipeline clusters exactly as without ``--also``; the others wait in ``also_matrices`` for ``finish``.  One process."""
+        wanted = [self.metric] + self.also
+        self.banner(2, f"{' + '.join(wanted)} distance matrices")
+        folder = self._dir(self.cache / "02_distmats")
+        found, missing = {}, []
+        for name in wanted:
+            cached = folder / f"{name}_distance_matrix.tsv"
+            if cached.is_file():
+                t0 = time.perf_counter()
+                found[name] = matrix_from_squareform(cached)
+                log.info(f"read cached {name} matrix in {time.perf_counter() - t0:.3f} s")
+            else:
+                missing.append(name)
+        if missing:
+            t0 = time.perf_counter()
+            filled = matrices_de_novo(self.genomes, [METRICS[name] for name in missing], cpus)
+            wall = time.perf_counter() - t0
+            st = _matrix.LAST_FILL
+            n = len(self.genomes)
+            line = (f"filled {len(missing)} {n} x {n} matrices ({', '.join(missing)}) from {st.get('fills', 1)} fill(s) on 1 GPU in {wall:.3f} s "
+                    f"(pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, fill+D2H {st.get('fill_s', 0.0):.3f}; kernels "
+                    f"{st.get('ms_total', 0.0):.3f} ms, of which the walk that writes them {st.get('ms_reduce', 0.0):.3f} ms)")
+            if st.get("n_cells"):
+                line += (f": {st['n_alignments']} alignments ({st.get('n_distinct_alignments', 0)} distinct), {st['n_cells']:.3e} DP cells, "
+                         f"{st.get('n_chunks', 1)} chunk(s), ONE alignment pass for all of them")
+            log.info(line)
+            noted = [name for name in missing if name in _metrics.PARITY_NOTE]
+            if noted:                                       # SURVEY 8c: say it wherever these numbers leave the program
+                log.info(f"parity: {_metrics.parity_note(noted[0])}")
+            for name in missing:
+                matrix_to_squareform(filled[name], folder / f"{name}_distance_matrix.tsv", lower_triangle=True)
+                found[name] = filled[name]
+        for name in wanted:
+            if not found[name].is_distance:
+                found[name].invert()
+            edges, diagonal, unfilled = check_matrix_integrity(found[name])
+            if edges or diagonal or unfilled:
+                log.error(f"{name} matrix failed integrity checks: edge count off by {edges}, diagonal off by {diagonal}, {unfilled} unfilled")
+                print("matrix validation failed - check log for details")
+                sys.exit(1)
+        self.also_matrices = {name: found[name] for name in self.also}
+        return found[self.metric]
+
     # 2, --adjacency-only
     def adjacency(self, similarity, prefilter=False):
         """Stage 2 as an edge-list fill: the pairs of similarity >= ``similarity`` (None: every non-zero one) straight into
@@ -268,23 +318,33 @@ class _Run:
     # 2, --pairs
     def pairs(self, listing):
         """Stage 2 as a pair-list fill: the pairs ``listing`` names (``read_pairs_file``), each oriented as written, into
-        ``pairwise_<metric>_pairs.tsv`` as ``source<TAB>target<TAB>similarity`` in the listing's order.  Nothing else is computed."""
-        self.banner(2, f"{self.metric} of the listed pairs (pair-list fill)")
+        ``pairwise_<metric>_pairs.tsv`` as ``source<TAB>target<TAB>similarity`` in the listing's order.  Nothing else is computed.  With
+        ``--also``: ONE joint pair-list fill for -m's metric and the ``--also`` metrics, and one such file per metric."""
+        wanted = [self.metric] + self.also
+        self.banner(2, f"{' + '.join(wanted)} of the listed pairs (pair-list fill)")
         t0 = time.perf_counter()
         named = read_pairs_file(listing)
-        values = _matrix.pairs_de_novo(self.genomes, METRICS[self.metric], named, as_distance=False)
+        if self.also:
+            values = _matrix.pairs_joint_de_novo(self.genomes, [METRICS[name] for name in wanted], named, as_distance=False)
+        else:
+            values = {self.metric: _matrix.pairs_de_novo(self.genomes, METRICS[self.metric], named, as_distance=False)}
         st = _matrix.LAST_FILL
         log.info(f"{len(named):,} listed pairs ({st.get('n_pairs', 0):,} off the diagonal) of {len(self.genomes):,} genomes on 1 GPU in "
                  f"{time.perf_counter() - t0:.3f} s (pack {st.get('pack_s', 0.0):.3f}, upload {st.get('upload_s', 0.0):.3f}, sort+fill+D2H "
-                 f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms)")
-        if self.metric in _metrics.PARITY_NOTE:
-            log.info(f"parity: {_metrics.parity_note(self.metric)}")
-        target = self.outdir / f"pairwise_{self.metric}_pairs.tsv"
-        with open(target, "w") as handle:
-            for (source, other), value in zip(named, values.tolist()):
-                handle.write(f"{source}\t{other}\t{value:.6f}\n")
-        log.info(f"wrote {target.name}")
-        return values
+                 f"{st.get('fill_s', 0.0):.3f}; kernels {st.get('ms_total', 0.0):.3f} ms)"
+                 + (f"; {len(wanted)} metrics from {st.get('fills', 1)} fill(s): {st.get('n_alignments', 0):,} alignments "
+                    f"({st.get('n_distinct_alignments', 0):,} distinct) in {st.get('n_chunks', 1)} chunk(s), ONE alignment pass for all of them"
+                    if self.also else ""))
+        noted = [name for name in wanted if name in _metrics.PARITY_NOTE]
+        if noted:
+            log.info(f"parity: {_metrics.parity_note(noted[0])}")
+        for name in wanted:
+            target = self.outdir / f"pairwise_{name}_pairs.tsv"
+            with open(target, "w") as handle:
+                for (source, other), value in zip(named, values[name].tolist()):
+                    handle.write(f"{source}\t{other}\t{value:.6f}\n")
+            log.info(f"wrote {target.name}")
+        return values[self.metric]
 
     # 2, --components-only
     def components(self, similarity):
@@ -768,6 +828,10 @@ class _Run:
             shutil.rmtree(old) if old.is_dir() else old.unlink()
         matrix_to_squareform(matrix, self.outdir / f"pairwise_{self.metric}_similarities.tsv")
         matrix_to_adjacency(matrix, self.outdir / f"pairwise_{self.metric}_adjacency.tsv", skip_zero=True)
+        for name, other in self.also_matrices.items():         # --also: the same square under each further metric, in the same node order
+            other.reorder(list(matrix.nodes))
+            other.invert()
+            matrix_to_squareform(other, self.outdir / f"pairwise_{name}_similarities.tsv")
         shutil.copytree(self.stage, self.outdir, dirs_exist_ok=True)
         shutil.rmtree(self.stage)
         if rm_tmp:
@@ -797,7 +861,7 @@ class _Run:
 def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, clu_distance, clu_linkage, sub_distance,
               sub_linkage, k_min, no_sub, colors, midpoint, cpus, rm_tmp, debug, extend=None, adjacency_only=False, edge_thresh=None,
               components_only=False, no_matrix=False, tree=False, grow=None, cluster_table=False, cluster_fit=False, place=None, grow_table=None, join_min=None,
-              distribution_only=False, distribution=False, pairs=None, prefilter=False, nearest_bound=False, grow_nearest=None, nearest=None):
+              distribution_only=False, distribution=False, pairs=None, prefilter=False, nearest_bound=False, also=None, grow_nearest=None, nearest=None):
     """Same signature as the reference's ``phamclust()`` (distances, not similarities, for the thresholds); ``extend``: the
     distance matrix of an earlier run over a subset of the genomes (``--extend``), or None; ``adjacency_only``: stop after an
     edge-list fill of the pairs of similarity >= ``edge_thresh`` (None: every non-zero one) and write only the adjacency file;
@@ -821,7 +885,17 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     pipeline only, on either route); ``pairs``: stop after a pair-list fill of the pairs that file names and write only
     ``pairwise_<metric>_pairs.tsv`` (``--pairs``); ``prefilter``: with ``adjacency_only``, peq and an ``edge_thresh``, the same adjacency
     file from the af edge list's pairs alone (``--prefilter``); ``nearest_bound``: with ``nearest`` and peq, the same lists from the
-    pairs the af bound leaves open (``--af-bound``)."""
+    pairs the af bound leaves open (``--af-bound``); ``also``: further metric names beside ``metric``, filled off the same alignment pass
+    (``--also``): on the dense route each is cached and written as ``pairwise_<name>_similarities.tsv`` while the clustering runs on
+    ``metric``'s matrix alone; with ``pairs`` one ``pairwise_<name>_pairs.tsv`` each."""
+    also = list(also or [])
+    if also:
+        if any(name not in METRICS for name in also) or metric in also or len(set(also)) != len(also):
+            raise ValueError(f"also names metrics among {', '.join(METRICS)} beside '{metric}', each once")
+        if (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
+                grow_nearest is not None or place is not None or distribution_only or prefilter or nearest_bound):
+            raise ValueError("also goes with the dense route or with pairs; it cannot be combined with adjacency_only, components_only, no_matrix, "
+                             "tree, nearest, extend, grow, grow_nearest, place, distribution_only, prefilter or nearest_bound")
     if pairs is not None and (adjacency_only or components_only or no_matrix or tree or nearest is not None or extend is not None or grow is not None or
                               place is not None or cluster_table or cluster_fit or distribution or distribution_only or prefilter):
         raise ValueError("pairs cannot be combined with adjacency_only, components_only, no_matrix, tree, nearest, extend, grow, place, cluster_table, "
@@ -882,6 +956,8 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
         settings["adjacency"] = "only" + ("" if edge_thresh is None else f", similarity >= {edge_thresh}") + (" (--prefilter: behind the af bound)" if prefilter else "")
     if pairs is not None:
         settings["pairs"] = f"only, the pairs listed in {pairs}"
+    if also:
+        settings["also"] = f"{', '.join(also)} (--also: off the same alignment pass)"
     if no_matrix:
         settings["matrix"] = "none (--no-matrix: components and groups fills)"
     if components_only:
@@ -913,6 +989,7 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
     run.extend = extend
     run.grow = grow
     run.grow_nearest = grow_nearest
+    run.also = also
     run.rank, run.world = distributed.ensure_process_group()      # (0, 1) unless started by torch.distributed.run
     _mark("torch_import_and_process_group")
     run.read(infile, is_genome_dir)
@@ -985,7 +1062,10 @@ def phamclust(infile, outdir, is_genome_dir, metric, nr_distance, nr_linkage, cl
             sys.exit(1)
         multi, single = run.clusters_no_matrix((nr_distance, nr_linkage), (clu_distance, clu_linkage))
     else:
-        matrix = run.distances(cpus)
+        if also and run.world > 1:
+            log.error("--also is a one-GPU call: run it in one process, not under a launcher")
+            sys.exit(1)
+        matrix = run.distances_also(cpus) if also else run.distances(cpus)
         if matrix is None:                    # ranks other than 0 are done once their shard is gathered
             return
         multi, single = run.clusters(matrix, (nr_distance, nr_linkage), (clu_distance, clu_linkage))
@@ -1146,7 +1226,8 @@ def _run(args, argv):
                   adjacency_only=args.adjacency_only, edge_thresh=args.edge_thresh, components_only=args.components_only, no_matrix=args.no_matrix,
                   nearest=args.nearest, tree=args.tree, grow=args.grow, grow_nearest=args.grow_nearest, cluster_table=args.cluster_table,
                   cluster_fit=args.cluster_fit, place=args.place, grow_table=args.grow_table, join_min=args.join_min,
-                  distribution_only=args.distribution_only, distribution=args.distribution, pairs=args.pairs, prefilter=args.prefilter, nearest_bound=args.af_bound)
+                  distribution_only=args.distribution_only, distribution=args.distribution, pairs=args.pairs, prefilter=args.prefilter, nearest_bound=args.af_bound,
+                  also=args.also)
     finally:
         if rank == 0:
             TIMELINE.mark("clustering_and_outputs")
